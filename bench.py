@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s of the HIP path tracer on BASELINE.json's headline configuration.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints ONE JSON line: `value` (Msamples/s over the timed steps),
+`ms_per_step`, the launch configuration and the roofline figures that follow from the timed kernel and the committed
+PMC profile.  `--full` adds what takes runs of its own: the frame delivered to a host buffer (rt_render), the general
+spheres-only kernel on the headline workload, the walk statistics of the -DRT_STATS diagnostic build and the CPU
+baseline (`--no-walk-stats` / `--no-cpu-baseline` drop the last two again).  `--dump-outputs DIR` writes what the last
+timed step computed -- `image.npy` (float32: the [H, W, 3] frame, or the packed [entries, 3] shard of a shard workload)
+and `rays_shot.npy` (float64) -- after the timed steps; the inputs are seeded, so equal arguments give equal inputs.
 
 One "step" = one complete render of the workload's frame, scene already resident in HBM.  The default
 workload is BASELINE.json configs[1]: scenes/rtweekend1.ssml at 1920x1080, 1024 spp, MIS, max_depth 50 =
@@ -29,7 +37,7 @@ fixed).  Rank 0 prints ONE JSON line.
     counters saw as `traffic`.
 SURVEY 8(d)'s algorithmic bytes (reference traversal semantics, counted by the oracle) stay as a secondary
 field; they are requested bytes, not HBM bytes, and never a roofline fraction.
-`cpu_baseline` times the CPU oracle (oracle/, a restatement of the reference's algorithm -- the Rust binary
+`cpu_baseline` (`--full`) times the CPU oracle (oracle/, a restatement of the reference's algorithm -- the Rust binary
 cannot be built in this pipeline) on this box's host cores on a bounded sample of the same workload.  The
 oracle is used for nothing else here.
 """
@@ -185,6 +193,14 @@ def cpu_baseline(pkg, name, scene_desc, camera_params, target_seconds=20.0):
                       f", {spp} of {w.get('full_spp', w['spp'])} spp, MIS, max_depth 50, {dt:.1f} s of CPU work"}
 
 
+def dump_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64, as given)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def run_cfg1(args):
     """BASELINE configs[0]: rtweekend1 at 400x225x64 on the CPU path (the oracle; no GPU), with max_depth 8 as
     BASELINE says and 50 as the reference has it (integrators/mod.rs:7) -- both reported."""
@@ -206,9 +222,13 @@ def run_cfg1(args):
             s.render(cam, o, n_threads=cores)
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            _, rays = s.render(cam, o, n_threads=cores)
+            img, rays = s.render(cam, o, n_threads=cores)
         dt = (time.perf_counter() - t0) / args.steps
         res[depth] = {"Msamples_per_s": W * H * SPP / dt / 1e6, "ms_per_step": dt * 1e3, "rays_shot": int(rays)}
+        if depth == 8 and args.dump_outputs:  # the run `value` times
+            import numpy as np
+            dump_outputs(args.dump_outputs, {"image": np.asarray(img, dtype=np.float32).reshape(H, W, 3),
+                                             "rays_shot": np.array([rays], dtype=np.float64)})
     out = {"metric": "Msamples/s on rtweekend1.ssml 400x225x64spp (CPU oracle)", "value": res[8]["Msamples_per_s"], "unit": "Msamples/s",
            "n_gpus": 0, "steps": args.steps, "warmup": args.warmup, "ms_per_step": res[8]["ms_per_step"], "higher_is_better": True,
            "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -297,6 +317,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: host-buffer frame, general kernel, walk statistics, CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's frame and ray count as DIR/image.npy and DIR/rays_shot.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-walk-stats", action="store_true")
     ap.add_argument("--workload", choices=sorted(WORKLOADS) + ["cfg1"], default="rtweekend1")
@@ -423,10 +447,15 @@ def main():
     elapsed = float(t.item())
     rays = D.reduce_rays(d_rays.clone().to(comm_device), world)
     launch = scene.last_launch_info()
+    if args.dump_outputs and rank == 0:  # before any untimed leg below reuses the buffers
+        import numpy as np
+        out_img = frame.view(HEIGHT, WIDTH, 3) if gather is not None else (shard.view(HEIGHT, WIDTH, 3) if abi_devices else shard)
+        dump_outputs(args.dump_outputs, {"image": out_img.cpu().numpy().astype(np.float32),
+                                         "rays_shot": np.array([int(rays.item())], dtype=np.float64)})
     # SURVEY 8(d) defines the metric on rt_render: the frame delivered to a HOST buffer (+ one D2H of W x H x 12 bytes and the
-    # host synchronisation).  Timed here next to the device-resident figure above, on a few untimed-for-`value` steps.
+    # host synchronisation).  Timed here (--full) next to the device-resident figure above, on a few untimed-for-`value` steps.
     host_frame_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         scene.render(cam, sopts)
         n_host = max(2, min(5, args.steps))
         t0 = time.perf_counter()
@@ -437,9 +466,9 @@ def main():
     # What the kernels that are NOT compiled for this scene's own tree and materials deliver on the same workload: the headline
     # workload's tree is one node over two single-sphere leaves, for which the library picks rt::FeatPair; RT_TUNE_FEATURE_SET = 0
     # names the general spheres-only set instead (same pixels: tests/test_gpu_parity.py::test_every_kernel_variant...).  Untimed
-    # for `value`: a few extra steps on a second handle of the same scene.
+    # for `value`: a few extra steps on a second handle of the same scene (--full).
     general = None
-    if world == 1 and name == "rtweekend1" and not abi_devices:
+    if world == 1 and name == "rtweekend1" and not abi_devices and args.full:
         g2 = hb.HipScene(scene_desc, device=local_rank)
         g2.set_tuning(abi.RT_TUNE_FEATURE_SET, 0)
         best = None
@@ -527,7 +556,7 @@ def main():
                                  "line each, 7.3 TB/s (profiles/r04h_random_fetch_microbench.txt); blended_ceiling = harmonic blend of the two at the "
                                  "kernel's own L2 hit rate (a model: the fractions are printed unclamped)"})
         ws = None
-        if world == 1 and not args.no_walk_stats:
+        if world == 1 and args.full and not args.no_walk_stats:
             ws, ws_error = walk_stats(name)
             if ws_error:
                 roof["walk_stats_error"] = ws_error
@@ -603,7 +632,7 @@ def main():
                        "scene_build_s": build_s},
             "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pkg, name, scene_desc, camera_params)
         print(json.dumps(out), flush=True)
     if use_dist:

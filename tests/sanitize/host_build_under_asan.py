@@ -1,5 +1,6 @@
-import sys, ctypes as C
-sys.path.insert(0,"/root/repo"); sys.path.insert(0,"/root/repo/oracle"); sys.path.insert(0,"/root/repo/tests")
+import os, sys, ctypes as C
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import oracle as O, scenes, numpy as np
 lib=C.CDLL("/tmp/rt_sanitize/libhostbuild_asan.so")
 abi=scenes.abi

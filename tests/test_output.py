@@ -54,14 +54,15 @@ def _read_png(path):
     return rows[:, 1:].reshape(h, w, 3)
 
 
-def test_png_and_ppm_round_trip(hb, tmp_path):
+def test_png_and_ppm_round_trip(hb, tmp_path, monkeypatch):
+    monkeypatch.chdir(tmp_path)  # the file name may hold one '.' only, the directory above it included: save by relative name
     rng = np.random.default_rng(1)
     for (h, w) in ((36, 64), (300, 250)):  # the second spans several 64 KiB stored-deflate blocks
         img = rng.uniform(0, 1, (h, w, 3)).astype(np.float32)
         want = hb.output_rgb8(img, 2.2)
-        hb.save_image(str(tmp_path / "a.png"), img, 2.2)
+        hb.save_image("a.png", img, 2.2)
         assert np.array_equal(_read_png(str(tmp_path / "a.png")), want)
-        hb.save_image(str(tmp_path / "a.ppm"), img, 2.2)
+        hb.save_image("a.ppm", img, 2.2)
         data = open(tmp_path / "a.ppm", "rb").read()
         header = f"P6\n{w} {h}\n255\n".encode()
         assert data.startswith(header) and np.array_equal(np.frombuffer(data[len(header):], np.uint8).reshape(h, w, 3), want)
@@ -100,16 +101,17 @@ def _read_exr(path):
     return img
 
 
-def test_exr_bmp_tiff(hb, tmp_path):
+def test_exr_bmp_tiff(hb, tmp_path, monkeypatch):
+    monkeypatch.chdir(tmp_path)  # exactly one '.' in the whole file name: save by relative name
     rng = np.random.default_rng(2)
     img = rng.uniform(0, 4, (37, 53, 3)).astype(np.float32)  # odd width: BMP row padding
     img[3, 5] = (np.inf, 1e-30, 0.0)
-    hb.save_image(str(tmp_path / "a.exr"), img, 2.2)
+    hb.save_image("a.exr", img, 2.2)
     assert _read_exr(str(tmp_path / "a.exr")).tobytes() == img.tobytes()  # gamma ignored, floats untouched
     want = hb.output_rgb8(img, 2.2)
     Image = pytest.importorskip("PIL.Image")
     for ext in ("bmp", "tiff", "png"):
-        hb.save_image(str(tmp_path / f"a.{ext}"), img, 2.2)
+        hb.save_image(f"a.{ext}", img, 2.2)
         with Image.open(tmp_path / f"a.{ext}") as im:
             assert im.mode == "RGB" and im.size == (53, 37)
             assert np.array_equal(np.asarray(im), want), ext
