@@ -452,6 +452,41 @@ int rt_check_hit(rt_scene *scene, const rt_ray_desc *rays, uint64_t n_rays, rt_h
 int rt_check_hit_index(rt_scene *scene, const rt_ray_desc *rays, const uint64_t *object_index, uint64_t n_rays,
                        rt_hit_record *out);
 
+/* ---- first-hit auxiliary buffers ("AOVs": what a denoiser, compositing or picking needs besides the noisy mean) over the SAME
+ * camera rays rt_render traces for passes [sample_begin, sample_begin + samples_per_pixel): pass p of pixel (x, y) uses the first
+ * two draws of the stream (seed, y*width + x, p) for its jitter, exactly as the render does.  Any pointer may be NULL (channel not
+ * produced); all NULL -> RT_ERR_INVALID_ARGUMENT.  FRAME layout, row-major, y down.
+ *
+ * Per pass, for the ray Ray::new(origin, lower_left + horizontal*u + vertical*v - origin) with wo its normalised direction:
+ *   hit:   normal = Hit.normal (what rt_check_hit reports for that ray), depth = Hit.t, albedo = colour_value(wo, hit.point)
+ *          of the material's texture -- times the `albedo` parameter for a Lambertian (lambertian.rs:47-49,
+ *          eval_over_scattering_pdf); Emit, Reflect, Refract and TrowbridgeReitz give the texture colour alone (no strength)
+ *   miss:  albedo = the sky material's texture colour in direction wo at point (0, 0, 0), with no factor whatever the material;
+ *          normal = 0; the pass counts toward neither depth nor coverage
+ * Fold: albedo and normal are f32 sums in pass order starting from +0, divided by (float)samples_per_pixel once (the normal is
+ * not renormalised); coverage = (float)hits / (float)samples_per_pixel; depth = (sum of t over the passes that hit, in pass
+ * order, from +0) / (float)hits, or 0 when no pass hit.
+ * IDs come from pass sample_begin alone: primitive = index in rt_scene_desc.primitives (not BVH order), material = the caller's
+ * material index; both UINT32_MAX on a miss.  A scene of >= 2^32 - 1 primitives returns RT_ERR_UNSUPPORTED when `primitive`
+ * is asked for.  The first call on a scene that asks for `primitive` uploads the slot -> index table (synchronously).
+ * Options: render_method, max_depth, rr_threshold and sample_split are ignored; output_layout must be RT_LAYOUT_FRAME and
+ * shard_count 1 (else RT_ERR_UNSUPPORTED); width and height >= 2.  The traversal follows the scene's mode (rt_scene_set_traversal;
+ * every mode gives the same bytes).  A host-only scene returns RT_ERR_NO_DEVICE; a multi-device head (rt_scene_create_multi)
+ * runs the pass on devices[0] alone.  No side effects: what rt_last_kernel_ms, rt_last_launch_info and a following rt_render
+ * return is unchanged.
+ * rt_render_aov: HOST buffers, blocking.  rt_render_aov_device: DEVICE buffers on the scene's GPU, asynchronous on hip_stream. */
+typedef struct rt_aov_buffers {
+	float *albedo;       /* w*h*3 */
+	float *normal;       /* w*h*3 */
+	float *depth;        /* w*h   */
+	float *coverage;     /* w*h   */
+	uint32_t *primitive; /* w*h   */
+	uint32_t *material;  /* w*h   */
+} rt_aov_buffers;
+int rt_render_aov(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_aov_buffers *host_out);
+int rt_render_aov_device(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_aov_buffers *device_out,
+                         void *hip_stream);
+
 /* Division by a constant a launch knows beforehand (image size - 1, sky table resolution, pi, 2 pi): the kernels replace `x / c` by
  * two fma steps on rc = RN(1 / c) where -- and only where -- the host has verified, by enumerating all 2^23 significands of x, that
  * this returns the bits of the division (csrc/rt_build.cpp verified_reciprocal, csrc/rt_lean.h div_by_verified).  This call runs that

@@ -299,6 +299,36 @@ inline std::vector<uint8_t> render_rgb8(const RenderOptions &o, const SimpleCame
 	return out;
 }
 
+// First-hit auxiliary buffers of the passes [sample_begin, sample_begin + o.samples_per_pixel) -- the camera rays a render with
+// the same seed traces (semantics: rt_hip.h rt_aov_buffers).  Every channel is produced; row-major, y down.
+struct AovBuffers {
+	std::vector<float> albedo, normal; // w*h*3
+	std::vector<float> depth, coverage; // w*h
+	std::vector<uint32_t> primitive, material; // w*h; UINT32_MAX where pass sample_begin missed
+};
+inline AovBuffers render_aov(const RenderOptions &o, const SimpleCamera &camera, const Bvh &bvh, uint64_t seed = 1,
+                             uint64_t sample_begin = 0)
+{
+	rt_render_opts opts;
+	rt_render_opts_default(&opts);
+	opts.width = o.width;
+	opts.height = o.height;
+	opts.samples_per_pixel = o.samples_per_pixel;
+	opts.sample_begin = sample_begin;
+	opts.seed = seed;
+	const size_t n = (size_t)o.width * o.height;
+	AovBuffers a;
+	a.albedo.resize(n * 3);
+	a.normal.resize(n * 3);
+	a.depth.resize(n);
+	a.coverage.resize(n);
+	a.primitive.resize(n);
+	a.material.resize(n);
+	const rt_aov_buffers b = {a.albedo.data(), a.normal.data(), a.depth.data(), a.coverage.data(), a.primitive.data(), a.material.data()};
+	check(rt_render_aov(bvh.raw(), &camera.raw(), &opts, &b));
+	return a;
+}
+
 struct Presentation { // what render_tui keeps: the mean image and the ray total (src/main.rs:160-173)
 	SamplerProgress sampler_progress;
 	Presentation(uint64_t pixel_num) : sampler_progress(pixel_num, 3) {}

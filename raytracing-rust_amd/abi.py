@@ -201,6 +201,20 @@ class LaunchInfo(C.Structure):  # rt_launch_info
     ]
 
 
+class AovBuffers(C.Structure):  # rt_aov_buffers
+    _fields_ = [
+        ("albedo", C.POINTER(C.c_float)),
+        ("normal", C.POINTER(C.c_float)),
+        ("depth", C.POINTER(C.c_float)),
+        ("coverage", C.POINTER(C.c_float)),
+        ("primitive", C.POINTER(C.c_uint32)),
+        ("material", C.POINTER(C.c_uint32)),
+    ]
+
+
+AOV_CHANNELS = ("albedo", "normal", "depth", "coverage", "primitive", "material")
+AOV_NO_ID = 0xFFFFFFFF  # primitive / material of a pass that missed
+
 # rt_presentation_update: int (*)(void *data, const rt_sampler_progress *, uint64_t samples_done)
 PresentationUpdate = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(SamplerProgressC), C.c_uint64)
 
@@ -219,6 +233,7 @@ EXPECTED_SIZES = {
     "rt_bvh_node": (BvhNode, 56),
     "rt_sampler_progress": (SamplerProgressC, 32),
     "rt_launch_info": (LaunchInfo, 224),
+    "rt_aov_buffers": (AovBuffers, 48),
 }
 
 # every symbol include/rt_hip.h declares
@@ -261,6 +276,8 @@ EXPORTED_SYMBOLS = [
     "rt_check_hit",
     "rt_check_hit_index",
     "rt_selftest_lean",
+    "rt_render_aov",
+    "rt_render_aov_device",
 ]
 
 

@@ -19,6 +19,7 @@
 #include <dlfcn.h>
 #include "rt_build.h"
 #include "rt_types.h"
+#include "rt_aov.h"
 
 namespace rt {
 size_t render_lds_bytes(const DevScene &S, bool sky_lds, bool scene_lds, uint32_t waves_per_block, uint32_t stack_cap);
@@ -139,6 +140,7 @@ struct rt_scene {
 	std::string gather_note;               // why (rt_scene_gather_info)
 	hipEvent_t ev_gathered = nullptr;      // head: the last render's gather + scatter have read every member's shard
 	bool gathered_once = false;
+	uint32_t *d_prim_desc = nullptr;       // rt_render_aov: BVH slot -> rt_scene_desc index, uploaded on first use (in `allocations`)
 };
 
 template <class T> static int upload(rt_scene *s, const T *src, size_t count, const T **dst)
@@ -2056,6 +2058,133 @@ int rt_selftest_lean(int device, uint64_t n_per_thread, uint64_t seed, uint64_t 
 	if (e != hipSuccess)
 		return hip_fail(e, "selftest");
 	return RT_OK;
+}
+
+
+// ---- first-hit AOV buffers (rt_aov.hip) ----
+// argument checks of both entry points, the device last (so that a host-only scene reports bad arguments as such)
+static int aov_check(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *b, uint32_t *mask)
+{
+	if (!s || !camera || !o || !b)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	*mask = (b->albedo ? kAovAlbedo : 0u) | (b->normal ? kAovNormal : 0u) | (b->depth ? kAovDepth : 0u) |
+	        (b->coverage ? kAovCoverage : 0u) | (b->primitive ? kAovPrimitive : 0u) | (b->material ? kAovMaterial : 0u);
+	if (*mask == 0u)
+		return fail(RT_ERR_INVALID_ARGUMENT, "rt_aov_buffers: every channel is NULL");
+	if (o->width < 2 || o->height < 2)
+		return fail(RT_ERR_INVALID_ARGUMENT, "width and height must be >= 2 (u and v divide by W-1 and H-1)");
+	if (o->width * o->height >= (1ull << 31))
+		return fail(RT_ERR_UNSUPPORTED, "image larger than 2^31 pixels");
+	if (o->samples_per_pixel == 0 || o->samples_per_pixel >= (1ull << 32))
+		return fail(RT_ERR_INVALID_ARGUMENT, "samples_per_pixel must be in [1, 2^32)");
+	if (o->output_layout != RT_LAYOUT_FRAME)
+		return fail(RT_ERR_UNSUPPORTED, "AOV buffers are produced in RT_LAYOUT_FRAME only");
+	if (o->shard_count != 1)
+		return fail(RT_ERR_UNSUPPORTED, "AOV buffers are produced for the whole frame only (shard_count 1)");
+	if (s->device == RT_DEVICE_NONE)
+		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
+	return RT_OK;
+}
+
+int rt_render_aov_device(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *d_out, void *hip_stream)
+{
+	uint32_t mask = 0;
+	int rc = aov_check(s, camera, o, d_out, &mask);
+	if (rc != RT_OK)
+		return rc;
+	// a multi-device head is an ordinary scene on devices[0]: the AOV pass runs there alone
+	HIP_TRY(hipSetDevice(s->device));
+	if ((mask & kAovPrimitive) && !s->d_prim_desc) { // first use: BVH slot -> caller's index (synchronous, once per scene)
+		const std::vector<uint64_t> &order = s->host.primitive_order;
+		if (order.size() >= 0xFFFFFFFFull)
+			return fail(RT_ERR_UNSUPPORTED, "primitive IDs need fewer than 2^32 - 1 primitives");
+		std::vector<uint32_t> desc(order.size());
+		for (size_t i = 0; i < order.size(); ++i)
+			desc[i] = (uint32_t)order[i];
+		const uint32_t *d = nullptr;
+		rc = upload(s, desc.data(), desc.size(), &d);
+		if (rc != RT_OK)
+			return rc;
+		s->d_prim_desc = const_cast<uint32_t *>(d);
+	}
+	// traversal as rt_render / rt_check_hit choose it; the whole worst-case stack of the workgroup in LDS: the wide tree's only
+	// where it is walked and fits, the two-child tree's (and the two-child walk for every ray) otherwise
+	const bool prune = s->traversal_mode == -1 ? s->dev.n_prims > kPruneAbove : s->traversal_mode == 1;
+	DevScene dev = s->dev;
+	const bool walks_wide = prune && dev.nodes4 != nullptr && dev.narrow_only == 0u;
+	if (!walks_wide || aov_lds_bytes(dev) > s->max_lds) {
+		if (walks_wide)
+			dev.narrow_only = 1u;
+		dev.stack_depth = s->stack_depth_narrow;
+	}
+	if (aov_lds_bytes(dev) > s->max_lds)
+		return fail(RT_ERR_UNSUPPORTED, "traversal stacks exceed the LDS of one CU");
+	DevAovParams P;
+	std::memset(&P, 0, sizeof P);
+	std::memcpy(P.cam.origin, camera->origin, 12);
+	std::memcpy(P.cam.lower_left, camera->lower_left, 12);
+	std::memcpy(P.cam.horizontal, camera->horizontal, 12);
+	std::memcpy(P.cam.vertical, camera->vertical, 12);
+	P.width = (uint32_t)o->width;
+	P.height = (uint32_t)o->height;
+	P.tiles_x = (P.width + 7u) / 8u;
+	P.n_tiles = P.tiles_x * ((P.height + 7u) / 8u);
+	P.spp = (uint32_t)o->samples_per_pixel;
+	P.mask = mask;
+	P.seed_lo = (uint32_t)o->seed;
+	P.seed_hi = (uint32_t)(o->seed >> 32);
+	P.sample_begin_lo = (uint32_t)o->sample_begin;
+	P.sample_begin_hi = (uint32_t)(o->sample_begin >> 32);
+	P.prim_desc = s->d_prim_desc;
+	P.albedo = d_out->albedo;
+	P.normal = d_out->normal;
+	P.depth = d_out->depth;
+	P.coverage = d_out->coverage;
+	P.primitive = d_out->primitive;
+	P.material = d_out->material;
+	HIP_TRY(launch_aov(prune, static_cast<hipStream_t>(hip_stream), dev, P));
+	return RT_OK;
+}
+
+int rt_render_aov(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *out)
+{
+	uint32_t mask = 0;
+	int rc = aov_check(s, camera, o, out, &mask);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	const size_t n_px = (size_t)(o->width * o->height);
+	// one device allocation for the requested channels, in rt_aov_buffers order; 4-byte elements throughout
+	void *host[6] = {out->albedo, out->normal, out->depth, out->coverage, out->primitive, out->material};
+	const size_t per_px[6] = {3, 3, 1, 1, 1, 1};
+	size_t offset[6], total = 0;
+	for (int c = 0; c < 6; ++c) {
+		offset[c] = total;
+		if (host[c])
+			total += per_px[c] * n_px;
+	}
+	char *d = nullptr;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), total * 4));
+	rt_aov_buffers dev_out;
+	dev_out.albedo = host[0] ? reinterpret_cast<float *>(d + 4 * offset[0]) : nullptr;
+	dev_out.normal = host[1] ? reinterpret_cast<float *>(d + 4 * offset[1]) : nullptr;
+	dev_out.depth = host[2] ? reinterpret_cast<float *>(d + 4 * offset[2]) : nullptr;
+	dev_out.coverage = host[3] ? reinterpret_cast<float *>(d + 4 * offset[3]) : nullptr;
+	dev_out.primitive = host[4] ? reinterpret_cast<uint32_t *>(d + 4 * offset[4]) : nullptr;
+	dev_out.material = host[5] ? reinterpret_cast<uint32_t *>(d + 4 * offset[5]) : nullptr;
+	rc = rt_render_aov_device(s, camera, o, &dev_out, s->stream);
+	hipError_t e = hipSuccess;
+	for (int c = 0; c < 6 && rc == RT_OK && e == hipSuccess; ++c)
+		if (host[c])
+			e = hipMemcpyAsync(host[c], d + 4 * offset[c], per_px[c] * n_px * 4, hipMemcpyDeviceToHost, s->stream);
+	if (rc == RT_OK && e == hipSuccess)
+		e = hipStreamSynchronize(s->stream);
+	else if (rc != RT_OK)
+		(void)hipStreamSynchronize(s->stream);
+	(void)hipFree(d);
+	if (rc == RT_OK && e != hipSuccess)
+		rc = hip_fail(e, "render_aov");
+	return rc;
 }
 
 } // extern "C"

@@ -252,6 +252,36 @@ class HipScene:
         d["kernel"] = li.kernel.decode()
         return d
 
+    # ---- first-hit AOV buffers (rt_render_aov): albedo, normal, depth, coverage, primitive / material IDs ----
+    def render_aov(self, camera, opts, channels=abi.AOV_CHANNELS):
+        """The auxiliary buffers of the primary hits of passes [sample_begin, sample_begin + samples_per_pixel) -- the camera rays
+        rt_render traces -- as {channel: numpy array}: albedo / normal (H, W, 3) f32, depth / coverage (H, W) f32, primitive /
+        material (H, W) u32 (abi.AOV_NO_ID where pass sample_begin missed).  Semantics: include/rt_hip.h rt_aov_buffers."""
+        channels = tuple(channels)
+        unknown = set(channels) - set(abi.AOV_CHANNELS)
+        if unknown:
+            raise ValueError(f"unknown AOV channels {sorted(unknown)}")
+        h, w = int(opts.height), int(opts.width)
+        out, bufs = {}, abi.AovBuffers()
+        for name in channels:
+            dtype, ctype = (np.uint32, C.c_uint32) if name in ("primitive", "material") else (np.float32, C.c_float)
+            shape = (h, w, 3) if name in ("albedo", "normal") else (h, w)
+            out[name] = np.zeros(shape, dtype=dtype)
+            setattr(bufs, name, _p(out[name], ctype))
+        _check(lib().rt_render_aov(self._h, C.byref(camera), C.byref(opts), C.byref(bufs)))
+        return out
+
+    def render_aov_device(self, camera, opts, d_ptrs, stream=0):
+        """rt_render_aov_device: asynchronous, into DEVICE buffers of the scene's GPU.  d_ptrs = {channel: device pointer}
+        (e.g. torch.Tensor.data_ptr()); channels left out are not produced."""
+        bufs = abi.AovBuffers()
+        for name, ptr in d_ptrs.items():
+            if name not in abi.AOV_CHANNELS:
+                raise ValueError(f"unknown AOV channel {name!r}")
+            ctype = C.c_uint32 if name in ("primitive", "material") else C.c_float
+            setattr(bufs, name, C.cast(C.c_void_p(int(ptr)), C.POINTER(ctype)) if ptr else None)
+        _check(lib().rt_render_aov_device(self._h, C.byref(camera), C.byref(opts), C.byref(bufs), C.c_void_p(stream)))
+
     # ---- AccelerationStructure::check_hit / check_hit_index for batches ----
     def check_hit(self, origins, directions):
         rays = _pack_rays(origins, directions)
@@ -357,6 +387,18 @@ def save_image(filename, image, gamma=2.2):
     a = np.ascontiguousarray(image, dtype=np.float32)
     h, w, _ = a.shape
     _check(lib().rt_output_save(filename.encode(), _p(a, C.c_float), C.c_uint32(w), C.c_uint32(h), C.c_float(gamma)))
+
+
+def save_aov(prefix, aovs):
+    """Write the albedo and normal buffers of HipScene.render_aov as `<prefix>_albedo.exr` / `<prefix>_normal.exr` (float
+    channels, through rt_output_save; the denoiser inputs).  Returns the paths written."""
+    paths = []
+    for name in ("albedo", "normal"):
+        if name in aovs:
+            path = f"{prefix}_{name}.exr"
+            save_image(path, aovs[name])
+            paths.append(path)
+    return paths
 
 
 def get_readable_duration(seconds):
