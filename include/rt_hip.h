@@ -487,6 +487,70 @@ int rt_render_aov(rt_scene *scene, const rt_camera *camera, const rt_render_opts
 int rt_render_aov_device(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_aov_buffers *device_out,
                          void *hip_stream);
 
+/* ---- AOV-guided edge-aware A-Trous denoiser (csrc/rt_denoise.hip): the spatial part of SVGF (Dammertz et al. HPG 2010, Schied et
+ * al. HPG 2017) on albedo-demodulated radiance.  W x H, FRAME layout, row-major, y down, f32 throughout.  Per pixel p:
+ *   c  RGB mean radiance (required; what rt_render writes)       a  albedo RGB (optional)    n  normal RGB (optional)
+ *   z  depth (optional)                                           v  variance of lum of the demodulated mean (optional)
+ * a, n and z are exactly the rt_render_aov channels.
+ * Prepass:  d(p) = fmaxf(a(p), 1e-3f) per channel (albedo given) else (1, 1, 1);  e0(p) = c(p) / d(p) per channel (IEEE division);
+ *   lum(e) = 0.2126f*e.r + 0.7152f*e.g + 0.0722f*e.b, left to right, no fma;  n^ = n / |n| (|n| = sqrtf(n.x*n.x + n.y*n.y + n.z*n.z)),
+ *   0 where |n| = 0.  p is INVALID if a component of c(p), or v(p), is not finite: its output is c(p) unchanged and it is a tap of
+ *   weight 0 everywhere (the variance estimate below included).
+ *   Var0(p) = v(p) if given; else over the in-frame VALID q of the 5 x 5 box around p: m = sum lum(e0(q)) / count, then
+ *   Var0 = sum (lum(e0(q)) - m)^2 / count (two passes).
+ * Iteration i = 0 .. N-1, step k = 2^i:
+ *   g(p) = sum g3(dx) g3(dy) Var_i(q) / sum g3(dx) g3(dy) over in-frame valid q = p + (dx, dy), dx, dy in -1..1, g3 = [1/4, 1/2, 1/4]
+ *   taps q = p + k (dx, dy), dy outer, dx inner, in -2..2; a tap out of frame (skipped, not clamped) or invalid contributes nothing.
+ *     h   = h5(dx) h5(dy), h5 = [1/16, 1/4, 3/8, 1/4, 1/16]
+ *     w_l = expf(-|lum(e_i(p)) - lum(e_i(q))| / (sigma_luminance * sqrtf(g(p)) + 1e-6f))
+ *     w_n = 1 without normals or where n^(p) = n^(q) = 0; else powf(fmaxf(0, dot(n^(p), n^(q))), sigma_normal)
+ *     w_z = 1 without depth or where z(p) = z(q) = 0 ("no pass hit"); 0 where exactly one is 0;
+ *           else expf(-|z(p) - z(q)| / (sigma_depth * z(p) * k))
+ *     w   = h * w_l * w_n * w_z; the centre tap has w = 9/64 exactly
+ *   e_{i+1}(p) = sum w e_i(q) / sum w;   Var_{i+1}(p) = sum w^2 Var_i(q) / (sum w)^2
+ * Output: out(p) = e_N(p) * d(p) for valid p, c(p) for invalid p; 3 floats per pixel, no alignment required.
+ * Options: iterations N in 1..10; every sigma finite and > 0; `reserved` is for later fields (rt_denoise_opts_default zeroes it).
+ * The defaults and the quality they give are measured in DESIGN.md section 10. */
+typedef struct rt_denoise_opts {
+	uint32_t width, height;
+	uint32_t iterations;   /* N, default 5 */
+	float sigma_luminance; /* default 4 */
+	float sigma_normal;    /* default 128 */
+	float sigma_depth;     /* default 0.1 */
+	uint32_t reserved[6];
+} rt_denoise_opts;
+/* Any pointer but `color` may be NULL (that guide not used; no variance -> the 5 x 5 spatial estimate).  color / albedo / normal:
+ * w*h*3; depth / variance: w*h. */
+typedef struct rt_denoise_inputs {
+	const float *color, *albedo, *normal, *depth, *variance;
+} rt_denoise_inputs;
+int rt_denoise_opts_default(rt_denoise_opts *out);
+/* The workspace rt_denoise_device needs: 48 bytes per pixel (three float4 planes: (e, Var) twice, ping-pong, and (n^, z)). */
+int rt_denoise_workspace_bytes(const rt_denoise_opts *opts, uint64_t *bytes);
+/* Checks (the device last, so that a host-only scene reports bad arguments as such): RT_ERR_INVALID_ARGUMENT for a NULL scene,
+ * inputs, opts, color or out, out overlapping an input, width or height 0, iterations outside 1..10, a sigma not finite or <= 0
+ * (and, device call, a NULL or not 16-byte aligned workspace or one overlapping an input or out); RT_ERR_UNSUPPORTED for more
+ * than 2^31 pixels; RT_ERR_NO_DEVICE for a host-only scene.  A multi-device head runs the filter on devices[0].
+ * No side effects: what rt_last_kernel_ms, rt_last_launch_info and a following rt_render return is unchanged.
+ * rt_denoise: HOST buffers, blocking; its device copies and workspace live on the scene (grown on first use and for larger frames
+ * only).  rt_denoise_device: DEVICE buffers on the scene's GPU, asynchronous on hip_stream; it allocates nothing and keeps no
+ * state, so it can be captured into a graph from its first call.  Ordering the reuse of one workspace across streams is the
+ * caller's job, as for the output buffers. */
+int rt_denoise(rt_scene *scene, const rt_denoise_inputs *host_in, const rt_denoise_opts *opts, float *host_out);
+int rt_denoise_device(rt_scene *scene, const rt_denoise_inputs *device_in, const rt_denoise_opts *opts, void *d_workspace,
+                      float *d_out, void *hip_stream);
+/* Render + AOV + filter in one blocking call.  With sb = opts->sample_begin and S = opts->samples_per_pixel (even, >= 2): renders
+ * passes [sb, sb + S/2) -> A and [sb + S/2, sb + S) -> B through rt_render_device (any sample_split; a multi-device head renders as
+ * it always does), the albedo / normal / depth AOVs of all S passes, then
+ *   noisy = (A + B) * 0.5f,   variance = (lA - lB) * (lA - lB) * 0.25f,  lA = lum(A / d), lB = lum(B / d)  (d, lum as above)
+ * and the filter of rt_denoise_device on (noisy, albedo, normal, depth, variance).  out_clean (and out_noisy unless NULL) get
+ * w*h*3 floats; *rays_shot (unless NULL) = the two halves' counts added.  noisy is NOT the bytes of one rt_render of S passes
+ * (that keeps a running mean; the two differ at the 1e-7 level).  width and height come from opts (>= 2, the AOV rule; those of
+ * dopts are ignored); output_layout must be RT_LAYOUT_FRAME and shard_count 1 (else RT_ERR_UNSUPPORTED).  rt_last_kernel_ms and
+ * rt_last_launch_info afterwards describe the render of the second half, B. */
+int rt_render_denoised(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_denoise_opts *dopts,
+                       float *out_clean, float *out_noisy, uint64_t *rays_shot);
+
 /* Division by a constant a launch knows beforehand (image size - 1, sky table resolution, pi, 2 pi): the kernels replace `x / c` by
  * two fma steps on rc = RN(1 / c) where -- and only where -- the host has verified, by enumerating all 2^23 significands of x, that
  * this returns the bits of the division (csrc/rt_build.cpp verified_reciprocal, csrc/rt_lean.h div_by_verified).  This call runs that

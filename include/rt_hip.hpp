@@ -329,6 +329,64 @@ inline AovBuffers render_aov(const RenderOptions &o, const SimpleCamera &camera,
 	return a;
 }
 
+// The A-Trous denoiser of rt_hip.h (rt_denoise_opts): the options a caller sets; defaults as rt_denoise_opts_default.
+struct DenoiseOptions {
+	uint32_t iterations = 5;
+	float sigma_luminance = 4.0f, sigma_normal = 128.0f, sigma_depth = 0.1f;
+};
+inline rt_denoise_opts denoise_opts(const DenoiseOptions &d, uint32_t width, uint32_t height)
+{
+	rt_denoise_opts o;
+	check(rt_denoise_opts_default(&o));
+	o.width = width;
+	o.height = height;
+	o.iterations = d.iterations;
+	o.sigma_luminance = d.sigma_luminance;
+	o.sigma_normal = d.sigma_normal;
+	o.sigma_depth = d.sigma_depth;
+	return o;
+}
+// Filter a width*height*3 radiance frame (what render writes) guided by the albedo, normal and depth of `aov` (render_aov of the
+// same passes; nullptr or an empty channel = that guide not used); the variance is estimated from the frame.  Blocking.
+inline std::vector<float> denoise(const Bvh &bvh, const std::vector<float> &color, const AovBuffers *aov, uint32_t width,
+                                  uint32_t height, const DenoiseOptions &d = DenoiseOptions())
+{
+	auto ptr = [](const std::vector<float> &v) { return v.empty() ? nullptr : v.data(); };
+	rt_denoise_inputs in = {color.data(), nullptr, nullptr, nullptr, nullptr};
+	if (aov) {
+		in.albedo = ptr(aov->albedo);
+		in.normal = ptr(aov->normal);
+		in.depth = ptr(aov->depth);
+	}
+	const rt_denoise_opts o = denoise_opts(d, width, height);
+	std::vector<float> out((size_t)width * height * 3);
+	check(rt_denoise(bvh.raw(), &in, &o, out.data()));
+	return out;
+}
+// Two half renders, the AOVs of all passes and the filter in one call (rt_render_denoised; o.samples_per_pixel even, >= 2).
+struct Denoised {
+	std::vector<float> clean, noisy; // w*h*3
+	uint64_t rays_shot = 0;
+};
+inline Denoised render_denoised(const RenderOptions &o, const SimpleCamera &camera, const Bvh &bvh,
+                                const DenoiseOptions &d = DenoiseOptions(), uint64_t seed = 1, uint64_t sample_begin = 0)
+{
+	rt_render_opts opts;
+	rt_render_opts_default(&opts);
+	opts.width = o.width;
+	opts.height = o.height;
+	opts.samples_per_pixel = o.samples_per_pixel;
+	opts.render_method = static_cast<int32_t>(o.render_method);
+	opts.sample_begin = sample_begin;
+	opts.seed = seed;
+	const rt_denoise_opts dopts = denoise_opts(d, 0, 0); // (the frame size comes from opts)
+	Denoised r;
+	r.clean.resize((size_t)o.width * o.height * 3);
+	r.noisy.resize(r.clean.size());
+	check(rt_render_denoised(bvh.raw(), &camera.raw(), &opts, &dopts, r.clean.data(), r.noisy.data(), &r.rays_shot));
+	return r;
+}
+
 struct Presentation { // what render_tui keeps: the mean image and the ray total (src/main.rs:160-173)
 	SamplerProgress sampler_progress;
 	Presentation(uint64_t pixel_num) : sampler_progress(pixel_num, 3) {}

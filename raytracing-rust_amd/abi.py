@@ -213,6 +213,26 @@ class AovBuffers(C.Structure):  # rt_aov_buffers
 
 
 AOV_CHANNELS = ("albedo", "normal", "depth", "coverage", "primitive", "material")
+
+
+class DenoiseOpts(C.Structure):  # rt_denoise_opts
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("iterations", C.c_uint32),
+        ("sigma_luminance", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_depth", C.c_float),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+
+class DenoiseInputs(C.Structure):  # rt_denoise_inputs
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in ("color", "albedo", "normal", "depth", "variance")]
+
+
+DENOISE_INPUTS = ("color", "albedo", "normal", "depth", "variance")
+DENOISE_WORKSPACE_BYTES_PER_PIXEL = 48  # three float4 planes
 AOV_NO_ID = 0xFFFFFFFF  # primitive / material of a pass that missed
 
 # rt_presentation_update: int (*)(void *data, const rt_sampler_progress *, uint64_t samples_done)
@@ -234,6 +254,8 @@ EXPECTED_SIZES = {
     "rt_sampler_progress": (SamplerProgressC, 32),
     "rt_launch_info": (LaunchInfo, 224),
     "rt_aov_buffers": (AovBuffers, 48),
+    "rt_denoise_opts": (DenoiseOpts, 48),
+    "rt_denoise_inputs": (DenoiseInputs, 40),
 }
 
 # every symbol include/rt_hip.h declares
@@ -278,7 +300,20 @@ EXPORTED_SYMBOLS = [
     "rt_selftest_lean",
     "rt_render_aov",
     "rt_render_aov_device",
+    "rt_denoise_opts_default",
+    "rt_denoise_workspace_bytes",
+    "rt_denoise",
+    "rt_denoise_device",
+    "rt_render_denoised",
 ]
+
+
+def default_denoise_opts(width=0, height=0, iterations=5, sigma_luminance=4.0, sigma_normal=128.0, sigma_depth=0.1):
+    """rt_denoise_opts_default (include/rt_hip.h) with the frame size filled in."""
+    o = DenoiseOpts()
+    o.width, o.height, o.iterations = width, height, iterations
+    o.sigma_luminance, o.sigma_normal, o.sigma_depth = sigma_luminance, sigma_normal, sigma_depth
+    return o
 
 
 def default_render_opts(width=1920, height=1080, spp=128, method=RT_METHOD_MIS, seed=1):

@@ -20,6 +20,7 @@
 #include "rt_build.h"
 #include "rt_types.h"
 #include "rt_aov.h"
+#include "rt_denoise.h"
 
 namespace rt {
 size_t render_lds_bytes(const DevScene &S, bool sky_lds, bool scene_lds, uint32_t waves_per_block, uint32_t stack_cap);
@@ -141,6 +142,8 @@ struct rt_scene {
 	hipEvent_t ev_gathered = nullptr;      // head: the last render's gather + scatter have read every member's shard
 	bool gathered_once = false;
 	uint32_t *d_prim_desc = nullptr;       // rt_render_aov: BVH slot -> rt_scene_desc index, uploaded on first use (in `allocations`)
+	char *d_denoise = nullptr;             // rt_denoise / rt_render_denoised: device frames + workspace, grown on first use
+	size_t d_denoise_bytes = 0;
 };
 
 template <class T> static int upload(rt_scene *s, const T *src, size_t count, const T **dst)
@@ -604,6 +607,8 @@ void rt_scene_destroy(rt_scene *s)
 		(void)hipFree(s->d_partial);
 	if (s->d_rgb8)
 		(void)hipFree(s->d_rgb8);
+	if (s->d_denoise)
+		(void)hipFree(s->d_denoise);
 	if (s->d_stack_ovf)
 		(void)hipFree(s->d_stack_ovf);
 	for (int b = 0; b < 2; ++b) {
@@ -2184,6 +2189,264 @@ int rt_render_aov(rt_scene *s, const rt_camera *camera, const rt_render_opts *o,
 	(void)hipFree(d);
 	if (rc == RT_OK && e != hipSuccess)
 		rc = hip_fail(e, "render_aov");
+	return rc;
+}
+
+} // extern "C"
+
+// ---- AOV-guided A-Trous denoiser (rt_denoise.hip) ----
+static bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
+{
+	if (!a || !b)
+		return false;
+	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+	return x < y + b_bytes && y < x + a_bytes;
+}
+
+// the frame size and the filter options (width and height are passed separately: rt_render_denoised takes them from the render)
+static int denoise_opts_check(const rt_denoise_opts *d, uint64_t w, uint64_t h)
+{
+	if (w == 0 || h == 0)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise: width and height must be >= 1");
+	if (d->iterations < 1 || d->iterations > 10)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise: iterations must be in 1..10");
+	const float sig[3] = {d->sigma_luminance, d->sigma_normal, d->sigma_depth};
+	for (float x : sig)
+		if (!std::isfinite(x) || !(x > 0.0f))
+			return fail(RT_ERR_INVALID_ARGUMENT, "denoise: sigma_luminance, sigma_normal and sigma_depth must be finite and > 0");
+	if (w > (1ull << 31) || h > (1ull << 31) || w * h > (1ull << 31))
+		return fail(RT_ERR_UNSUPPORTED, "denoise: more than 2^31 pixels");
+	return RT_OK;
+}
+
+// argument checks of rt_denoise / rt_denoise_device, the device last (so that a host-only scene reports bad arguments as such);
+// `ws` is checked for the device call only
+static int denoise_check(const rt_scene *s, const rt_denoise_inputs *in, const rt_denoise_opts *o, const float *out, bool device,
+                         const void *ws)
+{
+	if (!s || !in || !o)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (!in->color || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise: color and out must not be NULL");
+	int rc = denoise_opts_check(o, o->width, o->height);
+	if (rc != RT_OK)
+		return rc;
+	const uint64_t n = (uint64_t)o->width * o->height;
+	const void *inputs[5] = {in->color, in->albedo, in->normal, in->depth, in->variance};
+	const uint64_t bytes[5] = {12 * n, 12 * n, 12 * n, 4 * n, 4 * n};
+	for (int i = 0; i < 5; ++i)
+		if (ranges_overlap(out, 12 * n, inputs[i], bytes[i]))
+			return fail(RT_ERR_INVALID_ARGUMENT, "denoise: out overlaps an input");
+	if (device) {
+		if (!ws || reinterpret_cast<uintptr_t>(ws) % 16u != 0u)
+			return fail(RT_ERR_INVALID_ARGUMENT, "denoise: the workspace must be non-NULL and 16-byte aligned");
+		const uint64_t ws_bytes = kDenoiseWorkspaceBytesPerPixel * n;
+		bool clash = ranges_overlap(ws, ws_bytes, out, 12 * n);
+		for (int i = 0; i < 5; ++i)
+			clash = clash || ranges_overlap(ws, ws_bytes, inputs[i], bytes[i]);
+		if (clash)
+			return fail(RT_ERR_INVALID_ARGUMENT, "denoise: the workspace overlaps an input or out");
+	}
+	if (s->device == RT_DEVICE_NONE)
+		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
+	return RT_OK;
+}
+
+static DevDenoiseParams denoise_params(const rt_denoise_opts *o, uint64_t w, uint64_t h, const rt_denoise_inputs &in, void *ws,
+                                       float *out)
+{
+	DevDenoiseParams P;
+	std::memset(&P, 0, sizeof P);
+	P.width = (uint32_t)w;
+	P.height = (uint32_t)h;
+	P.iterations = o->iterations;
+	P.sigma_l = o->sigma_luminance;
+	P.sigma_n = o->sigma_normal;
+	P.sigma_z = o->sigma_depth;
+	P.color = in.color;
+	P.albedo = in.albedo;
+	P.normal = in.normal;
+	P.depth = in.depth;
+	P.variance = in.variance;
+	const size_t n = (size_t)(w * h);
+	P.plane0 = static_cast<float4 *>(ws);
+	P.plane1 = P.plane0 + n;
+	P.guide = P.plane1 + n;
+	P.out = out;
+	return P;
+}
+
+// the scene-owned device buffer of the blocking denoise entry points, grown on first use / larger frames only
+static int ensure_denoise_buffer(rt_scene *s, size_t bytes)
+{
+	if (bytes <= s->d_denoise_bytes)
+		return RT_OK;
+	if (s->d_denoise)
+		(void)hipFree(s->d_denoise);
+	s->d_denoise = nullptr;
+	s->d_denoise_bytes = 0;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_denoise), bytes));
+	s->d_denoise_bytes = bytes;
+	return RT_OK;
+}
+
+extern "C" {
+
+int rt_denoise_opts_default(rt_denoise_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	out->iterations = 5;
+	out->sigma_luminance = 4.0f;
+	out->sigma_normal = 128.0f;
+	out->sigma_depth = 0.1f;
+	return RT_OK;
+}
+
+int rt_denoise_workspace_bytes(const rt_denoise_opts *o, uint64_t *bytes)
+{
+	if (!o || !bytes)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (o->width == 0 || o->height == 0)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise: width and height must be >= 1");
+	const uint64_t n = (uint64_t)o->width * o->height;
+	if (n > (1ull << 31))
+		return fail(RT_ERR_UNSUPPORTED, "denoise: more than 2^31 pixels");
+	*bytes = kDenoiseWorkspaceBytesPerPixel * n;
+	return RT_OK;
+}
+
+int rt_denoise_device(rt_scene *s, const rt_denoise_inputs *d_in, const rt_denoise_opts *o, void *d_workspace, float *d_out,
+                      void *hip_stream)
+{
+	int rc = denoise_check(s, d_in, o, d_out, true, d_workspace);
+	if (rc != RT_OK)
+		return rc;
+	// a multi-device head is an ordinary scene on devices[0]: the filter runs there alone
+	HIP_TRY(hipSetDevice(s->device));
+	HIP_TRY(launch_denoise(static_cast<hipStream_t>(hip_stream), denoise_params(o, o->width, o->height, *d_in, d_workspace, d_out)));
+	return RT_OK;
+}
+
+int rt_denoise(rt_scene *s, const rt_denoise_inputs *in, const rt_denoise_opts *o, float *out)
+{
+	int rc = denoise_check(s, in, o, out, false, nullptr);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	const size_t n = (size_t)o->width * o->height;
+	// workspace first (16-byte aligned), then out, then the inputs given, in rt_denoise_inputs order
+	const float *host[5] = {in->color, in->albedo, in->normal, in->depth, in->variance};
+	const size_t per_px[5] = {3, 3, 3, 1, 1};
+	size_t offset[5], total = kDenoiseWorkspaceBytesPerPixel / 4 * n + 3 * n;
+	for (int c = 0; c < 5; ++c) {
+		offset[c] = total;
+		if (host[c])
+			total += per_px[c] * n;
+	}
+	rc = ensure_denoise_buffer(s, total * 4);
+	if (rc != RT_OK)
+		return rc;
+	float *base = reinterpret_cast<float *>(s->d_denoise);
+	float *d_out = base + kDenoiseWorkspaceBytesPerPixel / 4 * n;
+	const float *dev[5];
+	hipError_t e = hipSuccess;
+	for (int c = 0; c < 5; ++c) {
+		dev[c] = host[c] ? base + offset[c] : nullptr;
+		if (host[c] && e == hipSuccess)
+			e = hipMemcpyAsync(base + offset[c], host[c], per_px[c] * n * 4, hipMemcpyHostToDevice, s->stream);
+	}
+	if (e != hipSuccess) {
+		(void)hipStreamSynchronize(s->stream);
+		return hip_fail(e, "denoise upload");
+	}
+	const rt_denoise_inputs d_in = {dev[0], dev[1], dev[2], dev[3], dev[4]};
+	rc = rt_denoise_device(s, &d_in, o, s->d_denoise, d_out, s->stream);
+	if (rc == RT_OK)
+		e = hipMemcpyAsync(out, d_out, 3 * n * 4, hipMemcpyDeviceToHost, s->stream);
+	const hipError_t e_sync = hipStreamSynchronize(s->stream);
+	if (rc == RT_OK && e == hipSuccess)
+		e = e_sync;
+	if (rc == RT_OK && e != hipSuccess)
+		rc = hip_fail(e, "denoise");
+	return rc;
+}
+
+int rt_render_denoised(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_denoise_opts *dopts, float *out_clean,
+                       float *out_noisy, uint64_t *rays_shot)
+{
+	if (!s || !camera || !o || !dopts || !out_clean)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	int rc = denoise_opts_check(dopts, o->width, o->height);
+	if (rc != RT_OK)
+		return rc;
+	if (o->width < 2 || o->height < 2)
+		return fail(RT_ERR_INVALID_ARGUMENT, "width and height must be >= 2 (u and v divide by W-1 and H-1)");
+	if (o->samples_per_pixel < 2 || o->samples_per_pixel % 2 != 0 || o->samples_per_pixel >= (1ull << 32))
+		return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_denoised: samples_per_pixel must be even, >= 2 and < 2^32");
+	if (o->render_method != RT_METHOD_NAIVE && o->render_method != RT_METHOD_MIS)
+		return fail(RT_ERR_INVALID_ARGUMENT, "unknown render method");
+	if (o->output_layout != RT_LAYOUT_FRAME)
+		return fail(RT_ERR_UNSUPPORTED, "rt_render_denoised: RT_LAYOUT_FRAME only");
+	if (o->shard_count != 1)
+		return fail(RT_ERR_UNSUPPORTED, "rt_render_denoised: the whole frame only (shard_count 1)");
+	const size_t n = (size_t)(o->width * o->height);
+	if (ranges_overlap(out_clean, 12 * n, out_noisy, 12 * n))
+		return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_denoised: out_clean overlaps out_noisy");
+	if (s->device == RT_DEVICE_NONE)
+		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
+	HIP_TRY(hipSetDevice(s->device));
+	// two ray counters (16 bytes), the workspace, then the frames: A, B, albedo, normal, depth, noisy, clean
+	const size_t ws_floats = kDenoiseWorkspaceBytesPerPixel / 4 * n;
+	rc = ensure_denoise_buffer(s, 16 + 4 * (ws_floats + 19 * n));
+	if (rc != RT_OK)
+		return rc;
+	unsigned long long *d_rays = reinterpret_cast<unsigned long long *>(s->d_denoise);
+	float *ws = reinterpret_cast<float *>(s->d_denoise + 16);
+	float *d_a = ws + ws_floats, *d_b = d_a + 3 * n, *d_albedo = d_b + 3 * n, *d_normal = d_albedo + 3 * n,
+	      *d_depth = d_normal + 3 * n, *d_noisy = d_depth + n, *d_clean = d_noisy + 3 * n;
+	const uint64_t half = o->samples_per_pixel / 2;
+	rt_render_opts oh = *o;
+	oh.samples_per_pixel = half;
+	rc = rt_render_device(s, camera, &oh, d_a, reinterpret_cast<uint64_t *>(d_rays), s->stream);
+	if (rc == RT_OK) {
+		oh.sample_begin = o->sample_begin + half;
+		rc = rt_render_device(s, camera, &oh, d_b, reinterpret_cast<uint64_t *>(d_rays + 1), s->stream);
+	}
+	hipError_t e = hipSuccess;
+	if (rc == RT_OK)
+		e = hipSetDevice(s->device);
+	if (rc == RT_OK && e == hipSuccess) {
+		rt_aov_buffers aov;
+		std::memset(&aov, 0, sizeof aov);
+		aov.albedo = d_albedo;
+		aov.normal = d_normal;
+		aov.depth = d_depth;
+		rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
+	}
+	if (rc == RT_OK && e == hipSuccess) {
+		const rt_denoise_inputs in = {d_noisy, d_albedo, d_normal, d_depth, nullptr};
+		DevDenoiseParams P = denoise_params(dopts, o->width, o->height, in, ws, d_clean);
+		P.half_a = d_a;
+		P.half_b = d_b;
+		P.noisy = d_noisy;
+		e = launch_denoise(s->stream, P);
+	}
+	unsigned long long rays[2] = {0, 0};
+	if (rc == RT_OK && e == hipSuccess)
+		e = hipMemcpyAsync(out_clean, d_clean, 3 * n * 4, hipMemcpyDeviceToHost, s->stream);
+	if (rc == RT_OK && e == hipSuccess && out_noisy)
+		e = hipMemcpyAsync(out_noisy, d_noisy, 3 * n * 4, hipMemcpyDeviceToHost, s->stream);
+	if (rc == RT_OK && e == hipSuccess)
+		e = hipMemcpyAsync(rays, d_rays, sizeof rays, hipMemcpyDeviceToHost, s->stream);
+	const hipError_t e_sync = hipStreamSynchronize(s->stream);
+	if (rc == RT_OK && e == hipSuccess)
+		e = e_sync;
+	if (rc == RT_OK && e != hipSuccess)
+		rc = hip_fail(e, "render_denoised");
+	if (rc == RT_OK && rays_shot)
+		*rays_shot = rays[0] + rays[1];
 	return rc;
 }
 

@@ -282,6 +282,65 @@ class HipScene:
             setattr(bufs, name, C.cast(C.c_void_p(int(ptr)), C.POINTER(ctype)) if ptr else None)
         _check(lib().rt_render_aov_device(self._h, C.byref(camera), C.byref(opts), C.byref(bufs), C.c_void_p(stream)))
 
+    # ---- AOV-guided A-Trous denoiser (rt_denoise) ----
+    def denoise(self, color, albedo=None, normal=None, depth=None, variance=None, **opts):
+        """rt_denoise: filter an (H, W, 3) f32 radiance image guided by the optional albedo / normal (H, W, 3), depth and variance
+        (H, W); returns (H, W, 3) f32.  The guides may also come as the dict render_aov returns, in place of `albedo` (its
+        other channels are ignored), or with the image under "color" in place of `color`.  Keyword options: iterations,
+        sigma_luminance, sigma_normal, sigma_depth.  Semantics: include/rt_hip.h rt_denoise_opts."""
+        guides = {}
+        if isinstance(color, dict):  # denoise({"color": ..., **scene.render_aov(...)})
+            guides, color = color, color["color"]
+        elif isinstance(albedo, dict):  # denoise(color, scene.render_aov(...))
+            guides, albedo = albedo, None
+        albedo, normal = guides.get("albedo", albedo), guides.get("normal", normal)
+        depth, variance = guides.get("depth", depth), guides.get("variance", variance)
+        color = np.ascontiguousarray(color, dtype=np.float32)
+        if color.ndim != 3 or color.shape[2] != 3:
+            raise ValueError(f"color must be (H, W, 3), got {color.shape}")
+        h, w = color.shape[:2]
+        ins, keep = abi.DenoiseInputs(), [color]
+        ins.color = _p(color, C.c_float)
+        for name, a, shape in (("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w)),
+                               ("variance", variance, (h, w))):
+            if a is None:
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"{name} must be {shape}, got {a.shape}")
+            keep.append(a)
+            setattr(ins, name, _p(a, C.c_float))
+        o = denoise_opts(w, h, **opts)
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        _check(lib().rt_denoise(self._h, C.byref(ins), C.byref(o), _p(out, C.c_float)))
+        return out
+
+    def denoise_device(self, d_ptrs, d_workspace, d_out, opts, stream=0):
+        """rt_denoise_device: asynchronous, DEVICE buffers of the scene's GPU.  d_ptrs = {input: device pointer} over
+        abi.DENOISE_INPUTS ("color" required); d_workspace: denoise_workspace_bytes(opts) bytes, 16-byte aligned;
+        opts: abi.DenoiseOpts with the frame size set."""
+        ins = abi.DenoiseInputs()
+        for name, ptr in d_ptrs.items():
+            if name not in abi.DENOISE_INPUTS:
+                raise ValueError(f"unknown denoise input {name!r}")
+            setattr(ins, name, C.cast(C.c_void_p(int(ptr)), C.POINTER(C.c_float)) if ptr else None)
+        _check(lib().rt_denoise_device(self._h, C.byref(ins), C.byref(opts), C.c_void_p(int(d_workspace)),
+                                       C.cast(C.c_void_p(int(d_out)), C.POINTER(C.c_float)), C.c_void_p(stream)))
+
+    def render_denoised(self, camera, opts, dopts=None):
+        """rt_render_denoised: two half renders, the AOVs of all passes and the filter in one call.  Returns (clean, noisy,
+        rays_shot) with clean / noisy (H, W, 3) f32.  dopts: abi.DenoiseOpts (its width / height are ignored) or None for the
+        defaults."""
+        h, w = int(opts.height), int(opts.width)
+        if dopts is None:
+            dopts = denoise_opts(w, h)
+        clean = np.zeros((h, w, 3), dtype=np.float32)
+        noisy = np.zeros((h, w, 3), dtype=np.float32)
+        rays = C.c_uint64()
+        _check(lib().rt_render_denoised(self._h, C.byref(camera), C.byref(opts), C.byref(dopts), _p(clean, C.c_float),
+                                        _p(noisy, C.c_float), C.byref(rays)))
+        return clean, noisy, rays.value
+
     # ---- AccelerationStructure::check_hit / check_hit_index for batches ----
     def check_hit(self, origins, directions):
         rays = _pack_rays(origins, directions)
@@ -387,6 +446,25 @@ def save_image(filename, image, gamma=2.2):
     a = np.ascontiguousarray(image, dtype=np.float32)
     h, w, _ = a.shape
     _check(lib().rt_output_save(filename.encode(), _p(a, C.c_float), C.c_uint32(w), C.c_uint32(h), C.c_float(gamma)))
+
+
+def denoise_opts(width, height, **kw):
+    """rt_denoise_opts_default with the frame size and any of iterations / sigma_luminance / sigma_normal / sigma_depth set."""
+    o = abi.DenoiseOpts()
+    _check(lib().rt_denoise_opts_default(C.byref(o)))
+    o.width, o.height = int(width), int(height)
+    for k, v in kw.items():
+        if k not in ("iterations", "sigma_luminance", "sigma_normal", "sigma_depth"):
+            raise ValueError(f"unknown denoise option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def denoise_workspace_bytes(opts):
+    """rt_denoise_workspace_bytes: the workspace rt_denoise_device needs for opts' frame size."""
+    n = C.c_uint64()
+    _check(lib().rt_denoise_workspace_bytes(C.byref(opts), C.byref(n)))
+    return n.value
 
 
 def save_aov(prefix, aovs):
