@@ -551,6 +551,77 @@ int rt_denoise_device(rt_scene *scene, const rt_denoise_inputs *device_in, const
 int rt_render_denoised(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_denoise_opts *dopts,
                        float *out_clean, float *out_noisy, uint64_t *rays_shot);
 
+/* ---- Temporal accumulation with camera reprojection (csrc/rt_temporal.hip): the temporal half of SVGF (Schied et al. HPG 2017) in
+ * front of the A-Trous filter above, for a static scene seen by a moving camera.  W x H (both >= 2, the AOV rule), FRAME layout,
+ * row-major, y down, f32 throughout with the library's arithmetic contract: IEEE `/` and sqrtf, no fma, sums left to right.
+ * Inputs of one frame: c (required), a and n (optional), z (REQUIRED), the camera `cam` (o, ll, h, vv = origin, lower_left,
+ * horizontal, vertical) and the previous frame's camera `prev` (o', ll', h', v').  d, e0 = c / d, lum, n^ and validity are exactly
+ * those of rt_denoise without a variance input (p is INVALID if a component of c(p), or lum(e0(p)), is not finite).
+ *   dot(a, b)   = (a.x*b.x + a.y*b.y) + a.z*b.z
+ *   cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x)
+ * Reprojection of pixel (x, y) (vector operations per component):
+ *   u = ((float)x + 0.5f) / (float)(W - 1),  v = 1.0f - ((float)y + 0.5f) / (float)(H - 1)   (the centre of the render's jitter)
+ *   D = ((ll + h*u) + vv*v) - o,  |D| = sqrtf(dot(D, D)),  d^ = D / |D|
+ *   hit pixel (z > 0 and finite): R = (o + d^*z) - o';  miss pixel (z == 0): R = d^ (a point at infinity); any other z: FAILS
+ *   L' = ll' - o',  c' = cross(h', v'),  det = dot(L', c'),  s = dot(R, c') / det,  al = dot(L', cross(R, v')) / det,
+ *   be = dot(L', cross(h', R)) / det.  The projection FAILS if det == 0, s <= 0, or s, al or be is not finite.
+ *   X' = (al / s) * (float)(W - 1),  Y' = (1.0f - be / s) * (float)(H - 1);  motion = (X' - ((float)x + 0.5f), Y' - ((float)y + 0.5f)),
+ *   NaN in both components where the projection fails or there is no history.
+ *   fx = X' - 0.5f, fy = Y' - 0.5f, i0 = floorf(fx), j0 = floorf(fy), ax = fx - i0, ay = fy - j0, bx = 1.0f - ax, by = 1.0f - ay;
+ *   taps k = 0..3 in this order: (i0, j0) w = bx*by;  (i0 + 1.0f, j0) w = ax*by;  (i0, j0 + 1.0f) w = bx*ay;  (i0 + 1.0f, j0 + 1.0f)
+ *   w = ax*ay.  A tap q is ACCEPTED when all hold: 0 <= i <= (float)(W - 1) and 0 <= j <= (float)(H - 1) (as floats); w >= 1.0f/64;
+ *   n'(q) >= 1; hit pixel: z'(q) > 0 and fabsf(z'(q) - dist) <= depth_tolerance * dist with dist = sqrtf(dot(R, R)), miss pixel:
+ *   z'(q) == 0; with normals given and n^(p), n^'(q) both nonzero (not all three components 0): dot(n^(p), n^'(q)) >= normal_tolerance.
+ * Accumulation (l = lum(e0)):
+ *   >= 1 accepted tap: sums from +0 over the accepted taps in tap order, sw = sw + w, se = se + w*e'(q) per channel, s1 = s1 + w*m1'(q),
+ *     s2 = s2 + w*m2'(q); e_prev = se / sw, m1_prev = s1 / sw, m2_prev = s2 / sw; n_prev = the max n'(q) of the accepted taps;
+ *     n = fminf(n_prev + 1.0f, (float)max_history), a_c = fmaxf(alpha_color, 1.0f / n), a_m = fmaxf(alpha_moments, 1.0f / n);
+ *     e = e_prev + a_c*(e0 - e_prev),  m1 = m1_prev + a_m*(l - m1_prev),  m2 = m2_prev + a_m*(l*l - m2_prev)
+ *   otherwise (no history, failed projection, no accepted tap): n = 1, e = e0, m1 = l, m2 = l*l
+ *   Var = fmaxf(0.0f, m2 - m1*m1) where n >= 4, else rt_denoise's 5 x 5 spatial estimate over this frame's e0.
+ * Filter: the N A-Trous iterations of rt_denoise on (e, Var) with this frame's guides (n^, z), unchanged; out = e_N * d for valid p,
+ *   c(p) for invalid p.  Without history the output is therefore the bytes of rt_denoise with the same options and no variance.
+ * History written for the next frame: e_1 (iteration 0's output, demodulated), n, m1, m2, n^ and z.  An invalid pixel writes
+ *   n = 0, e_1 = m1 = m2 = 0, and is never an accepted tap.  Layout (callers treat it as opaque; 48 bytes per pixel): three float4
+ *   planes of W*H, one after the other: H0 = (e_1.rgb, n), H1 = (n^.xyz, z) (n^ = 0 without normals), H2 = (m1, m2, 0, 0).
+ * Options: `denoise` as for rt_denoise, its width and height the frame size; alpha_color and alpha_moments in (0, 1];
+ *   depth_tolerance finite and > 0; normal_tolerance in [-1, 1]; max_history >= 1.  `reserved` is zeroed by the default call. */
+typedef struct rt_temporal_opts {
+	rt_denoise_opts denoise;
+	float alpha_color;      /* default 0.2 */
+	float alpha_moments;    /* default 0.2 */
+	float depth_tolerance;  /* default 0.1 (relative) */
+	float normal_tolerance; /* default 0.9 (cosine) */
+	uint32_t max_history;   /* default 32 */
+	uint32_t reserved[7];
+} rt_temporal_opts;
+/* color / albedo / normal: w*h*3; depth: w*h.  albedo and normal may be NULL. */
+typedef struct rt_temporal_inputs {
+	const float *color, *albedo, *normal, *depth;
+} rt_temporal_inputs;
+int rt_temporal_opts_default(rt_temporal_opts *out);
+/* One history buffer: 48 bytes per pixel.  The workspace of rt_denoise_temporal_device: 32 bytes per pixel (two float4 planes). */
+int rt_temporal_history_bytes(const rt_temporal_opts *opts, uint64_t *bytes);
+int rt_temporal_workspace_bytes(const rt_temporal_opts *opts, uint64_t *bytes);
+/* Checks (the device last): RT_ERR_INVALID_ARGUMENT for a NULL scene, inputs, cam, opts, color, depth, out, history_out (device
+ * call) or workspace (device call), a NULL prev_cam with a history_in, width or height < 2, an option out of range, a history or
+ * the workspace not 16-byte aligned, and any overlap between a buffer written (out, motion, history_out, workspace) and any other
+ * buffer (history_in and history_out included); RT_ERR_UNSUPPORTED for more than 2^31 pixels; RT_ERR_NO_DEVICE for a host-only scene.
+ * A multi-device head runs on devices[0].  No side effects: what rt_last_kernel_ms, rt_last_launch_info and a following rt_render
+ * return is unchanged.
+ * rt_denoise_temporal_device: DEVICE buffers on the scene's GPU, asynchronous on hip_stream; it allocates nothing and keeps no state
+ *   (the caller alternates two history buffers), so it can be captured into a graph from its first call.  d_history_in NULL = no
+ *   history (prev_cam is then ignored).  d_motion (NULL = not written): w*h*2 floats (dx, dy) in pixels, previous minus current.
+ * rt_denoise_temporal: HOST buffers, blocking.  The scene keeps two history buffers, the previous camera and the frame size; the
+ *   first call after rt_scene_create, after rt_denoise_temporal_reset or with a frame size other than the last call's has no
+ *   history.  host_motion may be NULL.  rt_denoise_temporal_reset forgets the history (no GPU work; any scene). */
+int rt_denoise_temporal_device(rt_scene *scene, const rt_temporal_inputs *device_in, const rt_camera *cam, const rt_camera *prev_cam,
+                               const void *d_history_in, void *d_history_out, const rt_temporal_opts *opts, void *d_workspace,
+                               float *d_out, float *d_motion, void *hip_stream);
+int rt_denoise_temporal(rt_scene *scene, const rt_temporal_inputs *host_in, const rt_camera *cam, const rt_temporal_opts *opts,
+                        float *host_out, float *host_motion);
+int rt_denoise_temporal_reset(rt_scene *scene);
+
 /* Division by a constant a launch knows beforehand (image size - 1, sky table resolution, pi, 2 pi): the kernels replace `x / c` by
  * two fma steps on rc = RN(1 / c) where -- and only where -- the host has verified, by enumerating all 2^23 significands of x, that
  * this returns the bits of the division (csrc/rt_build.cpp verified_reciprocal, csrc/rt_lean.h div_by_verified).  This call runs that

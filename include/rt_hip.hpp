@@ -387,6 +387,56 @@ inline Denoised render_denoised(const RenderOptions &o, const SimpleCamera &came
 	return r;
 }
 
+// Temporal accumulation with camera reprojection (rt_hip.h rt_temporal_opts): the options a caller sets; defaults as
+// rt_temporal_opts_default.
+struct TemporalOptions {
+	DenoiseOptions denoise;
+	float alpha_color = 0.2f, alpha_moments = 0.2f, depth_tolerance = 0.1f, normal_tolerance = 0.9f;
+	uint32_t max_history = 32;
+};
+inline rt_temporal_opts temporal_opts(const TemporalOptions &t, uint32_t width, uint32_t height)
+{
+	rt_temporal_opts o;
+	check(rt_temporal_opts_default(&o));
+	o.denoise = denoise_opts(t.denoise, width, height);
+	o.alpha_color = t.alpha_color;
+	o.alpha_moments = t.alpha_moments;
+	o.depth_tolerance = t.depth_tolerance;
+	o.normal_tolerance = t.normal_tolerance;
+	o.max_history = t.max_history;
+	return o;
+}
+// One camera path through a static scene: each call filters one frame (render + render_aov of the same passes, with depth) and
+// accumulates it with the frames before, reprojected through the camera change (rt_denoise_temporal; blocking).  The history
+// buffers and the previous camera live on the scene: one TemporalDenoiser per scene at a time.  reset() (and a new frame size)
+// starts over, e.g. at a cut.
+class TemporalDenoiser {
+  public:
+	TemporalDenoiser(const Bvh &bvh, uint32_t width, uint32_t height, const TemporalOptions &t = TemporalOptions())
+	    : bvh_(bvh), opts_(temporal_opts(t, width, height))
+	{
+		reset();
+	}
+	// returns the filtered frame (w*h*3); *motion (unless nullptr) gets w*h*2 floats, the pixel offsets into the previous frame
+	std::vector<float> operator()(const std::vector<float> &color, const AovBuffers &aov, const SimpleCamera &camera,
+	                              std::vector<float> *motion = nullptr)
+	{
+		auto ptr = [](const std::vector<float> &v) { return v.empty() ? nullptr : v.data(); };
+		const rt_temporal_inputs in = {color.data(), ptr(aov.albedo), ptr(aov.normal), ptr(aov.depth)};
+		const size_t n = (size_t)opts_.denoise.width * opts_.denoise.height;
+		std::vector<float> out(n * 3);
+		if (motion)
+			motion->resize(n * 2);
+		check(rt_denoise_temporal(bvh_.raw(), &in, &camera.raw(), &opts_, out.data(), motion ? motion->data() : nullptr));
+		return out;
+	}
+	void reset() { check(rt_denoise_temporal_reset(bvh_.raw())); }
+
+  private:
+	const Bvh &bvh_;
+	rt_temporal_opts opts_;
+};
+
 struct Presentation { // what render_tui keeps: the mean image and the ray total (src/main.rs:160-173)
 	SamplerProgress sampler_progress;
 	Presentation(uint64_t pixel_num) : sampler_progress(pixel_num, 3) {}

@@ -233,6 +233,28 @@ class DenoiseInputs(C.Structure):  # rt_denoise_inputs
 
 DENOISE_INPUTS = ("color", "albedo", "normal", "depth", "variance")
 DENOISE_WORKSPACE_BYTES_PER_PIXEL = 48  # three float4 planes
+
+
+class TemporalOpts(C.Structure):  # rt_temporal_opts
+    _fields_ = [
+        ("denoise", DenoiseOpts),
+        ("alpha_color", C.c_float),
+        ("alpha_moments", C.c_float),
+        ("depth_tolerance", C.c_float),
+        ("normal_tolerance", C.c_float),
+        ("max_history", C.c_uint32),
+        ("reserved", C.c_uint32 * 7),
+    ]
+
+
+class TemporalInputs(C.Structure):  # rt_temporal_inputs
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in ("color", "albedo", "normal", "depth")]
+
+
+TEMPORAL_INPUTS = ("color", "albedo", "normal", "depth")
+TEMPORAL_OPTIONS = ("alpha_color", "alpha_moments", "depth_tolerance", "normal_tolerance", "max_history")
+TEMPORAL_HISTORY_BYTES_PER_PIXEL = 48  # H0 = (e_1, n), H1 = (n^, z), H2 = (m1, m2, 0, 0): three float4 planes
+TEMPORAL_WORKSPACE_BYTES_PER_PIXEL = 32  # the denoiser's two (e, Var) planes
 AOV_NO_ID = 0xFFFFFFFF  # primitive / material of a pass that missed
 
 # rt_presentation_update: int (*)(void *data, const rt_sampler_progress *, uint64_t samples_done)
@@ -256,6 +278,8 @@ EXPECTED_SIZES = {
     "rt_aov_buffers": (AovBuffers, 48),
     "rt_denoise_opts": (DenoiseOpts, 48),
     "rt_denoise_inputs": (DenoiseInputs, 40),
+    "rt_temporal_opts": (TemporalOpts, 96),
+    "rt_temporal_inputs": (TemporalInputs, 32),
 }
 
 # every symbol include/rt_hip.h declares
@@ -305,6 +329,12 @@ EXPORTED_SYMBOLS = [
     "rt_denoise",
     "rt_denoise_device",
     "rt_render_denoised",
+    "rt_temporal_opts_default",
+    "rt_temporal_history_bytes",
+    "rt_temporal_workspace_bytes",
+    "rt_denoise_temporal_device",
+    "rt_denoise_temporal",
+    "rt_denoise_temporal_reset",
 ]
 
 

@@ -21,6 +21,7 @@
 #include "rt_types.h"
 #include "rt_aov.h"
 #include "rt_denoise.h"
+#include "rt_temporal.h"
 
 namespace rt {
 size_t render_lds_bytes(const DevScene &S, bool sky_lds, bool scene_lds, uint32_t waves_per_block, uint32_t stack_cap);
@@ -144,6 +145,10 @@ struct rt_scene {
 	uint32_t *d_prim_desc = nullptr;       // rt_render_aov: BVH slot -> rt_scene_desc index, uploaded on first use (in `allocations`)
 	char *d_denoise = nullptr;             // rt_denoise / rt_render_denoised: device frames + workspace, grown on first use
 	size_t d_denoise_bytes = 0;
+	char *d_temporal = nullptr;            // rt_denoise_temporal: its two history buffers, for frames of temporal_w x temporal_h
+	uint32_t temporal_w = 0, temporal_h = 0;
+	int temporal_cur = -1;                 // the history buffer the last call wrote; -1 = no history
+	rt_camera temporal_prev{};             // the camera of that call
 };
 
 template <class T> static int upload(rt_scene *s, const T *src, size_t count, const T **dst)
@@ -609,6 +614,8 @@ void rt_scene_destroy(rt_scene *s)
 		(void)hipFree(s->d_rgb8);
 	if (s->d_denoise)
 		(void)hipFree(s->d_denoise);
+	if (s->d_temporal)
+		(void)hipFree(s->d_temporal);
 	if (s->d_stack_ovf)
 		(void)hipFree(s->d_stack_ovf);
 	for (int b = 0; b < 2; ++b) {
@@ -2448,6 +2455,214 @@ int rt_render_denoised(rt_scene *s, const rt_camera *camera, const rt_render_opt
 	if (rc == RT_OK && rays_shot)
 		*rays_shot = rays[0] + rays[1];
 	return rc;
+}
+
+} // extern "C"
+
+// ---- temporal accumulation with camera reprojection (rt_temporal.hip) ----
+static int temporal_opts_check(const rt_temporal_opts *o)
+{
+	const uint64_t w = o->denoise.width, h = o->denoise.height;
+	if (w < 2 || h < 2)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: width and height must be >= 2 (u and v divide by W-1 and H-1)");
+	int rc = denoise_opts_check(&o->denoise, w, h);
+	if (rc != RT_OK)
+		return rc;
+	if (!(o->alpha_color > 0.0f && o->alpha_color <= 1.0f) || !(o->alpha_moments > 0.0f && o->alpha_moments <= 1.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: alpha_color and alpha_moments must be in (0, 1]");
+	if (!std::isfinite(o->depth_tolerance) || !(o->depth_tolerance > 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: depth_tolerance must be finite and > 0");
+	if (!(o->normal_tolerance >= -1.0f && o->normal_tolerance <= 1.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: normal_tolerance must be in [-1, 1]");
+	if (o->max_history < 1)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: max_history must be >= 1");
+	return RT_OK;
+}
+
+// argument checks of rt_denoise_temporal(_device), the device last; hist_out and ws are checked for the device call only
+static int temporal_check(const rt_scene *s, const rt_temporal_inputs *in, const rt_camera *cam, const rt_camera *prev,
+                          const rt_temporal_opts *o, const void *hist_in, const void *hist_out, const void *ws, const float *out,
+                          const float *motion, bool device)
+{
+	if (!s || !in || !cam || !o)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (!in->color || !in->depth || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: color, depth and out must not be NULL");
+	if (device && (!hist_out || !ws))
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: history_out and the workspace must not be NULL");
+	if (hist_in && !prev)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: a history needs the previous camera");
+	int rc = temporal_opts_check(o);
+	if (rc != RT_OK)
+		return rc;
+	const uint64_t n = (uint64_t)o->denoise.width * o->denoise.height;
+	if (device) {
+		const void *aligned[3] = {hist_in, hist_out, ws};
+		for (const void *a : aligned)
+			if (reinterpret_cast<uintptr_t>(a) % 16u != 0u)
+				return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: the histories and the workspace must be 16-byte aligned");
+	}
+	// every buffer written against every other buffer (inputs may share memory with one another)
+	const void *buf[9] = {out, motion, hist_out, ws, in->color, in->albedo, in->normal, in->depth, hist_in};
+	const uint64_t bytes[9] = {12 * n, 8 * n, kTemporalHistoryBytesPerPixel * n, kTemporalWorkspaceBytesPerPixel * n,
+	                           12 * n, 12 * n, 12 * n, 4 * n, kTemporalHistoryBytesPerPixel * n};
+	for (int a = 0; a < 4; ++a)
+		for (int b = 0; b < 9; ++b)
+			if (a != b && ranges_overlap(buf[a], bytes[a], buf[b], bytes[b]))
+				return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: a buffer written overlaps another buffer");
+	if (s->device == RT_DEVICE_NONE)
+		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
+	return RT_OK;
+}
+
+static int temporal_bytes(const rt_temporal_opts *o, uint64_t per_pixel, uint64_t *bytes)
+{
+	if (!o || !bytes)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (o->denoise.width < 2 || o->denoise.height < 2)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: width and height must be >= 2");
+	const uint64_t n = (uint64_t)o->denoise.width * o->denoise.height;
+	if (n > (1ull << 31))
+		return fail(RT_ERR_UNSUPPORTED, "denoise_temporal: more than 2^31 pixels");
+	*bytes = per_pixel * n;
+	return RT_OK;
+}
+
+extern "C" {
+
+int rt_temporal_opts_default(rt_temporal_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	rt_denoise_opts_default(&out->denoise);
+	out->alpha_color = 0.2f;
+	out->alpha_moments = 0.2f;
+	out->depth_tolerance = 0.1f;
+	out->normal_tolerance = 0.9f;
+	out->max_history = 32;
+	return RT_OK;
+}
+
+int rt_temporal_history_bytes(const rt_temporal_opts *o, uint64_t *bytes)
+{
+	return temporal_bytes(o, kTemporalHistoryBytesPerPixel, bytes);
+}
+
+int rt_temporal_workspace_bytes(const rt_temporal_opts *o, uint64_t *bytes)
+{
+	return temporal_bytes(o, kTemporalWorkspaceBytesPerPixel, bytes);
+}
+
+int rt_denoise_temporal_device(rt_scene *s, const rt_temporal_inputs *d_in, const rt_camera *cam, const rt_camera *prev_cam,
+                               const void *d_history_in, void *d_history_out, const rt_temporal_opts *o, void *d_workspace,
+                               float *d_out, float *d_motion, void *hip_stream)
+{
+	int rc = temporal_check(s, d_in, cam, prev_cam, o, d_history_in, d_history_out, d_workspace, d_out, d_motion, true);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device)); // a multi-device head runs on devices[0]
+	const uint64_t w = o->denoise.width, h = o->denoise.height;
+	const size_t n = (size_t)(w * h);
+	DevTemporalParams T;
+	std::memset(&T, 0, sizeof T);
+	T.width = (uint32_t)w;
+	T.height = (uint32_t)h;
+	std::memcpy(T.cam, cam, sizeof T.cam);
+	if (d_history_in)
+		std::memcpy(T.prev, prev_cam, sizeof T.prev);
+	T.alpha_c = o->alpha_color;
+	T.alpha_m = o->alpha_moments;
+	T.depth_tol = o->depth_tolerance;
+	T.normal_tol = o->normal_tolerance;
+	T.max_history = (float)o->max_history;
+	T.color = d_in->color;
+	T.albedo = d_in->albedo;
+	T.normal = d_in->normal;
+	T.depth = d_in->depth;
+	T.hist_in = static_cast<const float4 *>(d_history_in);
+	T.hist_out = static_cast<float4 *>(d_history_out);
+	T.motion = d_motion;
+	const rt_denoise_inputs din = {d_in->color, d_in->albedo, d_in->normal, d_in->depth, nullptr};
+	DevDenoiseParams D = denoise_params(&o->denoise, w, h, din, d_workspace, d_out);
+	D.guide = T.hist_out + n; // H1 of the history written is the guide plane
+	HIP_TRY(launch_temporal(static_cast<hipStream_t>(hip_stream), T, D));
+	return RT_OK;
+}
+
+int rt_denoise_temporal(rt_scene *s, const rt_temporal_inputs *in, const rt_camera *cam, const rt_temporal_opts *o, float *out,
+                        float *motion)
+{
+	int rc = temporal_check(s, in, cam, nullptr, o, nullptr, nullptr, nullptr, out, motion, false);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	const uint32_t w = o->denoise.width, h = o->denoise.height;
+	const size_t n = (size_t)w * h;
+	if (w != s->temporal_w || h != s->temporal_h) { // a new frame size: new histories, no history
+		if (s->d_temporal)
+			(void)hipFree(s->d_temporal);
+		s->d_temporal = nullptr;
+		s->temporal_w = s->temporal_h = 0;
+		s->temporal_cur = -1;
+		HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_temporal), 2 * kTemporalHistoryBytesPerPixel * n));
+		s->temporal_w = w;
+		s->temporal_h = h;
+	}
+	// the workspace (16-byte aligned), out, motion, then the inputs given, in rt_temporal_inputs order
+	const float *host[4] = {in->color, in->albedo, in->normal, in->depth};
+	const size_t per_px[4] = {3, 3, 3, 1};
+	size_t offset[4], total = kTemporalWorkspaceBytesPerPixel / 4 * n + 5 * n;
+	for (int c = 0; c < 4; ++c) {
+		offset[c] = total;
+		if (host[c])
+			total += per_px[c] * n;
+	}
+	rc = ensure_denoise_buffer(s, total * 4);
+	if (rc != RT_OK)
+		return rc;
+	float *base = reinterpret_cast<float *>(s->d_denoise);
+	float *d_out = base + kTemporalWorkspaceBytesPerPixel / 4 * n, *d_motion = d_out + 3 * n;
+	const float *dev[4];
+	hipError_t e = hipSuccess;
+	for (int c = 0; c < 4; ++c) {
+		dev[c] = host[c] ? base + offset[c] : nullptr;
+		if (host[c] && e == hipSuccess)
+			e = hipMemcpyAsync(base + offset[c], host[c], per_px[c] * n * 4, hipMemcpyHostToDevice, s->stream);
+	}
+	if (e != hipSuccess) {
+		(void)hipStreamSynchronize(s->stream);
+		return hip_fail(e, "denoise_temporal upload");
+	}
+	const rt_temporal_inputs d_in = {dev[0], dev[1], dev[2], dev[3]};
+	char *hist[2] = {s->d_temporal, s->d_temporal + kTemporalHistoryBytesPerPixel * n};
+	const int next = s->temporal_cur == 0 ? 1 : 0;
+	const void *h_in = s->temporal_cur >= 0 ? hist[s->temporal_cur] : nullptr;
+	s->temporal_cur = -1; // until this call has succeeded
+	rc = rt_denoise_temporal_device(s, &d_in, cam, &s->temporal_prev, h_in, hist[next], o, s->d_denoise, d_out,
+	                                motion ? d_motion : nullptr, s->stream);
+	if (rc == RT_OK)
+		e = hipMemcpyAsync(out, d_out, 3 * n * 4, hipMemcpyDeviceToHost, s->stream);
+	if (rc == RT_OK && e == hipSuccess && motion)
+		e = hipMemcpyAsync(motion, d_motion, 2 * n * 4, hipMemcpyDeviceToHost, s->stream);
+	const hipError_t e_sync = hipStreamSynchronize(s->stream);
+	if (rc == RT_OK && e == hipSuccess)
+		e = e_sync;
+	if (rc == RT_OK && e != hipSuccess)
+		rc = hip_fail(e, "denoise_temporal");
+	if (rc == RT_OK) {
+		s->temporal_cur = next;
+		s->temporal_prev = *cam;
+	}
+	return rc;
+}
+
+int rt_denoise_temporal_reset(rt_scene *s)
+{
+	if (!s)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	s->temporal_cur = -1;
+	return RT_OK;
 }
 
 } // extern "C"

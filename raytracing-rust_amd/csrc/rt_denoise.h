@@ -25,4 +25,9 @@ struct DevDenoiseParams {
 // prepass (one or two launches) + one launch per iteration, all on `stream`; no allocation, no synchronisation
 hipError_t launch_denoise(hipStream_t stream, const DevDenoiseParams &P);
 
+// the parts rt_temporal.hip reuses: the 5 x 5 spatial variance (plane1 -> plane0) and iteration i (step 2^i; the last one,
+// i + 1 == P.iterations, remodulates into P.out and ignores dst)
+void launch_denoise_variance(hipStream_t stream, const DevDenoiseParams &P);
+void launch_denoise_iteration(hipStream_t stream, const DevDenoiseParams &P, uint32_t i, const float4 *src, float4 *dst);
+
 } // namespace rt

@@ -237,28 +237,48 @@ __global__ __launch_bounds__(256) void denoise_iteration_kernel(const DevDenoise
 	}
 }
 
+static void tile_grid(const DevDenoiseParams &P, uint32_t &tiles_x, uint32_t &n_tiles, dim3 &blocks)
+{
+	tiles_x = (P.width + 15u) / 16u;
+	n_tiles = tiles_x * ((P.height + 15u) / 16u);
+	blocks = dim3(std::min(n_tiles, kMaxBlocks));
+}
+
+void launch_denoise_variance(hipStream_t stream, const DevDenoiseParams &P)
+{
+	uint32_t tiles_x, n_tiles;
+	dim3 tile_blocks;
+	tile_grid(P, tiles_x, n_tiles, tile_blocks);
+	hipLaunchKernelGGL(denoise_variance_kernel, tile_blocks, dim3(256), 0, stream, P, tiles_x, n_tiles);
+}
+
+void launch_denoise_iteration(hipStream_t stream, const DevDenoiseParams &P, uint32_t i, const float4 *src, float4 *dst)
+{
+	uint32_t tiles_x, n_tiles;
+	dim3 tile_blocks;
+	tile_grid(P, tiles_x, n_tiles, tile_blocks);
+	const uint32_t step = 1u << i;
+	if (i + 1u == P.iterations)
+		hipLaunchKernelGGL(denoise_iteration_kernel<true>, tile_blocks, dim3(256), 0, stream, P, src, nullptr, step, tiles_x, n_tiles);
+	else
+		hipLaunchKernelGGL(denoise_iteration_kernel<false>, tile_blocks, dim3(256), 0, stream, P, src, dst, step, tiles_x, n_tiles);
+}
+
 hipError_t launch_denoise(hipStream_t stream, const DevDenoiseParams &P)
 {
 	const uint32_t n = P.width * P.height;
-	const uint32_t tiles_x = (P.width + 15u) / 16u, n_tiles = tiles_x * ((P.height + 15u) / 16u);
-	const dim3 pre_blocks(std::min<uint32_t>((n + 255u) / 256u, kMaxBlocks)), tile_blocks(std::min(n_tiles, kMaxBlocks));
+	const dim3 pre_blocks(std::min<uint32_t>((n + 255u) / 256u, kMaxBlocks));
 	if (P.half_a)
 		hipLaunchKernelGGL(denoise_prepass_kernel<2>, pre_blocks, dim3(256), 0, stream, P);
 	else if (P.variance)
 		hipLaunchKernelGGL(denoise_prepass_kernel<0>, pre_blocks, dim3(256), 0, stream, P);
 	else {
 		hipLaunchKernelGGL(denoise_prepass_kernel<1>, pre_blocks, dim3(256), 0, stream, P);
-		hipLaunchKernelGGL(denoise_variance_kernel, tile_blocks, dim3(256), 0, stream, P, tiles_x, n_tiles);
+		launch_denoise_variance(stream, P);
 	}
 	float4 *src = P.plane0, *dst = P.plane1;
 	for (uint32_t i = 0; i < P.iterations; ++i) {
-		const uint32_t step = 1u << i;
-		if (i + 1u == P.iterations)
-			hipLaunchKernelGGL(denoise_iteration_kernel<true>, tile_blocks, dim3(256), 0, stream, P, src, nullptr, step, tiles_x,
-			                   n_tiles);
-		else
-			hipLaunchKernelGGL(denoise_iteration_kernel<false>, tile_blocks, dim3(256), 0, stream, P, src, dst, step, tiles_x,
-			                   n_tiles);
+		launch_denoise_iteration(stream, P, i, src, dst);
 		std::swap(src, dst);
 	}
 	return hipGetLastError();

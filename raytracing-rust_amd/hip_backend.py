@@ -341,6 +341,66 @@ class HipScene:
                                         _p(noisy, C.c_float), C.byref(rays)))
         return clean, noisy, rays.value
 
+    # ---- temporal accumulation with camera reprojection (rt_denoise_temporal) ----
+    def denoise_temporal(self, color, camera, albedo=None, normal=None, depth=None, motion=False, **opts):
+        """rt_denoise_temporal: one frame of a camera path.  color (H, W, 3) f32 -- or the dict render_aov returns with the image
+        under "color" -- with the optional albedo / normal (H, W, 3) and the REQUIRED depth (H, W); camera: this frame's
+        abi.Camera.  The scene keeps the history between calls (temporal_reset forgets it; a new frame size starts over).
+        Returns out (H, W, 3) f32, or (out, motion (H, W, 2) f32) with motion=True.  Keyword options: those of denoise_opts and
+        of abi.TEMPORAL_OPTIONS.  Semantics: include/rt_hip.h rt_temporal_opts."""
+        guides = {}
+        if isinstance(color, dict):
+            guides, color = color, color["color"]
+        elif isinstance(albedo, dict):
+            guides, albedo = albedo, None
+        albedo, normal, depth = guides.get("albedo", albedo), guides.get("normal", normal), guides.get("depth", depth)
+        color = np.ascontiguousarray(color, dtype=np.float32)
+        if color.ndim != 3 or color.shape[2] != 3:
+            raise ValueError(f"color must be (H, W, 3), got {color.shape}")
+        if depth is None:
+            raise ValueError("denoise_temporal needs depth")
+        h, w = color.shape[:2]
+        ins, keep = abi.TemporalInputs(), [color]
+        ins.color = _p(color, C.c_float)
+        for name, a, shape in (("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
+            if a is None:
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != shape:
+                raise ValueError(f"{name} must be {shape}, got {a.shape}")
+            keep.append(a)
+            setattr(ins, name, _p(a, C.c_float))
+        o = temporal_opts(w, h, **opts)
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        mv = np.zeros((h, w, 2), dtype=np.float32) if motion else None
+        _check(lib().rt_denoise_temporal(self._h, C.byref(ins), C.byref(camera), C.byref(o), _p(out, C.c_float),
+                                         _p(mv, C.c_float) if motion else None))
+        return (out, mv) if motion else out
+
+    def temporal_reset(self):
+        """rt_denoise_temporal_reset: the next denoise_temporal call has no history."""
+        _check(lib().rt_denoise_temporal_reset(self._h))
+
+    def denoise_temporal_device(self, d_ptrs, camera, prev_camera, d_history_in, d_history_out, d_workspace, d_out, opts,
+                                d_motion=0, stream=0):
+        """rt_denoise_temporal_device: asynchronous, DEVICE buffers of the scene's GPU, no state.  d_ptrs = {input: device
+        pointer} over abi.TEMPORAL_INPUTS ("color" and "depth" required); d_history_in 0 = no history (prev_camera may then be
+        None); the histories temporal_history_bytes(opts) and the workspace temporal_workspace_bytes(opts) bytes, 16-byte
+        aligned; d_motion 0 = not written; opts: abi.TemporalOpts with the frame size set."""
+        ins = abi.TemporalInputs()
+        for name, ptr in d_ptrs.items():
+            if name not in abi.TEMPORAL_INPUTS:
+                raise ValueError(f"unknown temporal input {name!r}")
+            setattr(ins, name, C.cast(C.c_void_p(int(ptr)), C.POINTER(C.c_float)) if ptr else None)
+
+        def fp(ptr):
+            return C.cast(C.c_void_p(int(ptr)), C.POINTER(C.c_float)) if ptr else None
+
+        _check(lib().rt_denoise_temporal_device(
+            self._h, C.byref(ins), C.byref(camera), C.byref(prev_camera) if prev_camera is not None else None,
+            C.c_void_p(int(d_history_in) or None), C.c_void_p(int(d_history_out) or None), C.byref(opts),
+            C.c_void_p(int(d_workspace) or None), fp(d_out), fp(d_motion), C.c_void_p(stream)))
+
     # ---- AccelerationStructure::check_hit / check_hit_index for batches ----
     def check_hit(self, origins, directions):
         rays = _pack_rays(origins, directions)
@@ -464,6 +524,36 @@ def denoise_workspace_bytes(opts):
     """rt_denoise_workspace_bytes: the workspace rt_denoise_device needs for opts' frame size."""
     n = C.c_uint64()
     _check(lib().rt_denoise_workspace_bytes(C.byref(opts), C.byref(n)))
+    return n.value
+
+
+def temporal_opts(width, height, **kw):
+    """rt_temporal_opts_default with the frame size and any of the denoise_opts keywords (iterations, sigma_*) or
+    abi.TEMPORAL_OPTIONS set."""
+    o = abi.TemporalOpts()
+    _check(lib().rt_temporal_opts_default(C.byref(o)))
+    o.denoise.width, o.denoise.height = int(width), int(height)
+    for k, v in kw.items():
+        if k in ("iterations", "sigma_luminance", "sigma_normal", "sigma_depth"):
+            setattr(o.denoise, k, v)
+        elif k in abi.TEMPORAL_OPTIONS:
+            setattr(o, k, v)
+        else:
+            raise ValueError(f"unknown temporal option {k!r}")
+    return o
+
+
+def temporal_history_bytes(opts):
+    """rt_temporal_history_bytes: the size of one history buffer for opts' frame size."""
+    n = C.c_uint64()
+    _check(lib().rt_temporal_history_bytes(C.byref(opts), C.byref(n)))
+    return n.value
+
+
+def temporal_workspace_bytes(opts):
+    """rt_temporal_workspace_bytes: the workspace rt_denoise_temporal_device needs for opts' frame size."""
+    n = C.c_uint64()
+    _check(lib().rt_temporal_workspace_bytes(C.byref(opts), C.byref(n)))
     return n.value
 
 
