@@ -622,6 +622,99 @@ int rt_denoise_temporal(rt_scene *scene, const rt_temporal_inputs *host_in, cons
                         float *host_out, float *host_motion);
 int rt_denoise_temporal_reset(rt_scene *scene);
 
+/* ---- Display stage (csrc/rt_display.hip): a W x H RGB float frame (FRAME layout, what rt_render, rt_denoise* and
+ * rt_denoise_temporal* write) to 8-bit display pixels on the GPU -- luminance histogram, metered auto-exposure with eye adaptation,
+ * tone curve, output transfer function and quantisation.  f32 with the library's arithmetic contract (IEEE `/`, no fma, sums left
+ * to right); powf is include/rt_detmath.h's rt_powf, Philox is its rt_philox4x32_10.  Per pixel p = y*W + x with colour (r, g, b):
+ *   Y = 0.2126f*r + 0.7152f*g + 0.0722f*b (the denoiser's lum).  p is METERED when r, g, b and Y are finite and Y > 0.
+ * Histogram: 256 bins, 8 per octave, over [2^-16, 2^16), of the metered pixels only: bin = clamp((int)(bits(Y) >> 20) - 888, 0, 255)
+ *   with bits(Y) the uint32 of the float (below the range: bin 0, above it: bin 255).  Exact integer counts.
+ * Metering (both modes; in f64): T = number of metered pixels, lo = floor(T*meter_low), hi = ceil(T*meter_high); bin b covers the
+ *   ranks [C_b, C_b + n_b) (C_b = the counts of the bins below b) and weighs o_b = max(0, min(C_b + n_b, hi) - max(C_b, lo));
+ *   lambda_b = (double)((b >> 3) - 16) + (double)L[b & 7], L = {0.0874628413f, 0.247927513f, 0.392317423f, 0.523561956f,
+ *   0.643856190f, 0.754887502f, 0.857980995f, 0.954196310f} (L[m] = log2(1 + (m + 0.5)/8) as f32 literals);
+ *   num = sum o_b*lambda_b, den = sum o_b, both from +0 in bin order; metered = (float)(num / den), NaN when den == 0 (T == 0).
+ * Target: AUTO with den > 0: target = fminf(fmaxf(key_ev - metered, ev_min), ev_max) + exposure_ev; FIXED, or nothing metered:
+ *   target = exposure_ev.
+ * Adaptation: with a state whose frames > 0 and adaptation != 1: ev = prev + adaptation*(target - prev) (prev = the state's ev);
+ *   otherwise ev = target (adaptation 1 snaps exactly).  The state then holds ev, frames + 1 (saturating at 2^32 - 1) and metered.
+ *   The dither frame index F is the state's frames as read (0 without a state).
+ * Exposure: s = powf(2.0f, ev); x = c*s per channel.
+ * Tone curve (per pixel, on x):
+ *   CLAMP     y = x
+ *   REINHARD  extended Reinhard on luminance: Yx = lum(x); where Yx > 0 and finite, y = x*(((Yx*(1.0f + Yx/(w*w)))/(1.0f + Yx))/Yx)
+ *             per channel (w*w rounded to f32 first); elsewhere (Yx <= 0, NaN or inf) y = x, left to the clamp
+ *   ACES      Narkowicz's fit per channel: y = (x*(2.51f*x + 0.03f))/(x*(2.43f*x + 0.59f) + 0.14f)
+ *   HABLE     Uncharted 2 per channel: y = f(x)/f(w), f(x) = (x*(A*x + C*B) + D*E)/(x*(A*x + B) + D*F) - E/F with A .. F = 0.15f,
+ *             0.50f, 0.10f, 0.20f, 0.02f, 0.30f and C*B, D*E, D*F, E/F rounded to f32
+ * Clamp: v = fminf(fmaxf(y, 0.0f), 1.0f) (NaN becomes 0).
+ * Transfer: SRGB t = v <= 0.0031308f ? 12.92f*v : 1.055f*powf(v, 1.0f/2.4f) - 0.055f;  GAMMA t = powf(v, 1.0f/gamma);  LINEAR t = v.
+ * Quantisation, sat(q) = 0 if !(q > 0), 255 if q >= 255, else (uint8)q (truncation):
+ *   ROUND      sat(t*255.0f + 0.5f)
+ *   DITHER     sat(floorf(t*255.0f + u)), u = (float)(word >> 8) * 0x1p-24f; r, g and b take words 0, 1 and 2 of one Philox4x32-10
+ *              block with counter (x, y, F, 0) and key ((uint32)seed, (uint32)(seed >> 32))
+ *   REFERENCE  sat(t*255.999f): the shape of rt_output_rgb8's conversion
+ * Pixels: RGBA8 (r, g, b, 255), BGRA8 (b, g, r, 255), RGB8 (r, g, b); row-major, y down, no padding.
+ * With FIXED, exposure_ev 0, CLAMP, GAMMA g, REFERENCE and RGB8 the bytes are those of rt_output_rgb8_device with gamma g
+ * (powf(2, 0) is 1 exactly) for every input -- NaN, +inf, zeros, negatives -- except where the reference's powf gives a value
+ * below 0 a nonzero result: a negative value when 1/g is an even integer (a positive power), and -inf unless 1/g is an odd
+ * integer (+inf, 255).  The clamp maps both to 0.
+ * Options: width, height >= 1; every enum in range; exposure_ev, key_ev, ev_min, ev_max finite, ev_min <= ev_max;
+ * 0 <= meter_low < meter_high <= 1; adaptation in (0, 1]; white and gamma finite and > 0.  `reserved` is zeroed by the default call. */
+typedef enum { RT_EXPOSURE_FIXED = 0, RT_EXPOSURE_AUTO = 1 } rt_exposure_mode;
+typedef enum { RT_TONEMAP_CLAMP = 0, RT_TONEMAP_REINHARD = 1, RT_TONEMAP_ACES = 2, RT_TONEMAP_HABLE = 3 } rt_tonemap;
+typedef enum { RT_TRANSFER_SRGB = 0, RT_TRANSFER_GAMMA = 1, RT_TRANSFER_LINEAR = 2 } rt_transfer;
+typedef enum { RT_QUANT_ROUND = 0, RT_QUANT_DITHER = 1, RT_QUANT_REFERENCE = 2 } rt_quantiser;
+typedef enum { RT_PIXEL_RGBA8 = 0, RT_PIXEL_BGRA8 = 1, RT_PIXEL_RGB8 = 2 } rt_pixel_format;
+typedef struct rt_display_opts {
+	uint32_t width, height;
+	int32_t exposure_mode; /* rt_exposure_mode, default AUTO */
+	int32_t tonemap;       /* rt_tonemap, default ACES */
+	int32_t transfer;      /* rt_transfer, default SRGB */
+	int32_t quantiser;     /* rt_quantiser, default DITHER */
+	int32_t pixel_format;  /* rt_pixel_format, default RGBA8 */
+	float exposure_ev;     /* FIXED: the EV used; AUTO: compensation added after the clamp.  Default 0 */
+	float key_ev;          /* AUTO: log2 of the target middle grey; default log2(0.18) = -2.47393119f */
+	float meter_low, meter_high; /* metered luminance percentiles; default 0.10, 0.90 */
+	float ev_min, ev_max;  /* AUTO: clamp of the metered EV; default -16, 16 */
+	float adaptation;      /* default 1 */
+	float white;           /* REINHARD / HABLE white point; default 4 */
+	float gamma;           /* GAMMA transfer; default 2.2 */
+	uint64_t seed;         /* DITHER stream; default 0 */
+	uint32_t reserved[8];
+} rt_display_opts;
+/* 16 bytes; all zero = no history.  Callers may read it (e.g. to show the exposure); `reserved` is never written. */
+typedef struct rt_display_state {
+	float ev;         /* EV applied to the last frame */
+	uint32_t frames;  /* frames seen, saturating; also the dither frame index */
+	float metered;    /* metered mean log2 luminance of the last frame (NaN: nothing metered) */
+	uint32_t reserved;
+} rt_display_state;
+int rt_display_opts_default(rt_display_opts *out);
+/* The workspace of rt_display_device: 16 + 1024 * min(256, max(1, ceil(W*H / 2048))) bytes (a parameter block, then one row of
+ * 256 partial counts per histogram workgroup).  The output: W*H*4 bytes (RGBA8, BGRA8) or W*H*3 (RGB8). */
+int rt_display_workspace_bytes(const rt_display_opts *opts, uint64_t *bytes);
+int rt_display_output_bytes(const rt_display_opts *opts, uint64_t *bytes);
+/* Checks (the device last): RT_ERR_INVALID_ARGUMENT for a NULL scene, input, opts or output, width or height 0, an enum out of
+ * range, an option out of its range, a workspace (device call) that is NULL or not 16-byte aligned, and an output, histogram, state
+ * or workspace that overlaps any other buffer; RT_ERR_UNSUPPORTED for more than 2^31 pixels; RT_ERR_NO_DEVICE for a host-only
+ * scene.  A multi-device head runs on devices[0].  No side effects: what rt_last_kernel_ms, rt_last_launch_info and a following
+ * rt_render return is unchanged.
+ * rt_display_device: DEVICE buffers on the scene's GPU, asynchronous on hip_stream; it allocates nothing and keeps no state of its
+ *   own, so it can be captured into a graph from its first call.  d_state (NULL = no adaptation, dither frame 0) is read and written
+ *   in place on the device: a captured graph replayed N times advances exposure and dither exactly as N eager calls do.
+ *   d_histogram (NULL = not written): the 256 counts.  Any alignment of d_rgb and d_out is accepted (a 16-byte aligned input with
+ *   a 16-byte aligned RGBA8 / BGRA8 or 4-byte aligned RGB8 output takes the vectorised kernels).
+ * rt_display: HOST buffers, blocking.  The scene keeps the state (and its device buffers, grown for larger frames only); the first
+ *   call after rt_scene_create, after rt_display_reset or with a frame size other than the last call's starts from a zero state.
+ *   host_state (NULL = not wanted) receives the state after the call; host_histogram (NULL = not wanted) the 256 counts.
+ *   rt_display_reset forgets the state (no GPU work; any scene). */
+int rt_display_device(rt_scene *scene, const float *d_rgb, const rt_display_opts *opts, rt_display_state *d_state,
+                      void *d_workspace, void *d_out, uint32_t *d_histogram, void *hip_stream);
+int rt_display(rt_scene *scene, const float *host_rgb, const rt_display_opts *opts, void *host_out, rt_display_state *host_state,
+               uint32_t *host_histogram);
+int rt_display_reset(rt_scene *scene);
+
 /* Division by a constant a launch knows beforehand (image size - 1, sky table resolution, pi, 2 pi): the kernels replace `x / c` by
  * two fma steps on rc = RN(1 / c) where -- and only where -- the host has verified, by enumerating all 2^23 significands of x, that
  * this returns the bits of the division (csrc/rt_build.cpp verified_reciprocal, csrc/rt_lean.h div_by_verified).  This call runs that

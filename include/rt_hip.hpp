@@ -437,6 +437,70 @@ class TemporalDenoiser {
 	rt_temporal_opts opts_;
 };
 
+// The display stage (rt_hip.h rt_display_opts): the options a caller sets; defaults as rt_display_opts_default.
+struct DisplayOptions {
+	rt_exposure_mode exposure_mode = RT_EXPOSURE_AUTO;
+	rt_tonemap tonemap = RT_TONEMAP_ACES;
+	rt_transfer transfer = RT_TRANSFER_SRGB;
+	rt_quantiser quantiser = RT_QUANT_DITHER;
+	rt_pixel_format pixel_format = RT_PIXEL_RGBA8;
+	float exposure_ev = 0.0f, key_ev = -2.47393119f, meter_low = 0.10f, meter_high = 0.90f, ev_min = -16.0f, ev_max = 16.0f;
+	float adaptation = 1.0f, white = 4.0f, gamma = 2.2f;
+	uint64_t seed = 0;
+};
+inline rt_display_opts display_opts(const DisplayOptions &d, uint32_t width, uint32_t height)
+{
+	rt_display_opts o;
+	check(rt_display_opts_default(&o));
+	o.width = width;
+	o.height = height;
+	o.exposure_mode = d.exposure_mode;
+	o.tonemap = d.tonemap;
+	o.transfer = d.transfer;
+	o.quantiser = d.quantiser;
+	o.pixel_format = d.pixel_format;
+	o.exposure_ev = d.exposure_ev;
+	o.key_ev = d.key_ev;
+	o.meter_low = d.meter_low;
+	o.meter_high = d.meter_high;
+	o.ev_min = d.ev_min;
+	o.ev_max = d.ev_max;
+	o.adaptation = d.adaptation;
+	o.white = d.white;
+	o.gamma = d.gamma;
+	o.seed = d.seed;
+	return o;
+}
+// A sequence of frames to 8-bit display pixels (rt_display; blocking): each call meters, adapts the exposure from the frames
+// before, tone-maps and quantises.  The exposure state lives on the scene: one Display per scene at a time.  reset() (and a new
+// frame size) starts over, e.g. at a cut.
+class Display {
+  public:
+	Display(const Bvh &bvh, uint32_t width, uint32_t height, const DisplayOptions &d = DisplayOptions())
+	    : bvh_(bvh), opts_(display_opts(d, width, height))
+	{
+		reset();
+	}
+	// rgb: width*height*3 floats; returns width*height*4 (RGBA8 / BGRA8) or *3 (RGB8) bytes.  *state / *histogram (unless nullptr)
+	// receive the state after the call and the 256 luminance counts.
+	std::vector<uint8_t> operator()(const std::vector<float> &rgb, rt_display_state *state = nullptr,
+	                                std::vector<uint32_t> *histogram = nullptr)
+	{
+		uint64_t bytes = 0;
+		check(rt_display_output_bytes(&opts_, &bytes));
+		std::vector<uint8_t> out((size_t)bytes);
+		if (histogram)
+			histogram->resize(256);
+		check(rt_display(bvh_.raw(), rgb.data(), &opts_, out.data(), state, histogram ? histogram->data() : nullptr));
+		return out;
+	}
+	void reset() { check(rt_display_reset(bvh_.raw())); }
+
+  private:
+	const Bvh &bvh_;
+	rt_display_opts opts_;
+};
+
 struct Presentation { // what render_tui keeps: the mean image and the ray total (src/main.rs:160-173)
 	SamplerProgress sampler_progress;
 	Presentation(uint64_t pixel_num) : sampler_progress(pixel_num, 3) {}

@@ -257,6 +257,56 @@ TEMPORAL_HISTORY_BYTES_PER_PIXEL = 48  # H0 = (e_1, n), H1 = (n^, z), H2 = (m1, 
 TEMPORAL_WORKSPACE_BYTES_PER_PIXEL = 32  # the denoiser's two (e, Var) planes
 AOV_NO_ID = 0xFFFFFFFF  # primitive / material of a pass that missed
 
+# display stage (rt_display): rt_exposure_mode, rt_tonemap, rt_transfer, rt_quantiser, rt_pixel_format
+RT_EXPOSURE_FIXED, RT_EXPOSURE_AUTO = range(2)
+RT_TONEMAP_CLAMP, RT_TONEMAP_REINHARD, RT_TONEMAP_ACES, RT_TONEMAP_HABLE = range(4)
+RT_TRANSFER_SRGB, RT_TRANSFER_GAMMA, RT_TRANSFER_LINEAR = range(3)
+RT_QUANT_ROUND, RT_QUANT_DITHER, RT_QUANT_REFERENCE = range(3)
+RT_PIXEL_RGBA8, RT_PIXEL_BGRA8, RT_PIXEL_RGB8 = range(3)
+DISPLAY_ENUMS = {  # option -> {name: value}
+    "exposure_mode": {"fixed": RT_EXPOSURE_FIXED, "auto": RT_EXPOSURE_AUTO},
+    "tonemap": {"clamp": RT_TONEMAP_CLAMP, "reinhard": RT_TONEMAP_REINHARD, "aces": RT_TONEMAP_ACES, "hable": RT_TONEMAP_HABLE},
+    "transfer": {"srgb": RT_TRANSFER_SRGB, "gamma": RT_TRANSFER_GAMMA, "linear": RT_TRANSFER_LINEAR},
+    "quantiser": {"round": RT_QUANT_ROUND, "dither": RT_QUANT_DITHER, "reference": RT_QUANT_REFERENCE},
+    "pixel_format": {"rgba8": RT_PIXEL_RGBA8, "bgra8": RT_PIXEL_BGRA8, "rgb8": RT_PIXEL_RGB8},
+}
+DISPLAY_HISTOGRAM_BINS = 256
+
+
+class DisplayOpts(C.Structure):  # rt_display_opts
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("exposure_mode", C.c_int32),
+        ("tonemap", C.c_int32),
+        ("transfer", C.c_int32),
+        ("quantiser", C.c_int32),
+        ("pixel_format", C.c_int32),
+        ("exposure_ev", C.c_float),
+        ("key_ev", C.c_float),
+        ("meter_low", C.c_float),
+        ("meter_high", C.c_float),
+        ("ev_min", C.c_float),
+        ("ev_max", C.c_float),
+        ("adaptation", C.c_float),
+        ("white", C.c_float),
+        ("gamma", C.c_float),
+        ("seed", C.c_uint64),
+        ("reserved", C.c_uint32 * 8),
+    ]
+
+
+class DisplayState(C.Structure):  # rt_display_state
+    _fields_ = [
+        ("ev", C.c_float),
+        ("frames", C.c_uint32),
+        ("metered", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
+DISPLAY_OPTIONS = tuple(n for n, _ in DisplayOpts._fields_ if n not in ("width", "height", "reserved"))
+
 # rt_presentation_update: int (*)(void *data, const rt_sampler_progress *, uint64_t samples_done)
 PresentationUpdate = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(SamplerProgressC), C.c_uint64)
 
@@ -280,6 +330,8 @@ EXPECTED_SIZES = {
     "rt_denoise_inputs": (DenoiseInputs, 40),
     "rt_temporal_opts": (TemporalOpts, 96),
     "rt_temporal_inputs": (TemporalInputs, 32),
+    "rt_display_opts": (DisplayOpts, 104),
+    "rt_display_state": (DisplayState, 16),
 }
 
 # every symbol include/rt_hip.h declares
@@ -335,6 +387,12 @@ EXPORTED_SYMBOLS = [
     "rt_denoise_temporal_device",
     "rt_denoise_temporal",
     "rt_denoise_temporal_reset",
+    "rt_display_opts_default",
+    "rt_display_workspace_bytes",
+    "rt_display_output_bytes",
+    "rt_display_device",
+    "rt_display",
+    "rt_display_reset",
 ]
 
 

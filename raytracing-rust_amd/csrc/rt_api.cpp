@@ -22,6 +22,7 @@
 #include "rt_aov.h"
 #include "rt_denoise.h"
 #include "rt_temporal.h"
+#include "rt_display.h"
 
 namespace rt {
 size_t render_lds_bytes(const DevScene &S, bool sky_lds, bool scene_lds, uint32_t waves_per_block, uint32_t stack_cap);
@@ -149,6 +150,10 @@ struct rt_scene {
 	uint32_t temporal_w = 0, temporal_h = 0;
 	int temporal_cur = -1;                 // the history buffer the last call wrote; -1 = no history
 	rt_camera temporal_prev{};             // the camera of that call
+	char *d_display = nullptr;             // rt_display: state, histogram, workspace, output and input, grown for larger frames
+	size_t d_display_bytes = 0;
+	uint32_t display_w = 0, display_h = 0; // the frame size of the last successful call
+	bool display_has_state = false;        // false: the next rt_display starts from a zero state
 };
 
 template <class T> static int upload(rt_scene *s, const T *src, size_t count, const T **dst)
@@ -616,6 +621,8 @@ void rt_scene_destroy(rt_scene *s)
 		(void)hipFree(s->d_denoise);
 	if (s->d_temporal)
 		(void)hipFree(s->d_temporal);
+	if (s->d_display)
+		(void)hipFree(s->d_display);
 	if (s->d_stack_ovf)
 		(void)hipFree(s->d_stack_ovf);
 	for (int b = 0; b < 2; ++b) {
@@ -2662,6 +2669,226 @@ int rt_denoise_temporal_reset(rt_scene *s)
 	if (!s)
 		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
 	s->temporal_cur = -1;
+	return RT_OK;
+}
+
+} // extern "C"
+
+// ---- display stage: histogram, auto-exposure, tone curve, transfer, quantisation (rt_display.hip) ----
+static bool finite_f(float v) { return std::isfinite(v); }
+
+static int display_opts_check(const rt_display_opts *o)
+{
+	if (o->width == 0 || o->height == 0)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: width and height must be >= 1");
+	if (o->exposure_mode < RT_EXPOSURE_FIXED || o->exposure_mode > RT_EXPOSURE_AUTO)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown exposure_mode");
+	if (o->tonemap < RT_TONEMAP_CLAMP || o->tonemap > RT_TONEMAP_HABLE)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown tonemap");
+	if (o->transfer < RT_TRANSFER_SRGB || o->transfer > RT_TRANSFER_LINEAR)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown transfer");
+	if (o->quantiser < RT_QUANT_ROUND || o->quantiser > RT_QUANT_REFERENCE)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown quantiser");
+	if (o->pixel_format < RT_PIXEL_RGBA8 || o->pixel_format > RT_PIXEL_RGB8)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown pixel_format");
+	if (!finite_f(o->exposure_ev) || !finite_f(o->key_ev))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: exposure_ev and key_ev must be finite");
+	if (!(o->meter_low >= 0.0f && o->meter_low < o->meter_high && o->meter_high <= 1.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: need 0 <= meter_low < meter_high <= 1");
+	if (!finite_f(o->ev_min) || !finite_f(o->ev_max) || !(o->ev_min <= o->ev_max))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: ev_min and ev_max must be finite with ev_min <= ev_max");
+	if (!(o->adaptation > 0.0f && o->adaptation <= 1.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: adaptation must be in (0, 1]");
+	if (!finite_f(o->white) || !(o->white > 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: white must be finite and > 0");
+	if (!finite_f(o->gamma) || !(o->gamma > 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: gamma must be finite and > 0");
+	if ((uint64_t)o->width * o->height > (1ull << 31))
+		return fail(RT_ERR_UNSUPPORTED, "display: more than 2^31 pixels");
+	return RT_OK;
+}
+
+static uint64_t display_out_bytes(const rt_display_opts *o)
+{
+	return (uint64_t)o->width * o->height * (o->pixel_format == RT_PIXEL_RGB8 ? 3u : 4u);
+}
+
+// argument checks of rt_display(_device), the device last; ws is checked for the device call only
+static int display_check(const rt_scene *s, const float *rgb, const rt_display_opts *o, const void *state, const void *ws,
+                         const void *out, const void *histogram, bool device)
+{
+	if (!s || !rgb || !o || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	int rc = display_opts_check(o);
+	if (rc != RT_OK)
+		return rc;
+	const uint64_t n = (uint64_t)o->width * o->height;
+	if (device && (!ws || reinterpret_cast<uintptr_t>(ws) % 16u != 0u))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: the workspace must not be NULL and must be 16-byte aligned");
+	// every buffer written (out, histogram, state, workspace) against every other buffer
+	const void *buf[5] = {out, histogram, state, device ? ws : nullptr, rgb};
+	const uint64_t bytes[5] = {display_out_bytes(o), 4ull * kDisplayBins, sizeof(rt_display_state), display_workspace_bytes(n), 12 * n};
+	for (int a = 0; a < 4; ++a)
+		for (int b = 0; b < 5; ++b)
+			if (a != b && ranges_overlap(buf[a], bytes[a], buf[b], bytes[b]))
+				return fail(RT_ERR_INVALID_ARGUMENT, "display: a buffer written overlaps another buffer");
+	if (s->device == RT_DEVICE_NONE)
+		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
+	return RT_OK;
+}
+
+extern "C" {
+
+int rt_display_opts_default(rt_display_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	out->exposure_mode = RT_EXPOSURE_AUTO;
+	out->tonemap = RT_TONEMAP_ACES;
+	out->transfer = RT_TRANSFER_SRGB;
+	out->quantiser = RT_QUANT_DITHER;
+	out->pixel_format = RT_PIXEL_RGBA8;
+	out->exposure_ev = 0.0f;
+	out->key_ev = -2.47393119f; // log2(0.18)
+	out->meter_low = 0.10f;
+	out->meter_high = 0.90f;
+	out->ev_min = -16.0f;
+	out->ev_max = 16.0f;
+	out->adaptation = 1.0f;
+	out->white = 4.0f;
+	out->gamma = 2.2f;
+	return RT_OK;
+}
+
+int rt_display_workspace_bytes(const rt_display_opts *o, uint64_t *bytes)
+{
+	if (!o || !bytes)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (o->width == 0 || o->height == 0)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: width and height must be >= 1");
+	const uint64_t n = (uint64_t)o->width * o->height;
+	if (n > (1ull << 31))
+		return fail(RT_ERR_UNSUPPORTED, "display: more than 2^31 pixels");
+	*bytes = display_workspace_bytes(n);
+	return RT_OK;
+}
+
+int rt_display_output_bytes(const rt_display_opts *o, uint64_t *bytes)
+{
+	if (!o || !bytes)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (o->width == 0 || o->height == 0)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: width and height must be >= 1");
+	if (o->pixel_format < RT_PIXEL_RGBA8 || o->pixel_format > RT_PIXEL_RGB8)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown pixel_format");
+	if ((uint64_t)o->width * o->height > (1ull << 31))
+		return fail(RT_ERR_UNSUPPORTED, "display: more than 2^31 pixels");
+	*bytes = display_out_bytes(o);
+	return RT_OK;
+}
+
+int rt_display_device(rt_scene *s, const float *d_rgb, const rt_display_opts *o, rt_display_state *d_state, void *d_workspace,
+                      void *d_out, uint32_t *d_histogram, void *hip_stream)
+{
+	int rc = display_check(s, d_rgb, o, d_state, d_workspace, d_out, d_histogram, true);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device)); // a multi-device head runs on devices[0]
+	DevDisplayParams P;
+	std::memset(&P, 0, sizeof P);
+	P.n_px = o->width * o->height;
+	P.width = o->width;
+	P.mode = o->exposure_mode;
+	P.tonemap = o->tonemap;
+	P.transfer = o->transfer;
+	P.quantiser = o->quantiser;
+	P.format = o->pixel_format;
+	P.exposure_ev = o->exposure_ev;
+	P.key_ev = o->key_ev;
+	P.meter_low = o->meter_low;
+	P.meter_high = o->meter_high;
+	P.ev_min = o->ev_min;
+	P.ev_max = o->ev_max;
+	P.adaptation = o->adaptation;
+	P.white2 = o->white * o->white;
+	P.hable_fw = display_hable(o->white);
+	P.inv_gamma = 1.0f / o->gamma;
+	P.seed_lo = (uint32_t)o->seed;
+	P.seed_hi = (uint32_t)(o->seed >> 32);
+	P.rgb = d_rgb;
+	P.state = d_state;
+	P.ws = static_cast<char *>(d_workspace);
+	P.out = d_out;
+	P.histogram = d_histogram;
+	HIP_TRY(launch_display(static_cast<hipStream_t>(hip_stream), P));
+	return RT_OK;
+}
+
+int rt_display(rt_scene *s, const float *host_rgb, const rt_display_opts *o, void *host_out, rt_display_state *host_state,
+               uint32_t *host_histogram)
+{
+	int rc = display_check(s, host_rgb, o, host_state, nullptr, host_out, host_histogram, false);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	const uint64_t n = (uint64_t)o->width * o->height;
+	// state (16), histogram (1024), workspace, output, input: every part 16-byte aligned
+	auto up16 = [](uint64_t b) { return (b + 15u) / 16u * 16u; };
+	const uint64_t off_hist = 16, off_ws = off_hist + 4ull * kDisplayBins, off_out = off_ws + display_workspace_bytes(n);
+	const uint64_t off_in = off_out + up16(display_out_bytes(o)), total = off_in + 12 * n;
+	if (total > s->d_display_bytes) { // grown for larger frames only; the state is kept on the host side meanwhile
+		rt_display_state keep{};
+		if (s->d_display && s->display_has_state)
+			HIP_TRY(hipMemcpy(&keep, s->d_display, sizeof keep, hipMemcpyDeviceToHost));
+		if (s->d_display)
+			(void)hipFree(s->d_display);
+		s->d_display = nullptr;
+		s->d_display_bytes = 0;
+		HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_display), total));
+		s->d_display_bytes = total;
+		HIP_TRY(hipMemcpy(s->d_display, &keep, sizeof keep, hipMemcpyHostToDevice));
+	}
+	char *base = s->d_display;
+	rt_display_state *d_state = reinterpret_cast<rt_display_state *>(base);
+	uint32_t *d_hist = reinterpret_cast<uint32_t *>(base + off_hist);
+	const bool fresh = !s->display_has_state || o->width != s->display_w || o->height != s->display_h;
+	s->display_has_state = false; // until this call has succeeded
+	hipError_t e = hipSuccess;
+	if (fresh)
+		e = hipMemsetAsync(d_state, 0, sizeof(rt_display_state), s->stream);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(base + off_in, host_rgb, 12 * n, hipMemcpyHostToDevice, s->stream);
+	if (e != hipSuccess) {
+		(void)hipStreamSynchronize(s->stream);
+		return hip_fail(e, "display upload");
+	}
+	rc = rt_display_device(s, reinterpret_cast<const float *>(base + off_in), o, d_state, base + off_ws, base + off_out, d_hist,
+	                       s->stream);
+	if (rc == RT_OK)
+		e = hipMemcpyAsync(host_out, base + off_out, display_out_bytes(o), hipMemcpyDeviceToHost, s->stream);
+	if (rc == RT_OK && e == hipSuccess && host_state)
+		e = hipMemcpyAsync(host_state, d_state, sizeof(rt_display_state), hipMemcpyDeviceToHost, s->stream);
+	if (rc == RT_OK && e == hipSuccess && host_histogram)
+		e = hipMemcpyAsync(host_histogram, d_hist, 4ull * kDisplayBins, hipMemcpyDeviceToHost, s->stream);
+	const hipError_t e_sync = hipStreamSynchronize(s->stream);
+	if (rc == RT_OK && e == hipSuccess)
+		e = e_sync;
+	if (rc == RT_OK && e != hipSuccess)
+		rc = hip_fail(e, "display");
+	if (rc == RT_OK) {
+		s->display_has_state = true;
+		s->display_w = o->width;
+		s->display_h = o->height;
+	}
+	return rc;
+}
+
+int rt_display_reset(rt_scene *s)
+{
+	if (!s)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	s->display_has_state = false;
 	return RT_OK;
 }
 

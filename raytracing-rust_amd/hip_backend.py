@@ -401,6 +401,48 @@ class HipScene:
             C.c_void_p(int(d_history_in) or None), C.c_void_p(int(d_history_out) or None), C.byref(opts),
             C.c_void_p(int(d_workspace) or None), fp(d_out), fp(d_motion), C.c_void_p(stream)))
 
+    # ---- display stage: auto-exposure, tone curve, transfer, 8-bit output (rt_display) ----
+    def display(self, image, histogram=False, **opts):
+        """rt_display: an (H, W, 3) f32 frame to (H, W, 4) uint8 (RGBA8 / BGRA8) or (H, W, 3) (RGB8).  The scene keeps the exposure
+        state between calls (display_reset forgets it; a new frame size starts over); display_state() is the state after the last
+        call.  histogram=True returns (pixels, the 256 uint32 counts).  Keyword options: display_opts'.  Semantics: include/rt_hip.h
+        rt_display_opts."""
+        a = np.ascontiguousarray(image, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"image must be (H, W, 3), got {a.shape}")
+        h, w = a.shape[:2]
+        o = display_opts(w, h, **opts)
+        out = np.zeros((h, w, 3 if o.pixel_format == abi.RT_PIXEL_RGB8 else 4), dtype=np.uint8)
+        hist = np.zeros(abi.DISPLAY_HISTOGRAM_BINS, dtype=np.uint32)
+        state = abi.DisplayState()
+        _check(lib().rt_display(self._h, _p(a, C.c_float), C.byref(o), out.ctypes.data_as(C.c_void_p), C.byref(state),
+                                _p(hist, C.c_uint32)))
+        self._display_state = state
+        return (out, hist) if histogram else out
+
+    def display_state(self):
+        """the abi.DisplayState the last display call left (zero before the first call and after display_reset)"""
+        st = abi.DisplayState()
+        if getattr(self, "_display_state", None) is not None:
+            C.memmove(C.byref(st), C.byref(self._display_state), C.sizeof(st))
+        return st
+
+    def display_reset(self):
+        """rt_display_reset: the next display call starts from a zero state."""
+        _check(lib().rt_display_reset(self._h))
+        self._display_state = None
+
+    def display_device(self, d_rgb, opts, d_state, d_workspace, d_out, d_histogram=0, stream=0):
+        """rt_display_device: asynchronous, DEVICE buffers of the scene's GPU, no state of its own.  d_rgb: W*H*3 f32; d_state: an
+        rt_display_state (16 bytes, read and written on the device; 0 = none); d_workspace: display_workspace_bytes(opts) bytes,
+        16-byte aligned; d_out: display_output_bytes(opts) bytes; d_histogram: 256 uint32 or 0; opts: abi.DisplayOpts."""
+        def vp(ptr):
+            return C.c_void_p(int(ptr) or None)
+
+        _check(lib().rt_display_device(self._h, C.cast(vp(d_rgb), C.POINTER(C.c_float)), C.byref(opts), vp(d_state),
+                                       vp(d_workspace), vp(d_out), C.cast(vp(d_histogram), C.POINTER(C.c_uint32)),
+                                       C.c_void_p(stream)))
+
     # ---- AccelerationStructure::check_hit / check_hit_index for batches ----
     def check_hit(self, origins, directions):
         rays = _pack_rays(origins, directions)
@@ -554,6 +596,38 @@ def temporal_workspace_bytes(opts):
     """rt_temporal_workspace_bytes: the workspace rt_denoise_temporal_device needs for opts' frame size."""
     n = C.c_uint64()
     _check(lib().rt_temporal_workspace_bytes(C.byref(opts), C.byref(n)))
+    return n.value
+
+
+def display_opts(width, height, **kw):
+    """rt_display_opts_default with the frame size and any of abi.DISPLAY_OPTIONS set; the enum options also take their names
+    (tonemap="hable", pixel_format="rgb8", ...)."""
+    o = abi.DisplayOpts()
+    _check(lib().rt_display_opts_default(C.byref(o)))
+    o.width, o.height = int(width), int(height)
+    for k, v in kw.items():
+        if k not in abi.DISPLAY_OPTIONS:
+            raise ValueError(f"unknown display option {k!r}")
+        if isinstance(v, str):
+            names = abi.DISPLAY_ENUMS.get(k, {})
+            if v.lower() not in names:
+                raise ValueError(f"unknown {k} {v!r}: one of {sorted(names)}")
+            v = names[v.lower()]
+        setattr(o, k, v)
+    return o
+
+
+def display_workspace_bytes(opts):
+    """rt_display_workspace_bytes: the workspace rt_display_device needs for opts' frame size."""
+    n = C.c_uint64()
+    _check(lib().rt_display_workspace_bytes(C.byref(opts), C.byref(n)))
+    return n.value
+
+
+def display_output_bytes(opts):
+    """rt_display_output_bytes: W*H*4 (RGBA8, BGRA8) or W*H*3 (RGB8)."""
+    n = C.c_uint64()
+    _check(lib().rt_display_output_bytes(C.byref(opts), C.byref(n)))
     return n.value
 
 
