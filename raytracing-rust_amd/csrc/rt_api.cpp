@@ -4,6 +4,10 @@
 // persistent kernel launch (rt_render.hip) and reports errors as codes + rt_last_error().
 // There is NO CPU fallback: without a HIP device every compute entry point fails with
 // RT_ERR_NO_DEVICE.
+//
+// This file: scene creation, multi-device scenes, render, sampling, output, check-hit and the self-tests.  The
+// post-processing stages (AOV buffers, denoiser, temporal accumulation, display) are rt_api_post.cpp; what the two share
+// (rt_scene, the error convention, the argument checks and buffer plumbing) is rt_api_internal.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -17,12 +21,7 @@
 #include "../../include/rt_hip.h"
 #include "../../include/rt_detmath.h"
 #include <dlfcn.h>
-#include "rt_build.h"
-#include "rt_types.h"
-#include "rt_aov.h"
-#include "rt_denoise.h"
-#include "rt_temporal.h"
-#include "rt_display.h"
+#include "rt_api_internal.h"
 
 namespace rt {
 size_t render_lds_bytes(const DevScene &S, bool sky_lds, bool scene_lds, uint32_t waves_per_block, uint32_t stack_cap);
@@ -56,117 +55,17 @@ hipError_t launch_check_hit_index(bool prune, hipStream_t stream, const DevScene
 
 using namespace rt;
 
-static thread_local std::string g_error;
-
-static int fail(int code, const std::string &msg)
-{
-	g_error = msg;
-	return code;
-}
-static int hip_fail(hipError_t e, const char *what)
-{
-	g_error = std::string(what) + ": " + hipGetErrorString(e);
-	return e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_HIP;
-}
-#define HIP_TRY(expr)                       \
-	do {                                    \
-		hipError_t e_ = (expr);             \
-		if (e_ != hipSuccess)               \
-			return hip_fail(e_, #expr);     \
-	} while (0)
+thread_local std::string g_error; // rt_last_error(); the one definition (rt_api_internal.h)
 
 // Measured crossovers (tests/probes/gpu_crossover_probe.py, tests/probes/gpu_crossover_mesh.py, 1080p):
 //   exhaustive walk + coarse schedule wins up to ~100 primitives, the pruned walk beyond;
 //   the fine schedule (every step voted) wins from a few thousand triangles (10 k: 36 -> 26 ms, 1 M: 189 -> 77 ms)
 //   but only ties on sphere-only scenes even at 16 k (96 vs 106 ms): sphere leaves are cheap, triangle leaves
 //   are long and divergent.
-constexpr uint32_t kPruneAbove = 100;
+// (kPruneAbove: rt_api_internal.h, the AOV pass chooses its walk by it too)
 constexpr uint32_t kFineAboveTriangles = 4096; // round 2, with the wide walk under both schedules (8 spp 1080p, MIS coarse / fine):
                                                // 2 000 triangles 11.9 / 13.4 ms, 4 000: 14.9 / 16.2, 10 000: 30.2 / 26.2 (naive crosses near 3 000)
 constexpr uint32_t kFineAboveSpheres = 32768;
-
-struct rt_scene {
-	int device = 0;
-	HostScene host;
-	DevScene dev{};
-	std::vector<void *> allocations;
-	hipStream_t stream = nullptr; // used by the blocking entry points
-	uint32_t *d_work_counter = nullptr;
-	unsigned long long *d_rays = nullptr;
-	hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-	bool timed = false;
-	uint32_t n_launches = 0;
-	int n_cus = 0;
-	int traversal_mode = -1; // -1 auto, 0 exhaustive (reference order of work), 1 pruned
-	int schedule_mode = -1;  // -1 auto, 0 coarse (two super-phases), 1 fine (every step voted)
-	int feature_set = 2;     // smallest kernel variant covering the scene: 0 spheres-only, 1 simple, 2 full
-	int min_feature_set = 0; // what the scene needs (feature_set may be forced larger for tests)
-	// the tree is one inner node over two leaves of one primitive each: launches that would run the spheres-only exhaustive
-	// coarse kernels run their FeatPair twins (rt_types.h) -- unless a feature set was asked for by name (RT_TUNE_FEATURE_SET)
-	bool pair_tree = false, feature_set_forced = false;
-	DevPairScene pair{}; // pair_tree: the scene as the FeatPair kernels take it, in their kernel arguments (rt_types.h)
-	bool scene_lds_allowed = true;
-	float *d_partial = nullptr; // sample_split > 1: per-chunk means, grown on demand
-	size_t partial_floats = 0;
-	// rt_sample_image: two batches in flight (device + pinned host buffers, copy stream, events)
-	float *d_prog[2] = {nullptr, nullptr};
-	float *h_prog[2] = {nullptr, nullptr};
-	unsigned long long *d_prog_rays = nullptr; // [2]
-	unsigned long long *h_prog_rays = nullptr; // [2], pinned
-	size_t d_prog_floats[2] = {0, 0}, h_prog_floats[2] = {0, 0};
-	hipStream_t copy_stream = nullptr;
-	hipEvent_t ev_batch[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
-	size_t max_lds = 65536;
-	rt_launch_info last_launch{};
-	uint32_t stack_cap_override = 0; // RT_TUNE_STACK_CAP
-	int exchange_mode = 0;           // RT_TUNE_EXCHANGE
-	uint32_t stack_depth_narrow = 2; // HostScene::stack_depth_narrow (members of a multi-device scene have no host scene of their own)
-	uint32_t *d_stack_ovf = nullptr; // traversal-stack overflow area (deep trees under the fine schedule), grown on demand
-	size_t stack_ovf_words = 0;
-	uint8_t *d_rgb8 = nullptr; // rt_render_rgb8: the quantised frame
-	size_t d_rgb8_bytes = 0;
-	// ---- multi-device scenes (rt_scene_create_multi).  The handle a caller holds is the HEAD: an ordinary scene on
-	// devices[0] that additionally owns one member scene per further device (uploaded from the head's host build) and
-	// gathers their tile shards into its own frames.  Members render like any single-device scene. ----
-	std::vector<rt_scene *> peers;         // head only: the members on devices[1..n-1]
-	bool member_call = false;              // set while the head renders its own shard through the single-device path
-	float *d_shard = nullptr;              // every member incl. the head: its packed shard (RT_LAYOUT_SHARD)
-	size_t shard_floats = 0;
-	unsigned long long *d_member_rays = nullptr; // the member's own ray counter (the head's d_rays holds the job's total)
-	hipEvent_t ev_shard = nullptr;         // member: its shard is rendered
-	hipEvent_t ev_begin = nullptr;         // head: the caller's stream has reached this render
-	float *d_gather = nullptr;             // head: the peers' shards, once gathered
-	size_t gather_floats = 0;
-	unsigned long long *d_gather_rays = nullptr; // head: [n] the members' ray counters
-	void *nccl_comms = nullptr;            // head: ncclComm_t[n] when the devices are distinct and RCCL is usable
-	int gather_mode = 0;                   // rt_gather_mode, decided when the scene is created (rt_scene_create_multi)
-	std::string gather_note;               // why (rt_scene_gather_info)
-	hipEvent_t ev_gathered = nullptr;      // head: the last render's gather + scatter have read every member's shard
-	bool gathered_once = false;
-	uint32_t *d_prim_desc = nullptr;       // rt_render_aov: BVH slot -> rt_scene_desc index, uploaded on first use (in `allocations`)
-	char *d_denoise = nullptr;             // rt_denoise / rt_render_denoised: device frames + workspace, grown on first use
-	size_t d_denoise_bytes = 0;
-	char *d_temporal = nullptr;            // rt_denoise_temporal: its two history buffers, for frames of temporal_w x temporal_h
-	uint32_t temporal_w = 0, temporal_h = 0;
-	int temporal_cur = -1;                 // the history buffer the last call wrote; -1 = no history
-	rt_camera temporal_prev{};             // the camera of that call
-	char *d_display = nullptr;             // rt_display: state, histogram, workspace, output and input, grown for larger frames
-	size_t d_display_bytes = 0;
-	uint32_t display_w = 0, display_h = 0; // the frame size of the last successful call
-	bool display_has_state = false;        // false: the next rt_display starts from a zero state
-};
-
-template <class T> static int upload(rt_scene *s, const T *src, size_t count, const T **dst)
-{
-	void *p = nullptr;
-	const size_t bytes = (count ? count : 1) * sizeof(T);
-	HIP_TRY(hipMalloc(&p, bytes));
-	s->allocations.push_back(p);
-	if (count)
-		HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
-	*dst = static_cast<const T *>(p);
-	return RT_OK;
-}
 
 // ---- RCCL, loaded when a multi-device scene over DISTINCT devices is created.  The gather of a multi-device render is the one
 // collective of the path: grouped ncclSend / ncclRecv of the members' shards into the head's device over
@@ -1305,14 +1204,9 @@ int rt_render_device(rt_scene *s, const rt_camera *camera, const rt_render_opts 
 	float *render_target = d_out_rgb;
 	if (split > 1u) { // chunk means land in a scratch buffer; combine_chunks_kernel folds them into d_out_rgb
 		const size_t need = (size_t)g.n_work * split * 3;
-		if (need > s->partial_floats) { // grows on first use only (not capturable into a graph on that call)
-			if (s->d_partial)
-				(void)hipFree(s->d_partial);
-			s->d_partial = nullptr;
-			s->partial_floats = 0;
-			HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_partial), need * sizeof(float)));
-			s->partial_floats = need;
-		}
+		rc = grow_device_buffer(s->d_partial, s->partial_floats, need); // grows on first use only (not capturable into a graph on that call)
+		if (rc != RT_OK)
+			return rc;
 		render_target = s->d_partial;
 	}
 	P.shard_layout = o->output_layout == RT_LAYOUT_SHARD ? 1 : 0;
@@ -1502,14 +1396,9 @@ int rt_render_device(rt_scene *s, const rt_camera *camera, const rt_render_opts 
 	}
 	if (P.stack_ovf_depth != 0u) { // grown on first use only (like the sample_split scratch: not capturable on that call)
 		const size_t need = (size_t)n_blocks * block_threads * P.stack_ovf_depth;
-		if (need > s->stack_ovf_words) {
-			if (s->d_stack_ovf)
-				(void)hipFree(s->d_stack_ovf);
-			s->d_stack_ovf = nullptr;
-			s->stack_ovf_words = 0;
-			HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_stack_ovf), need * sizeof(uint32_t)));
-			s->stack_ovf_words = need;
-		}
+		rc = grow_device_buffer(s->d_stack_ovf, s->stack_ovf_words, need);
+		if (rc != RT_OK)
+			return rc;
 	}
 	HIP_TRY(hipEventRecord(s->ev_start, stream));
 	HIP_TRY(launch_render(o->render_method, prune, fine, sky_lds, feature_set, (uint32_t)n_blocks, lds_bytes, stream, dev, cam, P, render_target,
@@ -1527,8 +1416,8 @@ int rt_render(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, flo
 {
 	if (!s || !camera || !o)
 		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (s->device == RT_DEVICE_NONE)
-		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
+	if (int rc = need_device(s); rc != RT_OK)
+		return rc;
 	uint64_t n_floats = 0;
 	int rc = rt_render_output_floats(o, &n_floats);
 	if (rc != RT_OK)
@@ -1546,16 +1435,12 @@ int rt_render(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, flo
 		return rc;
 	float *d_out = s->d_prog[0];
 	rc = rt_render_device(s, camera, o, d_out, reinterpret_cast<uint64_t *>(s->d_rays), s->stream);
-	if (rc == RT_OK) {
-		hipError_t e = hipMemcpyAsync(out_rgb, d_out, n_floats * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-		if (e == hipSuccess && rays_shot)
-			e = hipMemcpyAsync(rays_shot, s->d_rays, sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream);
-		if (e == hipSuccess)
-			e = hipStreamSynchronize(s->stream);
-		if (e != hipSuccess)
-			rc = hip_fail(e, "render");
-	}
-	return rc;
+	if (rc != RT_OK)
+		return rc;
+	Staging st{s};
+	st.download(out_rgb, d_out, n_floats * sizeof(float));
+	st.download(rays_shot, s->d_rays, sizeof(uint64_t));
+	return st.finish("render");
 }
 
 int rt_output_rgb8_device(rt_scene *s, const float *d_rgb, uint64_t n_values, float gamma, uint8_t *d_out, void *hip_stream)
@@ -1575,8 +1460,8 @@ int rt_render_rgb8(rt_scene *s, const rt_camera *camera, const rt_render_opts *o
 {
 	if (!s || !camera || !o)
 		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (s->device == RT_DEVICE_NONE)
-		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
+	if (int rc = need_device(s); rc != RT_OK)
+		return rc;
 	uint64_t n_values = 0;
 	int rc = rt_render_output_floats(o, &n_values);
 	if (rc != RT_OK)
@@ -1592,37 +1477,27 @@ int rt_render_rgb8(rt_scene *s, const rt_camera *camera, const rt_render_opts *o
 	rc = ensure_frame_buffers(s, n_values, false);
 	if (rc != RT_OK)
 		return rc;
-	if (n_values > s->d_rgb8_bytes) { // scene-owned byte frame, grown on first use
-		if (s->d_rgb8)
-			(void)hipFree(s->d_rgb8);
-		s->d_rgb8 = nullptr;
-		s->d_rgb8_bytes = 0;
-		HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_rgb8), n_values));
-		s->d_rgb8_bytes = n_values;
-	}
+	rc = grow_device_buffer(s->d_rgb8, s->d_rgb8_bytes, (size_t)n_values); // scene-owned byte frame, grown on first use
+	if (rc != RT_OK)
+		return rc;
 	float *d_frame = s->d_prog[0];
 	rc = rt_render_device(s, camera, o, d_frame, reinterpret_cast<uint64_t *>(s->d_rays), s->stream);
 	if (rc != RT_OK)
 		return rc;
 	// the output stage runs where the frame is: the float frame never crosses PCIe, one byte per value does
-	hipError_t e = launch_quantise(s->stream, d_frame, (size_t)n_values, 1.0f / gamma, s->d_rgb8);
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(out_rgb8, s->d_rgb8, n_values, hipMemcpyDeviceToHost, s->stream);
-	if (e == hipSuccess && rays_shot)
-		e = hipMemcpyAsync(rays_shot, s->d_rays, sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream);
-	if (e == hipSuccess)
-		e = hipStreamSynchronize(s->stream);
-	if (e != hipSuccess)
-		return hip_fail(e, "render_rgb8");
-	return RT_OK;
+	Staging st{s};
+	st.e = launch_quantise(s->stream, d_frame, (size_t)n_values, 1.0f / gamma, s->d_rgb8);
+	st.download(out_rgb8, s->d_rgb8, n_values);
+	st.download(rays_shot, s->d_rays, sizeof(uint64_t));
+	return st.finish("render_rgb8");
 }
 
 int rt_sample_image(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, uint64_t batch, rt_presentation_update update, void *data)
 {
 	if (!s || !camera || !o)
 		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (s->device == RT_DEVICE_NONE)
-		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
+	if (int rc = need_device(s); rc != RT_OK)
+		return rc;
 	uint64_t n_floats = 0;
 	int rc = rt_render_output_floats(o, &n_floats);
 	if (rc != RT_OK)
@@ -1996,8 +1871,8 @@ static int check_common(rt_scene *s, const rt_ray_desc *rays, const uint64_t *ob
 {
 	if (!s || !rays || !out)
 		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (s->device == RT_DEVICE_NONE)
-		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
+	if (int rc = need_device(s); rc != RT_OK)
+		return rc;
 	if (n == 0)
 		return RT_OK;
 	if (object_index)
@@ -2076,819 +1951,6 @@ int rt_selftest_lean(int device, uint64_t n_per_thread, uint64_t seed, uint64_t 
 	(void)hipFree(d);
 	if (e != hipSuccess)
 		return hip_fail(e, "selftest");
-	return RT_OK;
-}
-
-
-// ---- first-hit AOV buffers (rt_aov.hip) ----
-// argument checks of both entry points, the device last (so that a host-only scene reports bad arguments as such)
-static int aov_check(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *b, uint32_t *mask)
-{
-	if (!s || !camera || !o || !b)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	*mask = (b->albedo ? kAovAlbedo : 0u) | (b->normal ? kAovNormal : 0u) | (b->depth ? kAovDepth : 0u) |
-	        (b->coverage ? kAovCoverage : 0u) | (b->primitive ? kAovPrimitive : 0u) | (b->material ? kAovMaterial : 0u);
-	if (*mask == 0u)
-		return fail(RT_ERR_INVALID_ARGUMENT, "rt_aov_buffers: every channel is NULL");
-	if (o->width < 2 || o->height < 2)
-		return fail(RT_ERR_INVALID_ARGUMENT, "width and height must be >= 2 (u and v divide by W-1 and H-1)");
-	if (o->width * o->height >= (1ull << 31))
-		return fail(RT_ERR_UNSUPPORTED, "image larger than 2^31 pixels");
-	if (o->samples_per_pixel == 0 || o->samples_per_pixel >= (1ull << 32))
-		return fail(RT_ERR_INVALID_ARGUMENT, "samples_per_pixel must be in [1, 2^32)");
-	if (o->output_layout != RT_LAYOUT_FRAME)
-		return fail(RT_ERR_UNSUPPORTED, "AOV buffers are produced in RT_LAYOUT_FRAME only");
-	if (o->shard_count != 1)
-		return fail(RT_ERR_UNSUPPORTED, "AOV buffers are produced for the whole frame only (shard_count 1)");
-	if (s->device == RT_DEVICE_NONE)
-		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
-	return RT_OK;
-}
-
-int rt_render_aov_device(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *d_out, void *hip_stream)
-{
-	uint32_t mask = 0;
-	int rc = aov_check(s, camera, o, d_out, &mask);
-	if (rc != RT_OK)
-		return rc;
-	// a multi-device head is an ordinary scene on devices[0]: the AOV pass runs there alone
-	HIP_TRY(hipSetDevice(s->device));
-	if ((mask & kAovPrimitive) && !s->d_prim_desc) { // first use: BVH slot -> caller's index (synchronous, once per scene)
-		const std::vector<uint64_t> &order = s->host.primitive_order;
-		if (order.size() >= 0xFFFFFFFFull)
-			return fail(RT_ERR_UNSUPPORTED, "primitive IDs need fewer than 2^32 - 1 primitives");
-		std::vector<uint32_t> desc(order.size());
-		for (size_t i = 0; i < order.size(); ++i)
-			desc[i] = (uint32_t)order[i];
-		const uint32_t *d = nullptr;
-		rc = upload(s, desc.data(), desc.size(), &d);
-		if (rc != RT_OK)
-			return rc;
-		s->d_prim_desc = const_cast<uint32_t *>(d);
-	}
-	// traversal as rt_render / rt_check_hit choose it; the whole worst-case stack of the workgroup in LDS: the wide tree's only
-	// where it is walked and fits, the two-child tree's (and the two-child walk for every ray) otherwise
-	const bool prune = s->traversal_mode == -1 ? s->dev.n_prims > kPruneAbove : s->traversal_mode == 1;
-	DevScene dev = s->dev;
-	const bool walks_wide = prune && dev.nodes4 != nullptr && dev.narrow_only == 0u;
-	if (!walks_wide || aov_lds_bytes(dev) > s->max_lds) {
-		if (walks_wide)
-			dev.narrow_only = 1u;
-		dev.stack_depth = s->stack_depth_narrow;
-	}
-	if (aov_lds_bytes(dev) > s->max_lds)
-		return fail(RT_ERR_UNSUPPORTED, "traversal stacks exceed the LDS of one CU");
-	DevAovParams P;
-	std::memset(&P, 0, sizeof P);
-	std::memcpy(P.cam.origin, camera->origin, 12);
-	std::memcpy(P.cam.lower_left, camera->lower_left, 12);
-	std::memcpy(P.cam.horizontal, camera->horizontal, 12);
-	std::memcpy(P.cam.vertical, camera->vertical, 12);
-	P.width = (uint32_t)o->width;
-	P.height = (uint32_t)o->height;
-	P.tiles_x = (P.width + 7u) / 8u;
-	P.n_tiles = P.tiles_x * ((P.height + 7u) / 8u);
-	P.spp = (uint32_t)o->samples_per_pixel;
-	P.mask = mask;
-	P.seed_lo = (uint32_t)o->seed;
-	P.seed_hi = (uint32_t)(o->seed >> 32);
-	P.sample_begin_lo = (uint32_t)o->sample_begin;
-	P.sample_begin_hi = (uint32_t)(o->sample_begin >> 32);
-	P.prim_desc = s->d_prim_desc;
-	P.albedo = d_out->albedo;
-	P.normal = d_out->normal;
-	P.depth = d_out->depth;
-	P.coverage = d_out->coverage;
-	P.primitive = d_out->primitive;
-	P.material = d_out->material;
-	HIP_TRY(launch_aov(prune, static_cast<hipStream_t>(hip_stream), dev, P));
-	return RT_OK;
-}
-
-int rt_render_aov(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *out)
-{
-	uint32_t mask = 0;
-	int rc = aov_check(s, camera, o, out, &mask);
-	if (rc != RT_OK)
-		return rc;
-	HIP_TRY(hipSetDevice(s->device));
-	const size_t n_px = (size_t)(o->width * o->height);
-	// one device allocation for the requested channels, in rt_aov_buffers order; 4-byte elements throughout
-	void *host[6] = {out->albedo, out->normal, out->depth, out->coverage, out->primitive, out->material};
-	const size_t per_px[6] = {3, 3, 1, 1, 1, 1};
-	size_t offset[6], total = 0;
-	for (int c = 0; c < 6; ++c) {
-		offset[c] = total;
-		if (host[c])
-			total += per_px[c] * n_px;
-	}
-	char *d = nullptr;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), total * 4));
-	rt_aov_buffers dev_out;
-	dev_out.albedo = host[0] ? reinterpret_cast<float *>(d + 4 * offset[0]) : nullptr;
-	dev_out.normal = host[1] ? reinterpret_cast<float *>(d + 4 * offset[1]) : nullptr;
-	dev_out.depth = host[2] ? reinterpret_cast<float *>(d + 4 * offset[2]) : nullptr;
-	dev_out.coverage = host[3] ? reinterpret_cast<float *>(d + 4 * offset[3]) : nullptr;
-	dev_out.primitive = host[4] ? reinterpret_cast<uint32_t *>(d + 4 * offset[4]) : nullptr;
-	dev_out.material = host[5] ? reinterpret_cast<uint32_t *>(d + 4 * offset[5]) : nullptr;
-	rc = rt_render_aov_device(s, camera, o, &dev_out, s->stream);
-	hipError_t e = hipSuccess;
-	for (int c = 0; c < 6 && rc == RT_OK && e == hipSuccess; ++c)
-		if (host[c])
-			e = hipMemcpyAsync(host[c], d + 4 * offset[c], per_px[c] * n_px * 4, hipMemcpyDeviceToHost, s->stream);
-	if (rc == RT_OK && e == hipSuccess)
-		e = hipStreamSynchronize(s->stream);
-	else if (rc != RT_OK)
-		(void)hipStreamSynchronize(s->stream);
-	(void)hipFree(d);
-	if (rc == RT_OK && e != hipSuccess)
-		rc = hip_fail(e, "render_aov");
-	return rc;
-}
-
-} // extern "C"
-
-// ---- AOV-guided A-Trous denoiser (rt_denoise.hip) ----
-static bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
-{
-	if (!a || !b)
-		return false;
-	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-	return x < y + b_bytes && y < x + a_bytes;
-}
-
-// the frame size and the filter options (width and height are passed separately: rt_render_denoised takes them from the render)
-static int denoise_opts_check(const rt_denoise_opts *d, uint64_t w, uint64_t h)
-{
-	if (w == 0 || h == 0)
-		return fail(RT_ERR_INVALID_ARGUMENT, "denoise: width and height must be >= 1");
-	if (d->iterations < 1 || d->iterations > 10)
-		return fail(RT_ERR_INVALID_ARGUMENT, "denoise: iterations must be in 1..10");
-	const float sig[3] = {d->sigma_luminance, d->sigma_normal, d->sigma_depth};
-	for (float x : sig)
-		if (!std::isfinite(x) || !(x > 0.0f))
-			return fail(RT_ERR_INVALID_ARGUMENT, "denoise: sigma_luminance, sigma_normal and sigma_depth must be finite and > 0");
-	if (w > (1ull << 31) || h > (1ull << 31) || w * h > (1ull << 31))
-		return fail(RT_ERR_UNSUPPORTED, "denoise: more than 2^31 pixels");
-	return RT_OK;
-}
-
-// argument checks of rt_denoise / rt_denoise_device, the device last (so that a host-only scene reports bad arguments as such);
-// `ws` is checked for the device call only
-static int denoise_check(const rt_scene *s, const rt_denoise_inputs *in, const rt_denoise_opts *o, const float *out, bool device,
-                         const void *ws)
-{
-	if (!s || !in || !o)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (!in->color || !out)
-		return fail(RT_ERR_INVALID_ARGUMENT, "denoise: color and out must not be NULL");
-	int rc = denoise_opts_check(o, o->width, o->height);
-	if (rc != RT_OK)
-		return rc;
-	const uint64_t n = (uint64_t)o->width * o->height;
-	const void *inputs[5] = {in->color, in->albedo, in->normal, in->depth, in->variance};
-	const uint64_t bytes[5] = {12 * n, 12 * n, 12 * n, 4 * n, 4 * n};
-	for (int i = 0; i < 5; ++i)
-		if (ranges_overlap(out, 12 * n, inputs[i], bytes[i]))
-			return fail(RT_ERR_INVALID_ARGUMENT, "denoise: out overlaps an input");
-	if (device) {
-		if (!ws || reinterpret_cast<uintptr_t>(ws) % 16u != 0u)
-			return fail(RT_ERR_INVALID_ARGUMENT, "denoise: the workspace must be non-NULL and 16-byte aligned");
-		const uint64_t ws_bytes = kDenoiseWorkspaceBytesPerPixel * n;
-		bool clash = ranges_overlap(ws, ws_bytes, out, 12 * n);
-		for (int i = 0; i < 5; ++i)
-			clash = clash || ranges_overlap(ws, ws_bytes, inputs[i], bytes[i]);
-		if (clash)
-			return fail(RT_ERR_INVALID_ARGUMENT, "denoise: the workspace overlaps an input or out");
-	}
-	if (s->device == RT_DEVICE_NONE)
-		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
-	return RT_OK;
-}
-
-static DevDenoiseParams denoise_params(const rt_denoise_opts *o, uint64_t w, uint64_t h, const rt_denoise_inputs &in, void *ws,
-                                       float *out)
-{
-	DevDenoiseParams P;
-	std::memset(&P, 0, sizeof P);
-	P.width = (uint32_t)w;
-	P.height = (uint32_t)h;
-	P.iterations = o->iterations;
-	P.sigma_l = o->sigma_luminance;
-	P.sigma_n = o->sigma_normal;
-	P.sigma_z = o->sigma_depth;
-	P.color = in.color;
-	P.albedo = in.albedo;
-	P.normal = in.normal;
-	P.depth = in.depth;
-	P.variance = in.variance;
-	const size_t n = (size_t)(w * h);
-	P.plane0 = static_cast<float4 *>(ws);
-	P.plane1 = P.plane0 + n;
-	P.guide = P.plane1 + n;
-	P.out = out;
-	return P;
-}
-
-// the scene-owned device buffer of the blocking denoise entry points, grown on first use / larger frames only
-static int ensure_denoise_buffer(rt_scene *s, size_t bytes)
-{
-	if (bytes <= s->d_denoise_bytes)
-		return RT_OK;
-	if (s->d_denoise)
-		(void)hipFree(s->d_denoise);
-	s->d_denoise = nullptr;
-	s->d_denoise_bytes = 0;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_denoise), bytes));
-	s->d_denoise_bytes = bytes;
-	return RT_OK;
-}
-
-extern "C" {
-
-int rt_denoise_opts_default(rt_denoise_opts *out)
-{
-	if (!out)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	std::memset(out, 0, sizeof *out);
-	out->iterations = 5;
-	out->sigma_luminance = 4.0f;
-	out->sigma_normal = 128.0f;
-	out->sigma_depth = 0.1f;
-	return RT_OK;
-}
-
-int rt_denoise_workspace_bytes(const rt_denoise_opts *o, uint64_t *bytes)
-{
-	if (!o || !bytes)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (o->width == 0 || o->height == 0)
-		return fail(RT_ERR_INVALID_ARGUMENT, "denoise: width and height must be >= 1");
-	const uint64_t n = (uint64_t)o->width * o->height;
-	if (n > (1ull << 31))
-		return fail(RT_ERR_UNSUPPORTED, "denoise: more than 2^31 pixels");
-	*bytes = kDenoiseWorkspaceBytesPerPixel * n;
-	return RT_OK;
-}
-
-int rt_denoise_device(rt_scene *s, const rt_denoise_inputs *d_in, const rt_denoise_opts *o, void *d_workspace, float *d_out,
-                      void *hip_stream)
-{
-	int rc = denoise_check(s, d_in, o, d_out, true, d_workspace);
-	if (rc != RT_OK)
-		return rc;
-	// a multi-device head is an ordinary scene on devices[0]: the filter runs there alone
-	HIP_TRY(hipSetDevice(s->device));
-	HIP_TRY(launch_denoise(static_cast<hipStream_t>(hip_stream), denoise_params(o, o->width, o->height, *d_in, d_workspace, d_out)));
-	return RT_OK;
-}
-
-int rt_denoise(rt_scene *s, const rt_denoise_inputs *in, const rt_denoise_opts *o, float *out)
-{
-	int rc = denoise_check(s, in, o, out, false, nullptr);
-	if (rc != RT_OK)
-		return rc;
-	HIP_TRY(hipSetDevice(s->device));
-	const size_t n = (size_t)o->width * o->height;
-	// workspace first (16-byte aligned), then out, then the inputs given, in rt_denoise_inputs order
-	const float *host[5] = {in->color, in->albedo, in->normal, in->depth, in->variance};
-	const size_t per_px[5] = {3, 3, 3, 1, 1};
-	size_t offset[5], total = kDenoiseWorkspaceBytesPerPixel / 4 * n + 3 * n;
-	for (int c = 0; c < 5; ++c) {
-		offset[c] = total;
-		if (host[c])
-			total += per_px[c] * n;
-	}
-	rc = ensure_denoise_buffer(s, total * 4);
-	if (rc != RT_OK)
-		return rc;
-	float *base = reinterpret_cast<float *>(s->d_denoise);
-	float *d_out = base + kDenoiseWorkspaceBytesPerPixel / 4 * n;
-	const float *dev[5];
-	hipError_t e = hipSuccess;
-	for (int c = 0; c < 5; ++c) {
-		dev[c] = host[c] ? base + offset[c] : nullptr;
-		if (host[c] && e == hipSuccess)
-			e = hipMemcpyAsync(base + offset[c], host[c], per_px[c] * n * 4, hipMemcpyHostToDevice, s->stream);
-	}
-	if (e != hipSuccess) {
-		(void)hipStreamSynchronize(s->stream);
-		return hip_fail(e, "denoise upload");
-	}
-	const rt_denoise_inputs d_in = {dev[0], dev[1], dev[2], dev[3], dev[4]};
-	rc = rt_denoise_device(s, &d_in, o, s->d_denoise, d_out, s->stream);
-	if (rc == RT_OK)
-		e = hipMemcpyAsync(out, d_out, 3 * n * 4, hipMemcpyDeviceToHost, s->stream);
-	const hipError_t e_sync = hipStreamSynchronize(s->stream);
-	if (rc == RT_OK && e == hipSuccess)
-		e = e_sync;
-	if (rc == RT_OK && e != hipSuccess)
-		rc = hip_fail(e, "denoise");
-	return rc;
-}
-
-int rt_render_denoised(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_denoise_opts *dopts, float *out_clean,
-                       float *out_noisy, uint64_t *rays_shot)
-{
-	if (!s || !camera || !o || !dopts || !out_clean)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	int rc = denoise_opts_check(dopts, o->width, o->height);
-	if (rc != RT_OK)
-		return rc;
-	if (o->width < 2 || o->height < 2)
-		return fail(RT_ERR_INVALID_ARGUMENT, "width and height must be >= 2 (u and v divide by W-1 and H-1)");
-	if (o->samples_per_pixel < 2 || o->samples_per_pixel % 2 != 0 || o->samples_per_pixel >= (1ull << 32))
-		return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_denoised: samples_per_pixel must be even, >= 2 and < 2^32");
-	if (o->render_method != RT_METHOD_NAIVE && o->render_method != RT_METHOD_MIS)
-		return fail(RT_ERR_INVALID_ARGUMENT, "unknown render method");
-	if (o->output_layout != RT_LAYOUT_FRAME)
-		return fail(RT_ERR_UNSUPPORTED, "rt_render_denoised: RT_LAYOUT_FRAME only");
-	if (o->shard_count != 1)
-		return fail(RT_ERR_UNSUPPORTED, "rt_render_denoised: the whole frame only (shard_count 1)");
-	const size_t n = (size_t)(o->width * o->height);
-	if (ranges_overlap(out_clean, 12 * n, out_noisy, 12 * n))
-		return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_denoised: out_clean overlaps out_noisy");
-	if (s->device == RT_DEVICE_NONE)
-		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
-	HIP_TRY(hipSetDevice(s->device));
-	// two ray counters (16 bytes), the workspace, then the frames: A, B, albedo, normal, depth, noisy, clean
-	const size_t ws_floats = kDenoiseWorkspaceBytesPerPixel / 4 * n;
-	rc = ensure_denoise_buffer(s, 16 + 4 * (ws_floats + 19 * n));
-	if (rc != RT_OK)
-		return rc;
-	unsigned long long *d_rays = reinterpret_cast<unsigned long long *>(s->d_denoise);
-	float *ws = reinterpret_cast<float *>(s->d_denoise + 16);
-	float *d_a = ws + ws_floats, *d_b = d_a + 3 * n, *d_albedo = d_b + 3 * n, *d_normal = d_albedo + 3 * n,
-	      *d_depth = d_normal + 3 * n, *d_noisy = d_depth + n, *d_clean = d_noisy + 3 * n;
-	const uint64_t half = o->samples_per_pixel / 2;
-	rt_render_opts oh = *o;
-	oh.samples_per_pixel = half;
-	rc = rt_render_device(s, camera, &oh, d_a, reinterpret_cast<uint64_t *>(d_rays), s->stream);
-	if (rc == RT_OK) {
-		oh.sample_begin = o->sample_begin + half;
-		rc = rt_render_device(s, camera, &oh, d_b, reinterpret_cast<uint64_t *>(d_rays + 1), s->stream);
-	}
-	hipError_t e = hipSuccess;
-	if (rc == RT_OK)
-		e = hipSetDevice(s->device);
-	if (rc == RT_OK && e == hipSuccess) {
-		rt_aov_buffers aov;
-		std::memset(&aov, 0, sizeof aov);
-		aov.albedo = d_albedo;
-		aov.normal = d_normal;
-		aov.depth = d_depth;
-		rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
-	}
-	if (rc == RT_OK && e == hipSuccess) {
-		const rt_denoise_inputs in = {d_noisy, d_albedo, d_normal, d_depth, nullptr};
-		DevDenoiseParams P = denoise_params(dopts, o->width, o->height, in, ws, d_clean);
-		P.half_a = d_a;
-		P.half_b = d_b;
-		P.noisy = d_noisy;
-		e = launch_denoise(s->stream, P);
-	}
-	unsigned long long rays[2] = {0, 0};
-	if (rc == RT_OK && e == hipSuccess)
-		e = hipMemcpyAsync(out_clean, d_clean, 3 * n * 4, hipMemcpyDeviceToHost, s->stream);
-	if (rc == RT_OK && e == hipSuccess && out_noisy)
-		e = hipMemcpyAsync(out_noisy, d_noisy, 3 * n * 4, hipMemcpyDeviceToHost, s->stream);
-	if (rc == RT_OK && e == hipSuccess)
-		e = hipMemcpyAsync(rays, d_rays, sizeof rays, hipMemcpyDeviceToHost, s->stream);
-	const hipError_t e_sync = hipStreamSynchronize(s->stream);
-	if (rc == RT_OK && e == hipSuccess)
-		e = e_sync;
-	if (rc == RT_OK && e != hipSuccess)
-		rc = hip_fail(e, "render_denoised");
-	if (rc == RT_OK && rays_shot)
-		*rays_shot = rays[0] + rays[1];
-	return rc;
-}
-
-} // extern "C"
-
-// ---- temporal accumulation with camera reprojection (rt_temporal.hip) ----
-static int temporal_opts_check(const rt_temporal_opts *o)
-{
-	const uint64_t w = o->denoise.width, h = o->denoise.height;
-	if (w < 2 || h < 2)
-		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: width and height must be >= 2 (u and v divide by W-1 and H-1)");
-	int rc = denoise_opts_check(&o->denoise, w, h);
-	if (rc != RT_OK)
-		return rc;
-	if (!(o->alpha_color > 0.0f && o->alpha_color <= 1.0f) || !(o->alpha_moments > 0.0f && o->alpha_moments <= 1.0f))
-		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: alpha_color and alpha_moments must be in (0, 1]");
-	if (!std::isfinite(o->depth_tolerance) || !(o->depth_tolerance > 0.0f))
-		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: depth_tolerance must be finite and > 0");
-	if (!(o->normal_tolerance >= -1.0f && o->normal_tolerance <= 1.0f))
-		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: normal_tolerance must be in [-1, 1]");
-	if (o->max_history < 1)
-		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: max_history must be >= 1");
-	return RT_OK;
-}
-
-// argument checks of rt_denoise_temporal(_device), the device last; hist_out and ws are checked for the device call only
-static int temporal_check(const rt_scene *s, const rt_temporal_inputs *in, const rt_camera *cam, const rt_camera *prev,
-                          const rt_temporal_opts *o, const void *hist_in, const void *hist_out, const void *ws, const float *out,
-                          const float *motion, bool device)
-{
-	if (!s || !in || !cam || !o)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (!in->color || !in->depth || !out)
-		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: color, depth and out must not be NULL");
-	if (device && (!hist_out || !ws))
-		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: history_out and the workspace must not be NULL");
-	if (hist_in && !prev)
-		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: a history needs the previous camera");
-	int rc = temporal_opts_check(o);
-	if (rc != RT_OK)
-		return rc;
-	const uint64_t n = (uint64_t)o->denoise.width * o->denoise.height;
-	if (device) {
-		const void *aligned[3] = {hist_in, hist_out, ws};
-		for (const void *a : aligned)
-			if (reinterpret_cast<uintptr_t>(a) % 16u != 0u)
-				return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: the histories and the workspace must be 16-byte aligned");
-	}
-	// every buffer written against every other buffer (inputs may share memory with one another)
-	const void *buf[9] = {out, motion, hist_out, ws, in->color, in->albedo, in->normal, in->depth, hist_in};
-	const uint64_t bytes[9] = {12 * n, 8 * n, kTemporalHistoryBytesPerPixel * n, kTemporalWorkspaceBytesPerPixel * n,
-	                           12 * n, 12 * n, 12 * n, 4 * n, kTemporalHistoryBytesPerPixel * n};
-	for (int a = 0; a < 4; ++a)
-		for (int b = 0; b < 9; ++b)
-			if (a != b && ranges_overlap(buf[a], bytes[a], buf[b], bytes[b]))
-				return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: a buffer written overlaps another buffer");
-	if (s->device == RT_DEVICE_NONE)
-		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
-	return RT_OK;
-}
-
-static int temporal_bytes(const rt_temporal_opts *o, uint64_t per_pixel, uint64_t *bytes)
-{
-	if (!o || !bytes)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (o->denoise.width < 2 || o->denoise.height < 2)
-		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: width and height must be >= 2");
-	const uint64_t n = (uint64_t)o->denoise.width * o->denoise.height;
-	if (n > (1ull << 31))
-		return fail(RT_ERR_UNSUPPORTED, "denoise_temporal: more than 2^31 pixels");
-	*bytes = per_pixel * n;
-	return RT_OK;
-}
-
-extern "C" {
-
-int rt_temporal_opts_default(rt_temporal_opts *out)
-{
-	if (!out)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	std::memset(out, 0, sizeof *out);
-	rt_denoise_opts_default(&out->denoise);
-	out->alpha_color = 0.2f;
-	out->alpha_moments = 0.2f;
-	out->depth_tolerance = 0.1f;
-	out->normal_tolerance = 0.9f;
-	out->max_history = 32;
-	return RT_OK;
-}
-
-int rt_temporal_history_bytes(const rt_temporal_opts *o, uint64_t *bytes)
-{
-	return temporal_bytes(o, kTemporalHistoryBytesPerPixel, bytes);
-}
-
-int rt_temporal_workspace_bytes(const rt_temporal_opts *o, uint64_t *bytes)
-{
-	return temporal_bytes(o, kTemporalWorkspaceBytesPerPixel, bytes);
-}
-
-int rt_denoise_temporal_device(rt_scene *s, const rt_temporal_inputs *d_in, const rt_camera *cam, const rt_camera *prev_cam,
-                               const void *d_history_in, void *d_history_out, const rt_temporal_opts *o, void *d_workspace,
-                               float *d_out, float *d_motion, void *hip_stream)
-{
-	int rc = temporal_check(s, d_in, cam, prev_cam, o, d_history_in, d_history_out, d_workspace, d_out, d_motion, true);
-	if (rc != RT_OK)
-		return rc;
-	HIP_TRY(hipSetDevice(s->device)); // a multi-device head runs on devices[0]
-	const uint64_t w = o->denoise.width, h = o->denoise.height;
-	const size_t n = (size_t)(w * h);
-	DevTemporalParams T;
-	std::memset(&T, 0, sizeof T);
-	T.width = (uint32_t)w;
-	T.height = (uint32_t)h;
-	std::memcpy(T.cam, cam, sizeof T.cam);
-	if (d_history_in)
-		std::memcpy(T.prev, prev_cam, sizeof T.prev);
-	T.alpha_c = o->alpha_color;
-	T.alpha_m = o->alpha_moments;
-	T.depth_tol = o->depth_tolerance;
-	T.normal_tol = o->normal_tolerance;
-	T.max_history = (float)o->max_history;
-	T.color = d_in->color;
-	T.albedo = d_in->albedo;
-	T.normal = d_in->normal;
-	T.depth = d_in->depth;
-	T.hist_in = static_cast<const float4 *>(d_history_in);
-	T.hist_out = static_cast<float4 *>(d_history_out);
-	T.motion = d_motion;
-	const rt_denoise_inputs din = {d_in->color, d_in->albedo, d_in->normal, d_in->depth, nullptr};
-	DevDenoiseParams D = denoise_params(&o->denoise, w, h, din, d_workspace, d_out);
-	D.guide = T.hist_out + n; // H1 of the history written is the guide plane
-	HIP_TRY(launch_temporal(static_cast<hipStream_t>(hip_stream), T, D));
-	return RT_OK;
-}
-
-int rt_denoise_temporal(rt_scene *s, const rt_temporal_inputs *in, const rt_camera *cam, const rt_temporal_opts *o, float *out,
-                        float *motion)
-{
-	int rc = temporal_check(s, in, cam, nullptr, o, nullptr, nullptr, nullptr, out, motion, false);
-	if (rc != RT_OK)
-		return rc;
-	HIP_TRY(hipSetDevice(s->device));
-	const uint32_t w = o->denoise.width, h = o->denoise.height;
-	const size_t n = (size_t)w * h;
-	if (w != s->temporal_w || h != s->temporal_h) { // a new frame size: new histories, no history
-		if (s->d_temporal)
-			(void)hipFree(s->d_temporal);
-		s->d_temporal = nullptr;
-		s->temporal_w = s->temporal_h = 0;
-		s->temporal_cur = -1;
-		HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_temporal), 2 * kTemporalHistoryBytesPerPixel * n));
-		s->temporal_w = w;
-		s->temporal_h = h;
-	}
-	// the workspace (16-byte aligned), out, motion, then the inputs given, in rt_temporal_inputs order
-	const float *host[4] = {in->color, in->albedo, in->normal, in->depth};
-	const size_t per_px[4] = {3, 3, 3, 1};
-	size_t offset[4], total = kTemporalWorkspaceBytesPerPixel / 4 * n + 5 * n;
-	for (int c = 0; c < 4; ++c) {
-		offset[c] = total;
-		if (host[c])
-			total += per_px[c] * n;
-	}
-	rc = ensure_denoise_buffer(s, total * 4);
-	if (rc != RT_OK)
-		return rc;
-	float *base = reinterpret_cast<float *>(s->d_denoise);
-	float *d_out = base + kTemporalWorkspaceBytesPerPixel / 4 * n, *d_motion = d_out + 3 * n;
-	const float *dev[4];
-	hipError_t e = hipSuccess;
-	for (int c = 0; c < 4; ++c) {
-		dev[c] = host[c] ? base + offset[c] : nullptr;
-		if (host[c] && e == hipSuccess)
-			e = hipMemcpyAsync(base + offset[c], host[c], per_px[c] * n * 4, hipMemcpyHostToDevice, s->stream);
-	}
-	if (e != hipSuccess) {
-		(void)hipStreamSynchronize(s->stream);
-		return hip_fail(e, "denoise_temporal upload");
-	}
-	const rt_temporal_inputs d_in = {dev[0], dev[1], dev[2], dev[3]};
-	char *hist[2] = {s->d_temporal, s->d_temporal + kTemporalHistoryBytesPerPixel * n};
-	const int next = s->temporal_cur == 0 ? 1 : 0;
-	const void *h_in = s->temporal_cur >= 0 ? hist[s->temporal_cur] : nullptr;
-	s->temporal_cur = -1; // until this call has succeeded
-	rc = rt_denoise_temporal_device(s, &d_in, cam, &s->temporal_prev, h_in, hist[next], o, s->d_denoise, d_out,
-	                                motion ? d_motion : nullptr, s->stream);
-	if (rc == RT_OK)
-		e = hipMemcpyAsync(out, d_out, 3 * n * 4, hipMemcpyDeviceToHost, s->stream);
-	if (rc == RT_OK && e == hipSuccess && motion)
-		e = hipMemcpyAsync(motion, d_motion, 2 * n * 4, hipMemcpyDeviceToHost, s->stream);
-	const hipError_t e_sync = hipStreamSynchronize(s->stream);
-	if (rc == RT_OK && e == hipSuccess)
-		e = e_sync;
-	if (rc == RT_OK && e != hipSuccess)
-		rc = hip_fail(e, "denoise_temporal");
-	if (rc == RT_OK) {
-		s->temporal_cur = next;
-		s->temporal_prev = *cam;
-	}
-	return rc;
-}
-
-int rt_denoise_temporal_reset(rt_scene *s)
-{
-	if (!s)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	s->temporal_cur = -1;
-	return RT_OK;
-}
-
-} // extern "C"
-
-// ---- display stage: histogram, auto-exposure, tone curve, transfer, quantisation (rt_display.hip) ----
-static bool finite_f(float v) { return std::isfinite(v); }
-
-static int display_opts_check(const rt_display_opts *o)
-{
-	if (o->width == 0 || o->height == 0)
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: width and height must be >= 1");
-	if (o->exposure_mode < RT_EXPOSURE_FIXED || o->exposure_mode > RT_EXPOSURE_AUTO)
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown exposure_mode");
-	if (o->tonemap < RT_TONEMAP_CLAMP || o->tonemap > RT_TONEMAP_HABLE)
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown tonemap");
-	if (o->transfer < RT_TRANSFER_SRGB || o->transfer > RT_TRANSFER_LINEAR)
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown transfer");
-	if (o->quantiser < RT_QUANT_ROUND || o->quantiser > RT_QUANT_REFERENCE)
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown quantiser");
-	if (o->pixel_format < RT_PIXEL_RGBA8 || o->pixel_format > RT_PIXEL_RGB8)
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown pixel_format");
-	if (!finite_f(o->exposure_ev) || !finite_f(o->key_ev))
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: exposure_ev and key_ev must be finite");
-	if (!(o->meter_low >= 0.0f && o->meter_low < o->meter_high && o->meter_high <= 1.0f))
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: need 0 <= meter_low < meter_high <= 1");
-	if (!finite_f(o->ev_min) || !finite_f(o->ev_max) || !(o->ev_min <= o->ev_max))
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: ev_min and ev_max must be finite with ev_min <= ev_max");
-	if (!(o->adaptation > 0.0f && o->adaptation <= 1.0f))
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: adaptation must be in (0, 1]");
-	if (!finite_f(o->white) || !(o->white > 0.0f))
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: white must be finite and > 0");
-	if (!finite_f(o->gamma) || !(o->gamma > 0.0f))
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: gamma must be finite and > 0");
-	if ((uint64_t)o->width * o->height > (1ull << 31))
-		return fail(RT_ERR_UNSUPPORTED, "display: more than 2^31 pixels");
-	return RT_OK;
-}
-
-static uint64_t display_out_bytes(const rt_display_opts *o)
-{
-	return (uint64_t)o->width * o->height * (o->pixel_format == RT_PIXEL_RGB8 ? 3u : 4u);
-}
-
-// argument checks of rt_display(_device), the device last; ws is checked for the device call only
-static int display_check(const rt_scene *s, const float *rgb, const rt_display_opts *o, const void *state, const void *ws,
-                         const void *out, const void *histogram, bool device)
-{
-	if (!s || !rgb || !o || !out)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	int rc = display_opts_check(o);
-	if (rc != RT_OK)
-		return rc;
-	const uint64_t n = (uint64_t)o->width * o->height;
-	if (device && (!ws || reinterpret_cast<uintptr_t>(ws) % 16u != 0u))
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: the workspace must not be NULL and must be 16-byte aligned");
-	// every buffer written (out, histogram, state, workspace) against every other buffer
-	const void *buf[5] = {out, histogram, state, device ? ws : nullptr, rgb};
-	const uint64_t bytes[5] = {display_out_bytes(o), 4ull * kDisplayBins, sizeof(rt_display_state), display_workspace_bytes(n), 12 * n};
-	for (int a = 0; a < 4; ++a)
-		for (int b = 0; b < 5; ++b)
-			if (a != b && ranges_overlap(buf[a], bytes[a], buf[b], bytes[b]))
-				return fail(RT_ERR_INVALID_ARGUMENT, "display: a buffer written overlaps another buffer");
-	if (s->device == RT_DEVICE_NONE)
-		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
-	return RT_OK;
-}
-
-extern "C" {
-
-int rt_display_opts_default(rt_display_opts *out)
-{
-	if (!out)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	std::memset(out, 0, sizeof *out);
-	out->exposure_mode = RT_EXPOSURE_AUTO;
-	out->tonemap = RT_TONEMAP_ACES;
-	out->transfer = RT_TRANSFER_SRGB;
-	out->quantiser = RT_QUANT_DITHER;
-	out->pixel_format = RT_PIXEL_RGBA8;
-	out->exposure_ev = 0.0f;
-	out->key_ev = -2.47393119f; // log2(0.18)
-	out->meter_low = 0.10f;
-	out->meter_high = 0.90f;
-	out->ev_min = -16.0f;
-	out->ev_max = 16.0f;
-	out->adaptation = 1.0f;
-	out->white = 4.0f;
-	out->gamma = 2.2f;
-	return RT_OK;
-}
-
-int rt_display_workspace_bytes(const rt_display_opts *o, uint64_t *bytes)
-{
-	if (!o || !bytes)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (o->width == 0 || o->height == 0)
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: width and height must be >= 1");
-	const uint64_t n = (uint64_t)o->width * o->height;
-	if (n > (1ull << 31))
-		return fail(RT_ERR_UNSUPPORTED, "display: more than 2^31 pixels");
-	*bytes = display_workspace_bytes(n);
-	return RT_OK;
-}
-
-int rt_display_output_bytes(const rt_display_opts *o, uint64_t *bytes)
-{
-	if (!o || !bytes)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (o->width == 0 || o->height == 0)
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: width and height must be >= 1");
-	if (o->pixel_format < RT_PIXEL_RGBA8 || o->pixel_format > RT_PIXEL_RGB8)
-		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown pixel_format");
-	if ((uint64_t)o->width * o->height > (1ull << 31))
-		return fail(RT_ERR_UNSUPPORTED, "display: more than 2^31 pixels");
-	*bytes = display_out_bytes(o);
-	return RT_OK;
-}
-
-int rt_display_device(rt_scene *s, const float *d_rgb, const rt_display_opts *o, rt_display_state *d_state, void *d_workspace,
-                      void *d_out, uint32_t *d_histogram, void *hip_stream)
-{
-	int rc = display_check(s, d_rgb, o, d_state, d_workspace, d_out, d_histogram, true);
-	if (rc != RT_OK)
-		return rc;
-	HIP_TRY(hipSetDevice(s->device)); // a multi-device head runs on devices[0]
-	DevDisplayParams P;
-	std::memset(&P, 0, sizeof P);
-	P.n_px = o->width * o->height;
-	P.width = o->width;
-	P.mode = o->exposure_mode;
-	P.tonemap = o->tonemap;
-	P.transfer = o->transfer;
-	P.quantiser = o->quantiser;
-	P.format = o->pixel_format;
-	P.exposure_ev = o->exposure_ev;
-	P.key_ev = o->key_ev;
-	P.meter_low = o->meter_low;
-	P.meter_high = o->meter_high;
-	P.ev_min = o->ev_min;
-	P.ev_max = o->ev_max;
-	P.adaptation = o->adaptation;
-	P.white2 = o->white * o->white;
-	P.hable_fw = display_hable(o->white);
-	P.inv_gamma = 1.0f / o->gamma;
-	P.seed_lo = (uint32_t)o->seed;
-	P.seed_hi = (uint32_t)(o->seed >> 32);
-	P.rgb = d_rgb;
-	P.state = d_state;
-	P.ws = static_cast<char *>(d_workspace);
-	P.out = d_out;
-	P.histogram = d_histogram;
-	HIP_TRY(launch_display(static_cast<hipStream_t>(hip_stream), P));
-	return RT_OK;
-}
-
-int rt_display(rt_scene *s, const float *host_rgb, const rt_display_opts *o, void *host_out, rt_display_state *host_state,
-               uint32_t *host_histogram)
-{
-	int rc = display_check(s, host_rgb, o, host_state, nullptr, host_out, host_histogram, false);
-	if (rc != RT_OK)
-		return rc;
-	HIP_TRY(hipSetDevice(s->device));
-	const uint64_t n = (uint64_t)o->width * o->height;
-	// state (16), histogram (1024), workspace, output, input: every part 16-byte aligned
-	auto up16 = [](uint64_t b) { return (b + 15u) / 16u * 16u; };
-	const uint64_t off_hist = 16, off_ws = off_hist + 4ull * kDisplayBins, off_out = off_ws + display_workspace_bytes(n);
-	const uint64_t off_in = off_out + up16(display_out_bytes(o)), total = off_in + 12 * n;
-	if (total > s->d_display_bytes) { // grown for larger frames only; the state is kept on the host side meanwhile
-		rt_display_state keep{};
-		if (s->d_display && s->display_has_state)
-			HIP_TRY(hipMemcpy(&keep, s->d_display, sizeof keep, hipMemcpyDeviceToHost));
-		if (s->d_display)
-			(void)hipFree(s->d_display);
-		s->d_display = nullptr;
-		s->d_display_bytes = 0;
-		HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_display), total));
-		s->d_display_bytes = total;
-		HIP_TRY(hipMemcpy(s->d_display, &keep, sizeof keep, hipMemcpyHostToDevice));
-	}
-	char *base = s->d_display;
-	rt_display_state *d_state = reinterpret_cast<rt_display_state *>(base);
-	uint32_t *d_hist = reinterpret_cast<uint32_t *>(base + off_hist);
-	const bool fresh = !s->display_has_state || o->width != s->display_w || o->height != s->display_h;
-	s->display_has_state = false; // until this call has succeeded
-	hipError_t e = hipSuccess;
-	if (fresh)
-		e = hipMemsetAsync(d_state, 0, sizeof(rt_display_state), s->stream);
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(base + off_in, host_rgb, 12 * n, hipMemcpyHostToDevice, s->stream);
-	if (e != hipSuccess) {
-		(void)hipStreamSynchronize(s->stream);
-		return hip_fail(e, "display upload");
-	}
-	rc = rt_display_device(s, reinterpret_cast<const float *>(base + off_in), o, d_state, base + off_ws, base + off_out, d_hist,
-	                       s->stream);
-	if (rc == RT_OK)
-		e = hipMemcpyAsync(host_out, base + off_out, display_out_bytes(o), hipMemcpyDeviceToHost, s->stream);
-	if (rc == RT_OK && e == hipSuccess && host_state)
-		e = hipMemcpyAsync(host_state, d_state, sizeof(rt_display_state), hipMemcpyDeviceToHost, s->stream);
-	if (rc == RT_OK && e == hipSuccess && host_histogram)
-		e = hipMemcpyAsync(host_histogram, d_hist, 4ull * kDisplayBins, hipMemcpyDeviceToHost, s->stream);
-	const hipError_t e_sync = hipStreamSynchronize(s->stream);
-	if (rc == RT_OK && e == hipSuccess)
-		e = e_sync;
-	if (rc == RT_OK && e != hipSuccess)
-		rc = hip_fail(e, "display");
-	if (rc == RT_OK) {
-		s->display_has_state = true;
-		s->display_w = o->width;
-		s->display_h = o->height;
-	}
-	return rc;
-}
-
-int rt_display_reset(rt_scene *s)
-{
-	if (!s)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	s->display_has_state = false;
 	return RT_OK;
 }
 

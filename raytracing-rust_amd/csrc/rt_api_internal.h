@@ -1,0 +1,228 @@
+// rt_api_internal.h -- what the host translation units of librt_hip.so share (rt_api.cpp, rt_api_post.cpp): the scene
+// handle, the error convention, and the plumbing every blocking entry point repeats.  Not installed, not part of include/.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/rt_hip.h"
+#include "rt_build.h"
+#include "rt_types.h"
+
+// the text behind rt_last_error(): ONE per thread for the whole library (defined in rt_api.cpp)
+extern thread_local std::string g_error;
+
+inline int fail(int code, const std::string &msg)
+{
+	g_error = msg;
+	return code;
+}
+inline int hip_fail(hipError_t e, const char *what)
+{
+	g_error = std::string(what) + ": " + hipGetErrorString(e);
+	return e == hipErrorOutOfMemory ? RT_ERR_OUT_OF_MEMORY : RT_ERR_HIP;
+}
+#define HIP_TRY(expr)                       \
+	do {                                    \
+		hipError_t e_ = (expr);             \
+		if (e_ != hipSuccess)               \
+			return hip_fail(e_, #expr);     \
+	} while (0)
+
+// the pruned walk above this many primitives, the exhaustive one up to it (measured: see the crossovers in rt_api.cpp)
+constexpr uint32_t kPruneAbove = 100;
+
+struct rt_scene {
+	int device = 0;
+	rt::HostScene host;
+	rt::DevScene dev{};
+	std::vector<void *> allocations;
+	hipStream_t stream = nullptr; // used by the blocking entry points
+	uint32_t *d_work_counter = nullptr;
+	unsigned long long *d_rays = nullptr;
+	hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+	bool timed = false;
+	uint32_t n_launches = 0;
+	int n_cus = 0;
+	int traversal_mode = -1; // -1 auto, 0 exhaustive (reference order of work), 1 pruned
+	int schedule_mode = -1;  // -1 auto, 0 coarse (two super-phases), 1 fine (every step voted)
+	int feature_set = 2;     // smallest kernel variant covering the scene: 0 spheres-only, 1 simple, 2 full
+	int min_feature_set = 0; // what the scene needs (feature_set may be forced larger for tests)
+	// the tree is one inner node over two leaves of one primitive each: launches that would run the spheres-only exhaustive
+	// coarse kernels run their FeatPair twins (rt_types.h) -- unless a feature set was asked for by name (RT_TUNE_FEATURE_SET)
+	bool pair_tree = false, feature_set_forced = false;
+	rt::DevPairScene pair{}; // pair_tree: the scene as the FeatPair kernels take it, in their kernel arguments (rt_types.h)
+	bool scene_lds_allowed = true;
+	float *d_partial = nullptr; // sample_split > 1: per-chunk means, grown on demand
+	size_t partial_floats = 0;
+	// rt_sample_image: two batches in flight (device + pinned host buffers, copy stream, events)
+	float *d_prog[2] = {nullptr, nullptr};
+	float *h_prog[2] = {nullptr, nullptr};
+	unsigned long long *d_prog_rays = nullptr; // [2]
+	unsigned long long *h_prog_rays = nullptr; // [2], pinned
+	size_t d_prog_floats[2] = {0, 0}, h_prog_floats[2] = {0, 0};
+	hipStream_t copy_stream = nullptr;
+	hipEvent_t ev_batch[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+	size_t max_lds = 65536;
+	rt_launch_info last_launch{};
+	uint32_t stack_cap_override = 0; // RT_TUNE_STACK_CAP
+	int exchange_mode = 0;           // RT_TUNE_EXCHANGE
+	uint32_t stack_depth_narrow = 2; // HostScene::stack_depth_narrow (members of a multi-device scene have no host scene of their own)
+	uint32_t *d_stack_ovf = nullptr; // traversal-stack overflow area (deep trees under the fine schedule), grown on demand
+	size_t stack_ovf_words = 0;
+	uint8_t *d_rgb8 = nullptr; // rt_render_rgb8: the quantised frame
+	size_t d_rgb8_bytes = 0;
+	// ---- multi-device scenes (rt_scene_create_multi).  The handle a caller holds is the HEAD: an ordinary scene on
+	// devices[0] that additionally owns one member scene per further device (uploaded from the head's host build) and
+	// gathers their tile shards into its own frames.  Members render like any single-device scene. ----
+	std::vector<rt_scene *> peers;         // head only: the members on devices[1..n-1]
+	bool member_call = false;              // set while the head renders its own shard through the single-device path
+	float *d_shard = nullptr;              // every member incl. the head: its packed shard (RT_LAYOUT_SHARD)
+	size_t shard_floats = 0;
+	unsigned long long *d_member_rays = nullptr; // the member's own ray counter (the head's d_rays holds the job's total)
+	hipEvent_t ev_shard = nullptr;         // member: its shard is rendered
+	hipEvent_t ev_begin = nullptr;         // head: the caller's stream has reached this render
+	float *d_gather = nullptr;             // head: the peers' shards, once gathered
+	size_t gather_floats = 0;
+	unsigned long long *d_gather_rays = nullptr; // head: [n] the members' ray counters
+	void *nccl_comms = nullptr;            // head: ncclComm_t[n] when the devices are distinct and RCCL is usable
+	int gather_mode = 0;                   // rt_gather_mode, decided when the scene is created (rt_scene_create_multi)
+	std::string gather_note;               // why (rt_scene_gather_info)
+	hipEvent_t ev_gathered = nullptr;      // head: the last render's gather + scatter have read every member's shard
+	bool gathered_once = false;
+	uint32_t *d_prim_desc = nullptr;       // rt_render_aov: BVH slot -> rt_scene_desc index, uploaded on first use (in `allocations`)
+	char *d_denoise = nullptr;             // rt_denoise / rt_render_denoised: device frames + workspace, grown on first use
+	size_t d_denoise_bytes = 0;
+	char *d_temporal = nullptr;            // rt_denoise_temporal: its two history buffers, for frames of temporal_w x temporal_h
+	uint32_t temporal_w = 0, temporal_h = 0;
+	int temporal_cur = -1;                 // the history buffer the last call wrote; -1 = no history
+	rt_camera temporal_prev{};             // the camera of that call
+	char *d_display = nullptr;             // rt_display: state, histogram, workspace, output and input, grown for larger frames
+	size_t d_display_bytes = 0;
+	uint32_t display_w = 0, display_h = 0; // the frame size of the last successful call
+	bool display_has_state = false;        // false: the next rt_display starts from a zero state
+};
+
+template <class T> static int upload(rt_scene *s, const T *src, size_t count, const T **dst)
+{
+	void *p = nullptr;
+	const size_t bytes = (count ? count : 1) * sizeof(T);
+	HIP_TRY(hipMalloc(&p, bytes));
+	s->allocations.push_back(p);
+	if (count)
+		HIP_TRY(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+	*dst = static_cast<const T *>(p);
+	return RT_OK;
+}
+
+inline bool ranges_overlap(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes)
+{
+	if (!a || !b)
+		return false;
+	const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+	return x < y + b_bytes && y < x + a_bytes;
+}
+
+// ---- the argument checks and buffer plumbing the entry points share ----
+
+// the last check of an entry point that computes (so that a host-only scene still reports bad arguments as such)
+inline int need_device(const rt_scene *s)
+{
+	if (s->device == RT_DEVICE_NONE)
+		return fail(RT_ERR_NO_DEVICE, "host-only scene (RT_DEVICE_NONE): this call needs a GPU, there is no CPU fallback");
+	return RT_OK;
+}
+
+// both sides of a frame >= min_side (2 where u and v divide by W-1 and H-1); `stage` starts the message: "denoise: ", or ""
+inline int frame_sides(const char *stage, uint64_t w, uint64_t h, uint64_t min_side)
+{
+	if (w >= min_side && h >= min_side)
+		return RT_OK;
+	return fail(RT_ERR_INVALID_ARGUMENT, stage + ("width and height must be >= " + std::to_string(min_side)) +
+	                                         (min_side >= 2 ? " (u and v divide by W-1 and H-1)" : ""));
+}
+
+// the sides, then *n = w * h, refused above 2^31 pixels (a side above 2^31 too: the product must not wrap).  A stage that reports
+// its other options between the two checks calls frame_sides first and this last.
+inline int frame_pixels(const char *stage, uint64_t w, uint64_t h, uint64_t min_side, uint64_t *n)
+{
+	if (const int rc = frame_sides(stage, w, h, min_side); rc != RT_OK)
+		return rc;
+	if (w > (1ull << 31) || h > (1ull << 31) || w * h > (1ull << 31))
+		return fail(RT_ERR_UNSUPPORTED, std::string(stage) + "more than 2^31 pixels");
+	*n = w * h;
+	return RT_OK;
+}
+
+// each of the first n_written buffers against every other of the n_total (those only read may share memory); NULL overlaps nothing
+inline int check_disjoint(const char *message, const void *const buf[], const uint64_t bytes[], int n_written, int n_total)
+{
+	for (int a = 0; a < n_written; ++a)
+		for (int b = 0; b < n_total; ++b)
+			if (a != b && ranges_overlap(buf[a], bytes[a], buf[b], bytes[b]))
+				return fail(RT_ERR_INVALID_ARGUMENT, message);
+	return RT_OK;
+}
+
+// a scene-owned device buffer of `count` elements, replaced (contents dropped) when `need` is larger; nothing is held after a failure
+template <class T> static int grow_device_buffer(T *&p, size_t &count, size_t need)
+{
+	if (need <= count)
+		return RT_OK;
+	if (p)
+		(void)hipFree(p);
+	p = nullptr;
+	count = 0;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p), need * sizeof(T)));
+	count = need;
+	return RT_OK;
+}
+
+// The copies and the status of one blocking entry point on s->stream.  Optional channels (host pointer or NULL, a count of
+// 4-byte elements) are laid out one after another behind a prefix the caller owns; copies are skipped once anything has
+// failed; finish() always drains the stream.  Which error wins: a non-OK `rc` (set by the caller from the _device call, its
+// message kept), else the first HIP error in `e`, else the synchronise error.
+struct Staging {
+	rt_scene *s;
+	size_t total = 0; // 4-byte elements laid out so far (construct with the prefix)
+	int rc = RT_OK;
+	hipError_t e = hipSuccess;
+	int n = 0;
+	const void *host[6];
+	size_t offset[6], count[6];
+
+	bool ok() const { return rc == RT_OK && e == hipSuccess; }
+	void add(const void *h, size_t elements)
+	{
+		host[n] = h;
+		offset[n] = total;
+		count[n++] = elements;
+		total += h ? elements : 0;
+	}
+	// channel c inside the allocation at `base`; NULL when the caller did not give it
+	template <class T = float> T *at(char *base, int c) const { return host[c] ? reinterpret_cast<T *>(base + 4 * offset[c]) : nullptr; }
+	void copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) // skipped for a NULL (optional) host side
+	{
+		if (dst && src && ok())
+			e = hipMemcpyAsync(dst, src, bytes, kind, s->stream);
+	}
+	void to_device(void *d, const void *h, size_t bytes) { copy(d, h, bytes, hipMemcpyHostToDevice); }
+	void download(void *h, const void *d, size_t bytes) { copy(h, d, bytes, hipMemcpyDeviceToHost); }
+	bool upload(char *base) // every channel given
+	{
+		for (int c = 0; c < n; ++c)
+			to_device(at<char>(base, c), host[c], 4 * count[c]);
+		return ok();
+	}
+	int finish(const char *what)
+	{
+		const hipError_t e_sync = hipStreamSynchronize(s->stream);
+		if (ok())
+			e = e_sync;
+		if (rc == RT_OK && e != hipSuccess)
+			rc = hip_fail(e, what);
+		return rc;
+	}
+};

@@ -1,0 +1,719 @@
+// rt_api_post.cpp -- the host side of the post-processing stages of librt_hip.so (include/rt_hip.h): first-hit AOV buffers,
+// the A-Trous denoiser, temporal accumulation and the display stage.  Each stage has its kernels in a file of its own
+// (rt_aov.hip, rt_denoise.hip, rt_temporal.hip, rt_display.hip); here are their argument checks, their _device entry points
+// and the blocking wrappers that stage host buffers through scene-owned device memory (Staging, rt_api_internal.h).
+// Every check function ends with the device (need_device), so that a host-only scene reports bad arguments as such.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "rt_api_internal.h"
+#include "rt_aov.h"
+#include "rt_denoise.h"
+#include "rt_temporal.h"
+#include "rt_display.h"
+
+using namespace rt;
+
+// ---- first-hit AOV buffers (rt_aov.hip) ----
+// argument checks of both entry points, the device last (so that a host-only scene reports bad arguments as such)
+static int aov_check(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *b, uint32_t *mask)
+{
+	if (!s || !camera || !o || !b)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	*mask = (b->albedo ? kAovAlbedo : 0u) | (b->normal ? kAovNormal : 0u) | (b->depth ? kAovDepth : 0u) |
+	        (b->coverage ? kAovCoverage : 0u) | (b->primitive ? kAovPrimitive : 0u) | (b->material ? kAovMaterial : 0u);
+	if (*mask == 0u)
+		return fail(RT_ERR_INVALID_ARGUMENT, "rt_aov_buffers: every channel is NULL");
+	if (int rc = frame_sides("", o->width, o->height, 2); rc != RT_OK)
+		return rc;
+	if (o->width * o->height >= (1ull << 31)) // (this pass alone refuses exactly 2^31 pixels too)
+		return fail(RT_ERR_UNSUPPORTED, "image larger than 2^31 pixels");
+	if (o->samples_per_pixel == 0 || o->samples_per_pixel >= (1ull << 32))
+		return fail(RT_ERR_INVALID_ARGUMENT, "samples_per_pixel must be in [1, 2^32)");
+	if (o->output_layout != RT_LAYOUT_FRAME)
+		return fail(RT_ERR_UNSUPPORTED, "AOV buffers are produced in RT_LAYOUT_FRAME only");
+	if (o->shard_count != 1)
+		return fail(RT_ERR_UNSUPPORTED, "AOV buffers are produced for the whole frame only (shard_count 1)");
+	return need_device(s);
+}
+
+extern "C" {
+
+int rt_render_aov_device(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *d_out, void *hip_stream)
+{
+	uint32_t mask = 0;
+	int rc = aov_check(s, camera, o, d_out, &mask);
+	if (rc != RT_OK)
+		return rc;
+	// a multi-device head is an ordinary scene on devices[0]: the AOV pass runs there alone
+	HIP_TRY(hipSetDevice(s->device));
+	if ((mask & kAovPrimitive) && !s->d_prim_desc) { // first use: BVH slot -> caller's index (synchronous, once per scene)
+		const std::vector<uint64_t> &order = s->host.primitive_order;
+		if (order.size() >= 0xFFFFFFFFull)
+			return fail(RT_ERR_UNSUPPORTED, "primitive IDs need fewer than 2^32 - 1 primitives");
+		std::vector<uint32_t> desc(order.size());
+		for (size_t i = 0; i < order.size(); ++i)
+			desc[i] = (uint32_t)order[i];
+		const uint32_t *d = nullptr;
+		rc = upload(s, desc.data(), desc.size(), &d);
+		if (rc != RT_OK)
+			return rc;
+		s->d_prim_desc = const_cast<uint32_t *>(d);
+	}
+	// traversal as rt_render / rt_check_hit choose it; the whole worst-case stack of the workgroup in LDS: the wide tree's only
+	// where it is walked and fits, the two-child tree's (and the two-child walk for every ray) otherwise
+	const bool prune = s->traversal_mode == -1 ? s->dev.n_prims > kPruneAbove : s->traversal_mode == 1;
+	DevScene dev = s->dev;
+	const bool walks_wide = prune && dev.nodes4 != nullptr && dev.narrow_only == 0u;
+	if (!walks_wide || aov_lds_bytes(dev) > s->max_lds) {
+		if (walks_wide)
+			dev.narrow_only = 1u;
+		dev.stack_depth = s->stack_depth_narrow;
+	}
+	if (aov_lds_bytes(dev) > s->max_lds)
+		return fail(RT_ERR_UNSUPPORTED, "traversal stacks exceed the LDS of one CU");
+	DevAovParams P;
+	std::memset(&P, 0, sizeof P);
+	std::memcpy(P.cam.origin, camera->origin, 12);
+	std::memcpy(P.cam.lower_left, camera->lower_left, 12);
+	std::memcpy(P.cam.horizontal, camera->horizontal, 12);
+	std::memcpy(P.cam.vertical, camera->vertical, 12);
+	P.width = (uint32_t)o->width;
+	P.height = (uint32_t)o->height;
+	P.tiles_x = (P.width + 7u) / 8u;
+	P.n_tiles = P.tiles_x * ((P.height + 7u) / 8u);
+	P.spp = (uint32_t)o->samples_per_pixel;
+	P.mask = mask;
+	P.seed_lo = (uint32_t)o->seed;
+	P.seed_hi = (uint32_t)(o->seed >> 32);
+	P.sample_begin_lo = (uint32_t)o->sample_begin;
+	P.sample_begin_hi = (uint32_t)(o->sample_begin >> 32);
+	P.prim_desc = s->d_prim_desc;
+	P.albedo = d_out->albedo;
+	P.normal = d_out->normal;
+	P.depth = d_out->depth;
+	P.coverage = d_out->coverage;
+	P.primitive = d_out->primitive;
+	P.material = d_out->material;
+	HIP_TRY(launch_aov(prune, static_cast<hipStream_t>(hip_stream), dev, P));
+	return RT_OK;
+}
+
+int rt_render_aov(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *out)
+{
+	uint32_t mask = 0;
+	int rc = aov_check(s, camera, o, out, &mask);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	// one device allocation per call for the requested channels, in rt_aov_buffers order; 4-byte elements throughout
+	const size_t n_px = (size_t)(o->width * o->height);
+	Staging st{s};
+	void *host[6] = {out->albedo, out->normal, out->depth, out->coverage, out->primitive, out->material};
+	for (int c = 0; c < 6; ++c)
+		st.add(host[c], (c < 2 ? 3 : 1) * n_px);
+	char *d = nullptr;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), st.total * 4));
+	const rt_aov_buffers dev_out = {st.at(d, 0), st.at(d, 1), st.at(d, 2), st.at(d, 3), st.at<uint32_t>(d, 4), st.at<uint32_t>(d, 5)};
+	st.rc = rt_render_aov_device(s, camera, o, &dev_out, s->stream);
+	for (int c = 0; c < 6; ++c)
+		st.download(host[c], st.at(d, c), 4 * st.count[c]);
+	rc = st.finish("render_aov");
+	(void)hipFree(d);
+	return rc;
+}
+
+} // extern "C"
+
+// ---- AOV-guided A-Trous denoiser (rt_denoise.hip) ----
+// the frame size and the filter options (width and height are passed separately: rt_render_denoised takes them from the render)
+static int denoise_opts_check(const rt_denoise_opts *d, uint64_t w, uint64_t h)
+{
+	if (int rc = frame_sides("denoise: ", w, h, 1); rc != RT_OK)
+		return rc;
+	if (d->iterations < 1 || d->iterations > 10)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise: iterations must be in 1..10");
+	const float sig[3] = {d->sigma_luminance, d->sigma_normal, d->sigma_depth};
+	for (float x : sig)
+		if (!std::isfinite(x) || !(x > 0.0f))
+			return fail(RT_ERR_INVALID_ARGUMENT, "denoise: sigma_luminance, sigma_normal and sigma_depth must be finite and > 0");
+	uint64_t n = 0;
+	return frame_pixels("denoise: ", w, h, 1, &n);
+}
+
+// argument checks of rt_denoise / rt_denoise_device, the device last (so that a host-only scene reports bad arguments as such);
+// `ws` is checked for the device call only
+static int denoise_check(const rt_scene *s, const rt_denoise_inputs *in, const rt_denoise_opts *o, const float *out, bool device,
+                         const void *ws)
+{
+	if (!s || !in || !o)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (!in->color || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise: color and out must not be NULL");
+	int rc = denoise_opts_check(o, o->width, o->height);
+	if (rc != RT_OK)
+		return rc;
+	const uint64_t n = (uint64_t)o->width * o->height;
+	// the workspace, then out, against what follows them (the inputs may share memory with one another)
+	const void *buf[7] = {ws, out, in->color, in->albedo, in->normal, in->depth, in->variance};
+	const uint64_t bytes[7] = {kDenoiseWorkspaceBytesPerPixel * n, 12 * n, 12 * n, 12 * n, 12 * n, 4 * n, 4 * n};
+	rc = check_disjoint("denoise: out overlaps an input", buf + 1, bytes + 1, 1, 6);
+	if (rc != RT_OK)
+		return rc;
+	if (device) {
+		if (!ws || reinterpret_cast<uintptr_t>(ws) % 16u != 0u)
+			return fail(RT_ERR_INVALID_ARGUMENT, "denoise: the workspace must be non-NULL and 16-byte aligned");
+		rc = check_disjoint("denoise: the workspace overlaps an input or out", buf, bytes, 1, 7);
+		if (rc != RT_OK)
+			return rc;
+	}
+	return need_device(s);
+}
+
+static DevDenoiseParams denoise_params(const rt_denoise_opts *o, uint64_t w, uint64_t h, const rt_denoise_inputs &in, void *ws,
+                                       float *out)
+{
+	DevDenoiseParams P;
+	std::memset(&P, 0, sizeof P);
+	P.width = (uint32_t)w;
+	P.height = (uint32_t)h;
+	P.iterations = o->iterations;
+	P.sigma_l = o->sigma_luminance;
+	P.sigma_n = o->sigma_normal;
+	P.sigma_z = o->sigma_depth;
+	P.color = in.color;
+	P.albedo = in.albedo;
+	P.normal = in.normal;
+	P.depth = in.depth;
+	P.variance = in.variance;
+	const size_t n = (size_t)(w * h);
+	P.plane0 = static_cast<float4 *>(ws);
+	P.plane1 = P.plane0 + n;
+	P.guide = P.plane1 + n;
+	P.out = out;
+	return P;
+}
+
+extern "C" {
+
+int rt_denoise_opts_default(rt_denoise_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	out->iterations = 5;
+	out->sigma_luminance = 4.0f;
+	out->sigma_normal = 128.0f;
+	out->sigma_depth = 0.1f;
+	return RT_OK;
+}
+
+int rt_denoise_workspace_bytes(const rt_denoise_opts *o, uint64_t *bytes)
+{
+	if (!o || !bytes)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	uint64_t n = 0;
+	const int rc = frame_pixels("denoise: ", o->width, o->height, 1, &n);
+	if (rc == RT_OK)
+		*bytes = kDenoiseWorkspaceBytesPerPixel * n;
+	return rc;
+}
+
+int rt_denoise_device(rt_scene *s, const rt_denoise_inputs *d_in, const rt_denoise_opts *o, void *d_workspace, float *d_out,
+                      void *hip_stream)
+{
+	int rc = denoise_check(s, d_in, o, d_out, true, d_workspace);
+	if (rc != RT_OK)
+		return rc;
+	// a multi-device head is an ordinary scene on devices[0]: the filter runs there alone
+	HIP_TRY(hipSetDevice(s->device));
+	HIP_TRY(launch_denoise(static_cast<hipStream_t>(hip_stream), denoise_params(o, o->width, o->height, *d_in, d_workspace, d_out)));
+	return RT_OK;
+}
+
+int rt_denoise(rt_scene *s, const rt_denoise_inputs *in, const rt_denoise_opts *o, float *out)
+{
+	int rc = denoise_check(s, in, o, out, false, nullptr);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	const size_t n = (size_t)o->width * o->height;
+	// workspace first (16-byte aligned), then out, then the inputs given, in rt_denoise_inputs order
+	Staging st{s, kDenoiseWorkspaceBytesPerPixel / 4 * n + 3 * n};
+	st.add(in->color, 3 * n);
+	st.add(in->albedo, 3 * n);
+	st.add(in->normal, 3 * n);
+	st.add(in->depth, n);
+	st.add(in->variance, n);
+	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, st.total * 4); // grown on first use / larger frames only
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_denoise;
+	float *d_out = reinterpret_cast<float *>(base) + kDenoiseWorkspaceBytesPerPixel / 4 * n;
+	if (!st.upload(base))
+		return st.finish("denoise upload");
+	const rt_denoise_inputs d_in = {st.at(base, 0), st.at(base, 1), st.at(base, 2), st.at(base, 3), st.at(base, 4)};
+	st.rc = rt_denoise_device(s, &d_in, o, base, d_out, s->stream);
+	st.download(out, d_out, 3 * n * 4);
+	return st.finish("denoise");
+}
+
+int rt_render_denoised(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_denoise_opts *dopts, float *out_clean,
+                       float *out_noisy, uint64_t *rays_shot)
+{
+	if (!s || !camera || !o || !dopts || !out_clean)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	int rc = denoise_opts_check(dopts, o->width, o->height);
+	if (rc != RT_OK)
+		return rc;
+	rc = frame_sides("", o->width, o->height, 2);
+	if (rc != RT_OK)
+		return rc;
+	if (o->samples_per_pixel < 2 || o->samples_per_pixel % 2 != 0 || o->samples_per_pixel >= (1ull << 32))
+		return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_denoised: samples_per_pixel must be even, >= 2 and < 2^32");
+	if (o->render_method != RT_METHOD_NAIVE && o->render_method != RT_METHOD_MIS)
+		return fail(RT_ERR_INVALID_ARGUMENT, "unknown render method");
+	if (o->output_layout != RT_LAYOUT_FRAME)
+		return fail(RT_ERR_UNSUPPORTED, "rt_render_denoised: RT_LAYOUT_FRAME only");
+	if (o->shard_count != 1)
+		return fail(RT_ERR_UNSUPPORTED, "rt_render_denoised: the whole frame only (shard_count 1)");
+	const size_t n = (size_t)(o->width * o->height);
+	if (ranges_overlap(out_clean, 12 * n, out_noisy, 12 * n))
+		return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_denoised: out_clean overlaps out_noisy");
+	rc = need_device(s);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	// two ray counters (16 bytes), the workspace, then the frames: A, B, albedo, normal, depth, noisy, clean
+	const size_t ws_floats = kDenoiseWorkspaceBytesPerPixel / 4 * n;
+	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, 16 + 4 * (ws_floats + 19 * n));
+	if (rc != RT_OK)
+		return rc;
+	unsigned long long *d_rays = reinterpret_cast<unsigned long long *>(s->d_denoise);
+	float *ws = reinterpret_cast<float *>(s->d_denoise + 16);
+	float *d_a = ws + ws_floats, *d_b = d_a + 3 * n, *d_albedo = d_b + 3 * n, *d_normal = d_albedo + 3 * n,
+	      *d_depth = d_normal + 3 * n, *d_noisy = d_depth + n, *d_clean = d_noisy + 3 * n;
+	const uint64_t half = o->samples_per_pixel / 2;
+	rt_render_opts oh = *o;
+	oh.samples_per_pixel = half;
+	Staging st{s};
+	st.rc = rt_render_device(s, camera, &oh, d_a, reinterpret_cast<uint64_t *>(d_rays), s->stream);
+	if (st.ok()) {
+		oh.sample_begin = o->sample_begin + half;
+		st.rc = rt_render_device(s, camera, &oh, d_b, reinterpret_cast<uint64_t *>(d_rays + 1), s->stream);
+	}
+	if (st.ok())
+		st.e = hipSetDevice(s->device);
+	if (st.ok()) {
+		rt_aov_buffers aov;
+		std::memset(&aov, 0, sizeof aov);
+		aov.albedo = d_albedo;
+		aov.normal = d_normal;
+		aov.depth = d_depth;
+		st.rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
+	}
+	if (st.ok()) {
+		const rt_denoise_inputs in = {d_noisy, d_albedo, d_normal, d_depth, nullptr};
+		DevDenoiseParams P = denoise_params(dopts, o->width, o->height, in, ws, d_clean);
+		P.half_a = d_a;
+		P.half_b = d_b;
+		P.noisy = d_noisy;
+		st.e = launch_denoise(s->stream, P);
+	}
+	unsigned long long rays[2] = {0, 0};
+	st.download(out_clean, d_clean, 3 * n * 4);
+	st.download(out_noisy, d_noisy, 3 * n * 4);
+	st.download(rays, d_rays, sizeof rays);
+	rc = st.finish("render_denoised");
+	if (rc == RT_OK && rays_shot)
+		*rays_shot = rays[0] + rays[1];
+	return rc;
+}
+
+} // extern "C"
+
+// ---- temporal accumulation with camera reprojection (rt_temporal.hip) ----
+static int temporal_opts_check(const rt_temporal_opts *o)
+{
+	const uint64_t w = o->denoise.width, h = o->denoise.height;
+	int rc = frame_sides("denoise_temporal: ", w, h, 2);
+	if (rc == RT_OK)
+		rc = denoise_opts_check(&o->denoise, w, h);
+	if (rc != RT_OK)
+		return rc;
+	if (!(o->alpha_color > 0.0f && o->alpha_color <= 1.0f) || !(o->alpha_moments > 0.0f && o->alpha_moments <= 1.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: alpha_color and alpha_moments must be in (0, 1]");
+	if (!std::isfinite(o->depth_tolerance) || !(o->depth_tolerance > 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: depth_tolerance must be finite and > 0");
+	if (!(o->normal_tolerance >= -1.0f && o->normal_tolerance <= 1.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: normal_tolerance must be in [-1, 1]");
+	if (o->max_history < 1)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: max_history must be >= 1");
+	return RT_OK;
+}
+
+// argument checks of rt_denoise_temporal(_device), the device last; hist_out and ws are checked for the device call only
+static int temporal_check(const rt_scene *s, const rt_temporal_inputs *in, const rt_camera *cam, const rt_camera *prev,
+                          const rt_temporal_opts *o, const void *hist_in, const void *hist_out, const void *ws, const float *out,
+                          const float *motion, bool device)
+{
+	if (!s || !in || !cam || !o)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (!in->color || !in->depth || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: color, depth and out must not be NULL");
+	if (device && (!hist_out || !ws))
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: history_out and the workspace must not be NULL");
+	if (hist_in && !prev)
+		return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: a history needs the previous camera");
+	int rc = temporal_opts_check(o);
+	if (rc != RT_OK)
+		return rc;
+	const uint64_t n = (uint64_t)o->denoise.width * o->denoise.height;
+	if (device) {
+		const void *aligned[3] = {hist_in, hist_out, ws};
+		for (const void *a : aligned)
+			if (reinterpret_cast<uintptr_t>(a) % 16u != 0u)
+				return fail(RT_ERR_INVALID_ARGUMENT, "denoise_temporal: the histories and the workspace must be 16-byte aligned");
+	}
+	// the four buffers written first
+	const void *buf[9] = {out, motion, hist_out, ws, in->color, in->albedo, in->normal, in->depth, hist_in};
+	const uint64_t bytes[9] = {12 * n, 8 * n, kTemporalHistoryBytesPerPixel * n, kTemporalWorkspaceBytesPerPixel * n,
+	                           12 * n, 12 * n, 12 * n, 4 * n, kTemporalHistoryBytesPerPixel * n};
+	rc = check_disjoint("denoise_temporal: a buffer written overlaps another buffer", buf, bytes, 4, 9);
+	return rc == RT_OK ? need_device(s) : rc;
+}
+
+static int temporal_bytes(const rt_temporal_opts *o, uint64_t per_pixel, uint64_t *bytes)
+{
+	if (!o || !bytes)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	uint64_t n = 0;
+	const int rc = frame_pixels("denoise_temporal: ", o->denoise.width, o->denoise.height, 2, &n);
+	if (rc == RT_OK)
+		*bytes = per_pixel * n;
+	return rc;
+}
+
+extern "C" {
+
+int rt_temporal_opts_default(rt_temporal_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	rt_denoise_opts_default(&out->denoise);
+	out->alpha_color = 0.2f;
+	out->alpha_moments = 0.2f;
+	out->depth_tolerance = 0.1f;
+	out->normal_tolerance = 0.9f;
+	out->max_history = 32;
+	return RT_OK;
+}
+
+int rt_temporal_history_bytes(const rt_temporal_opts *o, uint64_t *bytes)
+{
+	return temporal_bytes(o, kTemporalHistoryBytesPerPixel, bytes);
+}
+
+int rt_temporal_workspace_bytes(const rt_temporal_opts *o, uint64_t *bytes)
+{
+	return temporal_bytes(o, kTemporalWorkspaceBytesPerPixel, bytes);
+}
+
+int rt_denoise_temporal_device(rt_scene *s, const rt_temporal_inputs *d_in, const rt_camera *cam, const rt_camera *prev_cam,
+                               const void *d_history_in, void *d_history_out, const rt_temporal_opts *o, void *d_workspace,
+                               float *d_out, float *d_motion, void *hip_stream)
+{
+	int rc = temporal_check(s, d_in, cam, prev_cam, o, d_history_in, d_history_out, d_workspace, d_out, d_motion, true);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device)); // a multi-device head runs on devices[0]
+	const uint64_t w = o->denoise.width, h = o->denoise.height;
+	const size_t n = (size_t)(w * h);
+	DevTemporalParams T;
+	std::memset(&T, 0, sizeof T);
+	T.width = (uint32_t)w;
+	T.height = (uint32_t)h;
+	std::memcpy(T.cam, cam, sizeof T.cam);
+	if (d_history_in)
+		std::memcpy(T.prev, prev_cam, sizeof T.prev);
+	T.alpha_c = o->alpha_color;
+	T.alpha_m = o->alpha_moments;
+	T.depth_tol = o->depth_tolerance;
+	T.normal_tol = o->normal_tolerance;
+	T.max_history = (float)o->max_history;
+	T.color = d_in->color;
+	T.albedo = d_in->albedo;
+	T.normal = d_in->normal;
+	T.depth = d_in->depth;
+	T.hist_in = static_cast<const float4 *>(d_history_in);
+	T.hist_out = static_cast<float4 *>(d_history_out);
+	T.motion = d_motion;
+	const rt_denoise_inputs din = {d_in->color, d_in->albedo, d_in->normal, d_in->depth, nullptr};
+	DevDenoiseParams D = denoise_params(&o->denoise, w, h, din, d_workspace, d_out);
+	D.guide = T.hist_out + n; // H1 of the history written is the guide plane
+	HIP_TRY(launch_temporal(static_cast<hipStream_t>(hip_stream), T, D));
+	return RT_OK;
+}
+
+int rt_denoise_temporal(rt_scene *s, const rt_temporal_inputs *in, const rt_camera *cam, const rt_temporal_opts *o, float *out,
+                        float *motion)
+{
+	int rc = temporal_check(s, in, cam, nullptr, o, nullptr, nullptr, nullptr, out, motion, false);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	const uint32_t w = o->denoise.width, h = o->denoise.height;
+	const size_t n = (size_t)w * h;
+	if (w != s->temporal_w || h != s->temporal_h) { // a new frame size: new histories, no history
+		s->temporal_w = s->temporal_h = 0;
+		s->temporal_cur = -1;
+		size_t held = 0; // (always replaced: the buffer is two histories of exactly w x h)
+		rc = grow_device_buffer(s->d_temporal, held, 2 * kTemporalHistoryBytesPerPixel * n);
+		if (rc != RT_OK)
+			return rc;
+		s->temporal_w = w;
+		s->temporal_h = h;
+	}
+	// the workspace (16-byte aligned), out, motion, then the inputs given, in rt_temporal_inputs order
+	Staging st{s, kTemporalWorkspaceBytesPerPixel / 4 * n + 5 * n};
+	st.add(in->color, 3 * n);
+	st.add(in->albedo, 3 * n);
+	st.add(in->normal, 3 * n);
+	st.add(in->depth, n);
+	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, st.total * 4); // shared with rt_denoise / rt_render_denoised
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_denoise;
+	float *d_out = reinterpret_cast<float *>(base) + kTemporalWorkspaceBytesPerPixel / 4 * n, *d_motion = d_out + 3 * n;
+	if (!st.upload(base))
+		return st.finish("denoise_temporal upload");
+	const rt_temporal_inputs d_in = {st.at(base, 0), st.at(base, 1), st.at(base, 2), st.at(base, 3)};
+	char *hist[2] = {s->d_temporal, s->d_temporal + kTemporalHistoryBytesPerPixel * n};
+	const int next = s->temporal_cur == 0 ? 1 : 0;
+	const void *h_in = s->temporal_cur >= 0 ? hist[s->temporal_cur] : nullptr;
+	s->temporal_cur = -1; // until this call has succeeded
+	st.rc = rt_denoise_temporal_device(s, &d_in, cam, &s->temporal_prev, h_in, hist[next], o, base, d_out, motion ? d_motion : nullptr,
+	                                   s->stream);
+	st.download(out, d_out, 3 * n * 4);
+	st.download(motion, d_motion, 2 * n * 4);
+	rc = st.finish("denoise_temporal");
+	if (rc == RT_OK) {
+		s->temporal_cur = next;
+		s->temporal_prev = *cam;
+	}
+	return rc;
+}
+
+int rt_denoise_temporal_reset(rt_scene *s)
+{
+	if (!s)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	s->temporal_cur = -1;
+	return RT_OK;
+}
+
+} // extern "C"
+
+// ---- display stage: histogram, auto-exposure, tone curve, transfer, quantisation (rt_display.hip) ----
+static bool finite_f(float v) { return std::isfinite(v); }
+
+static int display_opts_check(const rt_display_opts *o)
+{
+	if (int rc = frame_sides("display: ", o->width, o->height, 1); rc != RT_OK)
+		return rc;
+	if (o->exposure_mode < RT_EXPOSURE_FIXED || o->exposure_mode > RT_EXPOSURE_AUTO)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown exposure_mode");
+	if (o->tonemap < RT_TONEMAP_CLAMP || o->tonemap > RT_TONEMAP_HABLE)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown tonemap");
+	if (o->transfer < RT_TRANSFER_SRGB || o->transfer > RT_TRANSFER_LINEAR)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown transfer");
+	if (o->quantiser < RT_QUANT_ROUND || o->quantiser > RT_QUANT_REFERENCE)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown quantiser");
+	if (o->pixel_format < RT_PIXEL_RGBA8 || o->pixel_format > RT_PIXEL_RGB8)
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: unknown pixel_format");
+	if (!finite_f(o->exposure_ev) || !finite_f(o->key_ev))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: exposure_ev and key_ev must be finite");
+	if (!(o->meter_low >= 0.0f && o->meter_low < o->meter_high && o->meter_high <= 1.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: need 0 <= meter_low < meter_high <= 1");
+	if (!finite_f(o->ev_min) || !finite_f(o->ev_max) || !(o->ev_min <= o->ev_max))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: ev_min and ev_max must be finite with ev_min <= ev_max");
+	if (!(o->adaptation > 0.0f && o->adaptation <= 1.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: adaptation must be in (0, 1]");
+	if (!finite_f(o->white) || !(o->white > 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: white must be finite and > 0");
+	if (!finite_f(o->gamma) || !(o->gamma > 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: gamma must be finite and > 0");
+	uint64_t n = 0;
+	return frame_pixels("display: ", o->width, o->height, 1, &n);
+}
+
+static uint64_t display_out_bytes(const rt_display_opts *o)
+{
+	return (uint64_t)o->width * o->height * (o->pixel_format == RT_PIXEL_RGB8 ? 3u : 4u);
+}
+
+// argument checks of rt_display(_device), the device last; ws is checked for the device call only
+static int display_check(const rt_scene *s, const float *rgb, const rt_display_opts *o, const void *state, const void *ws,
+                         const void *out, const void *histogram, bool device)
+{
+	if (!s || !rgb || !o || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	int rc = display_opts_check(o);
+	if (rc != RT_OK)
+		return rc;
+	const uint64_t n = (uint64_t)o->width * o->height;
+	if (device && (!ws || reinterpret_cast<uintptr_t>(ws) % 16u != 0u))
+		return fail(RT_ERR_INVALID_ARGUMENT, "display: the workspace must not be NULL and must be 16-byte aligned");
+	// every buffer written (out, histogram, state, workspace) against every other buffer
+	const void *buf[5] = {out, histogram, state, device ? ws : nullptr, rgb};
+	const uint64_t bytes[5] = {display_out_bytes(o), 4ull * kDisplayBins, sizeof(rt_display_state), display_workspace_bytes(n), 12 * n};
+	rc = check_disjoint("display: a buffer written overlaps another buffer", buf, bytes, 4, 5);
+	return rc == RT_OK ? need_device(s) : rc;
+}
+
+extern "C" {
+
+int rt_display_opts_default(rt_display_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	out->exposure_mode = RT_EXPOSURE_AUTO;
+	out->tonemap = RT_TONEMAP_ACES;
+	out->transfer = RT_TRANSFER_SRGB;
+	out->quantiser = RT_QUANT_DITHER;
+	out->pixel_format = RT_PIXEL_RGBA8;
+	out->exposure_ev = 0.0f;
+	out->key_ev = -2.47393119f; // log2(0.18)
+	out->meter_low = 0.10f;
+	out->meter_high = 0.90f;
+	out->ev_min = -16.0f;
+	out->ev_max = 16.0f;
+	out->adaptation = 1.0f;
+	out->white = 4.0f;
+	out->gamma = 2.2f;
+	return RT_OK;
+}
+
+int rt_display_workspace_bytes(const rt_display_opts *o, uint64_t *bytes)
+{
+	if (!o || !bytes)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	uint64_t n = 0;
+	const int rc = frame_pixels("display: ", o->width, o->height, 1, &n);
+	if (rc == RT_OK)
+		*bytes = display_workspace_bytes(n);
+	return rc;
+}
+
+int rt_display_output_bytes(const rt_display_opts *o, uint64_t *bytes)
+{
+	if (!o || !bytes)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	uint64_t n = 0;
+	int rc = frame_sides("display: ", o->width, o->height, 1);
+	if (rc == RT_OK && (o->pixel_format < RT_PIXEL_RGBA8 || o->pixel_format > RT_PIXEL_RGB8))
+		rc = fail(RT_ERR_INVALID_ARGUMENT, "display: unknown pixel_format");
+	if (rc == RT_OK)
+		rc = frame_pixels("display: ", o->width, o->height, 1, &n);
+	if (rc == RT_OK)
+		*bytes = display_out_bytes(o);
+	return rc;
+}
+
+int rt_display_device(rt_scene *s, const float *d_rgb, const rt_display_opts *o, rt_display_state *d_state, void *d_workspace,
+                      void *d_out, uint32_t *d_histogram, void *hip_stream)
+{
+	int rc = display_check(s, d_rgb, o, d_state, d_workspace, d_out, d_histogram, true);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device)); // a multi-device head runs on devices[0]
+	DevDisplayParams P;
+	std::memset(&P, 0, sizeof P);
+	P.n_px = o->width * o->height;
+	P.width = o->width;
+	P.mode = o->exposure_mode;
+	P.tonemap = o->tonemap;
+	P.transfer = o->transfer;
+	P.quantiser = o->quantiser;
+	P.format = o->pixel_format;
+	P.exposure_ev = o->exposure_ev;
+	P.key_ev = o->key_ev;
+	P.meter_low = o->meter_low;
+	P.meter_high = o->meter_high;
+	P.ev_min = o->ev_min;
+	P.ev_max = o->ev_max;
+	P.adaptation = o->adaptation;
+	P.white2 = o->white * o->white;
+	P.hable_fw = display_hable(o->white);
+	P.inv_gamma = 1.0f / o->gamma;
+	P.seed_lo = (uint32_t)o->seed;
+	P.seed_hi = (uint32_t)(o->seed >> 32);
+	P.rgb = d_rgb;
+	P.state = d_state;
+	P.ws = static_cast<char *>(d_workspace);
+	P.out = d_out;
+	P.histogram = d_histogram;
+	HIP_TRY(launch_display(static_cast<hipStream_t>(hip_stream), P));
+	return RT_OK;
+}
+
+int rt_display(rt_scene *s, const float *host_rgb, const rt_display_opts *o, void *host_out, rt_display_state *host_state,
+               uint32_t *host_histogram)
+{
+	int rc = display_check(s, host_rgb, o, host_state, nullptr, host_out, host_histogram, false);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	const uint64_t n = (uint64_t)o->width * o->height;
+	// state (16), histogram (1024), workspace, output, input: every part 16-byte aligned
+	auto up16 = [](uint64_t b) { return (b + 15u) / 16u * 16u; };
+	const uint64_t off_hist = 16, off_ws = off_hist + 4ull * kDisplayBins, off_out = off_ws + display_workspace_bytes(n);
+	const uint64_t off_in = off_out + up16(display_out_bytes(o)), total = off_in + 12 * n;
+	if (total > s->d_display_bytes) { // grown for larger frames only; the state is kept on the host side meanwhile
+		rt_display_state keep{};
+		if (s->d_display && s->display_has_state)
+			HIP_TRY(hipMemcpy(&keep, s->d_display, sizeof keep, hipMemcpyDeviceToHost));
+		rc = grow_device_buffer(s->d_display, s->d_display_bytes, (size_t)total);
+		if (rc != RT_OK)
+			return rc;
+		HIP_TRY(hipMemcpy(s->d_display, &keep, sizeof keep, hipMemcpyHostToDevice));
+	}
+	char *base = s->d_display;
+	rt_display_state *d_state = reinterpret_cast<rt_display_state *>(base);
+	uint32_t *d_hist = reinterpret_cast<uint32_t *>(base + off_hist);
+	const bool fresh = !s->display_has_state || o->width != s->display_w || o->height != s->display_h;
+	s->display_has_state = false; // until this call has succeeded
+	Staging st{s};
+	if (fresh)
+		st.e = hipMemsetAsync(d_state, 0, sizeof(rt_display_state), s->stream);
+	st.to_device(base + off_in, host_rgb, 12 * n);
+	if (!st.ok())
+		return st.finish("display upload");
+	st.rc = rt_display_device(s, reinterpret_cast<const float *>(base + off_in), o, d_state, base + off_ws, base + off_out, d_hist,
+	                          s->stream);
+	st.download(host_out, base + off_out, display_out_bytes(o));
+	st.download(host_state, d_state, sizeof(rt_display_state));
+	st.download(host_histogram, d_hist, 4ull * kDisplayBins);
+	rc = st.finish("display");
+	if (rc == RT_OK) {
+		s->display_has_state = true;
+		s->display_w = o->width;
+		s->display_h = o->height;
+	}
+	return rc;
+}
+
+int rt_display_reset(rt_scene *s)
+{
+	if (!s)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	s->display_has_state = false;
+	return RT_OK;
+}
+
+} // extern "C"

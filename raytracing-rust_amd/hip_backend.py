@@ -57,6 +57,32 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+def _dp(ptr, ctype=C.c_float):
+    """a device address (an int, 0 / None = not given) as a typed ctypes pointer"""
+    return C.cast(C.c_void_p(int(ptr)), C.POINTER(ctype)) if ptr else None
+
+
+def _set_f32_inputs(ins, color, optional, keep):
+    """the inputs of denoise / denoise_temporal: color (H, W, 3) and the optional (name, array or None, channels) guides as
+    contiguous f32 of the frame's size; sets the pointers of `ins`, appends the arrays to `keep`; returns (h, w)"""
+    color = np.ascontiguousarray(color, dtype=np.float32)
+    if color.ndim != 3 or color.shape[2] != 3:
+        raise ValueError(f"color must be (H, W, 3), got {color.shape}")
+    h, w = color.shape[:2]
+    keep.append(color)
+    ins.color = _p(color, C.c_float)
+    for name, a, channels in optional:
+        if a is None:
+            continue
+        shape = (h, w, channels) if channels > 1 else (h, w)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != shape:
+            raise ValueError(f"{name} must be {shape}, got {a.shape}")
+        keep.append(a)
+        setattr(ins, name, _p(a, C.c_float))
+    return h, w
+
+
 def _f3(v):
     return (C.c_float * 3)(*[float(np.float32(x)) for x in v])
 
@@ -279,7 +305,7 @@ class HipScene:
             if name not in abi.AOV_CHANNELS:
                 raise ValueError(f"unknown AOV channel {name!r}")
             ctype = C.c_uint32 if name in ("primitive", "material") else C.c_float
-            setattr(bufs, name, C.cast(C.c_void_p(int(ptr)), C.POINTER(ctype)) if ptr else None)
+            setattr(bufs, name, _dp(ptr, ctype))
         _check(lib().rt_render_aov_device(self._h, C.byref(camera), C.byref(opts), C.byref(bufs), C.c_void_p(stream)))
 
     # ---- AOV-guided A-Trous denoiser (rt_denoise) ----
@@ -295,21 +321,9 @@ class HipScene:
             guides, albedo = albedo, None
         albedo, normal = guides.get("albedo", albedo), guides.get("normal", normal)
         depth, variance = guides.get("depth", depth), guides.get("variance", variance)
-        color = np.ascontiguousarray(color, dtype=np.float32)
-        if color.ndim != 3 or color.shape[2] != 3:
-            raise ValueError(f"color must be (H, W, 3), got {color.shape}")
-        h, w = color.shape[:2]
-        ins, keep = abi.DenoiseInputs(), [color]
-        ins.color = _p(color, C.c_float)
-        for name, a, shape in (("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w)),
-                               ("variance", variance, (h, w))):
-            if a is None:
-                continue
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.shape != shape:
-                raise ValueError(f"{name} must be {shape}, got {a.shape}")
-            keep.append(a)
-            setattr(ins, name, _p(a, C.c_float))
+        ins, keep = abi.DenoiseInputs(), []
+        h, w = _set_f32_inputs(ins, color, (("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1),
+                                            ("variance", variance, 1)), keep)
         o = denoise_opts(w, h, **opts)
         out = np.zeros((h, w, 3), dtype=np.float32)
         _check(lib().rt_denoise(self._h, C.byref(ins), C.byref(o), _p(out, C.c_float)))
@@ -323,9 +337,9 @@ class HipScene:
         for name, ptr in d_ptrs.items():
             if name not in abi.DENOISE_INPUTS:
                 raise ValueError(f"unknown denoise input {name!r}")
-            setattr(ins, name, C.cast(C.c_void_p(int(ptr)), C.POINTER(C.c_float)) if ptr else None)
+            setattr(ins, name, _dp(ptr))
         _check(lib().rt_denoise_device(self._h, C.byref(ins), C.byref(opts), C.c_void_p(int(d_workspace)),
-                                       C.cast(C.c_void_p(int(d_out)), C.POINTER(C.c_float)), C.c_void_p(stream)))
+                                       _dp(d_out), C.c_void_p(stream)))
 
     def render_denoised(self, camera, opts, dopts=None):
         """rt_render_denoised: two half renders, the AOVs of all passes and the filter in one call.  Returns (clean, noisy,
@@ -354,22 +368,10 @@ class HipScene:
         elif isinstance(albedo, dict):
             guides, albedo = albedo, None
         albedo, normal, depth = guides.get("albedo", albedo), guides.get("normal", normal), guides.get("depth", depth)
-        color = np.ascontiguousarray(color, dtype=np.float32)
-        if color.ndim != 3 or color.shape[2] != 3:
-            raise ValueError(f"color must be (H, W, 3), got {color.shape}")
         if depth is None:
             raise ValueError("denoise_temporal needs depth")
-        h, w = color.shape[:2]
-        ins, keep = abi.TemporalInputs(), [color]
-        ins.color = _p(color, C.c_float)
-        for name, a, shape in (("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
-            if a is None:
-                continue
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.shape != shape:
-                raise ValueError(f"{name} must be {shape}, got {a.shape}")
-            keep.append(a)
-            setattr(ins, name, _p(a, C.c_float))
+        ins, keep = abi.TemporalInputs(), []
+        h, w = _set_f32_inputs(ins, color, (("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1)), keep)
         o = temporal_opts(w, h, **opts)
         out = np.zeros((h, w, 3), dtype=np.float32)
         mv = np.zeros((h, w, 2), dtype=np.float32) if motion else None
@@ -391,15 +393,11 @@ class HipScene:
         for name, ptr in d_ptrs.items():
             if name not in abi.TEMPORAL_INPUTS:
                 raise ValueError(f"unknown temporal input {name!r}")
-            setattr(ins, name, C.cast(C.c_void_p(int(ptr)), C.POINTER(C.c_float)) if ptr else None)
-
-        def fp(ptr):
-            return C.cast(C.c_void_p(int(ptr)), C.POINTER(C.c_float)) if ptr else None
-
+            setattr(ins, name, _dp(ptr))
         _check(lib().rt_denoise_temporal_device(
             self._h, C.byref(ins), C.byref(camera), C.byref(prev_camera) if prev_camera is not None else None,
             C.c_void_p(int(d_history_in) or None), C.c_void_p(int(d_history_out) or None), C.byref(opts),
-            C.c_void_p(int(d_workspace) or None), fp(d_out), fp(d_motion), C.c_void_p(stream)))
+            C.c_void_p(int(d_workspace) or None), _dp(d_out), _dp(d_motion), C.c_void_p(stream)))
 
     # ---- display stage: auto-exposure, tone curve, transfer, 8-bit output (rt_display) ----
     def display(self, image, histogram=False, **opts):

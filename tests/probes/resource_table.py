@@ -27,10 +27,22 @@ KEYS = ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spil
         "group_segment_fixed_size", "kernarg_segment_size", "max_flat_workgroup_size")
 
 
-def code_object(so_path):
-    """the gfx950 ELF inside the library's clang offload bundle"""
+MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+
+
+def rebuild_if_stale():
+    """make librt_hip.so again when it is older than its sources: what is read must describe THESE sources"""
+    csrc = os.path.join(ROOT, "raytracing-rust_amd", "csrc")
+    srcs = [os.path.join(csrc, n) for n in os.listdir(csrc) if n.endswith((".hip", ".h", ".cpp")) or n == "Makefile"]
+    srcs.append(os.path.join(ROOT, "include", "rt_detmath.h"))
+    if not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(p) for p in srcs):
+        subprocess.run(["make", "-C", csrc, "-s", "../librt_hip.so"], check=True)
+
+
+def code_object(so_path, start=0):
+    """the gfx950 ELF inside the library's clang offload bundle (the first one at or after `start`)"""
     data = open(so_path, "rb").read()
-    i = data.find(b"__CLANG_OFFLOAD_BUNDLE__")
+    i = data.find(MAGIC, start)
     if i < 0:
         raise RuntimeError(f"{so_path}: no offload bundle")
     n = struct.unpack_from("<Q", data, i + 24)[0]
@@ -52,9 +64,24 @@ def waves_per_simd(vgprs, agprs=0):
     return min(8, 512 // total)
 
 
-def extract(so_path=LIB):
+def extract_bundles(so_path=LIB):
+    """the kernel table (as extract) of every offload bundle in the file: each translation unit with kernels has its own"""
+    data, tables, i = open(so_path, "rb").read(), [], -1
+    while (i := data.find(MAGIC, i + 1)) >= 0:
+        tables.append(extract(so_path, i))
+    return tables
+
+
+def bundle_with(word, so_path=LIB):
+    """the table of the ONE bundle that holds kernels named *word*"""
+    found = [b for b in extract_bundles(so_path) if any(word in k for k in b)]
+    assert len(found) == 1, [sorted(b) for b in found]
+    return found[0]
+
+
+def extract(so_path=LIB, start=0):
     with tempfile.NamedTemporaryFile(suffix=".elf") as f:
-        f.write(code_object(so_path))
+        f.write(code_object(so_path, start))
         f.flush()
         notes = subprocess.run([READELF, "--notes", f.name], check=True, capture_output=True, text=True).stdout
     kernels = {}

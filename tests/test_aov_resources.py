@@ -1,11 +1,9 @@
 """Resource budget of the AOV kernel (csrc/rt_aov.hip): no scratch, no spilled registers, at least four waves per SIMD by
 registers.  The kernel is its own translation unit, so its code object is a second offload bundle in librt_hip.so, after the
-render kernels' bundle that profiles/resource_table.json describes.  tests/probes/resource_table.py reads the first bundle of a
-file; each bundle is handed to it here as a file that starts at that bundle."""
+render kernels' bundle that profiles/resource_table.json describes.  tests/probes/resource_table.py finds the bundle
+(bundle_with)."""
 import importlib.util
 import os
-import subprocess
-import tempfile
 
 import pytest
 
@@ -13,27 +11,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 spec = importlib.util.spec_from_file_location("resource_table", os.path.join(ROOT, "tests", "probes", "resource_table.py"))
 rtab = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(rtab)
-MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
 @pytest.fixture(scope="module")
 def aov_kernels():
     if not os.path.exists(rtab.READELF):
         pytest.skip("llvm-readelf not available")
-    csrc = os.path.join(ROOT, "raytracing-rust_amd", "csrc")
-    srcs = [os.path.join(csrc, n) for n in os.listdir(csrc) if n.endswith((".hip", ".h", ".cpp")) or n == "Makefile"]
-    if not os.path.exists(rtab.LIB) or os.path.getmtime(rtab.LIB) < max(os.path.getmtime(p) for p in srcs):
-        subprocess.run(["make", "-C", csrc, "-s", "../librt_hip.so"], check=True)
-    data = open(rtab.LIB, "rb").read()
-    found = {}
-    i = data.find(MAGIC)
-    while i >= 0:
-        with tempfile.NamedTemporaryFile(suffix=".bundle") as f:
-            f.write(data[i:])
-            f.flush()
-            found.update({k: v for k, v in rtab.extract(f.name).items() if "aov_kernel" in k})
-        i = data.find(MAGIC, i + len(MAGIC))
-    return found
+    rtab.rebuild_if_stale()
+    return {k: v for k, v in rtab.bundle_with("aov_kernel").items() if "aov_kernel" in k}
 
 
 def test_aov_kernel_resources(aov_kernels):

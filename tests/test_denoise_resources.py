@@ -1,11 +1,9 @@
 """Resource budget of the denoiser kernels (csrc/rt_denoise.hip): no scratch, no spilled registers, at least eight waves per SIMD
 by registers.  The kernels are their own translation unit, so their code object is an offload bundle of its own in librt_hip.so
-(as the AOV kernel's, tests/test_aov_resources.py).  tests/probes/resource_table.py reads the first bundle of a file; each bundle
-is handed to it here as a file that starts at that bundle."""
+(as the AOV kernel's, tests/test_aov_resources.py).  tests/probes/resource_table.py finds the bundle
+(bundle_with)."""
 import importlib.util
 import os
-import subprocess
-import tempfile
 
 import pytest
 
@@ -13,7 +11,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 spec = importlib.util.spec_from_file_location("resource_table", os.path.join(ROOT, "tests", "probes", "resource_table.py"))
 rtab = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(rtab)
-MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 KERNELS = {"void rt::denoise_prepass_kernel<0>", "void rt::denoise_prepass_kernel<1>", "void rt::denoise_prepass_kernel<2>",
            "rt::denoise_variance_kernel", "void rt::denoise_iteration_kernel<false>", "void rt::denoise_iteration_kernel<true>"}
 
@@ -23,22 +20,8 @@ def denoise_bundle():
     """every kernel of the bundle that holds the denoiser's kernels"""
     if not os.path.exists(rtab.READELF):
         pytest.skip("llvm-readelf not available")
-    csrc = os.path.join(ROOT, "raytracing-rust_amd", "csrc")
-    srcs = [os.path.join(csrc, n) for n in os.listdir(csrc) if n.endswith((".hip", ".h", ".cpp")) or n == "Makefile"]
-    if not os.path.exists(rtab.LIB) or os.path.getmtime(rtab.LIB) < max(os.path.getmtime(p) for p in srcs):
-        subprocess.run(["make", "-C", csrc, "-s", "../librt_hip.so"], check=True)
-    data = open(rtab.LIB, "rb").read()
-    bundles = []
-    i = data.find(MAGIC)
-    while i >= 0:
-        with tempfile.NamedTemporaryFile(suffix=".bundle") as f:
-            f.write(data[i:])
-            f.flush()
-            bundles.append(rtab.extract(f.name))
-        i = data.find(MAGIC, i + len(MAGIC))
-    found = [b for b in bundles if any("denoise_" in k for k in b)]
-    assert len(found) == 1, [sorted(b) for b in found]
-    return found[0]
+    rtab.rebuild_if_stale()
+    return rtab.bundle_with("denoise_")
 
 
 def test_denoise_kernel_resources(denoise_bundle):

@@ -5,7 +5,6 @@ rebuild, look at the difference (`python tests/probes/resource_table.py --diff`)
 import importlib.util
 import json
 import os
-import subprocess
 
 import pytest
 
@@ -19,11 +18,7 @@ spec.loader.exec_module(rtab)
 def built_table():
     if not os.path.exists(rtab.READELF):
         pytest.skip("llvm-readelf not available")
-    csrc = os.path.join(ROOT, "raytracing-rust_amd", "csrc")
-    srcs = [os.path.join(csrc, n) for n in os.listdir(csrc) if n.endswith((".hip", ".h", ".cpp")) or n == "Makefile"]
-    srcs.append(os.path.join(ROOT, "include", "rt_detmath.h"))
-    if not os.path.exists(rtab.LIB) or os.path.getmtime(rtab.LIB) < max(os.path.getmtime(p) for p in srcs):
-        subprocess.run(["make", "-C", csrc, "-s", "../librt_hip.so"], check=True)  # the table must describe THESE sources
+    rtab.rebuild_if_stale()  # the table must describe THESE sources
     return rtab.extract(rtab.LIB)
 
 
