@@ -715,6 +715,84 @@ int rt_display(rt_scene *scene, const float *host_rgb, const rt_display_opts *op
                uint32_t *host_histogram);
 int rt_display_reset(rt_scene *scene);
 
+/* ---- AOV-guided upscaling (csrc/rt_upscale.hip): render and filter at a reduced resolution, reconstruct the full-resolution frame
+ * from it -- joint bilateral upsampling (Kopf et al., SIGGRAPH 2007) of albedo-demodulated radiance, guided by the first-hit albedo,
+ * normal and depth at BOTH sizes (the camera does not depend on the resolution: rt_render_aov at the destination size gives the
+ * destination guides).  Texture detail and geometric edges come from the full-resolution guides; only the smooth demodulated
+ * irradiance is interpolated.  Source frame w x h, destination frame W x H (W >= w, H >= h, all >= 2), both FRAME layout, row-major,
+ * y down, f32 with the library's arithmetic contract: IEEE `/` and sqrtf, no fma, sums left to right; powf is include/rt_detmath.h's
+ * rt_powf, and neither expf nor the device's powf appears anywhere in this stage; dot as the temporal stage writes it; fminf / fmaxf return the other
+ * operand for a NaN.
+ * A guide is USED when it is given at both sizes; given at one size only is an error.  No guide at all is plain bilinear
+ * interpolation (with the fallbacks below for invalid source pixels).
+ * Per source pixel q: d_s(q) = fmaxf(a_s(q), 1e-3f) per channel (albedo used) else 1;  e(q) = c(q) / d_s(q);  n^_s(q) = n / |n|, 0 where
+ *   |n| = 0 (normals used);  q is INVALID if a component of c(q), or lum(e(q)), is not finite (lum, n^ as rt_denoise).  An invalid q
+ *   is a tap of weight 0 whose e(q) counts as 0: it never contributes.
+ * Per destination pixel p = (x, y), n^(p) and z(p) from the destination guides:
+ *   Position in the source frame, by the render's pixel-to-ray mapping u = (x + jitter) / (W - 1) at the jitter's centre:
+ *     X' = (((float)x + 0.5f) / (float)(W - 1)) * (float)(w - 1),  fx = X' - 0.5f,  i0 = floorf(fx),  ax = fx - i0,  bx = 1.0f - ax;
+ *     Y', fy, j0, ay, by likewise from y, H, h.  The source pixel of tap (i, j) is (fminf(fmaxf(i, 0), w - 1), fminf(fmaxf(j, 0), h - 1)):
+ *     taps off the frame are clamped onto its border, not skipped, in every stage.  (W = w is NOT an identity: X' is x + 0.5 only up
+ *     to rounding, so i0 may be x - 1 with ax one ulp below 1.)
+ *   Guide weight of a valid tap q:  g = w_n * w_z;  of an invalid one: 0.
+ *     w_n = 1 without normals or where n^(p) or n^_s(q) is 0 (all three components == 0); else
+ *           powf(fmaxf(0.0f, dot(n^(p), n^_s(q))), sigma_normal)
+ *     w_z = 1 without depth or where z(p) == 0 and z_s(q) == 0 (both sky); 0 where exactly one is 0; else with
+ *           t = fabsf(z(p) - z_s(q)) / (depth_tolerance * z(p)):  (1.0f - t) * (1.0f - t) if t < 1.0f, else 0 (a NaN compares false: 0)
+ *   Stage 1, the four bilinear taps in the temporal stage's order, (i0, j0) b = bx*by; (i0 + 1, j0) b = ax*by; (i0, j0 + 1) b = bx*ay;
+ *     (i0 + 1, j0 + 1) b = ax*ay:  sw = sw + b*g,  se = se + (b*g)*e(q) per channel, both from +0.
+ *     If sw >= 1.0f/16:  e^ = se / sw, stage = 1.
+ *   Stage 2 otherwise, the 4 x 4 taps j = j0 - 1 .. j0 + 2 (outer), i = i0 - 1 .. i0 + 2 (inner), i and j computed in float:
+ *     wt = (g * k(i - fx)) * k(j - fy) with the UNCLAMPED i, j and k(d) = fmaxf(0.0f, 1.0f - fabsf(d) * 0.4f);
+ *     sw = sw + wt, se = se + wt*e(q), both from +0 again.  If sw >= 1.0f/1024:  e^ = se / sw, stage = 2.
+ *   Stage 3 otherwise: e^ = e(q) of the VALID stage-1 tap with the largest b (the first in tap order on a tie; the guides are not
+ *     consulted), stage = 3.  No valid stage-1 tap: e^ = 0, stage = 0.
+ *   out(p) = e^ * d_d(p) per channel, d_d(p) = fmaxf(a_d(p), 1e-3f) (albedo used) else 1.
+ * The stage map (optional, one byte per destination pixel) receives the stage number: where it is not 1 the reconstruction had
+ * little (2), next to nothing (3) or nothing (0) to go on -- silhouettes, and objects thinner than a source pixel.
+ * Options: sigma_normal and depth_tolerance finite and > 0; `reserved` is zeroed by the default call.  Quality and cost are
+ * measured in DESIGN.md section 13. */
+typedef struct rt_upscale_opts {
+	uint32_t src_width, src_height; /* w, h >= 2 */
+	uint32_t dst_width, dst_height; /* W >= w, H >= h */
+	float sigma_normal;             /* default 32 */
+	float depth_tolerance;          /* default 0.1 (relative) */
+	uint32_t reserved[8];
+} rt_upscale_opts;
+/* color: w*h*3, required: a source-size frame (what rt_render, rt_denoise* write).  src_albedo / src_normal / src_depth: w*h*3, w*h*3,
+ * w*h, the rt_render_aov channels at the source size; dst_albedo / dst_normal / dst_depth: W*H*3, W*H*3, W*H, the same channels at the
+ * destination size.  Each guide: both pointers or neither. */
+typedef struct rt_upscale_inputs {
+	const float *color;
+	const float *src_albedo, *src_normal, *src_depth;
+	const float *dst_albedo, *dst_normal, *dst_depth;
+} rt_upscale_inputs;
+int rt_upscale_opts_default(rt_upscale_opts *out);
+/* Checks (the device last): RT_ERR_INVALID_ARGUMENT for a NULL scene, inputs, opts, color or out, a side of either frame below 2, a
+ * guide given at one size only, an option out of range, and an output or stage map that overlaps any other buffer (the inputs may
+ * share memory with one another); RT_ERR_UNSUPPORTED for W < w or H < h (this is not a downscaler) and for more than 2^31
+ * destination pixels; RT_ERR_NO_DEVICE for a host-only scene.  A multi-device head runs on devices[0].  No side effects: what
+ * rt_last_kernel_ms, rt_last_launch_info and a following rt_render return is unchanged.
+ * rt_upscale_device: DEVICE buffers on the scene's GPU, asynchronous on hip_stream; one kernel; it allocates nothing, keeps no state
+ *   and needs no workspace, so it can be captured into a graph from its first call.  Any alignment of the buffers is accepted.
+ *   d_out: W*H*3 floats; d_stage: W*H bytes or NULL.
+ * rt_upscale: HOST buffers, blocking; its device copies live on the scene (shared with rt_denoise; grown for larger frames only). */
+int rt_upscale_device(rt_scene *scene, const rt_upscale_inputs *device_in, const rt_upscale_opts *opts, float *d_out, uint8_t *d_stage,
+                      void *hip_stream);
+int rt_upscale(rt_scene *scene, const rt_upscale_inputs *host_in, const rt_upscale_opts *opts, float *host_out, uint8_t *host_stage);
+/* Render small, show large, in one blocking call with host buffers: the sibling of rt_render_denoised, built from the same pieces.
+ * opts->width and opts->height are the DESTINATION size W x H; src_width x src_height is the size that is traced.  At w x h exactly
+ * what rt_render_denoised does with opts at that size (two half renders, AOVs, variance, filter with dopts, whose sizes are ignored);
+ * the albedo / normal / depth AOVs at W x H over the same pass window [sample_begin, sample_begin + samples_per_pixel); then the
+ * stage above with all three guides and uopts (whose sizes are ignored).  out: W*H*3; out_src (unless NULL): the filtered w x h
+ * frame, w*h*3; *rays_shot (unless NULL): the two half renders' counts (the AOV passes are not counted, as in rt_render_denoised).
+ * The passes at the two sizes use DIFFERENT random streams -- a stream is keyed by y*width + x -- so the destination guides are not
+ * the source guides resampled; that is intended.  Option rules as rt_render_denoised (samples_per_pixel even and >= 2, FRAME layout,
+ * shard_count 1) and as rt_upscale_device; out must not overlap out_src.  rt_last_kernel_ms and rt_last_launch_info afterwards
+ * describe the render of the second half. */
+int rt_render_upscaled(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, uint32_t src_width, uint32_t src_height,
+                       const rt_denoise_opts *dopts, const rt_upscale_opts *uopts, float *out, float *out_src, uint64_t *rays_shot);
+
 /* Division by a constant a launch knows beforehand (image size - 1, sky table resolution, pi, 2 pi): the kernels replace `x / c` by
  * two fma steps on rc = RN(1 / c) where -- and only where -- the host has verified, by enumerating all 2^23 significands of x, that
  * this returns the bits of the division (csrc/rt_build.cpp verified_reciprocal, csrc/rt_lean.h div_by_verified).  This call runs that

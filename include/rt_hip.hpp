@@ -501,6 +501,80 @@ class Display {
 	rt_display_opts opts_;
 };
 
+// AOV-guided upscaling (rt_hip.h rt_upscale_opts): the options a caller sets; defaults as rt_upscale_opts_default.
+struct UpscaleOptions {
+	float sigma_normal = 32.0f, depth_tolerance = 0.1f;
+};
+inline rt_upscale_opts upscale_opts(const UpscaleOptions &u, uint32_t src_width, uint32_t src_height, uint32_t dst_width,
+                                    uint32_t dst_height)
+{
+	rt_upscale_opts o;
+	check(rt_upscale_opts_default(&o));
+	o.src_width = src_width;
+	o.src_height = src_height;
+	o.dst_width = dst_width;
+	o.dst_height = dst_height;
+	o.sigma_normal = u.sigma_normal;
+	o.depth_tolerance = u.depth_tolerance;
+	return o;
+}
+// A src_width*src_height*3 frame to dst_width*dst_height*3, guided by the albedo, normal and depth of `src` and `dst` (render_aov at
+// the two sizes; nullptr, or a channel empty in either, = that guide not used).  *stage (unless nullptr) receives the stage map.
+inline std::vector<float> upscale(const Bvh &bvh, const std::vector<float> &color, const AovBuffers *src, const AovBuffers *dst,
+                                  uint32_t src_width, uint32_t src_height, uint32_t dst_width, uint32_t dst_height,
+                                  const UpscaleOptions &u = UpscaleOptions(), std::vector<uint8_t> *stage = nullptr)
+{
+	rt_upscale_inputs in = {color.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+	if (src && dst) {
+		if (!src->albedo.empty() && !dst->albedo.empty()) {
+			in.src_albedo = src->albedo.data();
+			in.dst_albedo = dst->albedo.data();
+		}
+		if (!src->normal.empty() && !dst->normal.empty()) {
+			in.src_normal = src->normal.data();
+			in.dst_normal = dst->normal.data();
+		}
+		if (!src->depth.empty() && !dst->depth.empty()) {
+			in.src_depth = src->depth.data();
+			in.dst_depth = dst->depth.data();
+		}
+	}
+	const rt_upscale_opts o = upscale_opts(u, src_width, src_height, dst_width, dst_height);
+	const size_t n = (size_t)dst_width * dst_height;
+	std::vector<float> out(n * 3);
+	if (stage)
+		stage->resize(n);
+	check(rt_upscale(bvh.raw(), &in, &o, out.data(), stage ? stage->data() : nullptr));
+	return out;
+}
+// Render at src_width x src_height, filter there, reconstruct o.width x o.height (rt_render_upscaled; o.samples_per_pixel even, >= 2).
+struct Upscaled {
+	std::vector<float> image;  // o.width*o.height*3
+	std::vector<float> source; // src_width*src_height*3: the filtered frame that was upscaled
+	uint64_t rays_shot = 0;
+};
+inline Upscaled render_upscaled(const RenderOptions &o, uint32_t src_width, uint32_t src_height, const SimpleCamera &camera,
+                                const Bvh &bvh, const DenoiseOptions &d = DenoiseOptions(), const UpscaleOptions &u = UpscaleOptions(),
+                                uint64_t seed = 1, uint64_t sample_begin = 0)
+{
+	rt_render_opts opts;
+	rt_render_opts_default(&opts);
+	opts.width = o.width;
+	opts.height = o.height;
+	opts.samples_per_pixel = o.samples_per_pixel;
+	opts.render_method = static_cast<int32_t>(o.render_method);
+	opts.sample_begin = sample_begin;
+	opts.seed = seed;
+	const rt_denoise_opts dopts = denoise_opts(d, 0, 0); // (the frame sizes come from opts and the two arguments)
+	const rt_upscale_opts uopts = upscale_opts(u, 0, 0, 0, 0);
+	Upscaled r;
+	r.image.resize((size_t)o.width * o.height * 3);
+	r.source.resize((size_t)src_width * src_height * 3);
+	check(rt_render_upscaled(bvh.raw(), &camera.raw(), &opts, src_width, src_height, &dopts, &uopts, r.image.data(), r.source.data(),
+	                         &r.rays_shot));
+	return r;
+}
+
 struct Presentation { // what render_tui keeps: the mean image and the ray total (src/main.rs:160-173)
 	SamplerProgress sampler_progress;
 	Presentation(uint64_t pixel_num) : sampler_progress(pixel_num, 3) {}

@@ -305,6 +305,27 @@ class DisplayState(C.Structure):  # rt_display_state
     ]
 
 
+class UpscaleOpts(C.Structure):  # rt_upscale_opts
+    _fields_ = [
+        ("src_width", C.c_uint32),
+        ("src_height", C.c_uint32),
+        ("dst_width", C.c_uint32),
+        ("dst_height", C.c_uint32),
+        ("sigma_normal", C.c_float),
+        ("depth_tolerance", C.c_float),
+        ("reserved", C.c_uint32 * 8),
+    ]
+
+
+UPSCALE_INPUTS = ("color", "src_albedo", "src_normal", "src_depth", "dst_albedo", "dst_normal", "dst_depth")
+UPSCALE_GUIDES = ("albedo", "normal", "depth")
+UPSCALE_OPTIONS = ("sigma_normal", "depth_tolerance")
+
+
+class UpscaleInputs(C.Structure):  # rt_upscale_inputs
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in UPSCALE_INPUTS]
+
+
 DISPLAY_OPTIONS = tuple(n for n, _ in DisplayOpts._fields_ if n not in ("width", "height", "reserved"))
 
 # rt_presentation_update: int (*)(void *data, const rt_sampler_progress *, uint64_t samples_done)
@@ -332,6 +353,8 @@ EXPECTED_SIZES = {
     "rt_temporal_inputs": (TemporalInputs, 32),
     "rt_display_opts": (DisplayOpts, 104),
     "rt_display_state": (DisplayState, 16),
+    "rt_upscale_opts": (UpscaleOpts, 56),
+    "rt_upscale_inputs": (UpscaleInputs, 56),
 }
 
 # every symbol include/rt_hip.h declares
@@ -393,6 +416,10 @@ EXPORTED_SYMBOLS = [
     "rt_display_device",
     "rt_display",
     "rt_display_reset",
+    "rt_upscale_opts_default",
+    "rt_upscale_device",
+    "rt_upscale",
+    "rt_render_upscaled",
 ]
 
 

@@ -190,8 +190,8 @@ struct Staging {
 	int rc = RT_OK;
 	hipError_t e = hipSuccess;
 	int n = 0;
-	const void *host[6];
-	size_t offset[6], count[6];
+	const void *host[8];
+	size_t offset[8], count[8];
 
 	bool ok() const { return rc == RT_OK && e == hipSuccess; }
 	void add(const void *h, size_t elements)

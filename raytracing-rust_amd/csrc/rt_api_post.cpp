@@ -1,6 +1,6 @@
 // rt_api_post.cpp -- the host side of the post-processing stages of librt_hip.so (include/rt_hip.h): first-hit AOV buffers,
-// the A-Trous denoiser, temporal accumulation and the display stage.  Each stage has its kernels in a file of its own
-// (rt_aov.hip, rt_denoise.hip, rt_temporal.hip, rt_display.hip); here are their argument checks, their _device entry points
+// the A-Trous denoiser, temporal accumulation, the display stage and AOV-guided upscaling.  Each stage has its kernels in a file of
+// its own (rt_aov.hip, rt_denoise.hip, rt_temporal.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
 // and the blocking wrappers that stage host buffers through scene-owned device memory (Staging, rt_api_internal.h).
 // Every check function ends with the device (need_device), so that a host-only scene reports bad arguments as such.
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 #include "rt_denoise.h"
 #include "rt_temporal.h"
 #include "rt_display.h"
+#include "rt_upscale.h"
 
 using namespace rt;
 
@@ -197,6 +198,74 @@ static DevDenoiseParams denoise_params(const rt_denoise_opts *o, uint64_t w, uin
 	return P;
 }
 
+// what rt_render_denoised and rt_render_upscaled ask of their render options, for a render of w x h
+static int render_denoised_opts_check(const char *who, const rt_render_opts *o, const rt_denoise_opts *dopts, uint64_t w, uint64_t h)
+{
+	int rc = denoise_opts_check(dopts, w, h);
+	if (rc != RT_OK)
+		return rc;
+	rc = frame_sides("", w, h, 2);
+	if (rc != RT_OK)
+		return rc;
+	if (o->samples_per_pixel < 2 || o->samples_per_pixel % 2 != 0 || o->samples_per_pixel >= (1ull << 32))
+		return fail(RT_ERR_INVALID_ARGUMENT, std::string(who) + ": samples_per_pixel must be even, >= 2 and < 2^32");
+	if (o->render_method != RT_METHOD_NAIVE && o->render_method != RT_METHOD_MIS)
+		return fail(RT_ERR_INVALID_ARGUMENT, "unknown render method");
+	if (o->output_layout != RT_LAYOUT_FRAME)
+		return fail(RT_ERR_UNSUPPORTED, std::string(who) + ": RT_LAYOUT_FRAME only");
+	if (o->shard_count != 1)
+		return fail(RT_ERR_UNSUPPORTED, std::string(who) + ": the whole frame only (shard_count 1)");
+	return RT_OK;
+}
+
+// The device side of rt_render_denoised in the scene's buffer at `base`: two ray counters (16 bytes), the workspace, then the
+// frames A, B, albedo, normal, depth, noisy, clean of o's size.
+struct DenoisedFrames {
+	unsigned long long *d_rays;
+	float *d_albedo, *d_normal, *d_depth, *d_noisy, *d_clean;
+};
+static size_t denoised_frames_bytes(size_t n) { return 16 + 4 * (kDenoiseWorkspaceBytesPerPixel / 4 * n + 19 * n); }
+
+// two half renders, the AOVs of all passes, the variance and the filter on s->stream; the status goes to `st`
+static DenoisedFrames enqueue_render_denoised(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_denoise_opts *dopts,
+                                              char *base, Staging &st)
+{
+	const size_t n = (size_t)(o->width * o->height);
+	const size_t ws_floats = kDenoiseWorkspaceBytesPerPixel / 4 * n;
+	unsigned long long *d_rays = reinterpret_cast<unsigned long long *>(base);
+	float *ws = reinterpret_cast<float *>(base + 16);
+	float *d_a = ws + ws_floats, *d_b = d_a + 3 * n, *d_albedo = d_b + 3 * n, *d_normal = d_albedo + 3 * n,
+	      *d_depth = d_normal + 3 * n, *d_noisy = d_depth + n, *d_clean = d_noisy + 3 * n;
+	const uint64_t half = o->samples_per_pixel / 2;
+	rt_render_opts oh = *o;
+	oh.samples_per_pixel = half;
+	if (st.ok())
+		st.rc = rt_render_device(s, camera, &oh, d_a, reinterpret_cast<uint64_t *>(d_rays), s->stream);
+	if (st.ok()) {
+		oh.sample_begin = o->sample_begin + half;
+		st.rc = rt_render_device(s, camera, &oh, d_b, reinterpret_cast<uint64_t *>(d_rays + 1), s->stream);
+	}
+	if (st.ok())
+		st.e = hipSetDevice(s->device);
+	if (st.ok()) {
+		rt_aov_buffers aov;
+		std::memset(&aov, 0, sizeof aov);
+		aov.albedo = d_albedo;
+		aov.normal = d_normal;
+		aov.depth = d_depth;
+		st.rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
+	}
+	if (st.ok()) {
+		const rt_denoise_inputs in = {d_noisy, d_albedo, d_normal, d_depth, nullptr};
+		DevDenoiseParams P = denoise_params(dopts, o->width, o->height, in, ws, d_clean);
+		P.half_a = d_a;
+		P.half_b = d_b;
+		P.noisy = d_noisy;
+		st.e = launch_denoise(s->stream, P);
+	}
+	return DenoisedFrames{d_rays, d_albedo, d_normal, d_depth, d_noisy, d_clean};
+}
+
 extern "C" {
 
 int rt_denoise_opts_default(rt_denoise_opts *out)
@@ -266,20 +335,9 @@ int rt_render_denoised(rt_scene *s, const rt_camera *camera, const rt_render_opt
 {
 	if (!s || !camera || !o || !dopts || !out_clean)
 		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	int rc = denoise_opts_check(dopts, o->width, o->height);
+	int rc = render_denoised_opts_check("rt_render_denoised", o, dopts, o->width, o->height);
 	if (rc != RT_OK)
 		return rc;
-	rc = frame_sides("", o->width, o->height, 2);
-	if (rc != RT_OK)
-		return rc;
-	if (o->samples_per_pixel < 2 || o->samples_per_pixel % 2 != 0 || o->samples_per_pixel >= (1ull << 32))
-		return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_denoised: samples_per_pixel must be even, >= 2 and < 2^32");
-	if (o->render_method != RT_METHOD_NAIVE && o->render_method != RT_METHOD_MIS)
-		return fail(RT_ERR_INVALID_ARGUMENT, "unknown render method");
-	if (o->output_layout != RT_LAYOUT_FRAME)
-		return fail(RT_ERR_UNSUPPORTED, "rt_render_denoised: RT_LAYOUT_FRAME only");
-	if (o->shard_count != 1)
-		return fail(RT_ERR_UNSUPPORTED, "rt_render_denoised: the whole frame only (shard_count 1)");
 	const size_t n = (size_t)(o->width * o->height);
 	if (ranges_overlap(out_clean, 12 * n, out_noisy, 12 * n))
 		return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_denoised: out_clean overlaps out_noisy");
@@ -287,46 +345,15 @@ int rt_render_denoised(rt_scene *s, const rt_camera *camera, const rt_render_opt
 	if (rc != RT_OK)
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
-	// two ray counters (16 bytes), the workspace, then the frames: A, B, albedo, normal, depth, noisy, clean
-	const size_t ws_floats = kDenoiseWorkspaceBytesPerPixel / 4 * n;
-	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, 16 + 4 * (ws_floats + 19 * n));
+	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, denoised_frames_bytes(n));
 	if (rc != RT_OK)
 		return rc;
-	unsigned long long *d_rays = reinterpret_cast<unsigned long long *>(s->d_denoise);
-	float *ws = reinterpret_cast<float *>(s->d_denoise + 16);
-	float *d_a = ws + ws_floats, *d_b = d_a + 3 * n, *d_albedo = d_b + 3 * n, *d_normal = d_albedo + 3 * n,
-	      *d_depth = d_normal + 3 * n, *d_noisy = d_depth + n, *d_clean = d_noisy + 3 * n;
-	const uint64_t half = o->samples_per_pixel / 2;
-	rt_render_opts oh = *o;
-	oh.samples_per_pixel = half;
 	Staging st{s};
-	st.rc = rt_render_device(s, camera, &oh, d_a, reinterpret_cast<uint64_t *>(d_rays), s->stream);
-	if (st.ok()) {
-		oh.sample_begin = o->sample_begin + half;
-		st.rc = rt_render_device(s, camera, &oh, d_b, reinterpret_cast<uint64_t *>(d_rays + 1), s->stream);
-	}
-	if (st.ok())
-		st.e = hipSetDevice(s->device);
-	if (st.ok()) {
-		rt_aov_buffers aov;
-		std::memset(&aov, 0, sizeof aov);
-		aov.albedo = d_albedo;
-		aov.normal = d_normal;
-		aov.depth = d_depth;
-		st.rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
-	}
-	if (st.ok()) {
-		const rt_denoise_inputs in = {d_noisy, d_albedo, d_normal, d_depth, nullptr};
-		DevDenoiseParams P = denoise_params(dopts, o->width, o->height, in, ws, d_clean);
-		P.half_a = d_a;
-		P.half_b = d_b;
-		P.noisy = d_noisy;
-		st.e = launch_denoise(s->stream, P);
-	}
+	const DenoisedFrames F = enqueue_render_denoised(s, camera, o, dopts, s->d_denoise, st);
 	unsigned long long rays[2] = {0, 0};
-	st.download(out_clean, d_clean, 3 * n * 4);
-	st.download(out_noisy, d_noisy, 3 * n * 4);
-	st.download(rays, d_rays, sizeof rays);
+	st.download(out_clean, F.d_clean, 3 * n * 4);
+	st.download(out_noisy, F.d_noisy, 3 * n * 4);
+	st.download(rays, F.d_rays, sizeof rays);
 	rc = st.finish("render_denoised");
 	if (rc == RT_OK && rays_shot)
 		*rays_shot = rays[0] + rays[1];
@@ -714,6 +741,174 @@ int rt_display_reset(rt_scene *s)
 		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
 	s->display_has_state = false;
 	return RT_OK;
+}
+
+} // extern "C"
+
+// ---- AOV-guided upscaling (rt_upscale.hip) ----
+// the two frame sizes and the options; sizes are passed separately (rt_render_upscaled takes them from the render)
+static int upscale_opts_check(const rt_upscale_opts *o, uint64_t w, uint64_t h, uint64_t W, uint64_t H)
+{
+	int rc = frame_sides("upscale: source ", w, h, 2);
+	if (rc == RT_OK)
+		rc = frame_sides("upscale: destination ", W, H, 2);
+	if (rc != RT_OK)
+		return rc;
+	if (!std::isfinite(o->sigma_normal) || !(o->sigma_normal > 0.0f) || !std::isfinite(o->depth_tolerance) || !(o->depth_tolerance > 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "upscale: sigma_normal and depth_tolerance must be finite and > 0");
+	if (W < w || H < h)
+		return fail(RT_ERR_UNSUPPORTED, "upscale: the destination is smaller than the source (this is not a downscaler)");
+	uint64_t n = 0;
+	return frame_pixels("upscale: ", W, H, 2, &n);
+}
+
+// argument checks of rt_upscale(_device), the device last
+static int upscale_check(const rt_scene *s, const rt_upscale_inputs *in, const rt_upscale_opts *o, const float *out, const uint8_t *stage)
+{
+	if (!s || !in || !o)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (!in->color || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "upscale: color and out must not be NULL");
+	if (!in->src_albedo != !in->dst_albedo || !in->src_normal != !in->dst_normal || !in->src_depth != !in->dst_depth)
+		return fail(RT_ERR_INVALID_ARGUMENT, "upscale: a guide must be given at both sizes or at neither");
+	int rc = upscale_opts_check(o, o->src_width, o->src_height, o->dst_width, o->dst_height);
+	if (rc != RT_OK)
+		return rc;
+	const uint64_t n = (uint64_t)o->src_width * o->src_height, N = (uint64_t)o->dst_width * o->dst_height;
+	// the two buffers written against every other buffer (the inputs may share memory with one another)
+	const void *buf[9] = {out, stage, in->color, in->src_albedo, in->src_normal, in->src_depth, in->dst_albedo, in->dst_normal, in->dst_depth};
+	const uint64_t bytes[9] = {12 * N, N, 12 * n, 12 * n, 12 * n, 4 * n, 12 * N, 12 * N, 4 * N};
+	rc = check_disjoint("upscale: out or the stage map overlaps another buffer", buf, bytes, 2, 9);
+	return rc == RT_OK ? need_device(s) : rc;
+}
+
+static DevUpscaleParams upscale_params(const rt_upscale_opts *o, uint64_t w, uint64_t h, uint64_t W, uint64_t H, const rt_upscale_inputs &in,
+                                       float *out, uint8_t *stage)
+{
+	DevUpscaleParams P;
+	std::memset(&P, 0, sizeof P);
+	P.w = (uint32_t)w;
+	P.h = (uint32_t)h;
+	P.W = (uint32_t)W;
+	P.H = (uint32_t)H;
+	P.sigma_n = o->sigma_normal;
+	P.depth_tol = o->depth_tolerance;
+	P.color = in.color;
+	P.src_albedo = in.src_albedo;
+	P.src_normal = in.src_normal;
+	P.src_depth = in.src_depth;
+	P.dst_albedo = in.dst_albedo;
+	P.dst_normal = in.dst_normal;
+	P.dst_depth = in.dst_depth;
+	P.out = out;
+	P.stage = stage;
+	return P;
+}
+
+extern "C" {
+
+int rt_upscale_opts_default(rt_upscale_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	out->sigma_normal = 32.0f;
+	out->depth_tolerance = 0.1f;
+	return RT_OK;
+}
+
+int rt_upscale_device(rt_scene *s, const rt_upscale_inputs *d_in, const rt_upscale_opts *o, float *d_out, uint8_t *d_stage, void *hip_stream)
+{
+	int rc = upscale_check(s, d_in, o, d_out, d_stage);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device)); // a multi-device head runs on devices[0]
+	HIP_TRY(launch_upscale(static_cast<hipStream_t>(hip_stream),
+	                       upscale_params(o, o->src_width, o->src_height, o->dst_width, o->dst_height, *d_in, d_out, d_stage)));
+	return RT_OK;
+}
+
+int rt_upscale(rt_scene *s, const rt_upscale_inputs *in, const rt_upscale_opts *o, float *out, uint8_t *stage)
+{
+	int rc = upscale_check(s, in, o, out, stage);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	const size_t n = (size_t)o->src_width * o->src_height, N = (size_t)o->dst_width * o->dst_height;
+	// out first, then the inputs given, in rt_upscale_inputs order, then the stage map (bytes)
+	Staging st{s, 3 * N};
+	st.add(in->color, 3 * n);
+	st.add(in->src_albedo, 3 * n);
+	st.add(in->src_normal, 3 * n);
+	st.add(in->src_depth, n);
+	st.add(in->dst_albedo, 3 * N);
+	st.add(in->dst_normal, 3 * N);
+	st.add(in->dst_depth, N);
+	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, st.total * 4 + N); // shared with rt_denoise / rt_render_denoised
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_denoise;
+	float *d_out = reinterpret_cast<float *>(base);
+	uint8_t *d_stage = reinterpret_cast<uint8_t *>(base + st.total * 4);
+	if (!st.upload(base))
+		return st.finish("upscale upload");
+	const rt_upscale_inputs d_in = {st.at(base, 0), st.at(base, 1), st.at(base, 2), st.at(base, 3), st.at(base, 4), st.at(base, 5), st.at(base, 6)};
+	st.rc = rt_upscale_device(s, &d_in, o, d_out, stage ? d_stage : nullptr, s->stream);
+	st.download(out, d_out, 3 * N * 4);
+	st.download(stage, d_stage, N);
+	return st.finish("upscale");
+}
+
+int rt_render_upscaled(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, uint32_t src_width, uint32_t src_height,
+                       const rt_denoise_opts *dopts, const rt_upscale_opts *uopts, float *out, float *out_src, uint64_t *rays_shot)
+{
+	if (!s || !camera || !o || !dopts || !uopts || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	const uint64_t w = src_width, h = src_height, W = o->width, H = o->height;
+	int rc = render_denoised_opts_check("rt_render_upscaled", o, dopts, w, h);
+	if (rc == RT_OK)
+		rc = upscale_opts_check(uopts, w, h, W, H);
+	if (rc != RT_OK)
+		return rc;
+	const size_t n = (size_t)(w * h), N = (size_t)(W * H);
+	if (ranges_overlap(out, 12 * N, out_src, 12 * n))
+		return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_upscaled: out overlaps out_src");
+	rc = need_device(s);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	// rt_render_denoised's frames at the source size (16-byte aligned end), then at the destination size: albedo, normal, depth, out
+	const size_t src_bytes = (denoised_frames_bytes(n) + 15) / 16 * 16;
+	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, src_bytes + 4 * 10 * N);
+	if (rc != RT_OK)
+		return rc;
+	float *d_albedo = reinterpret_cast<float *>(s->d_denoise + src_bytes), *d_normal = d_albedo + 3 * N, *d_depth = d_normal + 3 * N,
+	      *d_out = d_depth + N;
+	rt_render_opts os = *o;
+	os.width = w;
+	os.height = h;
+	Staging st{s};
+	const DenoisedFrames F = enqueue_render_denoised(s, camera, &os, dopts, s->d_denoise, st);
+	if (st.ok()) {
+		rt_aov_buffers aov;
+		std::memset(&aov, 0, sizeof aov);
+		aov.albedo = d_albedo;
+		aov.normal = d_normal;
+		aov.depth = d_depth;
+		st.rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
+	}
+	if (st.ok()) {
+		const rt_upscale_inputs in = {F.d_clean, F.d_albedo, F.d_normal, F.d_depth, d_albedo, d_normal, d_depth};
+		st.e = launch_upscale(s->stream, upscale_params(uopts, w, h, W, H, in, d_out, nullptr));
+	}
+	unsigned long long rays[2] = {0, 0};
+	st.download(out, d_out, 3 * N * 4);
+	st.download(out_src, F.d_clean, 3 * n * 4);
+	st.download(rays, F.d_rays, sizeof rays);
+	rc = st.finish("render_upscaled");
+	if (rc == RT_OK && rays_shot)
+		*rays_shot = rays[0] + rays[1];
+	return rc;
 }
 
 } // extern "C"

@@ -441,6 +441,68 @@ class HipScene:
                                        vp(d_workspace), vp(d_out), C.cast(vp(d_histogram), C.POINTER(C.c_uint32)),
                                        C.c_void_p(stream)))
 
+    # ---- AOV-guided upscaling (rt_upscale): a source-size frame to the destination size ----
+    def upscale(self, color, src=None, dst=None, stage=False, **opts):
+        """rt_upscale: an (h, w, 3) f32 frame to (H, W, 3), guided by the albedo / normal (.., 3) and depth of `src` (at h x w) and
+        `dst` (at H x W): dicts as render_aov returns them (other channels are ignored); a guide is used when both hold it, and
+        both must then hold it.  Without guides `dst` is the destination size (H, W): plain bilinear interpolation.
+        stage=True returns (out, the (H, W) uint8 stage map).  Keyword options: abi.UPSCALE_OPTIONS.  Semantics: include/rt_hip.h
+        rt_upscale_opts."""
+        src = src or {}
+        if isinstance(dst, dict):
+            shapes = [np.shape(dst[k])[:2] for k in abi.UPSCALE_GUIDES if dst.get(k) is not None]
+            if not shapes:
+                raise ValueError("upscale: dst holds no guide; pass the destination size (H, W) instead")
+            H, W = shapes[0]
+        elif dst is not None:
+            (H, W), dst = dst, {}
+        else:
+            raise ValueError("upscale needs dst: the destination guides, or the destination size (H, W)")
+        ins, keep = abi.UpscaleInputs(), []
+        h, w = _set_f32_inputs(ins, color, [("src_" + k, src.get(k), 3 if k != "depth" else 1) for k in abi.UPSCALE_GUIDES], keep)
+        for k in abi.UPSCALE_GUIDES:
+            a = dst.get(k)
+            if a is None:
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            shape = (H, W, 3) if k != "depth" else (H, W)
+            if a.shape != shape:
+                raise ValueError(f"dst {k} must be {shape}, got {a.shape}")
+            keep.append(a)
+            setattr(ins, "dst_" + k, _p(a, C.c_float))
+        o = upscale_opts(w, h, W, H, **opts)
+        out = np.zeros((H, W, 3), dtype=np.float32)
+        smap = np.zeros((H, W), dtype=np.uint8) if stage else None
+        _check(lib().rt_upscale(self._h, C.byref(ins), C.byref(o), _p(out, C.c_float), _p(smap, C.c_uint8) if stage else None))
+        return (out, smap) if stage else out
+
+    def upscale_device(self, d_ptrs, d_out, opts, d_stage=0, stream=0):
+        """rt_upscale_device: asynchronous, DEVICE buffers of the scene's GPU, no state, no workspace.  d_ptrs = {input: device
+        pointer} over abi.UPSCALE_INPUTS ("color" required; each guide at both sizes or not at all); d_out: W*H*3 f32; d_stage:
+        W*H bytes or 0; opts: abi.UpscaleOpts with both frame sizes set."""
+        ins = abi.UpscaleInputs()
+        for name, ptr in d_ptrs.items():
+            if name not in abi.UPSCALE_INPUTS:
+                raise ValueError(f"unknown upscale input {name!r}")
+            setattr(ins, name, _dp(ptr))
+        _check(lib().rt_upscale_device(self._h, C.byref(ins), C.byref(opts), _dp(d_out), _dp(d_stage, C.c_uint8), C.c_void_p(stream)))
+
+    def render_upscaled(self, camera, opts, src_width, src_height, dopts=None, uopts=None):
+        """rt_render_upscaled: trace and filter at src_width x src_height, reconstruct opts.width x opts.height.  Returns (out
+        (H, W, 3), out_src (h, w, 3): the filtered source frame, rays_shot).  dopts / uopts: abi.DenoiseOpts / abi.UpscaleOpts
+        (their sizes are ignored) or None for the defaults."""
+        H, W, h, w = int(opts.height), int(opts.width), int(src_height), int(src_width)
+        if dopts is None:
+            dopts = denoise_opts(w, h)
+        if uopts is None:
+            uopts = upscale_opts(w, h, W, H)
+        out = np.zeros((H, W, 3), dtype=np.float32)
+        out_src = np.zeros((h, w, 3), dtype=np.float32)
+        rays = C.c_uint64()
+        _check(lib().rt_render_upscaled(self._h, C.byref(camera), C.byref(opts), C.c_uint32(w), C.c_uint32(h), C.byref(dopts),
+                                        C.byref(uopts), _p(out, C.c_float), _p(out_src, C.c_float), C.byref(rays)))
+        return out, out_src, rays.value
+
     # ---- AccelerationStructure::check_hit / check_hit_index for batches ----
     def check_hit(self, origins, directions):
         rays = _pack_rays(origins, directions)
@@ -627,6 +689,18 @@ def display_output_bytes(opts):
     n = C.c_uint64()
     _check(lib().rt_display_output_bytes(C.byref(opts), C.byref(n)))
     return n.value
+
+
+def upscale_opts(src_width, src_height, dst_width, dst_height, **kw):
+    """rt_upscale_opts_default with the two frame sizes and any of abi.UPSCALE_OPTIONS set."""
+    o = abi.UpscaleOpts()
+    _check(lib().rt_upscale_opts_default(C.byref(o)))
+    o.src_width, o.src_height, o.dst_width, o.dst_height = int(src_width), int(src_height), int(dst_width), int(dst_height)
+    for k, v in kw.items():
+        if k not in abi.UPSCALE_OPTIONS:
+            raise ValueError(f"unknown upscale option {k!r}")
+        setattr(o, k, v)
+    return o
 
 
 def save_aov(prefix, aovs):
