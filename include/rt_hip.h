@@ -468,7 +468,7 @@ int rt_check_hit_index(rt_scene *scene, const rt_ray_desc *rays, const uint64_t 
  * order, from +0) / (float)hits, or 0 when no pass hit.
  * IDs come from pass sample_begin alone: primitive = index in rt_scene_desc.primitives (not BVH order), material = the caller's
  * material index; both UINT32_MAX on a miss.  A scene of >= 2^32 - 1 primitives returns RT_ERR_UNSUPPORTED when `primitive`
- * is asked for.  The first call on a scene that asks for `primitive` uploads the slot -> index table (synchronously).
+ * is asked for.  The slot -> index table is uploaded with the scene (4 bytes per primitive).
  * Options: render_method, max_depth, rr_threshold and sample_split are ignored; output_layout must be RT_LAYOUT_FRAME and
  * shard_count 1 (else RT_ERR_UNSUPPORTED); width and height >= 2.  The traversal follows the scene's mode (rt_scene_set_traversal;
  * every mode gives the same bytes).  A host-only scene returns RT_ERR_NO_DEVICE; a multi-device head (rt_scene_create_multi)
@@ -486,6 +486,59 @@ typedef struct rt_aov_buffers {
 int rt_render_aov(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_aov_buffers *host_out);
 int rt_render_aov_device(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_aov_buffers *device_out,
                          void *hip_stream);
+
+/* ---- specular-chain auxiliary buffers (csrc/rt_aov_chain.hip): the channels above taken at the first vertex of each camera path
+ * that is NOT a followed mirror or glass surface -- what a denoiser wants for guides where the first hit is perfectly specular
+ * (there the first-hit channels describe the mirror, not what is seen in it).  No random draw is taken beyond the jitter, so the
+ * result is exact and reproducible bit for bit like the first-hit pass.  Arguments, layout, options ignored, traversal modes,
+ * host-only scenes, multi-device heads and "no side effects" are those of rt_render_aov; a kernel of its own, no other entry point
+ * changes.
+ *
+ * Per pass p of pixel (x, y):
+ *   Segment 0 is exactly the camera ray of rt_render_aov (the first two draws of stream (seed, pixel, p) for the jitter; NO
+ *   further draw is taken).  T = (1, 1, 1), D = +0, b = 0.  Each segment is traced for its closest hit; with wo the segment's
+ *   normalised direction:
+ *   - a miss ends the chain on the sky;
+ *   - a hit on a FOLLOWED material while b < max_chain continues it:  T = T * colour_value(wo, hit.point) of the material's
+ *     texture, per channel;  D = D + Hit.t;  b = b + 1;  and the next segment is
+ *       Reflect with fuzz <= fuzz_limit:  Ray::new(offset_ray(point, normal, error, true), reflected(-wo, normal)), i.e.
+ *           reflect.rs:27-31 with the fuzz term LEFT OUT (not multiplied by zero: direction + 0 * v can turn -0 into +0);
+ *       Refract:  with eta_fraction, cos_theta and sin_theta of refract.rs:28-35: the branch the reference takes with certainty
+ *           or with the larger weight, never by chance -- if eta_fraction * sin_theta > 1 the Reflect segment above, otherwise the
+ *           refracted direction and origin of refract.rs:44-48 (offset_ray(..., false)); the Fresnel draw is not made;
+ *     a Reflect with fuzz > fuzz_limit (or NaN) is not followed;
+ *   - any other hit -- a material that is not followed, or a followed one once b = max_chain -- ends the chain: the TERMINAL.
+ *   Per-pass terms:  albedo = T * (the first-hit albedo rule applied to the terminal with its segment's wo, or to the sky on a
+ *   miss);  normal = the terminal's Hit.normal (world space, as the reflected surface has it: it is NOT un-mirrored; 0 on the
+ *   sky);  depth term = D + the terminal's Hit.t, a chain that ends on the sky counts toward neither depth nor coverage;
+ *   bounces term = (float)b.
+ * Folds: those of rt_render_aov; bounces = (f32 sum of the terms in pass order from +0) / (float)samples_per_pixel.  IDs are those
+ * of the terminal of pass sample_begin (UINT32_MAX on the sky).
+ * Consequences: with max_chain = 0, and for any max_chain on a scene without followed materials, every channel holds the BYTES of
+ * rt_render_aov (1 * c and +0 + t are exact).
+ * Options: max_chain 0..64 (default 8); fuzz_limit finite and >= 0 (default 0: perfect mirrors and glass only -- any fuzz blurs
+ * what the chain reports sharply; the option exists so that the effect of following fuzzy mirrors can be measured); else
+ * RT_ERR_INVALID_ARGUMENT.  `reserved` is for later fields (rt_aov_chain_opts_default zeroes it).
+ * The chain depth is a PATH LENGTH, not a distance from the camera: it is not valid for rt_denoise_temporal's reprojection test
+ * (feeding chain guides to the temporal stage is not defined here).  albedo / normal / depth are drop-in inputs for rt_denoise
+ * and rt_upscale.  Quality and cost: DESIGN.md section 14.
+ * rt_render_aov_chain: HOST buffers, blocking.  rt_render_aov_chain_device: DEVICE buffers on the scene's GPU, asynchronous on
+ * hip_stream; it allocates nothing and keeps no state, so it can be captured into a graph from its first call (the slot -> index
+ * table of the `primitive` channel is uploaded with the scene). */
+typedef struct rt_aov_chain_opts {
+	uint32_t max_chain; /* followed hits per pass at most, default 8 */
+	float fuzz_limit;   /* a Reflect is followed when its fuzz <= this, default 0 */
+	uint32_t reserved[6];
+} rt_aov_chain_opts;
+typedef struct rt_aov_chain_buffers {
+	rt_aov_buffers aov; /* as rt_render_aov, at the terminal */
+	float *bounces;     /* w*h: mean number of followed hits */
+} rt_aov_chain_buffers;
+int rt_aov_chain_opts_default(rt_aov_chain_opts *out);
+int rt_render_aov_chain(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_aov_chain_opts *chain,
+                        const rt_aov_chain_buffers *host_out);
+int rt_render_aov_chain_device(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_aov_chain_opts *chain,
+                               const rt_aov_chain_buffers *device_out, void *hip_stream);
 
 /* ---- AOV-guided edge-aware A-Trous denoiser (csrc/rt_denoise.hip): the spatial part of SVGF (Dammertz et al. HPG 2010, Schied et
  * al. HPG 2017) on albedo-demodulated radiance.  W x H, FRAME layout, row-major, y down, f32 throughout.  Per pixel p:

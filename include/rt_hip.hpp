@@ -329,6 +329,45 @@ inline AovBuffers render_aov(const RenderOptions &o, const SimpleCamera &camera,
 	return a;
 }
 
+// The same channels taken through perfect mirrors and glass, at the first vertex of each camera path that is not one (semantics:
+// rt_hip.h rt_aov_chain_opts); `bounces` is the mean number of surfaces followed.  AovChainBuffers is an AovBuffers, so it goes
+// wherever one is taken (denoise, upscale) -- but not to TemporalDenoiser: its depth is a path length.
+struct AovChainOptions {
+	uint32_t max_chain = 8;
+	float fuzz_limit = 0.0f;
+};
+struct AovChainBuffers : AovBuffers {
+	std::vector<float> bounces; // w*h
+};
+inline AovChainBuffers render_aov_chain(const RenderOptions &o, const SimpleCamera &camera, const Bvh &bvh,
+                                        const AovChainOptions &c = AovChainOptions(), uint64_t seed = 1, uint64_t sample_begin = 0)
+{
+	rt_render_opts opts;
+	rt_render_opts_default(&opts);
+	opts.width = o.width;
+	opts.height = o.height;
+	opts.samples_per_pixel = o.samples_per_pixel;
+	opts.sample_begin = sample_begin;
+	opts.seed = seed;
+	rt_aov_chain_opts copts;
+	rt_aov_chain_opts_default(&copts);
+	copts.max_chain = c.max_chain;
+	copts.fuzz_limit = c.fuzz_limit;
+	const size_t n = (size_t)o.width * o.height;
+	AovChainBuffers a;
+	a.albedo.resize(n * 3);
+	a.normal.resize(n * 3);
+	a.depth.resize(n);
+	a.coverage.resize(n);
+	a.primitive.resize(n);
+	a.material.resize(n);
+	a.bounces.resize(n);
+	const rt_aov_chain_buffers b = {{a.albedo.data(), a.normal.data(), a.depth.data(), a.coverage.data(), a.primitive.data(), a.material.data()},
+	                                a.bounces.data()};
+	check(rt_render_aov_chain(bvh.raw(), &camera.raw(), &opts, &copts, &b));
+	return a;
+}
+
 // The A-Trous denoiser of rt_hip.h (rt_denoise_opts): the options a caller sets; defaults as rt_denoise_opts_default.
 struct DenoiseOptions {
 	uint32_t iterations = 5;

@@ -215,6 +215,25 @@ class AovBuffers(C.Structure):  # rt_aov_buffers
 AOV_CHANNELS = ("albedo", "normal", "depth", "coverage", "primitive", "material")
 
 
+class AovChainOpts(C.Structure):  # rt_aov_chain_opts
+    _fields_ = [
+        ("max_chain", C.c_uint32),
+        ("fuzz_limit", C.c_float),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+
+class AovChainBuffers(C.Structure):  # rt_aov_chain_buffers
+    _fields_ = [
+        ("aov", AovBuffers),
+        ("bounces", C.POINTER(C.c_float)),
+    ]
+
+
+AOV_CHAIN_CHANNELS = AOV_CHANNELS + ("bounces",)
+AOV_CHAIN_MAX_CHAIN = 64
+
+
 class DenoiseOpts(C.Structure):  # rt_denoise_opts
     _fields_ = [
         ("width", C.c_uint32),
@@ -347,6 +366,8 @@ EXPECTED_SIZES = {
     "rt_sampler_progress": (SamplerProgressC, 32),
     "rt_launch_info": (LaunchInfo, 224),
     "rt_aov_buffers": (AovBuffers, 48),
+    "rt_aov_chain_opts": (AovChainOpts, 32),
+    "rt_aov_chain_buffers": (AovChainBuffers, 56),
     "rt_denoise_opts": (DenoiseOpts, 48),
     "rt_denoise_inputs": (DenoiseInputs, 40),
     "rt_temporal_opts": (TemporalOpts, 96),
@@ -399,6 +420,9 @@ EXPORTED_SYMBOLS = [
     "rt_selftest_lean",
     "rt_render_aov",
     "rt_render_aov_device",
+    "rt_aov_chain_opts_default",
+    "rt_render_aov_chain",
+    "rt_render_aov_chain_device",
     "rt_denoise_opts_default",
     "rt_denoise_workspace_bytes",
     "rt_denoise",
@@ -421,6 +445,13 @@ EXPORTED_SYMBOLS = [
     "rt_upscale",
     "rt_render_upscaled",
 ]
+
+
+def default_aov_chain_opts(max_chain=8, fuzz_limit=0.0):
+    """rt_aov_chain_opts_default (include/rt_hip.h)."""
+    o = AovChainOpts()
+    o.max_chain, o.fuzz_limit = max_chain, fuzz_limit
+    return o
 
 
 def default_denoise_opts(width=0, height=0, iterations=5, sigma_luminance=4.0, sigma_normal=128.0, sigma_depth=0.1):

@@ -298,6 +298,16 @@ static int upload_scene(rt_scene *s, const HostScene &h)
 	if ((rc = upload(s, h.dev_prims.data(), h.dev_prims.size(), &D.prims)) != RT_OK) return bail(rc);
 	if ((rc = upload(s, h.dev_shade.data(), h.dev_shade.size(), &D.shade)) != RT_OK) return bail(rc);
 	if ((rc = upload(s, h.prim_rank.data(), h.prim_rank.size(), &D.prim_rank)) != RT_OK) return bail(rc);
+	// BVH slot -> index in rt_scene_desc.primitives for the AOV passes' `primitive` channel: with the scene, so that those passes
+	// allocate nothing (the members of a multi-device scene never run them; >= 2^32 - 1 primitives: the channel is refused)
+	if (&h == &s->host && h.primitive_order.size() < 0xFFFFFFFFull) {
+		std::vector<uint32_t> desc(h.primitive_order.size());
+		for (size_t i = 0; i < desc.size(); ++i)
+			desc[i] = (uint32_t)h.primitive_order[i];
+		const uint32_t *d_desc = nullptr;
+		if ((rc = upload(s, desc.data(), desc.size(), &d_desc)) != RT_OK) return bail(rc);
+		s->d_prim_desc = const_cast<uint32_t *>(d_desc);
+	}
 	{
 		const uint32_t *d_big = nullptr;
 		if ((rc = upload(s, h.big_leaves.data(), h.big_leaves.size(), &d_big)) != RT_OK) return bail(rc);

@@ -92,7 +92,7 @@ struct rt_scene {
 	std::string gather_note;               // why (rt_scene_gather_info)
 	hipEvent_t ev_gathered = nullptr;      // head: the last render's gather + scatter have read every member's shard
 	bool gathered_once = false;
-	uint32_t *d_prim_desc = nullptr;       // rt_render_aov: BVH slot -> rt_scene_desc index, uploaded on first use (in `allocations`)
+	uint32_t *d_prim_desc = nullptr;       // AOV passes: BVH slot -> rt_scene_desc index, uploaded with the scene (in `allocations`)
 	char *d_denoise = nullptr;             // rt_denoise / rt_render_denoised: device frames + workspace, grown on first use
 	size_t d_denoise_bytes = 0;
 	char *d_temporal = nullptr;            // rt_denoise_temporal: its two history buffers, for frames of temporal_w x temporal_h

@@ -1,6 +1,6 @@
-// rt_api_post.cpp -- the host side of the post-processing stages of librt_hip.so (include/rt_hip.h): first-hit AOV buffers,
-// the A-Trous denoiser, temporal accumulation, the display stage and AOV-guided upscaling.  Each stage has its kernels in a file of
-// its own (rt_aov.hip, rt_denoise.hip, rt_temporal.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
+// rt_api_post.cpp -- the host side of the post-processing stages of librt_hip.so (include/rt_hip.h): first-hit and specular-chain
+// AOV buffers, the A-Trous denoiser, temporal accumulation, the display stage and AOV-guided upscaling.  Each stage has its kernels in a file of
+// its own (rt_aov.hip, rt_aov_chain.hip, rt_denoise.hip, rt_temporal.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
 // and the blocking wrappers that stage host buffers through scene-owned device memory (Staging, rt_api_internal.h).
 // Every check function ends with the device (need_device), so that a host-only scene reports bad arguments as such.
 #include <hip/hip_runtime.h>
@@ -11,6 +11,7 @@
 
 #include "rt_api_internal.h"
 #include "rt_aov.h"
+#include "rt_aov_chain.h"
 #include "rt_denoise.h"
 #include "rt_temporal.h"
 #include "rt_display.h"
@@ -41,31 +42,11 @@ static int aov_check(const rt_scene *s, const rt_camera *camera, const rt_render
 	return need_device(s);
 }
 
-extern "C" {
-
-int rt_render_aov_device(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *d_out, void *hip_stream)
+// traversal as rt_render / rt_check_hit choose it; the whole worst-case stack of the workgroup in LDS: the wide tree's only
+// where it is walked and fits, the two-child tree's (and the two-child walk for every ray) otherwise.  Both AOV kernels keep the
+// same stacks (aov_lds_bytes == aov_chain_lds_bytes).
+static int aov_traversal(const rt_scene *s, bool *prune_out, DevScene *dev_out)
 {
-	uint32_t mask = 0;
-	int rc = aov_check(s, camera, o, d_out, &mask);
-	if (rc != RT_OK)
-		return rc;
-	// a multi-device head is an ordinary scene on devices[0]: the AOV pass runs there alone
-	HIP_TRY(hipSetDevice(s->device));
-	if ((mask & kAovPrimitive) && !s->d_prim_desc) { // first use: BVH slot -> caller's index (synchronous, once per scene)
-		const std::vector<uint64_t> &order = s->host.primitive_order;
-		if (order.size() >= 0xFFFFFFFFull)
-			return fail(RT_ERR_UNSUPPORTED, "primitive IDs need fewer than 2^32 - 1 primitives");
-		std::vector<uint32_t> desc(order.size());
-		for (size_t i = 0; i < order.size(); ++i)
-			desc[i] = (uint32_t)order[i];
-		const uint32_t *d = nullptr;
-		rc = upload(s, desc.data(), desc.size(), &d);
-		if (rc != RT_OK)
-			return rc;
-		s->d_prim_desc = const_cast<uint32_t *>(d);
-	}
-	// traversal as rt_render / rt_check_hit choose it; the whole worst-case stack of the workgroup in LDS: the wide tree's only
-	// where it is walked and fits, the two-child tree's (and the two-child walk for every ray) otherwise
 	const bool prune = s->traversal_mode == -1 ? s->dev.n_prims > kPruneAbove : s->traversal_mode == 1;
 	DevScene dev = s->dev;
 	const bool walks_wide = prune && dev.nodes4 != nullptr && dev.narrow_only == 0u;
@@ -76,6 +57,14 @@ int rt_render_aov_device(rt_scene *s, const rt_camera *camera, const rt_render_o
 	}
 	if (aov_lds_bytes(dev) > s->max_lds)
 		return fail(RT_ERR_UNSUPPORTED, "traversal stacks exceed the LDS of one CU");
+	*prune_out = prune;
+	*dev_out = dev;
+	return RT_OK;
+}
+
+// the launch parameters both AOV kernels share
+static DevAovParams aov_params(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *d_out, uint32_t mask)
+{
 	DevAovParams P;
 	std::memset(&P, 0, sizeof P);
 	std::memcpy(P.cam.origin, camera->origin, 12);
@@ -99,6 +88,27 @@ int rt_render_aov_device(rt_scene *s, const rt_camera *camera, const rt_render_o
 	P.coverage = d_out->coverage;
 	P.primitive = d_out->primitive;
 	P.material = d_out->material;
+	return P;
+}
+
+extern "C" {
+
+int rt_render_aov_device(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *d_out, void *hip_stream)
+{
+	uint32_t mask = 0;
+	int rc = aov_check(s, camera, o, d_out, &mask);
+	if (rc != RT_OK)
+		return rc;
+	// a multi-device head is an ordinary scene on devices[0]: the AOV pass runs there alone
+	HIP_TRY(hipSetDevice(s->device));
+	if ((mask & kAovPrimitive) && !s->d_prim_desc) // (upload_scene, rt_api.cpp, makes the table for fewer primitives)
+		return fail(RT_ERR_UNSUPPORTED, "primitive IDs need fewer than 2^32 - 1 primitives");
+	bool prune = false;
+	DevScene dev;
+	rc = aov_traversal(s, &prune, &dev);
+	if (rc != RT_OK)
+		return rc;
+	const DevAovParams P = aov_params(s, camera, o, d_out, mask);
 	HIP_TRY(launch_aov(prune, static_cast<hipStream_t>(hip_stream), dev, P));
 	return RT_OK;
 }
@@ -123,6 +133,88 @@ int rt_render_aov(rt_scene *s, const rt_camera *camera, const rt_render_opts *o,
 	for (int c = 0; c < 6; ++c)
 		st.download(host[c], st.at(d, c), 4 * st.count[c]);
 	rc = st.finish("render_aov");
+	(void)hipFree(d);
+	return rc;
+}
+
+
+// ---- specular-chain AOV buffers (rt_aov_chain.hip) ----
+int rt_aov_chain_opts_default(rt_aov_chain_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	out->max_chain = 8;
+	out->fuzz_limit = 0.0f;
+	return RT_OK;
+}
+
+// argument checks of both chain entry points: the chain's own, then those of the first-hit pass (the device last)
+static int aov_chain_check(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_chain_opts *c,
+                           const rt_aov_chain_buffers *b, uint32_t *mask)
+{
+	if (!s || !camera || !o || !c || !b)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (c->max_chain > kAovChainMaxChain)
+		return fail(RT_ERR_INVALID_ARGUMENT, "aov_chain: max_chain must be in 0..64");
+	if (!std::isfinite(c->fuzz_limit) || !(c->fuzz_limit >= 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "aov_chain: fuzz_limit must be finite and >= 0");
+	// (a `bounces` pointer stands in for "some channel is given" in the first-hit check)
+	rt_aov_buffers any = b->aov;
+	if (b->bounces && !any.albedo)
+		any.albedo = b->bounces;
+	const int rc = aov_check(s, camera, o, &any, mask);
+	*mask = (*mask & ~(b->aov.albedo ? 0u : kAovAlbedo)) | (b->bounces ? kAovBounces : 0u);
+	return rc;
+}
+
+int rt_render_aov_chain_device(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_chain_opts *c,
+                               const rt_aov_chain_buffers *d_out, void *hip_stream)
+{
+	uint32_t mask = 0;
+	int rc = aov_chain_check(s, camera, o, c, d_out, &mask);
+	if (rc != RT_OK)
+		return rc;
+	// a multi-device head is an ordinary scene on devices[0]: the pass runs there alone
+	HIP_TRY(hipSetDevice(s->device));
+	if ((mask & kAovPrimitive) && !s->d_prim_desc)
+		return fail(RT_ERR_UNSUPPORTED, "primitive IDs need fewer than 2^32 - 1 primitives");
+	bool prune = false;
+	DevScene dev;
+	rc = aov_traversal(s, &prune, &dev);
+	if (rc != RT_OK)
+		return rc;
+	DevAovChainParams P;
+	std::memset(&P, 0, sizeof P);
+	P.A = aov_params(s, camera, o, &d_out->aov, mask);
+	P.max_chain = c->max_chain;
+	P.fuzz_limit = c->fuzz_limit;
+	P.bounces = d_out->bounces;
+	HIP_TRY(launch_aov_chain(prune, static_cast<hipStream_t>(hip_stream), dev, P));
+	return RT_OK;
+}
+
+int rt_render_aov_chain(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_chain_opts *c,
+                        const rt_aov_chain_buffers *out)
+{
+	uint32_t mask = 0;
+	int rc = aov_chain_check(s, camera, o, c, out, &mask);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	// one device allocation per call for the requested channels, in rt_aov_chain_buffers order; 4-byte elements throughout
+	const size_t n_px = (size_t)(o->width * o->height);
+	Staging st{s};
+	void *host[7] = {out->aov.albedo, out->aov.normal, out->aov.depth, out->aov.coverage, out->aov.primitive, out->aov.material, out->bounces};
+	for (int ch = 0; ch < 7; ++ch)
+		st.add(host[ch], (ch < 2 ? 3 : 1) * n_px);
+	char *d = nullptr;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), st.total * 4));
+	const rt_aov_chain_buffers dev_out = {{st.at(d, 0), st.at(d, 1), st.at(d, 2), st.at(d, 3), st.at<uint32_t>(d, 4), st.at<uint32_t>(d, 5)}, st.at(d, 6)};
+	st.rc = rt_render_aov_chain_device(s, camera, o, c, &dev_out, s->stream);
+	for (int ch = 0; ch < 7; ++ch)
+		st.download(host[ch], st.at(d, ch), 4 * st.count[ch]);
+	rc = st.finish("render_aov_chain");
 	(void)hipFree(d);
 	return rc;
 }

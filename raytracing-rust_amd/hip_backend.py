@@ -308,6 +308,40 @@ class HipScene:
             setattr(bufs, name, _dp(ptr, ctype))
         _check(lib().rt_render_aov_device(self._h, C.byref(camera), C.byref(opts), C.byref(bufs), C.c_void_p(stream)))
 
+    # ---- specular-chain AOV buffers (rt_render_aov_chain): the same channels seen through perfect mirrors and glass ----
+    def render_aov_chain(self, camera, opts, channels=abi.AOV_CHAIN_CHANNELS, max_chain=8, fuzz_limit=0.0):
+        """The channels of render_aov taken at the first vertex of each camera path that is not a followed Reflect / Refract
+        surface, plus "bounces" (H, W) f32, the mean number of surfaces followed; as {channel: numpy array}.  albedo / normal /
+        depth are drop-in guides for denoise and upscale (not for denoise_temporal: the depth is a path length).  Semantics:
+        include/rt_hip.h rt_aov_chain_opts."""
+        channels = tuple(channels)
+        unknown = set(channels) - set(abi.AOV_CHAIN_CHANNELS)
+        if unknown:
+            raise ValueError(f"unknown AOV channels {sorted(unknown)}")
+        h, w = int(opts.height), int(opts.width)
+        out, bufs = {}, abi.AovChainBuffers()
+        for name in channels:
+            dtype, ctype = (np.uint32, C.c_uint32) if name in ("primitive", "material") else (np.float32, C.c_float)
+            shape = (h, w, 3) if name in ("albedo", "normal") else (h, w)
+            out[name] = np.zeros(shape, dtype=dtype)
+            setattr(bufs if name == "bounces" else bufs.aov, name, _p(out[name], ctype))
+        copts = abi.default_aov_chain_opts(max_chain, fuzz_limit)
+        _check(lib().rt_render_aov_chain(self._h, C.byref(camera), C.byref(opts), C.byref(copts), C.byref(bufs)))
+        return out
+
+    def render_aov_chain_device(self, camera, opts, d_ptrs, stream=0, max_chain=8, fuzz_limit=0.0):
+        """rt_render_aov_chain_device: asynchronous, into DEVICE buffers of the scene's GPU.  d_ptrs = {channel: device pointer}
+        over abi.AOV_CHAIN_CHANNELS; channels left out are not produced.  Allocates nothing: capturable from the first call."""
+        bufs = abi.AovChainBuffers()
+        for name, ptr in d_ptrs.items():
+            if name not in abi.AOV_CHAIN_CHANNELS:
+                raise ValueError(f"unknown AOV channel {name!r}")
+            ctype = C.c_uint32 if name in ("primitive", "material") else C.c_float
+            setattr(bufs if name == "bounces" else bufs.aov, name, _dp(ptr, ctype))
+        copts = abi.default_aov_chain_opts(max_chain, fuzz_limit)
+        _check(lib().rt_render_aov_chain_device(self._h, C.byref(camera), C.byref(opts), C.byref(copts), C.byref(bufs),
+                                                C.c_void_p(stream)))
+
     # ---- AOV-guided A-Trous denoiser (rt_denoise) ----
     def denoise(self, color, albedo=None, normal=None, depth=None, variance=None, **opts):
         """rt_denoise: filter an (H, W, 3) f32 radiance image guided by the optional albedo / normal (H, W, 3), depth and variance
