@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void temporal_reproject(const DevTemporalParam
 						if (P.normal && !np0 && !(hq1.x == 0.0f && hq1.y == 0.0f && hq1.z == 0.0f) &&
 						    !(g.x * hq1.x + g.y * hq1.y + g.z * hq1.z >= P.normal_tol))
 							continue;
-						const float4 hq2 = P.hist_in[2u * n_px + q];
+						const float4 hq2 = P.hist_in[2ull * n_px + q];
 						sw = sw + w;
 						sr = sr + w * hq0.x;
 						sg = sg + w * hq0.y;
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256) void temporal_reproject(const DevTemporalParam
 			P.motion[2ull * p + 1] = my;
 		}
 		P.hist_out[p] = valid ? make_float4(e[0], e[1], e[2], n) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-		P.hist_out[2u * n_px + p] = valid ? make_float4(m1, m2, 0.0f, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+		P.hist_out[2ull * n_px + p] = valid ? make_float4(m1, m2, 0.0f, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 	}
 }
 
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void temporal_resolve(const DevTemporalParams 
 		const float4 h0 = P.hist_out[p];
 		float var = spatial;
 		if (h0.w >= 4.0f) {
-			const float4 h2 = P.hist_out[2u * n_px + p];
+			const float4 h2 = P.hist_out[2ull * n_px + p];
 			var = fmaxf(0.0f, h2.y - h2.x * h2.x);
 		}
 		plane0[p] = make_float4(h0.x, h0.y, h0.z, var);

@@ -86,15 +86,16 @@ class DeviceRunner:
         return T.history_array(self.hist[i].cpu().numpy(), self.h, self.w)
 
 
-def check_step(inputs, cam, prev, h_in, out, motion, h_out, what, iterations=5, normal=True):
+def check_step(inputs, cam, prev, h_in, out, motion, h_out, what, iterations=5, normal=True, **opts):
+    """`opts`: the temporal options and sigmas the GPU ran with, for the checker (the defaults when none are given)"""
     st = T.step(inputs["color"], inputs["depth"], cam, prev, h_in, albedo=inputs.get("albedo"),
-                normal=inputs.get("normal") if normal else None)
+                normal=inputs.get("normal") if normal else None, **opts)
     assert bits_equal(motion, st["motion"]), f"{what}: motion"
     assert bits_equal(h_out[0, ..., 3], st["n"]), f"{what}: n"
     assert bits_equal(h_out[2, ..., 0], st["m1"]) and bits_equal(h_out[2, ..., 1], st["m2"]), f"{what}: moments"
     assert bits_equal(h_out[1], st["history"][1]), f"{what}: n^ and z"
     assert not h_out[2, ..., 2:].any(), what
-    e1, ref = T.filtered(st, inputs["color"], normal, iterations=iterations)
+    e1, ref = T.filtered(st, inputs["color"], normal, iterations=iterations, **{k: v for k, v in opts.items() if k.startswith("sigma_")})
     ok = st["valid"]
     assert np.array_equal(out[~ok], inputs["color"][~ok], equal_nan=True), f"{what}: invalid pixels pass through"
     err_e1, err_out = K.relative_error(h_out[0][ok][:, :3], e1[ok]), K.relative_error(out[ok], ref[ok])
