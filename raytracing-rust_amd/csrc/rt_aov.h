@@ -1,4 +1,4 @@
-// rt_aov.h -- launch interface of the first-hit AOV kernel (rt_aov.hip), shared with rt_api.cpp.
+// rt_aov.h -- launch interface of the first-hit AOV kernel (rt_aov.hip), shared with rt_api_post.cpp.
 #pragma once
 
 #include "rt_types.h"
@@ -28,8 +28,7 @@ struct DevAovParams {
 	uint32_t *primitive, *material;
 };
 
-// the whole worst-case traversal stack of a 256-thread workgroup in LDS (as the batch hit queries keep it)
-size_t aov_lds_bytes(const DevScene &S);
+// (the whole worst-case traversal stack of a 256-thread workgroup in LDS: four_wave_stack_lds_bytes, rt_types.h)
 hipError_t launch_aov(bool prune, hipStream_t stream, const DevScene &S, const DevAovParams &P);
 
 } // namespace rt

@@ -15,8 +15,6 @@ struct DevAovChainParams {
 	float *bounces;
 };
 
-// the whole worst-case traversal stack of a 256-thread workgroup in LDS (as the first-hit pass keeps it)
-size_t aov_chain_lds_bytes(const DevScene &S);
 hipError_t launch_aov_chain(bool prune, hipStream_t stream, const DevScene &S, const DevAovChainParams &P);
 
 } // namespace rt

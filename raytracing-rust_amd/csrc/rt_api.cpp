@@ -5,9 +5,10 @@
 // There is NO CPU fallback: without a HIP device every compute entry point fails with
 // RT_ERR_NO_DEVICE.
 //
-// This file: scene creation, multi-device scenes, render, sampling, output, check-hit and the self-tests.  The
-// post-processing stages (AOV buffers, denoiser, temporal accumulation, display) are rt_api_post.cpp; what the two share
-// (rt_scene, the error convention, the argument checks and buffer plumbing) is rt_api_internal.h.
+// This file: scene creation, multi-device scenes, the render-launch planner (plan_render_launch) and rt_render_device that carries
+// a plan out, sampling, output, check-hit and the self-tests; what rt_render.hip exports to it is rt_render.h.  The post-processing
+// stages (AOV buffers, denoiser, temporal accumulation, display) are rt_api_post.cpp; what the two share (rt_scene, the error
+// convention, the four-wave kernels' traversal policy, the argument checks and buffer plumbing) is rt_api_internal.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -22,36 +23,7 @@
 #include "../../include/rt_detmath.h"
 #include <dlfcn.h>
 #include "rt_api_internal.h"
-
-namespace rt {
-size_t render_lds_bytes(const DevScene &S, bool sky_lds, bool scene_lds, uint32_t waves_per_block, uint32_t stack_cap);
-uint32_t render_waves_per_simd(int feature_set, bool fine);
-uint32_t render_block_threads(int feature_set, bool fine, bool xchg = false);
-size_t render_exchange_fine_lds_bytes(uint32_t waves_per_block);
-uint32_t render_max_block_threads(int feature_set, bool fine, bool xchg);
-hipError_t render_occupancy(int method, bool prune, bool fine, bool sky_lds, int feature_set, size_t lds_bytes, int *blocks_per_cu, bool xchg,
-                            uint32_t block_threads = 0);
-bool render_exchange_available(int method, bool prune, bool fine, int feature_set);
-size_t render_exchange_lds_bytes(uint32_t slots);
-uint32_t render_exchange_max_slots();
-hipError_t launch_render(int method, bool prune, bool fine, bool sky_lds, int feature_set, uint32_t n_blocks, size_t lds_bytes, hipStream_t stream,
-                         const DevScene &S, const DevCamera &cam, const DevRenderParams &P, float *out,
-                         unsigned long long *rays_shot, uint32_t *work_counter, uint32_t *stack_ovf, bool xchg, const DevPairScene *pair,
-                         uint32_t block_threads = 0);
-hipError_t launch_combine(hipStream_t stream, const DevRenderParams &P, const float *partial, float *out);
-hipError_t launch_reset(hipStream_t stream, uint32_t *work_counter, unsigned long long *rays_shot, float *out, size_t n_out_floats);
-hipError_t launch_quantise(hipStream_t stream, const float *rgb, size_t n_values, float inv_gamma, uint8_t *out);
-hipError_t launch_check_hit(bool prune, hipStream_t stream, const DevScene &S, const void *rays, uint64_t n, void *out);
-#ifdef RT_STATS
-hipError_t launch_trace_queue(int waves, uint32_t n_blocks, size_t lds_bytes, hipStream_t stream, const DevScene &S, const void *rays, uint32_t n, void *out,
-                              uint32_t *counter, unsigned long long *steps, uint32_t cap, uint32_t ovf_depth, uint32_t *ovf);
-#endif
-hipError_t launch_scatter_shard(hipStream_t stream, const DevRenderParams &P, const float *shard, float *frame);
-hipError_t launch_sum_u64(hipStream_t stream, const unsigned long long *parts, uint32_t n, unsigned long long *out);
-hipError_t launch_selftest_lean(hipStream_t stream, uint32_t blocks, uint64_t n_per_thread, uint64_t seed, unsigned long long *mismatches);
-hipError_t launch_check_hit_index(bool prune, hipStream_t stream, const DevScene &S, const void *rays, const void *object_index,
-                                  uint64_t n, void *out);
-} // namespace rt
+#include "rt_render.h"
 
 using namespace rt;
 
@@ -917,6 +889,248 @@ static int ensure_frame_buffers(rt_scene *s, uint64_t n_floats, bool progressive
 	return RT_OK;
 }
 
+// ---- planning a render launch: every decision first (plan_render_launch), every side effect after (rt_render_device) ----
+// the tile and shard fields of DevRenderParams: what the render kernel and the scatter of a multi-device render both decode pixels by
+static void fill_tiling(DevRenderParams &P, const rt_render_opts *o, const ShardGeometry &g)
+{
+	P.width = (uint32_t)o->width;
+	P.height = (uint32_t)o->height;
+	P.shard_index = o->shard_index;
+	P.shard_count = o->shard_count;
+	P.tile_w = g.tile_w;
+	P.tile_h = g.tile_h;
+	P.tiles_x = g.tiles_x;
+	P.tiles_y = g.tiles_y;
+	P.n_work = (uint32_t)g.n_work;
+}
+
+// What one render launch will be: a plain value, made without touching the scene, a stream or device memory.
+struct RenderLaunchPlan { // (filled in this order at the end of plan_render_launch)
+	DevRenderParams P; // (P.stack_ovf_depth: entries per lane the launch needs in the scene's global overflow area)
+	DevScene dev;      // the scene as this launch sees it (narrow_only)
+	bool prune, fine, sky_lds, scene_lds, xchg;
+	int feature_set, blocks_per_cu; // (the feature set of THIS launch: 3 = FeatPair)
+	uint32_t block_threads, n_blocks;
+	size_t lds_bytes;
+	uint32_t split; // sample_split, resolved
+};
+
+// Walk, schedule, feature set, stacks, workgroup size, where the sky tables and the scene live, the exchange pool and the grid
+// of the render of shard `g` under `o`.  The occupancy queries need s->device to be the current device.
+static int plan_render_launch(const rt_scene *s, const rt_render_opts *o, const ShardGeometry &g, RenderLaunchPlan *plan)
+{
+	DevRenderParams P;
+	std::memset(&P, 0, sizeof P);
+	fill_tiling(P, o, g);
+	P.spp = (uint32_t)o->samples_per_pixel;
+	P.sample_begin_lo = (uint32_t)o->sample_begin;
+	P.sample_begin_hi = (uint32_t)(o->sample_begin >> 32);
+	P.seed_lo = (uint32_t)o->seed;
+	P.seed_hi = (uint32_t)(o->seed >> 32);
+	P.max_depth = o->max_depth;
+	P.rr_threshold = o->rr_threshold;
+	// sample_split 0 = automatic, on one device as on several (auto_sample_split: >= 64 work items per resident lane)
+	uint32_t split = o->sample_split;
+	if (split == 0u)
+		split = auto_sample_split(s->n_cus, o->width * o->height, o->samples_per_pixel, o->shard_count);
+	{ // u = (jitter + x) / (W - 1), v = (jitter + y) / (H - 1) by verified reciprocals (cached per divisor: rt_build.cpp)
+		float rw = 0.0f, rh = 0.0f;
+		const bool sized = o->width <= (1u << 24) && o->height <= (1u << 24);
+		const bool ok_w = sized && verified_reciprocal((float)(o->width - 1), &rw), ok_h = sized && verified_reciprocal((float)(o->height - 1), &rh);
+		const bool ok = ok_w && ok_h;
+		P.w1h1_ok = ok ? 1u : 0u;
+		P.inv_w1 = rw;
+		P.inv_h1 = rh;
+	}
+	P.tile_log2_w = 0xFFFFFFFFu;
+	if (g.tile_w * g.tile_h == 64u && (g.tile_w & (g.tile_w - 1u)) == 0u && o->width < 65536u && o->height < 65536u &&
+	    (split & (split - 1u)) == 0u && split <= 64u)
+		for (uint32_t lw = 0; lw < 7u; ++lw)
+			for (uint32_t ls = 0; ls < 7u; ++ls)
+				if ((1u << lw) == g.tile_w && (1u << ls) == split)
+					P.tile_log2_w = lw | (ls << 8);
+	if (split > o->samples_per_pixel)
+		return fail(RT_ERR_INVALID_ARGUMENT, "sample_split larger than samples_per_pixel");
+	if (g.n_work * split >= (1ull << 32))
+		return fail(RT_ERR_UNSUPPORTED, "pixels x sample_split exceeds 2^32 work items");
+	P.sample_split = split;
+	P.n_items = (uint32_t)(g.n_work * split);
+	P.shard_layout = o->output_layout == RT_LAYOUT_SHARD ? 1 : 0;
+
+	// traversal: exhaustive (the reference's own amount of work) for tiny trees where pruning cannot
+	// pay, t-pruned otherwise; both select the same winner (rt_intersect.h)
+	// and how finely the wave votes: measured crossovers on random sphere scenes (tests/probes/gpu_crossover_probe.py)
+	bool prune = scene_prunes(s);
+	// the fine schedule walks the wide tree: scenes without one (non-finite bounds, a single leaf) stay coarse
+	const bool fine = s->dev.nodes4 != nullptr &&
+	                  (s->schedule_mode == -1 ? (prune && s->dev.n_prims > (s->dev.has_triangles ? kFineAboveTriangles : kFineAboveSpheres))
+	                                          : s->schedule_mode == 1);
+	if (fine)
+		prune = true;
+	P.prune = prune ? 1 : 0;
+
+	const bool samplable = (s->dev.sky.res_x | s->dev.sky.res_y) != 0u;
+	const size_t sky_bytes = samplable ? ((size_t)s->dev.sky.res_y * (s->dev.sky.res_x + 1u) + s->dev.sky.res_y + 1u) * 4 +
+	                                         (size_t)(s->dev.sky.res_y + 1u) * s->dev.sky.guide_k : 0;
+	// Sky CDF tables in LDS (next to the traversal stacks) or left in global memory: LDS only while
+	// it does not cost resident workgroups.  Tiny trees: 41 KB tables + 1-2 KB stacks still fit 3
+	// workgroups per CU, the register limit.  Deep trees: the stacks alone are tens of KB and the
+	// sky is a small share of the work, so residency (latency hiding for the node fetches) wins.
+	// Tiny scenes under the coarse schedule: the whole scene rides in LDS too.
+	const bool scene_lds = !fine && s->dev.blob_bytes != 0u && s->scene_lds_allowed;
+	P.scene_in_lds = scene_lds ? 1u : 0u;
+	bool sky_lds = false;
+	// RT_TUNE_EXCHANGE (rt_render.hip, XCHG).  Fine schedule: 512-thread workgroups whose waves trade whole lane states
+	// through two record pools behind the stacks; coarse MIS kernels: decided below, once the occupancy is known
+	// (feature set of THIS launch: 3 = FeatPair, built for the exhaustive coarse kernels without the exchange only)
+	const int feature_set =
+	    (s->feature_set == 0 && s->pair_tree && !s->feature_set_forced && !prune && !fine && s->exchange_mode != 1) ? 3 : s->feature_set;
+	bool xchg = s->exchange_mode == 1 && render_exchange_available(o->render_method, prune, fine, feature_set);
+	const bool xchg_fine = xchg && fine;
+	uint32_t block_threads = render_block_threads(feature_set, fine, xchg_fine);
+	const size_t fine_pool_bytes = xchg_fine ? render_exchange_fine_lds_bytes(block_threads / 64u) : 0;
+	// Traversal stacks: one LDS column per lane.  The worst case of a deep tree (three pending siblings per level of
+	// the wide tree) is far above what walks reach, and LDS sized for it would cost resident waves; under the fine
+	// schedule the LDS part is capped at the share a workgroup gets at the occupancy its register budget allows, the
+	// rest of the worst case lives in a global overflow area that is touched only if a walk really gets that deep.
+	// The coarse kernels keep a walk's WHOLE worst-case stack in LDS.  The wide tree's worst case (three pending siblings
+	// per level) is about 1.5 x the two-child tree's, and only pruned walks of regular rays descend it: an exhaustive
+	// launch needs the two-child depth only, and a pruned coarse launch whose wide worst case does not fit the LDS of a CU
+	// (a deep, skewed tree) walks the two-child tree for every ray instead of failing.
+	DevScene dev = s->dev; // what this launch sees
+	const bool walks_wide = prune && dev.nodes4 != nullptr && dev.narrow_only == 0u;
+	uint32_t stack_need = (fine || walks_wide) ? dev.stack_depth : s->stack_depth_narrow;
+	if (!fine && walks_wide &&
+	    render_lds_bytes(dev, false, scene_lds, render_block_threads(feature_set, false, false) / 64u, stack_need) > s->max_lds) {
+		dev.narrow_only = 1u;
+		stack_need = s->stack_depth_narrow;
+	}
+	uint32_t stack_cap = stack_need;
+	if (fine) {
+		const uint32_t blocks_wanted = std::max(1u, render_waves_per_simd(feature_set, true) * 256u / block_threads);
+		const size_t share = s->max_lds / blocks_wanted;
+		const uint32_t fit = (uint32_t)((share > fine_pool_bytes ? share - fine_pool_bytes : 0) / ((block_threads / 64u) * 64u * 4u));
+		stack_cap = std::min(stack_cap, std::max(8u, fit));
+	}
+	if (fine && s->stack_cap_override != 0u) // (coarse kernels keep the whole stack in LDS and walk without capacity checks)
+		stack_cap = std::min(stack_need, s->stack_cap_override);
+	P.stack_cap = stack_cap;
+	P.stack_ovf_depth = stack_need - stack_cap;
+	// What one workgroup size gives: resident workgroups per CU without and -- where that does not cost any -- with the sky tables in LDS
+	const bool sky_lds_possible = samplable && o->render_method == RT_METHOD_MIS && sky_bytes <= 96 * 1024;
+	struct Sizing { uint32_t block; int blocks_per_cu; bool sky; size_t lds; };
+	auto size_launch = [&](uint32_t block, Sizing &z) -> hipError_t {
+		z.block = block;
+		z.sky = false;
+		z.blocks_per_cu = 0;
+		z.lds = render_lds_bytes(dev, false, scene_lds, block / 64u, stack_cap) + fine_pool_bytes;
+		if (z.lds > s->max_lds)
+			return hipSuccess; // (does not fit: blocks_per_cu stays 0)
+		hipError_t e = render_occupancy(o->render_method, prune, fine, false, feature_set, z.lds, &z.blocks_per_cu, xchg_fine, block);
+		if (e != hipSuccess)
+			return e;
+		if (sky_lds_possible) {
+			const size_t lds_with = render_lds_bytes(dev, true, scene_lds, block / 64u, stack_cap) + fine_pool_bytes;
+			int blocks_with = 0;
+			if (lds_with <= s->max_lds &&
+			    render_occupancy(o->render_method, prune, fine, true, feature_set, lds_with, &blocks_with, xchg_fine, block) == hipSuccess &&
+			    blocks_with >= z.blocks_per_cu && blocks_with >= 1) {
+				z.sky = true;
+				z.lds = lds_with;
+				z.blocks_per_cu = blocks_with;
+			}
+		}
+		return hipSuccess;
+	};
+	Sizing Z;
+	HIP_TRY(size_launch(block_threads, Z));
+	if (Z.lds > s->max_lds)
+		return fail(RT_ERR_UNSUPPORTED, "traversal stacks exceed the LDS of one CU");
+	// Coarse spheres-only kernels (FeatPair among them) are issue-bound and use 66 - 100 VGPRs: every further wave per SIMD the
+	// registers allow is worth about 2 % (rt_render.hip RT_PAIR_WAVES).  Three 512-thread workgroups do not fit the LDS with the
+	// sky tables, two of 768 threads do: try the larger workgroup too, keep what puts most waves on a CU, at equal waves what keeps
+	// the sky tables in LDS, at equal both the smaller workgroup.  Only multiples of 256 threads: a workgroup whose waves do not
+	// divide evenly over the four SIMDs is reported as resident twice by the occupancy query, but the second one is not placed
+	// once the fuller SIMDs are out of registers (640 x 2 at 93 VGPRs: 18.8 -> 23.3 ms, 896 x 2: no gain; profiles/r04v_small_ab.log).
+	if (!fine && !xchg) {
+		for (uint32_t cand = block_threads + 256u; cand <= render_max_block_threads(feature_set, fine, false); cand += 256u) {
+			Sizing C;
+			if (size_launch(cand, C) != hipSuccess || C.blocks_per_cu < 1)
+				continue;
+			const uint32_t waves_c = (uint32_t)C.blocks_per_cu * C.block, waves_z = (uint32_t)Z.blocks_per_cu * Z.block;
+			if (waves_c > waves_z || (waves_c == waves_z && C.sky && !Z.sky))
+				Z = C;
+		}
+		block_threads = Z.block;
+	}
+	size_t lds_bytes = Z.lds;
+	int blocks_per_cu = Z.blocks_per_cu;
+	sky_lds = Z.sky;
+	P.sky_in_lds = sky_lds ? 1u : 0u;
+	if (blocks_per_cu < 1)
+		return fail(RT_ERR_HIP, "render kernel does not fit on a CU");
+	// RT_TUNE_EXCHANGE (asked for by name, off by default): the workgroup's pool of parked path states sits behind the stacks
+	// (rt_render.hip, XCHG) and gets the LDS that is left at the occupancy the EXCHANGE kernel reaches by its registers -- it never
+	// costs the sky tables their place; it can cost a resident workgroup where that kernel needs more registers than the plain one
+	// (full feature set: 141 against 125 VGPRs)
+	P.xchg_slots = 0;
+	if (xchg && !fine) {
+		int blocks_plain = 0;
+		if (render_occupancy(o->render_method, prune, fine, sky_lds, feature_set, lds_bytes, &blocks_plain, true) != hipSuccess || blocks_plain < 1) {
+			xchg = false;
+		} else {
+			const int target = std::min(blocks_per_cu, blocks_plain);
+			const size_t share = s->max_lds / (size_t)target; // max_lds is the LDS of one CU
+			uint32_t slots = render_exchange_max_slots();
+			while (slots >= 16u && lds_bytes + render_exchange_lds_bytes(slots) > share)
+				slots -= 4u;
+			int blocks_x = 0;
+			if (slots >= 16u &&
+			    render_occupancy(o->render_method, prune, fine, sky_lds, feature_set, lds_bytes + render_exchange_lds_bytes(slots), &blocks_x, true) == hipSuccess &&
+			    blocks_x >= target) {
+				P.xchg_slots = slots;
+				lds_bytes += render_exchange_lds_bytes(slots);
+				blocks_per_cu = target;
+			} else {
+				xchg = false;
+			}
+		}
+	}
+	uint64_t n_blocks = (uint64_t)s->n_cus * (uint64_t)blocks_per_cu;
+	const uint64_t blocks_needed = ((uint64_t)P.n_items + block_threads - 1) / block_threads;
+	if (n_blocks > blocks_needed)
+		n_blocks = blocks_needed ? blocks_needed : 1;
+	*plan = {P, dev, prune, fine, sky_lds, scene_lds, xchg, feature_set, blocks_per_cu, block_threads, (uint32_t)n_blocks, lds_bytes, split};
+	return RT_OK;
+}
+
+// what is about to run, for rt_last_launch_info
+static void fill_launch_info(const RenderLaunchPlan &plan, const rt_render_opts *o, int n_cus, rt_launch_info *out)
+{
+	rt_launch_info &L = *out;
+	std::memset(&L, 0, sizeof L);
+	L.method = o->render_method;
+	L.pruned = plan.prune ? 1 : 0;
+	L.fine = plan.fine ? 1 : 0;
+	L.sky_in_lds = plan.sky_lds ? 1 : 0;
+	L.scene_in_lds = plan.scene_lds ? 1 : 0;
+	L.feature_set = plan.feature_set;
+	L.block_threads = plan.block_threads;
+	L.n_blocks = plan.n_blocks;
+	L.blocks_per_cu = (uint32_t)plan.blocks_per_cu;
+	L.waves_per_simd = (uint32_t)plan.blocks_per_cu * L.block_threads / 256u;
+	L.lds_bytes = (uint32_t)plan.lds_bytes;
+	L.n_cus = (uint32_t)n_cus;
+	L.sample_split = plan.split;
+	L.n_items = plan.P.n_items;
+	static const char *const feat_names[4] = {"rt::Feat<false, false, false, false>", "rt::Feat<true, true, false, false>",
+	                                          "rt::Feat<true, true, true, true>", "rt::FeatPair"};
+	// pick_render (rt_render.hip) folds these: naive never stages the sky, fine implies pruned
+	std::snprintf(L.kernel, sizeof L.kernel, "rt::render_kernel<%d, %s, %s, %s, %s%s>", (int)o->render_method, plan.prune ? "true" : "false",
+	              plan.fine ? "true" : "false", (plan.sky_lds && o->render_method == RT_METHOD_MIS) ? "true" : "false", feat_names[plan.feature_set],
+	              plan.xchg ? ", true" : ", false"); // the name rocprofv3 prints
+}
+
 extern "C" {
 
 int rt_scene_auto_sample_split(const rt_scene *s, const rt_render_opts *o, uint32_t *split)
@@ -1101,15 +1315,7 @@ static int render_device_multi_enqueue(rt_scene *head, const std::vector<rt_scen
 			return rc;
 		DevRenderParams P;
 		std::memset(&P, 0, sizeof P);
-		P.width = (uint32_t)o->width;
-		P.height = (uint32_t)o->height;
-		P.shard_index = m;
-		P.shard_count = n;
-		P.tile_w = g.tile_w;
-		P.tile_h = g.tile_h;
-		P.tiles_x = g.tiles_x;
-		P.tiles_y = g.tiles_y;
-		P.n_work = (uint32_t)g.n_work;
+		fill_tiling(P, &om, g);
 		HIP_TRY(launch_scatter_shard(stream, P, m == 0 ? head->d_shard : head->d_gather + offset[m], d_out_rgb));
 	}
 	if (d_rays_shot) { // SamplerProgress.rays_shot of the whole job
@@ -1167,204 +1373,25 @@ int rt_render_device(rt_scene *s, const rt_camera *camera, const rt_render_opts 
 		return RT_OK;
 	}
 
-	DevRenderParams P;
-	std::memset(&P, 0, sizeof P);
-	P.width = (uint32_t)o->width;
-	P.height = (uint32_t)o->height;
-	P.spp = (uint32_t)o->samples_per_pixel;
-	P.sample_begin_lo = (uint32_t)o->sample_begin;
-	P.sample_begin_hi = (uint32_t)(o->sample_begin >> 32);
-	P.seed_lo = (uint32_t)o->seed;
-	P.seed_hi = (uint32_t)(o->seed >> 32);
-	P.max_depth = o->max_depth;
-	P.rr_threshold = o->rr_threshold;
-	P.shard_index = o->shard_index;
-	P.shard_count = o->shard_count;
-	P.tile_w = g.tile_w;
-	P.tile_h = g.tile_h;
-	P.tiles_x = g.tiles_x;
-	P.tiles_y = g.tiles_y;
-	P.n_work = (uint32_t)g.n_work;
-	// sample_split 0 = automatic, on one device as on several (auto_sample_split: >= 64 work items per resident lane)
-	uint32_t split = o->sample_split;
-	if (split == 0u)
-		split = auto_sample_split(s->n_cus, o->width * o->height, o->samples_per_pixel, o->shard_count);
-	{ // u = (jitter + x) / (W - 1), v = (jitter + y) / (H - 1) by verified reciprocals (cached per divisor: rt_build.cpp)
-		float rw = 0.0f, rh = 0.0f;
-		const bool sized = o->width <= (1u << 24) && o->height <= (1u << 24);
-		const bool ok_w = sized && verified_reciprocal((float)(o->width - 1), &rw), ok_h = sized && verified_reciprocal((float)(o->height - 1), &rh);
-		const bool ok = ok_w && ok_h;
-		P.w1h1_ok = ok ? 1u : 0u;
-		P.inv_w1 = rw;
-		P.inv_h1 = rh;
-	}
-	P.tile_log2_w = 0xFFFFFFFFu;
-	if (g.tile_w * g.tile_h == 64u && (g.tile_w & (g.tile_w - 1u)) == 0u && o->width < 65536u && o->height < 65536u &&
-	    (split & (split - 1u)) == 0u && split <= 64u)
-		for (uint32_t lw = 0; lw < 7u; ++lw)
-			for (uint32_t ls = 0; ls < 7u; ++ls)
-				if ((1u << lw) == g.tile_w && (1u << ls) == split)
-					P.tile_log2_w = lw | (ls << 8);
-	if (split > o->samples_per_pixel)
-		return fail(RT_ERR_INVALID_ARGUMENT, "sample_split larger than samples_per_pixel");
-	if (g.n_work * split >= (1ull << 32))
-		return fail(RT_ERR_UNSUPPORTED, "pixels x sample_split exceeds 2^32 work items");
-	P.sample_split = split;
-	P.n_items = (uint32_t)(g.n_work * split);
+	RenderLaunchPlan plan;
+	rc = plan_render_launch(s, o, g, &plan);
+	if (rc != RT_OK)
+		return rc;
+	const DevRenderParams &P = plan.P;
 	float *render_target = d_out_rgb;
-	if (split > 1u) { // chunk means land in a scratch buffer; combine_chunks_kernel folds them into d_out_rgb
-		const size_t need = (size_t)g.n_work * split * 3;
+	if (plan.split > 1u) { // chunk means land in a scratch buffer; combine_chunks_kernel folds them into d_out_rgb
+		const size_t need = (size_t)g.n_work * plan.split * 3;
 		rc = grow_device_buffer(s->d_partial, s->partial_floats, need); // grows on first use only (not capturable into a graph on that call)
 		if (rc != RT_OK)
 			return rc;
 		render_target = s->d_partial;
 	}
-	P.shard_layout = o->output_layout == RT_LAYOUT_SHARD ? 1 : 0;
-
-	// traversal: exhaustive (the reference's own amount of work) for tiny trees where pruning cannot
-	// pay, t-pruned otherwise; both select the same winner (rt_intersect.h)
-	// and how finely the wave votes: measured crossovers on random sphere scenes (tests/probes/gpu_crossover_probe.py)
-	bool prune = s->traversal_mode == -1 ? s->dev.n_prims > kPruneAbove : s->traversal_mode == 1;
-	// the fine schedule walks the wide tree: scenes without one (non-finite bounds, a single leaf) stay coarse
-	const bool fine = s->dev.nodes4 != nullptr &&
-	                  (s->schedule_mode == -1 ? (prune && s->dev.n_prims > (s->dev.has_triangles ? kFineAboveTriangles : kFineAboveSpheres))
-	                                          : s->schedule_mode == 1);
-	if (fine)
-		prune = true;
-	P.prune = prune ? 1 : 0;
-
-	const bool samplable = (s->dev.sky.res_x | s->dev.sky.res_y) != 0u;
-	const size_t sky_bytes = samplable ? ((size_t)s->dev.sky.res_y * (s->dev.sky.res_x + 1u) + s->dev.sky.res_y + 1u) * 4 +
-	                                         (size_t)(s->dev.sky.res_y + 1u) * s->dev.sky.guide_k : 0;
-	// Sky CDF tables in LDS (next to the traversal stacks) or left in global memory: LDS only while
-	// it does not cost resident workgroups.  Tiny trees: 41 KB tables + 1-2 KB stacks still fit 3
-	// workgroups per CU, the register limit.  Deep trees: the stacks alone are tens of KB and the
-	// sky is a small share of the work, so residency (latency hiding for the node fetches) wins.
-	// Tiny scenes under the coarse schedule: the whole scene rides in LDS too.
-	const bool scene_lds = !fine && s->dev.blob_bytes != 0u && s->scene_lds_allowed;
-	P.scene_in_lds = scene_lds ? 1u : 0u;
-	bool sky_lds = false;
-	// RT_TUNE_EXCHANGE (rt_render.hip, XCHG).  Fine schedule: 512-thread workgroups whose waves trade whole lane states
-	// through two record pools behind the stacks; coarse MIS kernels: decided below, once the occupancy is known
-	// (feature set of THIS launch: 3 = FeatPair, built for the exhaustive coarse kernels without the exchange only)
-	const int feature_set =
-	    (s->feature_set == 0 && s->pair_tree && !s->feature_set_forced && !prune && !fine && s->exchange_mode != 1) ? 3 : s->feature_set;
-	bool xchg = s->exchange_mode == 1 && render_exchange_available(o->render_method, prune, fine, feature_set);
-	const bool xchg_fine = xchg && fine;
-	uint32_t block_threads = render_block_threads(feature_set, fine, xchg_fine);
-	const size_t fine_pool_bytes = xchg_fine ? render_exchange_fine_lds_bytes(block_threads / 64u) : 0;
-	// Traversal stacks: one LDS column per lane.  The worst case of a deep tree (three pending siblings per level of
-	// the wide tree) is far above what walks reach, and LDS sized for it would cost resident waves; under the fine
-	// schedule the LDS part is capped at the share a workgroup gets at the occupancy its register budget allows, the
-	// rest of the worst case lives in a global overflow area that is touched only if a walk really gets that deep.
-	// The coarse kernels keep a walk's WHOLE worst-case stack in LDS.  The wide tree's worst case (three pending siblings
-	// per level) is about 1.5 x the two-child tree's, and only pruned walks of regular rays descend it: an exhaustive
-	// launch needs the two-child depth only, and a pruned coarse launch whose wide worst case does not fit the LDS of a CU
-	// (a deep, skewed tree) walks the two-child tree for every ray instead of failing.
-	DevScene dev = s->dev; // what this launch sees
-	const bool walks_wide = prune && dev.nodes4 != nullptr && dev.narrow_only == 0u;
-	uint32_t stack_need = (fine || walks_wide) ? dev.stack_depth : s->stack_depth_narrow;
-	if (!fine && walks_wide &&
-	    render_lds_bytes(dev, false, scene_lds, render_block_threads(feature_set, false, false) / 64u, stack_need) > s->max_lds) {
-		dev.narrow_only = 1u;
-		stack_need = s->stack_depth_narrow;
+	if (P.stack_ovf_depth != 0u) { // grown on first use only (like the sample_split scratch: not capturable on that call)
+		const size_t need = (size_t)plan.n_blocks * plan.block_threads * P.stack_ovf_depth;
+		rc = grow_device_buffer(s->d_stack_ovf, s->stack_ovf_words, need);
+		if (rc != RT_OK)
+			return rc;
 	}
-	uint32_t stack_cap = stack_need;
-	if (fine) {
-		const uint32_t blocks_wanted = std::max(1u, render_waves_per_simd(feature_set, true) * 256u / block_threads);
-		const size_t share = s->max_lds / blocks_wanted;
-		const uint32_t fit = (uint32_t)((share > fine_pool_bytes ? share - fine_pool_bytes : 0) / ((block_threads / 64u) * 64u * 4u));
-		stack_cap = std::min(stack_cap, std::max(8u, fit));
-	}
-	if (fine && s->stack_cap_override != 0u) // (coarse kernels keep the whole stack in LDS and walk without capacity checks)
-		stack_cap = std::min(stack_need, s->stack_cap_override);
-	P.stack_cap = stack_cap;
-	P.stack_ovf_depth = stack_need - stack_cap;
-	// What one workgroup size gives: resident workgroups per CU without and -- where that does not cost any -- with the sky tables in LDS
-	const bool sky_lds_possible = samplable && o->render_method == RT_METHOD_MIS && sky_bytes <= 96 * 1024;
-	struct Sizing { uint32_t block; int blocks_per_cu; bool sky; size_t lds; };
-	auto size_launch = [&](uint32_t block, Sizing &z) -> hipError_t {
-		z.block = block;
-		z.sky = false;
-		z.blocks_per_cu = 0;
-		z.lds = render_lds_bytes(dev, false, scene_lds, block / 64u, stack_cap) + fine_pool_bytes;
-		if (z.lds > s->max_lds)
-			return hipSuccess; // (does not fit: blocks_per_cu stays 0)
-		hipError_t e = render_occupancy(o->render_method, prune, fine, false, feature_set, z.lds, &z.blocks_per_cu, xchg_fine, block);
-		if (e != hipSuccess)
-			return e;
-		if (sky_lds_possible) {
-			const size_t lds_with = render_lds_bytes(dev, true, scene_lds, block / 64u, stack_cap) + fine_pool_bytes;
-			int blocks_with = 0;
-			if (lds_with <= s->max_lds &&
-			    render_occupancy(o->render_method, prune, fine, true, feature_set, lds_with, &blocks_with, xchg_fine, block) == hipSuccess &&
-			    blocks_with >= z.blocks_per_cu && blocks_with >= 1) {
-				z.sky = true;
-				z.lds = lds_with;
-				z.blocks_per_cu = blocks_with;
-			}
-		}
-		return hipSuccess;
-	};
-	Sizing Z;
-	HIP_TRY(size_launch(block_threads, Z));
-	if (Z.lds > s->max_lds)
-		return fail(RT_ERR_UNSUPPORTED, "traversal stacks exceed the LDS of one CU");
-	// Coarse spheres-only kernels (FeatPair among them) are issue-bound and use 66 - 100 VGPRs: every further wave per SIMD the
-	// registers allow is worth about 2 % (rt_render.hip RT_PAIR_WAVES).  Three 512-thread workgroups do not fit the LDS with the
-	// sky tables, two of 768 threads do: try the larger workgroup too, keep what puts most waves on a CU, at equal waves what keeps
-	// the sky tables in LDS, at equal both the smaller workgroup.  Only multiples of 256 threads: a workgroup whose waves do not
-	// divide evenly over the four SIMDs is reported as resident twice by the occupancy query, but the second one is not placed
-	// once the fuller SIMDs are out of registers (640 x 2 at 93 VGPRs: 18.8 -> 23.3 ms, 896 x 2: no gain; profiles/r04v_small_ab.log).
-	if (!fine && !xchg) {
-		for (uint32_t cand = block_threads + 256u; cand <= render_max_block_threads(feature_set, fine, false); cand += 256u) {
-			Sizing C;
-			if (size_launch(cand, C) != hipSuccess || C.blocks_per_cu < 1)
-				continue;
-			const uint32_t waves_c = (uint32_t)C.blocks_per_cu * C.block, waves_z = (uint32_t)Z.blocks_per_cu * Z.block;
-			if (waves_c > waves_z || (waves_c == waves_z && C.sky && !Z.sky))
-				Z = C;
-		}
-		block_threads = Z.block;
-	}
-	size_t lds_bytes = Z.lds;
-	int blocks_per_cu = Z.blocks_per_cu;
-	sky_lds = Z.sky;
-	P.sky_in_lds = sky_lds ? 1u : 0u;
-	if (blocks_per_cu < 1)
-		return fail(RT_ERR_HIP, "render kernel does not fit on a CU");
-	// RT_TUNE_EXCHANGE (asked for by name, off by default): the workgroup's pool of parked path states sits behind the stacks
-	// (rt_render.hip, XCHG) and gets the LDS that is left at the occupancy the EXCHANGE kernel reaches by its registers -- it never
-	// costs the sky tables their place; it can cost a resident workgroup where that kernel needs more registers than the plain one
-	// (full feature set: 141 against 125 VGPRs)
-	P.xchg_slots = 0;
-	if (xchg && !fine) {
-		int blocks_plain = 0;
-		if (render_occupancy(o->render_method, prune, fine, sky_lds, feature_set, lds_bytes, &blocks_plain, true) != hipSuccess || blocks_plain < 1) {
-			xchg = false;
-		} else {
-			const int target = std::min(blocks_per_cu, blocks_plain);
-			const size_t share = s->max_lds / (size_t)target; // max_lds is the LDS of one CU
-			uint32_t slots = render_exchange_max_slots();
-			while (slots >= 16u && lds_bytes + render_exchange_lds_bytes(slots) > share)
-				slots -= 4u;
-			int blocks_x = 0;
-			if (slots >= 16u &&
-			    render_occupancy(o->render_method, prune, fine, sky_lds, feature_set, lds_bytes + render_exchange_lds_bytes(slots), &blocks_x, true) == hipSuccess &&
-			    blocks_x >= target) {
-				P.xchg_slots = slots;
-				lds_bytes += render_exchange_lds_bytes(slots);
-				blocks_per_cu = target;
-			} else {
-				xchg = false;
-			}
-		}
-	}
-	uint64_t n_blocks = (uint64_t)s->n_cus * (uint64_t)blocks_per_cu;
-	const uint64_t blocks_needed = ((uint64_t)P.n_items + block_threads - 1) / block_threads;
-	if (n_blocks > blocks_needed)
-		n_blocks = blocks_needed ? blocks_needed : 1;
-
 	{ // counters, and the parts of the output no lane will write (other shards' pixels, edge-tile padding)
 		size_t zero_floats = 0;
 		if (o->output_layout == RT_LAYOUT_FRAME && o->shard_count > 1)
@@ -1373,49 +1400,18 @@ int rt_render_device(rt_scene *s, const rt_camera *camera, const rt_render_opts 
 			zero_floats = (size_t)(g.n_work * 3);
 		HIP_TRY(launch_reset(stream, s->d_work_counter, reinterpret_cast<unsigned long long *>(d_rays_shot), d_out_rgb, zero_floats));
 	}
-
+	fill_launch_info(plan, o, s->n_cus, &s->last_launch);
 	DevCamera cam;
 	std::memcpy(cam.origin, camera->origin, 12);
 	std::memcpy(cam.lower_left, camera->lower_left, 12);
 	std::memcpy(cam.horizontal, camera->horizontal, 12);
 	std::memcpy(cam.vertical, camera->vertical, 12);
-
-	{ // what is about to run, for rt_last_launch_info
-		rt_launch_info &L = s->last_launch;
-		std::memset(&L, 0, sizeof L);
-		L.method = o->render_method;
-		L.pruned = prune ? 1 : 0;
-		L.fine = fine ? 1 : 0;
-		L.sky_in_lds = sky_lds ? 1 : 0;
-		L.scene_in_lds = scene_lds ? 1 : 0;
-		L.feature_set = feature_set;
-		L.block_threads = block_threads;
-		L.n_blocks = (uint32_t)n_blocks;
-		L.blocks_per_cu = (uint32_t)blocks_per_cu;
-		L.waves_per_simd = (uint32_t)blocks_per_cu * L.block_threads / 256u;
-		L.lds_bytes = (uint32_t)lds_bytes;
-		L.n_cus = (uint32_t)s->n_cus;
-		L.sample_split = split;
-		L.n_items = P.n_items;
-		static const char *const feat_names[4] = {"rt::Feat<false, false, false, false>", "rt::Feat<true, true, false, false>",
-		                                          "rt::Feat<true, true, true, true>", "rt::FeatPair"};
-		// pick_render (rt_render.hip) folds these: naive never stages the sky, fine implies pruned
-		std::snprintf(L.kernel, sizeof L.kernel, "rt::render_kernel<%d, %s, %s, %s, %s%s>", (int)o->render_method, prune ? "true" : "false",
-		              fine ? "true" : "false", (sky_lds && o->render_method == RT_METHOD_MIS) ? "true" : "false", feat_names[feature_set],
-		              xchg ? ", true" : ", false"); // the name rocprofv3 prints
-	}
-	if (P.stack_ovf_depth != 0u) { // grown on first use only (like the sample_split scratch: not capturable on that call)
-		const size_t need = (size_t)n_blocks * block_threads * P.stack_ovf_depth;
-		rc = grow_device_buffer(s->d_stack_ovf, s->stack_ovf_words, need);
-		if (rc != RT_OK)
-			return rc;
-	}
 	HIP_TRY(hipEventRecord(s->ev_start, stream));
-	HIP_TRY(launch_render(o->render_method, prune, fine, sky_lds, feature_set, (uint32_t)n_blocks, lds_bytes, stream, dev, cam, P, render_target,
-	                      reinterpret_cast<unsigned long long *>(d_rays_shot), s->d_work_counter, s->d_stack_ovf, xchg,
-	                      feature_set == 3 ? &s->pair : nullptr, block_threads));
+	HIP_TRY(launch_render(o->render_method, plan.prune, plan.fine, plan.sky_lds, plan.feature_set, plan.n_blocks, plan.lds_bytes, stream, plan.dev, cam, P,
+	                      render_target, reinterpret_cast<unsigned long long *>(d_rays_shot), s->d_work_counter, s->d_stack_ovf, plan.xchg,
+	                      plan.feature_set == 3 ? &s->pair : nullptr, plan.block_threads));
 	HIP_TRY(hipEventRecord(s->ev_stop, stream));
-	if (split > 1u)
+	if (plan.split > 1u)
 		HIP_TRY(launch_combine(stream, P, s->d_partial, d_out_rgb));
 	s->timed = true;
 	s->n_launches = 1;
@@ -1889,6 +1885,10 @@ static int check_common(rt_scene *s, const rt_ray_desc *rays, const uint64_t *ob
 		for (uint64_t i = 0; i < n; ++i)
 			if (object_index[i] >= s->dev.n_prims)
 				return fail(RT_ERR_INVALID_ARGUMENT, "object index out of range");
+	bool prune = false;
+	DevScene dev;
+	if (int rc = four_wave_traversal(s, &prune, &dev); rc != RT_OK) // (rt_api_internal.h)
+		return rc;
 	HIP_TRY(hipSetDevice(s->device));
 	void *d_rays = nullptr, *d_out = nullptr, *d_idx = nullptr;
 	HIP_TRY(hipMalloc(&d_rays, n * sizeof(rt_ray_desc)));
@@ -1899,16 +1899,6 @@ static int check_common(rt_scene *s, const rt_ray_desc *rays, const uint64_t *ob
 		e = hipMemcpyAsync(d_rays, rays, n * sizeof(rt_ray_desc), hipMemcpyHostToDevice, s->stream);
 	if (e == hipSuccess && object_index)
 		e = hipMemcpyAsync(d_idx, object_index, n * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream);
-	const bool prune = s->traversal_mode == -1 ? s->dev.n_prims > kPruneAbove : s->traversal_mode == 1;
-	// the batch kernels keep the whole worst-case stack of four waves in LDS: the wide tree's only where it is walked and
-	// fits, the two-child tree's (and the two-child walk for every ray) otherwise -- as rt_render_device does
-	DevScene dev = s->dev;
-	const bool walks_wide = prune && dev.nodes4 != nullptr && dev.narrow_only == 0u;
-	if (!walks_wide || (size_t)4 * dev.stack_depth * 64u * sizeof(uint32_t) > s->max_lds) {
-		if (walks_wide)
-			dev.narrow_only = 1u;
-		dev.stack_depth = s->stack_depth_narrow;
-	}
 	if (e == hipSuccess)
 		e = object_index ? launch_check_hit_index(prune, s->stream, dev, d_rays, d_idx, n, d_out)
 		                 : launch_check_hit(prune, s->stream, dev, d_rays, n, d_out);

@@ -105,6 +105,34 @@ struct rt_scene {
 	bool display_has_state = false;        // false: the next rt_display starts from a zero state
 };
 
+// ---- traversal policy: which walk, and for the four-wave kernels which tree and how much stack ----
+// the walk every launch on this scene takes (rt_scene_set_traversal / RT_TUNE_TRAVERSAL, else by size); the fine schedule of
+// the render kernels additionally implies the pruned walk (plan_render_launch, rt_api.cpp)
+inline bool scene_prunes(const rt_scene *s)
+{
+	return s->traversal_mode == -1 ? s->dev.n_prims > kPruneAbove : s->traversal_mode == 1;
+}
+
+// The batch hit queries and both AOV passes keep the whole worst-case stack of their four waves in LDS
+// (four_wave_stack_lds_bytes, rt_types.h): the wide tree's only where it is walked and fits the LDS of a CU, the two-child
+// tree's (and the two-child walk for every ray: narrow_only) otherwise -- the fallback the coarse render kernels take.  *dev is
+// the scene as such a launch sees it.  A scene whose two-child stack does not fit either is refused; no test builds one: a
+// two-child tree deeper than 160 levels cannot be made from finite float coordinates with the generators of tests/scenes.py.
+inline int four_wave_traversal(const rt_scene *s, bool *prune, rt::DevScene *dev)
+{
+	*prune = scene_prunes(s);
+	*dev = s->dev;
+	const bool walks_wide = *prune && dev->nodes4 != nullptr && dev->narrow_only == 0u;
+	if (!walks_wide || rt::four_wave_stack_lds_bytes(*dev) > s->max_lds) {
+		if (walks_wide)
+			dev->narrow_only = 1u;
+		dev->stack_depth = s->stack_depth_narrow;
+	}
+	if (rt::four_wave_stack_lds_bytes(*dev) > s->max_lds)
+		return fail(RT_ERR_UNSUPPORTED, "traversal stacks exceed the LDS of one CU");
+	return RT_OK;
+}
+
 template <class T> static int upload(rt_scene *s, const T *src, size_t count, const T **dst)
 {
 	void *p = nullptr;

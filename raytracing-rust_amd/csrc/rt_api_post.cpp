@@ -42,26 +42,6 @@ static int aov_check(const rt_scene *s, const rt_camera *camera, const rt_render
 	return need_device(s);
 }
 
-// traversal as rt_render / rt_check_hit choose it; the whole worst-case stack of the workgroup in LDS: the wide tree's only
-// where it is walked and fits, the two-child tree's (and the two-child walk for every ray) otherwise.  Both AOV kernels keep the
-// same stacks (aov_lds_bytes == aov_chain_lds_bytes).
-static int aov_traversal(const rt_scene *s, bool *prune_out, DevScene *dev_out)
-{
-	const bool prune = s->traversal_mode == -1 ? s->dev.n_prims > kPruneAbove : s->traversal_mode == 1;
-	DevScene dev = s->dev;
-	const bool walks_wide = prune && dev.nodes4 != nullptr && dev.narrow_only == 0u;
-	if (!walks_wide || aov_lds_bytes(dev) > s->max_lds) {
-		if (walks_wide)
-			dev.narrow_only = 1u;
-		dev.stack_depth = s->stack_depth_narrow;
-	}
-	if (aov_lds_bytes(dev) > s->max_lds)
-		return fail(RT_ERR_UNSUPPORTED, "traversal stacks exceed the LDS of one CU");
-	*prune_out = prune;
-	*dev_out = dev;
-	return RT_OK;
-}
-
 // the launch parameters both AOV kernels share
 static DevAovParams aov_params(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *d_out, uint32_t mask)
 {
@@ -105,7 +85,7 @@ int rt_render_aov_device(rt_scene *s, const rt_camera *camera, const rt_render_o
 		return fail(RT_ERR_UNSUPPORTED, "primitive IDs need fewer than 2^32 - 1 primitives");
 	bool prune = false;
 	DevScene dev;
-	rc = aov_traversal(s, &prune, &dev);
+	rc = four_wave_traversal(s, &prune, &dev); // (rt_api_internal.h)
 	if (rc != RT_OK)
 		return rc;
 	const DevAovParams P = aov_params(s, camera, o, d_out, mask);
@@ -181,7 +161,7 @@ int rt_render_aov_chain_device(rt_scene *s, const rt_camera *camera, const rt_re
 		return fail(RT_ERR_UNSUPPORTED, "primitive IDs need fewer than 2^32 - 1 primitives");
 	bool prune = false;
 	DevScene dev;
-	rc = aov_traversal(s, &prune, &dev);
+	rc = four_wave_traversal(s, &prune, &dev); // (rt_api_internal.h)
 	if (rc != RT_OK)
 		return rc;
 	DevAovChainParams P;

@@ -380,8 +380,8 @@ template <class F> __device__ __forceinline__ void make_sky_hit_lean(const DevSc
 //   ref <  0 (bit 31 set)   leaf: bits 26-30 primitive count (1..31), bits 0-25 first slot;
 //                           count field 0 = index into DevScene::big_leaves (first, count)
 // Per-lane stack in LDS: entry e of lane l lives at stack[e * 64 + l]; `stk` already points at
-// the lane's column, so consecutive lanes hit consecutive banks (conflict-free ds_read/ds_write_b32).
-constexpr int kStackStride = 64;
+// the lane's column, so consecutive lanes hit consecutive banks (conflict-free ds_read/ds_write_b32): kStackStride (rt_types.h,
+// where the host sizes the LDS by it).
 // Where a lane's stack lives: the first `cap` entries in its LDS column, the rest (rare: the host sizes `cap` from the
 // occupancy it wants, the worst case of a wide tree is far above what walks reach) in a global overflow area
 // [thread][ovf_depth].  All fields are wave-uniform.  The overflow address is recomputed from the LDS column pointer when

@@ -36,6 +36,7 @@
 // staged once per workgroup into LDS next to the per-lane traversal stacks.  HBM write traffic is
 // 12 bytes per pixel for the whole render.  No MFMA: nothing here is a dense contraction.
 #include "rt_shade.h"
+#include "rt_render.h"
 
 namespace rt {
 
@@ -2310,7 +2311,7 @@ hipError_t launch_render(int method, bool prune, bool fine, bool sky_lds, int fe
 
 hipError_t launch_check_hit(bool prune, hipStream_t stream, const DevScene &S, const void *rays, uint64_t n, void *out)
 {
-	const size_t lds_bytes = (size_t)4 * S.stack_depth * kStackStride * sizeof(uint32_t);
+	const size_t lds_bytes = four_wave_stack_lds_bytes(S);
 	const uint32_t blocks = (uint32_t)((n + 255) / 256);
 	// deep trees: more than the default 64 KB of dynamic LDS per workgroup (the whole worst-case stack lives in LDS here)
 	hipError_t e = hipFuncSetAttribute(prune ? reinterpret_cast<const void *>(check_hit_kernel<true>) : reinterpret_cast<const void *>(check_hit_kernel<false>),
@@ -2329,7 +2330,7 @@ hipError_t launch_check_hit(bool prune, hipStream_t stream, const DevScene &S, c
 hipError_t launch_check_hit_index(bool prune, hipStream_t stream, const DevScene &S, const void *rays, const void *object_index,
                                   uint64_t n, void *out)
 {
-	const size_t lds_bytes = (size_t)4 * S.stack_depth * kStackStride * sizeof(uint32_t);
+	const size_t lds_bytes = four_wave_stack_lds_bytes(S);
 	const uint32_t blocks = (uint32_t)((n + 255) / 256);
 	hipError_t e = hipFuncSetAttribute(prune ? reinterpret_cast<const void *>(check_hit_index_kernel<true>)
 	                                         : reinterpret_cast<const void *>(check_hit_index_kernel<false>),
