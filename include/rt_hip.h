@@ -468,7 +468,8 @@ int rt_check_hit_index(rt_scene *scene, const rt_ray_desc *rays, const uint64_t 
  * order, from +0) / (float)hits, or 0 when no pass hit.
  * IDs come from pass sample_begin alone: primitive = index in rt_scene_desc.primitives (not BVH order), material = the caller's
  * material index; both UINT32_MAX on a miss.  A scene of >= 2^32 - 1 primitives returns RT_ERR_UNSUPPORTED when `primitive`
- * is asked for.  The slot -> index table is uploaded with the scene (4 bytes per primitive).
+ * is asked for.  The slot -> index table is uploaded with the scene (4 bytes per primitive).  (One pass, so aliased: the IDs of
+ * ALL passes with their coverage fractions are rt_render_matte's, below.)
  * Options: render_method, max_depth, rr_threshold and sample_split are ignored; output_layout must be RT_LAYOUT_FRAME and
  * shard_count 1 (else RT_ERR_UNSUPPORTED); width and height >= 2.  The traversal follows the scene's mode (rt_scene_set_traversal;
  * every mode gives the same bytes).  A host-only scene returns RT_ERR_NO_DEVICE; a multi-device head (rt_scene_create_multi)
@@ -539,6 +540,69 @@ int rt_render_aov_chain(rt_scene *scene, const rt_camera *camera, const rt_rende
                         const rt_aov_chain_buffers *host_out);
 int rt_render_aov_chain_device(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_aov_chain_opts *chain,
                                const rt_aov_chain_buffers *device_out, void *hip_stream);
+
+/* ---- Anti-aliased ID mattes (csrc/rt_matte.hip): per pixel the few most-covering primitive or material IDs over ALL passes with
+ * their coverage fractions -- the Cryptomatte form (Friedman and Jones, SIGGRAPH 2015 posters) without its file-format half -- and
+ * the matte of a selection of IDs.  Where the `primitive` / `material` channels of rt_render_aov are one sample of a pixel, these
+ * layers are all of them: a matte cut from them has the anti-aliased edges of the beauty frame, a pick at a silhouette sees every
+ * object in the pixel with its share.  Counting in integers throughout; the only rounding is one IEEE division per value written.
+ *
+ * Layers (rt_render_matte, rt_render_matte_device).  The camera rays are exactly those of rt_render_aov for passes [sample_begin,
+ * sample_begin + samples_per_pixel); no random draw is taken beyond the jitter.  The ID of a pass is the value rt_render_aov
+ * would write into its `primitive` (id_kind RT_MATTE_ID_PRIMITIVE) or `material` (RT_MATTE_ID_MATERIAL) channel for that pass
+ * alone: the index in rt_scene_desc.primitives or the caller's material index, UINT32_MAX on a miss -- the sky is an ID like any
+ * other, so that a pixel's counts add up to samples_per_pixel.
+ *   Table: per pixel RT_MATTE_SLOTS = 8 slots (id, count), all free at first.  Passes in pass order: an ID that is in the table has
+ *   its count raised by one; otherwise it takes the FIRST free slot with count 1; otherwise (table full) `overflow` goes up by one --
+ *   an ID that arrives after the table is full is never counted, even if it recurs.
+ *   Ranking: the occupied slots by count descending, then by ID ascending (the sky last among equals).
+ *   Layer l < K of pixel q = y*w + x:  ids[l*w*h + q] = the ID of rank l,  coverage[l*w*h + q] = (float)count / (float)samples_per_pixel.
+ *   A layer beyond the occupied slots receives ID UINT32_MAX and coverage +0: an empty layer and a sky layer differ in coverage only.
+ *   residual[q] = (float)(samples_per_pixel - (the counts of the K layers written)) / (float)samples_per_pixel: what the layers leave
+ *   out -- the ranks beyond K, and the overflow.
+ * With a power-of-two samples_per_pixel every value is exact and the coverages of a pixel and its residual add up to 1.0f.
+ * Options: id_kind (default MATERIAL); layers = K in 1..8 (default 4); `reserved` must be zero (rt_matte_opts_default zeroes it).
+ * RT_ERR_INVALID_ARGUMENT for a NULL argument, NULL `ids` or `coverage` (`residual` may be NULL: not produced), layers outside 1..8,
+ * an id_kind out of range, a nonzero `reserved` word, and two output buffers that overlap.  Everything else -- options of
+ * rt_render_opts ignored, RT_LAYOUT_FRAME and shard_count 1, width and height >= 2, traversal modes (the same bytes in each),
+ * host-only scenes, multi-device heads (devices[0] alone) and "no side effects" -- is as for rt_render_aov; a primitive-kind
+ * request on a scene of >= 2^32 - 1 primitives returns RT_ERR_UNSUPPORTED.
+ * rt_render_matte: HOST buffers, blocking; its device copies live on the scene (shared with rt_denoise; grown for larger frames
+ * only).  rt_render_matte_device: DEVICE buffers on the scene's GPU, asynchronous on hip_stream; it allocates nothing and keeps no
+ * state, so it can be captured into a graph from its first call.
+ *
+ * Extraction (rt_matte_extract, rt_matte_extract_device): the matte of the IDs in a selection, from K layers of a width x height
+ * frame.  Per pixel: m = +0; for l = 0 .. K-1 in order, m = m + coverage_l where coverage_l > 0 and ids_l is in the selection;
+ * out = fminf(m, 1.0f).  Empty layers (coverage +0) match nothing, so selecting UINT32_MAX selects the sky alone.  `residual` is not
+ * read.  n_ids = 0 (ids may then be NULL) gives an all-zero matte; n_ids > 2^20 returns RT_ERR_UNSUPPORTED.
+ * Checks (the device last): RT_ERR_INVALID_ARGUMENT for a NULL scene, layers struct, `ids`, `coverage` or out, a NULL selection with
+ * n_ids > 0, width or height 0, layers outside 1..8, and an out that overlaps the layers or the selection; RT_ERR_UNSUPPORTED for
+ * more than 2^31 pixels; RT_ERR_NO_DEVICE for a host-only scene.  A multi-device head runs on devices[0].  No side effects, as above.
+ * rt_matte_extract: HOST buffers, blocking; the selection in any order, duplicates allowed (a sorted copy is made).
+ * rt_matte_extract_device: DEVICE buffers, asynchronous on hip_stream, allocates nothing, keeps no state (graph-capturable from its
+ * first call); d_sorted_ids must be ASCENDING (duplicates allowed).  That is not verified: an unsorted list gives unspecified matte
+ * values, but no access out of bounds -- the search is bounded by n_ids.  Cost: DESIGN.md section 15. */
+#define RT_MATTE_SLOTS 8u
+typedef enum { RT_MATTE_ID_PRIMITIVE = 0, RT_MATTE_ID_MATERIAL = 1 } rt_matte_id_kind;
+typedef struct rt_matte_opts {
+	int32_t id_kind; /* rt_matte_id_kind, default MATERIAL */
+	uint32_t layers; /* K, 1..8, default 4 */
+	uint32_t reserved[6];
+} rt_matte_opts;
+typedef struct rt_matte_buffers {
+	uint32_t *ids;   /* K*w*h, layer-major */
+	float *coverage; /* K*w*h */
+	float *residual; /* w*h or NULL */
+} rt_matte_buffers;
+int rt_matte_opts_default(rt_matte_opts *out);
+int rt_render_matte(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_matte_opts *matte,
+                    const rt_matte_buffers *host_out);
+int rt_render_matte_device(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_matte_opts *matte,
+                           const rt_matte_buffers *device_out, void *hip_stream);
+int rt_matte_extract(rt_scene *scene, const rt_matte_buffers *host_layers, uint32_t width, uint32_t height, uint32_t layers,
+                     const uint32_t *ids, uint64_t n_ids, float *host_out);
+int rt_matte_extract_device(rt_scene *scene, const rt_matte_buffers *device_layers, uint32_t width, uint32_t height, uint32_t layers,
+                            const uint32_t *d_sorted_ids, uint64_t n_ids, float *d_out, void *hip_stream);
 
 /* ---- AOV-guided edge-aware A-Trous denoiser (csrc/rt_denoise.hip): the spatial part of SVGF (Dammertz et al. HPG 2010, Schied et
  * al. HPG 2017) on albedo-demodulated radiance.  W x H, FRAME layout, row-major, y down, f32 throughout.  Per pixel p:

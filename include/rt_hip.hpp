@@ -368,6 +368,53 @@ inline AovChainBuffers render_aov_chain(const RenderOptions &o, const SimpleCame
 	return a;
 }
 
+// Anti-aliased ID mattes (semantics: rt_hip.h rt_matte_opts): the `layers` most-covering primitive or material IDs of every pixel
+// over ALL passes with their coverage fractions, layer-major, and what they leave out; then the matte of a selection of IDs.
+struct MatteOptions {
+	rt_matte_id_kind id_kind = RT_MATTE_ID_MATERIAL;
+	uint32_t layers = 4; // 1..RT_MATTE_SLOTS
+};
+struct MatteLayers {
+	uint32_t width = 0, height = 0, layers = 0;
+	std::vector<uint32_t> ids;   // layers*w*h; UINT32_MAX: the sky (coverage > 0) or an empty layer (coverage 0)
+	std::vector<float> coverage; // layers*w*h
+	std::vector<float> residual; // w*h
+};
+inline MatteLayers render_matte(const RenderOptions &o, const SimpleCamera &camera, const Bvh &bvh, const MatteOptions &m = MatteOptions(),
+                                uint64_t seed = 1, uint64_t sample_begin = 0)
+{
+	rt_render_opts opts;
+	rt_render_opts_default(&opts);
+	opts.width = o.width;
+	opts.height = o.height;
+	opts.samples_per_pixel = o.samples_per_pixel;
+	opts.sample_begin = sample_begin;
+	opts.seed = seed;
+	rt_matte_opts mopts;
+	check(rt_matte_opts_default(&mopts));
+	mopts.id_kind = (int32_t)m.id_kind;
+	mopts.layers = m.layers;
+	const size_t n = (size_t)o.width * o.height, k = m.layers <= RT_MATTE_SLOTS ? m.layers : 0;
+	MatteLayers r;
+	r.width = (uint32_t)o.width;
+	r.height = (uint32_t)o.height;
+	r.layers = m.layers;
+	r.ids.resize(k * n);
+	r.coverage.resize(k * n);
+	r.residual.resize(n);
+	const rt_matte_buffers b = {r.ids.data(), r.coverage.data(), r.residual.data()};
+	check(rt_render_matte(bvh.raw(), &camera.raw(), &opts, &mopts, &b));
+	return r;
+}
+// the matte (w*h, in [0, 1]) of the IDs in `selection`: any order, duplicates allowed; UINT32_MAX selects the sky
+inline std::vector<float> matte_extract(const Bvh &bvh, const MatteLayers &layers, const std::vector<uint32_t> &selection)
+{
+	std::vector<float> out((size_t)layers.width * layers.height);
+	const rt_matte_buffers b = {const_cast<uint32_t *>(layers.ids.data()), const_cast<float *>(layers.coverage.data()), nullptr};
+	check(rt_matte_extract(bvh.raw(), &b, layers.width, layers.height, layers.layers, selection.data(), selection.size(), out.data()));
+	return out;
+}
+
 // The A-Trous denoiser of rt_hip.h (rt_denoise_opts): the options a caller sets; defaults as rt_denoise_opts_default.
 struct DenoiseOptions {
 	uint32_t iterations = 5;

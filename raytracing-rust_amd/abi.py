@@ -234,6 +234,32 @@ AOV_CHAIN_CHANNELS = AOV_CHANNELS + ("bounces",)
 AOV_CHAIN_MAX_CHAIN = 64
 
 
+# anti-aliased ID mattes (rt_render_matte, rt_matte_extract)
+RT_MATTE_SLOTS = 8  # (id, count) slots per pixel, and the most layers
+RT_MATTE_ID_PRIMITIVE, RT_MATTE_ID_MATERIAL = range(2)  # rt_matte_id_kind
+MATTE_ID_KINDS = {"primitive": RT_MATTE_ID_PRIMITIVE, "material": RT_MATTE_ID_MATERIAL}
+MATTE_MAX_IDS = 1 << 20  # largest selection rt_matte_extract takes
+
+
+class MatteOpts(C.Structure):  # rt_matte_opts
+    _fields_ = [
+        ("id_kind", C.c_int32),
+        ("layers", C.c_uint32),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+
+class MatteBuffers(C.Structure):  # rt_matte_buffers
+    _fields_ = [
+        ("ids", C.POINTER(C.c_uint32)),
+        ("coverage", C.POINTER(C.c_float)),
+        ("residual", C.POINTER(C.c_float)),
+    ]
+
+
+MATTE_BUFFERS = ("ids", "coverage", "residual")
+
+
 class DenoiseOpts(C.Structure):  # rt_denoise_opts
     _fields_ = [
         ("width", C.c_uint32),
@@ -368,6 +394,8 @@ EXPECTED_SIZES = {
     "rt_aov_buffers": (AovBuffers, 48),
     "rt_aov_chain_opts": (AovChainOpts, 32),
     "rt_aov_chain_buffers": (AovChainBuffers, 56),
+    "rt_matte_opts": (MatteOpts, 32),
+    "rt_matte_buffers": (MatteBuffers, 24),
     "rt_denoise_opts": (DenoiseOpts, 48),
     "rt_denoise_inputs": (DenoiseInputs, 40),
     "rt_temporal_opts": (TemporalOpts, 96),
@@ -423,6 +451,11 @@ EXPORTED_SYMBOLS = [
     "rt_aov_chain_opts_default",
     "rt_render_aov_chain",
     "rt_render_aov_chain_device",
+    "rt_matte_opts_default",
+    "rt_render_matte",
+    "rt_render_matte_device",
+    "rt_matte_extract",
+    "rt_matte_extract_device",
     "rt_denoise_opts_default",
     "rt_denoise_workspace_bytes",
     "rt_denoise",
@@ -451,6 +484,13 @@ def default_aov_chain_opts(max_chain=8, fuzz_limit=0.0):
     """rt_aov_chain_opts_default (include/rt_hip.h)."""
     o = AovChainOpts()
     o.max_chain, o.fuzz_limit = max_chain, fuzz_limit
+    return o
+
+
+def default_matte_opts(id_kind=RT_MATTE_ID_MATERIAL, layers=4):
+    """rt_matte_opts_default (include/rt_hip.h)."""
+    o = MatteOpts()
+    o.id_kind, o.layers = id_kind, layers
     return o
 
 

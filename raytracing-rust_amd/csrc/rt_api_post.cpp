@@ -1,10 +1,11 @@
 // rt_api_post.cpp -- the host side of the post-processing stages of librt_hip.so (include/rt_hip.h): first-hit and specular-chain
-// AOV buffers, the A-Trous denoiser, temporal accumulation, the display stage and AOV-guided upscaling.  Each stage has its kernels in a file of
-// its own (rt_aov.hip, rt_aov_chain.hip, rt_denoise.hip, rt_temporal.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
+// AOV buffers, ID mattes, the A-Trous denoiser, temporal accumulation, the display stage and AOV-guided upscaling.  Each stage has its kernels in a file of
+// its own (rt_aov.hip, rt_aov_chain.hip, rt_matte.hip, rt_denoise.hip, rt_temporal.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
 // and the blocking wrappers that stage host buffers through scene-owned device memory (Staging, rt_api_internal.h).
 // Every check function ends with the device (need_device), so that a host-only scene reports bad arguments as such.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -12,6 +13,7 @@
 #include "rt_api_internal.h"
 #include "rt_aov.h"
 #include "rt_aov_chain.h"
+#include "rt_matte.h"
 #include "rt_denoise.h"
 #include "rt_temporal.h"
 #include "rt_display.h"
@@ -20,15 +22,9 @@
 using namespace rt;
 
 // ---- first-hit AOV buffers (rt_aov.hip) ----
-// argument checks of both entry points, the device last (so that a host-only scene reports bad arguments as such)
-static int aov_check(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *b, uint32_t *mask)
+// what every pass over the camera rays asks of its render options (both AOV passes and the ID-matte layers)
+static int aov_opts_check(const rt_render_opts *o)
 {
-	if (!s || !camera || !o || !b)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	*mask = (b->albedo ? kAovAlbedo : 0u) | (b->normal ? kAovNormal : 0u) | (b->depth ? kAovDepth : 0u) |
-	        (b->coverage ? kAovCoverage : 0u) | (b->primitive ? kAovPrimitive : 0u) | (b->material ? kAovMaterial : 0u);
-	if (*mask == 0u)
-		return fail(RT_ERR_INVALID_ARGUMENT, "rt_aov_buffers: every channel is NULL");
 	if (int rc = frame_sides("", o->width, o->height, 2); rc != RT_OK)
 		return rc;
 	if (o->width * o->height >= (1ull << 31)) // (this pass alone refuses exactly 2^31 pixels too)
@@ -39,6 +35,20 @@ static int aov_check(const rt_scene *s, const rt_camera *camera, const rt_render
 		return fail(RT_ERR_UNSUPPORTED, "AOV buffers are produced in RT_LAYOUT_FRAME only");
 	if (o->shard_count != 1)
 		return fail(RT_ERR_UNSUPPORTED, "AOV buffers are produced for the whole frame only (shard_count 1)");
+	return RT_OK;
+}
+
+// argument checks of both entry points, the device last (so that a host-only scene reports bad arguments as such)
+static int aov_check(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *b, uint32_t *mask)
+{
+	if (!s || !camera || !o || !b)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	*mask = (b->albedo ? kAovAlbedo : 0u) | (b->normal ? kAovNormal : 0u) | (b->depth ? kAovDepth : 0u) |
+	        (b->coverage ? kAovCoverage : 0u) | (b->primitive ? kAovPrimitive : 0u) | (b->material ? kAovMaterial : 0u);
+	if (*mask == 0u)
+		return fail(RT_ERR_INVALID_ARGUMENT, "rt_aov_buffers: every channel is NULL");
+	if (int rc = aov_opts_check(o); rc != RT_OK)
+		return rc;
 	return need_device(s);
 }
 
@@ -197,6 +207,171 @@ int rt_render_aov_chain(rt_scene *s, const rt_camera *camera, const rt_render_op
 	rc = st.finish("render_aov_chain");
 	(void)hipFree(d);
 	return rc;
+}
+
+} // extern "C"
+
+// ---- anti-aliased ID mattes (rt_matte.hip) ----
+// argument checks of rt_render_matte(_device): the matte's own, then those of the first-hit pass, the device last
+static int matte_check(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_matte_opts *m, const rt_matte_buffers *b)
+{
+	if (!s || !camera || !o || !m || !b)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (!b->ids || !b->coverage)
+		return fail(RT_ERR_INVALID_ARGUMENT, "matte: ids and coverage must not be NULL");
+	if (m->layers < 1 || m->layers > kMatteSlots)
+		return fail(RT_ERR_INVALID_ARGUMENT, "matte: layers must be in 1..8");
+	if (m->id_kind != RT_MATTE_ID_PRIMITIVE && m->id_kind != RT_MATTE_ID_MATERIAL)
+		return fail(RT_ERR_INVALID_ARGUMENT, "matte: unknown id_kind");
+	for (uint32_t r : m->reserved)
+		if (r != 0u)
+			return fail(RT_ERR_INVALID_ARGUMENT, "matte: reserved must be zero");
+	int rc = aov_opts_check(o);
+	if (rc != RT_OK)
+		return rc;
+	const uint64_t n = o->width * o->height;
+	const void *buf[3] = {b->ids, b->coverage, b->residual};
+	const uint64_t bytes[3] = {4 * m->layers * n, 4 * m->layers * n, 4 * n};
+	rc = check_disjoint("matte: two output buffers overlap", buf, bytes, 3, 3);
+	return rc == RT_OK ? need_device(s) : rc;
+}
+
+// argument checks of rt_matte_extract(_device), the device last
+static int matte_extract_check(const rt_scene *s, const rt_matte_buffers *b, uint64_t w, uint64_t h, uint32_t layers, const uint32_t *ids,
+                               uint64_t n_ids, const float *out)
+{
+	if (!s || !b)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (!b->ids || !b->coverage || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "matte_extract: ids, coverage and out must not be NULL");
+	if (n_ids != 0 && !ids)
+		return fail(RT_ERR_INVALID_ARGUMENT, "matte_extract: a NULL selection with n_ids > 0");
+	if (int rc = frame_sides("matte_extract: ", w, h, 1); rc != RT_OK)
+		return rc;
+	if (layers < 1 || layers > kMatteSlots)
+		return fail(RT_ERR_INVALID_ARGUMENT, "matte_extract: layers must be in 1..8");
+	if (n_ids > kMatteMaxIds)
+		return fail(RT_ERR_UNSUPPORTED, "matte_extract: more than 2^20 selected IDs");
+	uint64_t n = 0;
+	int rc = frame_pixels("matte_extract: ", w, h, 1, &n);
+	if (rc != RT_OK)
+		return rc;
+	const void *buf[4] = {out, b->ids, b->coverage, ids};
+	const uint64_t bytes[4] = {4 * n, 4 * layers * n, 4 * layers * n, 4 * n_ids};
+	rc = check_disjoint("matte_extract: out overlaps the layers or the selection", buf, bytes, 1, 4);
+	return rc == RT_OK ? need_device(s) : rc;
+}
+
+extern "C" {
+
+int rt_matte_opts_default(rt_matte_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	out->id_kind = RT_MATTE_ID_MATERIAL;
+	out->layers = 4;
+	return RT_OK;
+}
+
+int rt_render_matte_device(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_matte_opts *m,
+                           const rt_matte_buffers *d_out, void *hip_stream)
+{
+	int rc = matte_check(s, camera, o, m, d_out);
+	if (rc != RT_OK)
+		return rc;
+	// a multi-device head is an ordinary scene on devices[0]: the pass runs there alone
+	HIP_TRY(hipSetDevice(s->device));
+	if (m->id_kind == RT_MATTE_ID_PRIMITIVE && !s->d_prim_desc) // (upload_scene, rt_api.cpp, makes the table for fewer primitives)
+		return fail(RT_ERR_UNSUPPORTED, "primitive IDs need fewer than 2^32 - 1 primitives");
+	bool prune = false;
+	DevScene dev;
+	rc = four_wave_traversal(s, &prune, &dev); // (rt_api_internal.h)
+	if (rc != RT_OK)
+		return rc;
+	const rt_aov_buffers no_channels = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+	DevMatteParams P;
+	std::memset(&P, 0, sizeof P);
+	P.A = aov_params(s, camera, o, &no_channels, 0u);
+	P.id_kind = (uint32_t)m->id_kind;
+	P.layers = m->layers;
+	P.ids = d_out->ids;
+	P.coverage = d_out->coverage;
+	P.residual = d_out->residual;
+	HIP_TRY(launch_matte(prune, static_cast<hipStream_t>(hip_stream), dev, P));
+	return RT_OK;
+}
+
+int rt_render_matte(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_matte_opts *m, const rt_matte_buffers *out)
+{
+	int rc = matte_check(s, camera, o, m, out);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	// ids, coverage, then the residual if asked for; 4-byte elements throughout
+	const size_t n = (size_t)(o->width * o->height);
+	Staging st{s};
+	st.add(out->ids, m->layers * n);
+	st.add(out->coverage, m->layers * n);
+	st.add(out->residual, n);
+	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, st.total * 4); // shared with rt_denoise / rt_render_denoised
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_denoise;
+	const rt_matte_buffers d_out = {st.at<uint32_t>(base, 0), st.at(base, 1), st.at(base, 2)};
+	st.rc = rt_render_matte_device(s, camera, o, m, &d_out, s->stream);
+	st.download(out->ids, d_out.ids, 4 * st.count[0]);
+	st.download(out->coverage, d_out.coverage, 4 * st.count[1]);
+	st.download(out->residual, d_out.residual, 4 * st.count[2]);
+	return st.finish("render_matte");
+}
+
+int rt_matte_extract_device(rt_scene *s, const rt_matte_buffers *d_layers, uint32_t width, uint32_t height, uint32_t layers,
+                            const uint32_t *d_sorted_ids, uint64_t n_ids, float *d_out, void *hip_stream)
+{
+	int rc = matte_extract_check(s, d_layers, width, height, layers, d_sorted_ids, n_ids, d_out);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device)); // a multi-device head runs on devices[0]
+	DevMatteExtractParams P;
+	std::memset(&P, 0, sizeof P);
+	P.ids = d_layers->ids;
+	P.coverage = d_layers->coverage;
+	P.sel = d_sorted_ids;
+	P.n_sel = (uint32_t)n_ids;
+	P.layers = layers;
+	P.n_px = (uint32_t)((uint64_t)width * height);
+	P.out = d_out;
+	HIP_TRY(launch_matte_extract(static_cast<hipStream_t>(hip_stream), P));
+	return RT_OK;
+}
+
+int rt_matte_extract(rt_scene *s, const rt_matte_buffers *layers_in, uint32_t width, uint32_t height, uint32_t layers, const uint32_t *ids,
+                     uint64_t n_ids, float *out)
+{
+	int rc = matte_extract_check(s, layers_in, width, height, layers, ids, n_ids, out);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	std::vector<uint32_t> sorted(ids, ids + n_ids); // the caller's selection in any order, duplicates and all
+	std::sort(sorted.begin(), sorted.end());
+	const size_t n = (size_t)width * height;
+	// out first, then the layers and the sorted selection
+	Staging st{s, n};
+	st.add(layers_in->ids, layers * n);
+	st.add(layers_in->coverage, layers * n);
+	st.add(sorted.data(), sorted.size());
+	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, st.total * 4); // shared with rt_denoise / rt_render_denoised
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_denoise;
+	float *d_out = reinterpret_cast<float *>(base);
+	if (!st.upload(base))
+		return st.finish("matte_extract upload");
+	const rt_matte_buffers d_layers = {st.at<uint32_t>(base, 0), st.at(base, 1), nullptr};
+	st.rc = rt_matte_extract_device(s, &d_layers, width, height, layers, st.at<uint32_t>(base, 2), n_ids, d_out, s->stream);
+	st.download(out, d_out, 4 * n);
+	return st.finish("matte_extract");
 }
 
 } // extern "C"

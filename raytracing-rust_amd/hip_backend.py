@@ -342,6 +342,62 @@ class HipScene:
         _check(lib().rt_render_aov_chain_device(self._h, C.byref(camera), C.byref(opts), C.byref(copts), C.byref(bufs),
                                                 C.c_void_p(stream)))
 
+    # ---- anti-aliased ID mattes (rt_render_matte, rt_matte_extract): ranked ID / coverage layers over all passes ----
+    def render_matte(self, camera, opts, id_kind="material", layers=4, residual=False):
+        """The `layers` most-covering primitive or material IDs of every pixel over passes [sample_begin, sample_begin +
+        samples_per_pixel) with their coverage fractions, as {"ids": (K, H, W) u32, "coverage": (K, H, W) f32} plus "residual"
+        (H, W) f32 -- the share the layers leave out -- when asked for.  A sky layer has ID abi.AOV_NO_ID and a positive coverage,
+        an empty layer the same ID and coverage 0.  id_kind: "material" / "primitive" or abi.RT_MATTE_ID_*.  Semantics:
+        include/rt_hip.h rt_matte_opts."""
+        m = matte_opts(id_kind=id_kind, layers=layers)
+        h, w, k = int(opts.height), int(opts.width), max(0, min(int(layers), abi.RT_MATTE_SLOTS))
+        out = {"ids": np.zeros((k, h, w), dtype=np.uint32), "coverage": np.zeros((k, h, w), dtype=np.float32)}
+        if residual:
+            out["residual"] = np.zeros((h, w), dtype=np.float32)
+        bufs = abi.MatteBuffers()
+        for name, a in out.items():
+            setattr(bufs, name, _p(a, C.c_uint32 if name == "ids" else C.c_float))
+        _check(lib().rt_render_matte(self._h, C.byref(camera), C.byref(opts), C.byref(m), C.byref(bufs)))
+        return out
+
+    def render_matte_device(self, camera, opts, d_ptrs, id_kind="material", layers=4, stream=0):
+        """rt_render_matte_device: asynchronous, into DEVICE buffers of the scene's GPU.  d_ptrs = {"ids": ..., "coverage": ...,
+        "residual": ...} device pointers (the residual may be left out).  Allocates nothing: capturable from the first call."""
+        bufs = abi.MatteBuffers()
+        for name, ptr in d_ptrs.items():
+            if name not in abi.MATTE_BUFFERS:
+                raise ValueError(f"unknown matte buffer {name!r}")
+            setattr(bufs, name, _dp(ptr, C.c_uint32 if name == "ids" else C.c_float))
+        m = matte_opts(id_kind=id_kind, layers=layers)
+        _check(lib().rt_render_matte_device(self._h, C.byref(camera), C.byref(opts), C.byref(m), C.byref(bufs), C.c_void_p(stream)))
+
+    def matte_extract(self, ids, coverage, selection):
+        """rt_matte_extract: the (H, W) f32 matte of the IDs in `selection` (any order, duplicates allowed; abi.AOV_NO_ID selects
+        the sky) from the (K, H, W) layers render_matte returns -- which may also come as that dict, in place of `ids` with
+        coverage=None."""
+        if isinstance(ids, dict):
+            ids, coverage = ids["ids"], ids["coverage"]
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        coverage = np.ascontiguousarray(coverage, dtype=np.float32)
+        if ids.ndim != 3 or coverage.shape != ids.shape:
+            raise ValueError(f"ids and coverage must both be (K, H, W), got {ids.shape} and {coverage.shape}")
+        k, h, w = ids.shape
+        sel = np.ascontiguousarray(np.asarray(selection, dtype=np.uint32).reshape(-1))
+        bufs = abi.MatteBuffers()
+        bufs.ids, bufs.coverage = _p(ids, C.c_uint32), _p(coverage, C.c_float)
+        out = np.zeros((h, w), dtype=np.float32)
+        _check(lib().rt_matte_extract(self._h, C.byref(bufs), C.c_uint32(w), C.c_uint32(h), C.c_uint32(k),
+                                      _p(sel, C.c_uint32) if sel.size else None, C.c_uint64(sel.size), _p(out, C.c_float)))
+        return out
+
+    def matte_extract_device(self, d_ids, d_coverage, width, height, layers, d_sorted_ids, n_ids, d_out, stream=0):
+        """rt_matte_extract_device: asynchronous, DEVICE buffers of the scene's GPU, no state.  d_sorted_ids: n_ids u32 in ASCENDING
+        order (not verified; 0 / None with n_ids = 0)."""
+        bufs = abi.MatteBuffers()
+        bufs.ids, bufs.coverage = _dp(d_ids, C.c_uint32), _dp(d_coverage, C.c_float)
+        _check(lib().rt_matte_extract_device(self._h, C.byref(bufs), C.c_uint32(width), C.c_uint32(height), C.c_uint32(layers),
+                                             _dp(d_sorted_ids, C.c_uint32), C.c_uint64(n_ids), _dp(d_out), C.c_void_p(stream)))
+
     # ---- AOV-guided A-Trous denoiser (rt_denoise) ----
     def denoise(self, color, albedo=None, normal=None, depth=None, variance=None, **opts):
         """rt_denoise: filter an (H, W, 3) f32 radiance image guided by the optional albedo / normal (H, W, 3), depth and variance
@@ -652,6 +708,21 @@ def denoise_opts(width, height, **kw):
     for k, v in kw.items():
         if k not in ("iterations", "sigma_luminance", "sigma_normal", "sigma_depth"):
             raise ValueError(f"unknown denoise option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def matte_opts(**kw):
+    """rt_matte_opts_default with id_kind (abi.RT_MATTE_ID_* or its name, "primitive" / "material") and / or layers set."""
+    o = abi.MatteOpts()
+    _check(lib().rt_matte_opts_default(C.byref(o)))
+    for k, v in kw.items():
+        if k not in ("id_kind", "layers"):
+            raise ValueError(f"unknown matte option {k!r}")
+        if isinstance(v, str):
+            if v.lower() not in abi.MATTE_ID_KINDS:
+                raise ValueError(f"unknown {k} {v!r}: one of {sorted(abi.MATTE_ID_KINDS)}")
+            v = abi.MATTE_ID_KINDS[v.lower()]
         setattr(o, k, v)
     return o
 
