@@ -604,6 +604,55 @@ int rt_matte_extract(rt_scene *scene, const rt_matte_buffers *host_layers, uint3
 int rt_matte_extract_device(rt_scene *scene, const rt_matte_buffers *device_layers, uint32_t width, uint32_t height, uint32_t layers,
                             const uint32_t *d_sorted_ids, uint64_t n_ids, float *d_out, void *hip_stream);
 
+/* ---- Ambient occlusion (csrc/rt_ao.hip): how open the first hit of each pixel is to its surroundings -- the share of short
+ * cosine-weighted rays from it that reach nothing (visibility), and the mean direction of those rays (the bent normal): contact
+ * shadows for compositing, a fast look-dev preview, a lighting-independent guide.  No integrator runs: a pass is one closest-hit
+ * ray and K any-hit rays.
+ *
+ * For pixel q = y*w + x and passes s = 0 .. samples_per_pixel-1 of the window [sample_begin, sample_begin + samples_per_pixel):
+ *   1. Camera ray: exactly rt_render_aov's -- the first two draws of the stream (seed, q, sample_begin + s) jitter the pixel.  A
+ *      pass whose camera ray misses draws nothing more and contributes nothing.
+ *   2. Hit: the closest hit as rt_check_hit reports it (under the scene's traversal mode; the same bytes in each); its normal,
+ *      point and error are used as they stand.
+ *   3. AO rays, on the SAME stream, continuing behind the jitter; for k = 0 .. K-1 in order (K = rays_per_pass):
+ *      d_k = the Lambertian's sampled direction about Hit.normal (the reference's lambertian.rs:5-18): with r1, r2 the next two
+ *      rt_rng_f32 draws, cos_t = sqrt(1 - r1), sin_t = sqrt(1 - cos_t*cos_t), phi = 2*pi*r2, the local vector
+ *      (cos(phi)*sin_t, sin(phi)*sin_t, cos_t) taken into the frame Coord::new_from_z(normal) -- cosine-weighted about the normal;
+ *      origin = offset_ray(point, normal, error, is_brdf = true), the origin a Lambertian scatter uses; the ray is
+ *      Ray::new(origin, d_k).
+ *   4. Occlusion: the rule of the sky shadow ray with nothing skipped -- the ray is occluded when some primitive has 0 < t and
+ *      NOT (t >= t_limit).  radius == 0: no limit (t_limit = NaN, any t > 0 occludes); radius > 0, +inf included: t_limit = radius.
+ *      No falloff, and no special case for a non-finite direction: what rt_check_hit says about the ray is the answer (occluded =
+ *      a hit is found and NOT (its t >= radius)).
+ *   5. Folds: integer counts and f32 sums from +0 in (pass, k) order, every value written divided once.  With n = hits * K (hits
+ *      = the passes whose camera ray hit) and u = the rays not occluded:
+ *        visibility[q]         = n == 0 ? 1.0f : (float)u / (float)n
+ *        bent_normal[3q + c]   = n == 0 ? +0   : (sum over the rays not occluded of d_k[c]) / (float)n
+ *      d_k as sampled (not the ray's normalised direction), not re-normalised: the length of the bent normal is the openness, its
+ *      direction the bent normal.  The coverage (hits / samples_per_pixel) is rt_render_aov's over the same window.
+ * Options: rays_per_pass = K in 1..64 (default 4); radius >= 0 (default 0); `reserved` must be zero (rt_ao_opts_default zeroes it).
+ * RT_ERR_INVALID_ARGUMENT for a NULL argument, both channels NULL (either alone may be), K outside 1..64, a negative or NaN radius,
+ * a nonzero `reserved` word, samples_per_pixel * K >= 2^32, and two output buffers that overlap.  Everything else -- options of
+ * rt_render_opts ignored, RT_LAYOUT_FRAME and shard_count 1, width and height >= 2, traversal modes, host-only scenes,
+ * multi-device heads (devices[0] alone) and "no side effects" (rt_last_kernel_ms, rt_last_launch_info and the next render are what
+ * they would have been) -- is as for rt_render_aov.
+ * rt_render_ao: HOST buffers, blocking; its device copies live on the scene (shared with rt_denoise; grown for larger frames only).
+ * rt_render_ao_device: DEVICE buffers on the scene's GPU, asynchronous on hip_stream; it allocates nothing, keeps no state and does
+ * not synchronise with the host, so it can be captured into a graph from the scene's first call.  Cost: DESIGN.md section 16. */
+typedef struct rt_ao_opts {
+	uint32_t rays_per_pass; /* K, 1..64, default 4 */
+	float radius;           /* 0: no limit (default); > 0: only hits nearer than this occlude */
+	uint32_t reserved[6];
+} rt_ao_opts;
+typedef struct rt_ao_buffers {
+	float *visibility;  /* w*h or NULL */
+	float *bent_normal; /* 3*w*h or NULL */
+} rt_ao_buffers;
+int rt_ao_opts_default(rt_ao_opts *out);
+int rt_render_ao(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_ao_opts *ao, const rt_ao_buffers *host_out);
+int rt_render_ao_device(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_ao_opts *ao,
+                        const rt_ao_buffers *device_out, void *hip_stream);
+
 /* ---- AOV-guided edge-aware A-Trous denoiser (csrc/rt_denoise.hip): the spatial part of SVGF (Dammertz et al. HPG 2010, Schied et
  * al. HPG 2017) on albedo-demodulated radiance.  W x H, FRAME layout, row-major, y down, f32 throughout.  Per pixel p:
  *   c  RGB mean radiance (required; what rt_render writes)       a  albedo RGB (optional)    n  normal RGB (optional)

@@ -415,6 +415,39 @@ inline std::vector<float> matte_extract(const Bvh &bvh, const MatteLayers &layer
 	return out;
 }
 
+// Ambient occlusion (semantics: rt_hip.h rt_ao_opts): per pixel the share of `rays_per_pass` cosine-weighted rays per pass from the
+// first hit that reach nothing within `radius` (0: no limit), and the mean direction of those rays (length = openness).
+struct AoOptions {
+	uint32_t rays_per_pass = 4; // 1..64
+	float radius = 0.0f;
+};
+struct AoBuffers {
+	std::vector<float> visibility;  // w*h, 1 where no pass hit
+	std::vector<float> bent_normal; // 3*w*h, 0 where no pass hit
+};
+inline AoBuffers render_ao(const RenderOptions &o, const SimpleCamera &camera, const Bvh &bvh, const AoOptions &a = AoOptions(),
+                           uint64_t seed = 1, uint64_t sample_begin = 0)
+{
+	rt_render_opts opts;
+	rt_render_opts_default(&opts);
+	opts.width = o.width;
+	opts.height = o.height;
+	opts.samples_per_pixel = o.samples_per_pixel;
+	opts.sample_begin = sample_begin;
+	opts.seed = seed;
+	rt_ao_opts aopts;
+	check(rt_ao_opts_default(&aopts));
+	aopts.rays_per_pass = a.rays_per_pass;
+	aopts.radius = a.radius;
+	const size_t n = (size_t)o.width * o.height;
+	AoBuffers r;
+	r.visibility.resize(n);
+	r.bent_normal.resize(3 * n);
+	const rt_ao_buffers b = {r.visibility.data(), r.bent_normal.data()};
+	check(rt_render_ao(bvh.raw(), &camera.raw(), &opts, &aopts, &b));
+	return r;
+}
+
 // The A-Trous denoiser of rt_hip.h (rt_denoise_opts): the options a caller sets; defaults as rt_denoise_opts_default.
 struct DenoiseOptions {
 	uint32_t iterations = 5;

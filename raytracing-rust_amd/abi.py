@@ -260,6 +260,28 @@ class MatteBuffers(C.Structure):  # rt_matte_buffers
 MATTE_BUFFERS = ("ids", "coverage", "residual")
 
 
+# ambient occlusion (rt_render_ao)
+AO_MAX_RAYS = 64  # most AO rays per pass
+
+
+class AoOpts(C.Structure):  # rt_ao_opts
+    _fields_ = [
+        ("rays_per_pass", C.c_uint32),
+        ("radius", C.c_float),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+
+class AoBuffers(C.Structure):  # rt_ao_buffers
+    _fields_ = [
+        ("visibility", C.POINTER(C.c_float)),
+        ("bent_normal", C.POINTER(C.c_float)),
+    ]
+
+
+AO_CHANNELS = ("visibility", "bent_normal")
+
+
 class DenoiseOpts(C.Structure):  # rt_denoise_opts
     _fields_ = [
         ("width", C.c_uint32),
@@ -396,6 +418,8 @@ EXPECTED_SIZES = {
     "rt_aov_chain_buffers": (AovChainBuffers, 56),
     "rt_matte_opts": (MatteOpts, 32),
     "rt_matte_buffers": (MatteBuffers, 24),
+    "rt_ao_opts": (AoOpts, 32),
+    "rt_ao_buffers": (AoBuffers, 16),
     "rt_denoise_opts": (DenoiseOpts, 48),
     "rt_denoise_inputs": (DenoiseInputs, 40),
     "rt_temporal_opts": (TemporalOpts, 96),
@@ -456,6 +480,9 @@ EXPORTED_SYMBOLS = [
     "rt_render_matte_device",
     "rt_matte_extract",
     "rt_matte_extract_device",
+    "rt_ao_opts_default",
+    "rt_render_ao",
+    "rt_render_ao_device",
     "rt_denoise_opts_default",
     "rt_denoise_workspace_bytes",
     "rt_denoise",
@@ -491,6 +518,13 @@ def default_matte_opts(id_kind=RT_MATTE_ID_MATERIAL, layers=4):
     """rt_matte_opts_default (include/rt_hip.h)."""
     o = MatteOpts()
     o.id_kind, o.layers = id_kind, layers
+    return o
+
+
+def default_ao_opts(rays_per_pass=4, radius=0.0):
+    """rt_ao_opts_default (include/rt_hip.h)."""
+    o = AoOpts()
+    o.rays_per_pass, o.radius = rays_per_pass, radius
     return o
 
 

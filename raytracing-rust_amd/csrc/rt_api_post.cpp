@@ -1,6 +1,6 @@
 // rt_api_post.cpp -- the host side of the post-processing stages of librt_hip.so (include/rt_hip.h): first-hit and specular-chain
-// AOV buffers, ID mattes, the A-Trous denoiser, temporal accumulation, the display stage and AOV-guided upscaling.  Each stage has its kernels in a file of
-// its own (rt_aov.hip, rt_aov_chain.hip, rt_matte.hip, rt_denoise.hip, rt_temporal.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
+// AOV buffers, ID mattes, ambient occlusion, the A-Trous denoiser, temporal accumulation, the display stage and AOV-guided upscaling.  Each stage has its kernels in a file of
+// its own (rt_aov.hip, rt_aov_chain.hip, rt_matte.hip, rt_ao.hip, rt_denoise.hip, rt_temporal.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
 // and the blocking wrappers that stage host buffers through scene-owned device memory (Staging, rt_api_internal.h).
 // Every check function ends with the device (need_device), so that a host-only scene reports bad arguments as such.
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 #include "rt_aov.h"
 #include "rt_aov_chain.h"
 #include "rt_matte.h"
+#include "rt_ao.h"
 #include "rt_denoise.h"
 #include "rt_temporal.h"
 #include "rt_display.h"
@@ -372,6 +373,97 @@ int rt_matte_extract(rt_scene *s, const rt_matte_buffers *layers_in, uint32_t wi
 	st.rc = rt_matte_extract_device(s, &d_layers, width, height, layers, st.at<uint32_t>(base, 2), n_ids, d_out, s->stream);
 	st.download(out, d_out, 4 * n);
 	return st.finish("matte_extract");
+}
+
+} // extern "C"
+
+// ---- ambient occlusion (rt_ao.hip) ----
+// argument checks of rt_render_ao(_device): the pass's own, then those of the first-hit pass, the device last
+static int ao_check(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_ao_opts *a, const rt_ao_buffers *b)
+{
+	if (!s || !camera || !o || !a || !b)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (!b->visibility && !b->bent_normal)
+		return fail(RT_ERR_INVALID_ARGUMENT, "rt_ao_buffers: every channel is NULL");
+	if (a->rays_per_pass < 1 || a->rays_per_pass > kAoMaxRays)
+		return fail(RT_ERR_INVALID_ARGUMENT, "ao: rays_per_pass must be in 1..64");
+	if (!(a->radius >= 0.0f)) // (a NaN too)
+		return fail(RT_ERR_INVALID_ARGUMENT, "ao: radius must be >= 0 (0: no limit)");
+	for (uint32_t r : a->reserved)
+		if (r != 0u)
+			return fail(RT_ERR_INVALID_ARGUMENT, "ao: reserved must be zero");
+	int rc = aov_opts_check(o);
+	if (rc != RT_OK)
+		return rc;
+	if (o->samples_per_pixel * a->rays_per_pass >= (1ull << 32)) // (the ray counts of a pixel are 32-bit)
+		return fail(RT_ERR_INVALID_ARGUMENT, "ao: samples_per_pixel * rays_per_pass must be below 2^32");
+	uint64_t n = 0;
+	rc = frame_pixels("", o->width, o->height, 2, &n);
+	if (rc != RT_OK)
+		return rc;
+	const void *buf[2] = {b->visibility, b->bent_normal};
+	const uint64_t bytes[2] = {4 * n, 12 * n};
+	rc = check_disjoint("ao: the two output buffers overlap", buf, bytes, 2, 2);
+	return rc == RT_OK ? need_device(s) : rc;
+}
+
+extern "C" {
+
+int rt_ao_opts_default(rt_ao_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	out->rays_per_pass = 4;
+	out->radius = 0.0f;
+	return RT_OK;
+}
+
+int rt_render_ao_device(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_ao_opts *a, const rt_ao_buffers *d_out,
+                        void *hip_stream)
+{
+	int rc = ao_check(s, camera, o, a, d_out);
+	if (rc != RT_OK)
+		return rc;
+	// a multi-device head is an ordinary scene on devices[0]: the pass runs there alone
+	HIP_TRY(hipSetDevice(s->device));
+	bool prune = false;
+	DevScene dev;
+	rc = four_wave_traversal(s, &prune, &dev); // (rt_api_internal.h)
+	if (rc != RT_OK)
+		return rc;
+	const rt_aov_buffers no_channels = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+	DevAoParams P;
+	std::memset(&P, 0, sizeof P);
+	P.A = aov_params(s, camera, o, &no_channels, 0u);
+	P.rays_per_pass = a->rays_per_pass;
+	P.t_limit = a->radius > 0.0f ? a->radius : std::nanf(""); // radius 0: no limit, as the sky shadow ray (rt_intersect.h trace_any)
+	P.visibility = d_out->visibility;
+	P.bent_normal = d_out->bent_normal;
+	HIP_TRY(launch_ao(prune, static_cast<hipStream_t>(hip_stream), dev, P));
+	return RT_OK;
+}
+
+int rt_render_ao(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_ao_opts *a, const rt_ao_buffers *out)
+{
+	int rc = ao_check(s, camera, o, a, out);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	// the visibility, then the bent normal, each if asked for; 4-byte elements throughout
+	const size_t n = (size_t)(o->width * o->height);
+	Staging st{s};
+	st.add(out->visibility, n);
+	st.add(out->bent_normal, 3 * n);
+	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, st.total * 4); // shared with rt_denoise / rt_render_denoised
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_denoise;
+	const rt_ao_buffers d_out = {st.at(base, 0), st.at(base, 1)};
+	st.rc = rt_render_ao_device(s, camera, o, a, &d_out, s->stream);
+	st.download(out->visibility, d_out.visibility, 4 * st.count[0]);
+	st.download(out->bent_normal, d_out.bent_normal, 4 * st.count[1]);
+	return st.finish("render_ao");
 }
 
 } // extern "C"

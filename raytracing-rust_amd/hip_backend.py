@@ -398,6 +398,35 @@ class HipScene:
         _check(lib().rt_matte_extract_device(self._h, C.byref(bufs), C.c_uint32(width), C.c_uint32(height), C.c_uint32(layers),
                                              _dp(d_sorted_ids, C.c_uint32), C.c_uint64(n_ids), _dp(d_out), C.c_void_p(stream)))
 
+    # ---- ambient occlusion (rt_render_ao): visibility and bent normal at the first hit ----
+    def render_ao(self, camera, opts, rays_per_pass=4, radius=0.0, channels=abi.AO_CHANNELS):
+        """The share of `rays_per_pass` cosine-weighted rays per pass from the first hit that reach nothing within `radius` (0: no
+        limit) and the mean direction of those rays, over passes [sample_begin, sample_begin + samples_per_pixel), as
+        {"visibility": (H, W) f32, "bent_normal": (H, W, 3) f32}; only `channels` are produced.  A pixel no pass hit has visibility
+        1 and bent normal 0.  Semantics: include/rt_hip.h rt_ao_opts."""
+        a = ao_opts(rays_per_pass=rays_per_pass, radius=radius)
+        h, w = int(opts.height), int(opts.width)
+        out = {}
+        bufs = abi.AoBuffers()
+        for name in channels:
+            if name not in abi.AO_CHANNELS:
+                raise ValueError(f"unknown AO channel {name!r}")
+            out[name] = np.zeros((h, w, 3) if name == "bent_normal" else (h, w), dtype=np.float32)
+            setattr(bufs, name, _p(out[name], C.c_float))
+        _check(lib().rt_render_ao(self._h, C.byref(camera), C.byref(opts), C.byref(a), C.byref(bufs)))
+        return out
+
+    def render_ao_device(self, camera, opts, d_ptrs, rays_per_pass=4, radius=0.0, stream=0):
+        """rt_render_ao_device: asynchronous, into DEVICE buffers of the scene's GPU.  d_ptrs = {"visibility": ..., "bent_normal":
+        ...} device pointers (either may be left out).  Allocates nothing: capturable from the first call."""
+        bufs = abi.AoBuffers()
+        for name, ptr in d_ptrs.items():
+            if name not in abi.AO_CHANNELS:
+                raise ValueError(f"unknown AO channel {name!r}")
+            setattr(bufs, name, _dp(ptr, C.c_float))
+        a = ao_opts(rays_per_pass=rays_per_pass, radius=radius)
+        _check(lib().rt_render_ao_device(self._h, C.byref(camera), C.byref(opts), C.byref(a), C.byref(bufs), C.c_void_p(stream)))
+
     # ---- AOV-guided A-Trous denoiser (rt_denoise) ----
     def denoise(self, color, albedo=None, normal=None, depth=None, variance=None, **opts):
         """rt_denoise: filter an (H, W, 3) f32 radiance image guided by the optional albedo / normal (H, W, 3), depth and variance
@@ -723,6 +752,17 @@ def matte_opts(**kw):
             if v.lower() not in abi.MATTE_ID_KINDS:
                 raise ValueError(f"unknown {k} {v!r}: one of {sorted(abi.MATTE_ID_KINDS)}")
             v = abi.MATTE_ID_KINDS[v.lower()]
+        setattr(o, k, v)
+    return o
+
+
+def ao_opts(**kw):
+    """rt_ao_opts_default with rays_per_pass and / or radius set."""
+    o = abi.AoOpts()
+    _check(lib().rt_ao_opts_default(C.byref(o)))
+    for k, v in kw.items():
+        if k not in ("rays_per_pass", "radius"):
+            raise ValueError(f"unknown AO option {k!r}")
         setattr(o, k, v)
     return o
 
