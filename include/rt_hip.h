@@ -717,6 +717,94 @@ int rt_denoise_device(rt_scene *scene, const rt_denoise_inputs *device_in, const
 int rt_render_denoised(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_denoise_opts *dopts,
                        float *out_clean, float *out_noisy, uint64_t *rays_shot);
 
+/* ---- Per-pixel noise estimates and render-until-converged (csrc/rt_noise.hip): how noisy is this frame, and can I stop?  A render
+ * at sample_split = S > 1 leaves S independent sums per pixel in the scene's partial buffer; they give a variance of the mean at no
+ * extra ray, from the SAME launch rt_render_device makes.  W x H, RT_LAYOUT_FRAME and shard_count 1 (else RT_ERR_UNSUPPORTED; a
+ * multi-device scene too), f32 throughout with the library's arithmetic contract: IEEE `/` and sqrtf, no fma, sums left to right
+ * from +0 unless a tree is given.
+ * Split.  spp = samples_per_pixel.  An explicit sample_split S must satisfy 2 <= S <= 64 and divide spp; sample_split = 0 takes
+ *   rt_scene_auto_sample_split's value (on a host-only scene: for 256 CUs) halved until it divides spp; RT_ERR_INVALID_ARGUMENT if
+ *   the rule leaves nothing >= 2 (an odd spp).  rt_last_launch_info reports the split used.
+ * One render.  n = spp / S; sum_c = chunk c's sum as the render kernel writes it (passes [c*n, (c+1)*n) in pass order).
+ *   mean  = what rt_render_device writes at that S: (sum_0 + ... + sum_{S-1}) / (float)spp  (the same launches, the same bytes)
+ *   m_c   = sum_c / (float)n per channel;   d = fmaxf(albedo, 1e-3f) per channel with an albedo plane, else 1 (rt_denoise's d)
+ *   l_c   = lum(m_c / d)  (rt_denoise's lum);   lbar = (l_0 + ... + l_{S-1}) / (float)S
+ *   var   = ((l_0 - lbar)^2 + ... + (l_{S-1} - lbar)^2) / (float)(S * (S - 1))
+ *   the variance of lum of the demodulated mean, the quantity rt_denoise takes as `variance`.  Non-finite values propagate as the
+ *   arithmetic gives them (rt_denoise treats a non-finite variance as an invalid pixel).
+ * Batches.  State M (3 channels), L, V per pixel from +0; batch b adds M += mean_b, L += lbar_b, V += var_b; after nb batches
+ *   mean = M / (float)nb,  lum_mean = L / (float)nb,  variance = V / (float)(nb * nb)   (nb * nb in f32)
+ *   One render is nb = 1 through the same code: x / 1.0f = x, so it returns mean_1, lbar_1 and var_1 bit for bit.
+ * Tiles, 8 x 8 in frame raster: tile (tx, ty) = tile index ty * ceil(W / 8) + tx covers x in [8tx, 8tx + 8), y in [8ty, 8ty + 8).
+ *   r(p) = sqrtf(variance) / (fabsf(lum_mean) + luminance_floor); r = +inf if that is not finite.
+ *   slot j = 8 * (y & 7) + (x & 7) holds r; slots outside the frame hold +0.  Butterfly: for k = 0 .. 5: v[j] = v[j] + v[j ^ (1 << k)]
+ *   for all j at once (every slot ends with the same bits; one wave sums a tile across its lanes with no LDS round trip).
+ *   tile_error = v[0] / (float)(pixels of the tile inside the frame).  Every term is >= 0 or +inf for variances >= +0: no NaN arises.
+ * Summary (16 bytes): max_tile_error = the largest tile_error + 0.0f (an atomic max on the bit pattern; the + 0.0f only turns the
+ *   -0 of a tile of -0 variances, which a caller's own planes could hold, into +0); tiles_above = the tiles with tile_error >
+ *   threshold (strict); n_tiles; a reserved word, 0.
+ * Options: luminance_floor finite and > 0 (default 0.01), threshold finite and >= 0 (default 0.05); `reserved` must be zero.  BOTH
+ * DEFAULTS ARE STARTING VALUES NOBODY HAS TUNED: no image set has been rendered to choose them.
+ *
+ * rt_render_noise_device: DEVICE buffers, asynchronous on hip_stream: the launches of rt_render_device(opts with the split) into
+ *   `mean`, then the two kernels.  Any field of rt_noise_buffers but `mean` may be NULL.  d_albedo (3*w*h, rt_render_aov's) or
+ *   NULL.  Scratch (16 + 20 bytes per pixel) lives on the scene and is grown on first use and for larger frames only, so -- like
+ *   the partial buffer -- the first call of a scene at a frame size cannot be captured into a graph; later ones can.
+ * rt_render_noise: the same on HOST buffers, blocking; *rays_shot unless NULL.
+ * rt_noise_tiles[_device]: the tile stage alone on the caller's lum_mean and variance planes (w*h each; width, height >= 1):
+ *   tile_error (ceil(w/8) * ceil(h/8) floats) and / or summary, not both NULL.  The _device form allocates nothing and keeps no state.
+ * rt_render_converged: blocking.  Renders windows [sample_begin + b*batch, sample_begin + (b+1)*batch), b = 0, 1, ...
+ *   (samples_per_pixel is ignored; the split rule applies to `batch`), accumulates each and reads the summary.  Stops after the
+ *   first window for which batches rendered >= min_batches and max_tile_error <= threshold (result->converged = 1), or when another
+ *   window would exceed max_passes (converged = 0).  out_mean (required), out_variance, out_tile_error (either may be NULL) are as
+ *   after the last batch.  out_mean is a MEAN OF BATCH MEANS: not the bytes of one rt_render of all the passes.
+ * rt_render_denoised_split: rt_render_denoised from ONE render: the albedo / normal / depth AOVs, rt_render_noise_device with
+ *   that albedo (the split rule applies to opts as it stands), then rt_denoise_device on (noisy, albedo, normal, depth, variance).
+ *   out_noisy (may be NULL) is the bytes of rt_render_device at that split; out_variance (may be NULL) w*h floats.
+ * Checks: RT_ERR_INVALID_ARGUMENT for a NULL argument (or `mean`), options outside their ranges, a split the rule refuses,
+ * batch = 0, max_passes < batch, written buffers that overlap each other or a buffer read; then RT_ERR_UNSUPPORTED as above; the
+ * device last (RT_ERR_NO_DEVICE), so a host-only scene reports bad arguments as such.  Afterwards rt_last_kernel_ms and
+ * rt_last_launch_info describe the last render launch; a following rt_render returns what it would have. */
+typedef struct rt_noise_opts {
+	float luminance_floor; /* default 0.01 (untuned) */
+	float threshold;       /* default 0.05 (untuned) */
+	uint32_t reserved[6];
+} rt_noise_opts;
+typedef struct rt_noise_summary {
+	float max_tile_error;
+	uint32_t tiles_above; /* tiles with tile_error > threshold */
+	uint32_t n_tiles;
+	uint32_t reserved;
+} rt_noise_summary;
+typedef struct rt_noise_buffers {
+	float *mean;       /* 3*w*h, required */
+	float *variance;   /* w*h or NULL */
+	float *lum_mean;   /* w*h or NULL */
+	float *tile_error; /* ceil(w/8) * ceil(h/8) or NULL */
+	rt_noise_summary *summary; /* or NULL */
+} rt_noise_buffers;
+typedef struct rt_noise_result {
+	uint64_t passes;    /* rendered per pixel: batches * batch */
+	uint64_t rays_shot; /* summed over the batches */
+	uint32_t batches;
+	uint32_t converged; /* 1: stopped below the threshold; 0: stopped by max_passes */
+	rt_noise_summary summary; /* after the last batch */
+} rt_noise_result;
+int rt_noise_opts_default(rt_noise_opts *out);
+int rt_render_noise(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_noise_opts *nopts,
+                    const float *albedo_or_null, const rt_noise_buffers *host_out, uint64_t *rays_shot);
+int rt_render_noise_device(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_noise_opts *nopts,
+                           const float *d_albedo_or_null, const rt_noise_buffers *device_out, uint64_t *d_rays_shot, void *hip_stream);
+int rt_noise_tiles(rt_scene *scene, const float *lum_mean, const float *variance, uint32_t width, uint32_t height,
+                   const rt_noise_opts *nopts, float *tile_error, rt_noise_summary *summary);
+int rt_noise_tiles_device(rt_scene *scene, const float *d_lum_mean, const float *d_variance, uint32_t width, uint32_t height,
+                          const rt_noise_opts *nopts, float *d_tile_error, rt_noise_summary *d_summary, void *hip_stream);
+int rt_render_converged(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_noise_opts *nopts,
+                        uint64_t batch, uint32_t min_batches, uint64_t max_passes, float *out_mean, float *out_variance,
+                        float *out_tile_error, rt_noise_result *result);
+int rt_render_denoised_split(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_denoise_opts *dopts,
+                             float *out_clean, float *out_noisy, float *out_variance, uint64_t *rays_shot);
+
 /* ---- Temporal accumulation with camera reprojection (csrc/rt_temporal.hip): the temporal half of SVGF (Schied et al. HPG 2017) in
  * front of the A-Trous filter above, for a static scene seen by a moving camera.  W x H (both >= 2, the AOV rule), FRAME layout,
  * row-major, y down, f32 throughout with the library's arithmetic contract: IEEE `/` and sqrtf, no fma, sums left to right.

@@ -448,6 +448,78 @@ inline AoBuffers render_ao(const RenderOptions &o, const SimpleCamera &camera, c
 	return r;
 }
 
+// Noise estimates (semantics: rt_hip.h rt_noise_opts): from ONE render at `sample_split` (2..64 dividing the passes, 0 = automatic)
+// the mean rt_render gives at that split, the variance of the luminance of that mean, the 8 x 8 tile error map and its summary.
+struct NoiseOptions {
+	float luminance_floor = 0.01f; // untuned starting value
+	float threshold = 0.05f;       // untuned starting value
+};
+struct NoiseEstimate {
+	std::vector<float> mean;       // 3*w*h
+	std::vector<float> variance;   // w*h
+	std::vector<float> lum_mean;   // w*h
+	std::vector<float> tile_error; // ceil(w/8) * ceil(h/8)
+	rt_noise_summary summary{};
+	uint64_t rays_shot = 0;
+};
+namespace detail {
+inline rt_noise_opts noise_opts(const NoiseOptions &n)
+{
+	rt_noise_opts o;
+	check(rt_noise_opts_default(&o));
+	o.luminance_floor = n.luminance_floor;
+	o.threshold = n.threshold;
+	return o;
+}
+inline rt_render_opts noise_render_opts(const RenderOptions &o, uint32_t sample_split, uint64_t seed, uint64_t sample_begin)
+{
+	rt_render_opts opts;
+	rt_render_opts_default(&opts);
+	opts.width = o.width;
+	opts.height = o.height;
+	opts.samples_per_pixel = o.samples_per_pixel;
+	opts.sample_begin = sample_begin;
+	opts.seed = seed;
+	opts.sample_split = sample_split;
+	return opts;
+}
+} // namespace detail
+inline NoiseEstimate render_noise(const RenderOptions &o, const SimpleCamera &camera, const Bvh &bvh, uint32_t sample_split = 0,
+                                  const NoiseOptions &n = NoiseOptions(), uint64_t seed = 1, uint64_t sample_begin = 0)
+{
+	const rt_render_opts opts = detail::noise_render_opts(o, sample_split, seed, sample_begin);
+	const rt_noise_opts nopts = detail::noise_opts(n);
+	const size_t px = (size_t)o.width * o.height;
+	NoiseEstimate r;
+	r.mean.resize(3 * px);
+	r.variance.resize(px);
+	r.lum_mean.resize(px);
+	r.tile_error.resize(((size_t)o.width + 7) / 8 * (((size_t)o.height + 7) / 8));
+	const rt_noise_buffers b = {r.mean.data(), r.variance.data(), r.lum_mean.data(), r.tile_error.data(), &r.summary};
+	check(rt_render_noise(bvh.raw(), &camera.raw(), &opts, &nopts, nullptr, &b, &r.rays_shot));
+	return r;
+}
+// Render windows of `batch` passes until every tile's error is at most the threshold (after at least min_batches windows) or another
+// window would exceed max_passes.  The mean is a mean of batch means, not the bytes of one render of all the passes.
+struct ConvergedFrame {
+	std::vector<float> mean, variance, tile_error;
+	rt_noise_result result{};
+};
+inline ConvergedFrame render_converged(const RenderOptions &o, const SimpleCamera &camera, const Bvh &bvh, uint32_t sample_split, uint64_t batch,
+                                       uint32_t min_batches, uint64_t max_passes, const NoiseOptions &n = NoiseOptions(), uint64_t seed = 1)
+{
+	const rt_render_opts opts = detail::noise_render_opts(o, sample_split, seed, 0);
+	const rt_noise_opts nopts = detail::noise_opts(n);
+	const size_t px = (size_t)o.width * o.height;
+	ConvergedFrame r;
+	r.mean.resize(3 * px);
+	r.variance.resize(px);
+	r.tile_error.resize(((size_t)o.width + 7) / 8 * (((size_t)o.height + 7) / 8));
+	check(rt_render_converged(bvh.raw(), &camera.raw(), &opts, &nopts, batch, min_batches, max_passes, r.mean.data(), r.variance.data(),
+	                          r.tile_error.data(), &r.result));
+	return r;
+}
+
 // The A-Trous denoiser of rt_hip.h (rt_denoise_opts): the options a caller sets; defaults as rt_denoise_opts_default.
 struct DenoiseOptions {
 	uint32_t iterations = 5;

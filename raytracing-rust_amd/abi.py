@@ -282,6 +282,52 @@ class AoBuffers(C.Structure):  # rt_ao_buffers
 AO_CHANNELS = ("visibility", "bent_normal")
 
 
+# noise estimates (rt_render_noise, rt_noise_tiles, rt_render_converged)
+NOISE_MAX_SPLIT = 64  # the largest sample_split an estimate is taken from
+NOISE_TILE = 8  # tiles of the error map are NOISE_TILE x NOISE_TILE pixels
+NOISE_TILES_PER_GRID_PASS = 8192  # tiles the tile kernel's grid covers before it strides (csrc/rt_noise.h kNoiseTileGridBlocks * 4)
+
+
+class NoiseOpts(C.Structure):  # rt_noise_opts
+    _fields_ = [
+        ("luminance_floor", C.c_float),
+        ("threshold", C.c_float),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+
+class NoiseSummary(C.Structure):  # rt_noise_summary
+    _fields_ = [
+        ("max_tile_error", C.c_float),
+        ("tiles_above", C.c_uint32),
+        ("n_tiles", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class NoiseBuffers(C.Structure):  # rt_noise_buffers
+    _fields_ = [
+        ("mean", C.POINTER(C.c_float)),
+        ("variance", C.POINTER(C.c_float)),
+        ("lum_mean", C.POINTER(C.c_float)),
+        ("tile_error", C.POINTER(C.c_float)),
+        ("summary", C.POINTER(NoiseSummary)),
+    ]
+
+
+class NoiseResult(C.Structure):  # rt_noise_result
+    _fields_ = [
+        ("passes", C.c_uint64),
+        ("rays_shot", C.c_uint64),
+        ("batches", C.c_uint32),
+        ("converged", C.c_uint32),
+        ("summary", NoiseSummary),
+    ]
+
+
+NOISE_CHANNELS = ("mean", "variance", "lum_mean", "tile_error", "summary")
+
+
 class DenoiseOpts(C.Structure):  # rt_denoise_opts
     _fields_ = [
         ("width", C.c_uint32),
@@ -420,6 +466,10 @@ EXPECTED_SIZES = {
     "rt_matte_buffers": (MatteBuffers, 24),
     "rt_ao_opts": (AoOpts, 32),
     "rt_ao_buffers": (AoBuffers, 16),
+    "rt_noise_opts": (NoiseOpts, 32),
+    "rt_noise_summary": (NoiseSummary, 16),
+    "rt_noise_buffers": (NoiseBuffers, 40),
+    "rt_noise_result": (NoiseResult, 40),
     "rt_denoise_opts": (DenoiseOpts, 48),
     "rt_denoise_inputs": (DenoiseInputs, 40),
     "rt_temporal_opts": (TemporalOpts, 96),
@@ -488,6 +538,13 @@ EXPORTED_SYMBOLS = [
     "rt_denoise",
     "rt_denoise_device",
     "rt_render_denoised",
+    "rt_noise_opts_default",
+    "rt_render_noise",
+    "rt_render_noise_device",
+    "rt_noise_tiles",
+    "rt_noise_tiles_device",
+    "rt_render_converged",
+    "rt_render_denoised_split",
     "rt_temporal_opts_default",
     "rt_temporal_history_bytes",
     "rt_temporal_workspace_bytes",
@@ -525,6 +582,13 @@ def default_ao_opts(rays_per_pass=4, radius=0.0):
     """rt_ao_opts_default (include/rt_hip.h)."""
     o = AoOpts()
     o.rays_per_pass, o.radius = rays_per_pass, radius
+    return o
+
+
+def default_noise_opts(luminance_floor=0.01, threshold=0.05):
+    """rt_noise_opts_default (include/rt_hip.h)."""
+    o = NoiseOpts()
+    o.luminance_floor, o.threshold = luminance_floor, threshold
     return o
 
 

@@ -504,6 +504,8 @@ void rt_scene_destroy(rt_scene *s)
 		(void)hipFree(s->d_temporal);
 	if (s->d_display)
 		(void)hipFree(s->d_display);
+	if (s->d_noise)
+		(void)hipFree(s->d_noise);
 	if (s->d_stack_ovf)
 		(void)hipFree(s->d_stack_ovf);
 	for (int b = 0; b < 2; ++b) {
@@ -838,7 +840,7 @@ int shard_geometry(const rt_render_opts *o, ShardGeometry &g)
 // 146.0 / 140 / 134.5 ms at S = 16 / 32 / 64 on one GPU's share, ideal 124: profiles/r03k_mesh1m_share_splits.txt).  Measured on
 // one GPU, config 2: whole frame 93.4 ms at S = 1, 86.9 at S = 16; a 1/8 share 27.9 ms at S = 1, 11.1 at S = 32 / 64
 // (profiles/r03k_split_sweep.txt).
-static uint32_t auto_sample_split(int n_cus, uint64_t frame_pixels, uint64_t spp, uint32_t n_sharers)
+uint32_t auto_sample_split(int n_cus, uint64_t frame_pixels, uint64_t spp, uint32_t n_sharers)
 {
 	if (n_sharers == 0u)
 		n_sharers = 1u;

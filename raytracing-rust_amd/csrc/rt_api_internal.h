@@ -103,7 +103,12 @@ struct rt_scene {
 	size_t d_display_bytes = 0;
 	uint32_t display_w = 0, display_h = 0; // the frame size of the last successful call
 	bool display_has_state = false;        // false: the next rt_display starts from a zero state
+	char *d_noise = nullptr;               // rt_render_noise & co.: the batch state (16 + 20 bytes per pixel), then what the blocking calls stage
+	size_t d_noise_bytes = 0;
 };
+
+// sample_split = 0 (automatic), resolved (rt_api.cpp); the noise estimates halve it until it divides the passes (rt_api_post.cpp)
+uint32_t auto_sample_split(int n_cus, uint64_t frame_pixels, uint64_t spp, uint32_t n_sharers);
 
 // ---- traversal policy: which walk, and for the four-wave kernels which tree and how much stack ----
 // the walk every launch on this scene takes (rt_scene_set_traversal / RT_TUNE_TRAVERSAL, else by size); the fine schedule of

@@ -1,6 +1,6 @@
 // rt_api_post.cpp -- the host side of the post-processing stages of librt_hip.so (include/rt_hip.h): first-hit and specular-chain
-// AOV buffers, ID mattes, ambient occlusion, the A-Trous denoiser, temporal accumulation, the display stage and AOV-guided upscaling.  Each stage has its kernels in a file of
-// its own (rt_aov.hip, rt_aov_chain.hip, rt_matte.hip, rt_ao.hip, rt_denoise.hip, rt_temporal.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
+// AOV buffers, ID mattes, ambient occlusion, the A-Trous denoiser, noise estimates, temporal accumulation, the display stage and AOV-guided upscaling.  Each stage has its kernels in a file of
+// its own (rt_aov.hip, rt_aov_chain.hip, rt_matte.hip, rt_ao.hip, rt_denoise.hip, rt_noise.hip, rt_temporal.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
 // and the blocking wrappers that stage host buffers through scene-owned device memory (Staging, rt_api_internal.h).
 // Every check function ends with the device (need_device), so that a host-only scene reports bad arguments as such.
 #include <hip/hip_runtime.h>
@@ -16,6 +16,8 @@
 #include "rt_matte.h"
 #include "rt_ao.h"
 #include "rt_denoise.h"
+#include "rt_noise.h"
+#include "rt_render.h"
 #include "rt_temporal.h"
 #include "rt_display.h"
 #include "rt_upscale.h"
@@ -696,6 +698,402 @@ int rt_render_denoised(rt_scene *s, const rt_camera *camera, const rt_render_opt
 	rc = st.finish("render_denoised");
 	if (rc == RT_OK && rays_shot)
 		*rays_shot = rays[0] + rays[1];
+	return rc;
+}
+
+} // extern "C"
+
+// ---- per-pixel noise estimates and render-until-converged (rt_noise.hip) ----
+static int noise_opts_check(const rt_noise_opts *n)
+{
+	if (!std::isfinite(n->luminance_floor) || !(n->luminance_floor > 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "noise: luminance_floor must be finite and > 0");
+	if (!std::isfinite(n->threshold) || !(n->threshold >= 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "noise: threshold must be finite and >= 0");
+	for (uint32_t r : n->reserved)
+		if (r != 0u)
+			return fail(RT_ERR_INVALID_ARGUMENT, "noise: reserved must be zero");
+	return RT_OK;
+}
+
+// The split rule of rt_hip.h for `spp` passes: an explicit split in 2..64 that divides them, or the automatic one halved until it
+// does.  A host-only scene has no device to size the automatic split by: 256 CUs stand in (the rule's refusals do not depend on it).
+static int noise_split(const rt_scene *s, const rt_render_opts *o, uint64_t spp, uint32_t *split)
+{
+	if (spp == 0 || spp >= (1ull << 32))
+		return fail(RT_ERR_INVALID_ARGUMENT, "noise: the passes of one render must be in [1, 2^32)");
+	uint32_t S = o->sample_split;
+	if (S == 0u) {
+		S = auto_sample_split(s->n_cus, o->width * o->height, spp, 1u);
+		while (S > 1u && spp % S != 0u)
+			S /= 2u;
+		if (S < 2u)
+			return fail(RT_ERR_INVALID_ARGUMENT, "noise: no automatic sample_split >= 2 divides the passes (an odd number of passes)");
+	} else if (S < 2u || S > kNoiseMaxSplit || spp % S != 0u) {
+		return fail(RT_ERR_INVALID_ARGUMENT, "noise: sample_split must be in 2..64 and divide the passes of one render (0: automatic)");
+	}
+	*split = S;
+	return RT_OK;
+}
+
+// what every rendering entry point of this stage asks of the scene and the render options, for renders of `spp` passes; the
+// caller checks its buffers next and the device last
+static int noise_render_check(const rt_scene *s, const rt_render_opts *o, const rt_noise_opts *n, uint64_t spp, uint32_t *split, uint64_t *px)
+{
+	int rc = noise_opts_check(n);
+	if (rc != RT_OK)
+		return rc;
+	rc = frame_sides("", o->width, o->height, 2);
+	if (rc != RT_OK)
+		return rc;
+	if (o->render_method != RT_METHOD_NAIVE && o->render_method != RT_METHOD_MIS)
+		return fail(RT_ERR_INVALID_ARGUMENT, "unknown render method");
+	rc = noise_split(s, o, spp, split);
+	if (rc != RT_OK)
+		return rc;
+	if (o->output_layout != RT_LAYOUT_FRAME)
+		return fail(RT_ERR_UNSUPPORTED, "noise: RT_LAYOUT_FRAME only");
+	if (o->shard_count != 1)
+		return fail(RT_ERR_UNSUPPORTED, "noise: the whole frame only (shard_count 1)");
+	if (!s->peers.empty())
+		return fail(RT_ERR_UNSUPPORTED, "noise: a multi-device scene keeps its chunk sums on several devices");
+	return frame_pixels("noise: ", o->width, o->height, 2, px);
+}
+
+static uint64_t noise_tile_count(uint64_t w, uint64_t h) { return ((w + 7) / 8) * ((h + 7) / 8); }
+// the scene's scratch: the summary of the blocking calls, then the state planes M, L, V; what a blocking call stages comes behind
+static size_t noise_state_bytes(size_t n) { return kNoiseSummaryBytes + 20 * n; }
+
+static int noise_buffers_check(const rt_scene *s, const float *albedo, const rt_noise_buffers *b, uint64_t n, uint64_t w, uint64_t h)
+{
+	if (!b->mean)
+		return fail(RT_ERR_INVALID_ARGUMENT, "rt_noise_buffers: mean must not be NULL");
+	const void *buf[6] = {b->mean, b->variance, b->lum_mean, b->tile_error, b->summary, albedo};
+	const uint64_t bytes[6] = {12 * n, 4 * n, 4 * n, 4 * noise_tile_count(w, h), kNoiseSummaryBytes, 12 * n};
+	const int rc = check_disjoint("noise: an output buffer overlaps another buffer", buf, bytes, 5, 6);
+	return rc == RT_OK ? need_device(s) : rc;
+}
+
+// the tile stage on `stream`: the summary zeroed by reset_kernel (not a memset node: see its comment in rt_render.hip), its
+// reserved word standing in for the counter that kernel clears
+static int enqueue_noise_tiles(hipStream_t stream, const float *d_lum, const float *d_var, uint64_t w, uint64_t h, const rt_noise_opts *n,
+                               float *d_tile_error, rt_noise_summary *d_summary)
+{
+	DevNoiseTileParams T;
+	std::memset(&T, 0, sizeof T);
+	T.width = (uint32_t)w;
+	T.height = (uint32_t)h;
+	T.tiles_x = (uint32_t)((w + 7) / 8);
+	T.n_tiles = (uint32_t)noise_tile_count(w, h);
+	T.luminance_floor = n->luminance_floor;
+	T.threshold = n->threshold;
+	T.lum_mean = d_lum;
+	T.variance = d_var;
+	T.tile_error = d_tile_error;
+	T.summary = reinterpret_cast<uint32_t *>(d_summary);
+	if (d_summary)
+		HIP_TRY(launch_reset(stream, T.summary + 3, nullptr, reinterpret_cast<float *>(d_summary), 3));
+	HIP_TRY(launch_noise_tiles(stream, T));
+	return RT_OK;
+}
+
+// One batch on `stream`: the render of rt_render_device at `split` into d_render, the chunk kernel (state == nullptr: one batch,
+// nothing kept; else batch number `nb` of a sequence, 1 = fresh) and, if a tile output is asked for, the tile stage.
+// out->variance / lum_mean NULL with a tile output: the state's L and V planes stand in (`scratch`, noise_state_bytes).
+static int enqueue_noise_batch(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, uint32_t split, const rt_noise_opts *n,
+                               const float *d_albedo, float *d_render, char *scratch, bool keep_state, uint32_t nb, const rt_noise_buffers *out,
+                               uint64_t *d_rays, hipStream_t stream)
+{
+	rt_render_opts os = *o;
+	os.sample_split = split;
+	int rc = rt_render_device(s, camera, &os, d_render, d_rays, stream);
+	if (rc != RT_OK)
+		return rc;
+	const size_t px = (size_t)(o->width * o->height);
+	float *const state_m = reinterpret_cast<float *>(scratch + kNoiseSummaryBytes), *const state_l = state_m + 3 * px, *const state_v = state_l + px;
+	const bool tiles = out->tile_error || out->summary;
+	float *d_lum = out->lum_mean, *d_var = out->variance;
+	if (tiles && !keep_state) { // (a sequence divides its state out into planes of its own)
+		d_lum = d_lum ? d_lum : state_l;
+		d_var = d_var ? d_var : state_v;
+	}
+	DevNoiseChunkParams C;
+	std::memset(&C, 0, sizeof C);
+	C.width = (uint32_t)o->width;
+	C.height = (uint32_t)o->height;
+	C.tile_w = o->tile_width ? o->tile_width : 8u; // (shard_geometry, rt_api.cpp)
+	C.tile_h = o->tile_height ? o->tile_height : 8u;
+	C.tiles_x = (C.width + C.tile_w - 1u) / C.tile_w;
+	C.n_work = C.tiles_x * ((C.height + C.tile_h - 1u) / C.tile_h) * C.tile_w * C.tile_h;
+	C.split = split;
+	C.chunk_passes = (uint32_t)(os.samples_per_pixel / split);
+	C.fresh = nb == 1u ? 1u : 0u;
+	C.batches = (float)nb;
+	C.partial = s->d_partial;
+	C.albedo = d_albedo;
+	C.mean_in = d_render;
+	if (keep_state) {
+		C.state_m = state_m;
+		C.state_l = state_l;
+		C.state_v = state_v;
+	}
+	C.out_mean = out->mean;
+	C.out_lum = d_lum;
+	C.out_var = d_var;
+	HIP_TRY(launch_noise_chunks(stream, C));
+	if (tiles)
+		return enqueue_noise_tiles(stream, d_lum, d_var, o->width, o->height, n, out->tile_error, out->summary);
+	return RT_OK;
+}
+
+static int noise_tiles_check(const rt_scene *s, const float *lum_mean, const float *variance, uint32_t w, uint32_t h, const rt_noise_opts *n,
+                             const float *tile_error, const rt_noise_summary *summary)
+{
+	if (!s || !lum_mean || !variance || !n)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (!tile_error && !summary)
+		return fail(RT_ERR_INVALID_ARGUMENT, "noise_tiles: tile_error and summary are both NULL");
+	int rc = noise_opts_check(n);
+	if (rc != RT_OK)
+		return rc;
+	uint64_t px = 0;
+	rc = frame_pixels("noise_tiles: ", w, h, 1, &px);
+	if (rc != RT_OK)
+		return rc;
+	const void *buf[4] = {tile_error, summary, lum_mean, variance};
+	const uint64_t bytes[4] = {4 * noise_tile_count(w, h), kNoiseSummaryBytes, 4 * px, 4 * px};
+	rc = check_disjoint("noise_tiles: an output buffer overlaps another buffer", buf, bytes, 2, 4);
+	return rc == RT_OK ? need_device(s) : rc;
+}
+
+extern "C" {
+
+int rt_noise_opts_default(rt_noise_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	out->luminance_floor = 0.01f;
+	out->threshold = 0.05f;
+	return RT_OK;
+}
+
+int rt_render_noise_device(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_noise_opts *n, const float *d_albedo,
+                           const rt_noise_buffers *d_out, uint64_t *d_rays_shot, void *hip_stream)
+{
+	if (!s || !camera || !o || !n || !d_out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	uint32_t split = 0;
+	uint64_t px = 0;
+	int rc = noise_render_check(s, o, n, o->samples_per_pixel, &split, &px);
+	if (rc == RT_OK)
+		rc = noise_buffers_check(s, d_albedo, d_out, px, o->width, o->height);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, noise_state_bytes(px)); // grows on first use only (not capturable on that call)
+	if (rc != RT_OK)
+		return rc;
+	return enqueue_noise_batch(s, camera, o, split, n, d_albedo, d_out->mean, s->d_noise, false, 1u, d_out, d_rays_shot,
+	                           static_cast<hipStream_t>(hip_stream));
+}
+
+int rt_render_noise(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_noise_opts *n, const float *albedo,
+                    const rt_noise_buffers *out, uint64_t *rays_shot)
+{
+	if (!s || !camera || !o || !n || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	uint32_t split = 0;
+	uint64_t px = 0;
+	int rc = noise_render_check(s, o, n, o->samples_per_pixel, &split, &px);
+	if (rc == RT_OK)
+		rc = noise_buffers_check(s, albedo, out, px, o->width, o->height);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	// behind the state: the mean, then the channels asked for, the summary (4 words) and the albedo if given
+	Staging st{s, noise_state_bytes(px) / 4 + 3 * px};
+	st.add(out->variance, px);
+	st.add(out->lum_mean, px);
+	st.add(out->tile_error, noise_tile_count(o->width, o->height));
+	st.add(out->summary, 4);
+	st.add(albedo, 3 * px);
+	rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, st.total * 4);
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_noise;
+	float *d_mean = reinterpret_cast<float *>(base + noise_state_bytes(px));
+	st.to_device(st.at(base, 4), albedo, 12 * px);
+	const rt_noise_buffers d_out = {d_mean, st.at(base, 0), st.at(base, 1), st.at(base, 2), st.at<rt_noise_summary>(base, 3)};
+	if (st.ok())
+		st.rc = rt_render_noise_device(s, camera, o, n, st.at(base, 4), &d_out, reinterpret_cast<uint64_t *>(s->d_rays), s->stream);
+	st.download(out->mean, d_mean, 12 * px);
+	st.download(out->variance, d_out.variance, 4 * st.count[0]);
+	st.download(out->lum_mean, d_out.lum_mean, 4 * st.count[1]);
+	st.download(out->tile_error, d_out.tile_error, 4 * st.count[2]);
+	st.download(out->summary, d_out.summary, kNoiseSummaryBytes);
+	st.download(rays_shot, s->d_rays, sizeof(uint64_t));
+	return st.finish("render_noise");
+}
+
+int rt_noise_tiles_device(rt_scene *s, const float *d_lum_mean, const float *d_variance, uint32_t width, uint32_t height,
+                          const rt_noise_opts *n, float *d_tile_error, rt_noise_summary *d_summary, void *hip_stream)
+{
+	int rc = noise_tiles_check(s, d_lum_mean, d_variance, width, height, n, d_tile_error, d_summary);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	return enqueue_noise_tiles(static_cast<hipStream_t>(hip_stream), d_lum_mean, d_variance, width, height, n, d_tile_error, d_summary);
+}
+
+int rt_noise_tiles(rt_scene *s, const float *lum_mean, const float *variance, uint32_t width, uint32_t height, const rt_noise_opts *n,
+                   float *tile_error, rt_noise_summary *summary)
+{
+	int rc = noise_tiles_check(s, lum_mean, variance, width, height, n, tile_error, summary);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	const size_t px = (size_t)width * height;
+	Staging st{s};
+	st.add(lum_mean, px);
+	st.add(variance, px);
+	st.add(tile_error, noise_tile_count(width, height));
+	st.add(summary, 4);
+	rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, st.total * 4);
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_noise;
+	st.to_device(st.at(base, 0), lum_mean, 4 * px);
+	st.to_device(st.at(base, 1), variance, 4 * px);
+	if (st.ok())
+		st.rc = rt_noise_tiles_device(s, st.at(base, 0), st.at(base, 1), width, height, n, st.at(base, 2), st.at<rt_noise_summary>(base, 3), s->stream);
+	st.download(tile_error, st.at(base, 2), 4 * st.count[2]);
+	st.download(summary, st.at(base, 3), kNoiseSummaryBytes);
+	return st.finish("noise_tiles");
+}
+
+int rt_render_converged(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_noise_opts *n, uint64_t batch,
+                        uint32_t min_batches, uint64_t max_passes, float *out_mean, float *out_variance, float *out_tile_error,
+                        rt_noise_result *result)
+{
+	if (!s || !camera || !o || !n || !out_mean || !result)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (batch == 0 || max_passes < batch)
+		return fail(RT_ERR_INVALID_ARGUMENT, "render_converged: batch must be >= 1 and max_passes >= batch");
+	uint32_t split = 0;
+	uint64_t px = 0;
+	int rc = noise_render_check(s, o, n, batch, &split, &px);
+	if (rc != RT_OK)
+		return rc;
+	if (max_passes / batch >= (1ull << 24)) // (nb is divided by as a float)
+		return fail(RT_ERR_UNSUPPORTED, "render_converged: more than 2^24 batches");
+	const uint64_t n_tiles = noise_tile_count(o->width, o->height);
+	{
+		const void *buf[3] = {out_mean, out_variance, out_tile_error};
+		const uint64_t bytes[3] = {12 * px, 4 * px, 4 * n_tiles};
+		rc = check_disjoint("render_converged: two output buffers overlap", buf, bytes, 3, 3);
+		if (rc == RT_OK)
+			rc = need_device(s);
+		if (rc != RT_OK)
+			return rc;
+	}
+	HIP_TRY(hipSetDevice(s->device));
+	// behind the state (its first 16 bytes are the summary): this batch's render, then mean, lum_mean, variance and the tile errors
+	const size_t floats = noise_state_bytes(px) / 4 + 3 * px + 3 * px + px + px + n_tiles;
+	rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, floats * 4);
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_noise;
+	float *d_render = reinterpret_cast<float *>(base + noise_state_bytes(px)), *d_mean = d_render + 3 * px, *d_lum = d_mean + 3 * px,
+	      *d_var = d_lum + px, *d_tile = d_var + px;
+	const rt_noise_buffers d_out = {d_mean, d_var, d_lum, d_tile, reinterpret_cast<rt_noise_summary *>(base)};
+	std::memset(result, 0, sizeof *result);
+	rt_render_opts ob = *o;
+	ob.samples_per_pixel = batch;
+	for (uint32_t nb = 1;; ++nb) {
+		ob.sample_begin = o->sample_begin + (uint64_t)(nb - 1u) * batch;
+		Staging st{s};
+		st.rc = enqueue_noise_batch(s, camera, &ob, split, n, nullptr, d_render, base, true, nb, &d_out, reinterpret_cast<uint64_t *>(s->d_rays), s->stream);
+		unsigned long long rays = 0;
+		st.download(&result->summary, base, kNoiseSummaryBytes);
+		st.download(&rays, s->d_rays, sizeof rays);
+		rc = st.finish("render_converged");
+		if (rc != RT_OK)
+			return rc;
+		result->batches = nb;
+		result->passes = (uint64_t)nb * batch;
+		result->rays_shot += rays;
+		result->converged = nb >= min_batches && result->summary.max_tile_error <= n->threshold ? 1u : 0u;
+		if (result->converged || result->passes + batch > max_passes)
+			break;
+	}
+	Staging st{s};
+	st.download(out_mean, d_mean, 12 * px);
+	st.download(out_variance, d_var, 4 * px);
+	st.download(out_tile_error, d_tile, 4 * n_tiles);
+	return st.finish("render_converged");
+}
+
+int rt_render_denoised_split(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_denoise_opts *dopts, float *out_clean,
+                             float *out_noisy, float *out_variance, uint64_t *rays_shot)
+{
+	if (!s || !camera || !o || !dopts || !out_clean)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	int rc = denoise_opts_check(dopts, o->width, o->height);
+	if (rc != RT_OK)
+		return rc;
+	rt_noise_opts n;
+	rt_noise_opts_default(&n);
+	uint32_t split = 0;
+	uint64_t px = 0;
+	rc = noise_render_check(s, o, &n, o->samples_per_pixel, &split, &px);
+	if (rc != RT_OK)
+		return rc;
+	{
+		const void *buf[3] = {out_clean, out_noisy, out_variance};
+		const uint64_t bytes[3] = {12 * px, 12 * px, 4 * px};
+		rc = check_disjoint("rt_render_denoised_split: two output buffers overlap", buf, bytes, 3, 3);
+		if (rc == RT_OK)
+			rc = need_device(s);
+		if (rc != RT_OK)
+			return rc;
+	}
+	HIP_TRY(hipSetDevice(s->device));
+	// in the denoiser's buffer: the ray counter (16 bytes), the workspace, then albedo, normal, depth, noisy, variance, clean
+	const size_t ws_floats = kDenoiseWorkspaceBytesPerPixel / 4 * px;
+	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, 16 + 4 * (ws_floats + 14 * px));
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_denoise;
+	float *ws = reinterpret_cast<float *>(base + 16);
+	float *d_albedo = ws + ws_floats, *d_normal = d_albedo + 3 * px, *d_depth = d_normal + 3 * px, *d_noisy = d_depth + px,
+	      *d_var = d_noisy + 3 * px, *d_clean = d_var + px;
+	Staging st{s};
+	rt_aov_buffers aov;
+	std::memset(&aov, 0, sizeof aov);
+	aov.albedo = d_albedo;
+	aov.normal = d_normal;
+	aov.depth = d_depth;
+	st.rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
+	if (st.ok()) {
+		const rt_noise_buffers d_out = {d_noisy, d_var, nullptr, nullptr, nullptr};
+		st.rc = rt_render_noise_device(s, camera, o, &n, d_albedo, &d_out, reinterpret_cast<uint64_t *>(base), s->stream);
+	}
+	if (st.ok()) {
+		rt_denoise_opts d = *dopts;
+		d.width = (uint32_t)o->width;
+		d.height = (uint32_t)o->height;
+		const rt_denoise_inputs in = {d_noisy, d_albedo, d_normal, d_depth, d_var};
+		st.rc = rt_denoise_device(s, &in, &d, ws, d_clean, s->stream);
+	}
+	unsigned long long rays = 0;
+	st.download(out_clean, d_clean, 12 * px);
+	st.download(out_noisy, d_noisy, 12 * px);
+	st.download(out_variance, d_var, 4 * px);
+	st.download(&rays, base, sizeof rays);
+	rc = st.finish("render_denoised_split");
+	if (rc == RT_OK && rays_shot)
+		*rays_shot = rays;
 	return rc;
 }
 

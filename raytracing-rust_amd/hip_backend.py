@@ -474,6 +474,89 @@ class HipScene:
                                         _p(noisy, C.c_float), C.byref(rays)))
         return clean, noisy, rays.value
 
+    # ---- noise estimates (rt_render_noise, rt_noise_tiles, rt_render_converged, rt_render_denoised_split) ----
+    def render_noise(self, camera, opts, albedo=None, channels=abi.NOISE_CHANNELS, **nopts):
+        """rt_render_noise: ONE render at opts.sample_split (2..64 dividing the passes; 0 = automatic) and, from its chunk sums,
+        {"mean": (H, W, 3), "variance": (H, W), "lum_mean": (H, W), "tile_error": (ceil(H/8), ceil(W/8)) f32, "summary": dict,
+        "rays_shot": int}; only `channels` (always the mean) are produced.  albedo (H, W, 3): demodulate as rt_denoise does.
+        Keyword options: luminance_floor, threshold.  Semantics: include/rt_hip.h rt_noise_opts."""
+        n = noise_opts(**nopts)
+        h, w = int(opts.height), int(opts.width)
+        out, bufs, summary = _noise_outputs(w, h, channels)
+        if albedo is not None:
+            albedo = np.ascontiguousarray(albedo, dtype=np.float32)
+            if albedo.shape != (h, w, 3):
+                raise ValueError(f"albedo must be {(h, w, 3)}, got {albedo.shape}")
+        rays = C.c_uint64()
+        _check(lib().rt_render_noise(self._h, C.byref(camera), C.byref(opts), C.byref(n), _p(albedo, C.c_float) if albedo is not None else None,
+                                     C.byref(bufs), C.byref(rays)))
+        if summary is not None:
+            out["summary"] = _summary_dict(summary)
+        out["rays_shot"] = rays.value
+        return out
+
+    def render_noise_device(self, camera, opts, d_ptrs, d_albedo=None, d_rays_ptr=None, stream=0, **nopts):
+        """rt_render_noise_device: asynchronous, DEVICE buffers of the scene's GPU.  d_ptrs = {channel: device pointer} over
+        abi.NOISE_CHANNELS ("mean" required; "summary": 16 bytes)."""
+        bufs = abi.NoiseBuffers()
+        for name, ptr in d_ptrs.items():
+            if name not in abi.NOISE_CHANNELS:
+                raise ValueError(f"unknown noise channel {name!r}")
+            setattr(bufs, name, _dp(ptr, abi.NoiseSummary if name == "summary" else C.c_float))
+        n = noise_opts(**nopts)
+        _check(lib().rt_render_noise_device(self._h, C.byref(camera), C.byref(opts), C.byref(n), _dp(d_albedo), C.byref(bufs),
+                                            C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream)))
+
+    def noise_tiles(self, lum_mean, variance, **nopts):
+        """rt_noise_tiles: the tile stage alone on (H, W) f32 planes; returns (tile_error (ceil(H/8), ceil(W/8)), summary dict)."""
+        lum_mean = np.ascontiguousarray(lum_mean, dtype=np.float32)
+        variance = np.ascontiguousarray(variance, dtype=np.float32)
+        if lum_mean.ndim != 2 or lum_mean.shape != variance.shape:
+            raise ValueError(f"lum_mean and variance must be (H, W) alike, got {lum_mean.shape} and {variance.shape}")
+        h, w = lum_mean.shape
+        n = noise_opts(**nopts)
+        tiles = np.zeros(((h + 7) // 8, (w + 7) // 8), dtype=np.float32)
+        summary = abi.NoiseSummary()
+        _check(lib().rt_noise_tiles(self._h, _p(lum_mean, C.c_float), _p(variance, C.c_float), C.c_uint32(w), C.c_uint32(h), C.byref(n),
+                                    _p(tiles, C.c_float), C.byref(summary)))
+        return tiles, _summary_dict(summary)
+
+    def noise_tiles_device(self, d_lum_mean, d_variance, width, height, d_tile_error=None, d_summary=None, stream=0, **nopts):
+        """rt_noise_tiles_device: asynchronous, DEVICE planes; allocates nothing."""
+        n = noise_opts(**nopts)
+        _check(lib().rt_noise_tiles_device(self._h, _dp(d_lum_mean), _dp(d_variance), C.c_uint32(width), C.c_uint32(height), C.byref(n),
+                                           _dp(d_tile_error), _dp(d_summary, abi.NoiseSummary), C.c_void_p(stream)))
+
+    def render_converged(self, camera, opts, batch, min_batches=1, max_passes=None, **nopts):
+        """rt_render_converged: render windows of `batch` passes from opts.sample_begin on until every tile's error is at most the
+        threshold (after at least min_batches windows) or another window would exceed max_passes (default: 64 windows).  Returns
+        {"mean", "variance", "tile_error", "passes", "batches", "converged", "rays_shot", "summary"}; the mean is a mean of batch
+        means, not the bytes of one render of all the passes."""
+        n = noise_opts(**nopts)
+        h, w = int(opts.height), int(opts.width)
+        out, _, _ = _noise_outputs(w, h, ("mean", "variance", "tile_error"))
+        res = abi.NoiseResult()
+        _check(lib().rt_render_converged(self._h, C.byref(camera), C.byref(opts), C.byref(n), C.c_uint64(batch), C.c_uint32(min_batches),
+                                         C.c_uint64(64 * batch if max_passes is None else max_passes), _p(out["mean"], C.c_float),
+                                         _p(out["variance"], C.c_float), _p(out["tile_error"], C.c_float), C.byref(res)))
+        out.update(passes=res.passes, batches=res.batches, converged=bool(res.converged), rays_shot=res.rays_shot,
+                   summary=_summary_dict(res.summary))
+        return out
+
+    def render_denoised_split(self, camera, opts, dopts=None):
+        """rt_render_denoised_split: render_denoised from ONE render at opts.sample_split, the variance taken from its chunk sums.
+        Returns (clean, noisy, variance, rays_shot); noisy is the bytes render() gives at that split."""
+        h, w = int(opts.height), int(opts.width)
+        if dopts is None:
+            dopts = denoise_opts(w, h)
+        clean = np.zeros((h, w, 3), dtype=np.float32)
+        noisy = np.zeros((h, w, 3), dtype=np.float32)
+        variance = np.zeros((h, w), dtype=np.float32)
+        rays = C.c_uint64()
+        _check(lib().rt_render_denoised_split(self._h, C.byref(camera), C.byref(opts), C.byref(dopts), _p(clean, C.c_float),
+                                              _p(noisy, C.c_float), _p(variance, C.c_float), C.byref(rays)))
+        return clean, noisy, variance, rays.value
+
     # ---- temporal accumulation with camera reprojection (rt_denoise_temporal) ----
     def denoise_temporal(self, color, camera, albedo=None, normal=None, depth=None, motion=False, **opts):
         """rt_denoise_temporal: one frame of a camera path.  color (H, W, 3) f32 -- or the dict render_aov returns with the image
@@ -765,6 +848,37 @@ def ao_opts(**kw):
             raise ValueError(f"unknown AO option {k!r}")
         setattr(o, k, v)
     return o
+
+
+def noise_opts(**kw):
+    """rt_noise_opts_default with luminance_floor and / or threshold set."""
+    o = abi.NoiseOpts()
+    _check(lib().rt_noise_opts_default(C.byref(o)))
+    for k, v in kw.items():
+        if k not in ("luminance_floor", "threshold"):
+            raise ValueError(f"unknown noise option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def _noise_outputs(w, h, channels):
+    """(arrays by channel, rt_noise_buffers pointing at them, the summary struct or None) of a w x h frame"""
+    shapes = {"mean": (h, w, 3), "variance": (h, w), "lum_mean": (h, w), "tile_error": ((h + 7) // 8, (w + 7) // 8)}
+    out, bufs, summary = {}, abi.NoiseBuffers(), None
+    for name in ("mean", *channels):
+        if name not in abi.NOISE_CHANNELS:
+            raise ValueError(f"unknown noise channel {name!r}")
+        if name == "summary":
+            summary = abi.NoiseSummary()
+            bufs.summary = C.pointer(summary)
+        elif name not in out:
+            out[name] = np.zeros(shapes[name], dtype=np.float32)
+            setattr(bufs, name, _p(out[name], C.c_float))
+    return out, bufs, summary
+
+
+def _summary_dict(s):
+    return {"max_tile_error": np.float32(s.max_tile_error), "tiles_above": int(s.tiles_above), "n_tiles": int(s.n_tiles)}
 
 
 def denoise_workspace_bytes(opts):
