@@ -14,7 +14,7 @@ import denoise_checker as K
 import display_checker as D
 import temporal_checker as T
 import upscale_checker as U
-from test_gpu_denoise import TOL, _synthetic
+from post_runners import TOL, synthetic
 
 F32 = np.float32
 SENSITIVITY = 100 * TOL  # what an option must move the checker by, in denoise_checker.relative_error, to count as exercised
@@ -30,12 +30,12 @@ DENOISE_CASES = [
     ("sigma_depth_high", dict(sigma_depth=0.5)),
     ("all", dict(sigma_luminance=1.5, sigma_normal=16.0, sigma_depth=0.3, iterations=3)),
 ]
-DENOISE_RENDERED = ("rtweekend1", 67, 37)  # (a name of test_gpu_denoise.SCENES, w, h): the GPU test checks sensitivity itself
+DENOISE_RENDERED = ("rtweekend1", 67, 37)  # (a name of post_runners.SCENES, w, h): the GPU test checks sensitivity itself
 
 
 def denoise_synthetic():
-    """test_gpu_denoise._synthetic at 67 x 37: random normals and depths, so the normal and depth weights matter"""
-    return _synthetic(37, 67, seed=5)
+    """post_runners.synthetic at 67 x 37: random normals and depths, so the normal and depth weights matter"""
+    return synthetic(37, 67, seed=5)
 
 
 def denoise_sensitivity(inputs, opts):

@@ -19,7 +19,7 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 import scenes  # noqa: E402
-import test_gpu_aov_chain as T  # noqa: E402  (the quality scene)
+import gpu_support as T  # noqa: E402  (the quality scene)
 
 W, H, SPP = 1920, 1080, 16
 REPS = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else 5

@@ -2,15 +2,10 @@
 registers for the histogram and exposure kernels and at least four for the map kernel (DESIGN.md section 12 says why it holds five).
 They are their own translation unit, so their code object is an offload bundle of its own in librt_hip.so, found here as the
 temporal kernels' is (tests/test_temporal_resources.py)."""
-import importlib.util
-import os
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-spec = importlib.util.spec_from_file_location("resource_table", os.path.join(ROOT, "tests", "probes", "resource_table.py"))
-rtab = importlib.util.module_from_spec(spec)
-spec.loader.exec_module(rtab)
+from resource_budget import assert_budget, bundle
+
 KERNELS = {"void rt::display_histogram<true>", "void rt::display_histogram<false>", "rt::display_exposure",
            "void rt::display_map<true>", "void rt::display_map<false>"}
 
@@ -18,20 +13,13 @@ KERNELS = {"void rt::display_histogram<true>", "void rt::display_histogram<false
 @pytest.fixture(scope="module")
 def display_bundle():
     """every kernel of the bundle that holds the display kernels"""
-    if not os.path.exists(rtab.READELF):
-        pytest.skip("llvm-readelf not available")
-    rtab.rebuild_if_stale()
-    return rtab.bundle_with("display_")
+    return bundle("display_")
 
 
 def test_display_kernel_resources(display_bundle):
     assert set(display_bundle) == KERNELS, sorted(display_bundle)
-    for name, d in display_bundle.items():
-        assert d["private_segment_fixed_size"] == 0, (name, d)
-        assert d["vgpr_spill_count"] == 0 and d["sgpr_spill_count"] == 0, (name, d)
-        need = 4 if "display_map" in name else 8
-        assert d["waves_per_simd_by_registers"] >= need, (name, d)
-        assert d["max_flat_workgroup_size"] == (1024 if "exposure" in name else 256), (name, d)
+    for part, waves, workgroup in (("display_map", 4, 256), ("display_histogram", 8, 256), ("display_exposure", 8, 1024)):
+        assert_budget({k: d for k, d in display_bundle.items() if part in k}, waves=waves, workgroup=workgroup)
 
 
 def test_only_display_kernels_in_the_display_bundle(display_bundle):

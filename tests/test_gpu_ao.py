@@ -8,6 +8,7 @@ import pytest
 import ao_checker as A
 import aov_checker as K
 import scenes
+from gpu_support import GuardedBuffers, assert_render_unaffected, assert_same_bits, capture, ssml_scene
 
 pytestmark = pytest.mark.gpu
 abi = scenes.abi
@@ -16,18 +17,13 @@ F32 = np.float32
 CHANNELS = abi.AO_CHANNELS
 
 
-def _ssml(name):
-    ls = scenes.load_ssml(name)
-    return ls.scene, ls.camera_params
-
-
 SCENES = {
     "emit_scene": lambda: (K.emit_scene(), K.EMIT_CAMERA),
     "all_materials": lambda: (scenes.all_materials(), scenes.ALL_MATERIALS_CAMERA),
     "spheres500": lambda: (scenes.random_spheres(500), scenes.ALL_MATERIALS_CAMERA),
-    "pyramid": lambda: _ssml("pyramid"),
-    "rtweekend1": lambda: _ssml("rtweekend1"),
-    "overshadowed": lambda: _ssml("overshadowed"),
+    "pyramid": lambda: ssml_scene("pyramid"),
+    "rtweekend1": lambda: ssml_scene("rtweekend1"),
+    "overshadowed": lambda: ssml_scene("overshadowed"),
     # triangles wide enough to be seen and to shadow each other (the default edge of 0.05 is hit by 0.2 % of the camera rays)
     "mesh2000_wide": lambda: (scenes.random_triangle_mesh(2000, edge=2.0), scenes.MESH_CAMERA),
     "mesh20000": lambda: (scenes.random_triangle_mesh(20000, edge=1.0), scenes.MESH_CAMERA),
@@ -68,18 +64,10 @@ def _opts(w=W, h=H, spp=SPP, seed=SEED, sample_begin=0):
     return o
 
 
-def assert_same(a, b, what):
-    assert a.dtype == b.dtype == np.float32 and a.shape == b.shape, (what, a.dtype, b.dtype, a.shape, b.shape)
-    same = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))  # bits, but any NaN equals any NaN
-    if not same.all():
-        bad = np.argwhere(~same)
-        pytest.fail(f"{what}: {len(bad)} elements differ, first at {bad[0].tolist()}: gpu {a[tuple(bad[0])]!r} checker {b[tuple(bad[0])]!r}")
-
-
 def assert_ao_equal(gpu, ref, what):
     assert set(gpu) == set(ref), (what, sorted(gpu), sorted(ref))
     for name in ref:
-        assert_same(gpu[name], ref[name], f"{what} {name}")
+        assert_same_bits(gpu[name], ref[name], f"{what} {name}", nan_equal=True)
 
 
 def _shares(r):
@@ -174,34 +162,9 @@ def test_ragged_and_tiny_frames(hb, size):
     assert_ao_equal(gpu.render_ao(cam, _opts(w, h, 3, seed=12, sample_begin=4), radius=0.5), ref, f"{w}x{h}")
 
 
-class DeviceAo:
+def device_ao(torch, w, h, off=0):
     """device buffers `off` floats past an aligned base, with guard values before and after every channel"""
-    GUARD = 0x5A5A5A5A
-
-    def __init__(self, torch, w, h, off=0):
-        self.torch, self.w, self.h, self.off = torch, w, h, off
-        dev = torch.device("cuda", 0)
-        self.n = {"visibility": w * h, "bent_normal": 3 * w * h}
-        self.buf = {name: torch.full((n + 2 * 8,), self.GUARD, dtype=torch.int32, device=dev) for name, n in self.n.items()}
-
-    def ptrs(self, channels=CHANNELS):
-        return {name: self.buf[name].data_ptr() + 4 * (4 + self.off) for name in channels}
-
-    def refill(self):
-        for t in self.buf.values():
-            t.fill_(self.GUARD)
-
-    def untouched(self, name):
-        return bool((self.buf[name].cpu().numpy().view(np.uint32) == self.GUARD).all())
-
-    def read(self, channels=CHANNELS):
-        out = {}
-        for name in channels:
-            a = self.buf[name].cpu().numpy().view(np.uint32)
-            lo, hi = 4 + self.off, 4 + self.off + self.n[name]
-            assert (a[:lo] == self.GUARD).all() and (a[hi:] == self.GUARD).all(), f"{name}: a guard value was overwritten"
-            out[name] = a[lo:hi].copy().view(np.float32).reshape((self.h, self.w, 3) if name == "bent_normal" else (self.h, self.w))
-        return out
+    return GuardedBuffers(torch, {"visibility": ((h, w), np.float32), "bent_normal": ((h, w, 3), np.float32)}, off=off)
 
 
 def test_each_channel_alone_off_alignment_with_guards(hb):
@@ -213,19 +176,19 @@ def test_each_channel_alone_off_alignment_with_guards(hb):
     for name in CHANNELS:  # the host entry: only what was asked for comes back
         got = gpu.render_ao(cam, opts, radius=0.5, channels=(name,))
         assert set(got) == {name}
-        assert_same(got[name], ref[name], f"host entry, {name} alone")
+        assert_same_bits(got[name], ref[name], f"host entry, {name} alone", nan_equal=True)
     for off in (0, 1, 3):  # 0, 4 and 12 bytes off a 16-byte boundary
-        run = DeviceAo(torch, w, h, off)
+        run = device_ao(torch, w, h, off)
         torch.cuda.synchronize()
         gpu.render_ao_device(cam, opts, run.ptrs(), radius=0.5)
         torch.cuda.synchronize()
-        assert_ao_equal(run.read(), ref, f"device entry off={off}")
+        assert_ao_equal(run.read_all(), ref, f"device entry off={off}")
         for name, other in (CHANNELS, CHANNELS[::-1]):
             run.refill()
             torch.cuda.synchronize()
             gpu.render_ao_device(cam, opts, run.ptrs((name,)), radius=0.5)
             torch.cuda.synchronize()
-            assert_same(run.read((name,))[name], ref[name], f"device entry off={off}, {name} alone")
+            assert_same_bits(run.read(name), ref[name], f"device entry off={off}, {name} alone", nan_equal=True)
             assert run.untouched(other), f"{other} was written though not asked for"
 
 
@@ -241,11 +204,11 @@ def test_host_entry_device_entry_streams_and_a_multi_device_head(hb):
         assert_ao_equal(gpu.render_ao(cam, opts, radius=1.0), ref, f"{what} host entry")
         created = torch.cuda.Stream(device=dev)
         for stream in (0, created.cuda_stream):
-            run = DeviceAo(torch, W, H)
+            run = device_ao(torch, W, H)
             torch.cuda.synchronize()
             gpu.render_ao_device(cam, opts, run.ptrs(), radius=1.0, stream=stream)
             torch.cuda.synchronize()
-            assert_ao_equal(run.read(), ref, f"{what} device entry, stream {'null' if stream == 0 else 'created'}")
+            assert_ao_equal(run.read_all(), ref, f"{what} device entry, stream {'null' if stream == 0 else 'created'}")
 
 
 def test_three_streams_in_flight(hb):
@@ -255,14 +218,14 @@ def test_three_streams_in_flight(hb):
     ref = _frames(_checked(name, W, H, SPP, 4, 0.0, SEED, 0), W, H)
     dev = torch.device("cuda", 0)
     streams = [torch.cuda.Stream(device=dev) for _ in range(3)]
-    runs = [DeviceAo(torch, W, H) for _ in streams]
+    runs = [device_ao(torch, W, H) for _ in streams]
     torch.cuda.synchronize()
     for _ in range(2):
         for s, run in zip(streams, runs):  # in flight together
             gpu.render_ao_device(cam, _opts(), run.ptrs(), stream=s.cuda_stream)
     torch.cuda.synchronize()
     for i, run in enumerate(runs):
-        assert_ao_equal(run.read(), ref, f"stream {i}")
+        assert_ao_equal(run.read_all(), ref, f"stream {i}")
 
 
 def test_graph_captured_from_the_first_call_replays_the_checkers_bytes(hb):
@@ -272,33 +235,20 @@ def test_graph_captured_from_the_first_call_replays_the_checkers_bytes(hb):
     gpu, cam = _gpu(hb, name)
     ref = _frames(_checked(name, W, H, SPP, 4, 0.0, SEED, 0), W, H)
     dev = torch.device("cuda", 0)
-    run = DeviceAo(torch, W, H)
-    side = torch.cuda.Stream(device=dev)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        gpu.render_ao_device(cam, _opts(), run.ptrs(), stream=torch.cuda.current_stream(dev).cuda_stream)
-    torch.cuda.synchronize(dev)
+    run = device_ao(torch, W, H)
+    g = capture(torch, lambda stream: gpu.render_ao_device(cam, _opts(), run.ptrs(), stream=stream))
     assert all(run.untouched(name) for name in CHANNELS)  # capture ran nothing
     for _ in range(2):
         run.refill()
         torch.cuda.synchronize(dev)
         g.replay()
         torch.cuda.synchronize(dev)
-        assert_ao_equal(run.read(), ref, "graph replay")
+        assert_ao_equal(run.read_all(), ref, "graph replay")
 
 
 def test_no_side_effects_on_render(hb):
     gpu, cam = _gpu(hb, "overshadowed")
-    opts = abi.default_render_opts(96, 54, 8, method=abi.RT_METHOD_MIS, seed=2)
-    img_a, rays_a = gpu.render(cam, opts)
-    n_a = gpu.last_kernel_ms()[1]
-    info_a = gpu.last_launch_info()
-    gpu.render_ao(cam, opts)
-    assert gpu.last_kernel_ms()[1] == n_a and gpu.last_launch_info() == info_a  # still describe the render
-    img_b, rays_b = gpu.render(cam, opts)
-    assert np.array_equal(img_a, img_b) and rays_a == rays_b
-    assert gpu.last_kernel_ms()[1] == n_a and gpu.last_launch_info() == info_a
+    assert_render_unaffected(gpu, cam, lambda opts, img: gpu.render_ao(cam, opts))
 
 
 # ---- properties ----
@@ -323,7 +273,7 @@ def test_the_rays_of_a_pass_are_the_same_for_every_k(hb):
         assert_ao_equal(got, _frames(_checked(name, W, H, 1, k, 0.0, 8, 0), W, H), f"K={k}")
         open_first_k = four["open"][:, 0, :k].sum(axis=1)
         expected = np.where(hit, open_first_k.astype(np.float32) / F32(k), F32(1.0)).astype(np.float32)
-        assert_same(got["visibility"].reshape(-1), expected, f"K={k}: the first {k} of four rays")
+        assert_same_bits(got["visibility"].reshape(-1), expected, f"K={k}: the first {k} of four rays", nan_equal=True)
 
 
 # ---- full size ----
@@ -348,6 +298,6 @@ def test_tiles_of_a_1080p_frame(hb):
     pixels = K.tile_pixels(w, h, sorted(set(tiles)))
     ref = A.ao(cpu, cam_c, w, h, spp, rays, seed=1, pixels=pixels)
     assert 0.05 <= _shares(ref)[1] <= 0.95
-    assert_same(got["visibility"].reshape(-1)[pixels], ref["visibility"], "1080p tiles visibility")
-    assert_same(got["bent_normal"].reshape(-1, 3)[pixels], ref["bent_normal"], "1080p tiles bent_normal")
+    assert_same_bits(got["visibility"].reshape(-1)[pixels], ref["visibility"], "1080p tiles visibility", nan_equal=True)
+    assert_same_bits(got["bent_normal"].reshape(-1, 3)[pixels], ref["bent_normal"], "1080p tiles bent_normal", nan_equal=True)
     assert np.isfinite(got["visibility"]).all() and got["visibility"].min() >= 0.0 and got["visibility"].max() <= 1.0

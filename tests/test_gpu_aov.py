@@ -7,6 +7,7 @@ import pytest
 
 import aov_checker as K
 import scenes
+from gpu_support import GuardedBuffers, assert_render_unaffected, assert_same_bits, ssml_scene
 
 pytestmark = pytest.mark.gpu
 abi = scenes.abi
@@ -20,15 +21,10 @@ def _lambertian_sky():
     return sc, scenes.ALL_MATERIALS_CAMERA
 
 
-def _ssml(name):
-    ls = scenes.load_ssml(name)
-    return ls.scene, ls.camera_params
-
-
 SCENES = {
-    "rtweekend1": lambda: _ssml("rtweekend1"),
-    "overshadowed": lambda: _ssml("overshadowed"),
-    "pyramid": lambda: _ssml("pyramid"),
+    "rtweekend1": lambda: ssml_scene("rtweekend1"),
+    "overshadowed": lambda: ssml_scene("overshadowed"),
+    "pyramid": lambda: ssml_scene("pyramid"),
     "all_materials": lambda: (scenes.all_materials(), scenes.ALL_MATERIALS_CAMERA),
     "structured_meshes": lambda: (scenes.structured_meshes(), scenes.STRUCTURED_CAMERA),
     "mesh50k": lambda: (scenes.random_triangle_mesh(50_000), scenes.MESH_CAMERA),
@@ -37,20 +33,9 @@ SCENES = {
 SCENES.update({f"random_everything_{seed}": (lambda seed=seed: scenes.random_everything(seed)) for seed in range(12)})
 
 
-def assert_same(a, b, what):
-    assert a.dtype == b.dtype and a.shape == b.shape, (what, a.dtype, b.dtype, a.shape, b.shape)
-    if a.dtype == np.float32:  # bits, but any NaN equals any NaN
-        same = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-    else:
-        same = a == b
-    if not same.all():
-        bad = np.argwhere(~same)
-        pytest.fail(f"{what}: {len(bad)} elements differ, first at {bad[0].tolist()}: gpu {a[tuple(bad[0])]!r} checker {b[tuple(bad[0])]!r}")
-
-
 def assert_aovs_equal(gpu, ref, what):
     for name in ref:
-        assert_same(gpu[name], ref[name], f"{what} {name}")
+        assert_same_bits(gpu[name], ref[name], f"{what} {name}", nan_equal=True)
 
 
 def _reference(sc, cpu, cam, w, h, spp, seed, sample_begin, pixels=None):
@@ -90,7 +75,7 @@ def test_every_channel_subset_gives_the_same_bytes(hb):
             got = gpu.render_aov(cam, opts, channels=subset)
             assert set(got) == set(subset)
             for name in subset:
-                assert_same(got[name], full[name], f"subset {subset} {name}")
+                assert_same_bits(got[name], full[name], f"subset {subset} {name}", nan_equal=True)
 
 
 def test_device_entry_point_on_a_side_stream(hb):
@@ -102,33 +87,21 @@ def test_device_entry_point_on_a_side_stream(hb):
     opts.sample_begin = 3
     ref = gpu.render_aov(cam, opts)
     dev = torch.device("cuda", 0)
-    t = {name: torch.full(ref[name].shape, 7, dtype=torch.int32 if ref[name].dtype == np.uint32 else torch.float32, device=dev)
-         for name in abi.AOV_CHANNELS}
+    run = GuardedBuffers(torch, {name: (ref[name].shape, ref[name].dtype.type) for name in abi.AOV_CHANNELS})
     side = torch.cuda.Stream(device=dev)
     side.wait_stream(torch.cuda.current_stream(dev))
     with torch.cuda.stream(side):
-        gpu.render_aov_device(cam, opts, {name: t[name].data_ptr() for name in abi.AOV_CHANNELS}, stream=side.cuda_stream)
+        gpu.render_aov_device(cam, opts, run.ptrs(), stream=side.cuda_stream)
     side.synchronize()
     for name in abi.AOV_CHANNELS:
-        got = t[name].cpu().numpy()
-        if ref[name].dtype == np.uint32:
-            got = got.view(np.uint32)
-        assert_same(got, ref[name], f"device entry point {name}")
+        assert_same_bits(run.read(name), ref[name], f"device entry point {name}", nan_equal=True)
 
 
 def test_no_side_effects_on_render(hb):
     sc, cam_params = SCENES["overshadowed"]()
     gpu = hb.HipScene(sc, device=0)
     cam = hb.camera_new(**cam_params)
-    opts = abi.default_render_opts(96, 54, 8, method=abi.RT_METHOD_MIS, seed=2)
-    img_a, rays_a = gpu.render(cam, opts)
-    n_a = gpu.last_kernel_ms()[1]
-    info_a = gpu.last_launch_info()
-    gpu.render_aov(cam, opts)
-    assert gpu.last_kernel_ms()[1] == n_a and gpu.last_launch_info() == info_a  # still describe the render
-    img_b, rays_b = gpu.render(cam, opts)
-    assert np.array_equal(img_a, img_b) and rays_a == rays_b
-    assert gpu.last_kernel_ms()[1] == n_a and gpu.last_launch_info() == info_a
+    assert_render_unaffected(gpu, cam, lambda opts, img: gpu.render_aov(cam, opts))
 
 
 def test_multi_device_head_scene(hb):
@@ -149,7 +122,7 @@ def test_albedo_equals_the_render_of_an_all_emit_scene(hb):
         opts.sample_begin = sample_begin
         opts.sample_split = 1
         img, _ = gpu.render(cam, opts)
-        assert_same(gpu.render_aov(cam, opts, channels=("albedo",))["albedo"], img, f"sample_begin={sample_begin}")
+        assert_same_bits(gpu.render_aov(cam, opts, channels=("albedo",))["albedo"], img, f"sample_begin={sample_begin}", nan_equal=True)
 
 
 def test_full_frame_rtweekend1(hb, O):
@@ -167,7 +140,7 @@ def test_full_frame_rtweekend1(hb, O):
     ref = _reference(sc, cpu, O.camera_new(**cam_params), w, h, spp, 1, 0, pixels=pixels)
     flat = {k: v.reshape(w * h, -1) if v.ndim == 3 else v.reshape(w * h) for k, v in got.items()}
     for name in ref:
-        assert_same(flat[name][pixels], ref[name], f"1080p tiles {name}")
+        assert_same_bits(flat[name][pixels], ref[name], f"1080p tiles {name}", nan_equal=True)
     for name in ("albedo", "normal", "depth", "coverage"):
         assert np.isfinite(got[name]).all(), name
     assert ((got["coverage"] >= 0) & (got["coverage"] <= 1)).all()

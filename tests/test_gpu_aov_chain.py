@@ -9,12 +9,13 @@ import pytest
 import aov_chain_checker as KC
 import aov_checker as K
 import scenes
+from gpu_support import (CAMERA_16_9, QUALITY_CAMERA, QUALITY_GLASS, QUALITY_MIRROR, GuardedBuffers, assert_render_unaffected,
+                         assert_same_bits, capture, quality_scene, ssml_scene)
 
 pytestmark = pytest.mark.gpu
 abi = scenes.abi
 W, H, SPP = 64, 36, 4
 F32 = np.float32
-CAMERA_16_9 = float(F32(16.0) / F32(9.0))
 
 
 def nested_and_facing():
@@ -42,21 +43,6 @@ NESTED_CAMERA = dict(origin=(0.0, 1.6, 6.5), lookat=(0.0, 0.7, 0.0), vup=(0.0, 1
                      aperture=0.0, focus_dist=10.0)
 
 
-def quality_scene():
-    """a perfect mirror sphere and a glass sphere over a checker-textured Lambertian floor, lit by the sky and a lamp"""
-    sc = scenes.SceneDescription()
-    sc.sphere((0, -1000, 0), 1000.0, sc.lambertian(sc.checkered((0.9, 0.9, 0.9), (0.2, 0.3, 0.6)), 0.8))
-    sc.sphere((-0.8, 0.6, 0.0), 0.6, sc.reflect(sc.solid((0.95, 0.95, 0.95)), 0.0))
-    sc.sphere((0.8, 0.6, 0.0), 0.6, sc.refract(sc.solid((1.0, 1.0, 1.0)), 1.5))
-    sc.sphere((0.0, 6.0, 3.0), 1.0, sc.emissive(sc.solid((1.0, 0.9, 0.8)), 8.0))
-    sc.set_sky(sc.lerp((0.5, 0.7, 1.0), (1.0, 1.0, 1.0)), (32, 16))
-    return sc
-
-
-QUALITY_CAMERA = dict(origin=(0.0, 2.0, 6.0), lookat=(0.0, 0.8, 0.0), vup=(0.0, 1.0, 0.0), fov=40.0, aspect_ratio=CAMERA_16_9,
-                      aperture=0.0, focus_dist=10.0)
-QUALITY_MIRROR, QUALITY_GLASS = 1, 2  # material indices in quality_scene()
-
 SCENES = {
     "all_materials": lambda: (scenes.all_materials(), scenes.ALL_MATERIALS_CAMERA),
     "nested_and_facing": lambda: (nested_and_facing(), NESTED_CAMERA),
@@ -66,21 +52,10 @@ SCENES.update({f"random_everything_{seed}": (lambda seed=seed: scenes.random_eve
 CHAINS = [(0, 0.0), (1, 0.0), (2, 0.0), (8, 0.0), (1, 1.0), (8, 1.0)]  # (max_chain, fuzz_limit)
 
 
-def assert_same(a, b, what):
-    assert a.dtype == b.dtype and a.shape == b.shape, (what, a.dtype, b.dtype, a.shape, b.shape)
-    if a.dtype == np.float32:  # bits, but any NaN equals any NaN
-        same = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-    else:
-        same = a == b
-    if not same.all():
-        bad = np.argwhere(~same)
-        pytest.fail(f"{what}: {len(bad)} elements differ, first at {bad[0].tolist()}: gpu {a[tuple(bad[0])]!r} checker {b[tuple(bad[0])]!r}")
-
-
 def assert_aovs_equal(gpu, ref, what):
     assert set(gpu) == set(ref), (what, sorted(gpu), sorted(ref))
     for name in ref:
-        assert_same(gpu[name], ref[name], f"{what} {name}")
+        assert_same_bits(gpu[name], ref[name], f"{what} {name}", nan_equal=True)
 
 
 def _reference(sc, cpu, cam, w, h, spp, seed, sample_begin, max_chain, fuzz_limit, pixels=None):
@@ -116,8 +91,7 @@ def test_max_chain_zero_and_scenes_without_delta_surfaces_give_the_first_hit_byt
         if name in SCENES:
             sc, cam_params = SCENES[name]()
         else:
-            ls = scenes.load_ssml(name)
-            sc, cam_params = ls.scene, ls.camera_params
+            sc, cam_params = ssml_scene(name)
         gpu = hb.HipScene(sc, device=0)
         cam = hb.camera_new(**cam_params)
         opts = abi.default_render_opts(W, H, 16, seed=6)
@@ -127,7 +101,7 @@ def test_max_chain_zero_and_scenes_without_delta_surfaces_give_the_first_hit_byt
         for max_chain in chains:
             got = gpu.render_aov_chain(cam, opts, max_chain=max_chain, fuzz_limit=1.0)
             for ch in abi.AOV_CHANNELS:
-                assert_same(got[ch], first[ch], f"{name} max_chain={max_chain} {ch}")
+                assert_same_bits(got[ch], first[ch], f"{name} max_chain={max_chain} {ch}", nan_equal=True)
             assert (got["bounces"] == 0.0).all()
 
 
@@ -142,7 +116,7 @@ def test_every_channel_subset_gives_the_same_bytes(hb):
             got = gpu.render_aov_chain(cam, opts, channels=subset)
             assert set(got) == set(subset)
             for name in subset:
-                assert_same(got[name], full[name], f"subset {subset} {name}")
+                assert_same_bits(got[name], full[name], f"subset {subset} {name}", nan_equal=True)
 
 
 @pytest.mark.parametrize("size", [(2, 2), (3, 5), (9, 7), (65, 37)])
@@ -174,41 +148,16 @@ def test_tiles_of_a_1080p_frame(hb, O):
     ref = _reference(sc, cpu, O.camera_new(**cam_params), w, h, spp, 1, 0, 8, 0.0, pixels=pixels)
     flat = {k: v.reshape(w * h, -1) if v.ndim == 3 else v.reshape(w * h) for k, v in got.items()}
     for name in ref:
-        assert_same(flat[name][pixels], ref[name], f"1080p tiles {name}")
+        assert_same_bits(flat[name][pixels], ref[name], f"1080p tiles {name}", nan_equal=True)
     assert len(glass) > 0 and ref["bounces"].max() >= 2.0
     assert ((got["primitive"] == abi.AOV_NO_ID) == (got["material"] == abi.AOV_NO_ID)).all()
 
 
-class DeviceChain:
+def device_chain(torch, w, h, off=0):
     """device buffers `off` floats past an aligned base, with guard values before and after every channel"""
-    GUARD = 0x5A5A5A5A
-
-    def __init__(self, torch, w, h, off=0):
-        self.torch, self.w, self.h, self.off = torch, w, h, off
-        dev = torch.device("cuda", 0)
-        self.buf, self.n = {}, {}
-        for name in abi.AOV_CHAIN_CHANNELS:
-            self.n[name] = w * h * (3 if name in ("albedo", "normal") else 1)
-            self.buf[name] = torch.full((self.n[name] + 2 * 8,), self.GUARD, dtype=torch.int32, device=dev)
-
-    def ptrs(self, channels=abi.AOV_CHAIN_CHANNELS):
-        return {name: self.buf[name].data_ptr() + 4 * (4 + self.off) for name in channels}
-
-    def refill(self):
-        for t in self.buf.values():
-            t.fill_(self.GUARD)
-
-    def read(self):
-        out = {}
-        for name, t in self.buf.items():
-            a = t.cpu().numpy().view(np.uint32)
-            lo, hi = 4 + self.off, 4 + self.off + self.n[name]
-            assert (a[:lo] == self.GUARD).all() and (a[hi:] == self.GUARD).all(), f"{name}: a guard value was overwritten"
-            body = a[lo:hi].copy()
-            if name not in ("primitive", "material"):
-                body = body.view(np.float32)
-            out[name] = body.reshape((self.h, self.w, 3) if name in ("albedo", "normal") else (self.h, self.w))
-        return out
+    return GuardedBuffers(torch, {name: ((h, w, 3) if name in ("albedo", "normal") else (h, w),
+                                         np.uint32 if name in ("primitive", "material") else np.float32)
+                                  for name in abi.AOV_CHAIN_CHANNELS}, off=off)
 
 
 def test_device_entry_equals_host_entry_off_alignment_with_guards(hb):
@@ -221,19 +170,19 @@ def test_device_entry_equals_host_entry_off_alignment_with_guards(hb):
     opts.sample_begin = 3
     ref = gpu.render_aov_chain(cam, opts, max_chain=6, fuzz_limit=0.5)
     for off in (0, 1, 3):
-        run = DeviceChain(torch, w, h, off)
+        run = device_chain(torch, w, h, off)
         torch.cuda.synchronize()
         gpu.render_aov_chain_device(cam, opts, run.ptrs(), max_chain=6, fuzz_limit=0.5)
         torch.cuda.synchronize()
-        assert_aovs_equal(run.read(), ref, f"device entry off={off}")
-    run = DeviceChain(torch, w, h, 1)  # a subset: the other buffers stay untouched
+        assert_aovs_equal(run.read_all(), ref, f"device entry off={off}")
+    run = device_chain(torch, w, h, 1)  # a subset: the other buffers stay untouched
     torch.cuda.synchronize()
     gpu.render_aov_chain_device(cam, opts, run.ptrs(("depth", "bounces")), max_chain=6, fuzz_limit=0.5)
     torch.cuda.synchronize()
-    got = run.read()
-    assert_same(got["depth"], ref["depth"], "subset depth")
-    assert_same(got["bounces"], ref["bounces"], "subset bounces")
-    assert (got["material"] == DeviceChain.GUARD).all() and (got["albedo"].view(np.uint32) == DeviceChain.GUARD).all()
+    got = run.read_all()
+    assert_same_bits(got["depth"], ref["depth"], "subset depth", nan_equal=True)
+    assert_same_bits(got["bounces"], ref["bounces"], "subset bounces", nan_equal=True)
+    assert (got["material"] == run.guard).all() and (got["albedo"].view(np.uint32) == run.guard).all()
 
 
 def test_determinism_across_streams(hb):
@@ -245,14 +194,14 @@ def test_determinism_across_streams(hb):
     ref = gpu.render_aov_chain(cam, opts, fuzz_limit=1.0)
     dev = torch.device("cuda", 0)
     streams = [torch.cuda.Stream(device=dev) for _ in range(3)]
-    runs = [DeviceChain(torch, W, H) for _ in streams]
+    runs = [device_chain(torch, W, H) for _ in streams]
     torch.cuda.synchronize()
     for _ in range(2):
         for s, run in zip(streams, runs):  # in flight together
             gpu.render_aov_chain_device(cam, opts, run.ptrs(), stream=s.cuda_stream, fuzz_limit=1.0)
     torch.cuda.synchronize()
     for i, run in enumerate(runs):
-        assert_aovs_equal(run.read(), ref, f"stream {i}")
+        assert_aovs_equal(run.read_all(), ref, f"stream {i}")
 
 
 def test_graph_captured_from_the_first_call_replays_the_eager_bytes(hb):
@@ -263,36 +212,23 @@ def test_graph_captured_from_the_first_call_replays_the_eager_bytes(hb):
     cam = hb.camera_new(**cam_params)
     opts = abi.default_render_opts(W, H, 6, seed=17)
     dev = torch.device("cuda", 0)
-    run = DeviceChain(torch, W, H)
-    side = torch.cuda.Stream(device=dev)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        gpu.render_aov_chain_device(cam, opts, run.ptrs(), stream=torch.cuda.current_stream(dev).cuda_stream)
-    torch.cuda.synchronize(dev)
-    assert all((t.cpu().numpy().view(np.uint32) == DeviceChain.GUARD).all() for t in run.buf.values())  # capture ran nothing
+    run = device_chain(torch, W, H)
+    g = capture(torch, lambda stream: gpu.render_aov_chain_device(cam, opts, run.ptrs(), stream=stream))
+    assert all(run.untouched(name) for name in run.buf)  # capture ran nothing
     eager = gpu.render_aov_chain(cam, opts)
     for _ in range(2):
         run.refill()
         torch.cuda.synchronize(dev)
         g.replay()
         torch.cuda.synchronize(dev)
-        assert_aovs_equal(run.read(), eager, "graph replay")
+        assert_aovs_equal(run.read_all(), eager, "graph replay")
 
 
 def test_no_side_effects_on_render(hb):
-    ls = scenes.load_ssml("overshadowed")
-    gpu = hb.HipScene(ls.scene, device=0)
-    cam = hb.camera_new(**ls.camera_params)
-    opts = abi.default_render_opts(96, 54, 8, method=abi.RT_METHOD_MIS, seed=2)
-    img_a, rays_a = gpu.render(cam, opts)
-    n_a = gpu.last_kernel_ms()[1]
-    info_a = gpu.last_launch_info()
-    gpu.render_aov_chain(cam, opts)
-    assert gpu.last_kernel_ms()[1] == n_a and gpu.last_launch_info() == info_a  # still describe the render
-    img_b, rays_b = gpu.render(cam, opts)
-    assert np.array_equal(img_a, img_b) and rays_a == rays_b
-    assert gpu.last_kernel_ms()[1] == n_a and gpu.last_launch_info() == info_a
+    sc, cam_params = ssml_scene("overshadowed")
+    gpu = hb.HipScene(sc, device=0)
+    cam = hb.camera_new(**cam_params)
+    assert_render_unaffected(gpu, cam, lambda opts, img: gpu.render_aov_chain(cam, opts))
 
 
 def test_multi_device_head_scene(hb):
@@ -303,11 +239,11 @@ def test_multi_device_head_scene(hb):
     opts = abi.default_render_opts(W, H, 8, seed=6)
     ref = single.render_aov_chain(cam, opts, fuzz_limit=1.0)
     assert_aovs_equal(multi.render_aov_chain(cam, opts, fuzz_limit=1.0), ref, "devices=[0, 0]")
-    run = DeviceChain(torch, W, H)
+    run = device_chain(torch, W, H)
     torch.cuda.synchronize()
     multi.render_aov_chain_device(cam, opts, run.ptrs(), fuzz_limit=1.0)
     torch.cuda.synchronize()
-    assert_aovs_equal(run.read(), ref, "devices=[0, 0] device entry")
+    assert_aovs_equal(run.read_all(), ref, "devices=[0, 0] device entry")
 
 
 # ---- quality: the protocol of the denoiser's test (display-space MSE against a 4096-pass render, 320 x 180, 16 MIS passes) ----

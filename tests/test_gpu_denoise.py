@@ -8,29 +8,11 @@ import pytest
 
 import denoise_checker as K
 import scenes
+from gpu_support import assert_render_unaffected, capture
+from post_runners import SCENES, TOL, check_against_checker, device_run, display_mse, rendered_inputs, synthetic
 
 pytestmark = pytest.mark.gpu
 abi = scenes.abi
-
-# The GPU filters in f32 with the device's expf / powf / sqrtf, the checker in float64: every output pixel must satisfy
-#   |gpu - ref| / (|ref| + 1e-3 * mean|ref|) <= 1e-4
-# A wrong tap, weight or border rule misses this by orders of magnitude.
-TOL = 1e-4
-
-
-def _ssml(name):
-    ls = scenes.load_ssml(name)
-    return ls.scene, ls.camera_params
-
-
-SCENES = {
-    "rtweekend1": lambda: _ssml("rtweekend1"),
-    "overshadowed": lambda: _ssml("overshadowed"),
-    "pyramid": lambda: _ssml("pyramid"),
-    "all_materials": lambda: (scenes.all_materials(), scenes.ALL_MATERIALS_CAMERA),
-    "structured_meshes": lambda: (scenes.structured_meshes(), scenes.STRUCTURED_CAMERA),
-}
-SCENES.update({f"random_everything_{seed}": (lambda seed=seed: scenes.random_everything(seed)) for seed in range(4)})
 
 INPUT_SETS = {
     "all": ("albedo", "normal", "depth", "variance"),
@@ -39,27 +21,6 @@ INPUT_SETS = {
     "no_depth": ("albedo", "normal", "variance"),
     "no_variance": ("albedo", "normal", "depth"),
 }
-
-
-def rendered_inputs(gpu, cam, w, h, spp=8, seed=3, method=abi.RT_METHOD_MIS):
-    """color (rt_render of spp passes), the AOVs of the same passes, and the two-halves variance of passes [0, spp/2), [spp/2, spp)"""
-    opts = abi.default_render_opts(w, h, spp, method=method, seed=seed)
-    color, _ = gpu.render(cam, opts)
-    aov = gpu.render_aov(cam, opts, channels=("albedo", "normal", "depth"))
-    halves = []
-    for begin in (0, spp // 2):
-        o = abi.default_render_opts(w, h, spp // 2, method=method, seed=seed)
-        o.sample_begin = begin
-        halves.append(gpu.render(cam, o)[0])
-    return dict(color=color, variance=K.halves_variance(halves[0], halves[1], aov["albedo"]), **aov)
-
-
-def check_against_checker(gpu_out, inputs, what, **opts):
-    ref = K.denoise(inputs["color"], inputs.get("albedo"), inputs.get("normal"), inputs.get("depth"), inputs.get("variance"), **opts)
-    assert gpu_out.dtype == np.float32 and gpu_out.shape == ref.shape
-    err = K.relative_error(gpu_out, ref)
-    assert err <= TOL, f"{what}: relative error {err:.3e}"
-    return ref
 
 
 @pytest.mark.parametrize("name", list(SCENES))
@@ -78,14 +39,6 @@ def test_gpu_matches_the_checker(hb, name):
                     assert K.relative_error(full["color"], ref) > 1e-3
 
 
-def _synthetic(h, w, seed=0):
-    rng = np.random.default_rng(seed)
-    n = rng.normal(size=(h, w, 3)).astype(np.float32)
-    return dict(color=rng.uniform(0.0, 2.0, (h, w, 3)).astype(np.float32), albedo=rng.uniform(0, 1, (h, w, 3)).astype(np.float32),
-                normal=n, depth=rng.uniform(0.5, 3.0, (h, w)).astype(np.float32),
-                variance=rng.uniform(0, 0.2, (h, w)).astype(np.float32))
-
-
 @pytest.fixture(scope="module")
 def dev_scene(hb):
     sc, cam_params = SCENES["rtweekend1"]()
@@ -95,7 +48,7 @@ def dev_scene(hb):
 @pytest.mark.parametrize("w,h", [(1, 1), (1, 9), (9, 1), (7, 5)])
 def test_tiny_frames(hb, dev_scene, w, h):
     gpu, _ = dev_scene
-    full = _synthetic(h, w, seed=w * 10 + h)
+    full = synthetic(h, w, seed=w * 10 + h)
     for keys in INPUT_SETS.values():
         inputs = {"color": full["color"], **{k: full[k] for k in keys}}
         check_against_checker(gpu.denoise(**inputs, iterations=5), inputs, f"{w}x{h} {keys}", iterations=5)
@@ -104,7 +57,7 @@ def test_tiny_frames(hb, dev_scene, w, h):
 def test_nan_and_inf_pixels_pass_through(hb, dev_scene):
     gpu, _ = dev_scene
     h, w = 24, 40
-    full = _synthetic(h, w, seed=7)
+    full = synthetic(h, w, seed=7)
     for keys in (INPUT_SETS["all"], INPUT_SETS["no_variance"]):
         inputs = {"color": full["color"].copy(), **{k: full[k] for k in keys}}
         inputs["color"][5, 7, 0] = np.nan
@@ -163,18 +116,6 @@ def test_invalid_arguments_on_a_device_scene(hb, dev_scene):
     assert e.value.code == abi.RT_ERR_INVALID_ARGUMENT
 
 
-def _device_run(torch, hb, gpu, inputs, opts, stream):
-    """rt_denoise_device on `stream` over torch copies of `inputs`; returns the output as numpy"""
-    dev = torch.device("cuda", 0)
-    t = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in inputs.items()}
-    ws = torch.empty(hb.denoise_workspace_bytes(opts), dtype=torch.uint8, device=dev)
-    out = torch.full(inputs["color"].shape, 7.0, dtype=torch.float32, device=dev)
-    torch.cuda.synchronize(dev)
-    gpu.denoise_device({k: v.data_ptr() for k, v in t.items()}, ws.data_ptr(), out.data_ptr(), opts, stream=stream)
-    torch.cuda.synchronize(dev)
-    return out.cpu().numpy()
-
-
 def test_determinism_and_entry_points_agree(hb, dev_scene):
     import torch
     gpu, cam = dev_scene
@@ -183,14 +124,14 @@ def test_determinism_and_entry_points_agree(hb, dev_scene):
     a, b = gpu.denoise(**inputs), gpu.denoise(**inputs)
     assert a.tobytes() == b.tobytes()
     opts = hb.denoise_opts(w, h)
-    assert _device_run(torch, hb, gpu, inputs, opts, 0).tobytes() == a.tobytes()
+    assert device_run(torch, hb, gpu, inputs, opts, 0).tobytes() == a.tobytes()
     side = torch.cuda.Stream(device=torch.device("cuda", 0))
-    assert _device_run(torch, hb, gpu, inputs, opts, side.cuda_stream).tobytes() == a.tobytes()
+    assert device_run(torch, hb, gpu, inputs, opts, side.cuda_stream).tobytes() == a.tobytes()
     no_var = {k: v for k, v in inputs.items() if k != "variance"}
-    assert _device_run(torch, hb, gpu, no_var, opts, side.cuda_stream).tobytes() == gpu.denoise(**no_var).tobytes()
+    assert device_run(torch, hb, gpu, no_var, opts, side.cuda_stream).tobytes() == gpu.denoise(**no_var).tobytes()
     sc, _ = SCENES["rtweekend1"]()
     multi = hb.HipScene(sc, devices=[0, 0])
-    assert _device_run(torch, hb, multi, inputs, opts, 0).tobytes() == a.tobytes()
+    assert device_run(torch, hb, multi, inputs, opts, 0).tobytes() == a.tobytes()
     assert multi.denoise(**inputs).tobytes() == a.tobytes()
 
 
@@ -223,11 +164,6 @@ def test_render_denoised_is_its_parts(hb, sample_begin, sample_split):
     assert clean3.tobytes() == gpu.denoise(noisy, aov, variance=var, iterations=3).tobytes()
 
 
-def _display_mse(img, ref):
-    f = lambda a: np.clip(a.astype(np.float64), 0.0, 1.0) ** (1 / 2.2)  # noqa: E731
-    return float(((f(img) - f(ref)) ** 2).mean())
-
-
 QUALITY = {"rtweekend1": 0.5, "overshadowed": 0.7}
 
 
@@ -239,7 +175,7 @@ def test_quality_against_a_converged_render(hb, name):
     w, h = 320, 180
     ref, _ = gpu.render(cam, abi.default_render_opts(w, h, 4096, method=abi.RT_METHOD_MIS, seed=99))
     clean, noisy, _ = gpu.render_denoised(cam, abi.default_render_opts(w, h, 16, method=abi.RT_METHOD_MIS, seed=1))
-    mse_noisy, mse_clean = _display_mse(noisy, ref), _display_mse(clean, ref)
+    mse_noisy, mse_clean = display_mse(noisy, ref), display_mse(clean, ref)
     ratio = mse_clean / mse_noisy
     mean_shift = abs(float(clean.astype(np.float64).mean()) / float(noisy.astype(np.float64).mean()) - 1.0)
     print(f"{name}: display MSE noisy {mse_noisy:.4e} clean {mse_clean:.4e} ratio {ratio:.3f}; mean radiance shift {mean_shift:.4f}")
@@ -251,15 +187,12 @@ def test_no_side_effects_on_render(hb):
     sc, cam_params = SCENES["overshadowed"]()
     gpu = hb.HipScene(sc, device=0)
     cam = hb.camera_new(**cam_params)
-    opts = abi.default_render_opts(96, 54, 8, method=abi.RT_METHOD_MIS, seed=2)
-    img_a, rays_a = gpu.render(cam, opts)
-    n_a = gpu.last_kernel_ms()[1]
-    info_a = gpu.last_launch_info()
-    gpu.denoise(img_a)
-    gpu.denoise(img_a, albedo=np.ones_like(img_a), variance=np.zeros(img_a.shape[:2], np.float32))
-    assert gpu.last_kernel_ms()[1] == n_a and gpu.last_launch_info() == info_a
-    img_b, rays_b = gpu.render(cam, opts)
-    assert img_a.tobytes() == img_b.tobytes() and rays_a == rays_b
+
+    def both_calls(opts, img):
+        gpu.denoise(img)
+        gpu.denoise(img, albedo=np.ones_like(img), variance=np.zeros(img.shape[:2], np.float32))
+
+    assert_render_unaffected(gpu, cam, both_calls)
 
 
 def test_render_aov_and_denoise_are_graph_capturable(hb):
@@ -291,9 +224,7 @@ def test_render_aov_and_denoise_are_graph_capturable(hb):
     img, _ = gpu.render(cam, opts)
     a = gpu.render_aov(cam, opts, channels=("albedo", "normal", "depth"))
     assert direct.tobytes() == gpu.denoise(img, a).tobytes()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=side):
-        launch_all(torch.cuda.current_stream(dev).cuda_stream)
+    graph = capture(torch, launch_all, side=side)
     for _ in range(2):
         for t in (color, out, *aov.values()):
             t.fill_(7)

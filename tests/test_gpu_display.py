@@ -9,7 +9,8 @@ import pytest
 
 import display_checker as D
 import scenes
-from test_gpu_denoise import SCENES
+from gpu_support import assert_render_unaffected, capture, load_gpu
+from post_runners import SCENES, DeviceDisplay, check_display, same_state, state_tuple
 
 pytestmark = pytest.mark.gpu
 abi = scenes.abi
@@ -17,90 +18,16 @@ F32 = np.float32
 FRAME_SCENES = ["rtweekend1", "overshadowed", "all_materials"]
 
 
-def _load(hb, name, devices=None):
-    sc, cam_params = SCENES[name]()
-    gpu = hb.HipScene(sc, devices=devices) if devices else hb.HipScene(sc, device=0)
-    return gpu, cam_params
-
-
 def render(hb, gpu, p, w, h, spp=8, seed=3):
     img, _ = gpu.render(hb.camera_new(**p), abi.default_render_opts(w, h, spp, method=abi.RT_METHOD_MIS, seed=seed))
     return img
-
-
-def state_array(st):
-    """(ev, frames, metered) -> the 16 bytes of an rt_display_state"""
-    a = np.zeros(4, np.uint32)
-    a[0] = np.array([st[0]], F32).view(np.uint32)[0]
-    a[1] = st[1]
-    a[2] = np.array([st[2]], F32).view(np.uint32)[0]
-    return a
-
-
-def state_tuple(a):
-    a = np.asarray(a, np.uint32)
-    return (a[0:1].view(F32)[0], int(a[1]), a[2:3].view(F32)[0])
-
-
-def same_state(a, b):
-    return (np.array([a[0]], F32).view(np.uint32)[0] == np.array([b[0]], F32).view(np.uint32)[0] and a[1] == b[1]
-            and ((np.isnan(a[2]) and np.isnan(b[2])) or np.array([a[2]], F32).view(np.uint32)[0] == np.array([b[2]], F32).view(np.uint32)[0]))
-
-
-class DeviceDisplay:
-    """rt_display_device over torch buffers; in_off / out_off shift the input (floats) and the output (bytes) off 16-byte alignment"""
-
-    def __init__(self, torch, hb, gpu, w, h, in_off=0, out_off=0, **opts):
-        self.torch, self.gpu, self.w, self.h, self.in_off, self.out_off = torch, gpu, w, h, in_off, out_off
-        self.dev = torch.device("cuda", 0)
-        self.opts = hb.display_opts(w, h, **opts)
-        self.nbytes = hb.display_output_bytes(self.opts)
-        self.src = torch.zeros(w * h * 3 + 4, dtype=torch.float32, device=self.dev)
-        self.ws = torch.full((hb.display_workspace_bytes(self.opts),), 0xA5, dtype=torch.uint8, device=self.dev)
-        self.out = torch.full((self.nbytes + 16,), 0x5A, dtype=torch.uint8, device=self.dev)
-        self.hist = torch.zeros(256, dtype=torch.int32, device=self.dev)
-        self.state = torch.zeros(4, dtype=torch.int32, device=self.dev)
-
-    def upload(self, img, state=None):
-        n = img.size
-        self.src[self.in_off:self.in_off + n] = self.torch.from_numpy(np.ascontiguousarray(img, F32).ravel()).to(self.dev)
-        if state is not None:
-            self.state.copy_(self.torch.from_numpy(state_array(state).view(np.int32)).to(self.dev))
-
-    def launch(self, use_state=True, stream=0):
-        self.gpu.display_device(self.src.data_ptr() + 4 * self.in_off, self.opts, self.state.data_ptr() if use_state else 0,
-                                self.ws.data_ptr(), self.out.data_ptr() + self.out_off, self.hist.data_ptr(), stream=stream)
-
-    def read(self):
-        self.torch.cuda.synchronize(self.dev)
-        o = self.out.cpu().numpy()
-        assert (o[:self.out_off] == 0x5A).all() and (o[self.out_off + self.nbytes:] == 0x5A).all(), "wrote outside the output"
-        px = o[self.out_off:self.out_off + self.nbytes].reshape(self.h, self.w, -1)
-        return px, self.hist.cpu().numpy().view(np.uint32), state_tuple(self.state.cpu().numpy().view(np.uint32))
-
-    def __call__(self, img, state=None):
-        self.upload(img, state)
-        self.torch.cuda.synchronize(self.dev)
-        self.launch(use_state=state is not None)
-        return self.read()
-
-
-def check(O, run, img, state, what, **opts):
-    px, hist, st = run(img, state)
-    ref_px, ref_hist, ref_st = D.display(O, img, state, **opts)
-    assert np.array_equal(hist, ref_hist), f"{what}: histogram"
-    assert px.shape == ref_px.shape and np.array_equal(px, ref_px), \
-        f"{what}: {int((px != ref_px).sum())} bytes differ"
-    if state is not None:
-        assert same_state(st, ref_st), f"{what}: state {st} vs {ref_st}"
-    return px, ref_st
 
 
 @pytest.fixture(scope="module")
 def frames(hb):
     out = {}
     for name in FRAME_SCENES:
-        gpu, p = _load(hb, name)
+        gpu, p = load_gpu(hb, SCENES, name)
         out[name] = render(hb, gpu, p, 33, 17)
         gpu.close()
     return out
@@ -112,7 +39,7 @@ COMBOS = list(itertools.product(range(4), range(3), range(3), range(3)))
 @pytest.mark.parametrize("tonemap,transfer,quantiser,fmt", COMBOS)
 def test_every_combination_matches_the_checker(hb, O, frames, tonemap, transfer, quantiser, fmt):
     import torch
-    gpu, _ = _load(hb, "rtweekend1")
+    gpu, _ = load_gpu(hb, SCENES, "rtweekend1")
     kw = dict(tonemap=tonemap, transfer=transfer, quantiser=quantiser, pixel_format=fmt, seed=0x1234567890AB, white=3.0, gamma=1.8)
     for name, img in frames.items():
         for (h, w), (in_off, out_off) in itertools.product(((17, 33), (5, 7), (1, 1)), ((0, 0), (1, 3))):
@@ -122,7 +49,7 @@ def test_every_combination_matches_the_checker(hb, O, frames, tonemap, transfer,
                                         ("adapting", (F32(1.25), 5, F32(-3.0)), dict(adaptation=0.3)),
                                         ("no state", None, dict(exposure_mode=D.FIXED, exposure_ev=-0.5))):
                 run = DeviceDisplay(torch, hb, gpu, w, h, in_off, out_off, **kw, **extra)
-                check(O, run, crop, state, f"{what} {label}", **kw, **extra)
+                check_display(O, run, crop, state, f"{what} {label}", **kw, **extra)
 
 
 @pytest.mark.parametrize("kw", [dict(), dict(tonemap="hable", transfer="gamma", quantiser="round", pixel_format="bgra8"),
@@ -131,25 +58,25 @@ def test_every_combination_matches_the_checker(hb, O, frames, tonemap, transfer,
                                 dict(tonemap="reinhard", transfer="linear", quantiser="dither", pixel_format="rgb8", seed=9)])
 def test_1080p(hb, O, kw):
     import torch
-    gpu, p = _load(hb, "rtweekend1")
+    gpu, p = load_gpu(hb, SCENES, "rtweekend1")
     w, h = 1920, 1080
     img = render(hb, gpu, p, w, h, spp=1)
     opts = {k: abi.DISPLAY_ENUMS[k][v] if isinstance(v, str) else v for k, v in kw.items()}
     for in_off, out_off in ((0, 0), (1, 1)):
         run = DeviceDisplay(torch, hb, gpu, w, h, in_off, out_off, **opts)
-        check(O, run, img, (F32(0.5), 2, F32(0)), f"1080p offsets {in_off},{out_off}", **opts)
+        check_display(O, run, img, (F32(0.5), 2, F32(0)), f"1080p offsets {in_off},{out_off}", **opts)
 
 
 def test_auto_sequence_with_a_brightness_step(hb, O):
     import torch
-    gpu, p = _load(hb, "all_materials")
+    gpu, p = load_gpu(hb, SCENES, "all_materials")
     w, h = 64, 36
     base = render(hb, gpu, p, w, h, spp=8)
     run = DeviceDisplay(torch, hb, gpu, w, h, adaptation=0.3)
     state, evs = (F32(0), 0, F32(0)), []
     for i in range(8):
         img = base * F32(16.0) if i >= 4 else base
-        _, state = check(O, run, img, state, f"frame {i}", adaptation=0.3)
+        _, state = check_display(O, run, img, state, f"frame {i}", adaptation=0.3)
         evs.append(float(state[0]))
     assert evs[0] == evs[1] == evs[2] == evs[3]  # snapped at frame 0, then steady
     target = float(D.exposure(D.histogram(base * F32(16.0))[0])[0])
@@ -162,7 +89,7 @@ def test_auto_sequence_with_a_brightness_step(hb, O):
 def test_device_state_advances_on_the_device(hb, O):
     """no upload between calls: the stage reads back what it wrote"""
     import torch
-    gpu, p = _load(hb, "overshadowed")
+    gpu, p = load_gpu(hb, SCENES, "overshadowed")
     w, h = 64, 36
     img = render(hb, gpu, p, w, h)
     run = DeviceDisplay(torch, hb, gpu, w, h, adaptation=0.5, exposure_ev=1.0)
@@ -180,7 +107,7 @@ def test_device_state_advances_on_the_device(hb, O):
 @pytest.mark.parametrize("gamma", [2.2, 1.0, 0.5])
 def test_identity_with_output_rgb8_device(hb, gamma):
     import torch
-    gpu, p = _load(hb, "rtweekend1")
+    gpu, p = load_gpu(hb, SCENES, "rtweekend1")
     dev = torch.device("cuda", 0)
     frame = render(hb, gpu, p, 64, 36) * F32(3.0)
     for w, h in ((64, 36), (33, 17), (1, 1)):
@@ -201,7 +128,7 @@ def test_identity_with_output_rgb8_device(hb, gamma):
 
 def test_host_entry_equals_device_entry(hb, O):
     import torch
-    gpu, p = _load(hb, "all_materials")
+    gpu, p = load_gpu(hb, SCENES, "all_materials")
     w, h = 48, 27
     imgs = [render(hb, gpu, p, w, h, spp=2 + i, seed=i) * F32(1 + 3 * (i % 2)) for i in range(4)]
     kw = dict(adaptation=0.4, seed=77)
@@ -233,7 +160,7 @@ def test_host_entry_equals_device_entry(hb, O):
 
 def test_graph_replay_equals_eager(hb, O):
     import torch
-    gpu, p = _load(hb, "overshadowed")
+    gpu, p = load_gpu(hb, SCENES, "overshadowed")
     w, h = 96, 54
     img = render(hb, gpu, p, w, h)
     kw = dict(adaptation=0.5, seed=3)
@@ -245,13 +172,8 @@ def test_graph_replay_equals_eager(hb, O):
         torch.cuda.synchronize()
         run.launch()
         eager.append(run.read())
-    side = torch.cuda.Stream(device=run.dev)
     run.upload(img, start)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        run.launch(stream=torch.cuda.current_stream(run.dev).cuda_stream)
-    torch.cuda.synchronize()
+    g = capture(torch, lambda stream: run.launch(stream=stream))
     assert state_tuple(run.state.cpu().numpy().view(np.uint32))[1] == 1  # capture ran nothing
     for k in range(3):
         run.out.fill_(0x5A)
@@ -269,7 +191,7 @@ def test_graph_replay_equals_eager(hb, O):
 def test_frame_graph_render_aov_temporal_display(hb, O):
     """render, AOV, rt_denoise_temporal_device and the display on one stream, captured once, replayed with the checker's bytes"""
     import torch
-    gpu, p = _load(hb, "all_materials")
+    gpu, p = load_gpu(hb, SCENES, "all_materials")
     w, h = 160, 90
     dev = torch.device("cuda", 0)
     cam = hb.camera_new(**p)
@@ -282,7 +204,6 @@ def test_frame_graph_render_aov_temporal_display(hb, O):
     tws = torch.empty(hb.temporal_workspace_bytes(topts), dtype=torch.uint8, device=dev)
     clean = torch.zeros(h * w * 3, dtype=torch.float32, device=dev)
     disp = DeviceDisplay(torch, hb, gpu, w, h, adaptation=0.3)
-    side = torch.cuda.Stream(device=dev)
 
     def frame(stream_handle):
         gpu.render_device(cam, ropts, color.data_ptr(), rays.data_ptr(), stream_handle)
@@ -292,11 +213,7 @@ def test_frame_graph_render_aov_temporal_display(hb, O):
         gpu.display_device(clean.data_ptr(), disp.opts, disp.state.data_ptr(), disp.ws.data_ptr(), disp.out.data_ptr(),
                            disp.hist.data_ptr(), stream=stream_handle)
 
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        frame(torch.cuda.current_stream(dev).cuda_stream)
-    torch.cuda.synchronize()
+    g = capture(torch, frame)
     state = (F32(0), 0, F32(0))
     for k in range(2):
         clean.fill_(7)
@@ -309,22 +226,19 @@ def test_frame_graph_render_aov_temporal_display(hb, O):
 
 
 def test_no_side_effects_on_render(hb):
-    gpu, p = _load(hb, "overshadowed")
+    gpu, p = load_gpu(hb, SCENES, "overshadowed")
     cam = hb.camera_new(**p)
-    opts = abi.default_render_opts(96, 54, 8, method=abi.RT_METHOD_MIS, seed=2)
-    img_a, rays_a = gpu.render(cam, opts)
-    n_a = gpu.last_kernel_ms()[1]
-    info_a = gpu.last_launch_info()
-    gpu.display(img_a)
-    gpu.display(img_a, tonemap="hable", pixel_format="rgb8")
-    assert gpu.last_kernel_ms()[1] == n_a and gpu.last_launch_info() == info_a
-    img_b, rays_b = gpu.render(cam, opts)
-    assert img_a.tobytes() == img_b.tobytes() and rays_a == rays_b
+
+    def both_calls(opts, img):
+        gpu.display(img)
+        gpu.display(img, tonemap="hable", pixel_format="rgb8")
+
+    assert_render_unaffected(gpu, cam, both_calls)
 
 
 def test_multi_device_head_runs_on_the_first_device(hb):
-    single, p = _load(hb, "rtweekend1")
-    multi, _ = _load(hb, "rtweekend1", devices=[0, 0])
+    single, p = load_gpu(hb, SCENES, "rtweekend1")
+    multi, _ = load_gpu(hb, SCENES, "rtweekend1", devices=[0, 0])
     img = render(hb, single, p, 96, 54)
     for i in range(3):
         a = multi.display(img * F32(1 + i), adaptation=0.5)

@@ -9,6 +9,7 @@ import pytest
 import aov_checker as K
 import matte_checker as M
 import scenes
+from gpu_support import GuardedBuffers, assert_render_unaffected, assert_same_bits, capture, ssml_scene
 
 pytestmark = pytest.mark.gpu
 abi = scenes.abi
@@ -16,11 +17,7 @@ F32 = np.float32
 W, H, SPP = 64, 36, 16
 SKY = abi.AOV_NO_ID
 KINDS = ("primitive", "material")
-
-
-def _ssml(name):
-    ls = scenes.load_ssml(name)
-    return ls.scene, ls.camera_params
+OUTPUTS = ("ids", "coverage", "residual")  # of rt_render_matte_device
 
 
 SCENES = {
@@ -28,7 +25,7 @@ SCENES = {
     "all_materials": lambda: (scenes.all_materials(), scenes.ALL_MATERIALS_CAMERA),
     "spheres500": lambda: (scenes.random_spheres(500), scenes.MESH_CAMERA),
     "mesh2000": lambda: (scenes.random_triangle_mesh(2000), scenes.MESH_CAMERA),
-    "pyramid": lambda: _ssml("pyramid"),
+    "pyramid": lambda: ssml_scene("pyramid"),
     # triangles two units wide: a pixel of a 16 x 9 frame sees more than eight of them (the overflow case; chosen with the oracle)
     "mesh2000_wide": lambda: (scenes.random_triangle_mesh(2000, edge=2.0), scenes.MESH_CAMERA),
 }
@@ -63,21 +60,13 @@ def _reference(hb, name, kind, w, h, spp, seed, sample_begin, layers=8):
     return ref
 
 
-def assert_same(a, b, what):
-    assert a.dtype == b.dtype and a.shape == b.shape, (what, a.dtype, b.dtype, a.shape, b.shape)
-    same = a.view(np.uint32) == b.view(np.uint32)
-    if not same.all():
-        bad = np.argwhere(~same)
-        pytest.fail(f"{what}: {len(bad)} elements differ, first at {bad[0].tolist()}: gpu {a[tuple(bad[0])]!r} checker {b[tuple(bad[0])]!r}")
-
-
 def assert_layers_equal(got, ref, what):
     """got: the dict of HipScene.render_matte; ref: the checker's flat (ids, coverage, residual)"""
     k, h, w = got["ids"].shape
-    assert_same(got["ids"].reshape(k, -1), ref[0], f"{what} ids")
-    assert_same(got["coverage"].reshape(k, -1), ref[1], f"{what} coverage")
+    assert_same_bits(got["ids"].reshape(k, -1), ref[0], f"{what} ids", nan_equal=False)
+    assert_same_bits(got["coverage"].reshape(k, -1), ref[1], f"{what} coverage", nan_equal=False)
     if "residual" in got:
-        assert_same(got["residual"].reshape(-1), ref[2], f"{what} residual")
+        assert_same_bits(got["residual"].reshape(-1), ref[2], f"{what} residual", nan_equal=False)
 
 
 # ---- the layers ----
@@ -105,9 +94,9 @@ def test_layers_match_the_oracle(hb, O, name):
     for kind in KINDS:
         ref = M.layers_from_pass_ids(M.pass_ids(sc, cpu, cam_c, W, H, SPP, 3, 0, kind, pixels=pixels), 8)
         got = gpu.render_matte(cam, _opts(W, H, SPP, 3), id_kind=kind, layers=8, residual=True)
-        assert_same(got["ids"].reshape(8, -1)[:, pixels], ref[0], f"{name} {kind} ids")
-        assert_same(got["coverage"].reshape(8, -1)[:, pixels], ref[1], f"{name} {kind} coverage")
-        assert_same(got["residual"].reshape(-1)[pixels], ref[2], f"{name} {kind} residual")
+        assert_same_bits(got["ids"].reshape(8, -1)[:, pixels], ref[0], f"{name} {kind} ids", nan_equal=False)
+        assert_same_bits(got["coverage"].reshape(8, -1)[:, pixels], ref[1], f"{name} {kind} coverage", nan_equal=False)
+        assert_same_bits(got["residual"].reshape(-1)[pixels], ref[2], f"{name} {kind} residual", nan_equal=False)
 
 
 def test_overflow_is_exercised(hb):
@@ -152,9 +141,9 @@ def test_fewer_layers_are_prefixes(hb, kind):
     for k in range(7, 0, -1):
         got = gpu.render_matte(cam, opts, id_kind=kind, layers=k, residual=True)
         assert got["ids"].shape == got["coverage"].shape == (k, 18, 32)
-        assert_same(got["ids"], full["ids"][:k], f"{kind} K={k} ids")
-        assert_same(got["coverage"], full["coverage"][:k], f"{kind} K={k} coverage")
-        assert_same(got["residual"], (previous + full["coverage"][k]).astype(np.float32), f"{kind} K={k} residual")  # sixteenths: exact
+        assert_same_bits(got["ids"], full["ids"][:k], f"{kind} K={k} ids", nan_equal=False)
+        assert_same_bits(got["coverage"], full["coverage"][:k], f"{kind} K={k} coverage", nan_equal=False)
+        assert_same_bits(got["residual"], (previous + full["coverage"][k]).astype(np.float32), f"{kind} K={k} residual", nan_equal=False)  # sixteenths: exact
         assert (got["residual"] >= previous).all()
         previous = got["residual"]
     if kind == "primitive":
@@ -178,32 +167,11 @@ def test_ragged_and_tiny_frames(hb, w, h):
         assert_layers_equal(gpu.render_matte(cam, _opts(w, h, 8, 4), id_kind=kind, layers=8, residual=True), ref, f"{w}x{h} {kind}")
 
 
-class DeviceMatte:
-    """the three output buffers on the device between guard words, and a matte behind them"""
-    GUARD = 0x7FC0BEEF
-
-    def __init__(self, torch, w, h, layers=8):
-        self.torch, self.w, self.h, self.k = torch, w, h, layers
-        self.n = {"ids": layers * w * h, "coverage": layers * w * h, "residual": w * h, "matte": w * h}
-        self.buf = {name: torch.full((n + 8,), self.GUARD, dtype=torch.int32, device="cuda:0") for name, n in self.n.items()}
-
-    def ptr(self, name):
-        return self.buf[name].data_ptr() + 16
-
-    def ptrs(self, names=("ids", "coverage", "residual")):
-        return {name: self.ptr(name) for name in names}
-
-    def read(self, name, layers=None):
-        a = self.buf[name].cpu().numpy().view(np.uint32)
-        used = self.n[name] if layers is None or name in ("residual", "matte") else layers * self.w * self.h
-        assert (a[:4] == self.GUARD).all() and (a[4 + used:] == self.GUARD).all(), f"{name}: a word outside the output was written"
-        body = a[4:4 + used].copy()
-        if name != "ids":
-            body = body.view(np.float32)
-        return body.reshape((self.h, self.w) if name in ("residual", "matte") else (-1, self.h, self.w))
-
-    def untouched(self, name):
-        return bool((self.buf[name].cpu().numpy().view(np.uint32) == self.GUARD).all())
+def device_matte(torch, w, h, layers=8):
+    """the three output buffers on the device between guard words (a NaN pattern: the strict compare tells it from any output), and
+    a matte behind them"""
+    return GuardedBuffers(torch, {"ids": ((layers, h, w), np.uint32), "coverage": ((layers, h, w), np.float32),
+                                  "residual": ((h, w), np.float32), "matte": ((h, w), np.float32)}, guard=0x7FC0BEEF)
 
 
 def test_without_the_residual_nothing_is_written_to_it(hb):
@@ -211,16 +179,16 @@ def test_without_the_residual_nothing_is_written_to_it(hb):
     _, _, gpu, cam = _scene(hb, "all_materials")
     opts = _opts(37, 21, 8, 2)
     ref = gpu.render_matte(cam, opts, layers=3, residual=True)
-    run = DeviceMatte(torch, 37, 21)
+    run = device_matte(torch, 37, 21)
     torch.cuda.synchronize()
     gpu.render_matte_device(cam, opts, run.ptrs(("ids", "coverage")), layers=3)
     torch.cuda.synchronize()
     assert run.untouched("residual")
-    assert_same(run.read("ids", 3), ref["ids"], "ids")  # (read() checks that layers 3 .. 7 of the buffers still hold the guard)
-    assert_same(run.read("coverage", 3), ref["coverage"], "coverage")
+    assert_same_bits(run.read("ids", used=3 * 37 * 21), ref["ids"], "ids", nan_equal=False)  # (read() checks that layers 3 .. 7 still hold the guard)
+    assert_same_bits(run.read("coverage", used=3 * 37 * 21), ref["coverage"], "coverage", nan_equal=False)
     host = gpu.render_matte(cam, opts, layers=3)
     assert set(host) == {"ids", "coverage"}
-    assert_same(host["ids"], ref["ids"], "host call without the residual")
+    assert_same_bits(host["ids"], ref["ids"], "host call without the residual", nan_equal=False)
 
 
 def test_host_call_device_call_streams_and_a_multi_device_head_agree(hb):
@@ -231,11 +199,11 @@ def test_host_call_device_call_streams_and_a_multi_device_head_agree(hb):
     dev = torch.device("cuda", 0)
     side = torch.cuda.Stream(device=dev)
     for stream in (0, side.cuda_stream):
-        run = DeviceMatte(torch, W, H)
+        run = device_matte(torch, W, H)
         torch.cuda.synchronize()
-        gpu.render_matte_device(cam, opts, run.ptrs(), id_kind="primitive", layers=8, stream=stream)
+        gpu.render_matte_device(cam, opts, run.ptrs(OUTPUTS), id_kind="primitive", layers=8, stream=stream)
         torch.cuda.synchronize()
-        got = {name: run.read(name) for name in ("ids", "coverage", "residual")}
+        got = run.read_all(OUTPUTS)
         assert_layers_equal(got, ref, f"device call on stream {stream}")
     multi = hb.HipScene(sc, devices=[0, 0])
     assert_layers_equal(multi.render_matte(cam, opts, id_kind="primitive", layers=8, residual=True), ref, "devices=[0, 0]")
@@ -254,38 +222,27 @@ def test_graph_of_layers_then_extraction_replays_the_eager_bytes(hb):
     assert 0 < eager_matte.max() and (eager_matte < 1).any()
     gpu = hb.HipScene(sc, device=0)
     dev = torch.device("cuda", 0)
-    run = DeviceMatte(torch, W, H, 4)
+    run = device_matte(torch, W, H, 4)
     selection = torch.from_numpy(chosen.view(np.int32).copy()).to(dev)  # (the same words: torch has no uint32 arithmetic to offer)
-    side = torch.cuda.Stream(device=dev)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        gpu.render_matte_device(cam, opts, run.ptrs(), layers=4, stream=stream)
+
+    def layers_then_extraction(stream):
+        gpu.render_matte_device(cam, opts, run.ptrs(OUTPUTS), layers=4, stream=stream)
         gpu.matte_extract_device(run.ptr("ids"), run.ptr("coverage"), W, H, 4, selection.data_ptr(), len(chosen), run.ptr("matte"), stream=stream)
-    torch.cuda.synchronize(dev)
+
+    g = capture(torch, layers_then_extraction)
     assert all(run.untouched(name) for name in run.buf)  # capture ran nothing
     g.replay()
     torch.cuda.synchronize(dev)
-    for name in ("ids", "coverage", "residual"):
-        assert_same(run.read(name), eager[name], f"graph replay {name}")
-    assert_same(run.read("matte"), eager_matte, "graph replay matte")
+    for name in OUTPUTS:
+        assert_same_bits(run.read(name), eager[name], f"graph replay {name}", nan_equal=False)
+    assert_same_bits(run.read("matte"), eager_matte, "graph replay matte", nan_equal=False)
 
 
 def test_no_side_effects_on_render(hb):
-    ls = scenes.load_ssml("overshadowed")
-    gpu = hb.HipScene(ls.scene, device=0)
-    cam = hb.camera_new(**ls.camera_params)
-    opts = abi.default_render_opts(96, 54, 8, method=abi.RT_METHOD_MIS, seed=2)
-    img_a, rays_a = gpu.render(cam, opts)
-    n_a = gpu.last_kernel_ms()[1]
-    info_a = gpu.last_launch_info()
-    layers = gpu.render_matte(cam, opts, residual=True)
-    gpu.matte_extract(layers, None, [0, 1])
-    assert gpu.last_kernel_ms()[1] == n_a and gpu.last_launch_info() == info_a  # still describe the render
-    img_b, rays_b = gpu.render(cam, opts)
-    assert np.array_equal(img_a, img_b) and rays_a == rays_b
-    assert gpu.last_kernel_ms()[1] == n_a and gpu.last_launch_info() == info_a
+    sc, cam_params = ssml_scene("overshadowed")
+    gpu = hb.HipScene(sc, device=0)
+    cam = hb.camera_new(**cam_params)
+    assert_render_unaffected(gpu, cam, lambda opts, img: gpu.matte_extract(gpu.render_matte(cam, opts, residual=True), None, [0, 1]))
 
 
 # ---- extraction ----
@@ -299,21 +256,21 @@ def test_extraction_matches_the_checker(hb):
 
     def both(selection):
         got = gpu.matte_extract(ids, cov, selection)
-        assert_same(got, M.extract(ids, cov, selection), f"selection {np.asarray(selection).tolist()[:8]}")
+        assert_same_bits(got, M.extract(ids, cov, selection), f"selection {np.asarray(selection).tolist()[:8]}", nan_equal=False)
         return got
 
     assert (both([]) == 0).all() and not np.signbit(both([])).any()
     one = both([int(objects[0])])
     assert 0 < one.max() <= 1 and (one == 0).any()
     sky = both([SKY])
-    assert_same(sky, np.where(ids == SKY, cov, F32(0)).sum(axis=0, dtype=F32), "the sky alone: empty layers must not match")
+    assert_same_bits(sky, np.where(ids == SKY, cov, F32(0)).sum(axis=0, dtype=F32), "the sky alone: empty layers must not match", nan_equal=False)
     everything = both(present)
-    assert_same(everything, (F32(1.0) - layers["residual"]).astype(np.float32), "every ID present: 1 - residual, exact in sixteenths")
+    assert_same_bits(everything, (F32(1.0) - layers["residual"]).astype(np.float32), "every ID present: 1 - residual, exact in sixteenths", nan_equal=False)
     half = objects[: len(objects) // 2]
     rest = np.setdiff1d(present, half)
-    assert_same((both(half) + both(rest)).astype(np.float32), everything, "complementary selections")
+    assert_same_bits((both(half) + both(rest)).astype(np.float32), everything, "complementary selections", nan_equal=False)
     shuffled = np.concatenate([present[::-1], present, objects[:2]])  # unsorted, with duplicates: the host call sorts a copy
-    assert_same(both(shuffled), everything, "an unsorted selection with duplicates")
+    assert_same_bits(both(shuffled), everything, "an unsorted selection with duplicates", nan_equal=False)
     absent = both([int(objects.max()) + 1, 0x7FFFFFFF])
     assert (absent == 0).all()
 
@@ -328,12 +285,12 @@ def test_a_selection_larger_than_the_staged_one(hb):
     selection[::50] = rng.integers(2000, 1 << 32, 100).astype(np.uint32)  # and IDs that nothing has
     for sel in (selection, selection[:2048], selection[:2049]):  # both kernels, and both sides of the threshold
         got = gpu.matte_extract(ids, cov, sel)
-        assert_same(got, M.extract(ids, cov, sel), f"{len(sel)} IDs")
+        assert_same_bits(got, M.extract(ids, cov, sel), f"{len(sel)} IDs", nan_equal=False)
     assert 0 < (got > 0).mean() and (got < 1).any()
 
 
 def test_full_frame_through_both_kernels(hb, O):
-    sc, cam_params = _ssml("rtweekend1")
+    sc, cam_params = ssml_scene("rtweekend1")
     gpu, cpu = hb.HipScene(sc, device=0), O.Scene(sc)
     cam, cam_c = hb.camera_new(**cam_params), O.camera_new(**cam_params)
     w, h, spp, k = 1920, 1080, 4, 4
@@ -345,16 +302,16 @@ def test_full_frame_through_both_kernels(hb, O):
         tiles.add((int(rng.integers(0, tiles_x)), int(rng.integers(0, tiles_y))))
     pixels = K.tile_pixels(w, h, sorted(tiles))
     ref = M.layers_from_pass_ids(M.pass_ids(sc, cpu, cam_c, w, h, spp, 1, 0, "primitive", pixels=pixels), k)
-    assert_same(layers["ids"].reshape(k, -1)[:, pixels], ref[0], "1080p tiles ids")
-    assert_same(layers["coverage"].reshape(k, -1)[:, pixels], ref[1], "1080p tiles coverage")
-    assert_same(layers["residual"].reshape(-1)[pixels], ref[2], "1080p tiles residual")
+    assert_same_bits(layers["ids"].reshape(k, -1)[:, pixels], ref[0], "1080p tiles ids", nan_equal=False)
+    assert_same_bits(layers["coverage"].reshape(k, -1)[:, pixels], ref[1], "1080p tiles coverage", nan_equal=False)
+    assert_same_bits(layers["residual"].reshape(-1)[pixels], ref[2], "1080p tiles residual", nan_equal=False)
     n_prims = gpu.counts()[1]
     assert ((layers["ids"] < n_prims) | (layers["ids"] == SKY)).all()
     total = layers["residual"] + layers["coverage"].sum(axis=0, dtype=F32)
     assert (total == F32(1.0)).all()  # four passes: quarters
     selection = [0, SKY]  # the ground sphere and the sky
     matte = gpu.matte_extract(layers["ids"], layers["coverage"], selection)
-    assert_same(matte.reshape(-1)[pixels], M.extract(ref[0], ref[1], selection), "1080p tiles matte")
+    assert_same_bits(matte.reshape(-1)[pixels], M.extract(ref[0], ref[1], selection), "1080p tiles matte", nan_equal=False)
     whole = M.extract(layers["ids"], layers["coverage"], selection)
-    assert_same(matte, whole, "1080p matte against the checker on the library's layers")
+    assert_same_bits(matte, whole, "1080p matte against the checker on the library's layers", nan_equal=False)
     assert 0 < matte.mean() < 1

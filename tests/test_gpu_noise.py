@@ -9,6 +9,7 @@ import pytest
 import aov_checker as K
 import noise_checker as N
 import scenes
+from gpu_support import GuardedBuffers, assert_same_bits, capture, ssml_scene
 
 pytestmark = pytest.mark.gpu
 abi = scenes.abi
@@ -18,18 +19,13 @@ WHOLE, RAGGED = (24, 20), (13, 11)  # whole and half tiles; ragged on both axes
 MIS, NAIVE = abi.RT_METHOD_MIS, abi.RT_METHOD_NAIVE
 
 
-def _ssml(name):
-    ls = scenes.load_ssml(name)
-    return ls.scene, ls.camera_params
-
-
 SCENES = {  # the set of tests/test_gpu_ao.py: spheres, triangles, lights, textured sky, all materials
     "emit_scene": lambda: (K.emit_scene(), K.EMIT_CAMERA),
     "all_materials": lambda: (scenes.all_materials(), scenes.ALL_MATERIALS_CAMERA),
     "spheres500": lambda: (scenes.random_spheres(500), scenes.ALL_MATERIALS_CAMERA),
-    "pyramid": lambda: _ssml("pyramid"),
-    "rtweekend1": lambda: _ssml("rtweekend1"),
-    "overshadowed": lambda: _ssml("overshadowed"),
+    "pyramid": lambda: ssml_scene("pyramid"),
+    "rtweekend1": lambda: ssml_scene("rtweekend1"),
+    "overshadowed": lambda: ssml_scene("overshadowed"),
     "mesh2000_wide": lambda: (scenes.random_triangle_mesh(2000, edge=2.0), scenes.MESH_CAMERA),
     "mesh20000": lambda: (scenes.random_triangle_mesh(20000, edge=1.0), scenes.MESH_CAMERA),
 }
@@ -68,55 +64,30 @@ def _gpu(hb, name):
     return hb.HipScene(sc, device=0), hb.camera_new(**cam_params)
 
 
-def assert_same(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.dtype == b.dtype == np.float32 and a.shape == b.shape, (what, a.dtype, b.dtype, a.shape, b.shape)
-    same = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))  # bits, but any NaN equals any NaN
-    if not same.all():
-        bad = np.argwhere(~same)
-        pytest.fail(f"{what}: {len(bad)} elements differ, first at {bad[0].tolist()}: gpu {a[tuple(bad[0])]!r} checker {b[tuple(bad[0])]!r}")
-
-
 def assert_summary(got, ref, what):
-    assert_same(np.asarray([got["max_tile_error"]], F32), np.asarray([ref["max_tile_error"]], F32), f"{what} max_tile_error")
+    assert_same_bits(np.asarray([got["max_tile_error"]], F32), np.asarray([ref["max_tile_error"]], F32), f"{what} max_tile_error", nan_equal=True)
     assert (got["tiles_above"], got["n_tiles"]) == (ref["tiles_above"], ref["n_tiles"]), (what, got, ref)
 
 
 def assert_estimate(got, ref, what, channels=("mean", "variance", "lum_mean", "tile_error")):
     for name in channels:
-        assert_same(got[name], ref[name], f"{what} {name}")
+        assert_same_bits(got[name], ref[name], f"{what} {name}", nan_equal=True)
     assert_summary(got["summary"], ref["summary"], what)
 
 
-class DeviceNoise:
-    """the five outputs in device memory, each with guard values before and after"""
-    GUARD = 0x5A5A5A5A
+class DeviceNoise(GuardedBuffers):
+    """the five outputs in device memory, each with guard values before and after, and the ray counter"""
 
     def __init__(self, torch, w, h):
-        self.torch, self.w, self.h = torch, w, h
         ty, tx = (h + 7) // 8, (w + 7) // 8
-        self.shape = {"mean": (h, w, 3), "variance": (h, w), "lum_mean": (h, w), "tile_error": (ty, tx), "summary": (4,)}
-        dev = torch.device("cuda", 0)
-        self.buf = {k: torch.full((int(np.prod(s)) + 8,), self.GUARD, dtype=torch.int32, device=dev) for k, s in self.shape.items()}
-        self.rays = torch.zeros(1, dtype=torch.int64, device=dev)
+        super().__init__(torch, {"mean": ((h, w, 3), F32), "variance": ((h, w), F32), "lum_mean": ((h, w), F32),
+                                 "tile_error": ((ty, tx), F32), "summary": ((4,), np.uint32)})
+        self.rays = torch.zeros(1, dtype=torch.int64, device="cuda:0")
 
-    def ptrs(self, channels=abi.NOISE_CHANNELS):
-        return {k: self.buf[k].data_ptr() + 16 for k in channels}
-
-    def fill(self, value):
-        for t in self.buf.values():
-            t.fill_(value)
-
-    def read(self):
-        out = {}
-        for k, shape in self.shape.items():
-            a = self.buf[k].cpu().numpy().view(np.uint32)
-            n = int(np.prod(shape))
-            assert (a[:4] == self.GUARD).all() and (a[4 + n:] == self.GUARD).all(), f"{k}: a guard value was overwritten"
-            out[k] = a[4:4 + n].copy()
-        s = out.pop("summary")
+    def read_estimate(self):
+        res = self.read_all()
+        s = res["summary"]
         assert s[3] == 0, "the reserved word of the summary"
-        res = {k: v.view(np.float32).reshape(self.shape[k]) for k, v in out.items()}
         res["summary"] = {"max_tile_error": s[:1].view(np.float32)[0], "tiles_above": int(s[1]), "n_tiles": int(s[2])}
         return res
 
@@ -165,7 +136,7 @@ def test_a_ragged_frame_through_the_host_and_the_device_entry(hb, split):
         torch.cuda.synchronize()
         gpu.render_noise_device(cam, o, run.ptrs(), d_albedo=d_alb, d_rays_ptr=run.rays.data_ptr())
         torch.cuda.synchronize()
-        got = run.read()
+        got = run.read_estimate()
         assert_estimate(got, ref, f"device S={split} albedo={alb is not None}")
         assert got["mean"].tobytes() == frame.tobytes() and int(run.rays.item()) == gpu.render(cam, o)[1]
         # the tile outputs without the planes they are made from, and the mean alone
@@ -175,11 +146,10 @@ def test_a_ragged_frame_through_the_host_and_the_device_entry(hb, split):
             gpu.render_noise_device(cam, o, part.ptrs(channels), d_albedo=d_alb)
             torch.cuda.synchronize()
             for k in abi.NOISE_CHANNELS:
-                raw = part.buf[k].cpu().numpy().view(np.uint32)
                 if k in channels:
-                    assert raw[4:-4].tobytes() == run.buf[k].cpu().numpy().view(np.uint32)[4:-4].tobytes(), (channels, k)
+                    assert part.read(k).tobytes() == run.read(k).tobytes(), (channels, k)
                 else:
-                    assert (raw == DeviceNoise.GUARD).all(), f"{k} was written though not asked for"
+                    assert part.untouched(k), f"{k} was written though not asked for"
     host_only_mean = gpu.render_noise(cam, o, channels=())
     assert set(host_only_mean) == {"mean", "rays_shot"} and host_only_mean["mean"].tobytes() == frame.tobytes()
 
@@ -235,7 +205,7 @@ def _tiles_device(hb, gpu, lum, var, **nopts):
     torch.cuda.synchronize()
     gpu.noise_tiles_device(d_lum.data_ptr(), d_var.data_ptr(), w, h, run.ptrs()["tile_error"], run.ptrs()["summary"], **nopts)
     torch.cuda.synchronize()
-    got = run.read()
+    got = run.read_estimate()
     return got["tile_error"], got["summary"]
 
 
@@ -263,7 +233,7 @@ def test_tiles_that_hold_a_non_finite_pixel_report_infinity(hb):
     assert ref_summary["tiles_above"] == int((clean[untouched] > F32(0.05)).sum()) + 4
     for entry in ("device", "host"):
         err, summary = _tiles_device(hb, gpu, lum, var) if entry == "device" else gpu.noise_tiles(lum, var)
-        assert_same(err, ref, f"{entry} tile_error")
+        assert_same_bits(err, ref, f"{entry} tile_error", nan_equal=True)
         assert_summary(summary, ref_summary, entry)
         assert summary["max_tile_error"] == np.inf
     err, summary = gpu.noise_tiles(np.abs(np.nan_to_num(lum, nan=1.0)), np.abs(np.nan_to_num(var, nan=0.0, posinf=1.0)))
@@ -281,7 +251,7 @@ def test_a_threshold_equal_to_a_tiles_error_does_not_count_it(hb):
         _, ref_summary = N.tiles(lum, var, threshold=threshold)
         assert ref_summary["tiles_above"] == above
         err, summary = _tiles_device(hb, gpu, lum, var, threshold=threshold)
-        assert_same(err, ref, f"threshold {threshold}")
+        assert_same_bits(err, ref, f"threshold {threshold}", nan_equal=True)
         assert_summary(summary, ref_summary, f"threshold {threshold}")
         assert_summary(gpu.noise_tiles(lum, var, threshold=threshold)[1], ref_summary, f"host, threshold {threshold}")
 
@@ -296,7 +266,7 @@ def test_a_strip_with_more_tiles_than_one_pass_of_the_grid(hb):
     ref, ref_summary = N.tiles(lum, var, luminance_floor=0.02, threshold=0.1)
     assert ref.size == 2 * (abi.NOISE_TILES_PER_GRID_PASS + 4) and 0 < ref_summary["tiles_above"] < ref.size
     err, summary = _tiles_device(hb, gpu, lum, var, luminance_floor=0.02, threshold=0.1)
-    assert_same(err, ref, "strip tile_error")
+    assert_same_bits(err, ref, "strip tile_error", nan_equal=True)
     assert_summary(summary, ref_summary, "strip")
     # the summary alone, and a one-pixel frame
     import torch
@@ -335,9 +305,9 @@ def _converge(gpu, cam, **kw):
 def _assert_converged(got, ref, n_batches, what):
     mean, _, var, err, _ = ref[n_batches - 1]
     assert (got["batches"], got["passes"]) == (n_batches, n_batches * CONV["batch"]), (what, got["batches"], got["passes"])
-    assert_same(got["mean"], mean, f"{what} mean")
-    assert_same(got["variance"], var, f"{what} variance")
-    assert_same(got["tile_error"], err, f"{what} tile_error")
+    assert_same_bits(got["mean"], mean, f"{what} mean", nan_equal=True)
+    assert_same_bits(got["variance"], var, f"{what} variance", nan_equal=True)
+    assert_same_bits(got["tile_error"], err, f"{what} tile_error", nan_equal=True)
 
 
 def test_converged_stops_at_the_batch_the_checker_predicts(hb):
@@ -409,7 +379,7 @@ def test_denoised_split_is_one_render_its_variance_and_the_filter(hb):
     aov = gpu.render_aov(cam, o, channels=("albedo", "normal", "depth"))
     one = gpu.render_noise(cam, o, albedo=aov["albedo"], channels=("variance",))
     assert variance.tobytes() == one["variance"].tobytes()
-    assert_same(variance, _expected(name, WHOLE, MIS, spp, split, aov["albedo"])["variance"], "variance")
+    assert_same_bits(variance, _expected(name, WHOLE, MIS, spp, split, aov["albedo"])["variance"], "variance", nan_equal=True)
     dopts = hb.denoise_opts(w, h)
     planes = {"color": noisy, "albedo": aov["albedo"], "normal": aov["normal"], "depth": aov["depth"], "variance": variance}
     d = {k: torch.from_numpy(np.ascontiguousarray(v)).to("cuda:0") for k, v in planes.items()}
@@ -437,24 +407,19 @@ def test_a_captured_second_call_replays_the_eager_bytes(hb):
     torch.cuda.synchronize()
     gpu.render_noise_device(cam, o, eager.ptrs(), d_rays_ptr=eager.rays.data_ptr(), threshold=0.01)
     torch.cuda.synchronize()
-    ref = eager.read()
+    ref = eager.read_estimate()
     assert ref["summary"]["tiles_above"] > 0
     assert_estimate(ref, _expected(name, RAGGED, MIS, spp, split, threshold=0.01), "eager")
     run = DeviceNoise(torch, w, h)
-    side = torch.cuda.Stream(device=dev)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        gpu.render_noise_device(cam, o, run.ptrs(), d_rays_ptr=run.rays.data_ptr(), stream=torch.cuda.current_stream(dev).cuda_stream,
-                                threshold=0.01)
-    torch.cuda.synchronize(dev)
-    assert all((t.cpu().numpy().view(np.uint32) == DeviceNoise.GUARD).all() for t in run.buf.values())  # capture ran nothing
+    g = capture(torch, lambda stream: gpu.render_noise_device(cam, o, run.ptrs(), d_rays_ptr=run.rays.data_ptr(), stream=stream,
+                                                               threshold=0.01))
+    assert all(run.untouched(k) for k in run.buf)  # capture ran nothing
     for replay in range(2):
         run.rays.zero_()
         torch.cuda.synchronize(dev)
         g.replay()
         torch.cuda.synchronize(dev)
-        got = run.read()
+        got = run.read_estimate()
         assert_estimate(got, ref, f"replay {replay}")
         assert int(run.rays.item()) == int(eager.rays.item())
 

@@ -21,9 +21,7 @@ import denoise_checker as K
 import display_checker as D
 import scenes
 import temporal_checker as T
-from test_gpu_denoise import SCENES, TOL
-from test_gpu_display import DeviceDisplay, check
-from test_gpu_temporal import bits_equal
+from post_runners import SCENES, TOL, DeviceDisplay, bits_equal, check_display
 
 pytestmark = pytest.mark.gpu
 abi = scenes.abi
@@ -246,6 +244,6 @@ def test_display_past_the_map_caps(hb, O, dev_scene, in_off, out_off, kw):
     img = (rng.uniform(0.2, 1.0, (h, w, 3)).astype(F32) * np.exp2(rng.uniform(-6.0, 4.0, (h, w, 1))).astype(F32))
     img[h - 1, w - 1] = (np.nan, 1.0, 1.0)
     run = DeviceDisplay(torch, hb, gpu, w, h, in_off, out_off, **kw)
-    check(O, run, img, (F32(0.5), 2, F32(0)), f"4097x2161 offsets {in_off},{out_off}", **kw)
+    check_display(O, run, img, (F32(0.5), 2, F32(0)), f"4097x2161 offsets {in_off},{out_off}", **kw)
     del run
     torch.cuda.empty_cache()

@@ -10,11 +10,9 @@ import pytest
 import denoise_checker as K
 import post_options_cases as P
 import scenes
-from test_gpu_denoise import SCENES, _device_run, check_against_checker, rendered_inputs
-from test_gpu_display import DeviceDisplay, check, same_state
-from test_gpu_temporal import DeviceRunner, check_step
-from test_gpu_upscale import GUIDES, DeviceUpscale, library_inputs
-from test_gpu_upscale import check as check_upscale
+from gpu_support import load_gpu
+from post_runners import (GUIDES, SCENES, DeviceDisplay, DeviceRunner, DeviceUpscale, check_against_checker, check_display,
+                          check_step, check_upscale, device_run, library_inputs, rendered_inputs, same_state)
 
 pytestmark = pytest.mark.gpu
 abi = scenes.abi
@@ -22,8 +20,8 @@ F32 = np.float32
 
 
 def _load(hb, name):
-    sc, cam_params = SCENES[name]()
-    return hb.HipScene(sc, device=0), hb.camera_new(**cam_params)
+    gpu, cam_params = load_gpu(hb, SCENES, name)
+    return gpu, hb.camera_new(**cam_params)
 
 
 @pytest.fixture(scope="module")
@@ -50,7 +48,7 @@ def test_denoise_options(hb, dev_scene, denoise_inputs, case, source):
     assert moved >= P.SENSITIVITY, f"{name} does nothing on the {source} frame: {moved:.3e}"
     host = gpu.denoise(**inputs, **opts)
     ref = check_against_checker(host, inputs, f"{source} {name} host", **opts)
-    dev = _device_run(torch, hb, gpu, inputs, hb.denoise_opts(w, h, **opts), 0)
+    dev = device_run(torch, hb, gpu, inputs, hb.denoise_opts(w, h, **opts), 0)
     check_against_checker(dev, inputs, f"{source} {name} device", **opts)
     assert dev.tobytes() == host.tobytes()
     print(f"denoise {source} {name}: moved {moved:.3e}, error {K.relative_error(host, ref):.3e}")
@@ -91,7 +89,7 @@ def test_display_options(hb, O, dev_scene, case):
     for (label, state), (in_off, out_off), fmt in zip(P.DISPLAY_STATES, ((0, 0), (1, 3)), (D.RGBA8, D.RGB8)):
         kw = dict(opts, pixel_format=fmt)
         run = DeviceDisplay(torch, hb, gpu, w, h, in_off, out_off, **kw)
-        check(O, run, img, state, f"{name} {label} device", **kw)  # bytes, histogram and state
+        check_display(O, run, img, state, f"{name} {label} device", **kw)  # bytes, histogram and state
     # the host entry from a zero state
     gpu.display_reset()
     px, hist = gpu.display(img, histogram=True, **opts)

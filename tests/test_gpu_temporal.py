@@ -5,20 +5,12 @@ against a converged render."""
 import numpy as np
 import pytest
 
-import denoise_checker as K
 import scenes
-import temporal_checker as T
-from test_gpu_denoise import SCENES, _display_mse
+from gpu_support import assert_render_unaffected, capture, load_gpu
+from post_runners import SCENES, DeviceRunner, bits_equal, check_step, display_mse
 
 pytestmark = pytest.mark.gpu
 abi = scenes.abi
-TOL = 1e-4  # e_1 and out against the float64 filter checker, as tests/test_gpu_denoise.py
-
-
-def _load(hb, name, devices=None):
-    sc, cam_params = SCENES[name]()
-    gpu = hb.HipScene(sc, devices=devices) if devices else hb.HipScene(sc, device=0)
-    return gpu, cam_params
 
 
 def path_camera(hb, p, i, orbit_deg=1.5, dolly=0.01):
@@ -40,76 +32,13 @@ def frame_inputs(gpu, cam, w, h, spp, sample_begin, seed=3):
     return dict(color=color, **aov)
 
 
-def bits_equal(a, b):
-    """same bits, NaN == NaN whatever its payload"""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    na, nb = np.isnan(a), np.isnan(b)
-    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(a[~na].view(np.uint32), b[~nb].view(np.uint32))
-
-
-class DeviceRunner:
-    """rt_denoise_temporal_device over torch buffers, two histories ping-ponged"""
-
-    def __init__(self, torch, hb, gpu, w, h, **opts):
-        self.torch, self.hb, self.gpu, self.w, self.h = torch, hb, gpu, w, h
-        self.dev = torch.device("cuda", 0)
-        self.opts = hb.temporal_opts(w, h, **opts)
-        hb_ = hb.temporal_history_bytes(self.opts)
-        self.hist = [torch.full((hb_ // 4,), 7.0, dtype=torch.float32, device=self.dev) for _ in range(2)]
-        self.ws = torch.empty(hb.temporal_workspace_bytes(self.opts), dtype=torch.uint8, device=self.dev)
-        self.out = torch.zeros(h * w * 3, dtype=torch.float32, device=self.dev)
-        self.motion = torch.zeros(h * w * 2, dtype=torch.float32, device=self.dev)
-        self.cur, self.prev = -1, None
-
-    def upload(self, inputs):
-        self.t = {k: self.torch.from_numpy(np.ascontiguousarray(v)).to(self.dev) for k, v in inputs.items()}
-
-    def launch(self, cam, stream=0):
-        nxt = 1 if self.cur == 0 else 0
-        h_in = self.hist[self.cur].data_ptr() if self.cur >= 0 else 0
-        self.gpu.denoise_temporal_device({k: v.data_ptr() for k, v in self.t.items()}, cam, self.prev, h_in,
-                                         self.hist[nxt].data_ptr(), self.ws.data_ptr(), self.out.data_ptr(), self.opts,
-                                         d_motion=self.motion.data_ptr(), stream=stream)
-        self.cur, self.prev = nxt, cam
-
-    def step(self, inputs, cam):
-        """one frame; returns (out, motion, history written, history read or None) as numpy"""
-        h_in = self.history(self.cur) if self.cur >= 0 else None
-        self.upload(inputs)
-        self.torch.cuda.synchronize(self.dev)
-        self.launch(cam)
-        self.torch.cuda.synchronize(self.dev)
-        return (self.out.cpu().numpy().reshape(self.h, self.w, 3), self.motion.cpu().numpy().reshape(self.h, self.w, 2),
-                self.history(self.cur), h_in)
-
-    def history(self, i):
-        return T.history_array(self.hist[i].cpu().numpy(), self.h, self.w)
-
-
-def check_step(inputs, cam, prev, h_in, out, motion, h_out, what, iterations=5, normal=True, **opts):
-    """`opts`: the temporal options and sigmas the GPU ran with, for the checker (the defaults when none are given)"""
-    st = T.step(inputs["color"], inputs["depth"], cam, prev, h_in, albedo=inputs.get("albedo"),
-                normal=inputs.get("normal") if normal else None, **opts)
-    assert bits_equal(motion, st["motion"]), f"{what}: motion"
-    assert bits_equal(h_out[0, ..., 3], st["n"]), f"{what}: n"
-    assert bits_equal(h_out[2, ..., 0], st["m1"]) and bits_equal(h_out[2, ..., 1], st["m2"]), f"{what}: moments"
-    assert bits_equal(h_out[1], st["history"][1]), f"{what}: n^ and z"
-    assert not h_out[2, ..., 2:].any(), what
-    e1, ref = T.filtered(st, inputs["color"], normal, iterations=iterations, **{k: v for k, v in opts.items() if k.startswith("sigma_")})
-    ok = st["valid"]
-    assert np.array_equal(out[~ok], inputs["color"][~ok], equal_nan=True), f"{what}: invalid pixels pass through"
-    err_e1, err_out = K.relative_error(h_out[0][ok][:, :3], e1[ok]), K.relative_error(out[ok], ref[ok])
-    assert err_e1 <= TOL and err_out <= TOL, f"{what}: e_1 {err_e1:.3e} out {err_out:.3e}"
-    return st
-
-
 PATH_SCENES = ["rtweekend1", "overshadowed", "all_materials", "structured_meshes", "random_everything_1"]
 
 
 @pytest.mark.parametrize("name", PATH_SCENES)
 def test_every_step_matches_the_checker(hb, name):
     import torch
-    gpu, p = _load(hb, name)
+    gpu, p = load_gpu(hb, SCENES, name)
     for w, h in ((160, 90), (320, 180)):
         run = DeviceRunner(torch, hb, gpu, w, h)
         begin, prev = 0, None
@@ -130,7 +59,7 @@ def test_every_step_matches_the_checker(hb, name):
 @pytest.mark.parametrize("name", list(SCENES))
 def test_no_history_is_rt_denoise(hb, name, iterations):
     import torch
-    gpu, p = _load(hb, name)
+    gpu, p = load_gpu(hb, SCENES, name)
     cam = hb.camera_new(**p)
     for w, h in ((64, 36), (67, 37)):
         inputs = frame_inputs(gpu, cam, w, h, 4, 0)
@@ -148,7 +77,7 @@ def test_no_history_is_rt_denoise(hb, name, iterations):
 
 def test_host_and_device_entries_agree(hb):
     import torch
-    gpu, p = _load(hb, "all_materials")
+    gpu, p = load_gpu(hb, SCENES, "all_materials")
     w, h = 96, 54
     run = DeviceRunner(torch, hb, gpu, w, h)
     side = torch.cuda.Stream(device=torch.device("cuda", 0))
@@ -181,7 +110,7 @@ def test_host_and_device_entries_agree(hb):
 
 def test_nan_and_inf_pixels(hb):
     import torch
-    gpu, p = _load(hb, "rtweekend1")
+    gpu, p = load_gpu(hb, SCENES, "rtweekend1")
     w, h = 64, 36
     cam = hb.camera_new(**p)
     run = DeviceRunner(torch, hb, gpu, w, h)
@@ -204,7 +133,7 @@ def test_nan_and_inf_pixels(hb):
 
 def test_ping_pong_graphs_equal_eager(hb):
     import torch
-    gpu, p = _load(hb, "all_materials")
+    gpu, p = load_gpu(hb, SCENES, "all_materials")
     w, h = 160, 90
     dev = torch.device("cuda", 0)
     cams = [path_camera(hb, p, 0), path_camera(hb, p, 1)]
@@ -238,10 +167,7 @@ def test_ping_pong_graphs_equal_eager(hb):
     side.synchronize()
     graphs = []
     for k in range(2):
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, stream=side):
-            frame(cams[(k + 1) % 2], torch.cuda.current_stream(dev).cuda_stream)
-        graphs.append(g)
+        graphs.append(capture(torch, lambda stream: frame(cams[(k + 1) % 2], stream), side=side))
     assert run.cur == 0  # capture launched nothing, but the runner's ping-pong went round once
     for k in range(4):
         run.out.fill_(7)
@@ -252,23 +178,20 @@ def test_ping_pong_graphs_equal_eager(hb):
 
 
 def test_no_side_effects_on_render(hb):
-    gpu, p = _load(hb, "overshadowed")
+    gpu, p = load_gpu(hb, SCENES, "overshadowed")
     cam = hb.camera_new(**p)
-    opts = abi.default_render_opts(96, 54, 8, method=abi.RT_METHOD_MIS, seed=2)
-    img_a, rays_a = gpu.render(cam, opts)
-    n_a = gpu.last_kernel_ms()[1]
-    info_a = gpu.last_launch_info()
-    aov = gpu.render_aov(cam, opts, channels=("albedo", "normal", "depth"))
-    gpu.denoise_temporal(img_a, cam, aov)
-    gpu.denoise_temporal(img_a, path_camera(hb, p, 1), aov, motion=True)
-    assert gpu.last_kernel_ms()[1] == n_a and gpu.last_launch_info() == info_a
-    img_b, rays_b = gpu.render(cam, opts)
-    assert img_a.tobytes() == img_b.tobytes() and rays_a == rays_b
+
+    def aov_and_two_frames(opts, img):
+        aov = gpu.render_aov(cam, opts, channels=("albedo", "normal", "depth"))
+        gpu.denoise_temporal(img, cam, aov)
+        gpu.denoise_temporal(img, path_camera(hb, p, 1), aov, motion=True)
+
+    assert_render_unaffected(gpu, cam, aov_and_two_frames)
 
 
 def test_full_frame_1080p_with_motion(hb):
     import torch
-    gpu, p = _load(hb, "rtweekend1")
+    gpu, p = load_gpu(hb, SCENES, "rtweekend1")
     w, h = 1920, 1080
     run = DeviceRunner(torch, hb, gpu, w, h)
     prev = None
@@ -282,8 +205,8 @@ def test_full_frame_1080p_with_motion(hb):
 
 
 def test_multi_device_head_runs_on_the_first_device(hb):
-    single, p = _load(hb, "rtweekend1")
-    multi, _ = _load(hb, "rtweekend1", devices=[0, 0])
+    single, p = load_gpu(hb, SCENES, "rtweekend1")
+    multi, _ = load_gpu(hb, SCENES, "rtweekend1", devices=[0, 0])
     w, h = 96, 54
     for i in range(3):
         cam = path_camera(hb, p, i)
@@ -292,7 +215,7 @@ def test_multi_device_head_runs_on_the_first_device(hb):
 
 
 def _quality(hb, name, orbit_deg, frames=8, spp=2, w=320, h=180):
-    gpu, p = _load(hb, name)
+    gpu, p = load_gpu(hb, SCENES, name)
     gpu.temporal_reset()
     for i in range(frames):
         cam = path_camera(hb, p, i, orbit_deg=orbit_deg, dolly=0.0)
@@ -300,7 +223,7 @@ def _quality(hb, name, orbit_deg, frames=8, spp=2, w=320, h=180):
         temporal = gpu.denoise_temporal(inputs, cam)
     single = gpu.denoise(**inputs)
     ref, _ = gpu.render(cam, abi.default_render_opts(w, h, 4096, method=abi.RT_METHOD_MIS, seed=99))
-    mse_t, mse_s = _display_mse(temporal, ref), _display_mse(single, ref)
+    mse_t, mse_s = display_mse(temporal, ref), display_mse(single, ref)
     shift = abs(float(temporal.astype(np.float64).mean()) / float(ref.astype(np.float64).mean()) - 1.0)
     print(f"{name} orbit {orbit_deg} deg/frame: display MSE single-frame {mse_s:.4e} temporal {mse_t:.4e} "
           f"ratio {mse_t / mse_s:.3f}; mean radiance shift {shift:.4f}")

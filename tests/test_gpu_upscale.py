@@ -10,45 +10,22 @@ import numpy as np
 import pytest
 
 import scenes
-import upscale_checker as U
-from test_gpu_denoise import SCENES, _display_mse
+from gpu_support import assert_render_unaffected, capture, load_gpu
+from post_runners import GUIDES, SCENES, STAGES_SEEN, DeviceUpscale, check_upscale, display_mse, library_inputs
 
 pytestmark = pytest.mark.gpu
 abi = scenes.abi
 F32 = np.float32
-GUIDES = ("albedo", "normal", "depth")
 SUBSETS = [tuple(g for g, on in zip(GUIDES, bits) if on) for bits in itertools.product((False, True), repeat=3)]
-STAGES_SEEN = set()  # the union of the stage maps of this module's runs: test_zz_every_stage_value_occurred
 
 
 def _load(hb, name, devices=None):
-    sc, cam_params = SCENES[name]()
-    gpu = hb.HipScene(sc, devices=devices) if devices else hb.HipScene(sc, device=0)
+    gpu, cam_params = load_gpu(hb, SCENES, name, devices)
     return gpu, hb.camera_new(**cam_params)
-
-
-def library_inputs(gpu, cam, w, h, W, H, spp=8, seed=3):
-    """the filtered source frame (rt_render_denoised at w x h) and the rt_render_aov guides at both sizes"""
-    so = abi.default_render_opts(w, h, spp, method=abi.RT_METHOD_MIS, seed=seed)
-    clean, _, _ = gpu.render_denoised(cam, so)
-    src = gpu.render_aov(cam, so, channels=GUIDES)
-    dst = gpu.render_aov(cam, abi.default_render_opts(W, H, spp, method=abi.RT_METHOD_MIS, seed=seed), channels=GUIDES)
-    return clean, src, dst
 
 
 def pick(guides, keys):
     return {k: guides[k] for k in keys}
-
-
-def check(O, gpu, color, src, dst, W, H, what, **opts):
-    """host entry against the checker: frame and stage map, bit for bit"""
-    out, stage = gpu.upscale(color, src=src, dst=dst if dst else (H, W), stage=True, **opts)
-    ref, ref_stage = U.upscale(O, color, W, H, src=src, dst=dst, **opts)
-    STAGES_SEEN.update(int(v) for v in np.unique(stage))
-    assert np.array_equal(stage, ref_stage), f"{what}: {int((stage != ref_stage).sum())} stage values differ"
-    same = out.view(np.uint32) == ref.view(np.uint32)
-    assert same.all(), f"{what}: {int((~same).sum())} floats differ, max |d| {np.nanmax(np.abs(out - ref)):.3e}"
-    return out, stage
 
 
 RATIOS = [((64, 36), (128, 72)), ((64, 36), (96, 54)), ((64, 36), (192, 108)), ((64, 36), (64, 36)), ((67, 37), (131, 40))]
@@ -61,14 +38,14 @@ def test_gpu_matches_the_checker_bit_for_bit(hb, O, name):
         color, src, dst = library_inputs(gpu, cam, w, h, W, H)
         subsets = SUBSETS if (W, H) in ((128, 72), (131, 40)) else [(), GUIDES]
         for keys in subsets:
-            check(O, gpu, color, pick(src, keys), pick(dst, keys), W, H, f"{name} {w}x{h} -> {W}x{H} guides {keys}")
-        check(O, gpu, color, src, dst, W, H, f"{name} {w}x{h} -> {W}x{H} options", sigma_normal=4.0, depth_tolerance=0.02)
+            check_upscale(O, gpu, color, pick(src, keys), pick(dst, keys), W, H, f"{name} {w}x{h} -> {W}x{H} guides {keys}")
+        check_upscale(O, gpu, color, src, dst, W, H, f"{name} {w}x{h} -> {W}x{H} options", sigma_normal=4.0, depth_tolerance=0.02)
 
 
 def test_960x540_to_1080p(hb, O):
     gpu, cam = _load(hb, "rtweekend1")
     color, src, dst = library_inputs(gpu, cam, 960, 540, 1920, 1080, spp=4, seed=1)
-    _, stage = check(O, gpu, color, src, dst, 1920, 1080, "960x540 -> 1920x1080")
+    _, stage = check_upscale(O, gpu, color, src, dst, 1920, 1080, "960x540 -> 1920x1080")
     share = np.bincount(stage.ravel(), minlength=4) / stage.size
     print(f"rtweekend1 960x540 -> 1920x1080: stage shares 0..3 = {share.round(6).tolist()}")
     assert share[1] > 0.9
@@ -98,7 +75,7 @@ def test_every_stage_value_by_construction(hb, O):
     gpu, _ = _load(hb, "rtweekend1")
     color, src, dst, W, H = every_stage_input()
     for keys in SUBSETS:
-        _, stage = check(O, gpu, color, pick(src, keys), pick(dst, keys), W, H, f"constructed, guides {keys}")
+        _, stage = check_upscale(O, gpu, color, pick(src, keys), pick(dst, keys), W, H, f"constructed, guides {keys}")
         assert np.isfinite(gpu.upscale(color, src=pick(src, keys), dst=pick(dst, keys) or (H, W))).all()
         if "depth" in keys or "normal" in keys:
             assert set(np.unique(stage)) == {0, 1, 2, 3}, keys
@@ -116,38 +93,8 @@ def test_nan_and_inf_pixels_in_a_rendered_frame(hb, O):
     color[10:16, 40:46] = np.nan
     color[35, 63] = np.nan  # a corner: its clamped copies are invalid too
     for keys in ((), GUIDES):
-        out, stage = check(O, gpu, color, pick(src, keys), pick(dst, keys), 128, 72, f"non-finite pixels, guides {keys}")
+        out, stage = check_upscale(O, gpu, color, pick(src, keys), pick(dst, keys), 128, 72, f"non-finite pixels, guides {keys}")
         assert np.isfinite(out).all() and (out[stage == 0] == 0).all() and (stage == 0).any()
-
-
-class DeviceUpscale:
-    """rt_upscale_device over torch buffers; `off` shifts every float buffer by that many floats and the stage map by as many bytes"""
-
-    def __init__(self, torch, hb, gpu, color, src, dst, W, H, off=0, **opts):
-        self.torch, self.gpu, self.W, self.H, self.off = torch, gpu, W, H, off
-        self.dev = torch.device("cuda", 0)
-        h, w = color.shape[:2]
-        self.opts = hb.upscale_opts(w, h, W, H, **opts)
-        arrays = {"color": color, **{"src_" + k: v for k, v in src.items()}, **{"dst_" + k: v for k, v in dst.items()}}
-        self.bufs = {}
-        for k, a in arrays.items():
-            t = torch.zeros(a.size + off, dtype=torch.float32, device=self.dev)
-            t[off:] = torch.from_numpy(np.ascontiguousarray(a, F32).ravel()).to(self.dev)
-            self.bufs[k] = t
-        self.out = torch.full((W * H * 3 + off + 4,), 7.0, dtype=torch.float32, device=self.dev)
-        self.stage = torch.full((W * H + off + 16,), 0x5A, dtype=torch.uint8, device=self.dev)
-
-    def launch(self, stream=0, with_stage=True):
-        self.gpu.upscale_device({k: t.data_ptr() + 4 * self.off for k, t in self.bufs.items()}, self.out.data_ptr() + 4 * self.off,
-                                self.opts, self.stage.data_ptr() + self.off if with_stage else 0, stream=stream)
-
-    def read(self):
-        self.torch.cuda.synchronize(self.dev)
-        o, s = self.out.cpu().numpy(), self.stage.cpu().numpy()
-        n = self.W * self.H
-        assert (o[:self.off] == 7.0).all() and (o[self.off + 3 * n:] == 7.0).all(), "wrote outside the output"
-        assert (s[:self.off] == 0x5A).all() and (s[self.off + n:] == 0x5A).all(), "wrote outside the stage map"
-        return o[self.off:self.off + 3 * n].reshape(self.H, self.W, 3).copy(), s[self.off:self.off + n].reshape(self.H, self.W).copy()
 
 
 @pytest.mark.parametrize("sizes", [((67, 37), (131, 75)), ((64, 36), (128, 72))])
@@ -158,7 +105,7 @@ def test_device_entry_unaligned_buffers_and_host_entry(hb, O, sizes):
     color, src, dst = library_inputs(gpu, cam, w, h, W, H)
     for keys in ((), ("albedo",), GUIDES):
         s, d = pick(src, keys), pick(dst, keys)
-        host_out, host_stage = check(O, gpu, color, s, d, W, H, f"host {keys}")
+        host_out, host_stage = check_upscale(O, gpu, color, s, d, W, H, f"host {keys}")
         for off in (0, 1, 3):
             run = DeviceUpscale(torch, hb, gpu, color, s, d, W, H, off=off)
             torch.cuda.synchronize()
@@ -246,10 +193,7 @@ def test_graph_replay_equals_eager(hb):
     with torch.cuda.stream(side):
         frame(side.cuda_stream, upscale=False)  # the render's and the AOV pass's first-use allocations; the upscale has none
     side.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=side):
-        frame(torch.cuda.current_stream(dev).cuda_stream)
-    torch.cuda.synchronize(dev)
+    g = capture(torch, frame, side=side)
     assert (out.cpu().numpy() == 0).all()  # capture ran nothing
     eager = gpu.upscale(clean.cpu().numpy().reshape(h, w, 3), src={k: v.cpu().numpy().reshape((h, w, 3) if k != "depth" else (h, w))
                                                                    for k, v in src.items()},
@@ -266,16 +210,13 @@ def test_graph_replay_equals_eager(hb):
 
 def test_no_side_effects_on_render(hb):
     gpu, cam = _load(hb, "overshadowed")
-    opts = abi.default_render_opts(96, 54, 8, method=abi.RT_METHOD_MIS, seed=2)
-    img_a, rays_a = gpu.render(cam, opts)
-    n_a = gpu.last_kernel_ms()[1]
-    info_a = gpu.last_launch_info()
-    aov = gpu.render_aov(cam, opts, channels=GUIDES)
-    gpu.upscale(img_a, dst=(108, 192))
-    gpu.upscale(img_a, src=aov, dst=aov, stage=True)
-    assert gpu.last_kernel_ms()[1] == n_a and gpu.last_launch_info() == info_a
-    img_b, rays_b = gpu.render(cam, opts)
-    assert img_a.tobytes() == img_b.tobytes() and rays_a == rays_b
+
+    def aov_and_both_calls(opts, img):
+        aov = gpu.render_aov(cam, opts, channels=GUIDES)
+        gpu.upscale(img, dst=(108, 192))
+        gpu.upscale(img, src=aov, dst=aov, stage=True)
+
+    assert_render_unaffected(gpu, cam, aov_and_both_calls)
 
 
 def test_multi_device_head_runs_on_the_first_device(hb):
@@ -312,7 +253,7 @@ def test_quality_against_a_converged_render(hb, name):
     gpu.render_upscaled(cam, opts, w, h)
     t_up = time.perf_counter() - t0
     plain = gpu.upscale(source, dst=(H, W))
-    mse_guided, mse_plain = _display_mse(guided, ref), _display_mse(plain, ref)
+    mse_guided, mse_plain = display_mse(guided, ref), display_mse(plain, ref)
     ratio = mse_guided / mse_plain
     mean_shift = abs(float(guided.astype(np.float64).mean()) / float(source.astype(np.float64).mean()) - 1.0)
     # not asserted: the equal-cost alternative, the full-size frame with a quarter of the passes
@@ -323,8 +264,8 @@ def test_quality_against_a_converged_render(hb, name):
     t_full = time.perf_counter() - t0
     full16, _, _ = gpu.render_denoised(cam, opts)
     print(f"{name}: display MSE guided {mse_guided:.4e} unguided {mse_plain:.4e} ratio {ratio:.3f}; mean shift {mean_shift:.4f}; "
-          f"equal cost: 320x180 @ 4 passes denoised MSE {_display_mse(full4, ref):.4e} in {t_full * 1e3:.2f} ms, "
-          f"160x90 @ 16 upscaled in {t_up * 1e3:.2f} ms; 320x180 @ 16 passes denoised MSE {_display_mse(full16, ref):.4e}")
+          f"equal cost: 320x180 @ 4 passes denoised MSE {display_mse(full4, ref):.4e} in {t_full * 1e3:.2f} ms, "
+          f"160x90 @ 16 upscaled in {t_up * 1e3:.2f} ms; 320x180 @ 16 passes denoised MSE {display_mse(full16, ref):.4e}")
     assert ratio < 1.0, (mse_guided, mse_plain)
     assert mean_shift <= 0.02
 

@@ -2,23 +2,16 @@
 3.5 % and 6 % losses from edits that only perturbed register allocation), so the table of the shipped library is committed as
 profiles/resource_table.json and a build whose DEFAULT kernels differ from it fails here: whoever changes a kernel has to
 rebuild, look at the difference (`python tests/probes/resource_table.py --diff`), measure, and commit the new table with the change."""
-import importlib.util
 import json
-import os
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-spec = importlib.util.spec_from_file_location("resource_table", os.path.join(ROOT, "tests", "probes", "resource_table.py"))
-rtab = importlib.util.module_from_spec(spec)
-spec.loader.exec_module(rtab)
+from resource_budget import require_built, rtab
 
 
 @pytest.fixture(scope="module")
 def built_table():
-    if not os.path.exists(rtab.READELF):
-        pytest.skip("llvm-readelf not available")
-    rtab.rebuild_if_stale()  # the table must describe THESE sources
+    require_built()  # the table must describe THESE sources
     return rtab.extract(rtab.LIB)
 
 
