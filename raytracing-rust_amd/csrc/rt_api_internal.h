@@ -123,6 +123,8 @@ inline bool scene_prunes(const rt_scene *s)
 // tree's (and the two-child walk for every ray: narrow_only) otherwise -- the fallback the coarse render kernels take.  *dev is
 // the scene as such a launch sees it.  A scene whose two-child stack does not fit either is refused; no test builds one: a
 // two-child tree deeper than 160 levels cannot be made from finite float coordinates with the generators of tests/scenes.py.
+// On this hardware the refusal is unreachable whatever the scene: the build caps stack_depth at 96 entries, and
+// 4 waves x 96 x 256 B = 98 304 B is below the 160 KB of a CU, so the branch is live only on a device that reports less LDS.
 inline int four_wave_traversal(const rt_scene *s, bool *prune, rt::DevScene *dev)
 {
 	*prune = scene_prunes(s);

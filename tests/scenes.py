@@ -57,19 +57,33 @@ def random_spheres(n, seed=0, split_type=abi.RT_SPLIT_SAH, emissive_every=0, sam
     return sc
 
 
-def skewed_chain_of_spheres(n=64, ratio=1.35, split_type=abi.RT_SPLIT_MIDDLE):
+def skewed_chain_of_spheres(n=64, ratio=1.35, split_type=abi.RT_SPLIT_MIDDLE, specular_every=0):
     """collinear spheres whose positions and radii grow geometrically: every split peels one sphere off the small end, so the
     reference tree is a chain about n levels deep -- the deepest kind of tree a scene of n primitives can have (the
     wide-tree stack bound of such a tree is ~1.5 x its two-child depth: csrc/rt_api.cpp falls back to the two-child walk when that
-    does not fit the LDS of a CU)"""
+    does not fit the LDS of a CU).  specular_every = k > 0 makes every k-th sphere alternately a perfect mirror and glass (something
+    for the chain AOVs to follow inside the deep tree); 0 is the scene as it always was, byte for byte."""
     sc = SceneDescription(split_type)
     mats = [sc.lambertian(sc.solid((0.8, 0.3, 0.3)), 0.8), sc.lambertian(sc.solid((0.3, 0.8, 0.3)), 0.8), sc.emissive(sc.solid((1.0, 0.9, 0.8)), 3.0)]
+    specular = [sc.reflect(sc.solid((0.9, 0.9, 0.95)), 0.0), sc.refract(sc.solid((1.0, 1.0, 1.0)), 1.5)] if specular_every else []
     x = 1.0
     for i in range(n):
-        sc.sphere((x, 0.0, 0.0), 0.2 * x, mats[2] if i % 9 == 4 else mats[i % 2])
+        m = mats[2] if i % 9 == 4 else mats[i % 2]
+        if specular_every and i % specular_every == specular_every - 1:
+            m = specular[(i // specular_every) % 2]
+        sc.sphere((x, 0.0, 0.0), 0.2 * x, m)
         x *= ratio
     sc.set_sky(sc.lerp((0.5, 0.7, 1.0), (1.0, 1.0, 1.0)), (16, 8))
     return sc
+
+
+# the camera the tiny trees (random_spheres(n), random_triangle_mesh(n, extent=1.0, edge=1.5), n = 2 .. 7) are rendered from
+TINY_TREE_CAMERA = dict(origin=(0.0, -14.0, 2.0), lookat=(0.0, 0.0, 0.0), vup=(0.0, 0.0, 1.0), fov=70.0,
+                        aspect_ratio=float(np.float32(16.0) / np.float32(9.0)), aperture=0.0, focus_dist=10.0)
+
+# the camera tests/test_gpu_parity.py renders the 112-sphere, ratio-1.44 chain from
+CHAIN_CAMERA = dict(origin=(30.0, -60.0, 15.0), lookat=(20.0, 0.0, 0.0), vup=(0.0, 0.0, 1.0), fov=60.0,
+                    aspect_ratio=float(np.float32(16.0) / np.float32(9.0)), aperture=0.0, focus_dist=10.0)
 
 
 def random_triangle_mesh(n, seed=42, extent=10.0, edge=0.05, emissive_every=1000, split_type=abi.RT_SPLIT_SAH,
@@ -310,3 +324,80 @@ def small_far_scenes():
     sc.set_sky(sc.solid(1.0), (0, 0))
     out.append(("a far clump of triangles", sc, c.astype(np.float32)))
     return out
+
+
+def small_far_camera(target, offset=(9.0, 7.0, 6.0), fov=0.001):
+    """a camera that looks at a clump of small_far_scenes() from `offset` away (the defaults: 13 units, 0.001 degrees)"""
+    return dict(origin=tuple(float(x) for x in target + np.float32(offset)), lookat=tuple(float(x) for x in target),
+                vup=(0.0, 0.0, 1.0), fov=fov, aspect_ratio=float(np.float32(16.0) / np.float32(9.0)), aperture=0.0, focus_dist=10.0)
+
+
+LATTICE_GRID = np.linspace(-4.0, 4.0, 17).astype(np.float32)
+
+
+def flat_box_lattice(rng):
+    """160 axis-aligned boxes on a coarse lattice: 1 920 flat triangles (flat leaf boxes), many coplanar faces.  Draws from the
+    caller's generator, which a caller may go on drawing rays from (LATTICE_GRID holds every face coordinate)."""
+    sc = SceneDescription()
+    grey = sc.lambertian(sc.solid(0.5), 0.5)
+    light = sc.emissive(sc.solid(1.0), 3.0)
+    for i in range(160):
+        a = rng.choice(LATTICE_GRID, 3)
+        b = a + rng.choice(np.array([0.5, 1.0, 1.5], dtype=np.float32), 3)
+        sc.aacuboid(tuple(a), tuple(b), light if i % 40 == 0 else grey)
+    sc.set_sky(sc.solid(1.0), (0, 0))
+    return sc
+
+
+LATTICE_CAMERA = dict(origin=(9.0, 7.0, 6.0), lookat=(0.0, 0.0, 0.0), vup=(0.0, 0.0, 1.0), fov=50.0,
+                      aspect_ratio=float(np.float32(16.0) / np.float32(9.0)), aperture=0.0, focus_dist=10.0)
+
+
+def non_finite_geometry():
+    """NaN and infinite primitives among ordinary ones: data, not errors (the reference would build a tree from them too)"""
+    nan, inf = float("nan"), float("inf")
+    sc = SceneDescription()
+    grey = sc.lambertian(sc.solid(0.6), 0.8)
+    light = sc.emissive(sc.solid((1.0, 0.9, 0.8)), 5.0)
+    sc.sphere((0.0, -1000.0, 0.0), 1000.0, grey)
+    sc.sphere((0.0, 0.6, 0.0), 0.6, grey)
+    sc.sphere((nan, 1.0, 0.0), 0.5, grey)
+    sc.sphere((1.5, 0.5, 0.0), nan, grey)
+    sc.sphere((-1.5, 0.5, 0.0), inf, grey)
+    sc.sphere((0.0, 3.0, 0.0), 0.4, light)
+    n = (0.0, 0.0, 1.0)
+    sc.triangle([(-1.0, 0.0, -1.0), (1.0, 0.0, -1.0), (0.0, inf, -1.0)], [n, n, n], grey)
+    sc.triangle([(-1.0, 0.0, -2.0), (nan, 0.0, -2.0), (0.0, 2.0, -2.0)], [n, n, n], grey)
+    sc.set_sky(sc.lerp((0.5, 0.7, 1.0), (1.0, 1.0, 1.0)), (8, 4))
+    return sc
+
+
+NON_FINITE_CAMERA = dict(origin=(0.0, 1.5, 6.0), lookat=(0.0, 0.6, 0.0), vup=(0.0, 1.0, 0.0), fov=50.0,
+                         aspect_ratio=float(np.float32(16.0) / np.float32(9.0)), aperture=0.0, focus_dist=10.0)
+
+
+def single_sphere():
+    """one primitive: the root node is a leaf"""
+    sc = SceneDescription()
+    sc.sphere((0, 0, -3), 1.0, sc.lambertian(sc.solid(0.5), 0.5))
+    sc.set_sky(sc.lerp((0.5, 0.7, 1.0), (1, 1, 1)), (8, 4))
+    return sc
+
+
+def degenerate_geometry():
+    """zero-area triangles, a zero-radius sphere, and a refracting sphere around the origin (where ORIGIN_CAMERA sits)"""
+    sc = SceneDescription()
+    m = sc.lambertian(sc.solid(0.7), 0.9)
+    n = (0.0, 0.0, 1.0)
+    sc.triangle([(0, 0, -2), (0, 0, -2), (0, 0, -2)], [n, n, n], m)            # a point
+    sc.triangle([(-1, 0, -2), (0, 0, -2), (1, 0, -2)], [n, n, n], m)           # collinear
+    sc.triangle([(-1, -1, -4), (1, -1, -4), (0, 1, -4)], [n, n, n], m)         # a real one behind them
+    sc.sphere((0.5, 0.5, -2.5), 0.0, m)                                        # zero radius
+    sc.sphere((0, 0, 0), 0.5, sc.refract(sc.solid(1.0), 1.5))                  # the camera sits inside this one
+    sc.sphere((0, -100.5, -3), 100.0, m)
+    sc.set_sky(sc.lerp((0.5, 0.7, 1.0), (1, 1, 1)), (8, 4))
+    return sc
+
+
+# at the origin, looking down -z: in front of single_sphere(), inside the glass of degenerate_geometry()
+ORIGIN_CAMERA = dict(origin=(0, 0, 0), lookat=(0, 0, -1), vup=(0, 1, 0), fov=60.0, aspect_ratio=1.0, aperture=0.0, focus_dist=1.0)
