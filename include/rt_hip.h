@@ -328,6 +328,26 @@ int rt_scene_get_leaf_boxes(const rt_scene *scene, float *out, uint64_t capacity
 int rt_scene_get_wide_nodes_compact(const rt_scene *scene, void *out, uint64_t capacity_nodes);
 int rt_scene_get_leaf_boxes_compact(const rt_scene *scene, float *out, uint64_t capacity_leaves, uint64_t *n_leaves);
 
+/* The sky's sampling tables as the host built them (Sky::new, sky.rs:22-39; csrc/rt_build.cpp), for inspection by tests; both calls
+ * work on host-only scenes.  guide_k: entries per guide row (16 ... 256), 0 = no guides (a resolution above 254, or a CDF that is
+ * not finite and non-decreasing: the kernels then search as the reference does).  inv_res_ok / inv_res_x / inv_res_y: whether
+ * sky_sample divides by both resolutions through verified reciprocals (see the division self-test below), and the two candidates
+ * as the verification left them.  table_bytes: CDFs + guides, the size a render launch compares with its limit for tables in LDS
+ * (rt_launch_info.sky_in_lds).  A sky with sampler_res 0 x 0 reports zeros and has no tables to copy. */
+typedef struct rt_sky_info {
+	uint32_t res_x, res_y;
+	uint32_t guide_k;
+	uint32_t inv_res_ok;
+	float inv_res_x, inv_res_y;
+	uint64_t table_bytes;
+} rt_sky_info;
+int rt_scene_sky_info(const rt_scene *scene, rt_sky_info *info);
+/* row_cdf: res_y rows of res_x + 1; marginal_cdf: res_y + 1; guide (unless NULL, and only where guide_k != 0): res_y + 1 rows of
+ * guide_k bytes, row res_y the marginal's -- entry k of a row is the number of CDF entries <= k / guide_k.  The capacities count
+ * elements of each buffer; one that is too small is RT_ERR_INVALID_ARGUMENT and nothing is written. */
+int rt_scene_get_sky_tables(const rt_scene *scene, float *row_cdf, uint64_t capacity_rows, float *marginal_cdf, uint64_t capacity_marginal,
+                            uint8_t *guide, uint64_t capacity_guide);
+
 /* How the BVH is walked: -1 automatic (default), 0 exhaustive = every AABB-hit node and every
  * primitive of every hit leaf, the reference's own amount of work (acceleration/mod.rs:199-224,
  * 270-293), 1 = near-first with t-pruning.  All modes return the same hits. */
@@ -1061,6 +1081,15 @@ int rt_selftest_division(float divisor, float *reciprocal, int *exact);
  * 8 Ray::new (rt_core/src/ray.rs:13-46).  Every count must be zero. ---- */
 #define RT_SELFTEST_LEAN_CLASSES 9
 int rt_selftest_lean(int device, uint64_t n_per_thread, uint64_t seed, uint64_t mismatches[RT_SELFTEST_LEAN_CLASSES]);
+
+/* ---- self-test of the kernels' sky sampling: sky_sample and sky_pdf of csrc/rt_shade.h as the render kernels inline them, run
+ * directly on the scene's device.  Blocking; host buffers.  Sample i < n seeds its stream as pixel 0, sample i of `seed`, draws a
+ * direction (out_dirs: 3 * n) and evaluates the pdf there (out_pdf_of_sample: n); out_pdf[j] is the pdf at dirs[3 j .. 3 j + 2],
+ * j < m.  tables_in_lds = 0 reads the tables from global memory, 1 stages tables and guides into LDS the way a render launch
+ * does: RT_ERR_UNSUPPORTED when they exceed the limit such a launch applies.  RT_ERR_INVALID_ARGUMENT for a sky that is not
+ * samplable (sampler_res 0 x 0), RT_ERR_NO_DEVICE on a host-only scene. ---- */
+int rt_selftest_sky(rt_scene *scene, int tables_in_lds, uint64_t seed, uint64_t n, float *out_dirs, float *out_pdf_of_sample,
+                    const float *dirs, uint64_t m, float *out_pdf);
 
 #ifdef __cplusplus
 }

@@ -774,6 +774,17 @@ int ora_rng_fill_f32(uint64_t seed, uint64_t pixel, uint64_t sample, uint64_t n,
 		out[i] = rt_rng_f32(&r);
 	return RT_OK;
 }
+/* the first `per_stream` draws of streams (pixel 0, sample 0 .. n_streams - 1): the streams ora_sample_directions seeds */
+int ora_rng_fill_streams_f32(uint64_t seed, uint64_t n_streams, uint64_t per_stream, float *out)
+{
+	for (uint64_t i = 0; i < n_streams; ++i) {
+		rt_rng r;
+		rt_rng_seed(&r, seed, 0, i);
+		for (uint64_t k = 0; k < per_stream; ++k)
+			out[i * per_stream + k] = rt_rng_f32(&r);
+	}
+	return RT_OK;
+}
 int ora_rng_fill_u32(uint64_t seed, uint64_t pixel, uint64_t sample, uint64_t n, uint32_t *out)
 {
 	rt_rng r;

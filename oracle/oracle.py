@@ -214,6 +214,13 @@ def rng_f32(seed, pixel, sample, n):
     return out
 
 
+def rng_streams_f32(seed, n_streams, per_stream):
+    """[n_streams, per_stream]: the first draws of streams (pixel 0, sample i), the streams sample_directions runs on"""
+    out = np.zeros((n_streams, per_stream), dtype=np.float32)
+    _check(lib().ora_rng_fill_streams_f32(C.c_uint64(seed), C.c_uint64(n_streams), C.c_uint64(per_stream), _p(out, C.c_float)))
+    return out
+
+
 def rng_u32(seed, pixel, sample, n):
     out = np.zeros(n, dtype=np.uint32)
     _check(lib().ora_rng_fill_u32(C.c_uint64(seed), C.c_uint64(pixel), C.c_uint64(sample), C.c_uint64(n),

@@ -62,6 +62,7 @@ int ora_integrate_ray(const ora_scene *scene, const rt_ray_desc *ray, int32_t re
 /* elementwise rt_detmath functions: which = 0 sin, 1 cos, 2 acos, 3 atan2(a,b), 4 tan, 5 pow5 */
 int ora_detmath_eval(int32_t which, const float *a, const float *b, uint64_t n, float *out);
 int ora_rng_fill_f32(uint64_t seed, uint64_t pixel, uint64_t sample, uint64_t n, float *out);
+int ora_rng_fill_streams_f32(uint64_t seed, uint64_t n_streams, uint64_t per_stream, float *out);
 int ora_rng_fill_u32(uint64_t seed, uint64_t pixel, uint64_t sample, uint64_t n, uint32_t *out);
 int ora_rng_fill_below(uint64_t seed, uint32_t bound, uint64_t n, uint32_t *out);
 /* directions sampled by: 0 lambertian(incoming,normal), 1 trowbridge-reitz VNDF(alpha),

@@ -201,6 +201,18 @@ class LaunchInfo(C.Structure):  # rt_launch_info
     ]
 
 
+class SkyInfo(C.Structure):  # rt_sky_info
+    _fields_ = [
+        ("res_x", C.c_uint32),
+        ("res_y", C.c_uint32),
+        ("guide_k", C.c_uint32),
+        ("inv_res_ok", C.c_uint32),
+        ("inv_res_x", C.c_float),
+        ("inv_res_y", C.c_float),
+        ("table_bytes", C.c_uint64),
+    ]
+
+
 class AovBuffers(C.Structure):  # rt_aov_buffers
     _fields_ = [
         ("albedo", C.POINTER(C.c_float)),
@@ -459,6 +471,7 @@ EXPECTED_SIZES = {
     "rt_bvh_node": (BvhNode, 56),
     "rt_sampler_progress": (SamplerProgressC, 32),
     "rt_launch_info": (LaunchInfo, 224),
+    "rt_sky_info": (SkyInfo, 32),
     "rt_aov_buffers": (AovBuffers, 48),
     "rt_aov_chain_opts": (AovChainOpts, 32),
     "rt_aov_chain_buffers": (AovChainBuffers, 56),
@@ -504,6 +517,8 @@ EXPORTED_SYMBOLS = [
     "rt_rccl_probe",
     "rt_selftest_division",
     "rt_scene_get_leaf_boxes_compact",
+    "rt_scene_sky_info",
+    "rt_scene_get_sky_tables",
     "rt_scene_set_traversal",
     "rt_scene_set_tuning",
     "rt_render",
@@ -520,6 +535,7 @@ EXPORTED_SYMBOLS = [
     "rt_check_hit",
     "rt_check_hit_index",
     "rt_selftest_lean",
+    "rt_selftest_sky",
     "rt_render_aov",
     "rt_render_aov_device",
     "rt_aov_chain_opts_default",

@@ -24,6 +24,7 @@
 #include <dlfcn.h>
 #include "rt_api_internal.h"
 #include "rt_render.h"
+#include "rt_sky_selftest.h"
 
 using namespace rt;
 
@@ -227,6 +228,26 @@ static int multi_decide_gather(rt_scene *head, const std::vector<rt_scene *> &me
 	return RT_OK;
 }
 
+// u = nu / res_x, v = nv / res_y of sky_sample (rt_shade.h): the verified reciprocals of both resolutions, or *ok = 0 (plain division)
+static void sky_reciprocals(const rt_sky_desc &sky, uint32_t *ok, float *inv_x, float *inv_y)
+{
+	*ok = 0u;
+	*inv_x = *inv_y = 0.0f;
+	if (sky.sampler_res_x != 0 && sky.sampler_res_y != 0 && sky.sampler_res_x < (1u << 24) && sky.sampler_res_y < (1u << 24)) {
+		const bool ok_x = verified_reciprocal((float)sky.sampler_res_x, inv_x), ok_y = verified_reciprocal((float)sky.sampler_res_y, inv_y);
+		*ok = (ok_x && ok_y) ? 1u : 0u;
+	}
+}
+
+// the bytes of the sky's CDF tables and guides: what a launch compares with kSkyLdsLimit before it asks for them in LDS
+constexpr size_t kSkyLdsLimit = 96 * 1024;
+static size_t sky_table_bytes(uint32_t res_x, uint32_t res_y, uint32_t guide_k)
+{
+	if ((res_x | res_y) == 0u)
+		return 0;
+	return ((size_t)res_y * (res_x + 1u) + res_y + 1u) * 4 + (size_t)(res_y + 1u) * guide_k;
+}
+
 // Lays a built scene out in the HBM of s->device (every array of rt_types.h) and creates the scene's stream, events and
 // counters.  `h` is only read: the members of a multi-device scene (rt_scene_create_multi) are uploaded from one host build.
 static int upload_scene(rt_scene *s, const HostScene &h)
@@ -345,13 +366,7 @@ static int upload_scene(rt_scene *s, const HostScene &h)
 		float rc_pi = 0.0f, rc_tau = 0.0f;
 		if (!verified_reciprocal(RT_PI, &rc_pi) || !verified_reciprocal(RT_TAU, &rc_tau) || rc_pi != 1.0f / RT_PI || rc_tau != 1.0f / RT_TAU)
 			return bail(fail(RT_ERR_UNSUPPORTED, "self-check failed: division by pi / 2 pi through their reciprocals is not exact on this host (the kernels assume it)"));
-		D.sky.inv_res_ok = 0u;
-		D.sky.inv_res_x = D.sky.inv_res_y = 0.0f;
-		if (h.sky.sampler_res_x != 0 && h.sky.sampler_res_y != 0 && h.sky.sampler_res_x < (1u << 24) && h.sky.sampler_res_y < (1u << 24)) {
-			const bool ok_x = verified_reciprocal((float)h.sky.sampler_res_x, &D.sky.inv_res_x), ok_y = verified_reciprocal((float)h.sky.sampler_res_y, &D.sky.inv_res_y);
-			const bool ok = ok_x && ok_y;
-			D.sky.inv_res_ok = ok ? 1u : 0u;
-		}
+		sky_reciprocals(h.sky, &D.sky.inv_res_ok, &D.sky.inv_res_x, &D.sky.inv_res_y);
 		// Lambertian numerators (rt_shade.h cosine_is_tame_): SolidColour textures, |colour x albedo| components zero or in
 		// [2^-30, 2^30], vertex normals finite and below 2^20
 		bool tame = true;
@@ -789,6 +804,34 @@ int rt_scene_get_leaf_boxes_compact(const rt_scene *s, float *out, uint64_t capa
 	std::memcpy(out, s->host.leaf_box_c.data(), s->host.leaf_box_c.size() * sizeof(DevLeafBox));
 	return RT_OK;
 }
+int rt_scene_sky_info(const rt_scene *s, rt_sky_info *info)
+{
+	if (!s || !info)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(info, 0, sizeof *info);
+	info->res_x = s->host.sky.sampler_res_x;
+	info->res_y = s->host.sky.sampler_res_y;
+	info->guide_k = s->host.sky_guide_k;
+	sky_reciprocals(s->host.sky, &info->inv_res_ok, &info->inv_res_x, &info->inv_res_y);
+	info->table_bytes = sky_table_bytes(info->res_x, info->res_y, info->guide_k);
+	return RT_OK;
+}
+int rt_scene_get_sky_tables(const rt_scene *s, float *row_cdf, uint64_t capacity_rows, float *marginal_cdf, uint64_t capacity_marginal, uint8_t *guide,
+                            uint64_t capacity_guide)
+{
+	if (!s || !row_cdf || !marginal_cdf)
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments");
+	const size_t rx = s->host.sky.sampler_res_x, ry = s->host.sky.sampler_res_y;
+	if ((rx | ry) == 0 || s->host.sky_cdf.size() != ry * (rx + 1) + ry + 1)
+		return fail(RT_ERR_INVALID_ARGUMENT, "the sky has no tables (sampler_res 0 x 0)");
+	if (capacity_rows < ry * (rx + 1) || capacity_marginal < ry + 1 || (guide && capacity_guide < s->host.sky_guide.size()))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments");
+	std::memcpy(row_cdf, s->host.sky_cdf.data(), ry * (rx + 1) * sizeof(float));
+	std::memcpy(marginal_cdf, s->host.sky_cdf.data() + ry * (rx + 1), (ry + 1) * sizeof(float));
+	if (guide && !s->host.sky_guide.empty())
+		std::memcpy(guide, s->host.sky_guide.data(), s->host.sky_guide.size());
+	return RT_OK;
+}
 int rt_scene_get_lights(const rt_scene *s, uint64_t *out, uint64_t capacity)
 {
 	if (!s || !out || capacity < s->host.lights.size())
@@ -972,8 +1015,7 @@ static int plan_render_launch(const rt_scene *s, const rt_render_opts *o, const 
 	P.prune = prune ? 1 : 0;
 
 	const bool samplable = (s->dev.sky.res_x | s->dev.sky.res_y) != 0u;
-	const size_t sky_bytes = samplable ? ((size_t)s->dev.sky.res_y * (s->dev.sky.res_x + 1u) + s->dev.sky.res_y + 1u) * 4 +
-	                                         (size_t)(s->dev.sky.res_y + 1u) * s->dev.sky.guide_k : 0;
+	const size_t sky_bytes = sky_table_bytes(s->dev.sky.res_x, s->dev.sky.res_y, s->dev.sky.guide_k);
 	// Sky CDF tables in LDS (next to the traversal stacks) or left in global memory: LDS only while
 	// it does not cost resident workgroups.  Tiny trees: 41 KB tables + 1-2 KB stacks still fit 3
 	// workgroups per CU, the register limit.  Deep trees: the stacks alone are tens of KB and the
@@ -1019,7 +1061,7 @@ static int plan_render_launch(const rt_scene *s, const rt_render_opts *o, const 
 	P.stack_cap = stack_cap;
 	P.stack_ovf_depth = stack_need - stack_cap;
 	// What one workgroup size gives: resident workgroups per CU without and -- where that does not cost any -- with the sky tables in LDS
-	const bool sky_lds_possible = samplable && o->render_method == RT_METHOD_MIS && sky_bytes <= 96 * 1024;
+	const bool sky_lds_possible = samplable && o->render_method == RT_METHOD_MIS && sky_bytes <= kSkyLdsLimit;
 	struct Sizing { uint32_t block; int blocks_per_cu; bool sky; size_t lds; };
 	auto size_launch = [&](uint32_t block, Sizing &z) -> hipError_t {
 		z.block = block;
@@ -1932,6 +1974,54 @@ int rt_selftest_division(float divisor, float *reciprocal, int *exact)
 	if (!reciprocal || !exact)
 		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
 	*exact = verified_reciprocal(divisor, reciprocal) ? 1 : 0;
+	return RT_OK;
+}
+
+int rt_selftest_sky(rt_scene *s, int tables_in_lds, uint64_t seed, uint64_t n, float *out_dirs, float *out_pdf_of_sample, const float *dirs, uint64_t m,
+                    float *out_pdf)
+{
+	if (!s || (tables_in_lds != 0 && tables_in_lds != 1) || (n && (!out_dirs || !out_pdf_of_sample)) || (m && (!dirs || !out_pdf)))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments");
+	if (n > (1ull << 28) || m > (1ull << 28))
+		return fail(RT_ERR_INVALID_ARGUMENT, "at most 2^28 samples and 2^28 directions");
+	if ((s->host.sky.sampler_res_x | s->host.sky.sampler_res_y) == 0u)
+		return fail(RT_ERR_INVALID_ARGUMENT, "the sky is not samplable (sampler_res 0 x 0)");
+	if (int rc = need_device(s); rc != RT_OK)
+		return rc;
+	if (tables_in_lds && (sky_table_bytes(s->dev.sky.res_x, s->dev.sky.res_y, s->dev.sky.guide_k) > kSkyLdsLimit || sky_selftest_lds_bytes(s->dev) > s->max_lds))
+		return fail(RT_ERR_UNSUPPORTED, "the sky tables exceed what a launch stages into LDS");
+	if (n + m == 0)
+		return RT_OK;
+	HIP_TRY(hipSetDevice(s->device));
+	// one allocation: directions and pdfs of the samples, then the caller's directions and their pdfs
+	float *d = nullptr;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), (4 * n + 4 * m) * sizeof(float)));
+	DevSkySelftest P;
+	P.seed = seed;
+	P.n = n;
+	P.m = m;
+	P.out_dirs = d;
+	P.out_pdf_s = d + 3 * n;
+	float *d_dirs = d + 4 * n;
+	P.dirs = d_dirs;
+	P.out_pdf = d_dirs + 3 * m;
+	hipError_t e = hipSuccess;
+	if (m)
+		e = hipMemcpyAsync(d_dirs, dirs, 3 * m * sizeof(float), hipMemcpyHostToDevice, s->stream);
+	if (e == hipSuccess)
+		e = launch_sky_selftest(tables_in_lds != 0, s->stream, s->dev, P);
+	if (e == hipSuccess && n)
+		e = hipMemcpyAsync(out_dirs, P.out_dirs, 3 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
+	if (e == hipSuccess && n)
+		e = hipMemcpyAsync(out_pdf_of_sample, P.out_pdf_s, n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
+	if (e == hipSuccess && m)
+		e = hipMemcpyAsync(out_pdf, P.out_pdf, m * sizeof(float), hipMemcpyDeviceToHost, s->stream);
+	const hipError_t e_sync = hipStreamSynchronize(s->stream);
+	if (e == hipSuccess)
+		e = e_sync;
+	(void)hipFree(d);
+	if (e != hipSuccess)
+		return hip_fail(e, "selftest_sky");
 	return RT_OK;
 }
 

@@ -1,0 +1,24 @@
+// rt_sky_selftest.h -- launch interface of the sky self-test kernel (rt_sky_selftest.hip), shared with rt_api.cpp.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "rt_types.h"
+
+namespace rt {
+
+struct DevSkySelftest {
+	uint64_t seed;
+	uint64_t n;          // streams: sample i runs on rt_rng_seed(seed, 0, i)
+	float *out_dirs;     // 3 * n: sky_sample of stream i
+	float *out_pdf_s;    // n: sky_pdf at that direction
+	const float *dirs;   // 3 * m directions the caller chose
+	uint64_t m;
+	float *out_pdf;      // m: sky_pdf at each of them
+};
+
+// the dynamic LDS the kernel needs with the tables staged (render_kernel's prologue layout: rows, marginal, padding to 16 bytes, guides)
+size_t sky_selftest_lds_bytes(const DevScene &S);
+hipError_t launch_sky_selftest(bool tables_in_lds, hipStream_t stream, const DevScene &S, const DevSkySelftest &P);
+
+} // namespace rt

@@ -214,6 +214,36 @@ class HipScene:
             _check(lib().rt_scene_get_leaf_boxes_compact(self._h, _p(boxes, C.c_float), C.c_uint64(boxes.shape[0]), C.byref(n_leaves)))
         return nodes[:n.value], boxes[:n_leaves.value]
 
+    def sky_info(self):
+        """rt_scene_sky_info as a dict: res_x, res_y, guide_k, inv_res_ok, the two reciprocals (f32) and table_bytes"""
+        si = abi.SkyInfo()
+        _check(lib().rt_scene_sky_info(self._h, C.byref(si)))
+        d = {name: getattr(si, name) for name, _ in abi.SkyInfo._fields_}
+        d["inv_res_x"], d["inv_res_y"] = np.float32(si.inv_res_x), np.float32(si.inv_res_y)
+        return d
+
+    def sky_tables(self):
+        """(row CDFs [res_y, res_x + 1], marginal CDF [res_y + 1], guide bytes [res_y + 1, guide_k] or None) as the host built them"""
+        si = self.sky_info()
+        rows = np.zeros((si["res_y"], si["res_x"] + 1), dtype=np.float32)
+        marg = np.zeros(si["res_y"] + 1, dtype=np.float32)
+        guide = np.zeros((si["res_y"] + 1, si["guide_k"]), dtype=np.uint8) if si["guide_k"] else None
+        _check(lib().rt_scene_get_sky_tables(self._h, _p(rows, C.c_float), C.c_uint64(rows.size), _p(marg, C.c_float), C.c_uint64(marg.size),
+                                             _p(guide, C.c_uint8) if guide is not None else None, C.c_uint64(0 if guide is None else guide.size)))
+        return rows, marg, guide
+
+    def selftest_sky(self, tables_in_lds, n, seed=1, dirs=None):
+        """rt_selftest_sky: (directions [n, 3] of sky_sample on streams 0..n-1 of `seed`, sky_pdf at each of them [n], sky_pdf at
+        each row of `dirs` [m]) computed by the kernels' own sky code, with the tables in global memory (0) or staged in LDS (1)"""
+        dirs = np.zeros((0, 3), np.float32) if dirs is None else np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        m = dirs.shape[0]
+        out_dirs = np.zeros((max(1, n), 3), dtype=np.float32)
+        out_pdf_s = np.zeros(max(1, n), dtype=np.float32)
+        out_pdf = np.zeros(max(1, m), dtype=np.float32)
+        _check(lib().rt_selftest_sky(self._h, C.c_int(int(tables_in_lds)), C.c_uint64(seed), C.c_uint64(n), _p(out_dirs, C.c_float),
+                                     _p(out_pdf_s, C.c_float), _p(dirs, C.c_float) if m else None, C.c_uint64(m), _p(out_pdf, C.c_float)))
+        return out_dirs[:n], out_pdf_s[:n], out_pdf[:m]
+
     def set_traversal(self, mode):
         """-1 auto, 0 exhaustive (reference amount of work), 1 pruned."""
         _check(lib().rt_scene_set_traversal(self._h, C.c_int(mode)))
