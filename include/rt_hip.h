@@ -825,6 +825,83 @@ int rt_render_converged(rt_scene *scene, const rt_camera *camera, const rt_rende
 int rt_render_denoised_split(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_denoise_opts *dopts,
                              float *out_clean, float *out_noisy, float *out_variance, uint64_t *rays_shot);
 
+/* ---- Firefly-robust frames (csrc/rt_robust.hip): a rank-trimmed mean of the chunk sums.  The integrator keeps the reference's
+ * quirks, so one wild sample -- or one inf / NaN -- ends up in a pixel's mean, where no later stage can undo it.  The S
+ * independent sums per pixel that a render at sample_split = S > 1 leaves in the scene's partial buffer (see the noise estimates
+ * above) are what a median-of-means / trimmed-mean estimator needs, at no extra ray and from the SAME launch rt_render_device
+ * makes.  The adaptive mode, driven by the Gini coefficient of the chunk means, follows the idea of Buisine et al., "Firefly
+ * removal in Monte Carlo rendering with adaptive Median of meaNs", EGSR 2021; the definition below is this library's own.
+ * W x H, RT_LAYOUT_FRAME, f32 throughout with the library's arithmetic contract: IEEE `/`, no fma, sums left to right from +0.
+ * Per pixel: S chunk sums sum_c (3 channels), the chunk length n in passes, optionally an albedo.
+ * Keys.    l_c = lum(sum_c / (float)n / d) per channel, exactly the l_c of the noise estimates: d = fmaxf(albedo, 1e-3f) per
+ *   channel with an albedo plane, else 1; lum is rt_denoise's.  Chunk c is FINITE iff l_c is finite; S_f = the number of finite
+ *   chunks.  The ordering key k_c is a uint32: 0xFFFFFFFF if l_c is not finite (NaN, +inf and -inf alike); otherwise, with b the
+ *   bits of l_c, ~b if the sign bit of b is set, else b | 0x80000000 -- the order of the values, with -0 below +0.
+ * Ranks.   r_c = #{ j : k_j < k_c, or k_j == k_c and j < c }: a permutation of 0 .. S-1 in which the finite chunks hold the ranks
+ *   0 .. S_f-1 and ties go to the lower chunk index.
+ * Gini.    Over the finite chunks in chunk order, from +0:  A = sum (float)(2*r_c - (S_f - 1)) * l_c  (the integer coefficient
+ *   is exact),  B = sum l_c,  G = A / ((float)S_f * B),  g = fminf(fmaxf(G, 0.0f), 1.0f) with C's fmaxf: a NaN G (an all-black
+ *   pixel) gives g = 0; so does S_f = 0.  fmaxf(-0, +0), which C leaves open, is +0 here: g is never -0.
+ * Trim.    tmax = (S_f - 1) / 2 in integers, 0 for S_f = 0.
+ *   RT_ROBUST_TRIM: t = min(trim, tmax).   RT_ROBUST_MEDIAN: t = tmax.
+ *   RT_ROBUST_GINI: t = (uint32_t)fminf(g * gini_gain * (float)tmax, (float)tmax)   (products left to right).
+ * Output.  Chunk c is KEPT iff it is finite and t <= r_c < S_f - t: k = S_f - 2t >= 1 chunks whenever S_f >= 1.
+ *   out = (sum over the kept c, in CHUNK order from +0, of sum_c) / (float)(k * n) per channel   (k * n in integers)
+ *   The sum runs in chunk order, not in sorted order.  With t = 0 and S_f = S this is (sum_0 + ... + sum_{S-1}) / (float)spp: the
+ *   bytes of rt_render at that split.  For S_f = 0, out is that plain combine over all chunks, non-finite as the arithmetic gives it.
+ *   mean = the plain combine.   Optional planes, w*h each: gini = g (f32), trimmed = t (uint8), dropped = S - S_f (uint8).
+ * SYMMETRIC TRIMMING OF A SKEWED DISTRIBUTION DARKENS: a pixel's samples are skewed to the bright side, the t highest chunks carry
+ *   more than the t lowest, and the trimmed mean is below the mean in expectation.  That is the price of the estimator; it is not
+ *   corrected.  Neither the darkening nor what the defaults do to an image has been measured.
+ * Options (32 bytes): mode (default RT_ROBUST_GINI); trim (default 1); gini_gain finite and > 0 (default 1.0), checked in every
+ *   mode; `reserved` must be zero.  THE DEFAULTS ARE STARTING VALUES NOBODY HAS TUNED: no image set has been rendered to choose them.
+ *
+ * rt_render_robust_device: DEVICE buffers, asynchronous on hip_stream: the launches of rt_render_device(opts with the split)
+ *   under the split rule of the noise estimates (an explicit sample_split in 2 .. 64 dividing samples_per_pixel, or the automatic
+ *   one halved until it does) into `mean` -- or into scene-owned scratch if `mean` is NULL -- then ONE kernel on the partial buffer
+ *   that launch leaves behind.  `out` is required; any other field of rt_robust_buffers may be NULL.  d_albedo (3*w*h,
+ *   rt_render_aov's) or NULL.  Restrictions as rt_render_noise_device: RT_LAYOUT_FRAME and shard_count 1, a multi-device scene is
+ *   RT_ERR_UNSUPPORTED.  The scratch is grown on first use and for larger frames only, so -- like the partial buffer -- the first
+ *   call of a scene at a frame size cannot be captured into a graph; later ones can.
+ * rt_render_robust: the same on HOST buffers, blocking; *rays_shot unless NULL.
+ * rt_robust_combine[_device]: the same kernel on the CALLER's chunk sums, [S][h][w][3] in frame raster: S renders of different
+ *   sample windows (each times its passes), rt_sample_image batches, the shards of a multi-device job.  split in 2 .. 64,
+ *   chunk_passes >= 1, split * chunk_passes < 2^32, width and height >= 1.  Here `mean`, if given, is written by the kernel.  The
+ *   _device form allocates nothing and keeps no state: it can be captured into a graph from its first call.
+ * rt_render_denoised_robust: blocking: the albedo / normal / depth AOVs, rt_render_robust_device with that albedo, then
+ *   rt_denoise_device on (out, albedo, normal, depth) with NO variance plane: the filter uses its own 5 x 5 estimate (a variance
+ *   of the trimmed mean is not defined here).  out_robust (may be NULL) gets the robust frame.  Checks as rt_render_denoised_split.
+ * Checks: RT_ERR_INVALID_ARGUMENT for a NULL argument (or `out`), options outside their ranges, a split the rule refuses, written
+ * buffers that overlap each other or a buffer read; then RT_ERR_UNSUPPORTED as above; the device last (RT_ERR_NO_DEVICE), so a
+ * host-only scene reports bad arguments as such.  Afterwards rt_last_kernel_ms and rt_last_launch_info describe the render launch
+ * (rt_robust_combine leaves them alone); a following rt_render returns what it would have. */
+typedef enum { RT_ROBUST_TRIM = 0, RT_ROBUST_MEDIAN = 1, RT_ROBUST_GINI = 2 } rt_robust_mode;
+typedef struct rt_robust_opts {
+	int32_t mode;      /* rt_robust_mode; default RT_ROBUST_GINI (untuned) */
+	uint32_t trim;     /* RT_ROBUST_TRIM: chunks cut from each end; default 1 (untuned) */
+	float gini_gain;   /* RT_ROBUST_GINI; default 1.0 (untuned) */
+	uint32_t reserved[5];
+} rt_robust_opts;
+typedef struct rt_robust_buffers {
+	float *out;       /* 3*w*h, required */
+	float *mean;      /* 3*w*h or NULL */
+	float *gini;      /* w*h or NULL */
+	uint8_t *trimmed; /* w*h or NULL */
+	uint8_t *dropped; /* w*h or NULL */
+} rt_robust_buffers;
+int rt_robust_opts_default(rt_robust_opts *out);
+int rt_render_robust(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_robust_opts *ropts,
+                     const float *albedo_or_null, const rt_robust_buffers *host_out, uint64_t *rays_shot);
+int rt_render_robust_device(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_robust_opts *ropts,
+                            const float *d_albedo_or_null, const rt_robust_buffers *device_out, uint64_t *d_rays_shot, void *hip_stream);
+int rt_robust_combine(rt_scene *scene, const float *chunk_sums, uint32_t split, uint64_t chunk_passes, uint32_t width, uint32_t height,
+                      const float *albedo_or_null, const rt_robust_opts *ropts, const rt_robust_buffers *host_out);
+int rt_robust_combine_device(rt_scene *scene, const float *d_chunk_sums, uint32_t split, uint64_t chunk_passes, uint32_t width,
+                             uint32_t height, const float *d_albedo_or_null, const rt_robust_opts *ropts,
+                             const rt_robust_buffers *device_out, void *hip_stream);
+int rt_render_denoised_robust(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_robust_opts *ropts,
+                              const rt_denoise_opts *dopts, float *out_clean, float *out_robust, uint64_t *rays_shot);
+
 /* ---- Temporal accumulation with camera reprojection (csrc/rt_temporal.hip): the temporal half of SVGF (Schied et al. HPG 2017) in
  * front of the A-Trous filter above, for a static scene seen by a moving camera.  W x H (both >= 2, the AOV rule), FRAME layout,
  * row-major, y down, f32 throughout with the library's arithmetic contract: IEEE `/` and sqrtf, no fma, sums left to right.

@@ -520,6 +520,63 @@ inline ConvergedFrame render_converged(const RenderOptions &o, const SimpleCamer
 	return r;
 }
 
+// Firefly-robust frames (semantics: rt_hip.h rt_robust_opts): from ONE render at `sample_split` (2..64 dividing the passes, 0 =
+// automatic) the rank-trimmed mean of its chunk sums next to the plain mean rt_render gives at that split.  Symmetric trimming
+// darkens; the defaults are untuned starting values.
+struct RobustOptions {
+	rt_robust_mode mode = RT_ROBUST_GINI;
+	uint32_t trim = 1;
+	float gini_gain = 1.0f;
+};
+struct RobustFrame {
+	std::vector<float> out, mean;         // 3*w*h
+	std::vector<float> gini;              // w*h
+	std::vector<uint8_t> trimmed, dropped; // w*h
+	uint64_t rays_shot = 0;
+};
+namespace detail {
+inline rt_robust_opts robust_opts(const RobustOptions &r)
+{
+	rt_robust_opts o;
+	check(rt_robust_opts_default(&o));
+	o.mode = static_cast<int32_t>(r.mode);
+	o.trim = r.trim;
+	o.gini_gain = r.gini_gain;
+	return o;
+}
+inline rt_robust_buffers robust_frame(RobustFrame &f, size_t px)
+{
+	f.out.resize(3 * px);
+	f.mean.resize(3 * px);
+	f.gini.resize(px);
+	f.trimmed.resize(px);
+	f.dropped.resize(px);
+	return rt_robust_buffers{f.out.data(), f.mean.data(), f.gini.data(), f.trimmed.data(), f.dropped.data()};
+}
+} // namespace detail
+inline RobustFrame render_robust(const RenderOptions &o, const SimpleCamera &camera, const Bvh &bvh, uint32_t sample_split = 0,
+                                 const RobustOptions &r = RobustOptions(), uint64_t seed = 1, uint64_t sample_begin = 0)
+{
+	rt_render_opts opts = detail::noise_render_opts(o, sample_split, seed, sample_begin);
+	opts.render_method = static_cast<int32_t>(o.render_method);
+	const rt_robust_opts ropts = detail::robust_opts(r);
+	RobustFrame f;
+	const rt_robust_buffers b = detail::robust_frame(f, (size_t)o.width * o.height);
+	check(rt_render_robust(bvh.raw(), &camera.raw(), &opts, &ropts, nullptr, &b, &f.rays_shot));
+	return f;
+}
+// The same estimator on the caller's chunk sums, split * width * height * 3 floats laid out [chunk][y][x][3], each the sum of
+// chunk_passes passes (rt_robust_combine); `bvh` names the GPU.
+inline RobustFrame robust_combine(const Bvh &bvh, const std::vector<float> &chunk_sums, uint32_t split, uint64_t chunk_passes, uint32_t width,
+                                  uint32_t height, const RobustOptions &r = RobustOptions())
+{
+	const rt_robust_opts ropts = detail::robust_opts(r);
+	RobustFrame f;
+	const rt_robust_buffers b = detail::robust_frame(f, (size_t)width * height);
+	check(rt_robust_combine(bvh.raw(), chunk_sums.data(), split, chunk_passes, width, height, nullptr, &ropts, &b));
+	return f;
+}
+
 // The A-Trous denoiser of rt_hip.h (rt_denoise_opts): the options a caller sets; defaults as rt_denoise_opts_default.
 struct DenoiseOptions {
 	uint32_t iterations = 5;

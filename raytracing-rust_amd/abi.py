@@ -340,6 +340,34 @@ class NoiseResult(C.Structure):  # rt_noise_result
 NOISE_CHANNELS = ("mean", "variance", "lum_mean", "tile_error", "summary")
 
 
+# firefly-robust frames (rt_render_robust, rt_robust_combine, rt_render_denoised_robust)
+RT_ROBUST_TRIM, RT_ROBUST_MEDIAN, RT_ROBUST_GINI = range(3)  # rt_robust_mode
+ROBUST_MODES = {"trim": RT_ROBUST_TRIM, "median": RT_ROBUST_MEDIAN, "gini": RT_ROBUST_GINI}
+ROBUST_MAX_SPLIT = 64  # the most chunks a pixel is ranked over
+
+
+class RobustOpts(C.Structure):  # rt_robust_opts
+    _fields_ = [
+        ("mode", C.c_int32),
+        ("trim", C.c_uint32),
+        ("gini_gain", C.c_float),
+        ("reserved", C.c_uint32 * 5),
+    ]
+
+
+class RobustBuffers(C.Structure):  # rt_robust_buffers
+    _fields_ = [
+        ("out", C.POINTER(C.c_float)),
+        ("mean", C.POINTER(C.c_float)),
+        ("gini", C.POINTER(C.c_float)),
+        ("trimmed", C.POINTER(C.c_uint8)),
+        ("dropped", C.POINTER(C.c_uint8)),
+    ]
+
+
+ROBUST_CHANNELS = ("out", "mean", "gini", "trimmed", "dropped")
+
+
 class DenoiseOpts(C.Structure):  # rt_denoise_opts
     _fields_ = [
         ("width", C.c_uint32),
@@ -483,6 +511,8 @@ EXPECTED_SIZES = {
     "rt_noise_summary": (NoiseSummary, 16),
     "rt_noise_buffers": (NoiseBuffers, 40),
     "rt_noise_result": (NoiseResult, 40),
+    "rt_robust_opts": (RobustOpts, 32),
+    "rt_robust_buffers": (RobustBuffers, 40),
     "rt_denoise_opts": (DenoiseOpts, 48),
     "rt_denoise_inputs": (DenoiseInputs, 40),
     "rt_temporal_opts": (TemporalOpts, 96),
@@ -561,6 +591,12 @@ EXPORTED_SYMBOLS = [
     "rt_noise_tiles_device",
     "rt_render_converged",
     "rt_render_denoised_split",
+    "rt_robust_opts_default",
+    "rt_render_robust",
+    "rt_render_robust_device",
+    "rt_robust_combine",
+    "rt_robust_combine_device",
+    "rt_render_denoised_robust",
     "rt_temporal_opts_default",
     "rt_temporal_history_bytes",
     "rt_temporal_workspace_bytes",
@@ -605,6 +641,13 @@ def default_noise_opts(luminance_floor=0.01, threshold=0.05):
     """rt_noise_opts_default (include/rt_hip.h)."""
     o = NoiseOpts()
     o.luminance_floor, o.threshold = luminance_floor, threshold
+    return o
+
+
+def default_robust_opts(mode=RT_ROBUST_GINI, trim=1, gini_gain=1.0):
+    """rt_robust_opts_default (include/rt_hip.h)."""
+    o = RobustOpts()
+    o.mode, o.trim, o.gini_gain = mode, trim, gini_gain
     return o
 
 

@@ -1,6 +1,6 @@
 // rt_api_post.cpp -- the host side of the post-processing stages of librt_hip.so (include/rt_hip.h): first-hit and specular-chain
-// AOV buffers, ID mattes, ambient occlusion, the A-Trous denoiser, noise estimates, temporal accumulation, the display stage and AOV-guided upscaling.  Each stage has its kernels in a file of
-// its own (rt_aov.hip, rt_aov_chain.hip, rt_matte.hip, rt_ao.hip, rt_denoise.hip, rt_noise.hip, rt_temporal.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
+// AOV buffers, ID mattes, ambient occlusion, the A-Trous denoiser, noise estimates, firefly-robust frames, temporal accumulation, the display stage and AOV-guided upscaling.  Each stage has its kernels in a file of
+// its own (rt_aov.hip, rt_aov_chain.hip, rt_matte.hip, rt_ao.hip, rt_denoise.hip, rt_noise.hip, rt_robust.hip, rt_temporal.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
 // and the blocking wrappers that stage host buffers through scene-owned device memory (Staging, rt_api_internal.h).
 // Every check function ends with the device (need_device), so that a host-only scene reports bad arguments as such.
 #include <hip/hip_runtime.h>
@@ -18,6 +18,7 @@
 #include "rt_denoise.h"
 #include "rt_noise.h"
 #include "rt_render.h"
+#include "rt_robust.h"
 #include "rt_temporal.h"
 #include "rt_display.h"
 #include "rt_upscale.h"
@@ -1092,6 +1093,275 @@ int rt_render_denoised_split(rt_scene *s, const rt_camera *camera, const rt_rend
 	st.download(out_variance, d_var, 4 * px);
 	st.download(&rays, base, sizeof rays);
 	rc = st.finish("render_denoised_split");
+	if (rc == RT_OK && rays_shot)
+		*rays_shot = rays;
+	return rc;
+}
+
+} // extern "C"
+
+// ---- firefly-robust frames: a rank-trimmed mean of the chunk sums (rt_robust.hip) ----
+static int robust_opts_check(const rt_robust_opts *r)
+{
+	if (r->mode != RT_ROBUST_TRIM && r->mode != RT_ROBUST_MEDIAN && r->mode != RT_ROBUST_GINI)
+		return fail(RT_ERR_INVALID_ARGUMENT, "robust: unknown mode");
+	if (!std::isfinite(r->gini_gain) || !(r->gini_gain > 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "robust: gini_gain must be finite and > 0");
+	for (uint32_t w : r->reserved)
+		if (w != 0u)
+			return fail(RT_ERR_INVALID_ARGUMENT, "robust: reserved must be zero");
+	return RT_OK;
+}
+
+// the robust options, then what the noise stage asks of the scene and the render options (its split rule included)
+static int robust_render_check(const rt_scene *s, const rt_render_opts *o, const rt_robust_opts *r, uint32_t *split, uint64_t *px)
+{
+	int rc = robust_opts_check(r);
+	if (rc != RT_OK)
+		return rc;
+	rt_noise_opts n;
+	rt_noise_opts_default(&n);
+	return noise_render_check(s, o, &n, o->samples_per_pixel, split, px);
+}
+
+// the five outputs against each other and against what is read (`sums` of sums_bytes: the caller's planes, or NULL); the device last
+static int robust_buffers_check(const rt_scene *s, const rt_robust_buffers *b, const float *albedo, const float *sums, uint64_t sums_bytes,
+                                uint64_t n)
+{
+	if (!b->out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "rt_robust_buffers: out must not be NULL");
+	const void *buf[7] = {b->out, b->mean, b->gini, b->trimmed, b->dropped, albedo, sums};
+	const uint64_t bytes[7] = {12 * n, 12 * n, 4 * n, n, n, 12 * n, sums_bytes};
+	const int rc = check_disjoint("robust: an output buffer overlaps another buffer", buf, bytes, 5, 7);
+	return rc == RT_OK ? need_device(s) : rc;
+}
+
+static DevRobustParams robust_params(const rt_robust_opts *r, uint64_t w, uint64_t h, uint32_t split, uint32_t chunk_passes, const float *d_sums,
+                                     const float *d_albedo, const rt_robust_buffers *d_out)
+{
+	DevRobustParams P;
+	std::memset(&P, 0, sizeof P);
+	P.width = (uint32_t)w;
+	P.height = (uint32_t)h;
+	P.n_work = (uint32_t)(w * h); // frame raster; the render form sets its tiles
+	P.split = split;
+	P.chunk_passes = chunk_passes;
+	P.mode = r->mode;
+	P.trim = r->trim;
+	P.gini_gain = r->gini_gain;
+	P.sums = d_sums;
+	P.albedo = d_albedo;
+	P.out = d_out->out;
+	P.mean = d_out->mean;
+	P.gini = d_out->gini;
+	P.trimmed = d_out->trimmed;
+	P.dropped = d_out->dropped;
+	return P;
+}
+
+static int robust_combine_check(const rt_scene *s, const float *sums, uint32_t split, uint64_t chunk_passes, uint32_t w, uint32_t h,
+                                const float *albedo, const rt_robust_opts *r, const rt_robust_buffers *b, uint64_t *px)
+{
+	if (!s || !sums || !r || !b)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	int rc = robust_opts_check(r);
+	if (rc != RT_OK)
+		return rc;
+	if (split < 2u || split > kRobustMaxSplit)
+		return fail(RT_ERR_INVALID_ARGUMENT, "robust_combine: split must be in 2..64");
+	if (chunk_passes == 0 || chunk_passes >= (1ull << 32) || split * chunk_passes >= (1ull << 32))
+		return fail(RT_ERR_INVALID_ARGUMENT, "robust_combine: chunk_passes must be >= 1 and split * chunk_passes < 2^32");
+	rc = frame_pixels("robust_combine: ", w, h, 1, px);
+	if (rc != RT_OK)
+		return rc;
+	return robust_buffers_check(s, b, albedo, sums, 12 * *px * split, *px);
+}
+
+extern "C" {
+
+int rt_robust_opts_default(rt_robust_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	out->mode = RT_ROBUST_GINI;
+	out->trim = 1;
+	out->gini_gain = 1.0f;
+	return RT_OK;
+}
+
+int rt_render_robust_device(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_robust_opts *r, const float *d_albedo,
+                            const rt_robust_buffers *d_out, uint64_t *d_rays_shot, void *hip_stream)
+{
+	if (!s || !camera || !o || !r || !d_out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	uint32_t split = 0;
+	uint64_t px = 0;
+	int rc = robust_render_check(s, o, r, &split, &px);
+	if (rc == RT_OK)
+		rc = robust_buffers_check(s, d_out, d_albedo, nullptr, 0, px);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+	float *d_render = d_out->mean;
+	if (!d_render) { // the render's frame goes to the noise stage's scratch: grows on first use only (not capturable on that call)
+		rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, 12 * px);
+		if (rc != RT_OK)
+			return rc;
+		d_render = reinterpret_cast<float *>(s->d_noise);
+	}
+	rt_render_opts os = *o;
+	os.sample_split = split;
+	rc = rt_render_device(s, camera, &os, d_render, d_rays_shot, stream);
+	if (rc != RT_OK)
+		return rc;
+	rt_robust_buffers kernel_out = *d_out;
+	kernel_out.mean = nullptr; // combine_chunks_kernel has written it
+	DevRobustParams P = robust_params(r, o->width, o->height, split, (uint32_t)(o->samples_per_pixel / split), s->d_partial, d_albedo, &kernel_out);
+	P.tile_w = o->tile_width ? o->tile_width : 8u; // (shard_geometry, rt_api.cpp)
+	P.tile_h = o->tile_height ? o->tile_height : 8u;
+	P.tiles_x = (P.width + P.tile_w - 1u) / P.tile_w;
+	P.n_work = P.tiles_x * ((P.height + P.tile_h - 1u) / P.tile_h) * P.tile_w * P.tile_h;
+	HIP_TRY(launch_robust_chunks(stream, P));
+	return RT_OK;
+}
+
+int rt_render_robust(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_robust_opts *r, const float *albedo,
+                     const rt_robust_buffers *out, uint64_t *rays_shot)
+{
+	if (!s || !camera || !o || !r || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	uint32_t split = 0;
+	uint64_t px = 0;
+	int rc = robust_render_check(s, o, r, &split, &px);
+	if (rc == RT_OK)
+		rc = robust_buffers_check(s, out, albedo, nullptr, 0, px);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	// the render's frame first (where the _device call would put its scratch), then out, the planes asked for and the albedo if given
+	Staging st{s, 3 * px};
+	st.add(out->out, 3 * px);
+	st.add(out->gini, px);
+	st.add(out->trimmed, (px + 3) / 4);
+	st.add(out->dropped, (px + 3) / 4);
+	st.add(albedo, 3 * px);
+	rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, st.total * 4);
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_noise;
+	float *d_mean = reinterpret_cast<float *>(base);
+	st.to_device(st.at(base, 4), albedo, 12 * px);
+	const rt_robust_buffers d_out = {st.at(base, 0), d_mean, st.at(base, 1), st.at<uint8_t>(base, 2), st.at<uint8_t>(base, 3)};
+	if (st.ok())
+		st.rc = rt_render_robust_device(s, camera, o, r, st.at(base, 4), &d_out, reinterpret_cast<uint64_t *>(s->d_rays), s->stream);
+	st.download(out->out, d_out.out, 12 * px);
+	st.download(out->mean, d_mean, 12 * px);
+	st.download(out->gini, d_out.gini, 4 * px);
+	st.download(out->trimmed, d_out.trimmed, px);
+	st.download(out->dropped, d_out.dropped, px);
+	st.download(rays_shot, s->d_rays, sizeof(uint64_t));
+	return st.finish("render_robust");
+}
+
+int rt_robust_combine_device(rt_scene *s, const float *d_sums, uint32_t split, uint64_t chunk_passes, uint32_t width, uint32_t height,
+                             const float *d_albedo, const rt_robust_opts *r, const rt_robust_buffers *d_out, void *hip_stream)
+{
+	uint64_t px = 0;
+	const int rc = robust_combine_check(s, d_sums, split, chunk_passes, width, height, d_albedo, r, d_out, &px);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	HIP_TRY(launch_robust_chunks(static_cast<hipStream_t>(hip_stream),
+	                             robust_params(r, width, height, split, (uint32_t)chunk_passes, d_sums, d_albedo, d_out)));
+	return RT_OK;
+}
+
+int rt_robust_combine(rt_scene *s, const float *sums, uint32_t split, uint64_t chunk_passes, uint32_t width, uint32_t height,
+                      const float *albedo, const rt_robust_opts *r, const rt_robust_buffers *out)
+{
+	uint64_t px = 0;
+	int rc = robust_combine_check(s, sums, split, chunk_passes, width, height, albedo, r, out, &px);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	Staging st{s};
+	st.add(sums, 3 * px * split);
+	st.add(albedo, 3 * px);
+	st.add(out->out, 3 * px);
+	st.add(out->mean, 3 * px);
+	st.add(out->gini, px);
+	st.add(out->trimmed, (px + 3) / 4);
+	st.add(out->dropped, (px + 3) / 4);
+	rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, st.total * 4);
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_noise;
+	st.to_device(st.at(base, 0), sums, 12 * px * split);
+	st.to_device(st.at(base, 1), albedo, 12 * px);
+	const rt_robust_buffers d_out = {st.at(base, 2), st.at(base, 3), st.at(base, 4), st.at<uint8_t>(base, 5), st.at<uint8_t>(base, 6)};
+	if (st.ok())
+		st.rc = rt_robust_combine_device(s, st.at(base, 0), split, chunk_passes, width, height, st.at(base, 1), r, &d_out, s->stream);
+	st.download(out->out, d_out.out, 12 * px);
+	st.download(out->mean, d_out.mean, 12 * px);
+	st.download(out->gini, d_out.gini, 4 * px);
+	st.download(out->trimmed, d_out.trimmed, px);
+	st.download(out->dropped, d_out.dropped, px);
+	return st.finish("robust_combine");
+}
+
+int rt_render_denoised_robust(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_robust_opts *r,
+                              const rt_denoise_opts *dopts, float *out_clean, float *out_robust, uint64_t *rays_shot)
+{
+	if (!s || !camera || !o || !r || !dopts || !out_clean)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	int rc = denoise_opts_check(dopts, o->width, o->height);
+	if (rc != RT_OK)
+		return rc;
+	uint32_t split = 0;
+	uint64_t px = 0;
+	rc = robust_render_check(s, o, r, &split, &px);
+	if (rc != RT_OK)
+		return rc;
+	if (ranges_overlap(out_clean, 12 * px, out_robust, 12 * px))
+		return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_denoised_robust: out_clean overlaps out_robust");
+	rc = need_device(s);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	// in the denoiser's buffer: the ray counter (16 bytes), the workspace, then albedo, normal, depth, the render, robust, clean
+	const size_t ws_floats = kDenoiseWorkspaceBytesPerPixel / 4 * px;
+	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, 16 + 4 * (ws_floats + 16 * px));
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_denoise;
+	float *ws = reinterpret_cast<float *>(base + 16);
+	float *d_albedo = ws + ws_floats, *d_normal = d_albedo + 3 * px, *d_depth = d_normal + 3 * px, *d_mean = d_depth + px,
+	      *d_robust = d_mean + 3 * px, *d_clean = d_robust + 3 * px;
+	Staging st{s};
+	rt_aov_buffers aov;
+	std::memset(&aov, 0, sizeof aov);
+	aov.albedo = d_albedo;
+	aov.normal = d_normal;
+	aov.depth = d_depth;
+	st.rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
+	if (st.ok()) {
+		const rt_robust_buffers d_out = {d_robust, d_mean, nullptr, nullptr, nullptr};
+		st.rc = rt_render_robust_device(s, camera, o, r, d_albedo, &d_out, reinterpret_cast<uint64_t *>(base), s->stream);
+	}
+	if (st.ok()) {
+		rt_denoise_opts d = *dopts;
+		d.width = (uint32_t)o->width;
+		d.height = (uint32_t)o->height;
+		const rt_denoise_inputs in = {d_robust, d_albedo, d_normal, d_depth, nullptr};
+		st.rc = rt_denoise_device(s, &in, &d, ws, d_clean, s->stream);
+	}
+	unsigned long long rays = 0;
+	st.download(out_clean, d_clean, 12 * px);
+	st.download(out_robust, d_robust, 12 * px);
+	st.download(&rays, base, sizeof rays);
+	rc = st.finish("render_denoised_robust");
 	if (rc == RT_OK && rays_shot)
 		*rays_shot = rays;
 	return rc;

@@ -587,6 +587,65 @@ class HipScene:
                                               _p(noisy, C.c_float), _p(variance, C.c_float), C.byref(rays)))
         return clean, noisy, variance, rays.value
 
+    # ---- firefly-robust frames (rt_render_robust, rt_robust_combine, rt_render_denoised_robust) ----
+    def render_robust(self, camera, opts, albedo=None, channels=abi.ROBUST_CHANNELS, **ropts):
+        """rt_render_robust: ONE render at opts.sample_split (2..64 dividing the passes; 0 = automatic) and the rank-trimmed mean
+        of its chunk sums: {"out": (H, W, 3) f32, "mean": (H, W, 3) f32 -- the bytes render() gives at that split --, "gini":
+        (H, W) f32, "trimmed", "dropped": (H, W) uint8, "rays_shot": int}; only `channels` (always "out") are produced.
+        albedo (H, W, 3): rank the demodulated luminances.  Keyword options: mode (abi.RT_ROBUST_* or "trim" / "median" /
+        "gini"), trim, gini_gain.  Semantics: include/rt_hip.h rt_robust_opts."""
+        r = robust_opts(**ropts)
+        h, w = int(opts.height), int(opts.width)
+        out, bufs = _robust_outputs(w, h, channels)
+        albedo = _robust_albedo(albedo, w, h)
+        rays = C.c_uint64()
+        _check(lib().rt_render_robust(self._h, C.byref(camera), C.byref(opts), C.byref(r), _p(albedo, C.c_float) if albedo is not None else None,
+                                      C.byref(bufs), C.byref(rays)))
+        out["rays_shot"] = rays.value
+        return out
+
+    def render_robust_device(self, camera, opts, d_ptrs, d_albedo=None, d_rays_ptr=None, stream=0, **ropts):
+        """rt_render_robust_device: asynchronous, DEVICE buffers of the scene's GPU.  d_ptrs = {channel: device pointer} over
+        abi.ROBUST_CHANNELS ("out" required)."""
+        r = robust_opts(**ropts)
+        _check(lib().rt_render_robust_device(self._h, C.byref(camera), C.byref(opts), C.byref(r), _dp(d_albedo), C.byref(_robust_device_buffers(d_ptrs)),
+                                             C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream)))
+
+    def robust_combine(self, chunk_sums, chunk_passes, albedo=None, channels=abi.ROBUST_CHANNELS, **ropts):
+        """rt_robust_combine: the rank-trimmed mean of the caller's chunk sums (S, H, W, 3) f32, each the sum of chunk_passes
+        passes.  Returns the dict of render_robust without "rays_shot"; "mean" is the plain combine."""
+        sums = np.ascontiguousarray(chunk_sums, dtype=np.float32)
+        if sums.ndim != 4 or sums.shape[3] != 3:
+            raise ValueError(f"chunk_sums must be (S, H, W, 3), got {sums.shape}")
+        split, h, w = sums.shape[:3]
+        r = robust_opts(**ropts)
+        out, bufs = _robust_outputs(w, h, channels)
+        albedo = _robust_albedo(albedo, w, h)
+        _check(lib().rt_robust_combine(self._h, _p(sums, C.c_float), C.c_uint32(split), C.c_uint64(chunk_passes), C.c_uint32(w), C.c_uint32(h),
+                                       _p(albedo, C.c_float) if albedo is not None else None, C.byref(r), C.byref(bufs)))
+        return out
+
+    def robust_combine_device(self, d_chunk_sums, split, chunk_passes, width, height, d_ptrs, d_albedo=None, stream=0, **ropts):
+        """rt_robust_combine_device: asynchronous, DEVICE planes [S][h][w][3]; allocates nothing."""
+        r = robust_opts(**ropts)
+        _check(lib().rt_robust_combine_device(self._h, _dp(d_chunk_sums), C.c_uint32(split), C.c_uint64(chunk_passes), C.c_uint32(width),
+                                              C.c_uint32(height), _dp(d_albedo), C.byref(r), C.byref(_robust_device_buffers(d_ptrs)),
+                                              C.c_void_p(stream)))
+
+    def render_denoised_robust(self, camera, opts, dopts=None, **ropts):
+        """rt_render_denoised_robust: the AOVs, render_robust with their albedo and the filter on the robust frame (no variance
+        plane).  Returns (clean, robust, rays_shot)."""
+        h, w = int(opts.height), int(opts.width)
+        if dopts is None:
+            dopts = denoise_opts(w, h)
+        r = robust_opts(**ropts)
+        clean = np.zeros((h, w, 3), dtype=np.float32)
+        robust = np.zeros((h, w, 3), dtype=np.float32)
+        rays = C.c_uint64()
+        _check(lib().rt_render_denoised_robust(self._h, C.byref(camera), C.byref(opts), C.byref(r), C.byref(dopts), _p(clean, C.c_float),
+                                               _p(robust, C.c_float), C.byref(rays)))
+        return clean, robust, rays.value
+
     # ---- temporal accumulation with camera reprojection (rt_denoise_temporal) ----
     def denoise_temporal(self, color, camera, albedo=None, normal=None, depth=None, motion=False, **opts):
         """rt_denoise_temporal: one frame of a camera path.  color (H, W, 3) f32 -- or the dict render_aov returns with the image
@@ -889,6 +948,54 @@ def noise_opts(**kw):
             raise ValueError(f"unknown noise option {k!r}")
         setattr(o, k, v)
     return o
+
+
+def robust_opts(**kw):
+    """rt_robust_opts_default with mode (abi.RT_ROBUST_* or its name, "trim" / "median" / "gini"), trim and / or gini_gain set."""
+    o = abi.RobustOpts()
+    _check(lib().rt_robust_opts_default(C.byref(o)))
+    for k, v in kw.items():
+        if k not in ("mode", "trim", "gini_gain"):
+            raise ValueError(f"unknown robust option {k!r}")
+        if isinstance(v, str):
+            if v.lower() not in abi.ROBUST_MODES:
+                raise ValueError(f"unknown {k} {v!r}: one of {sorted(abi.ROBUST_MODES)}")
+            v = abi.ROBUST_MODES[v.lower()]
+        setattr(o, k, v)
+    return o
+
+
+def _robust_outputs(w, h, channels):
+    """(arrays by channel, rt_robust_buffers pointing at them) of a w x h frame"""
+    shapes = {"out": ((h, w, 3), np.float32), "mean": ((h, w, 3), np.float32), "gini": ((h, w), np.float32),
+              "trimmed": ((h, w), np.uint8), "dropped": ((h, w), np.uint8)}
+    out, bufs = {}, abi.RobustBuffers()
+    for name in ("out", *channels):
+        if name not in abi.ROBUST_CHANNELS:
+            raise ValueError(f"unknown robust channel {name!r}")
+        if name not in out:
+            shape, dtype = shapes[name]
+            out[name] = np.zeros(shape, dtype=dtype)
+            setattr(bufs, name, _p(out[name], C.c_float if dtype is np.float32 else C.c_uint8))
+    return out, bufs
+
+
+def _robust_albedo(albedo, w, h):
+    if albedo is None:
+        return None
+    albedo = np.ascontiguousarray(albedo, dtype=np.float32)
+    if albedo.shape != (h, w, 3):
+        raise ValueError(f"albedo must be {(h, w, 3)}, got {albedo.shape}")
+    return albedo
+
+
+def _robust_device_buffers(d_ptrs):
+    bufs = abi.RobustBuffers()
+    for name, ptr in d_ptrs.items():
+        if name not in abi.ROBUST_CHANNELS:
+            raise ValueError(f"unknown robust channel {name!r}")
+        setattr(bufs, name, _dp(ptr, C.c_uint8 if name in ("trimmed", "dropped") else C.c_float))
+    return bufs
 
 
 def _noise_outputs(w, h, channels):
