@@ -1066,6 +1066,64 @@ int rt_display(rt_scene *scene, const float *host_rgb, const rt_display_opts *op
                uint32_t *host_histogram);
 int rt_display_reset(rt_scene *scene);
 
+/* ---- Bloom stage (csrc/rt_bloom.hip): glare around over-range pixels, between the float frame and the display stage.  A W x H RGB
+ * f32 frame (FRAME layout: what rt_render, rt_denoise* and rt_upscale* write) to a W x H RGB f32 frame: the input plus `intensity`
+ * times a wide blur of its over-threshold part, so that after rt_display's tone curve an emitter still says how far above white it
+ * was.  The blur is a pyramid of 2:1 reductions and expansions (the dual-filter bloom of real-time renderers); the exact f32
+ * definition below is this library's own.  f32 throughout with the library's arithmetic contract: IEEE `/`, no fma, sums in the
+ * order written; powf is include/rt_detmath.h's rt_powf; lum is the display stage's Y; fminf / fmaxf are C's.
+ * Exposure.  ev = exposure_ev, or state.ev + exposure_ev when a display state is given (rt_display's, read ON THE DEVICE by the
+ *   kernels, never by the host and never written: a captured graph follows the display's adaptation).  s = powf(2.0f, ev).
+ * Bright pass, per source pixel, v each of its channel values:
+ *   a = (v finite and v > 0) ? v : 0;  x = fminf(a*s, FLT_MAX) per channel;  Y = lum(x)
+ *   if Y > clamp_max: x = x*(clamp_max/Y) per channel (the quotient first) and Y = clamp_max
+ *   k = threshold*knee;  q = fminf(fmaxf((Y - threshold) + k, 0.0f), 2.0f*k);  soft = (q*q)/(4.0f*k + 1e-5f)
+ *   wgt = fmaxf(soft, Y - threshold)/fmaxf(Y, 1e-5f);  b = x*wgt per channel
+ *   Every b is finite and >= 0 whatever the input.  With knee = 0 a pixel at or below the threshold contributes exactly 0; with a
+ *   knee a pixel AT the threshold contributes soft = (k*k)/(4.0f*k + 1e-5f), about a quarter of the knee's width.
+ * Reduce R, w x h -> ceil(w/2) x ceil(h/2); separable, horizontal first, source indices clamped to the image:
+ *   T(X, y) = ((I(2X-1, y)*0.125f + I(2X, y)*0.375f) + I(2X+1, y)*0.375f) + I(2X+2, y)*0.125f,  then the same formula down the
+ *   columns of T:  R(X, Y) = ((T(X, 2Y-1)*0.125f + T(X, 2Y)*0.375f) + T(X, 2Y+1)*0.375f) + T(X, 2Y+2)*0.125f
+ * Expand E, a coarse image J of ceil(w/2) x ceil(h/2) -> w x h; separable, horizontal first, coarse indices clamped:
+ *   fine X even: J(X/2 - 1)*0.25f + J(X/2)*0.75f;   fine X odd: J((X-1)/2)*0.75f + J((X+1)/2)*0.25f;   then the same vertically.
+ * Levels.  B_0 = R(bright(frame)), B_{i+1} = R(B_i); n = min(levels, the number of levels up to and including the first of size
+ *   1 x 1).  U_{n-1} = B_{n-1};  U_i = B_i + scatter*E(U_{i+1}) (the product first, then the sum).
+ * Composite, per channel: out = c + (intensity*E(U_0))/s with c the untouched input value: NaN, +-inf and negatives in the frame
+ *   pass through and never spread (they contribute 0 to the pyramid); -0 comes out as +0, as the sum gives it.
+ * Options (64 bytes): width, height >= 1; threshold finite and >= 0 (default 1); knee in [0, 1] (default 0.5); intensity finite
+ *   and >= 0 (default 0.05); scatter in [0, 1] (default 0.7); levels in 1 .. 12 (default 6); exposure_ev finite (default 0);
+ *   clamp_max finite and > 0 (default 65504); fuse_tail 0 or 1 (default 1): 1 lets ONE workgroup make the smallest levels in LDS
+ *   instead of two launches per level -- the same arithmetic per pixel, so the same bytes; `reserved` must be zero.
+ *   THE DEFAULTS ARE STARTING VALUES NOBODY HAS TUNED: no image set has been rendered to choose them. */
+typedef struct rt_bloom_opts {
+	uint32_t width, height;
+	float threshold;    /* default 1 (untuned) */
+	float knee;         /* default 0.5 (untuned) */
+	float intensity;    /* default 0.05 (untuned) */
+	float scatter;      /* default 0.7 (untuned) */
+	uint32_t levels;    /* default 6 (untuned) */
+	float exposure_ev;  /* default 0 */
+	float clamp_max;    /* default 65504 */
+	uint32_t fuse_tail; /* default 1 */
+	uint32_t reserved[6];
+} rt_bloom_opts;
+int rt_bloom_opts_default(rt_bloom_opts *out);
+/* The workspace of rt_bloom_device: the n levels one after the other, each an RGB f32 image rounded up to 16 bytes:
+ *   sum over i < n of 16*ceil(12*w_i*h_i / 16),  w_0 = ceil(W/2), h_0 = ceil(H/2), w_{i+1} = ceil(w_i/2), h_{i+1} = ceil(h_i/2). */
+int rt_bloom_workspace_bytes(const rt_bloom_opts *opts, uint64_t *bytes);
+/* Checks (the device last): RT_ERR_INVALID_ARGUMENT for a NULL scene, input, opts or output, width or height 0, an option out of
+ * its range, a workspace (device call) that is NULL or not 16-byte aligned, and any overlap among input, output, workspace and
+ * state except out == rgb exactly (in place: the composite reads only its own pixel of the frame); RT_ERR_UNSUPPORTED for more
+ * than 2^31 pixels; RT_ERR_NO_DEVICE for a host-only scene.  A multi-device head runs on devices[0].  No side effects: what
+ * rt_last_kernel_ms, rt_last_launch_info and a following rt_render return is unchanged.
+ * rt_bloom_device: DEVICE buffers on the scene's GPU, asynchronous on hip_stream; it allocates nothing and keeps no state, so it
+ *   can be captured into a graph from its first call.  d_state: rt_display_device's state, or NULL.  Any 4-byte alignment of d_rgb
+ *   and d_out is accepted.
+ * rt_bloom: HOST buffers, blocking; the scene owns the device buffers and grows them on first use and for larger frames only. */
+int rt_bloom_device(rt_scene *scene, const float *d_rgb, const rt_bloom_opts *opts, const rt_display_state *d_state, void *d_workspace,
+                    float *d_out, void *hip_stream);
+int rt_bloom(rt_scene *scene, const float *host_rgb, const rt_bloom_opts *opts, const rt_display_state *host_state, float *host_out);
+
 /* ---- AOV-guided upscaling (csrc/rt_upscale.hip): render and filter at a reduced resolution, reconstruct the full-resolution frame
  * from it -- joint bilateral upsampling (Kopf et al., SIGGRAPH 2007) of albedo-demodulated radiance, guided by the first-hit albedo,
  * normal and depth at BOTH sizes (the camera does not depend on the resolution: rt_render_aov at the destination size gives the

@@ -458,6 +458,26 @@ class DisplayState(C.Structure):  # rt_display_state
     ]
 
 
+class BloomOpts(C.Structure):  # rt_bloom_opts
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("threshold", C.c_float),
+        ("knee", C.c_float),
+        ("intensity", C.c_float),
+        ("scatter", C.c_float),
+        ("levels", C.c_uint32),
+        ("exposure_ev", C.c_float),
+        ("clamp_max", C.c_float),
+        ("fuse_tail", C.c_uint32),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+
+BLOOM_OPTIONS = tuple(n for n, _ in BloomOpts._fields_ if n not in ("width", "height", "reserved"))
+BLOOM_MAX_LEVELS = 12
+
+
 class UpscaleOpts(C.Structure):  # rt_upscale_opts
     _fields_ = [
         ("src_width", C.c_uint32),
@@ -519,6 +539,7 @@ EXPECTED_SIZES = {
     "rt_temporal_inputs": (TemporalInputs, 32),
     "rt_display_opts": (DisplayOpts, 104),
     "rt_display_state": (DisplayState, 16),
+    "rt_bloom_opts": (BloomOpts, 64),
     "rt_upscale_opts": (UpscaleOpts, 56),
     "rt_upscale_inputs": (UpscaleInputs, 56),
 }
@@ -609,6 +630,10 @@ EXPORTED_SYMBOLS = [
     "rt_display_device",
     "rt_display",
     "rt_display_reset",
+    "rt_bloom_opts_default",
+    "rt_bloom_workspace_bytes",
+    "rt_bloom_device",
+    "rt_bloom",
     "rt_upscale_opts_default",
     "rt_upscale_device",
     "rt_upscale",

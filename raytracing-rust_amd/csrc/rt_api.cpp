@@ -521,6 +521,8 @@ void rt_scene_destroy(rt_scene *s)
 		(void)hipFree(s->d_display);
 	if (s->d_noise)
 		(void)hipFree(s->d_noise);
+	if (s->d_bloom)
+		(void)hipFree(s->d_bloom);
 	if (s->d_stack_ovf)
 		(void)hipFree(s->d_stack_ovf);
 	for (int b = 0; b < 2; ++b) {

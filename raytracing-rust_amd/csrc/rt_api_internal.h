@@ -105,6 +105,8 @@ struct rt_scene {
 	bool display_has_state = false;        // false: the next rt_display starts from a zero state
 	char *d_noise = nullptr;               // rt_render_noise & co.: the batch state (16 + 20 bytes per pixel), then what the blocking calls stage
 	size_t d_noise_bytes = 0;
+	char *d_bloom = nullptr;               // rt_bloom: state, workspace, input and output, grown for larger frames
+	size_t d_bloom_bytes = 0;
 };
 
 // sample_split = 0 (automatic), resolved (rt_api.cpp); the noise estimates halve it until it divides the passes (rt_api_post.cpp)

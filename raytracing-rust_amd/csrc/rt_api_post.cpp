@@ -1,6 +1,6 @@
 // rt_api_post.cpp -- the host side of the post-processing stages of librt_hip.so (include/rt_hip.h): first-hit and specular-chain
-// AOV buffers, ID mattes, ambient occlusion, the A-Trous denoiser, noise estimates, firefly-robust frames, temporal accumulation, the display stage and AOV-guided upscaling.  Each stage has its kernels in a file of
-// its own (rt_aov.hip, rt_aov_chain.hip, rt_matte.hip, rt_ao.hip, rt_denoise.hip, rt_noise.hip, rt_robust.hip, rt_temporal.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
+// AOV buffers, ID mattes, ambient occlusion, the A-Trous denoiser, noise estimates, firefly-robust frames, temporal accumulation, the bloom and display stages and AOV-guided upscaling.  Each stage has its kernels in a file of
+// its own (rt_aov.hip, rt_aov_chain.hip, rt_matte.hip, rt_ao.hip, rt_denoise.hip, rt_noise.hip, rt_robust.hip, rt_temporal.hip, rt_bloom.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
 // and the blocking wrappers that stage host buffers through scene-owned device memory (Staging, rt_api_internal.h).
 // Every check function ends with the device (need_device), so that a host-only scene reports bad arguments as such.
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@
 #include "rt_render.h"
 #include "rt_robust.h"
 #include "rt_temporal.h"
+#include "rt_bloom.h"
 #include "rt_display.h"
 #include "rt_upscale.h"
 
@@ -1748,6 +1749,141 @@ int rt_display_reset(rt_scene *s)
 		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
 	s->display_has_state = false;
 	return RT_OK;
+}
+
+} // extern "C"
+
+// ---- bloom stage: bright pass, reduce / expand pyramid, composite (rt_bloom.hip) ----
+static int bloom_opts_check(const rt_bloom_opts *o)
+{
+	if (int rc = frame_sides("bloom: ", o->width, o->height, 1); rc != RT_OK)
+		return rc;
+	if (!finite_f(o->threshold) || !(o->threshold >= 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bloom: threshold must be finite and >= 0");
+	if (!(o->knee >= 0.0f && o->knee <= 1.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bloom: knee must be in [0, 1]");
+	if (!finite_f(o->intensity) || !(o->intensity >= 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bloom: intensity must be finite and >= 0");
+	if (!(o->scatter >= 0.0f && o->scatter <= 1.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bloom: scatter must be in [0, 1]");
+	if (o->levels < 1u || o->levels > kBloomMaxLevels)
+		return fail(RT_ERR_INVALID_ARGUMENT, "bloom: levels must be in 1..12");
+	if (!finite_f(o->exposure_ev))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bloom: exposure_ev must be finite");
+	if (!finite_f(o->clamp_max) || !(o->clamp_max > 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bloom: clamp_max must be finite and > 0");
+	if (o->fuse_tail > 1u)
+		return fail(RT_ERR_INVALID_ARGUMENT, "bloom: fuse_tail must be 0 or 1");
+	for (uint32_t r : o->reserved)
+		if (r != 0u)
+			return fail(RT_ERR_INVALID_ARGUMENT, "bloom: reserved must be zero");
+	uint64_t n = 0;
+	return frame_pixels("bloom: ", o->width, o->height, 1, &n);
+}
+
+// argument checks of rt_bloom(_device), the device last; ws is checked for the device call only
+static int bloom_check(const rt_scene *s, const float *rgb, const rt_bloom_opts *o, const void *state, const void *ws, const float *out,
+                       bool device)
+{
+	if (!s || !rgb || !o || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	int rc = bloom_opts_check(o);
+	if (rc != RT_OK)
+		return rc;
+	const uint64_t n = (uint64_t)o->width * o->height;
+	if (device && (!ws || reinterpret_cast<uintptr_t>(ws) % 16u != 0u))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bloom: the workspace must not be NULL and must be 16-byte aligned");
+	// every pair of buffers; out may BE the frame (the composite reads only its own pixel of it), nothing else may be shared
+	const void *buf[4] = {out, device ? ws : nullptr, state, rgb};
+	const uint64_t bytes[4] = {12 * n, bloom_levels(o->width, o->height, o->levels).bytes, sizeof(rt_display_state), 12 * n};
+	for (int a = 0; a < 4; ++a)
+		for (int b = a + 1; b < 4; ++b)
+			if (!(a == 0 && b == 3 && out == rgb) && ranges_overlap(buf[a], bytes[a], buf[b], bytes[b]))
+				return fail(RT_ERR_INVALID_ARGUMENT, "bloom: two buffers overlap (only out == rgb is allowed)");
+	return need_device(s);
+}
+
+extern "C" {
+
+int rt_bloom_opts_default(rt_bloom_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	out->threshold = 1.0f;
+	out->knee = 0.5f;
+	out->intensity = 0.05f;
+	out->scatter = 0.7f;
+	out->levels = 6;
+	out->exposure_ev = 0.0f;
+	out->clamp_max = 65504.0f;
+	out->fuse_tail = 1;
+	return RT_OK;
+}
+
+int rt_bloom_workspace_bytes(const rt_bloom_opts *o, uint64_t *bytes)
+{
+	if (!o || !bytes)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (o->levels < 1u || o->levels > kBloomMaxLevels)
+		return fail(RT_ERR_INVALID_ARGUMENT, "bloom: levels must be in 1..12");
+	uint64_t n = 0;
+	const int rc = frame_pixels("bloom: ", o->width, o->height, 1, &n);
+	if (rc == RT_OK)
+		*bytes = bloom_levels(o->width, o->height, o->levels).bytes;
+	return rc;
+}
+
+int rt_bloom_device(rt_scene *s, const float *d_rgb, const rt_bloom_opts *o, const rt_display_state *d_state, void *d_workspace,
+                    float *d_out, void *hip_stream)
+{
+	int rc = bloom_check(s, d_rgb, o, d_state, d_workspace, d_out, true);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device)); // a multi-device head runs on devices[0]
+	DevBloomParams P;
+	std::memset(&P, 0, sizeof P);
+	P.width = o->width;
+	P.height = o->height;
+	P.threshold = o->threshold;
+	P.knee = o->knee;
+	P.intensity = o->intensity;
+	P.scatter = o->scatter;
+	P.exposure_ev = o->exposure_ev;
+	P.clamp_max = o->clamp_max;
+	P.fuse_tail = o->fuse_tail;
+	P.rgb = d_rgb;
+	P.state = d_state;
+	P.ws = static_cast<char *>(d_workspace);
+	P.out = d_out;
+	HIP_TRY(launch_bloom(static_cast<hipStream_t>(hip_stream), P, bloom_levels(o->width, o->height, o->levels)));
+	return RT_OK;
+}
+
+int rt_bloom(rt_scene *s, const float *host_rgb, const rt_bloom_opts *o, const rt_display_state *host_state, float *host_out)
+{
+	int rc = bloom_check(s, host_rgb, o, host_state, nullptr, host_out, false);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	const uint64_t n = (uint64_t)o->width * o->height;
+	// state (16), workspace (a multiple of 16), output, input: every part 16-byte aligned
+	auto up16 = [](uint64_t b) { return (b + 15u) / 16u * 16u; };
+	const uint64_t off_ws = 16, off_out = off_ws + bloom_levels(o->width, o->height, o->levels).bytes, off_in = off_out + up16(12 * n);
+	rc = grow_device_buffer(s->d_bloom, s->d_bloom_bytes, (size_t)(off_in + 12 * n));
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_bloom;
+	Staging st{s};
+	st.to_device(base, host_state, sizeof(rt_display_state));
+	st.to_device(base + off_in, host_rgb, 12 * n);
+	if (!st.ok())
+		return st.finish("bloom upload");
+	st.rc = rt_bloom_device(s, reinterpret_cast<const float *>(base + off_in), o,
+	                        host_state ? reinterpret_cast<const rt_display_state *>(base) : nullptr, base + off_ws,
+	                        reinterpret_cast<float *>(base + off_out), s->stream);
+	st.download(host_out, base + off_out, 12 * n);
+	return st.finish("bloom");
 }
 
 } // extern "C"

@@ -732,6 +732,28 @@ class HipScene:
                                        vp(d_workspace), vp(d_out), C.cast(vp(d_histogram), C.POINTER(C.c_uint32)),
                                        C.c_void_p(stream)))
 
+    # ---- bloom stage: glare around over-range pixels, ahead of the display stage (rt_bloom) ----
+    def bloom(self, image, state=None, **opts):
+        """rt_bloom: an (H, W, 3) f32 frame to an (H, W, 3) f32 frame, the input plus `intensity` times a wide blur of its
+        over-threshold part.  state: an abi.DisplayState (display_state()) whose ev is added to exposure_ev, or None.  Keyword
+        options: bloom_opts'.  Semantics: include/rt_hip.h rt_bloom_opts."""
+        a = np.ascontiguousarray(image, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"image must be (H, W, 3), got {a.shape}")
+        h, w = a.shape[:2]
+        o = bloom_opts(w, h, **opts)
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        _check(lib().rt_bloom(self._h, _p(a, C.c_float), C.byref(o), C.byref(state) if state is not None else None,
+                              _p(out, C.c_float)))
+        return out
+
+    def bloom_device(self, d_rgb, opts, d_state, d_workspace, d_out, stream=0):
+        """rt_bloom_device: asynchronous, DEVICE buffers of the scene's GPU, no state.  d_rgb, d_out: W*H*3 f32 (d_out may be
+        d_rgb); d_state: an rt_display_state read on the device, or 0; d_workspace: bloom_workspace_bytes(opts) bytes, 16-byte
+        aligned; opts: abi.BloomOpts."""
+        _check(lib().rt_bloom_device(self._h, _dp(d_rgb), C.byref(opts), C.c_void_p(int(d_state) or None),
+                                     C.c_void_p(int(d_workspace) or None), _dp(d_out), C.c_void_p(stream)))
+
     # ---- AOV-guided upscaling (rt_upscale): a source-size frame to the destination size ----
     def upscale(self, color, src=None, dst=None, stage=False, **opts):
         """rt_upscale: an (h, w, 3) f32 frame to (H, W, 3), guided by the albedo / normal (.., 3) and depth of `src` (at h x w) and
@@ -1084,6 +1106,25 @@ def display_output_bytes(opts):
     """rt_display_output_bytes: W*H*4 (RGBA8, BGRA8) or W*H*3 (RGB8)."""
     n = C.c_uint64()
     _check(lib().rt_display_output_bytes(C.byref(opts), C.byref(n)))
+    return n.value
+
+
+def bloom_opts(width, height, **kw):
+    """rt_bloom_opts_default with the frame size and any of abi.BLOOM_OPTIONS set."""
+    o = abi.BloomOpts()
+    _check(lib().rt_bloom_opts_default(C.byref(o)))
+    o.width, o.height = int(width), int(height)
+    for k, v in kw.items():
+        if k not in abi.BLOOM_OPTIONS:
+            raise ValueError(f"unknown bloom option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def bloom_workspace_bytes(opts):
+    """rt_bloom_workspace_bytes: the workspace rt_bloom_device needs for opts' frame size and levels."""
+    n = C.c_uint64()
+    _check(lib().rt_bloom_workspace_bytes(C.byref(opts), C.byref(n)))
     return n.value
 
 
