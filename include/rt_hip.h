@@ -1217,6 +1217,14 @@ int rt_selftest_division(float divisor, float *reciprocal, int *exact);
 #define RT_SELFTEST_LEAN_CLASSES 9
 int rt_selftest_lean(int device, uint64_t n_per_thread, uint64_t seed, uint64_t mismatches[RT_SELFTEST_LEAN_CLASSES]);
 
+/* ---- self-test of the two-sphere kernels' primary walk.  A render of a scene those kernels take (one inner node over two
+ * single-sphere leaves: scenes/rtweekend1.ssml) hands them the terms of the box and sphere tests that depend on the camera's origin
+ * and the scene alone -- 28 values, csrc/rt_types.h DevPairPrimary -- computed once on the host.  This call forms them for `origin`
+ * as a render would, forms them again ON the scene's device with the plain operators and counts the words that differ (NaN ==
+ * NaN; the validity flag included): *mismatches must be zero.  *valid = 0: the origin or a term is not finite and a render would not use
+ * the block.  RT_ERR_UNSUPPORTED for any other kind of scene, RT_ERR_NO_DEVICE on a host-only scene.  Blocking. ---- */
+int rt_selftest_pair_primary(rt_scene *scene, const float origin[3], uint32_t *valid, uint64_t *mismatches);
+
 /* ---- self-test of the kernels' sky sampling: sky_sample and sky_pdf of csrc/rt_shade.h as the render kernels inline them, run
  * directly on the scene's device.  Blocking; host buffers.  Sample i < n seeds its stream as pixel 0, sample i of `seed`, draws a
  * direction (out_dirs: 3 * n) and evaluates the pdf there (out_pdf_of_sample: n); out_pdf[j] is the pdf at dirs[3 j .. 3 j + 2],

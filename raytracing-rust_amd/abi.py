@@ -586,6 +586,7 @@ EXPORTED_SYMBOLS = [
     "rt_check_hit",
     "rt_check_hit_index",
     "rt_selftest_lean",
+    "rt_selftest_pair_primary",
     "rt_selftest_sky",
     "rt_render_aov",
     "rt_render_aov_device",

@@ -1452,10 +1452,15 @@ int rt_render_device(rt_scene *s, const rt_camera *camera, const rt_render_opts 
 	std::memcpy(cam.lower_left, camera->lower_left, 12);
 	std::memcpy(cam.horizontal, camera->horizontal, 12);
 	std::memcpy(cam.vertical, camera->vertical, 12);
+	// FeatPair: the origin-only terms of the primary walks (rt_types.h DevPairPrimary).  The camera belongs to the render, not to
+	// the scene, so they are formed here, per launch: some forty operations
+	DevPairPrimary primary{};
+	if (plan.feature_set == 3)
+		pair_primary_terms(s->pair, plan.dev.root_min, plan.dev.root_max, v3(cam.origin[0], cam.origin[1], cam.origin[2]), primary);
 	HIP_TRY(hipEventRecord(s->ev_start, stream));
 	HIP_TRY(launch_render(o->render_method, plan.prune, plan.fine, plan.sky_lds, plan.feature_set, plan.n_blocks, plan.lds_bytes, stream, plan.dev, cam, P,
 	                      render_target, reinterpret_cast<unsigned long long *>(d_rays_shot), s->d_work_counter, s->d_stack_ovf, plan.xchg,
-	                      plan.feature_set == 3 ? &s->pair : nullptr, plan.block_threads));
+	                      plan.feature_set == 3 ? &s->pair : nullptr, plan.feature_set == 3 ? &primary : nullptr, plan.block_threads));
 	HIP_TRY(hipEventRecord(s->ev_stop, stream));
 	if (plan.split > 1u)
 		HIP_TRY(launch_combine(stream, P, s->d_partial, d_out_rgb));
@@ -2045,6 +2050,30 @@ int rt_selftest_lean(int device, uint64_t n_per_thread, uint64_t seed, uint64_t 
 	(void)hipFree(d);
 	if (e != hipSuccess)
 		return hip_fail(e, "selftest");
+	return RT_OK;
+}
+
+int rt_selftest_pair_primary(rt_scene *s, const float origin[3], uint32_t *valid, uint64_t *mismatches)
+{
+	if (!s || !origin || !valid || !mismatches)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (int rc = need_device(s); rc != RT_OK)
+		return rc;
+	if (!s->pair_tree)
+		return fail(RT_ERR_UNSUPPORTED, "not a scene the two-sphere kernels take");
+	HIP_TRY(hipSetDevice(s->device));
+	DevPairPrimary host{};
+	pair_primary_terms(s->pair, s->dev.root_min, s->dev.root_max, v3(origin[0], origin[1], origin[2]), host);
+	unsigned long long *d = nullptr, bad = 0;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof *d));
+	hipError_t e = launch_selftest_pair_primary(nullptr, s->pair, s->dev.root_min, s->dev.root_max, origin, host, d);
+	if (e == hipSuccess)
+		e = hipMemcpy(&bad, d, sizeof bad, hipMemcpyDeviceToHost);
+	(void)hipFree(d);
+	if (e != hipSuccess)
+		return hip_fail(e, "selftest_pair_primary");
+	*valid = host.valid;
+	*mismatches = bad;
 	return RT_OK;
 }
 

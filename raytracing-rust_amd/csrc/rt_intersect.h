@@ -79,25 +79,28 @@ __device__ __forceinline__ bool ray_swaps_xz(const Ray &r) // Axis::get_max_abs_
 
 // AABB::does_int  aabb.rs:22-57.  Returns the reference's predicate; tmin_out is the entry
 // distance (used only for ordering / pruning).
-__device__ __forceinline__ bool aabb_does_int(const float bmin[3], const float bmax[3], const Ray &r, float &tmin_out)
+// ... with the differences bound - origin as the caller supplies them -- delta(axis, false) the lower bound's, delta(axis, true)
+// the upper's, each asked for once, where the slab needs it: formed from the ray's origin (aabb_does_int), or taken ready-made
+// where the origin is a launch constant (aabb_does_int_from)
+template <class D> __device__ __forceinline__ bool aabb_slabs(const D &delta, const V3 &inv, float &tmin_out)
 {
 	constexpr float widen = 1.0f + 2.0f * gamma_n(3);
-	float t1 = (bmin[0] - r.o.x) * r.inv.x;
-	float t2 = (bmax[0] - r.o.x) * r.inv.x;
+	float t1 = delta(0, false) * inv.x;
+	float t2 = delta(0, true) * inv.x;
 	if (t1 > t2) { const float s = t1; t1 = t2; t2 = s; }
 	t2 *= widen;
 	float tmin = fmin_(t1, t2);
 	float tmax = fmax_(t1, t2);
 
-	t1 = (bmin[1] - r.o.y) * r.inv.y;
-	t2 = (bmax[1] - r.o.y) * r.inv.y;
+	t1 = delta(1, false) * inv.y;
+	t2 = delta(1, true) * inv.y;
 	if (t1 > t2) { const float s = t1; t1 = t2; t2 = s; }
 	t2 *= widen;
 	tmin = fmax_(tmin, fmin_(t1, t2));
 	tmax = fmin_(tmax, fmax_(t1, t2));
 
-	t1 = (bmin[2] - r.o.z) * r.inv.z;
-	t2 = (bmax[2] - r.o.z) * r.inv.z;
+	t1 = delta(2, false) * inv.z;
+	t2 = delta(2, true) * inv.z;
 	if (t1 > t2) { const float s = t1; t1 = t2; t2 = s; }
 	t2 *= widen;
 	tmin = fmax_(tmin, fmin_(t1, t2));
@@ -105,6 +108,15 @@ __device__ __forceinline__ bool aabb_does_int(const float bmin[3], const float b
 
 	tmin_out = tmin;
 	return tmax > fmax_(tmin, 0.0f);
+}
+__device__ __forceinline__ bool aabb_does_int(const float bmin[3], const float bmax[3], const Ray &r, float &tmin_out)
+{
+	const float o[3] = {r.o.x, r.o.y, r.o.z};
+	return aabb_slabs([&](int axis, bool upper) { return (upper ? bmax[axis] : bmin[axis]) - o[axis]; }, r.inv, tmin_out);
+}
+__device__ __forceinline__ bool aabb_does_int_from(const float dmin[3], const float dmax[3], const V3 &inv, float &tmin_out)
+{
+	return aabb_slabs([&](int axis, bool upper) { return upper ? dmax[axis] : dmin[axis]; }, inv, tmin_out);
 }
 
 // sqrtf; the short form of rt_lean.h where the argument is in its range (>= 2^-96; zero, negatives and NaN too), the plain
@@ -119,11 +131,11 @@ __device__ __forceinline__ float sqrt_from_(float x)
 }
 
 // Sphere::get_int up to the choice of t  sphere.rs:34-77
-__device__ __forceinline__ bool sphere_t(V3 center, float radius, const Ray &r, float &t)
+// ... with deltap = centre - origin and ddp = dot(r.d, deltap) given and c() = dot(deltap, deltap) - radius * radius asked for where
+// the quotient needs it: formed from the ray's origin (sphere_t), or taken ready-made where the origin is a launch constant
+// (sphere_t_from)
+template <class C> __device__ __forceinline__ bool sphere_t_tail(V3 deltap, float ddp, const C &c, float radius, const Ray &r, float &t)
 {
-	const V3 deltap = center - r.o;
-	const float ddp = dot(r.d, deltap);
-	const float deltapdot = dot(deltap, deltap);
 	const V3 remedy_term = deltap - ddp * r.d;
 	const float discriminant = radius * radius - dot(remedy_term, remedy_term);
 	if (!(discriminant > 0.0f))
@@ -131,7 +143,7 @@ __device__ __forceinline__ bool sphere_t(V3 center, float radius, const Ray &r, 
 	const float sqrt_val = sqrtf(discriminant); // (the tested short form, sqrt_from_, measured no gain here: its branch costs what it saves)
 	const float q = ddp > 0.0f ? ddp + sqrt_val : ddp - sqrt_val;
 	float t0 = q;
-	float t1 = (deltapdot - radius * radius) / q;
+	float t1 = c() / q;
 	if (t1 < t0) { const float s = t0; t0 = t1; t1 = s; }
 	if (t0 > 0.0f) {
 		t = t0;
@@ -141,6 +153,17 @@ __device__ __forceinline__ bool sphere_t(V3 center, float radius, const Ray &r, 
 		return false;
 	t = t1;
 	return true;
+}
+__device__ __forceinline__ bool sphere_t(V3 center, float radius, const Ray &r, float &t)
+{
+	const V3 deltap = center - r.o;
+	const float ddp = dot(r.d, deltap);
+	const float deltapdot = dot(deltap, deltap);
+	return sphere_t_tail(deltap, ddp, [&]() { return deltapdot - radius * radius; }, radius, r, t);
+}
+__device__ __forceinline__ bool sphere_t_from(V3 deltap, float c, float radius, const Ray &r, float &t)
+{
+	return sphere_t_tail(deltap, dot(r.d, deltap), [&]() { return c; }, radius, r, t);
 }
 
 // triangle_intersection up to the barycentrics and t  triangle.rs:105-177
@@ -804,6 +827,27 @@ __device__ __forceinline__ PairBoxes pair_boxes(const DevPairScene &ps)
 		b.c1min[k] = ps.c1min[k]; b.c1max[k] = ps.c1max[k];
 	}
 	return b;
+}
+
+// FeatPair, a ray from the camera's origin: trace_closest's pair arm with the origin-only terms of both box tests and both
+// sphere tests taken from the host's block (rt_types.h DevPairPrimary) instead of formed from r.o
+__device__ __forceinline__ void trace_closest_pair_primary(const Ray &r, float &best_t, uint32_t &best_prim, const DevPairScene &ps, const DevPairPrimary &pp)
+{
+	best_t = 0.0f;
+	best_prim = kNoPrim;
+	float t0, t1, t;
+	const bool h0 = aabb_does_int_from(pp.box[0][0], pp.box[0][1], r.inv, t0);
+	const bool h1 = aabb_does_int_from(pp.box[1][0], pp.box[1][1], r.inv, t1);
+	if (h0 && sphere_t_from(v3(pp.sphere[0][0], pp.sphere[0][1], pp.sphere[0][2]), pp.sphere[0][3], ps.sphere[0][3], r, t) && t > 0.0f) {
+		best_t = t;
+		best_prim = ps.slot0;
+	}
+	if (h1 && sphere_t_from(v3(pp.sphere[1][0], pp.sphere[1][1], pp.sphere[1][2]), pp.sphere[1][3], ps.sphere[1][3], r, t) && t > 0.0f) {
+		if (best_prim == kNoPrim || t < best_t || (t == best_t && ps.rank1 < ps.rank0)) {
+			best_t = t;
+			best_prim = ps.slot1;
+		}
+	}
 }
 
 template <class F, bool PRUNE, bool OVF = false>

@@ -252,6 +252,7 @@ struct RenderArgs {
 	uint32_t *work_counter;
 	uint32_t *stack_ovf;
 	DevPairScene pair; // FeatPair only (rt_types.h): the whole scene, read where it is used
+	DevPairPrimary primary; // FeatPair only: the origin-only terms of this render's primary walks
 };
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const __attribute__((address_space(4))) RenderArgs *KArgs; // the kernarg segment is constant memory: s_load
@@ -282,13 +283,25 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 	// FeatPair: the scene in scalar registers for the length of a super-phase -- read from the kernel arguments in ONE round of
 	// scalar loads at its top (rt_types.h DevPairScene), by the walks, make_hit and the material evaluations after that
 	DevPairScene PS = {};
-	auto load_pair_scene = [&]() {
+	auto load_pair_boxes = [&]() {
 		if constexpr (F::pair) {
 			const KArgs k = kargs();
 #pragma unroll
 			for (int i = 0; i < 3; ++i) {
 				PS.c0min[i] = k->pair.c0min[i]; PS.c0max[i] = k->pair.c0max[i];
 				PS.c1min[i] = k->pair.c1min[i]; PS.c1max[i] = k->pair.c1max[i];
+			}
+		}
+	};
+	// (BOXES = false: the PRIMARY super-phase, whose walk takes the boxes' differences from DevPairPrimary instead -- twelve scalar
+	// registers it does not hold through the phase)
+	auto load_pair_scene = [&](auto with_boxes) {
+		if constexpr (F::pair) {
+			if constexpr (decltype(with_boxes)::value)
+				load_pair_boxes();
+			const KArgs k = kargs();
+#pragma unroll
+			for (int i = 0; i < 3; ++i) {
 				PS.sky_c1[i] = k->pair.sky_c1[i]; PS.sky_c2[i] = k->pair.sky_c2[i];
 			}
 			PS.slot0 = k->pair.slot0; PS.slot1 = k->pair.slot1; PS.rank0 = k->pair.rank0; PS.rank1 = k->pair.rank1;
@@ -300,6 +313,25 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 			PS.inv_radius[0] = k->pair.inv_radius[0]; PS.inv_radius[1] = k->pair.inv_radius[1];
 			PS.sky_param = k->pair.sky_param;
 			PS.sky_tex_type = k->pair.sky_tex_type;
+		}
+	};
+	// ... and, for the PRIMARY super-phase, the origin-only terms of its walk (rt_types.h DevPairPrimary; the root's, which no pair
+	// walk tests, are not read).  A round of its own AFTER do_gen, whose camera and seed have left the scalar registers by then: in
+	// one round with the scene, two more loop-invariant 64-bit scalars moved into VGPR lanes (six spilled SGPRs instead of four)
+	DevPairPrimary PP = {};
+	auto load_pair_primary = [&]() {
+		if constexpr (F::pair) {
+			const KArgs k = kargs();
+#pragma unroll
+			for (int i = 0; i < 3; ++i) {
+				PP.box[0][0][i] = k->primary.box[0][0][i]; PP.box[0][1][i] = k->primary.box[0][1][i];
+				PP.box[1][0][i] = k->primary.box[1][0][i]; PP.box[1][1][i] = k->primary.box[1][1][i];
+			}
+#pragma unroll
+			for (int i = 0; i < 4; ++i) {
+				PP.sphere[0][i] = k->primary.sphere[0][i]; PP.sphere[1][i] = k->primary.sphere[1][i];
+			}
+			PP.valid = k->primary.valid;
 		}
 	};
 	// (Passing the node / primitive / rank arrays of the two-leaf walk as separate `const __restrict__` kernel arguments turns
@@ -881,6 +913,21 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 			trace_closest<F, PRUNE>(S, S_global, SM, ray, stk, best_t, best_prim, PS);
 			ph = PH_SHADE;
 		}
+	};
+	// ... of a ray do_gen has just made (FeatPair: from the host's block when it is valid -- a wave-uniform test -- and by the
+	// walk above, with the boxes it needs, when not)
+	auto walk_closest_primary = [&]() {
+		if constexpr (F::pair) {
+			if (PP.valid != 0u) {
+				if (ph == PH_NODE && !any_hit) {
+					trace_closest_pair_primary(ray, best_t, best_prim, PS, PP);
+					ph = PH_SHADE;
+				}
+				return;
+			}
+			load_pair_boxes();
+		}
+		walk_closest_pending();
 	};
 	auto walk_shadow_pending = [&](const LightCtx &L, const Ray &sr) {
 		if (ph == PH_NODE && any_hit) {
@@ -1542,10 +1589,11 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 				if (!run_light) {
 					if (kFuseRegions) {
 						if (ph == PH_GEN) {
-							load_pair_scene();
+							load_pair_scene(std::false_type{});
 							do_gen();
+							load_pair_primary();
 							RT_SECTION(1);
-							walk_closest_pending();
+							walk_closest_primary();
 							RT_SECTION(2);
 							do_shade(std::integral_constant<int, 1>{});
 						}
@@ -1562,7 +1610,7 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 						}
 	#endif
 					} else {
-						load_pair_scene();
+						load_pair_scene(std::true_type{});
 						if (ph == PH_GEN)
 							do_gen();
 						RT_SECTION(1);
@@ -1584,7 +1632,7 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 					sray.o = sray.d = sray.inv = sray.shear = v3s(0.0f);
 					if (kFuseRegions) {
 						if (ph == PH_LIGHT) {
-							load_pair_scene();
+							load_pair_scene(std::true_type{});
 							do_light(L, sray);
 							RT_SECTION(4);
 							walk_shadow_pending(L, sray);
@@ -1599,7 +1647,7 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 						}
 						RT_SECTION(8);
 					} else {
-						load_pair_scene();
+						load_pair_scene(std::true_type{});
 						if (ph == PH_LIGHT)
 							do_light(L, sray);
 						RT_SECTION(4);
@@ -2176,6 +2224,47 @@ uint32_t render_max_block_threads(int feature_set, bool fine, bool xchg)
 }
 
 // waves per SIMD the kernel's register budget is declared for (its __launch_bounds__)
+// ---- rt_selftest_pair_primary: the host's DevPairPrimary against the same terms formed on the device (one lane), word by word ----
+struct PairPrimaryCheck {
+	DevPairScene pair;
+	DevPairPrimary host;
+	float root_min[3], root_max[3], origin[3];
+};
+__global__ __launch_bounds__(64) void selftest_pair_primary_kernel(const PairPrimaryCheck c, unsigned long long *__restrict__ mismatches)
+{
+	if (threadIdx.x != 0u || blockIdx.x != 0u)
+		return;
+	DevPairPrimary d;
+	pair_primary_terms(c.pair, c.root_min, c.root_max, v3(c.origin[0], c.origin[1], c.origin[2]), d);
+	auto differ = [](float a, float b) { return __float_as_uint(a) != __float_as_uint(b) && !(a != a && b != b); }; // (NaN == NaN)
+	unsigned long long bad = d.valid != c.host.valid ? 1ull : 0ull;
+	for (int ch = 0; ch < 2; ++ch) {
+		for (int k = 0; k < 3; ++k) {
+			bad += differ(d.box[ch][0][k], c.host.box[ch][0][k]);
+			bad += differ(d.box[ch][1][k], c.host.box[ch][1][k]);
+			bad += differ(d.root[ch][k], c.host.root[ch][k]);
+		}
+		for (int k = 0; k < 4; ++k)
+			bad += differ(d.sphere[ch][k], c.host.sphere[ch][k]);
+		bad += differ(d.deltapdot[ch], c.host.deltapdot[ch]);
+	}
+	*mismatches = bad;
+}
+hipError_t launch_selftest_pair_primary(hipStream_t stream, const DevPairScene &pair, const float root_min[3], const float root_max[3], const float origin[3],
+                                        const DevPairPrimary &host_block, unsigned long long *mismatches)
+{
+	PairPrimaryCheck c;
+	c.pair = pair;
+	c.host = host_block;
+	for (int k = 0; k < 3; ++k) {
+		c.root_min[k] = root_min[k];
+		c.root_max[k] = root_max[k];
+		c.origin[k] = origin[k];
+	}
+	hipLaunchKernelGGL(selftest_pair_primary_kernel, dim3(1), dim3(64), 0, stream, c, mismatches);
+	return hipGetLastError();
+}
+
 uint32_t render_waves_per_simd(int feature_set, bool fine)
 {
 	if (feature_set == 3)
@@ -2291,7 +2380,7 @@ hipError_t render_occupancy(int method, bool prune, bool fine, bool sky_lds, int
 hipError_t launch_render(int method, bool prune, bool fine, bool sky_lds, int feature_set, uint32_t n_blocks, size_t lds_bytes, hipStream_t stream,
                          const DevScene &S, const DevCamera &cam, const DevRenderParams &P, float *out,
                          unsigned long long *rays_shot, uint32_t *work_counter, uint32_t *stack_ovf, bool xchg, const DevPairScene *pair,
-                         uint32_t block_threads)
+                         const DevPairPrimary *primary, uint32_t block_threads)
 {
 	render_fn fn = pick_render(method, prune, fine, sky_lds, feature_set, xchg);
 	if (!fn)
@@ -2305,6 +2394,7 @@ hipError_t launch_render(int method, bool prune, bool fine, bool sky_lds, int fe
 	A.work_counter = work_counter;
 	A.stack_ovf = stack_ovf;
 	A.pair = pair ? *pair : DevPairScene{};
+	A.primary = primary ? *primary : DevPairPrimary{};
 	hipLaunchKernelGGL(fn, dim3(n_blocks), dim3(block_threads ? block_threads : render_block_threads(feature_set, fine, xchg)), lds_bytes, stream, A);
 	return hipGetLastError();
 }

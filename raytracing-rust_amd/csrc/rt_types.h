@@ -234,6 +234,52 @@ static_assert(sizeof(DevPairScene) == 192, "DevPairScene: three 64-byte lines");
 // (what the kernels of every other feature set pass where a pair scene is expected: never read)
 __device__ static const DevPairScene kNoPairScene = {};
 
+// FeatPair, primary rays: SimpleCamera::get_ray has no lens, so every primary ray of a render starts at the camera's origin o
+// and the terms of the slab test and of Sphere::get_int that depend on o and the scene alone are the same in every lane of
+// every wave.  The host forms them once per render (rt_api.cpp fill_pair_primary: the operators and the operation order
+// of rt_intersect.h, no contraction, so the bits are the device's -- rt_selftest_pair_primary compares them on the device)
+// and the primary walk reads them from SGPRs next to DevPairScene.  `valid` is clear when o or any of the values is not
+// finite (a NaN's sign and payload are not the same on both sides): the walk then computes them itself, as every other
+// walk does.  The kernels read box, sphere and valid.  deltapdot is the intermediate of sphere[.][3]; root is the scene's own box,
+// which a pair tree's walk never tests (its root is an inner node): both are there so that the block holds every origin-only
+// term of the reference's walk and the device check covers each step of the host's arithmetic.
+struct alignas(64) DevPairPrimary {
+	float box[2][2][3];   // [child][min, max]: bound - o
+	float sphere[2][4];   // [child]: deltap = centre - o, then dot(deltap, deltap) - radius * radius
+	uint32_t valid;
+	// (21 dwords up to here: what the kernels load)
+	float deltapdot[2];   // [child]: dot(deltap, deltap)
+	float root[2][3];     // [min, max]: DevScene::root_min / root_max - o
+	uint32_t pad[3];
+};
+static_assert(sizeof(DevPairPrimary) == 128, "DevPairPrimary: two 64-byte lines");
+constexpr int kPairPrimaryValues = 28; // 12 + 10 + 6
+// The block for origin o: the one spelling of its arithmetic, run by the host for a render and by the device for the check.
+// The operators and the operation order of aabb_does_int, sphere_t and dot().
+RT_FN void pair_primary_terms(const DevPairScene &q, const float root_min[3], const float root_max[3], V3 o, DevPairPrimary &pp)
+{
+	const float oc[3] = {o.x, o.y, o.z};
+	bool finite = finite_f(o.x) && finite_f(o.y) && finite_f(o.z);
+	for (int k = 0; k < 3; ++k) {
+		pp.box[0][0][k] = q.c0min[k] - oc[k]; pp.box[0][1][k] = q.c0max[k] - oc[k];
+		pp.box[1][0][k] = q.c1min[k] - oc[k]; pp.box[1][1][k] = q.c1max[k] - oc[k];
+		pp.root[0][k] = root_min[k] - oc[k]; pp.root[1][k] = root_max[k] - oc[k];
+		finite = finite && finite_f(pp.box[0][0][k]) && finite_f(pp.box[0][1][k]) && finite_f(pp.box[1][0][k]) && finite_f(pp.box[1][1][k]) &&
+		         finite_f(pp.root[0][k]) && finite_f(pp.root[1][k]);
+	}
+	for (int s = 0; s < 2; ++s) {
+		const float radius = q.sphere[s][3];
+		const V3 deltap = v3(q.sphere[s][0], q.sphere[s][1], q.sphere[s][2]) - o;
+		const float deltapdot = dot(deltap, deltap);
+		pp.sphere[s][0] = deltap.x; pp.sphere[s][1] = deltap.y; pp.sphere[s][2] = deltap.z;
+		pp.deltapdot[s] = deltapdot;
+		pp.sphere[s][3] = deltapdot - radius * radius;
+		finite = finite && finite_f(deltap.x) && finite_f(deltap.y) && finite_f(deltap.z) && finite_f(deltapdot) && finite_f(pp.sphere[s][3]);
+	}
+	pp.valid = finite ? 1u : 0u;
+	pp.pad[0] = pp.pad[1] = pp.pad[2] = 0u;
+}
+
 struct DevCamera {
 	float origin[3], lower_left[3], horizontal[3], vertical[3];
 };

@@ -106,6 +106,14 @@ def selftest_lean(device=0, n_per_thread=64, seed=1):
     return [int(x) for x in out]
 
 
+def selftest_pair_primary(scene, origin):
+    """rt_selftest_pair_primary: (valid, mismatches) -- whether a render from `origin` would use the host's block of
+    origin-only terms (csrc/rt_types.h DevPairPrimary), and how many of its words differ from the device's own arithmetic."""
+    valid, bad = C.c_uint32(), C.c_uint64()
+    _check(lib().rt_selftest_pair_primary(scene._h, _f3(origin), C.byref(valid), C.byref(bad)))
+    return bool(valid.value), int(bad.value)
+
+
 def camera_new(origin, lookat, vup, fov, aspect_ratio, aperture, focus_dist):
     """SimpleCamera::new (camera.rs:20-54)."""
     cam = abi.Camera()
