@@ -197,7 +197,8 @@ typedef struct rt_render_opts {
 	 * render cannot use more lanes than it has pixels (8 GPUs at 1080p have one pixel per lane), and even one GPU ends a 1080p
 	 * frame with most of its lanes idle while the last whole pixels finish (7 - 29 % of the launch on the BASELINE workloads).
 	 * (Rounds 1 - 3 folded each chunk as a running mean and combined sum_c mean_c * n_c: three IEEE divisions per sample that the
-	 * chunked form has no use for -- the reference's own fold is the S = 1 case, which is unchanged.) */
+	 * chunked form has no use for -- the reference's own fold is the S = 1 case, which is unchanged.)  Which lane folds a chunk, and
+	 * when, is not part of this definition: RT_TUNE_WHOLE_PIXEL_SHARE lets one lane fold all S chunks of a pixel, same S sums. */
 	uint32_t sample_split;
 	uint32_t reserved0;
 } rt_render_opts;
@@ -373,10 +374,23 @@ int rt_scene_set_traversal(rt_scene *scene, int mode);
  *                         stream) through pools in LDS -- under the coarse schedule with MIS and exhaustive traversal so
  *                         that each super-phase runs on full waves, under the fine schedule so that one wave of a
  *                         512-thread workgroup shades what the other seven walk.  Same pixels either way (measured
- *                         slower on every workload so far); other kernels ignore it */
+ *                         slower on every workload so far); other kernels ignore it
+ *   RT_TUNE_WHOLE_PIXEL_SHARE  0..16: sixteenths of a shard's tiles that the coarse kernels hand out as whole pixels -- a lane
+ *                         folds all sample_split chunks of its pixel, one after the other, into the same chunk sums -- before
+ *                         the remaining tiles go out chunk by chunk; -1 (default): the library decides by the tiles the
+ *                         launch has per wave resident on the device (none below 2.5: sharded and small frames keep
+ *                         every tile in chunk items; at most half the tiles, at most 3 whole tiles per resident wave).  Applies to the kernels of rt_launch_info.feature_set = 3
+ *                         on 64-pixel tiles of power-of-two width with a power-of-two sample_split in 2..64 (other launches
+ *                         ignore it: rt_launch_info.whole_claims = 0); 0 hands every tile out chunk by chunk */
 typedef enum rt_tuning_key { RT_TUNE_TRAVERSAL = 0, RT_TUNE_FEATURE_SET = 1, RT_TUNE_SCENE_IN_LDS = 2, RT_TUNE_SCHEDULE = 3, RT_TUNE_WALK = 4,
-                             RT_TUNE_STACK_CAP = 5, RT_TUNE_EXCHANGE = 6 } rt_tuning_key;
+                             RT_TUNE_STACK_CAP = 5, RT_TUNE_EXCHANGE = 6, RT_TUNE_WHOLE_PIXEL_SHARE = 7 } rt_tuning_key;
 int rt_scene_set_tuning(rt_scene *scene, int key, int value);
+/* The work items of a render under `opts` at an explicit split with `share` sixteenths of the shard's tiles handed out as whole
+ * pixels (RT_TUNE_WHOLE_PIXEL_SHARE): what rt_launch_info.whole_claims and .n_items report after such a render by a kernel that
+ * has whole-pixel items (feature_set = 3; any other kernel: as share 0).  resident_waves = rt_launch_info.n_cus x
+ * blocks_per_cu x block_threads / 64 of that render; only share -1 reads it.  Host-side. */
+int rt_plan_work_items(const rt_render_opts *opts, uint32_t split, int share, uint64_t resident_waves, uint32_t *whole_claims,
+                       uint64_t *n_items);
 
 /* ---- Sampler::sample_image  samplers/random_sampler.rs:10-99 ----
  * Renders opts->samples_per_pixel passes and returns their running mean
@@ -441,8 +455,9 @@ typedef struct rt_launch_info {
 	uint32_t lds_bytes;     /* dynamic LDS per workgroup */
 	uint32_t n_cus;
 	uint32_t sample_split;
-	uint32_t reserved;
-	uint64_t n_items;       /* work items of the launch (pixels x sample_split, incl. edge-tile padding) */
+	uint32_t whole_claims;  /* claims of 64 items that are whole tiles, one pixel per lane (RT_TUNE_WHOLE_PIXEL_SHARE) */
+	uint64_t n_items;       /* work items of the launch: 64 x (whole_claims + (tiles - whole_claims) x sample_split) in the tiled
+	                           order, else pixels x sample_split; incl. edge-tile padding */
 	char kernel[160];
 } rt_launch_info;
 int rt_last_launch_info(const rt_scene *scene, rt_launch_info *out);

@@ -26,7 +26,7 @@ RT_SPLIT_SAH, RT_SPLIT_MIDDLE, RT_SPLIT_EQUAL_COUNTS = range(3)
 # enum RenderMethod (samplers/mod.rs:43-47)
 RT_METHOD_NAIVE, RT_METHOD_MIS = range(2)
 RT_LAYOUT_FRAME, RT_LAYOUT_SHARD = range(2)
-RT_TUNE_TRAVERSAL, RT_TUNE_FEATURE_SET, RT_TUNE_SCENE_IN_LDS, RT_TUNE_SCHEDULE, RT_TUNE_WALK, RT_TUNE_STACK_CAP, RT_TUNE_EXCHANGE = range(7)
+RT_TUNE_TRAVERSAL, RT_TUNE_FEATURE_SET, RT_TUNE_SCENE_IN_LDS, RT_TUNE_SCHEDULE, RT_TUNE_WALK, RT_TUNE_STACK_CAP, RT_TUNE_EXCHANGE, RT_TUNE_WHOLE_PIXEL_SHARE = range(8)
 
 NO_INDEX = 0xFFFFFFFFFFFFFFFF  # usize::MAX
 RT_DEVICE_NONE = -1  # rt_scene_create: Bvh::new on the host only (no GPU touched, nothing can be rendered)
@@ -195,7 +195,7 @@ class LaunchInfo(C.Structure):  # rt_launch_info
         ("lds_bytes", C.c_uint32),
         ("n_cus", C.c_uint32),
         ("sample_split", C.c_uint32),
-        ("reserved", C.c_uint32),
+        ("whole_claims", C.c_uint32),
         ("n_items", C.c_uint64),
         ("kernel", C.c_char * 160),
     ]
@@ -577,6 +577,7 @@ EXPORTED_SYMBOLS = [
     "rt_render_device",
     "rt_render_output_floats",
     "rt_shard_pixel_order",
+    "rt_plan_work_items",
     "rt_last_kernel_ms",
     "rt_last_launch_info",
     "rt_output_rgb8",

@@ -722,6 +722,11 @@ static int set_tuning_one(rt_scene *s, int key, int value)
 			return fail(RT_ERR_INVALID_ARGUMENT, "exchange must be 0 (off) or 1 (on where the kernel has it)");
 		s->exchange_mode = value;
 		return RT_OK;
+	case RT_TUNE_WHOLE_PIXEL_SHARE:
+		if (value < -1 || value > 16)
+			return fail(RT_ERR_INVALID_ARGUMENT, "whole-pixel share must be -1 (automatic) or 0..16 (sixteenths of a shard's tiles)");
+		s->whole_share = value;
+		return RT_OK;
 	case RT_TUNE_WALK:
 		if (value < 0 || value > 1)
 			return fail(RT_ERR_INVALID_ARGUMENT, "walk must be 0 (automatic) or 1 (two-child walk for every ray)");
@@ -899,6 +904,34 @@ uint32_t auto_sample_split(int n_cus, uint64_t frame_pixels, uint64_t spp, uint3
 	return split;
 }
 
+// The work items of a launch over `tiles` tiles of 64 pixels at split S (a power of two <= 64) -- the tiled order of rt_render.hip's
+// acquire_coarse: the first whole_claims claims of 64 items are whole tiles, the other tiles follow as S claims of 64 chunk items
+// each.  `tiled` false (any other tiling or split) or S = 1: no whole-pixel claims, pixels x S items.
+// share 0 .. 16 (RT_TUNE_WHOLE_PIXEL_SHARE by name: tests, measurements): that many sixteenths of the tiles, whatever the launch.
+// share -1, the library's own choice, goes by tiles per RESIDENT WAVE, because whether whole pixels pay depends on how many
+// pixel-times a lane has in front of it, not on the frame: a whole pixel runs for one pixel-time on one lane, so whole pixels
+// stranded at the end cost up to that, and only a chunk part of several pixel-times per lane behind them absorbs it.  The one
+// sweep there is (config 2, 5.27 tiles per resident wave, profiles/r06_whole_claims_sweep.log): whole / chunk tiles per wave
+// 2.64 / 2.64 -> -1.9 %, 3.30 / 1.98 -> +10 %, 3.96 / 1.32 -> +21 %.  So: half the tiles, but never more than kWholeMaxPerWave
+// claims per resident wave and never so many that fewer than kChunkMinPerWave tiles per resident wave are left for chunk items.
+// A launch below 2.5 tiles per resident wave -- one device's eighth of a 1080p frame (0.66), 640 x 360 (0.59) -- gets none.
+constexpr uint64_t kWholeMaxPerWave = 3u;      // (claims; between the 2.64 that won and the 3.30 that lost)
+constexpr uint64_t kChunkMinPerWaveX2 = 5u;    // 2.5 tiles, in halves (between the 2.64 that won and the 1.98 that lost)
+WorkItems plan_work_items(uint64_t tiles, uint64_t tile_pixels, uint32_t split, bool tiled, int share, uint64_t resident_waves)
+{
+	WorkItems w;
+	w.whole_claims = 0u;
+	if (tiled && split > 1u && share >= 0) {
+		w.whole_claims = (tiles * (uint64_t)share) / 16u;
+	} else if (tiled && split > 1u) {
+		const uint64_t chunk_min = (kChunkMinPerWaveX2 * resident_waves + 1u) / 2u;
+		const uint64_t room = tiles > chunk_min ? tiles - chunk_min : 0u;
+		w.whole_claims = std::min(std::min(tiles / 2u, room), kWholeMaxPerWave * resident_waves);
+	}
+	w.n_items = tile_pixels * (w.whole_claims + (tiles - w.whole_claims) * split);
+	return w;
+}
+
 // Scene-owned frame buffers, grown on first use / larger frames only: rt_render needs one device frame,
 // rt_sample_image two device frames, two pinned host frames, a copy stream and its events.
 static int ensure_frame_buffers(rt_scene *s, uint64_t n_floats, bool progressive)
@@ -951,6 +984,18 @@ static void fill_tiling(DevRenderParams &P, const rt_render_opts *o, const Shard
 	P.n_work = (uint32_t)g.n_work;
 }
 
+// DevRenderParams::tile_log2_w: whether (and with which two logarithms) the launch hands its items out in the tiled order
+static uint32_t tiled_order_log2(const rt_render_opts *o, const ShardGeometry &g, uint32_t split)
+{
+	if (g.tile_w * g.tile_h == 64u && (g.tile_w & (g.tile_w - 1u)) == 0u && o->width < 65536u && o->height < 65536u &&
+	    (split & (split - 1u)) == 0u && split <= 64u)
+		for (uint32_t lw = 0; lw < 7u; ++lw)
+			for (uint32_t ls = 0; ls < 7u; ++ls)
+				if ((1u << lw) == g.tile_w && (1u << ls) == split)
+					return lw | (ls << 8);
+	return 0xFFFFFFFFu;
+}
+
 // What one render launch will be: a plain value, made without touching the scene, a stream or device memory.
 struct RenderLaunchPlan { // (filled in this order at the end of plan_render_launch)
 	DevRenderParams P; // (P.stack_ovf_depth: entries per lane the launch needs in the scene's global overflow area)
@@ -989,19 +1034,12 @@ static int plan_render_launch(const rt_scene *s, const rt_render_opts *o, const 
 		P.inv_w1 = rw;
 		P.inv_h1 = rh;
 	}
-	P.tile_log2_w = 0xFFFFFFFFu;
-	if (g.tile_w * g.tile_h == 64u && (g.tile_w & (g.tile_w - 1u)) == 0u && o->width < 65536u && o->height < 65536u &&
-	    (split & (split - 1u)) == 0u && split <= 64u)
-		for (uint32_t lw = 0; lw < 7u; ++lw)
-			for (uint32_t ls = 0; ls < 7u; ++ls)
-				if ((1u << lw) == g.tile_w && (1u << ls) == split)
-					P.tile_log2_w = lw | (ls << 8);
+	P.tile_log2_w = tiled_order_log2(o, g, split);
 	if (split > o->samples_per_pixel)
 		return fail(RT_ERR_INVALID_ARGUMENT, "sample_split larger than samples_per_pixel");
 	if (g.n_work * split >= (1ull << 32))
 		return fail(RT_ERR_UNSUPPORTED, "pixels x sample_split exceeds 2^32 work items");
 	P.sample_split = split;
-	P.n_items = (uint32_t)(g.n_work * split);
 	P.shard_layout = o->output_layout == RT_LAYOUT_SHARD ? 1 : 0;
 
 	// traversal: exhaustive (the reference's own amount of work) for tiny trees where pruning cannot
@@ -1143,6 +1181,13 @@ static int plan_render_launch(const rt_scene *s, const rt_render_opts *o, const 
 		}
 	}
 	uint64_t n_blocks = (uint64_t)s->n_cus * (uint64_t)blocks_per_cu;
+	// whole pixels first, chunk items for the tail of the shard only, sized by the waves the device holds at once (plan_work_items).
+	// The pair kernels alone are compiled with whole-pixel items (rt_render.hip kWholeItems, acquire_coarse); every other kernel
+	// hands out pixels x split chunk items as before
+	const WorkItems items = plan_work_items(g.n_tiles_owned, (uint64_t)g.tile_w * g.tile_h, split, P.tile_log2_w != 0xFFFFFFFFu,
+	                                        feature_set == 3 ? s->whole_share : 0, n_blocks * (block_threads / 64u));
+	P.whole_claims = (uint32_t)items.whole_claims;
+	P.n_items = (uint32_t)items.n_items;
 	const uint64_t blocks_needed = ((uint64_t)P.n_items + block_threads - 1) / block_threads;
 	if (n_blocks > blocks_needed)
 		n_blocks = blocks_needed ? blocks_needed : 1;
@@ -1168,6 +1213,7 @@ static void fill_launch_info(const RenderLaunchPlan &plan, const rt_render_opts 
 	L.lds_bytes = (uint32_t)plan.lds_bytes;
 	L.n_cus = (uint32_t)n_cus;
 	L.sample_split = plan.split;
+	L.whole_claims = plan.P.whole_claims;
 	L.n_items = plan.P.n_items;
 	static const char *const feat_names[4] = {"rt::Feat<false, false, false, false>", "rt::Feat<true, true, false, false>",
 	                                          "rt::Feat<true, true, true, true>", "rt::FeatPair"};
@@ -1189,6 +1235,24 @@ int rt_scene_auto_sample_split(const rt_scene *s, const rt_render_opts *o, uint3
 		return fail(RT_ERR_INVALID_ARGUMENT, "shard_count and samples_per_pixel must be >= 1");
 	const uint32_t members = (uint32_t)(1 + s->peers.size());
 	*split = auto_sample_split(s->n_cus, o->width * o->height, o->samples_per_pixel, members > 1u ? members : o->shard_count);
+	return RT_OK;
+}
+
+int rt_plan_work_items(const rt_render_opts *o, uint32_t split, int share, uint64_t resident_waves, uint32_t *whole_claims, uint64_t *n_items)
+{
+	ShardGeometry g;
+	int rc = shard_geometry(o, g);
+	if (rc != RT_OK)
+		return rc;
+	if (!whole_claims || !n_items)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (split == 0u || share < -1 || share > 16)
+		return fail(RT_ERR_INVALID_ARGUMENT, "split must be >= 1 (explicit) and the whole-pixel share -1 (automatic) or 0..16");
+	if (g.n_work * split >= (1ull << 32))
+		return fail(RT_ERR_UNSUPPORTED, "pixels x sample_split exceeds 2^32 work items");
+	const WorkItems w = plan_work_items(g.n_tiles_owned, (uint64_t)g.tile_w * g.tile_h, split, tiled_order_log2(o, g, split) != 0xFFFFFFFFu, share, resident_waves);
+	*whole_claims = (uint32_t)w.whole_claims;
+	*n_items = w.n_items;
 	return RT_OK;
 }
 

@@ -34,6 +34,9 @@ inline int hip_fail(hipError_t e, const char *what)
 // the pruned walk above this many primitives, the exhaustive one up to it (measured: see the crossovers in rt_api.cpp)
 constexpr uint32_t kPruneAbove = 100;
 
+// RT_TUNE_WHOLE_PIXEL_SHARE when nobody sets it: -1, the planner's own choice by tiles per resident wave (rt_api.cpp plan_work_items)
+constexpr int kWholeShareDefault = -1;
+
 struct rt_scene {
 	int device = 0;
 	rt::HostScene host;
@@ -69,6 +72,7 @@ struct rt_scene {
 	rt_launch_info last_launch{};
 	uint32_t stack_cap_override = 0; // RT_TUNE_STACK_CAP
 	int exchange_mode = 0;           // RT_TUNE_EXCHANGE
+	int whole_share = kWholeShareDefault; // RT_TUNE_WHOLE_PIXEL_SHARE
 	uint32_t stack_depth_narrow = 2; // HostScene::stack_depth_narrow (members of a multi-device scene have no host scene of their own)
 	uint32_t *d_stack_ovf = nullptr; // traversal-stack overflow area (deep trees under the fine schedule), grown on demand
 	size_t stack_ovf_words = 0;
@@ -111,6 +115,9 @@ struct rt_scene {
 
 // sample_split = 0 (automatic), resolved (rt_api.cpp); the noise estimates halve it until it divides the passes (rt_api_post.cpp)
 uint32_t auto_sample_split(int n_cus, uint64_t frame_pixels, uint64_t spp, uint32_t n_sharers);
+// the work items of a launch in the tiled order: whole-pixel claims first, chunk claims for the tiles left over (rt_api.cpp)
+struct WorkItems { uint64_t whole_claims, n_items; };
+WorkItems plan_work_items(uint64_t tiles, uint64_t tile_pixels, uint32_t split, bool tiled, int share, uint64_t resident_waves);
 
 // ---- traversal policy: which walk, and for the four-wave kernels which tree and how much stack ----
 // the walk every launch on this scene takes (rt_scene_set_traversal / RT_TUNE_TRAVERSAL, else by size); the fine schedule of

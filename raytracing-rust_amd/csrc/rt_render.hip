@@ -74,6 +74,8 @@ constexpr uint32_t kLightPhaseThreshold = RT_LIGHT_PHASE_THRESHOLD;
 #endif
 constexpr uint32_t kStarveLimit = RT_STARVE_LIMIT;
 constexpr uint32_t kClaim = 64; // work items a wave claims per atomic
+constexpr uint32_t kWholePixel = 64u;      // lane state chunk_c: the item is a whole pixel (the bits below hold the chunk's number, < 64)
+constexpr uint32_t kWholeClaim = 1u << 31; // wave state wq_pbase: the claim is one of whole pixels (a pixel's index in a shard is below 2^31)
 #ifndef RT_ACQUIRE_BATCH
 #define RT_ACQUIRE_BATCH 1
 #endif
@@ -420,6 +422,14 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 	unsigned long long st_fine_iters[PH_COUNT] = {}, st_fine_active[PH_COUNT] = {};
 #endif
 	const bool sky_samplable = sky_can_sample(S);
+	// whole-pixel work items (acquire_coarse): in the pair kernels only.  The other coarse kernels sit at their register budgets (the
+	// triangles-and-lights kernel of config 3 goes 4 bytes of scratch over its guarded 72 with the chunk number in its lane state,
+	// the pruned spheres kernels from 36 to 50 spilled VGPRs): they keep the lane state and the hand-out they had.
+	// (Why the chunk number has a register of its own, paid for by counting passes from the pixel's first, and px / py do not share
+	// one: the general order shares these kernels and allows images 65 536 pixels wide and more, so a packed px | py << 16 would need
+	// a wave-uniform unpacking choice in GEN, every sample; this form costs nothing per sample.)
+	constexpr bool kWholeItems = F::pair && !FINE;
+	static_assert(!(kWholeItems && XCHG), "the exchange's records carry chunk_begin and chunk_end, not chunk_c: no whole-pixel items there");
 	constexpr int known_path = F::known_materials ? kMatLambertian : kMatRead; // the material a path continues from (see do_shade)
 
 	// ---- per-lane state (registers) ----
@@ -442,8 +452,12 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 	hit.uvx = hit.uvy = 0.0f;
 	hit.has_uv = hit.out = false;
 	uint32_t mat = 0;
-	uint32_t depth = 0, sample_local = 0, out_index = 0, pixel_index = 0, px = 0, py = 0;
-	uint32_t chunk_begin = 0, chunk_n = P.spp; // the passes [chunk_begin, chunk_begin + chunk_n) this lane folds for its pixel
+	uint32_t depth = 0, out_index = 0, pixel_index = 0, px = 0, py = 0;
+	// the passes this lane folds for its pixel: [chunk_begin, chunk_begin + chunk_end) of them, sample_i the next one counted from
+	// chunk_begin.  The kernels with whole-pixel items (kWholeItems, acquire_coarse) count from the pixel's first pass instead:
+	// chunk_begin stays 0 and costs no register, which pays for chunk_c -- the chunk's number, | kWholePixel when the item is a
+	// whole pixel whose chunks this lane folds one after the other.
+	uint32_t sample_i = 0, chunk_begin = 0, chunk_end = P.spp, chunk_c = 0;
 	uint32_t ray_count = 0;
 	unsigned long long rays_total = 0;
 	bool primary = true;
@@ -519,19 +533,34 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 			mean.y += c.y;
 			mean.z += c.z;
 		} else {
-			const float i_f = (float)(sample_local + 1u);
+			const float i_f = (float)(sample_i + 1u); // (S = 1: the chunk is the pixel)
 			mean.x += (c.x - mean.x) / i_f; // src/main.rs:179-185
 			mean.y += (c.y - mean.y) / i_f;
 			mean.z += (c.z - mean.z) / i_f;
 		}
 		rays_total += ray_count;
-		sample_local += 1;
-		if (sample_local == chunk_n) {
-			float *const out = kargs()->out;
+		sample_i += 1;
+		if (sample_i == chunk_end) {
+			const KArgs k = kargs();
+			float *const out = k->out;
 			out[3u * (size_t)out_index + 0u] = mean.x;
 			out[3u * (size_t)out_index + 1u] = mean.y;
 			out[3u * (size_t)out_index + 2u] = mean.z;
 			ph = PH_NEED_PIXEL;
+			if constexpr (kWholeItems) {
+				// a whole-pixel item (acquire_coarse): on to the pixel's next chunk -- the same passes in the same order into the same
+				// place of the partial buffer as the chunk item would have been, without an acquire event.  sample_i already stands
+				// at the next chunk's first pass.
+				const uint32_t log2_s = k->P.tile_log2_w >> 8; // (whole-pixel items exist under the tiled order only)
+				const uint32_t c1 = (chunk_c & (kWholePixel - 1u)) + 1u;
+				if (chunk_c >= kWholePixel && (c1 >> log2_s) == 0u) {
+					chunk_c += 1u;
+					chunk_end = (uint32_t)(((uint64_t)(c1 + 1u) * k->P.spp) >> log2_s);
+					out_index += k->P.n_work;
+					mean = v3s(0.0f);
+					ph = PH_GEN;
+				}
+			}
 		} else {
 			ph = PH_GEN;
 		}
@@ -549,7 +578,7 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 		// (the image size in the same round of scalar loads as the rest: left to the compiler it is fetched after the Philox rounds,
 		// a round trip of its own)
 		const uint32_t w1 = here_(k->P.width - 1u), h1 = here_(k->P.height - 1u);
-		rt_rng_seed(&rng, seed, (uint64_t)pixel_index, sample_begin + chunk_begin + sample_local);
+		rt_rng_seed(&rng, seed, (uint64_t)pixel_index, sample_begin + chunk_begin + sample_i);
 		RT_SECTION(15); // GEN: loads + stream seed
 		// (jitter + pixel) / (W - 1): the numerator is zero or in [2^-23, 2^31), the denominator in [1, 2^31]: tame (rt_lean.h) --
 		// and when the host has verified the two divisors (DevRenderParams::w1h1_ok), two fma steps on its reciprocals
@@ -949,8 +978,8 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 		d[5] = make_uint4(__float_as_uint(hit.normal.x), __float_as_uint(hit.normal.y), __float_as_uint(hit.normal.z), __float_as_uint(hit.uvx));
 		d[6] = make_uint4(__float_as_uint(hit.uvy), fl, mat, depth);
 		d[7] = make_uint4(ray_count, __float_as_uint(mean.x), __float_as_uint(mean.y), __float_as_uint(mean.z));
-		d[8] = make_uint4(sample_local, out_index, pixel_index, px);
-		d[9] = make_uint4(py, chunk_begin, chunk_n, (uint32_t)ph);
+		d[8] = make_uint4(sample_i, out_index, pixel_index, px);
+		d[9] = make_uint4(py, chunk_begin, chunk_end, (uint32_t)ph);
 		d[10] = make_uint4(__float_as_uint(ray.o.x), __float_as_uint(ray.o.y), __float_as_uint(ray.o.z), __float_as_uint(ray.d.x));
 		d[11] = make_uint4(__float_as_uint(ray.d.y), __float_as_uint(ray.d.z), __float_as_uint(ray.inv.x), __float_as_uint(ray.inv.y));
 		d[12] = make_uint4(__float_as_uint(ray.inv.z), __float_as_uint(ray.shear.x), __float_as_uint(ray.shear.y), __float_as_uint(ray.shear.z));
@@ -977,8 +1006,8 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 		mat = a6.z; depth = a6.w;
 		ray_count = a7.x;
 		mean = v3(__uint_as_float(a7.y), __uint_as_float(a7.z), __uint_as_float(a7.w));
-		sample_local = a8.x; out_index = a8.y; pixel_index = a8.z; px = a8.w;
-		py = a9.x; chunk_begin = a9.y; chunk_n = a9.z; ph = (int)a9.w;
+		sample_i = a8.x; out_index = a8.y; pixel_index = a8.z; px = a8.w;
+		py = a9.x; chunk_begin = a9.y; chunk_end = a9.z; ph = (int)a9.w;
 		ray.o = v3(__uint_as_float(a10.x), __uint_as_float(a10.y), __uint_as_float(a10.z));
 		ray.d = v3(__uint_as_float(a10.w), __uint_as_float(a11.x), __uint_as_float(a11.y));
 		ray.inv = v3(__uint_as_float(a11.z), __uint_as_float(a11.w), __uint_as_float(a12.x));
@@ -1148,8 +1177,8 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 			d[5] = make_uint4(__float_as_uint(hit.normal.x), __float_as_uint(hit.normal.y), __float_as_uint(hit.normal.z), __float_as_uint(hit.uvx));
 			d[6] = make_uint4(__float_as_uint(hit.uvy), fl, mat, depth);
 			d[7] = make_uint4(ray_count, __float_as_uint(mean.x), __float_as_uint(mean.y), __float_as_uint(mean.z));
-			d[8] = make_uint4(sample_local, out_index, pixel_index, px);
-			d[9] = make_uint4(py, chunk_begin, chunk_n, 0u);
+			d[8] = make_uint4(sample_i, out_index, pixel_index, px);
+			d[9] = make_uint4(py, chunk_begin, chunk_end, 0u);
 		};
 		auto take_path = [&](uint32_t slot) {
 			const uint4 *d = reinterpret_cast<const uint4 *>(poolB + slot * kXchgBStride);
@@ -1169,22 +1198,22 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 			mat = a6.z; depth = a6.w;
 			ray_count = a7.x;
 			mean = v3(__uint_as_float(a7.y), __uint_as_float(a7.z), __uint_as_float(a7.w));
-			sample_local = a8.x; out_index = a8.y; pixel_index = a8.z; px = a8.w;
-			py = a9.x; chunk_begin = a9.y; chunk_n = a9.z;
+			sample_i = a8.x; out_index = a8.y; pixel_index = a8.z; px = a8.w;
+			py = a9.x; chunk_begin = a9.y; chunk_end = a9.z;
 			ph = PH_LIGHT;
 		};
 		auto park_pixel = [&](uint32_t slot) {
 			uint4 *d = reinterpret_cast<uint4 *>(poolP + slot * kXchgPStride);
-			d[0] = make_uint4(__float_as_uint(mean.x), __float_as_uint(mean.y), __float_as_uint(mean.z), sample_local);
+			d[0] = make_uint4(__float_as_uint(mean.x), __float_as_uint(mean.y), __float_as_uint(mean.z), sample_i);
 			d[1] = make_uint4(out_index, pixel_index, px, py);
-			d[2] = make_uint4(chunk_begin, chunk_n, 0u, 0u);
+			d[2] = make_uint4(chunk_begin, chunk_end, 0u, 0u);
 		};
 		auto take_pixel = [&](uint32_t slot) {
 			const uint4 *d = reinterpret_cast<const uint4 *>(poolP + slot * kXchgPStride);
 			const uint4 a0 = d[0], a1 = d[1], a2 = d[2];
 			mean = v3(__uint_as_float(a0.x), __uint_as_float(a0.y), __uint_as_float(a0.z));
-			sample_local = a0.w; out_index = a1.x; pixel_index = a1.y; px = a1.z; py = a1.w;
-			chunk_begin = a2.x; chunk_n = a2.y;
+			sample_i = a0.w; out_index = a1.x; pixel_index = a1.y; px = a1.z; py = a1.w;
+			chunk_begin = a2.x; chunk_end = a2.y;
 			ph = PH_GEN;
 		};
 		const unsigned long long below = (1ull << lane) - 1ull;
@@ -1256,6 +1285,11 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 	// chunks of a pixel in neighbouring lanes: the image is swept once, like S = 1, the divisions are done once per claim on
 	// wave-uniform values, and a lane's own part is masks and shifts.  What a pixel's chunks return does not depend on who folds
 	// them when, so the frame is the same as under the general order.
+	// Chunk items buy an even end of the launch and are paid for with an acquire event per chunk, so only the tail of the frame is
+	// handed out that way: the first DevRenderParams::whole_claims claims are WHOLE tiles, lane i taking pixel i with all its S
+	// chunks, which it folds one after the other (finalize) into the same S sums at the same places.  Which kind a claim is depends
+	// on its number alone -- wave-uniform, fixed by the host -- and rides in the top bit of wq_pbase, so that the leftovers of a
+	// claim of one kind are still decoded as that kind when the next claim is of the other.
 	auto acquire_coarse = [&]() {
 		const unsigned long long need = __ballot(ph == PH_NEED_PIXEL);
 		// Serving an acquire event costs the WHOLE wave a round of scalar loads and some sixty instructions, and with short items
@@ -1292,13 +1326,16 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 				base = (uint32_t)__builtin_amdgcn_readlane((int)claimed, leader);
 				if (tiled) {
 					const uint32_t b = base >> 6;              // claim number
-					const uint32_t kt = b >> log2_s;           // ... lies in this shard's kt-th tile
-					const uint32_t sub = b & ((1u << log2_s) - 1u); // ... and is that tile's sub-th group of 64 / S pixels
+					const uint32_t whole = kWholeItems ? k->P.whole_claims : 0u; // the first `whole` claims are whole tiles, pixel by pixel
+					const bool is_whole = b < whole;
+					const uint32_t bc = is_whole ? 0u : b - whole;  // chunk claims: numbered from the first tile left over
+					const uint32_t kt = is_whole ? b : whole + (bc >> log2_s); // the claim lies in this shard's kt-th tile
+					const uint32_t sub = bc & ((1u << log2_s) - 1u); // ... and is that tile's sub-th group of 64 / S pixels
 					const uint32_t tile = k->P.shard_index + kt * k->P.shard_count;
 					const uint32_t ty = tile / k->P.tiles_x;
 					const uint32_t tx = tile - ty * k->P.tiles_x;
 					wq_xy = (tx << log2_w) | ((ty * k->P.tile_h) << 16);
-					wq_pbase = (kt << 6) + (sub << (6u - log2_s));
+					wq_pbase = ((kt << 6) + (sub << (6u - log2_s))) | (is_whole ? kWholeClaim : 0u);
 				}
 				// the leftovers go first, the rest comes from the new claim
 				wq_next = base + (n - avail);
@@ -1318,38 +1355,62 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 				const uint32_t in = w & 63u;
 				// (the other single-sweep layout -- a claim = all 64 pixels of the tile for ONE chunk, claims tile-major -- measured the
 				// same to 0.3 % at every split: profiles/r03_ab_logs/r05v_split_ab.log)
-				const uint32_t wp = (from_old ? old_pbase : wq_pbase) + (in >> log2_s); // the pixel, in this shard's order
-				const uint32_t c = in & ((1u << log2_s) - 1u);                            // ... and which of its chunks
+				const uint32_t pbase = from_old ? old_pbase : wq_pbase;
+				const bool whole = kWholeItems && pbase >= kWholeClaim;
+				const uint32_t ls = whole ? 0u : log2_s; // a whole-pixel claim: 64 pixels, each from its chunk 0
+				const uint32_t wp = (kWholeItems ? pbase & (kWholeClaim - 1u) : pbase) + (in >> ls); // the pixel, in this shard's order
+				const uint32_t c = in & ((1u << ls) - 1u);                      // ... and which of its chunks
 				const uint32_t in_tile = wp & 63u;
 				px = (xy & 0xFFFFu) + (in_tile & ((1u << log2_w) - 1u));
 				py = (xy >> 16) + (in_tile >> log2_w);
 				inside = px < k->P.width && py < k->P.height;
 				pixel_index = py * k->P.width + px;
-				chunk_begin = (uint32_t)(((uint64_t)c * spp) >> log2_s); // = c * spp / S (rt_hip.h sample_split)
-				chunk_n = (uint32_t)(((uint64_t)(c + 1u) * spp) >> log2_s) - chunk_begin;
+				const uint32_t first = (uint32_t)(((uint64_t)c * spp) >> log2_s); // = c * spp / S (rt_hip.h sample_split)
+				const uint32_t end = (uint32_t)(((uint64_t)(c + 1u) * spp) >> log2_s);
+				if constexpr (kWholeItems) {
+					sample_i = first;
+					chunk_end = end;
+					chunk_c = c | (whole ? kWholePixel : 0u);
+				} else {
+					chunk_begin = first;
+					chunk_end = end - first;
+				}
 				// chunk sums go to the partial buffer chunk-major (combine_chunks_kernel); whole pixels to the frame or the packed shard
 				out_index = log2_s != 0u ? c * k->P.n_work + wp : (k->P.shard_layout ? wp : pixel_index);
 			} else {
 				const uint32_t split = k->P.sample_split, n_work = k->P.n_work;
 				inside = work_to_pixel(P, split > 1u ? w % n_work : w, px, py);
 				pixel_index = py * k->P.width + px;
+				if constexpr (kWholeItems)
+					chunk_c = 0u;
 				if (split > 1u) {
 					// sample_split (rt_hip.h): this item is chunk c of its pixel; its sum goes to the
 					// partial buffer (chunk-major) and combine_chunks_kernel folds the chunks in order
 					const uint32_t c = w / n_work;
-					chunk_begin = (uint32_t)(((uint64_t)c * spp) / split);
-					chunk_n = (uint32_t)(((uint64_t)(c + 1u) * spp) / split) - chunk_begin;
+					const uint32_t first = (uint32_t)(((uint64_t)c * spp) / split);
+					const uint32_t end = (uint32_t)(((uint64_t)(c + 1u) * spp) / split);
+					if constexpr (kWholeItems) {
+						sample_i = first;
+						chunk_end = end;
+					} else {
+						chunk_begin = first;
+						chunk_end = end - first;
+					}
 					out_index = w;
 				} else {
-					chunk_begin = 0u;
-					chunk_n = spp;
+					if constexpr (kWholeItems)
+						sample_i = 0u;
+					else
+						chunk_begin = 0u;
+					chunk_end = spp;
 					out_index = k->P.shard_layout ? w : pixel_index;
 				}
 			}
 			if (w >= k->P.n_items) {
 				ph = PH_DONE;
 			} else if (inside) {
-				sample_local = 0;
+				if constexpr (!kWholeItems)
+					sample_i = 0;
 				mean = v3s(0.0f);
 				ph = PH_GEN;
 			} // else: padding of an edge tile; ask again next iteration
@@ -1394,12 +1455,12 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 						// partial buffer (chunk-major) and combine_chunks_kernel folds the chunks in order
 						const uint32_t c = w / P.n_work;
 						chunk_begin = (uint32_t)(((uint64_t)c * P.spp) / P.sample_split);
-						chunk_n = (uint32_t)(((uint64_t)(c + 1u) * P.spp) / P.sample_split) - chunk_begin;
+						chunk_end = (uint32_t)(((uint64_t)(c + 1u) * P.spp) / P.sample_split) - chunk_begin;
 						out_index = w;
 					} else {
 						out_index = P.shard_layout ? w : pixel_index;
 					}
-					sample_local = 0;
+					sample_i = 0;
 					mean = v3s(0.0f);
 					ph = PH_GEN;
 				} // else: padding of an edge tile; ask again next iteration

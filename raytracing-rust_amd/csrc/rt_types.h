@@ -295,6 +295,7 @@ struct DevRenderParams {
 	uint32_t n_work;          // pixels this launch owns (incl. out-of-image padding of edge tiles)
 	uint32_t sample_split;    // S: chunks per pixel (1 = the reference's strictly sequential fold)
 	uint32_t n_items;         // n_work * S work items, chunk-major: item w = chunk (w / n_work) of pixel (w % n_work)
+	                          // (tiled order, below: 64 * (whole_claims + (tiles - whole_claims) * S), whole pixels first)
 	int32_t shard_layout;     // 1: packed shard output
 	int32_t prune;            // t-pruned traversal (validated equal to the reference's exhaustive one)
 	uint32_t sky_in_lds;      // sky CDF tables are staged in LDS
@@ -307,6 +308,9 @@ struct DevRenderParams {
 	// items then lies inside ONE tile -- 64 / S of its pixels times their S chunks -- whose origin is worked out once per claim
 	// (rt_render.hip, acquire_tiles).  0xFFFFFFFF: any other tiling or split, every item is decoded on its own (chunk-major).
 	uint32_t tile_log2_w;
+	// ... and the first whole_claims claims of that order are whole tiles, one PIXEL per lane with all its S chunks; the tiles left
+	// over are handed out chunk by chunk (rt_render.hip, acquire_coarse).  0 without the tiled order and at S = 1.
+	uint32_t whole_claims;
 	// (jitter + x) / (W - 1) and (jitter + y) / (H - 1) of the pixel loop (random_sampler.rs:55-59) by verified reciprocals
 	// (rt_build.h verified_reciprocal); w1h1_ok = 0: plain division
 	uint32_t w1h1_ok;

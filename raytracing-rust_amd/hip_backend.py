@@ -847,6 +847,14 @@ def output_floats(opts):
     return n.value
 
 
+def plan_work_items(opts, split, share, resident_waves=0):
+    """(whole_claims, n_items) of a render under `opts` at an explicit split and whole-pixel share (rt_plan_work_items, host-side);
+    share -1 is the library's own choice for a device that holds `resident_waves` waves at once"""
+    whole, n = C.c_uint32(), C.c_uint64()
+    _check(lib().rt_plan_work_items(C.byref(opts), C.c_uint32(split), C.c_int(share), C.c_uint64(resident_waves), C.byref(whole), C.byref(n)))
+    return whole.value, n.value
+
+
 def shard_pixel_order(opts):
     n = output_floats(_with_layout(opts, abi.RT_LAYOUT_SHARD)) // 3
     out = np.zeros(max(1, n), dtype=np.uint64)
