@@ -26,7 +26,7 @@ template <class Args> __device__ __forceinline__ KArgPtr<Args> aov_kargs(const A
 }
 
 // wave -> tile, lane -> pixel, and the lane's stack column.  The whole worst case is in LDS: the overflow branch is never taken
-// (its base only has to be some global pointer, see rt_render.hip check_hit_kernel).
+// (its base only has to be some global pointer, see rt_query.hip check_hit_kernel).
 struct AovLane {
 	uint32_t px, py;
 	uint64_t pixel;

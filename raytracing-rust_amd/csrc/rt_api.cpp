@@ -6,9 +6,10 @@
 // RT_ERR_NO_DEVICE.
 //
 // This file: scene creation, multi-device scenes, the render-launch planner (plan_render_launch) and rt_render_device that carries
-// a plan out, sampling, output, check-hit and the self-tests; what rt_render.hip exports to it is rt_render.h.  The post-processing
-// stages (AOV buffers, denoiser, temporal accumulation, display) are rt_api_post.cpp; what the two share (rt_scene, the error
-// convention, the four-wave kernels' traversal policy, the argument checks and buffer plumbing) is rt_api_internal.h.
+// a plan out, and sampling; what rt_render.hip exports to it is rt_render.h.  The post-processing stages (AOV buffers, denoiser,
+// temporal accumulation, display) are rt_api_post.cpp, the batch hit queries and the self-tests rt_api_query.cpp, the host-only
+// output stage rt_output.cpp; what they share (rt_scene, the error convention, the four-wave kernels' traversal policy, the
+// argument checks and buffer plumbing) is rt_api_internal.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -24,7 +25,6 @@
 #include <dlfcn.h>
 #include "rt_api_internal.h"
 #include "rt_render.h"
-#include "rt_sky_selftest.h"
 
 using namespace rt;
 
@@ -237,15 +237,6 @@ static void sky_reciprocals(const rt_sky_desc &sky, uint32_t *ok, float *inv_x, 
 		const bool ok_x = verified_reciprocal((float)sky.sampler_res_x, inv_x), ok_y = verified_reciprocal((float)sky.sampler_res_y, inv_y);
 		*ok = (ok_x && ok_y) ? 1u : 0u;
 	}
-}
-
-// the bytes of the sky's CDF tables and guides: what a launch compares with kSkyLdsLimit before it asks for them in LDS
-constexpr size_t kSkyLdsLimit = 96 * 1024;
-static size_t sky_table_bytes(uint32_t res_x, uint32_t res_y, uint32_t guide_k)
-{
-	if ((res_x | res_y) == 0u)
-		return 0;
-	return ((size_t)res_y * (res_x + 1u) + res_y + 1u) * 4 + (size_t)(res_y + 1u) * guide_k;
 }
 
 // Lays a built scene out in the HBM of s->device (every array of rt_types.h) and creates the scene's stream, events and
@@ -1721,423 +1712,6 @@ int rt_last_launch_info(const rt_scene *s, rt_launch_info *out)
 	if (!s->timed)
 		return fail(RT_ERR_INVALID_ARGUMENT, "no render has been launched on this scene");
 	*out = s->last_launch;
-	return RT_OK;
-}
-
-// ---- output stage (host only): crates/output/src/lib.rs:74-113 ----
-namespace {
-
-uint32_t crc32_update(uint32_t crc, const uint8_t *p, size_t n)
-{
-	static uint32_t table[256];
-	static bool init = false;
-	if (!init) {
-		for (uint32_t i = 0; i < 256; ++i) {
-			uint32_t c = i;
-			for (int k = 0; k < 8; ++k)
-				c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-			table[i] = c;
-		}
-		init = true;
-	}
-	for (size_t i = 0; i < n; ++i)
-		crc = table[(crc ^ p[i]) & 0xFFu] ^ (crc >> 8);
-	return crc;
-}
-void put_be32(std::vector<uint8_t> &v, uint32_t x)
-{
-	v.push_back((uint8_t)(x >> 24)); v.push_back((uint8_t)(x >> 16)); v.push_back((uint8_t)(x >> 8)); v.push_back((uint8_t)x);
-}
-void put_le32(std::vector<uint8_t> &v, uint32_t x)
-{
-	v.push_back((uint8_t)x); v.push_back((uint8_t)(x >> 8)); v.push_back((uint8_t)(x >> 16)); v.push_back((uint8_t)(x >> 24));
-}
-void put_str0(std::vector<uint8_t> &v, const char *s)
-{
-	v.insert(v.end(), s, s + std::strlen(s) + 1);
-}
-void png_chunk(std::vector<uint8_t> &png, const char type[4], const std::vector<uint8_t> &data)
-{
-	put_be32(png, (uint32_t)data.size());
-	const size_t start = png.size();
-	png.insert(png.end(), type, type + 4);
-	png.insert(png.end(), data.begin(), data.end());
-	put_be32(png, crc32_update(0xFFFFFFFFu, png.data() + start, png.size() - start) ^ 0xFFFFFFFFu);
-}
-
-} // namespace
-
-extern "C" {
-
-int rt_output_rgb8(const float *rgb, uint64_t n_values, float gamma, uint8_t *out)
-{
-	if (!rgb || !out)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	const float inv_gamma = 1.0f / gamma;
-	for (uint64_t i = 0; i < n_values; ++i)
-		out[i] = rt_quantise_u8(rgb[i], inv_gamma); // (val.powf(1.0 / gamma) * 255.999) as u8, powf = the contract's rt_powf
-	return RT_OK;
-}
-
-int rt_output_save(const char *filename, const float *rgb, uint32_t width, uint32_t height, float gamma)
-{
-	if (!filename || !rgb || width == 0 || height == 0)
-		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments");
-	const std::string name(filename);
-	// save_data_to_image splits on '.', demands exactly one, and dispatches on the extension (lib.rs:81-88)
-	const size_t dot = name.find('.');
-	if (dot == std::string::npos || name.find('.', dot + 1) != std::string::npos)
-		return fail(RT_ERR_INVALID_ARGUMENT, "Invalid filename: exactly one '.' expected");
-	const std::string ext = name.substr(dot + 1);
-	const uint64_t n = (uint64_t)width * height * 3;
-	std::vector<uint8_t> file;
-	if (ext == "exr") {
-		// "gamma is ignored because of exr" (lib.rs:99-106): the float image itself, as an uncompressed
-		// scanline OpenEXR file with FLOAT channels B, G, R
-		static const uint8_t magic[8] = {0x76, 0x2f, 0x31, 0x01, 2, 0, 0, 0};
-		file.assign(magic, magic + 8);
-		auto attr = [&](const char *aname, const char *type, const std::vector<uint8_t> &value) {
-			put_str0(file, aname);
-			put_str0(file, type);
-			put_le32(file, (uint32_t)value.size());
-			file.insert(file.end(), value.begin(), value.end());
-		};
-		std::vector<uint8_t> v;
-		for (const char *ch : {"B", "G", "R"}) {
-			put_str0(v, ch);
-			put_le32(v, 2); // FLOAT
-			put_le32(v, 0); // pLinear + 3 reserved bytes
-			put_le32(v, 1); // xSampling
-			put_le32(v, 1); // ySampling
-		}
-		v.push_back(0);
-		attr("channels", "chlist", v);
-		attr("compression", "compression", {0});
-		v.clear();
-		put_le32(v, 0); put_le32(v, 0); put_le32(v, width - 1); put_le32(v, height - 1);
-		attr("dataWindow", "box2i", v);
-		attr("displayWindow", "box2i", v);
-		attr("lineOrder", "lineOrder", {0});
-		v.clear();
-		put_le32(v, 0x3F800000u);
-		attr("pixelAspectRatio", "float", v);
-		attr("screenWindowWidth", "float", v);
-		v.clear();
-		put_le32(v, 0); put_le32(v, 0);
-		attr("screenWindowCenter", "v2f", v);
-		file.push_back(0);
-		const uint64_t row_bytes = (uint64_t)width * 12;
-		const uint64_t first = file.size() + (uint64_t)height * 8;
-		for (uint32_t y = 0; y < height; ++y) {
-			const uint64_t off = first + (uint64_t)y * (8 + row_bytes);
-			put_le32(file, (uint32_t)off);
-			put_le32(file, (uint32_t)(off >> 32));
-		}
-		file.reserve(file.size() + (size_t)height * (8 + row_bytes));
-		for (uint32_t y = 0; y < height; ++y) {
-			put_le32(file, y);
-			put_le32(file, (uint32_t)row_bytes);
-			for (int c = 2; c >= 0; --c) // B, G, R planes of the scanline
-				for (uint32_t x = 0; x < width; ++x) {
-					uint32_t bits;
-					std::memcpy(&bits, &rgb[((size_t)y * width + x) * 3 + c], 4);
-					put_le32(file, bits);
-				}
-		}
-	} else if (ext == "ppm" || ext == "png" || ext == "bmp" || ext == "tiff") {
-		std::vector<uint8_t> px(n);
-		rt_output_rgb8(rgb, n, gamma, px.data());
-		if (ext == "ppm") {
-			char header[64];
-			const int len = std::snprintf(header, sizeof header, "P6\n%u %u\n255\n", width, height);
-			file.assign(header, header + len);
-			file.insert(file.end(), px.begin(), px.end());
-		} else if (ext == "bmp") {
-			// 24-bit BI_RGB, bottom-up rows of B,G,R padded to 4 bytes
-			const uint32_t stride = (width * 3 + 3) & ~3u;
-			const uint32_t size = 54 + stride * height;
-			file.push_back('B'); file.push_back('M');
-			put_le32(file, size); put_le32(file, 0); put_le32(file, 54);
-			put_le32(file, 40); put_le32(file, width); put_le32(file, height);
-			put_le32(file, 1u | (24u << 16)); // planes, bits per pixel
-			put_le32(file, 0); put_le32(file, stride * height);
-			put_le32(file, 2835); put_le32(file, 2835); put_le32(file, 0); put_le32(file, 0);
-			file.resize(size, 0);
-			for (uint32_t y = 0; y < height; ++y) {
-				uint8_t *row = file.data() + 54 + (size_t)(height - 1 - y) * stride;
-				for (uint32_t x = 0; x < width; ++x)
-					for (int c = 0; c < 3; ++c)
-						row[x * 3 + c] = px[((size_t)y * width + x) * 3 + (2 - c)];
-			}
-		} else if (ext == "tiff") {
-			// little-endian baseline TIFF: one uncompressed RGB strip, then the IFD
-			const uint32_t strip = 8, bits_at = strip + (uint32_t)n, ifd_at = (bits_at + 6 + 1) & ~1u;
-			file.push_back('I'); file.push_back('I'); file.push_back(42); file.push_back(0);
-			put_le32(file, ifd_at);
-			file.insert(file.end(), px.begin(), px.end());
-			for (int c = 0; c < 3; ++c) { file.push_back(8); file.push_back(0); }
-			file.resize(ifd_at, 0);
-			struct Tag { uint16_t id, type; uint32_t count, value; };
-			const Tag tags[] = {{256, 4, 1, width}, {257, 4, 1, height}, {258, 3, 3, bits_at}, {259, 3, 1, 1}, {262, 3, 1, 2},
-			                    {273, 4, 1, strip}, {277, 3, 1, 3}, {278, 4, 1, height}, {279, 4, 1, (uint32_t)n}, {284, 3, 1, 1}};
-			const uint16_t n_tags = sizeof tags / sizeof tags[0];
-			file.push_back((uint8_t)n_tags); file.push_back(0);
-			for (const Tag &t : tags) {
-				file.push_back((uint8_t)t.id); file.push_back((uint8_t)(t.id >> 8));
-				file.push_back((uint8_t)t.type); file.push_back(0);
-				put_le32(file, t.count);
-				put_le32(file, t.value); // SHORT values sit in the low half of the little-endian field
-			}
-			put_le32(file, 0);
-		} else {
-			static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
-			file.assign(sig, sig + 8);
-			std::vector<uint8_t> ihdr;
-			put_be32(ihdr, width);
-			put_be32(ihdr, height);
-			const uint8_t rest[5] = {8, 2, 0, 0, 0}; // 8 bits, RGB
-			ihdr.insert(ihdr.end(), rest, rest + 5);
-			png_chunk(file, "IHDR", ihdr);
-			// scanlines with filter byte 0, wrapped in zlib "stored" blocks
-			std::vector<uint8_t> raw;
-			raw.reserve((size_t)height * (width * 3 + 1));
-			for (uint32_t y = 0; y < height; ++y) {
-				raw.push_back(0);
-				raw.insert(raw.end(), px.begin() + (size_t)y * width * 3, px.begin() + (size_t)(y + 1) * width * 3);
-			}
-			std::vector<uint8_t> z;
-			z.push_back(0x78);
-			z.push_back(0x01);
-			uint32_t a = 1, b = 0; // adler32
-			for (size_t pos = 0; pos < raw.size();) {
-				const size_t len = std::min<size_t>(65535, raw.size() - pos);
-				z.push_back(pos + len == raw.size() ? 1 : 0);
-				z.push_back((uint8_t)(len & 0xFF)); z.push_back((uint8_t)(len >> 8));
-				z.push_back((uint8_t)(~len & 0xFF)); z.push_back((uint8_t)((~len >> 8) & 0xFF));
-				z.insert(z.end(), raw.begin() + pos, raw.begin() + pos + len);
-				for (size_t i = pos; i < pos + len; ++i) {
-					a = (a + raw[i]) % 65521u;
-					b = (b + a) % 65521u;
-				}
-				pos += len;
-			}
-			put_be32(z, (b << 16) | a);
-			png_chunk(file, "IDAT", z);
-			png_chunk(file, "IEND", {});
-		}
-	} else {
-		// the reference also hands jpg/jpeg to the image crate; no JPEG encoder here
-		return fail(RT_ERR_UNSUPPORTED, "Unable to save file: (unknown or unsupported filetype ." + ext + ")");
-	}
-	FILE *f = std::fopen(filename, "wb");
-	if (!f)
-		return fail(RT_ERR_INVALID_ARGUMENT, "cannot open output file");
-	const size_t written = std::fwrite(file.data(), 1, file.size(), f);
-	std::fclose(f);
-	if (written != file.size())
-		return fail(RT_ERR_INVALID_ARGUMENT, "short write");
-	return RT_OK;
-}
-
-} // extern "C"
-
-#ifdef RT_STATS
-// diagnostic build only (tests/probes/gpu_trace_queue.py): n rays through the traversal-only persistent kernel at `waves`
-// waves/SIMD with `cap` stack entries per lane in LDS; returns (t, primitive) per ray, the kernel time and the node steps
-extern "C" int rt_debug_trace_queue(rt_scene *s, const rt_ray_desc *rays, uint64_t n, int waves, uint32_t cap, float *out_t, uint32_t *out_prim,
-                                    float *ms, unsigned long long *node_steps)
-{
-	if (!s || !rays || !out_t || !out_prim || n == 0 || n >= (1ull << 31) || s->device == RT_DEVICE_NONE || s->dev.nodes4 == nullptr)
-		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (or no wide tree)");
-	HIP_TRY(hipSetDevice(s->device));
-	cap = std::min(std::max(cap, 1u), s->dev.stack_depth);
-	const uint32_t ovf_depth = s->dev.stack_depth - cap;
-	const uint32_t n_blocks = (uint32_t)s->n_cus * (uint32_t)waves;
-	const size_t lds_bytes = (size_t)4 * cap * 64 * 4;
-	void *d_rays = nullptr, *d_out = nullptr, *d_misc = nullptr, *d_ovf = nullptr;
-	HIP_TRY(hipMalloc(&d_rays, n * sizeof(rt_ray_desc)));
-	HIP_TRY(hipMalloc(&d_out, n * 8));
-	HIP_TRY(hipMalloc(&d_misc, 16));
-	HIP_TRY(hipMalloc(&d_ovf, std::max<size_t>(16, (size_t)n_blocks * 256 * ovf_depth * 4)));
-	HIP_TRY(hipMemcpy(d_rays, rays, n * sizeof(rt_ray_desc), hipMemcpyHostToDevice));
-	float best = 1e30f;
-	for (int rep = 0; rep < 3; ++rep) {
-		HIP_TRY(hipMemset(d_misc, 0, 16));
-		HIP_TRY(hipEventRecord(s->ev_start, s->stream));
-		HIP_TRY(launch_trace_queue(waves, n_blocks, lds_bytes, s->stream, s->dev, d_rays, (uint32_t)n, d_out, static_cast<uint32_t *>(d_misc),
-		                           reinterpret_cast<unsigned long long *>(static_cast<char *>(d_misc) + 8), cap, ovf_depth, static_cast<uint32_t *>(d_ovf)));
-		HIP_TRY(hipEventRecord(s->ev_stop, s->stream));
-		HIP_TRY(hipEventSynchronize(s->ev_stop));
-		float t = 0.0f;
-		HIP_TRY(hipEventElapsedTime(&t, s->ev_start, s->ev_stop));
-		best = std::min(best, t);
-	}
-	std::vector<float> tmp(2 * n);
-	HIP_TRY(hipMemcpy(tmp.data(), d_out, n * 8, hipMemcpyDeviceToHost));
-	for (uint64_t i = 0; i < n; ++i) {
-		out_t[i] = tmp[2 * i];
-		std::memcpy(&out_prim[i], &tmp[2 * i + 1], 4);
-	}
-	if (node_steps)
-		HIP_TRY(hipMemcpy(node_steps, static_cast<char *>(d_misc) + 8, 8, hipMemcpyDeviceToHost));
-	if (ms)
-		*ms = best;
-	(void)hipFree(d_rays); (void)hipFree(d_out); (void)hipFree(d_misc); (void)hipFree(d_ovf);
-	return RT_OK;
-}
-#endif
-
-// ---- batch hit queries ----
-static int check_common(rt_scene *s, const rt_ray_desc *rays, const uint64_t *object_index, uint64_t n, rt_hit_record *out)
-{
-	if (!s || !rays || !out)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (int rc = need_device(s); rc != RT_OK)
-		return rc;
-	if (n == 0)
-		return RT_OK;
-	if (object_index)
-		for (uint64_t i = 0; i < n; ++i)
-			if (object_index[i] >= s->dev.n_prims)
-				return fail(RT_ERR_INVALID_ARGUMENT, "object index out of range");
-	bool prune = false;
-	DevScene dev;
-	if (int rc = four_wave_traversal(s, &prune, &dev); rc != RT_OK) // (rt_api_internal.h)
-		return rc;
-	HIP_TRY(hipSetDevice(s->device));
-	void *d_rays = nullptr, *d_out = nullptr, *d_idx = nullptr;
-	HIP_TRY(hipMalloc(&d_rays, n * sizeof(rt_ray_desc)));
-	hipError_t e = hipMalloc(&d_out, n * sizeof(rt_hit_record));
-	if (e == hipSuccess && object_index)
-		e = hipMalloc(&d_idx, n * sizeof(uint64_t));
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(d_rays, rays, n * sizeof(rt_ray_desc), hipMemcpyHostToDevice, s->stream);
-	if (e == hipSuccess && object_index)
-		e = hipMemcpyAsync(d_idx, object_index, n * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream);
-	if (e == hipSuccess)
-		e = object_index ? launch_check_hit_index(prune, s->stream, dev, d_rays, d_idx, n, d_out)
-		                 : launch_check_hit(prune, s->stream, dev, d_rays, n, d_out);
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(out, d_out, n * sizeof(rt_hit_record), hipMemcpyDeviceToHost, s->stream);
-	if (e == hipSuccess)
-		e = hipStreamSynchronize(s->stream);
-	(void)hipFree(d_rays);
-	(void)hipFree(d_out);
-	(void)hipFree(d_idx);
-	if (e != hipSuccess)
-		return hip_fail(e, "check_hit");
-	return RT_OK;
-}
-
-int rt_check_hit(rt_scene *s, const rt_ray_desc *rays, uint64_t n_rays, rt_hit_record *out)
-{
-	return check_common(s, rays, nullptr, n_rays, out);
-}
-int rt_check_hit_index(rt_scene *s, const rt_ray_desc *rays, const uint64_t *object_index, uint64_t n_rays, rt_hit_record *out)
-{
-	if (!object_index)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	return check_common(s, rays, object_index, n_rays, out);
-}
-
-int rt_selftest_division(float divisor, float *reciprocal, int *exact)
-{
-	if (!reciprocal || !exact)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	*exact = verified_reciprocal(divisor, reciprocal) ? 1 : 0;
-	return RT_OK;
-}
-
-int rt_selftest_sky(rt_scene *s, int tables_in_lds, uint64_t seed, uint64_t n, float *out_dirs, float *out_pdf_of_sample, const float *dirs, uint64_t m,
-                    float *out_pdf)
-{
-	if (!s || (tables_in_lds != 0 && tables_in_lds != 1) || (n && (!out_dirs || !out_pdf_of_sample)) || (m && (!dirs || !out_pdf)))
-		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments");
-	if (n > (1ull << 28) || m > (1ull << 28))
-		return fail(RT_ERR_INVALID_ARGUMENT, "at most 2^28 samples and 2^28 directions");
-	if ((s->host.sky.sampler_res_x | s->host.sky.sampler_res_y) == 0u)
-		return fail(RT_ERR_INVALID_ARGUMENT, "the sky is not samplable (sampler_res 0 x 0)");
-	if (int rc = need_device(s); rc != RT_OK)
-		return rc;
-	if (tables_in_lds && (sky_table_bytes(s->dev.sky.res_x, s->dev.sky.res_y, s->dev.sky.guide_k) > kSkyLdsLimit || sky_selftest_lds_bytes(s->dev) > s->max_lds))
-		return fail(RT_ERR_UNSUPPORTED, "the sky tables exceed what a launch stages into LDS");
-	if (n + m == 0)
-		return RT_OK;
-	HIP_TRY(hipSetDevice(s->device));
-	// one allocation: directions and pdfs of the samples, then the caller's directions and their pdfs
-	float *d = nullptr;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), (4 * n + 4 * m) * sizeof(float)));
-	DevSkySelftest P;
-	P.seed = seed;
-	P.n = n;
-	P.m = m;
-	P.out_dirs = d;
-	P.out_pdf_s = d + 3 * n;
-	float *d_dirs = d + 4 * n;
-	P.dirs = d_dirs;
-	P.out_pdf = d_dirs + 3 * m;
-	hipError_t e = hipSuccess;
-	if (m)
-		e = hipMemcpyAsync(d_dirs, dirs, 3 * m * sizeof(float), hipMemcpyHostToDevice, s->stream);
-	if (e == hipSuccess)
-		e = launch_sky_selftest(tables_in_lds != 0, s->stream, s->dev, P);
-	if (e == hipSuccess && n)
-		e = hipMemcpyAsync(out_dirs, P.out_dirs, 3 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-	if (e == hipSuccess && n)
-		e = hipMemcpyAsync(out_pdf_of_sample, P.out_pdf_s, n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-	if (e == hipSuccess && m)
-		e = hipMemcpyAsync(out_pdf, P.out_pdf, m * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-	const hipError_t e_sync = hipStreamSynchronize(s->stream);
-	if (e == hipSuccess)
-		e = e_sync;
-	(void)hipFree(d);
-	if (e != hipSuccess)
-		return hip_fail(e, "selftest_sky");
-	return RT_OK;
-}
-
-int rt_selftest_lean(int device, uint64_t n_per_thread, uint64_t seed, uint64_t mismatches[RT_SELFTEST_LEAN_CLASSES])
-{
-	if (!mismatches || n_per_thread == 0 || n_per_thread > (1ull << 20))
-		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (n_per_thread in [1, 2^20])");
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
-		return fail(RT_ERR_NO_DEVICE, "no such HIP device");
-	HIP_TRY(hipSetDevice(device));
-	unsigned long long *d = nullptr;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), RT_SELFTEST_LEAN_CLASSES * sizeof(unsigned long long)));
-	hipError_t e = hipMemset(d, 0, RT_SELFTEST_LEAN_CLASSES * sizeof(unsigned long long));
-	if (e == hipSuccess)
-		e = launch_selftest_lean(nullptr, 1024u, n_per_thread, seed, d);
-	if (e == hipSuccess)
-		e = hipMemcpy(mismatches, d, RT_SELFTEST_LEAN_CLASSES * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-	(void)hipFree(d);
-	if (e != hipSuccess)
-		return hip_fail(e, "selftest");
-	return RT_OK;
-}
-
-int rt_selftest_pair_primary(rt_scene *s, const float origin[3], uint32_t *valid, uint64_t *mismatches)
-{
-	if (!s || !origin || !valid || !mismatches)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (int rc = need_device(s); rc != RT_OK)
-		return rc;
-	if (!s->pair_tree)
-		return fail(RT_ERR_UNSUPPORTED, "not a scene the two-sphere kernels take");
-	HIP_TRY(hipSetDevice(s->device));
-	DevPairPrimary host{};
-	pair_primary_terms(s->pair, s->dev.root_min, s->dev.root_max, v3(origin[0], origin[1], origin[2]), host);
-	unsigned long long *d = nullptr, bad = 0;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof *d));
-	hipError_t e = launch_selftest_pair_primary(nullptr, s->pair, s->dev.root_min, s->dev.root_max, origin, host, d);
-	if (e == hipSuccess)
-		e = hipMemcpy(&bad, d, sizeof bad, hipMemcpyDeviceToHost);
-	(void)hipFree(d);
-	if (e != hipSuccess)
-		return hip_fail(e, "selftest_pair_primary");
-	*valid = host.valid;
-	*mismatches = bad;
 	return RT_OK;
 }
 

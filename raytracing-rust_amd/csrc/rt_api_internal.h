@@ -1,5 +1,6 @@
-// rt_api_internal.h -- what the host translation units of librt_hip.so share (rt_api.cpp, rt_api_post.cpp): the scene
-// handle, the error convention, and the plumbing every blocking entry point repeats.  Not installed, not part of include/.
+// rt_api_internal.h -- what the host translation units of librt_hip.so share (rt_api.cpp, rt_api_post.cpp, rt_api_query.cpp): the
+// scene handle, the error convention, and the plumbing every blocking entry point repeats; rt_output.cpp takes the error
+// convention from it.  Not installed, not part of include/.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -118,6 +119,15 @@ uint32_t auto_sample_split(int n_cus, uint64_t frame_pixels, uint64_t spp, uint3
 // the work items of a launch in the tiled order: whole-pixel claims first, chunk claims for the tiles left over (rt_api.cpp)
 struct WorkItems { uint64_t whole_claims, n_items; };
 WorkItems plan_work_items(uint64_t tiles, uint64_t tile_pixels, uint32_t split, bool tiled, int share, uint64_t resident_waves);
+
+// the bytes of the sky's CDF tables and guides: what a launch compares with kSkyLdsLimit before it asks for them in LDS
+constexpr size_t kSkyLdsLimit = 96 * 1024;
+inline size_t sky_table_bytes(uint32_t res_x, uint32_t res_y, uint32_t guide_k)
+{
+	if ((res_x | res_y) == 0u)
+		return 0;
+	return ((size_t)res_y * (res_x + 1u) + res_y + 1u) * 4 + (size_t)(res_y + 1u) * guide_k;
+}
 
 // ---- traversal policy: which walk, and for the four-wave kernels which tree and how much stack ----
 // the walk every launch on this scene takes (rt_scene_set_traversal / RT_TUNE_TRAVERSAL, else by size); the fine schedule of

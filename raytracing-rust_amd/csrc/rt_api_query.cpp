@@ -1,0 +1,220 @@
+// rt_api_query.cpp -- the entry points of librt_hip.so that ask a scene or the device a question without rendering: the batch
+// hit queries (rt_check_hit / rt_check_hit_index), the self-tests (rt_selftest_*) and, in the diagnostic build,
+// rt_debug_trace_queue.  Their kernels are rt_query.hip and rt_selftest.hip; the scene handle, the error convention and the
+// traversal policy are rt_api_internal.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "../../include/rt_hip.h"
+#include "rt_api_internal.h"
+#include "rt_query.h"
+#include "rt_selftest.h"
+
+using namespace rt;
+
+#ifdef RT_STATS
+// diagnostic build only (tests/probes/gpu_trace_queue.py): n rays through the traversal-only persistent kernel at `waves`
+// waves/SIMD with `cap` stack entries per lane in LDS; returns (t, primitive) per ray, the kernel time and the node steps
+extern "C" int rt_debug_trace_queue(rt_scene *s, const rt_ray_desc *rays, uint64_t n, int waves, uint32_t cap, float *out_t, uint32_t *out_prim,
+                                    float *ms, unsigned long long *node_steps)
+{
+	if (!s || !rays || !out_t || !out_prim || n == 0 || n >= (1ull << 31) || s->device == RT_DEVICE_NONE || s->dev.nodes4 == nullptr)
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (or no wide tree)");
+	HIP_TRY(hipSetDevice(s->device));
+	cap = std::min(std::max(cap, 1u), s->dev.stack_depth);
+	const uint32_t ovf_depth = s->dev.stack_depth - cap;
+	const uint32_t n_blocks = (uint32_t)s->n_cus * (uint32_t)waves;
+	const size_t lds_bytes = (size_t)4 * cap * 64 * 4;
+	void *d_rays = nullptr, *d_out = nullptr, *d_misc = nullptr, *d_ovf = nullptr;
+	HIP_TRY(hipMalloc(&d_rays, n * sizeof(rt_ray_desc)));
+	HIP_TRY(hipMalloc(&d_out, n * 8));
+	HIP_TRY(hipMalloc(&d_misc, 16));
+	HIP_TRY(hipMalloc(&d_ovf, std::max<size_t>(16, (size_t)n_blocks * 256 * ovf_depth * 4)));
+	HIP_TRY(hipMemcpy(d_rays, rays, n * sizeof(rt_ray_desc), hipMemcpyHostToDevice));
+	float best = 1e30f;
+	for (int rep = 0; rep < 3; ++rep) {
+		HIP_TRY(hipMemset(d_misc, 0, 16));
+		HIP_TRY(hipEventRecord(s->ev_start, s->stream));
+		HIP_TRY(launch_trace_queue(waves, n_blocks, lds_bytes, s->stream, s->dev, d_rays, (uint32_t)n, d_out, static_cast<uint32_t *>(d_misc),
+		                           reinterpret_cast<unsigned long long *>(static_cast<char *>(d_misc) + 8), cap, ovf_depth, static_cast<uint32_t *>(d_ovf)));
+		HIP_TRY(hipEventRecord(s->ev_stop, s->stream));
+		HIP_TRY(hipEventSynchronize(s->ev_stop));
+		float t = 0.0f;
+		HIP_TRY(hipEventElapsedTime(&t, s->ev_start, s->ev_stop));
+		best = std::min(best, t);
+	}
+	std::vector<float> tmp(2 * n);
+	HIP_TRY(hipMemcpy(tmp.data(), d_out, n * 8, hipMemcpyDeviceToHost));
+	for (uint64_t i = 0; i < n; ++i) {
+		out_t[i] = tmp[2 * i];
+		std::memcpy(&out_prim[i], &tmp[2 * i + 1], 4);
+	}
+	if (node_steps)
+		HIP_TRY(hipMemcpy(node_steps, static_cast<char *>(d_misc) + 8, 8, hipMemcpyDeviceToHost));
+	if (ms)
+		*ms = best;
+	(void)hipFree(d_rays); (void)hipFree(d_out); (void)hipFree(d_misc); (void)hipFree(d_ovf);
+	return RT_OK;
+}
+#endif
+
+extern "C" {
+
+// ---- batch hit queries ----
+static int check_common(rt_scene *s, const rt_ray_desc *rays, const uint64_t *object_index, uint64_t n, rt_hit_record *out)
+{
+	if (!s || !rays || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (int rc = need_device(s); rc != RT_OK)
+		return rc;
+	if (n == 0)
+		return RT_OK;
+	if (object_index)
+		for (uint64_t i = 0; i < n; ++i)
+			if (object_index[i] >= s->dev.n_prims)
+				return fail(RT_ERR_INVALID_ARGUMENT, "object index out of range");
+	bool prune = false;
+	DevScene dev;
+	if (int rc = four_wave_traversal(s, &prune, &dev); rc != RT_OK) // (rt_api_internal.h)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	void *d_rays = nullptr, *d_out = nullptr, *d_idx = nullptr;
+	HIP_TRY(hipMalloc(&d_rays, n * sizeof(rt_ray_desc)));
+	hipError_t e = hipMalloc(&d_out, n * sizeof(rt_hit_record));
+	if (e == hipSuccess && object_index)
+		e = hipMalloc(&d_idx, n * sizeof(uint64_t));
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(d_rays, rays, n * sizeof(rt_ray_desc), hipMemcpyHostToDevice, s->stream);
+	if (e == hipSuccess && object_index)
+		e = hipMemcpyAsync(d_idx, object_index, n * sizeof(uint64_t), hipMemcpyHostToDevice, s->stream);
+	if (e == hipSuccess)
+		e = object_index ? launch_check_hit_index(prune, s->stream, dev, d_rays, d_idx, n, d_out)
+		                 : launch_check_hit(prune, s->stream, dev, d_rays, n, d_out);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(out, d_out, n * sizeof(rt_hit_record), hipMemcpyDeviceToHost, s->stream);
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(s->stream);
+	(void)hipFree(d_rays);
+	(void)hipFree(d_out);
+	(void)hipFree(d_idx);
+	if (e != hipSuccess)
+		return hip_fail(e, "check_hit");
+	return RT_OK;
+}
+
+int rt_check_hit(rt_scene *s, const rt_ray_desc *rays, uint64_t n_rays, rt_hit_record *out)
+{
+	return check_common(s, rays, nullptr, n_rays, out);
+}
+int rt_check_hit_index(rt_scene *s, const rt_ray_desc *rays, const uint64_t *object_index, uint64_t n_rays, rt_hit_record *out)
+{
+	if (!object_index)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	return check_common(s, rays, object_index, n_rays, out);
+}
+
+int rt_selftest_division(float divisor, float *reciprocal, int *exact)
+{
+	if (!reciprocal || !exact)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	*exact = verified_reciprocal(divisor, reciprocal) ? 1 : 0;
+	return RT_OK;
+}
+
+int rt_selftest_sky(rt_scene *s, int tables_in_lds, uint64_t seed, uint64_t n, float *out_dirs, float *out_pdf_of_sample, const float *dirs, uint64_t m,
+                    float *out_pdf)
+{
+	if (!s || (tables_in_lds != 0 && tables_in_lds != 1) || (n && (!out_dirs || !out_pdf_of_sample)) || (m && (!dirs || !out_pdf)))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments");
+	if (n > (1ull << 28) || m > (1ull << 28))
+		return fail(RT_ERR_INVALID_ARGUMENT, "at most 2^28 samples and 2^28 directions");
+	if ((s->host.sky.sampler_res_x | s->host.sky.sampler_res_y) == 0u)
+		return fail(RT_ERR_INVALID_ARGUMENT, "the sky is not samplable (sampler_res 0 x 0)");
+	if (int rc = need_device(s); rc != RT_OK)
+		return rc;
+	if (tables_in_lds && (sky_table_bytes(s->dev.sky.res_x, s->dev.sky.res_y, s->dev.sky.guide_k) > kSkyLdsLimit || sky_selftest_lds_bytes(s->dev) > s->max_lds))
+		return fail(RT_ERR_UNSUPPORTED, "the sky tables exceed what a launch stages into LDS");
+	if (n + m == 0)
+		return RT_OK;
+	HIP_TRY(hipSetDevice(s->device));
+	// one allocation: directions and pdfs of the samples, then the caller's directions and their pdfs
+	float *d = nullptr;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), (4 * n + 4 * m) * sizeof(float)));
+	DevSkySelftest P;
+	P.seed = seed;
+	P.n = n;
+	P.m = m;
+	P.out_dirs = d;
+	P.out_pdf_s = d + 3 * n;
+	float *d_dirs = d + 4 * n;
+	P.dirs = d_dirs;
+	P.out_pdf = d_dirs + 3 * m;
+	hipError_t e = hipSuccess;
+	if (m)
+		e = hipMemcpyAsync(d_dirs, dirs, 3 * m * sizeof(float), hipMemcpyHostToDevice, s->stream);
+	if (e == hipSuccess)
+		e = launch_sky_selftest(tables_in_lds != 0, s->stream, s->dev, P);
+	if (e == hipSuccess && n)
+		e = hipMemcpyAsync(out_dirs, P.out_dirs, 3 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
+	if (e == hipSuccess && n)
+		e = hipMemcpyAsync(out_pdf_of_sample, P.out_pdf_s, n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
+	if (e == hipSuccess && m)
+		e = hipMemcpyAsync(out_pdf, P.out_pdf, m * sizeof(float), hipMemcpyDeviceToHost, s->stream);
+	const hipError_t e_sync = hipStreamSynchronize(s->stream);
+	if (e == hipSuccess)
+		e = e_sync;
+	(void)hipFree(d);
+	if (e != hipSuccess)
+		return hip_fail(e, "selftest_sky");
+	return RT_OK;
+}
+
+int rt_selftest_lean(int device, uint64_t n_per_thread, uint64_t seed, uint64_t mismatches[RT_SELFTEST_LEAN_CLASSES])
+{
+	if (!mismatches || n_per_thread == 0 || n_per_thread > (1ull << 20))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (n_per_thread in [1, 2^20])");
+	int n_dev = 0;
+	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
+		return fail(RT_ERR_NO_DEVICE, "no such HIP device");
+	HIP_TRY(hipSetDevice(device));
+	unsigned long long *d = nullptr;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), RT_SELFTEST_LEAN_CLASSES * sizeof(unsigned long long)));
+	hipError_t e = hipMemset(d, 0, RT_SELFTEST_LEAN_CLASSES * sizeof(unsigned long long));
+	if (e == hipSuccess)
+		e = launch_selftest_lean(nullptr, 1024u, n_per_thread, seed, d);
+	if (e == hipSuccess)
+		e = hipMemcpy(mismatches, d, RT_SELFTEST_LEAN_CLASSES * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+	(void)hipFree(d);
+	if (e != hipSuccess)
+		return hip_fail(e, "selftest");
+	return RT_OK;
+}
+
+int rt_selftest_pair_primary(rt_scene *s, const float origin[3], uint32_t *valid, uint64_t *mismatches)
+{
+	if (!s || !origin || !valid || !mismatches)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (int rc = need_device(s); rc != RT_OK)
+		return rc;
+	if (!s->pair_tree)
+		return fail(RT_ERR_UNSUPPORTED, "not a scene the two-sphere kernels take");
+	HIP_TRY(hipSetDevice(s->device));
+	DevPairPrimary host{};
+	pair_primary_terms(s->pair, s->dev.root_min, s->dev.root_max, v3(origin[0], origin[1], origin[2]), host);
+	unsigned long long *d = nullptr, bad = 0;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof *d));
+	hipError_t e = launch_selftest_pair_primary(nullptr, s->pair, s->dev.root_min, s->dev.root_max, origin, host, d);
+	if (e == hipSuccess)
+		e = hipMemcpy(&bad, d, sizeof bad, hipMemcpyDeviceToHost);
+	(void)hipFree(d);
+	if (e != hipSuccess)
+		return hip_fail(e, "selftest_pair_primary");
+	*valid = host.valid;
+	*mismatches = bad;
+	return RT_OK;
+}
+
+} // extern "C"

@@ -19,6 +19,7 @@
 #include <cfloat>
 
 #include "rt_bloom.h"
+#include "rt_post_common.h"
 #include "../../include/rt_detmath.h"
 
 namespace rt {
@@ -26,8 +27,6 @@ namespace rt {
 namespace {
 
 constexpr uint32_t kFootW = 2u * kBloomTileW + 2u, kFootH = 2u * kBloomTileH + 2u; // source pixels under one tile
-
-__device__ inline float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
 
 __device__ inline float bloom_scale(const DevBloomParams &P)
 {

@@ -16,26 +16,9 @@
 // wave's taps fall on few cache lines.  Taps are gathered through L1 / L2: the working set (48 B per pixel) stays in the
 // Infinity Cache at 1080p.
 #include "rt_denoise.h"
+#include "rt_post_common.h"
 
 namespace rt {
-
-namespace {
-
-constexpr uint32_t kMaxBlocks = 65536; // grid-stride beyond this (tall one-column frames)
-
-__device__ inline float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
-
-__device__ inline bool finite3(float a, float b, float c) { return __builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(c); }
-
-// pixel of this lane in 16 x 16 tile `tile`: wave w takes the 8 x 8 quadrant (w & 1, w >> 1), lane l the pixel (l & 7, l >> 3)
-__device__ inline void tile_pixel(uint32_t tile, uint32_t tiles_x, uint32_t &x, uint32_t &y)
-{
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	x = (tile % tiles_x) * 16u + (wave & 1u) * 8u + (lane & 7u);
-	y = (tile / tiles_x) * 16u + (wave >> 1) * 8u + (lane >> 3);
-}
-
-} // namespace
 
 template <int MODE>
 __global__ __launch_bounds__(256) void denoise_prepass_kernel(const DevDenoiseParams P)

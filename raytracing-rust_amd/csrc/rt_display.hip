@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "rt_display.h"
+#include "rt_post_common.h"
 #include "../../include/rt_detmath.h"
 
 namespace rt {
@@ -23,8 +24,6 @@ namespace {
 // log2(1 + (m + 0.5) / 8): the centre of sub-bin m of an octave (include/rt_hip.h)
 __constant__ const float kLog2Mid[8] = {0.0874628413f, 0.247927513f, 0.392317423f, 0.523561956f,
                                         0.643856190f,  0.754887502f, 0.857980995f, 0.954196310f};
-
-__device__ inline float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
 
 // the histogram bin of a metered pixel, -1 for one that is not metered
 __device__ inline int display_bin(float r, float g, float b)

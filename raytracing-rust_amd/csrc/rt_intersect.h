@@ -989,4 +989,24 @@ __device__ __forceinline__ bool trace_any(const DevScene &S, const DevScene &SU,
 	return false;
 }
 
+// ---- how a wave votes between the steps of its lanes' walks: the fine schedule of the render kernels (rt_render.hip) and the
+// traversal-only trace queue of the diagnostic build (rt_query.hip) ----
+#ifndef RT_DRAIN_LANES
+#define RT_DRAIN_LANES 6
+#endif
+constexpr uint32_t kDrainLanes = RT_DRAIN_LANES; // fine schedule: a short phase runs once this many lanes wait for it
+#ifndef RT_DRAIN_LANES_HEAVY
+// (the long phases wait for 8: 1 M triangles, ms, at 12 node steps per vote: 3 lanes 987, 4: 959, 6: 928, 8: 924, 10: 940; 10 M triangles
+// 1 011 / 998 / 987 / 984 / 998 -- profiles/r04au_heavy_drain_ab.log)
+#define RT_DRAIN_LANES_HEAVY 8
+#endif
+constexpr uint32_t kDrainLanesHeavy = RT_DRAIN_LANES_HEAVY; // ... the same for the long phases (GEN, SHADE, LIGHT, SCATTER)
+#ifndef RT_NODE_STEPS_PER_VOTE
+#define RT_NODE_STEPS_PER_VOTE 12 // wide tree, 1 M triangles MIS at 1080p x 256 (ms), round 4, same box, interleaved: 8 steps 964, 10: 942, 11: 929,
+                                  // 12: 928, 13: 932, 14: 936, 16: 949, 24: 1 020, 32: 1 108; 10 M triangles 984 at 12 - 13 against 990 at 16
+                                  // (profiles/r04ar_fine_knobs_ab.log, r04as, r04at_node_steps_ab.log).  Drain thresholds 4 / 5 / 8 / 10 lanes
+                                  // instead of 6: +2.5 / +0.7 / 0.0 / +2.7 %
+#endif
+constexpr int kNodeStepsPerVote = RT_NODE_STEPS_PER_VOTE;
+
 } // namespace rt

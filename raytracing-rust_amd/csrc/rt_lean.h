@@ -20,7 +20,7 @@
 //     zero, infinite or NaN or the exponents differ by more than the format allows.  So for operands whose magnitudes lie
 //     in [2^-81, 2^41] and whose exponent difference stays below 96 the remaining instructions compute bit for bit what
 //     `a / b` computes.  Every use states why its operands are tame, or tests it (one or two compares per ray) and takes
-//     the plain operator otherwise.  rt_selftest_lean (rt_api.cpp) runs both forms side by side ON THE DEVICE over random
+//     the plain operator otherwise.  rt_selftest_lean (rt_api_query.cpp) runs both forms side by side ON THE DEVICE over random
 //     and edge-case operands; tests/test_gpu_parity.py::test_lean_arithmetic_matches_the_ieee_operators asserts zero
 //     mismatches, and every parity test compares frames that went through them with the CPU checker's plain C.
 #pragma once

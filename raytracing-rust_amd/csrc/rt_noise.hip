@@ -12,15 +12,9 @@
 //                        bits and the result is the tree the header states), lane 0 writes the tile and does the two atomics.
 //                        -DRT_NOISE_TILE_LDS builds the same tree through LDS instead (a measurement variant).
 #include "rt_noise.h"
+#include "rt_post_common.h"
 
 namespace rt {
-
-namespace {
-
-// the denoiser's lum (rt_denoise.hip)
-__device__ inline float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
-
-} // namespace
 
 __global__ __launch_bounds__(256) void noise_chunk_kernel(const DevNoiseChunkParams P)
 {

@@ -24,18 +24,8 @@ hipError_t launch_render(int method, bool prune, bool fine, bool sky_lds, int fe
                          unsigned long long *rays_shot, uint32_t *work_counter, uint32_t *stack_ovf, bool xchg, const DevPairScene *pair,
                          const DevPairPrimary *primary, uint32_t block_threads = 0);
 hipError_t launch_combine(hipStream_t stream, const DevRenderParams &P, const float *partial, float *out);
-// ---- multi-device scenes, output, batch hit queries, self-tests ----
+// ---- multi-device scenes, output ----
 hipError_t launch_scatter_shard(hipStream_t stream, const DevRenderParams &P, const float *shard, float *frame);
 hipError_t launch_sum_u64(hipStream_t stream, const unsigned long long *parts, uint32_t n, unsigned long long *out);
 hipError_t launch_quantise(hipStream_t stream, const float *rgb, size_t n_values, float inv_gamma, uint8_t *out);
-hipError_t launch_check_hit(bool prune, hipStream_t stream, const DevScene &S, const void *rays, uint64_t n, void *out);
-hipError_t launch_check_hit_index(bool prune, hipStream_t stream, const DevScene &S, const void *rays, const void *object_index,
-                                  uint64_t n, void *out);
-hipError_t launch_selftest_lean(hipStream_t stream, uint32_t blocks, uint64_t n_per_thread, uint64_t seed, unsigned long long *mismatches);
-hipError_t launch_selftest_pair_primary(hipStream_t stream, const DevPairScene &pair, const float root_min[3], const float root_max[3], const float origin[3],
-                                        const DevPairPrimary &host_block, unsigned long long *mismatches);
-#ifdef RT_STATS
-hipError_t launch_trace_queue(int waves, uint32_t n_blocks, size_t lds_bytes, hipStream_t stream, const DevScene &S, const void *rays, uint32_t n, void *out,
-                              uint32_t *counter, unsigned long long *steps, uint32_t cap, uint32_t ovf_depth, uint32_t *ovf);
-#endif
 } // namespace rt

@@ -80,23 +80,6 @@ constexpr uint32_t kWholeClaim = 1u << 31; // wave state wq_pbase: the claim is 
 #define RT_ACQUIRE_BATCH 1
 #endif
 constexpr uint32_t kAcquireBatch = RT_ACQUIRE_BATCH; // coarse schedule, tile claims: lanes out of work are served once this many wait (or nothing else is left to do)
-#ifndef RT_DRAIN_LANES
-#define RT_DRAIN_LANES 6
-#endif
-constexpr uint32_t kDrainLanes = RT_DRAIN_LANES; // fine schedule: a short phase runs once this many lanes wait for it
-#ifndef RT_DRAIN_LANES_HEAVY
-// (the long phases wait for 8: 1 M triangles, ms, at 12 node steps per vote: 3 lanes 987, 4: 959, 6: 928, 8: 924, 10: 940; 10 M triangles
-// 1 011 / 998 / 987 / 984 / 998 -- profiles/r04au_heavy_drain_ab.log)
-#define RT_DRAIN_LANES_HEAVY 8
-#endif
-constexpr uint32_t kDrainLanesHeavy = RT_DRAIN_LANES_HEAVY; // ... the same for the long phases (GEN, SHADE, LIGHT, SCATTER)
-#ifndef RT_NODE_STEPS_PER_VOTE
-#define RT_NODE_STEPS_PER_VOTE 12 // wide tree, 1 M triangles MIS at 1080p x 256 (ms), round 4, same box, interleaved: 8 steps 964, 10: 942, 11: 929,
-                                  // 12: 928, 13: 932, 14: 936, 16: 949, 24: 1 020, 32: 1 108; 10 M triangles 984 at 12 - 13 against 990 at 16
-                                  // (profiles/r04ar_fine_knobs_ab.log, r04as, r04at_node_steps_ab.log).  Drain thresholds 4 / 5 / 8 / 10 lanes
-                                  // instead of 6: +2.5 / +0.7 / 0.0 / +2.7 %
-#endif
-constexpr int kNodeStepsPerVote = RT_NODE_STEPS_PER_VOTE;
 #ifndef RT_FULL_WAVES
 #define RT_FULL_WAVES 5 // waves per SIMD of the full-feature variants under the coarse schedule.  Round 2: 3 (a few dozen spilled
                         // registers, still faster than 2).  Round 4: the kernels need 119 - 125 VGPRs unconstrained (four 256-thread
@@ -1912,328 +1895,6 @@ hipError_t launch_combine(hipStream_t stream, const DevRenderParams &P, const fl
 	return hipGetLastError();
 }
 
-// ---- batch hit queries (AccelerationStructure::check_hit / check_hit_index) ----
-struct DevRayDesc {
-	float origin[3], direction[3];
-};
-struct DevHitRecord {
-	float t, point[3], error[3], normal[3], uv[2];
-	int32_t has_uv, out;
-	uint32_t material, found;
-	unsigned long long index;
-};
-static_assert(sizeof(DevHitRecord) == 72, "must match rt_hit_record");
-
-__device__ __forceinline__ void store_record(DevHitRecord &o, const Hit &h, uint32_t material, unsigned long long index, bool found)
-{
-	o.t = h.t;
-	o.point[0] = h.point.x; o.point[1] = h.point.y; o.point[2] = h.point.z;
-	o.error[0] = h.error.x; o.error[1] = h.error.y; o.error[2] = h.error.z;
-	o.normal[0] = h.normal.x; o.normal[1] = h.normal.y; o.normal[2] = h.normal.z;
-	o.uv[0] = h.uvx; o.uv[1] = h.uvy;
-	o.has_uv = h.has_uv ? 1 : 0;
-	o.out = h.out ? 1 : 0;
-	o.material = mat_handle_index(material); // (the caller's index, not the handle the kernels carry)
-	o.found = found ? 1u : 0u;
-	o.index = index;
-}
-
-template <bool PRUNE>
-__global__ __launch_bounds__(256) void check_hit_kernel(const DevScene S, const DevRayDesc *__restrict__ rays, uint64_t n,
-                                                        DevHitRecord *__restrict__ outr)
-{
-	using F = FeatFull; // batch queries serve every scene: all primitive types compiled in
-	extern __shared__ __align__(16) uint32_t lds[];
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	uint32_t *stk = lds + wave * (S.stack_depth * kStackStride) + lane;
-	// the whole worst case in LDS: the overflow branch is never taken (its base only has to be some global pointer;
-	// a literal null there sends this compiler's SimplifyCFG into a crash)
-	const StackMem SM = {S.stack_depth, 0u, reinterpret_cast<uint32_t *>(outr), lds};
-	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n)
-		return;
-	const Ray r = ray_new<F>(v3(rays[i].origin[0], rays[i].origin[1], rays[i].origin[2]),
-	                      v3(rays[i].direction[0], rays[i].direction[1], rays[i].direction[2]));
-	float t;
-	uint32_t prim;
-	trace_closest<F, PRUNE>(S, S, SM, r, stk, t, prim);
-	Hit h;
-	uint32_t m;
-	if (prim != kNoPrim) {
-		make_hit<F>(S, prim, r, t, h, m);
-		store_record(outr[i], h, m, prim, true);
-	} else {
-		make_sky_hit(S, h, m);
-		store_record(outr[i], h, m, 0xFFFFFFFFFFFFFFFFull, true);
-	}
-}
-
-template <bool PRUNE>
-__global__ __launch_bounds__(256) void check_hit_index_kernel(const DevScene S, const DevRayDesc *__restrict__ rays,
-                                                              const unsigned long long *__restrict__ object_index, uint64_t n,
-                                                              DevHitRecord *__restrict__ outr)
-{
-	using F = FeatFull; // batch queries serve every scene: all primitive types compiled in
-	extern __shared__ __align__(16) uint32_t lds[];
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	uint32_t *stk = lds + wave * (S.stack_depth * kStackStride) + lane;
-	const StackMem SM = {S.stack_depth, 0u, reinterpret_cast<uint32_t *>(outr), lds}; // see check_hit_kernel
-	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n)
-		return;
-	const Ray r = ray_new<F>(v3(rays[i].origin[0], rays[i].origin[1], rays[i].origin[2]),
-	                      v3(rays[i].direction[0], rays[i].direction[1], rays[i].direction[2]));
-	const uint32_t index = (uint32_t)object_index[i];
-	const PrimGeom g = load_prim<F>(S, index);
-	Hit h;
-	h.t = 0.0f;
-	h.point = h.error = h.normal = v3s(0.0f);
-	h.uvx = h.uvy = 0.0f;
-	h.has_uv = h.out = false;
-	uint32_t m = 0;
-	bool found = false;
-	float lt;
-	if (prim_t<F>(g, r, lt) && lt > 0.0f) {
-		if (!trace_any<F, PRUNE>(S, S, SM, r, stk, lt, index)) {
-			make_hit<F>(S, index, r, lt, h, m);
-			found = true;
-		}
-	}
-	store_record(outr[i], h, m, object_index[i], found);
-}
-
-#ifdef RT_STATS
-// ---- diagnostic build only: a register-lean TRAVERSAL-ONLY persistent kernel (tests/probes/gpu_trace_queue.py).
-// Lanes pull rays from a queue, walk the wide tree (NODE / LEAF voted as in the fine schedule), write (t, primitive) and
-// refill in place.  It holds nothing but the ray, the best hit and the stack, so it can run at up to 8 waves/SIMD: the
-// experiment behind DESIGN.md section 8.1 (what a wavefront split could give the big-tree configurations). ----
-template <int WAVES>
-__global__ __launch_bounds__(256, WAVES) void trace_queue_kernel(const DevScene S, const DevRayDesc *__restrict__ rays, uint32_t n, float2 *__restrict__ out,
-                                                                 uint32_t *__restrict__ counter, unsigned long long *__restrict__ steps_out,
-                                                                 uint32_t stack_cap, uint32_t ovf_depth, uint32_t *__restrict__ ovf)
-{
-	using F = Feat<true, true, false, false>;
-	extern __shared__ __align__(16) uint32_t lds[];
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	StackMem SM;
-	SM.cap = stack_cap;
-	SM.ovf_depth = ovf_depth;
-	SM.ovf = ovf;
-	SM.region = lds;
-	uint32_t *stk = lds + wave * (stack_cap * kStackStride) + lane;
-	enum { EMPTY = 0, NODE = 1, LEAF = 2, DONE = 3 };
-	int ph = EMPTY;
-	Ray ray;
-	ray.o = ray.d = ray.inv = ray.shear = v3s(0.0f);
-	uint32_t node = kRefDone, best_prim = kNoPrim, id = 0;
-	int sp = 0;
-	float best_t = 0.0f;
-	unsigned long long n_steps = 0;
-	uint32_t wq_next = 0, wq_end = 0;
-	auto finish = [&]() {
-		out[id] = make_float2(best_t, __uint_as_float(best_prim));
-		ph = EMPTY;
-	};
-	for (;;) {
-		const unsigned long long need = __ballot(ph == EMPTY);
-		if (need != 0ull) {
-			const uint32_t cnt = (uint32_t)__popcll(need), avail = wq_end - wq_next;
-			uint32_t base = wq_end;
-			if (avail < cnt) {
-				const int leader = __ffsll((long long)need) - 1;
-				uint32_t claimed = 0;
-				if ((int)lane == leader)
-					claimed = atomicAdd(counter, 64u);
-				base = __shfl(claimed, leader);
-			}
-			if (ph == EMPTY) {
-				const uint32_t r = (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
-				id = r < avail ? wq_next + r : base + (r - avail);
-				if (id >= n) {
-					ph = DONE;
-				} else {
-					ray = ray_new<F>(v3(rays[id].origin[0], rays[id].origin[1], rays[id].origin[2]),
-					                 v3(rays[id].direction[0], rays[id].direction[1], rays[id].direction[2]));
-					best_t = 0.0f;
-					best_prim = kNoPrim;
-					sp = 0;
-					node = S.root4_ref;
-					ph = ref_is_leaf(node) ? LEAF : NODE;
-				}
-			}
-			if (avail < cnt) {
-				wq_next = base + (cnt - avail);
-				wq_end = base + 64u;
-			} else {
-				wq_next += cnt;
-			}
-		}
-		const uint32_t c_node = (uint32_t)__popcll(__ballot(ph == NODE)), c_leaf = (uint32_t)__popcll(__ballot(ph == LEAF));
-		if (c_node + c_leaf == 0u) {
-			if (__ballot(ph == EMPTY) == 0ull)
-				break;
-			continue;
-		}
-		if (c_leaf >= kDrainLanes || c_node == 0u) {
-			if (ph == LEAF) {
-				uint32_t leaf_ref;
-				if (wide_leaf_hit(S, node, ray, leaf_ref))
-					closest_in_leaf<F>(S, ray, leaf_ref, best_t, best_prim);
-				if (sp == 0) {
-					finish();
-				} else {
-					--sp;
-					node = ovf_depth == 0u ? stack_load<false>(SM, stk, sp) : stack_load<true>(SM, stk, sp);
-					ph = ref_is_leaf(node) ? LEAF : NODE;
-				}
-			}
-		} else {
-#pragma unroll 1
-			for (int step = 0; step < kNodeStepsPerVote; ++step) {
-				if (ph == NODE) {
-					n_steps += 1;
-					if (ovf_depth == 0u)
-						node = descend4<true, false>(S, SM, ray, node, stk, sp, best_prim != kNoPrim, best_t);
-					else
-						node = descend4<true, true>(S, SM, ray, node, stk, sp, best_prim != kNoPrim, best_t);
-					if (node == kRefDone)
-						finish();
-					else if (ref_is_leaf(node))
-						ph = LEAF;
-				}
-			}
-		}
-	}
-	for (int off = 32; off > 0; off >>= 1)
-		n_steps += __shfl_down(n_steps, off);
-	if (lane == 0u)
-		atomicAdd(steps_out, n_steps);
-}
-
-hipError_t launch_trace_queue(int waves, uint32_t n_blocks, size_t lds_bytes, hipStream_t stream, const DevScene &S, const void *rays, uint32_t n, void *out,
-                              uint32_t *counter, unsigned long long *steps, uint32_t cap, uint32_t ovf_depth, uint32_t *ovf)
-{
-#define RT_TQ(W) \
-	if (waves == W) { \
-		hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(trace_queue_kernel<W>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
-		if (e_ != hipSuccess) \
-			return e_; \
-		hipLaunchKernelGGL(trace_queue_kernel<W>, dim3(n_blocks), dim3(256), lds_bytes, stream, S, static_cast<const DevRayDesc *>(rays), n, \
-		                   static_cast<float2 *>(out), counter, steps, cap, ovf_depth, ovf); \
-		return hipGetLastError(); \
-	}
-	RT_TQ(3) RT_TQ(4) RT_TQ(5) RT_TQ(6) RT_TQ(8)
-#undef RT_TQ
-	return hipErrorInvalidValue;
-}
-#endif
-
-// ---- rt_selftest_lean: the short arithmetic forms of rt_lean.h against the plain operators / rt_detmath.h, on the device.
-// Operand classes: 0 lean_div, 1 lean_div_fix (numerator may be zero / inf / NaN), 2 lean_inv, 3 lean_div3 (shared reciprocal),
-// 4 lean_sqrt, 5 lean_sincos, 6 lean_acos_dev, 7 lean_atan2, 8 ray_new (fast path and fallback against the plain operators).
-// mismatches[k] counts results whose BITS differ (two NaNs count as equal). ----
-__device__ __forceinline__ bool same_f32(float a, float b) { return __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b); }
-__device__ __forceinline__ float tame_from_bits(uint32_t u, int lo_exp, int hi_exp) // random sign and mantissa, exponent in [lo_exp, hi_exp]
-{
-	const uint32_t span = (uint32_t)(hi_exp - lo_exp + 1);
-	const uint32_t e = (uint32_t)(127 + lo_exp) + ((u >> 23) & 0xFFu) % span;
-	return __uint_as_float((u & 0x807FFFFFu) | (e << 23));
-}
-__device__ __noinline__ Ray ray_new_plain(V3 origin, V3 direction) // the plain operators, kept out of line so nothing is shared with the short form
-{
-	Ray r;
-	direction = direction / mag(direction);
-	r.o = origin;
-	r.d = direction;
-	r.inv = v3(1.0f / direction.x, 1.0f / direction.y, 1.0f / direction.z);
-	const float ax = fabsf(direction.x), ay = fabsf(direction.y), az = fabsf(direction.z);
-	const bool swap = (ax > ay && ax > az) || (ay > az);
-	const float sx = swap ? direction.z : direction.x;
-	const float sz = swap ? direction.x : direction.z;
-	r.shear = v3(-sx / sz, -direction.y / sz, 1.0f / sz);
-	return r;
-}
-__global__ __launch_bounds__(256) void selftest_lean_kernel(uint64_t n_per_thread, uint64_t seed, unsigned long long *__restrict__ mismatches)
-{
-	const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	rt_rng rng;
-	rt_rng_seed(&rng, seed, tid, 0x5E1F7E57ull);
-	unsigned long long bad[9] = {};
-	for (uint64_t it = 0; it < n_per_thread; ++it) {
-		const uint32_t u0 = rt_rng_u32(&rng), u1 = rt_rng_u32(&rng), u2 = rt_rng_u32(&rng), u3 = rt_rng_u32(&rng);
-		// tame operands at the EDGES of what the call sites guarantee as well as in the middle
-		const float d = tame_from_bits(u0, -81, 41), n = tame_from_bits(u1, -81, 41);
-		if (fabsf(n) <= fabsf(d) * 0x1p95f && fabsf(d) <= fabsf(n) * 0x1p120f) {
-			bad[0] += !same_f32(lean_div(n, d), n / d);
-			bad[1] += !same_f32(lean_div_fix(n, d), n / d);
-		}
-		const uint32_t pick = u2 & 7u; // special numerators for the fix-up form
-		const float ns = pick == 0u ? 0.0f : (pick == 1u ? -0.0f : (pick == 2u ? INFINITY : (pick == 3u ? -INFINITY : (pick == 4u ? __uint_as_float(0x7FC00000u) : n))));
-		if (pick < 5u)
-			bad[1] += !same_f32(lean_div_fix(ns, d), ns / d);
-		bad[2] += !same_f32(lean_inv(d), 1.0f / d);
-		{
-			const V3 v = v3(tame_from_bits(u1, -60, 20), tame_from_bits(u2, -60, 20), tame_from_bits(u3, -60, 20));
-			const float dd = tame_from_bits(u0, -20, 20);
-			const V3 a = lean_div3(v, dd), b = v / dd;
-			bad[3] += !(same_f32(a.x, b.x) && same_f32(a.y, b.y) && same_f32(a.z, b.z));
-			const V3 vz = v3((u3 & 1u) ? 0.0f : v.x, (u3 & 2u) ? -0.0f : v.y, v.z);
-			const V3 af = lean_div3_fix(vz, dd), bf = vz / dd;
-			bad[3] += !(same_f32(af.x, bf.x) && same_f32(af.y, bf.y) && same_f32(af.z, bf.z));
-		}
-		{
-			// square roots: the whole stated domain -- zero, [2^-96, inf], NaN, negatives -- and squares near exact roots
-			const uint32_t k = u3 & 15u;
-			float x = fabsf(tame_from_bits(u0, -96, 127));
-			if (k == 0u) x = 0.0f; else if (k == 1u) x = -0.0f; else if (k == 2u) x = INFINITY; else if (k == 3u) x = -fabsf(n);
-			else if (k == 4u) { const float r = fabsf(tame_from_bits(u1, -40, 40)); x = r * r; }
-			else if (k == 5u) x = 1.0f - (float)(u1 >> 8) * 5.9604644775390625e-08f; // 1 - r, the Lambert sampler's argument
-			else if (k == 6u) x = __uint_as_float(0x0F800000u + (u1 & 0xFFu));          // just above 2^-96
-			bad[4] += !same_f32(lean_sqrt(x), sqrtf(x));
-		}
-		{
-			const float r = (float)(u0 >> 8) * 5.9604644775390625e-08f;
-			const float ang = (u1 & 1u) ? 2.0f * kPi * r : ((u1 & 2u) ? kPi * r * (1.0f + 0x1p-20f) : (float)(int32_t)(u2 >> 9) * r - 4194304.0f * r);
-			float s_, c_;
-			lean_sincos(ang, s_, c_);
-			bad[5] += !(same_f32(s_, rt_sinf(ang)) && same_f32(c_, rt_cosf(ang)));
-		}
-		{
-			const uint32_t k = u3 & 7u;
-			float x = 2.0f * ((float)(u0 >> 8) * 5.9604644775390625e-08f) - 1.0f;
-			if (k == 0u) x = tame_from_bits(u0, -30, 1); else if (k == 1u) x = (u1 & 1u) ? 1.0f : -1.0f; else if (k == 2u) x = __uint_as_float(0x3F000000u + (u1 & 3u) - 1u);
-			else if (k == 3u) x = __uint_as_float(0x7FC00000u);
-			bad[6] += !same_f32(lean_acos_dev(x), rt_acosf(x));
-		}
-		{
-			const uint32_t k = u3 >> 28;
-			float y = tame_from_bits(u0, -30, 30), x = tame_from_bits(u1, -30, 30);
-			if (k == 0u) y = 0.0f; else if (k == 1u) x = -0.0f; else if (k == 2u) { x = 0.0f; y = -0.0f; } else if (k == 3u) y = (u2 & 1u) ? x : -x;
-			else if (k == 4u) x = INFINITY; else if (k == 5u) { x = -INFINITY; y = INFINITY; } else if (k == 6u) y = __uint_as_float(0x7FC00000u);
-			else if (k == 7u) { x = __uint_as_float(u0); y = __uint_as_float(u1); }
-			bad[7] += !same_f32(lean_atan2(y, x), rt_atan2f(y, x));
-		}
-		{
-			const uint32_t k = u3 & 15u;
-			V3 dir = v3(tame_from_bits(u0, -8, 8), tame_from_bits(u1, -8, 8), tame_from_bits(u2, -8, 8));
-			if (k == 0u) dir.x = 0.0f; else if (k == 1u) dir = v3(tame_from_bits(u0, -62, -58), tame_from_bits(u1, -8, 8), tame_from_bits(u2, -22, 21));
-			else if (k == 2u) dir = v3(tame_from_bits(u0, -70, 70), tame_from_bits(u1, -70, 70), tame_from_bits(u2, -70, 70));
-			else if (k == 3u) dir.y = -0.0f;
-			const Ray a = ray_new<FeatFull>(v3s(0.0f), dir), b = ray_new_plain(v3s(0.0f), dir);
-			bad[8] += !(same_f32(a.d.x, b.d.x) && same_f32(a.d.y, b.d.y) && same_f32(a.d.z, b.d.z) && same_f32(a.inv.x, b.inv.x) && same_f32(a.inv.y, b.inv.y) &&
-			            same_f32(a.inv.z, b.inv.z) && same_f32(a.shear.x, b.shear.x) && same_f32(a.shear.y, b.shear.y) && same_f32(a.shear.z, b.shear.z));
-		}
-	}
-	for (int k = 0; k < 9; ++k)
-		if (bad[k])
-			atomicAdd(&mismatches[k], bad[k]);
-}
-hipError_t launch_selftest_lean(hipStream_t stream, uint32_t blocks, uint64_t n_per_thread, uint64_t seed, unsigned long long *mismatches)
-{
-	hipLaunchKernelGGL(selftest_lean_kernel, dim3(blocks), dim3(256), 0, stream, n_per_thread, seed, mismatches);
-	return hipGetLastError();
-}
-
 // ---- launchers (called from rt_api.cpp) ----
 #ifdef RT_STATS
 extern "C" int rt_debug_hist(unsigned long long *out260, int reset)
@@ -2285,47 +1946,6 @@ uint32_t render_max_block_threads(int feature_set, bool fine, bool xchg)
 }
 
 // waves per SIMD the kernel's register budget is declared for (its __launch_bounds__)
-// ---- rt_selftest_pair_primary: the host's DevPairPrimary against the same terms formed on the device (one lane), word by word ----
-struct PairPrimaryCheck {
-	DevPairScene pair;
-	DevPairPrimary host;
-	float root_min[3], root_max[3], origin[3];
-};
-__global__ __launch_bounds__(64) void selftest_pair_primary_kernel(const PairPrimaryCheck c, unsigned long long *__restrict__ mismatches)
-{
-	if (threadIdx.x != 0u || blockIdx.x != 0u)
-		return;
-	DevPairPrimary d;
-	pair_primary_terms(c.pair, c.root_min, c.root_max, v3(c.origin[0], c.origin[1], c.origin[2]), d);
-	auto differ = [](float a, float b) { return __float_as_uint(a) != __float_as_uint(b) && !(a != a && b != b); }; // (NaN == NaN)
-	unsigned long long bad = d.valid != c.host.valid ? 1ull : 0ull;
-	for (int ch = 0; ch < 2; ++ch) {
-		for (int k = 0; k < 3; ++k) {
-			bad += differ(d.box[ch][0][k], c.host.box[ch][0][k]);
-			bad += differ(d.box[ch][1][k], c.host.box[ch][1][k]);
-			bad += differ(d.root[ch][k], c.host.root[ch][k]);
-		}
-		for (int k = 0; k < 4; ++k)
-			bad += differ(d.sphere[ch][k], c.host.sphere[ch][k]);
-		bad += differ(d.deltapdot[ch], c.host.deltapdot[ch]);
-	}
-	*mismatches = bad;
-}
-hipError_t launch_selftest_pair_primary(hipStream_t stream, const DevPairScene &pair, const float root_min[3], const float root_max[3], const float origin[3],
-                                        const DevPairPrimary &host_block, unsigned long long *mismatches)
-{
-	PairPrimaryCheck c;
-	c.pair = pair;
-	c.host = host_block;
-	for (int k = 0; k < 3; ++k) {
-		c.root_min[k] = root_min[k];
-		c.root_max[k] = root_max[k];
-		c.origin[k] = origin[k];
-	}
-	hipLaunchKernelGGL(selftest_pair_primary_kernel, dim3(1), dim3(64), 0, stream, c, mismatches);
-	return hipGetLastError();
-}
-
 uint32_t render_waves_per_simd(int feature_set, bool fine)
 {
 	if (feature_set == 3)
@@ -2457,45 +2077,6 @@ hipError_t launch_render(int method, bool prune, bool fine, bool sky_lds, int fe
 	A.pair = pair ? *pair : DevPairScene{};
 	A.primary = primary ? *primary : DevPairPrimary{};
 	hipLaunchKernelGGL(fn, dim3(n_blocks), dim3(block_threads ? block_threads : render_block_threads(feature_set, fine, xchg)), lds_bytes, stream, A);
-	return hipGetLastError();
-}
-
-hipError_t launch_check_hit(bool prune, hipStream_t stream, const DevScene &S, const void *rays, uint64_t n, void *out)
-{
-	const size_t lds_bytes = four_wave_stack_lds_bytes(S);
-	const uint32_t blocks = (uint32_t)((n + 255) / 256);
-	// deep trees: more than the default 64 KB of dynamic LDS per workgroup (the whole worst-case stack lives in LDS here)
-	hipError_t e = hipFuncSetAttribute(prune ? reinterpret_cast<const void *>(check_hit_kernel<true>) : reinterpret_cast<const void *>(check_hit_kernel<false>),
-	                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-	if (e != hipSuccess)
-		return e;
-	if (prune)
-		hipLaunchKernelGGL(check_hit_kernel<true>, dim3(blocks), dim3(256), lds_bytes, stream, S,
-		                   static_cast<const DevRayDesc *>(rays), n, static_cast<DevHitRecord *>(out));
-	else
-		hipLaunchKernelGGL(check_hit_kernel<false>, dim3(blocks), dim3(256), lds_bytes, stream, S,
-		                   static_cast<const DevRayDesc *>(rays), n, static_cast<DevHitRecord *>(out));
-	return hipGetLastError();
-}
-
-hipError_t launch_check_hit_index(bool prune, hipStream_t stream, const DevScene &S, const void *rays, const void *object_index,
-                                  uint64_t n, void *out)
-{
-	const size_t lds_bytes = four_wave_stack_lds_bytes(S);
-	const uint32_t blocks = (uint32_t)((n + 255) / 256);
-	hipError_t e = hipFuncSetAttribute(prune ? reinterpret_cast<const void *>(check_hit_index_kernel<true>)
-	                                         : reinterpret_cast<const void *>(check_hit_index_kernel<false>),
-	                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-	if (e != hipSuccess)
-		return e;
-	if (prune)
-		hipLaunchKernelGGL(check_hit_index_kernel<true>, dim3(blocks), dim3(256), lds_bytes, stream, S,
-		                   static_cast<const DevRayDesc *>(rays), static_cast<const unsigned long long *>(object_index), n,
-		                   static_cast<DevHitRecord *>(out));
-	else
-		hipLaunchKernelGGL(check_hit_index_kernel<false>, dim3(blocks), dim3(256), lds_bytes, stream, S,
-		                   static_cast<const DevRayDesc *>(rays), static_cast<const unsigned long long *>(object_index), n,
-		                   static_cast<DevHitRecord *>(out));
 	return hipGetLastError();
 }
 

@@ -15,15 +15,13 @@
 //     pass 2   (only lanes that drop or trim something) reads the S sums again and adds those whose rank is kept, in chunk order.
 //   Nothing synchronises: a lane touches its own column only.  S is padded to a multiple of eight with keys that rank last.
 #include "rt_robust.h"
+#include "rt_post_common.h"
 
 #include "../../include/rt_hip.h"
 
 namespace rt {
 
 namespace {
-
-// the denoiser's lum (rt_denoise.hip)
-__device__ inline float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
 
 constexpr uint32_t kNotFinite = 0xFFFFFFFFu;
 constexpr uint32_t T = kRobustBlockThreads;

@@ -1,4 +1,4 @@
-// rt_sky_selftest.h -- launch interface of the sky self-test kernel (rt_sky_selftest.hip), shared with rt_api.cpp.
+// rt_selftest.h -- launch interface of the device self-tests (rt_selftest.hip), shared with rt_api_query.cpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -6,6 +6,10 @@
 #include "rt_types.h"
 
 namespace rt {
+
+hipError_t launch_selftest_lean(hipStream_t stream, uint32_t blocks, uint64_t n_per_thread, uint64_t seed, unsigned long long *mismatches);
+hipError_t launch_selftest_pair_primary(hipStream_t stream, const DevPairScene &pair, const float root_min[3], const float root_max[3], const float origin[3],
+                                        const DevPairPrimary &host_block, unsigned long long *mismatches);
 
 struct DevSkySelftest {
 	uint64_t seed;

@@ -15,12 +15,11 @@
 //   denoise_iteration_kernel  iterations 1 .. N-1, the last one writing out
 // The denoiser kernels are launched through rt_denoise.hip's helpers; this file instantiates none of them.
 #include "rt_temporal.h"
+#include "rt_post_common.h"
 
 namespace rt {
 
 namespace {
-
-constexpr uint32_t kMaxBlocks = 65536; // grid-stride beyond this
 
 struct V {
 	float x, y, z;
@@ -32,18 +31,6 @@ __device__ inline V vmul(V a, float s) { return V{a.x * s, a.y * s, a.z * s}; }
 __device__ inline V vdiv(V a, float s) { return V{a.x / s, a.y / s, a.z / s}; }
 __device__ inline float vdot(V a, V b) { return a.x * b.x + a.y * b.y + a.z * b.z; } // (a.x*b.x + a.y*b.y) + a.z*b.z, no fma
 __device__ inline V vcross(V a, V b) { return V{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-
-__device__ inline float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
-
-__device__ inline bool finite3(float a, float b, float c) { return __builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(c); }
-
-// as rt_denoise.hip: wave w of a 256-thread workgroup takes the 8 x 8 quadrant (w & 1, w >> 1) of 16 x 16 tile `tile`
-__device__ inline void tile_pixel(uint32_t tile, uint32_t tiles_x, uint32_t &x, uint32_t &y)
-{
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	x = (tile % tiles_x) * 16u + (wave & 1u) * 8u + (lane & 7u);
-	y = (tile / tiles_x) * 16u + (wave >> 1) * 8u + (lane >> 3);
-}
 
 } // namespace
 

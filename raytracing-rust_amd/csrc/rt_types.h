@@ -203,7 +203,7 @@ struct DevScene {
 
 constexpr int kStackStride = 64; // traversal stacks in LDS: entry e of lane l lives at stack[e * kStackStride + l] (rt_intersect.h)
 // LDS of the kernels that run four waves per workgroup and keep each lane's WHOLE worst-case stack (S.stack_depth entries) there:
-// the batch hit queries (rt_render.hip) and both AOV passes.  The one copy: the launchers size their launch by it, the host
+// the batch hit queries (rt_query.hip) and both AOV passes.  The one copy: the launchers size their launch by it, the host
 // (rt_api_internal.h four_wave_traversal) decides by it which tree fits.
 constexpr uint32_t kFourWaves = 4;
 inline size_t four_wave_stack_lds_bytes(const DevScene &S) { return (size_t)kFourWaves * S.stack_depth * kStackStride * sizeof(uint32_t); }

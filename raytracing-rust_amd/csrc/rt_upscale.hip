@@ -10,6 +10,7 @@
 // lane and the output is written once.  The 4 x 4 stage and the nearest-tap stage are rare (silhouettes): they sit behind one
 // branch in rolled loops, so that the four unrolled taps of stage 1 set the register budget.
 #include "rt_upscale.h"
+#include "rt_post_common.h"
 
 #include "../../include/rt_detmath.h"
 
@@ -18,8 +19,6 @@ namespace rt {
 namespace {
 
 constexpr int kFoot = 20; // footprint side: 16 destination pixels span at most 17 values of floorf(fx), plus 1 before and 2 after
-
-__device__ inline float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
 
 // where destination pixel centre x falls in the source frame, minus the half pixel of the tap centres: fx of the header
 __device__ inline float src_coord(uint32_t x, float dst_m1, float src_m1) { return (((float)x + 0.5f) / dst_m1) * src_m1 - 0.5f; }

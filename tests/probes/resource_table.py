@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Register / spill / scratch / LDS table of every kernel in the SHIPPED librt_hip.so (gfx950 code object metadata).
+"""Register / spill / scratch / LDS table of the guarded kernels in the SHIPPED librt_hip.so (gfx950 code object metadata): the
+render kernels' bundle (rt_render.hip), the batch queries' (rt_query.hip) and the self-tests' (rt_selftest.hip).
 
 The render kernels sit on a register-allocation knife edge (a dead pointer expression cost 12 spilled
 registers and 3.5 %, an out-of-line claim loop 6 %), so the table of the default kernels is committed
@@ -68,18 +69,33 @@ def extract_bundles(so_path=LIB):
     """the kernel table (as extract) of every offload bundle in the file: each translation unit with kernels has its own"""
     data, tables, i = open(so_path, "rb").read(), [], -1
     while (i := data.find(MAGIC, i + 1)) >= 0:
-        tables.append(extract(so_path, i))
+        tables.append(extract_at(so_path, i))
     return tables
 
 
-def bundle_with(word, so_path=LIB):
-    """the table of the ONE bundle that holds kernels named *word*"""
-    found = [b for b in extract_bundles(so_path) if any(word in k for k in b)]
+def bundle_with(word, so_path=LIB, bundles=None):
+    """the table of the ONE bundle (of `bundles`: by default every bundle of the file) that holds kernels named *word*"""
+    found = [b for b in (bundles if bundles is not None else extract_bundles(so_path)) if any(word in k for k in b)]
     assert len(found) == 1, [sorted(b) for b in found]
     return found[0]
 
 
-def extract(so_path=LIB, start=0):
+GUARDED = ("render_kernel", "check_hit", "selftest_lean")  # one kernel name of each bundle the committed table describes
+
+
+def extract(so_path=LIB):
+    """the table: the union of the bundles that hold the GUARDED kernels (each translation unit is a bundle of its own)"""
+    table, bundles = {}, extract_bundles(so_path)
+    for word in GUARDED:
+        bundle = bundle_with(word, so_path, bundles)
+        twice = set(table) & set(bundle)
+        assert not twice, sorted(twice)
+        table.update(bundle)
+    return table
+
+
+def extract_at(so_path, start):
+    """the kernel table of the one bundle at or after byte `start`"""
     with tempfile.NamedTemporaryFile(suffix=".elf") as f:
         f.write(code_object(so_path, start))
         f.flush()

@@ -39,6 +39,7 @@ def assert_budget(kernels, *, waves, lds=None, workgroup=256):
 
 
 def assert_own_code_object(bundle, names, word):
-    """nothing but `names` in the bundle, and no kernel named like `word` in the render kernels' bundle"""
+    """nothing but `names` in the bundle, and no kernel named like `word` in the bundles the committed table describes (the render
+    kernels', the batch queries', the self-tests')"""
     assert set(bundle) == names, sorted(bundle)
     assert not any(word in k for k in rtab.extract(rtab.LIB))

@@ -1,7 +1,7 @@
 """The sky tables the kernels treat differently, as ONE table: test_sky_tables.py (CPU) shows through the host-only build that every
 case is in the regime it is there for, test_gpu_sky.py runs the kernels' sky code (rt_selftest_sky) and renders on it.  A case is a
 sky texture, a sampler_res and what the host must make of them: the guide width, whether the tables may be staged in LDS (the
-96 KB rule of csrc/rt_api.cpp) and whether sky_sample divides by the resolutions through verified reciprocals (recorded from
+96 KB rule of csrc/rt_api_internal.h) and whether sky_sample divides by the resolutions through verified reciprocals (recorded from
 rt_selftest_division on both axes; the CPU file asserts the record).  torch is never imported here."""
 import functools
 
@@ -78,7 +78,7 @@ VERIFIED_BELOW = 1 << 24  # resolutions the library tries to verify a reciprocal
 
 
 def table_bytes(rx, ry, guide_k):
-    """CDFs and guides: what csrc/rt_api.cpp compares with its limit for tables in LDS"""
+    """CDFs and guides: what the host (csrc/rt_api_internal.h sky_table_bytes) compares with its limit for tables in LDS"""
     return (ry * (rx + 1) + ry + 1) * 4 + (ry + 1) * guide_k
 
 
