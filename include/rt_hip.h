@@ -1081,6 +1081,83 @@ int rt_display(rt_scene *scene, const float *host_rgb, const rt_display_opts *op
                uint32_t *host_histogram);
 int rt_display_reset(rt_scene *scene);
 
+/* ---- Depth-of-field stage (csrc/rt_dof.hip): thin-lens defocus as a compositor, between the float frame and the bloom stage.  The
+ * render kernels are a pinhole, like the reference's SimpleCamera::get_ray, and stay one; this stage gives a scene file's `aperture`
+ * and `focus_dis` a meaning without shooting a ray: a W x H RGB f32 frame (FRAME layout: what rt_render, rt_denoise* and rt_upscale*
+ * write) and a W x H f32 depth plane (the depth channel of rt_render_aov or rt_render_aov_chain: the distance t along the camera
+ * ray, 0 where it left the scene) to a W x H RGB f32 frame in which every pixel is spread over a disc whose radius is its circle of
+ * confusion -- computed as a gather, with the usual occlusion rule that a blurred background does not bleed over a sharper
+ * foreground.  The exact f32 definition below is this library's own.  f32 throughout with the library's arithmetic contract: IEEE
+ * `/` and sqrtf (every division here is the plain one: none goes through a verified reciprocal), no fma, sums in the order
+ * written; fminf / fmaxf are C's (a NaN operand gives the other one).
+ * Circle of confusion, per pixel p = (x, y), with f = focus_distance and t = depth[p]:
+ *   z = t (planar_depth 0), or z = t * cosine(p) (planar_depth 1: the distance along the camera's axis, so that a wall facing the
+ *     camera is in focus as a whole).  cosine(p) = dot(n(D(u, v)), n(D(0.5f, 0.5f))) with u = (float)x / (float)(W - 1),
+ *     v = 1.0f - (float)y / (float)(H - 1) (the render's mapping at jitter 0),
+ *     D(u, v) = ((lower_left + horizontal*u) + vertical*v) - origin per component, n(d) = d / sqrtf((d.x*d.x + d.y*d.y) + d.z*d.z) per
+ *     component, dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *   p is AT INFINITY unless t is finite, t > 0 and z > 0 (a sky pixel of the AOV pass has depth 0; a NaN cosine ends here too):
+ *     k = 1, depthkey[p] = +inf, near[p] = false.
+ *   Otherwise k = fminf(fabsf(z - f) / z, FLT_MAX), depthkey[p] = z, near[p] = (z < f).
+ *   r[p] = fmaxf(0.5f, fminf(blur_scale * k, (float)max_radius)): always in [0.5, max_radius], never NaN (k is finite).
+ *   The optional CoC plane receives near[p] ? -r[p] : r[p]: negative in front of the focus plane.
+ * Gather, per output pixel p, R = max_radius; the taps are q = p + (dx, dy) for dy = -R .. R (outer), dx = -R .. R (inner).  A tap
+ *   off the frame is skipped; a tap any of whose three channels is not finite is skipped.  Otherwise
+ *     d = sqrtf((float)(dx*dx + dy*dy));  re = (depthkey[q] > depthkey[p]) ? fminf(r[q], r[p]) : r[q];
+ *     cover = fminf(fmaxf((re - d) + 0.5f, 0.0f), 1.0f);  a tap with cover == 0 contributes nothing (it is not added as a zero);
+ *     dm = re + re;  w = cover / (dm*dm);  sw = sw + w;  per channel sc = sc + w*c[q] (the product first).
+ *   All four sums start from -0, the additive identity of IEEE arithmetic (-0 + x is x for EVERY x, -0 included), so the first
+ *   covering tap enters the sums as it is.  out[p] = sc / sw per channel.  If p's own colour has a channel that is not finite,
+ *   out[p] is p's input, bytes unchanged; likewise if sw == 0 (which cannot happen for a finite p: its own tap has cover 1).
+ *   (The weight is cover over the disc's DIAMETER squared: an in-focus pixel, r = 0.5, has weight exactly 1.)
+ * Two consequences:
+ *   - blur_scale = 0: every r is 0.5, only the centre tap covers, w = 1 and (1*c)/1 = c: the output is the input bit for bit for
+ *     every finite pixel, -0, subnormals and FLT_MAX included -- and every other pixel passes through by the rule above.
+ *   - A tap with zero cover adds nothing, and cover is 0 wherever d >= re + 0.5.  A kernel MAY therefore bound its tap loops by
+ *     the largest radius in the neighbourhood it reads and still produce exactly the bytes of the loops to R.
+ * Options (64 bytes): width, height >= 1; focus_distance finite and > 0 (default 10, the loader's own `focus_dis` default);
+ *   blur_scale finite and >= 0: the blur radius in pixels of a point at infinity (default 0 = off); max_radius 1 .. 16 (default 8;
+ *   larger radii want a half-resolution far field: DESIGN.md section 20); planar_depth 0 or 1 (default 1): 1 needs a camera and
+ *   width, height >= 2; `reserved` must be zero. */
+typedef struct rt_dof_opts {
+	uint32_t width, height;
+	float focus_distance;  /* default 10 */
+	float blur_scale;      /* default 0: off */
+	uint32_t max_radius;   /* default 8 */
+	uint32_t planar_depth; /* default 1 */
+	uint32_t reserved[10];
+} rt_dof_opts;
+int rt_dof_opts_default(rt_dof_opts *out);
+/* What turns a scene file's `aperture` into a blur: the defaults, then width and height, focus_distance = focus_dist,
+ * planar_depth = 1 and blur_scale = ((aperture*0.5f) * (float)(width - 1)) / |horizontal|, |horizontal| = sqrtf((x*x + y*y) + z*z):
+ * the lens radius seen on the focus plane, in pixels (rt_camera_new scales `horizontal` by focus_dist, so the focus plane is
+ * |horizontal| wide).  `camera` must be the one made with the same focus_dist.  RT_ERR_INVALID_ARGUMENT for a NULL, an aperture
+ * that is not finite or < 0, a focus_dist that is not finite or <= 0, width or height below 2, a horizontal axis that is zero or
+ * not finite.  No GPU. */
+int rt_dof_opts_from_camera(rt_dof_opts *out, const rt_camera *camera, float aperture, float focus_dist, uint32_t width, uint32_t height);
+/* The workspace of rt_dof_device: (r, depthkey) per pixel, 16*ceil(8*W*H / 16) bytes. */
+int rt_dof_workspace_bytes(const rt_dof_opts *opts, uint64_t *bytes);
+/* Checks (the device last): RT_ERR_INVALID_ARGUMENT for a NULL scene, frame, depth, opts or output, width or height 0, an option
+ * out of its range, planar_depth 1 without a camera or with a side below 2, a workspace (device call) that is NULL or not 16-byte
+ * aligned, and ANY overlap among frame, depth, output, CoC plane and workspace -- out == rgb included: the gather reads the
+ * neighbours of the pixel it writes, so this stage does not run in place; RT_ERR_UNSUPPORTED for more than 2^31 pixels;
+ * RT_ERR_NO_DEVICE for a host-only scene.  A multi-device head runs on devices[0].  No side effects: what rt_last_kernel_ms,
+ * rt_last_launch_info and a following rt_render return is unchanged.  camera: the one the depth was rendered with, or NULL (then
+ * planar_depth must be 0).  coc: W*H floats or NULL.
+ * rt_dof_device: DEVICE buffers on the scene's GPU, asynchronous on hip_stream; two kernels; it allocates nothing and keeps no
+ *   state, so it can be captured into a graph from its first call (the camera and the options are read when it is called).  Any
+ *   4-byte alignment of the frame, the depth, the output and the CoC plane is accepted.
+ * rt_dof: HOST buffers, blocking; the scene owns the device buffers and grows them on first use and for larger frames only. */
+int rt_dof_device(rt_scene *scene, const float *d_rgb, const float *d_depth, const rt_camera *camera, const rt_dof_opts *opts,
+                  void *d_workspace, float *d_out, float *d_coc, void *hip_stream);
+int rt_dof(rt_scene *scene, const float *host_rgb, const float *host_depth, const rt_camera *camera, const rt_dof_opts *opts,
+           float *host_out, float *host_coc);
+/* Render and defocus in one blocking call with a host buffer, built from the same pieces: rt_render_device with opts, the depth
+ * channel of rt_render_aov_device over the same pass window, and the stage above with `camera` and dopts (whose width and height
+ * are ignored: the render's are used), on one stream.  out: W*H*3.  Option rules as rt_render_aov (width, height >= 2, FRAME layout,
+ * shard_count 1) and as rt_dof_device.  rt_last_kernel_ms and rt_last_launch_info afterwards describe the render. */
+int rt_render_dof(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_dof_opts *dopts, float *out);
+
 /* ---- Bloom stage (csrc/rt_bloom.hip): glare around over-range pixels, between the float frame and the display stage.  A W x H RGB
  * f32 frame (FRAME layout: what rt_render, rt_denoise* and rt_upscale* write) to a W x H RGB f32 frame: the input plus `intensity`
  * times a wide blur of its over-threshold part, so that after rt_display's tone curve an emitter still says how far above white it

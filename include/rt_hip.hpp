@@ -823,6 +823,68 @@ inline Upscaled render_upscaled(const RenderOptions &o, uint32_t src_width, uint
 	return r;
 }
 
+// The depth-of-field stage (rt_hip.h rt_dof_opts): the options a caller sets; defaults as rt_dof_opts_default.
+struct DofOptions {
+	float focus_distance = 10.0f, blur_scale = 0.0f;
+	uint32_t max_radius = 8;
+	bool planar_depth = true;
+};
+inline rt_dof_opts dof_opts(const DofOptions &d, uint32_t width, uint32_t height)
+{
+	rt_dof_opts o;
+	check(rt_dof_opts_default(&o));
+	o.width = width;
+	o.height = height;
+	o.focus_distance = d.focus_distance;
+	o.blur_scale = d.blur_scale;
+	o.max_radius = d.max_radius;
+	o.planar_depth = d.planar_depth ? 1u : 0u;
+	return o;
+}
+// A scene file's `aperture` and `focus_dis` as a blur (rt_dof_opts_from_camera); `camera` is the one made with that focus_dist.
+inline DofOptions dof_options_from_camera(const SimpleCamera &camera, float aperture, float focus_dist, uint32_t width, uint32_t height,
+                                          uint32_t max_radius = 8)
+{
+	rt_dof_opts o;
+	check(rt_dof_opts_from_camera(&o, &camera.raw(), aperture, focus_dist, width, height));
+	DofOptions d;
+	d.focus_distance = o.focus_distance;
+	d.blur_scale = o.blur_scale;
+	d.max_radius = max_radius;
+	d.planar_depth = true;
+	return d;
+}
+// A width*height*3 frame and its width*height depth plane (render_aov's) to the defocused frame; camera nullptr: planar_depth
+// must be false.  *coc (unless nullptr) receives the signed circle-of-confusion radii.
+inline std::vector<float> dof(const Bvh &bvh, const std::vector<float> &color, const std::vector<float> &depth, const SimpleCamera *camera,
+                              uint32_t width, uint32_t height, const DofOptions &d = DofOptions(), std::vector<float> *coc = nullptr)
+{
+	const rt_dof_opts o = dof_opts(d, width, height);
+	const size_t n = (size_t)width * height;
+	std::vector<float> out(n * 3);
+	if (coc)
+		coc->resize(n);
+	check(rt_dof(bvh.raw(), color.data(), depth.data(), camera ? &camera->raw() : nullptr, &o, out.data(), coc ? coc->data() : nullptr));
+	return out;
+}
+// Render, take the depth of the same passes and defocus, in one call (rt_render_dof).
+inline std::vector<float> render_dof(const RenderOptions &o, const SimpleCamera &camera, const Bvh &bvh, const DofOptions &d,
+                                     uint64_t seed = 1, uint64_t sample_begin = 0)
+{
+	rt_render_opts opts;
+	rt_render_opts_default(&opts);
+	opts.width = o.width;
+	opts.height = o.height;
+	opts.samples_per_pixel = o.samples_per_pixel;
+	opts.render_method = static_cast<int32_t>(o.render_method);
+	opts.sample_begin = sample_begin;
+	opts.seed = seed;
+	const rt_dof_opts dopts = dof_opts(d, 0, 0); // (the frame size comes from opts)
+	std::vector<float> out((size_t)o.width * o.height * 3);
+	check(rt_render_dof(bvh.raw(), &camera.raw(), &opts, &dopts, out.data()));
+	return out;
+}
+
 struct Presentation { // what render_tui keeps: the mean image and the ray total (src/main.rs:160-173)
 	SamplerProgress sampler_progress;
 	Presentation(uint64_t pixel_num) : sampler_progress(pixel_num, 3) {}

@@ -478,6 +478,22 @@ BLOOM_OPTIONS = tuple(n for n, _ in BloomOpts._fields_ if n not in ("width", "he
 BLOOM_MAX_LEVELS = 12
 
 
+class DofOpts(C.Structure):  # rt_dof_opts
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("focus_distance", C.c_float),
+        ("blur_scale", C.c_float),
+        ("max_radius", C.c_uint32),
+        ("planar_depth", C.c_uint32),
+        ("reserved", C.c_uint32 * 10),
+    ]
+
+
+DOF_OPTIONS = tuple(n for n, _ in DofOpts._fields_ if n not in ("width", "height", "reserved"))
+DOF_MAX_RADIUS = 16
+
+
 class UpscaleOpts(C.Structure):  # rt_upscale_opts
     _fields_ = [
         ("src_width", C.c_uint32),
@@ -540,6 +556,7 @@ EXPECTED_SIZES = {
     "rt_display_opts": (DisplayOpts, 104),
     "rt_display_state": (DisplayState, 16),
     "rt_bloom_opts": (BloomOpts, 64),
+    "rt_dof_opts": (DofOpts, 64),
     "rt_upscale_opts": (UpscaleOpts, 56),
     "rt_upscale_inputs": (UpscaleInputs, 56),
 }
@@ -636,6 +653,12 @@ EXPORTED_SYMBOLS = [
     "rt_bloom_workspace_bytes",
     "rt_bloom_device",
     "rt_bloom",
+    "rt_dof_opts_default",
+    "rt_dof_opts_from_camera",
+    "rt_dof_workspace_bytes",
+    "rt_dof_device",
+    "rt_dof",
+    "rt_render_dof",
     "rt_upscale_opts_default",
     "rt_upscale_device",
     "rt_upscale",

@@ -514,6 +514,8 @@ void rt_scene_destroy(rt_scene *s)
 		(void)hipFree(s->d_noise);
 	if (s->d_bloom)
 		(void)hipFree(s->d_bloom);
+	if (s->d_dof)
+		(void)hipFree(s->d_dof);
 	if (s->d_stack_ovf)
 		(void)hipFree(s->d_stack_ovf);
 	for (int b = 0; b < 2; ++b) {

@@ -112,6 +112,8 @@ struct rt_scene {
 	size_t d_noise_bytes = 0;
 	char *d_bloom = nullptr;               // rt_bloom: state, workspace, input and output, grown for larger frames
 	size_t d_bloom_bytes = 0;
+	char *d_dof = nullptr;                 // rt_dof / rt_render_dof: workspace, output, frame, depth and CoC plane, grown for larger frames
+	size_t d_dof_bytes = 0;
 };
 
 // sample_split = 0 (automatic), resolved (rt_api.cpp); the noise estimates halve it until it divides the passes (rt_api_post.cpp)

@@ -1,6 +1,6 @@
 // rt_api_post.cpp -- the host side of the post-processing stages of librt_hip.so (include/rt_hip.h): first-hit and specular-chain
-// AOV buffers, ID mattes, ambient occlusion, the A-Trous denoiser, noise estimates, firefly-robust frames, temporal accumulation, the bloom and display stages and AOV-guided upscaling.  Each stage has its kernels in a file of
-// its own (rt_aov.hip, rt_aov_chain.hip, rt_matte.hip, rt_ao.hip, rt_denoise.hip, rt_noise.hip, rt_robust.hip, rt_temporal.hip, rt_bloom.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
+// AOV buffers, ID mattes, ambient occlusion, the A-Trous denoiser, noise estimates, firefly-robust frames, temporal accumulation, the depth-of-field, bloom and display stages and AOV-guided upscaling.  Each stage has its kernels in a file of
+// its own (rt_aov.hip, rt_aov_chain.hip, rt_matte.hip, rt_ao.hip, rt_denoise.hip, rt_noise.hip, rt_robust.hip, rt_temporal.hip, rt_dof.hip, rt_bloom.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
 // and the blocking wrappers that stage host buffers through scene-owned device memory (Staging, rt_api_internal.h).
 // Every check function ends with the device (need_device), so that a host-only scene reports bad arguments as such.
 #include <hip/hip_runtime.h>
@@ -21,6 +21,7 @@
 #include "rt_robust.h"
 #include "rt_temporal.h"
 #include "rt_bloom.h"
+#include "rt_dof.h"
 #include "rt_display.h"
 #include "rt_upscale.h"
 
@@ -1749,6 +1750,211 @@ int rt_display_reset(rt_scene *s)
 		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
 	s->display_has_state = false;
 	return RT_OK;
+}
+
+} // extern "C"
+
+// ---- depth-of-field stage: circle of confusion from depth, occlusion-aware disc gather (rt_dof.hip) ----
+// the options for a frame of w x h (rt_render_dof takes the size from the render); with_camera: one was given
+static int dof_opts_check(const rt_dof_opts *o, uint64_t w, uint64_t h, bool with_camera)
+{
+	if (int rc = frame_sides("dof: ", w, h, 1); rc != RT_OK)
+		return rc;
+	if (!finite_f(o->focus_distance) || !(o->focus_distance > 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "dof: focus_distance must be finite and > 0");
+	if (!finite_f(o->blur_scale) || !(o->blur_scale >= 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "dof: blur_scale must be finite and >= 0");
+	if (o->max_radius < 1u || o->max_radius > kDofMaxRadius)
+		return fail(RT_ERR_INVALID_ARGUMENT, "dof: max_radius must be in 1..16");
+	if (o->planar_depth > 1u)
+		return fail(RT_ERR_INVALID_ARGUMENT, "dof: planar_depth must be 0 or 1");
+	if (o->planar_depth == 1u && !with_camera)
+		return fail(RT_ERR_INVALID_ARGUMENT, "dof: planar_depth 1 needs a camera");
+	if (o->planar_depth == 1u && (w < 2 || h < 2))
+		return fail(RT_ERR_INVALID_ARGUMENT, "dof: planar_depth 1 needs width and height >= 2 (u and v divide by W-1 and H-1)");
+	for (uint32_t r : o->reserved)
+		if (r != 0u)
+			return fail(RT_ERR_INVALID_ARGUMENT, "dof: reserved must be zero");
+	uint64_t n = 0;
+	return frame_pixels("dof: ", w, h, 1, &n);
+}
+
+// argument checks of rt_dof(_device), the device last; ws is checked for the device call only
+static int dof_check(const rt_scene *s, const float *rgb, const float *depth, const rt_camera *camera, const rt_dof_opts *o, const void *ws,
+                     const float *out, const float *coc, bool device)
+{
+	if (!s || !rgb || !depth || !o || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	int rc = dof_opts_check(o, o->width, o->height, camera != nullptr);
+	if (rc != RT_OK)
+		return rc;
+	const uint64_t n = (uint64_t)o->width * o->height;
+	if (device && (!ws || reinterpret_cast<uintptr_t>(ws) % 16u != 0u))
+		return fail(RT_ERR_INVALID_ARGUMENT, "dof: the workspace must not be NULL and must be 16-byte aligned");
+	// every pair of buffers: the gather reads the neighbours of the pixel it writes, so nothing may be shared, out == rgb included
+	const void *buf[5] = {out, coc, device ? ws : nullptr, rgb, depth};
+	const uint64_t bytes[5] = {12 * n, 4 * n, dof_workspace_bytes(n), 12 * n, 4 * n};
+	rc = check_disjoint("dof: two buffers overlap (in place is not supported: the gather reads neighbours)", buf, bytes, 5, 5);
+	return rc == RT_OK ? need_device(s) : rc;
+}
+
+static DevDofParams dof_params(const rt_dof_opts *o, uint64_t w, uint64_t h, const rt_camera *camera, const float *rgb, const float *depth,
+                               void *ws, float *out, float *coc)
+{
+	DevDofParams P;
+	std::memset(&P, 0, sizeof P);
+	P.width = (uint32_t)w;
+	P.height = (uint32_t)h;
+	P.focus_distance = o->focus_distance;
+	P.blur_scale = o->blur_scale;
+	P.max_radius = o->max_radius;
+	P.planar = o->planar_depth;
+	if (camera)
+		std::memcpy(P.cam, camera, sizeof P.cam); // origin, lower_left, horizontal, vertical
+	P.rgb = rgb;
+	P.depth = depth;
+	P.ws = static_cast<float2 *>(ws);
+	P.out = out;
+	P.coc = coc;
+	return P;
+}
+
+// the scene's buffer for a frame of n pixels: workspace, output, CoC plane, frame, depth, every part 16-byte aligned
+struct DofFrames {
+	char *ws;
+	float *out, *coc, *rgb, *depth;
+};
+static int dof_frames(rt_scene *s, uint64_t n, DofFrames *F)
+{
+	auto up16 = [](uint64_t b) { return (b + 15u) / 16u * 16u; };
+	const uint64_t off_out = dof_workspace_bytes(n), off_coc = off_out + up16(12 * n), off_rgb = off_coc + up16(4 * n),
+	               off_depth = off_rgb + up16(12 * n);
+	const int rc = grow_device_buffer(s->d_dof, s->d_dof_bytes, (size_t)(off_depth + 4 * n));
+	if (rc != RT_OK)
+		return rc;
+	char *base = s->d_dof;
+	*F = DofFrames{base, reinterpret_cast<float *>(base + off_out), reinterpret_cast<float *>(base + off_coc),
+	               reinterpret_cast<float *>(base + off_rgb), reinterpret_cast<float *>(base + off_depth)};
+	return RT_OK;
+}
+
+extern "C" {
+
+int rt_dof_opts_default(rt_dof_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	out->focus_distance = 10.0f;
+	out->blur_scale = 0.0f;
+	out->max_radius = 8;
+	out->planar_depth = 1;
+	return RT_OK;
+}
+
+int rt_dof_opts_from_camera(rt_dof_opts *out, const rt_camera *camera, float aperture, float focus_dist, uint32_t width, uint32_t height)
+{
+	if (!out || !camera)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (!finite_f(aperture) || !(aperture >= 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "dof: aperture must be finite and >= 0");
+	if (!finite_f(focus_dist) || !(focus_dist > 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "dof: focus_dist must be finite and > 0");
+	if (width < 2u || height < 2u)
+		return fail(RT_ERR_INVALID_ARGUMENT, "dof: width and height must be >= 2 (u and v divide by W-1 and H-1)");
+	const float *hz = camera->horizontal;
+	const float len = std::sqrt((hz[0] * hz[0] + hz[1] * hz[1]) + hz[2] * hz[2]);
+	const float scale = ((aperture * 0.5f) * (float)(width - 1u)) / len;
+	if (!finite_f(scale))
+		return fail(RT_ERR_INVALID_ARGUMENT, "dof: the camera's horizontal axis must be finite and not zero");
+	rt_dof_opts_default(out);
+	out->width = width;
+	out->height = height;
+	out->focus_distance = focus_dist;
+	out->blur_scale = scale;
+	out->planar_depth = 1;
+	return RT_OK;
+}
+
+int rt_dof_workspace_bytes(const rt_dof_opts *o, uint64_t *bytes)
+{
+	if (!o || !bytes)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	uint64_t n = 0;
+	const int rc = frame_pixels("dof: ", o->width, o->height, 1, &n);
+	if (rc == RT_OK)
+		*bytes = dof_workspace_bytes(n);
+	return rc;
+}
+
+int rt_dof_device(rt_scene *s, const float *d_rgb, const float *d_depth, const rt_camera *camera, const rt_dof_opts *o, void *d_workspace,
+                  float *d_out, float *d_coc, void *hip_stream)
+{
+	int rc = dof_check(s, d_rgb, d_depth, camera, o, d_workspace, d_out, d_coc, true);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device)); // a multi-device head runs on devices[0]
+	HIP_TRY(launch_dof(static_cast<hipStream_t>(hip_stream), dof_params(o, o->width, o->height, camera, d_rgb, d_depth, d_workspace, d_out, d_coc)));
+	return RT_OK;
+}
+
+int rt_dof(rt_scene *s, const float *host_rgb, const float *host_depth, const rt_camera *camera, const rt_dof_opts *o, float *host_out,
+           float *host_coc)
+{
+	int rc = dof_check(s, host_rgb, host_depth, camera, o, nullptr, host_out, host_coc, false);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	const uint64_t n = (uint64_t)o->width * o->height;
+	DofFrames F;
+	rc = dof_frames(s, n, &F);
+	if (rc != RT_OK)
+		return rc;
+	Staging st{s};
+	st.to_device(F.rgb, host_rgb, 12 * n);
+	st.to_device(F.depth, host_depth, 4 * n);
+	if (!st.ok())
+		return st.finish("dof upload");
+	st.rc = rt_dof_device(s, F.rgb, F.depth, camera, o, F.ws, F.out, host_coc ? F.coc : nullptr, s->stream);
+	st.download(host_out, F.out, 12 * n);
+	st.download(host_coc, F.coc, 4 * n);
+	return st.finish("dof");
+}
+
+int rt_render_dof(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_dof_opts *dopts, float *out)
+{
+	if (!s || !camera || !o || !dopts || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	int rc = dof_opts_check(dopts, o->width, o->height, true);
+	if (rc == RT_OK)
+		rc = aov_opts_check(o);
+	if (rc != RT_OK)
+		return rc;
+	if (o->render_method != RT_METHOD_NAIVE && o->render_method != RT_METHOD_MIS)
+		return fail(RT_ERR_INVALID_ARGUMENT, "unknown render method");
+	rc = need_device(s);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	const uint64_t n = o->width * o->height;
+	DofFrames F;
+	rc = dof_frames(s, n, &F);
+	if (rc != RT_OK)
+		return rc;
+	Staging st{s};
+	st.rc = rt_render_device(s, camera, o, F.rgb, nullptr, s->stream);
+	if (st.ok())
+		st.e = hipSetDevice(s->device);
+	if (st.ok()) {
+		rt_aov_buffers aov;
+		std::memset(&aov, 0, sizeof aov);
+		aov.depth = F.depth;
+		st.rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
+	}
+	if (st.ok())
+		st.e = launch_dof(s->stream, dof_params(dopts, o->width, o->height, camera, F.rgb, F.depth, F.ws, F.out, nullptr));
+	st.download(out, F.out, 12 * n);
+	return st.finish("render_dof");
 }
 
 } // extern "C"

@@ -329,7 +329,7 @@ void make_cdf(const float *values, uint64_t n, float *cdf)
 void camera_new(rt_camera *out, const float origin_[3], const float lookat_[3], const float vup_[3], float fov,
                 float aspect_ratio, float aperture, float focus_dist)
 {
-	(void)aperture; // stored as lens_radius and never read (camera.rs:51,57-63)
+	(void)aperture; // stored as lens_radius and never read (camera.rs:51,57-63): the rays are a pinhole's; rt_dof_opts_from_camera turns it into a blur
 	const V3 origin = v3(origin_[0], origin_[1], origin_[2]);
 	const V3 lookat = v3(lookat_[0], lookat_[1], lookat_[2]);
 	const V3 vup = v3(vup_[0], vup_[1], vup_[2]);

@@ -762,6 +762,39 @@ class HipScene:
         _check(lib().rt_bloom_device(self._h, _dp(d_rgb), C.byref(opts), C.c_void_p(int(d_state) or None),
                                      C.c_void_p(int(d_workspace) or None), _dp(d_out), C.c_void_p(stream)))
 
+    # ---- depth-of-field stage: depth-driven disc blur, ahead of the bloom stage (rt_dof) ----
+    def dof(self, image, depth, camera=None, coc=False, **opts):
+        """rt_dof: an (H, W, 3) f32 frame and its (H, W) depth plane (render_aov's "depth") to the defocused (H, W, 3) frame.
+        camera: the abi.Camera the depth was rendered with, or None (then planar_depth must be 0).  coc=True returns (out, the
+        (H, W) signed circle-of-confusion radii).  Keyword options: dof_opts'.  Semantics: include/rt_hip.h rt_dof_opts."""
+        a = np.ascontiguousarray(image, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"image must be (H, W, 3), got {a.shape}")
+        h, w = a.shape[:2]
+        z = np.ascontiguousarray(depth, dtype=np.float32)
+        if z.shape != (h, w):
+            raise ValueError(f"depth must be {(h, w)}, got {z.shape}")
+        o = dof_opts(w, h, **opts)
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        radii = np.zeros((h, w), dtype=np.float32) if coc else None
+        _check(lib().rt_dof(self._h, _p(a, C.c_float), _p(z, C.c_float), C.byref(camera) if camera is not None else None,
+                            C.byref(o), _p(out, C.c_float), _p(radii, C.c_float) if coc else None))
+        return (out, radii) if coc else out
+
+    def dof_device(self, d_rgb, d_depth, camera, opts, d_workspace, d_out, d_coc=0, stream=0):
+        """rt_dof_device: asynchronous, DEVICE buffers of the scene's GPU, no state.  d_rgb, d_out: W*H*3 f32 (disjoint); d_depth:
+        W*H f32; d_coc: W*H f32 or 0; d_workspace: dof_workspace_bytes(opts) bytes, 16-byte aligned; camera: abi.Camera or None;
+        opts: abi.DofOpts."""
+        _check(lib().rt_dof_device(self._h, _dp(d_rgb), _dp(d_depth), C.byref(camera) if camera is not None else None,
+                                   C.byref(opts), C.c_void_p(int(d_workspace) or None), _dp(d_out), _dp(d_coc), C.c_void_p(stream)))
+
+    def render_dof(self, camera, opts, dopts):
+        """rt_render_dof: rt_render, the depth of the same passes and rt_dof in one call; dopts: abi.DofOpts (its sizes are
+        ignored), e.g. dof_opts_from_camera's.  Returns the defocused (H, W, 3) frame."""
+        out = np.zeros((int(opts.height), int(opts.width), 3), dtype=np.float32)
+        _check(lib().rt_render_dof(self._h, C.byref(camera), C.byref(opts), C.byref(dopts), _p(out, C.c_float)))
+        return out
+
     # ---- AOV-guided upscaling (rt_upscale): a source-size frame to the destination size ----
     def upscale(self, color, src=None, dst=None, stage=False, **opts):
         """rt_upscale: an (h, w, 3) f32 frame to (H, W, 3), guided by the albedo / normal (.., 3) and depth of `src` (at h x w) and
@@ -1141,6 +1174,38 @@ def bloom_workspace_bytes(opts):
     """rt_bloom_workspace_bytes: the workspace rt_bloom_device needs for opts' frame size and levels."""
     n = C.c_uint64()
     _check(lib().rt_bloom_workspace_bytes(C.byref(opts), C.byref(n)))
+    return n.value
+
+
+def dof_opts(width, height, **kw):
+    """rt_dof_opts_default with the frame size and any of abi.DOF_OPTIONS set."""
+    o = abi.DofOpts()
+    _check(lib().rt_dof_opts_default(C.byref(o)))
+    o.width, o.height = int(width), int(height)
+    for k, v in kw.items():
+        if k not in abi.DOF_OPTIONS:
+            raise ValueError(f"unknown dof option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def dof_opts_from_camera(camera, aperture, focus_dist, width, height, **kw):
+    """rt_dof_opts_from_camera: a scene file's aperture and focus_dis as the blur of `camera` (made with that focus_dist) at
+    width x height; then any of abi.DOF_OPTIONS set (max_radius, say)."""
+    o = abi.DofOpts()
+    _check(lib().rt_dof_opts_from_camera(C.byref(o), C.byref(camera), C.c_float(aperture), C.c_float(focus_dist),
+                                         C.c_uint32(int(width)), C.c_uint32(int(height))))
+    for k, v in kw.items():
+        if k not in abi.DOF_OPTIONS:
+            raise ValueError(f"unknown dof option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def dof_workspace_bytes(opts):
+    """rt_dof_workspace_bytes: the workspace rt_dof_device needs for opts' frame size."""
+    n = C.c_uint64()
+    _check(lib().rt_dof_workspace_bytes(C.byref(opts), C.byref(n)))
     return n.value
 
 
