@@ -10,6 +10,7 @@
 
 #include "../../include/rt_hip.h"
 #include "rt_build.h"
+#include "rt_layout.h"
 #include "rt_types.h"
 
 // the text behind rt_last_error(): ONE per thread for the whole library (defined in rt_api.cpp)
@@ -30,6 +31,13 @@ inline int hip_fail(hipError_t e, const char *what)
 		hipError_t e_ = (expr);             \
 		if (e_ != hipSuccess)               \
 			return hip_fail(e_, #expr);     \
+	} while (0)
+// the same for a call that returns an rt status (its message is set already)
+#define RT_TRY(expr)            \
+	do {                        \
+		const int rc_ = (expr); \
+		if (rc_ != RT_OK)       \
+			return rc_;         \
 	} while (0)
 
 // the pruned walk above this many primitives, the exhaustive one up to it (measured: see the crossovers in rt_api.cpp)
@@ -108,7 +116,7 @@ struct rt_scene {
 	size_t d_display_bytes = 0;
 	uint32_t display_w = 0, display_h = 0; // the frame size of the last successful call
 	bool display_has_state = false;        // false: the next rt_display starts from a zero state
-	char *d_noise = nullptr;               // rt_render_noise & co.: the batch state (16 + 20 bytes per pixel), then what the blocking calls stage
+	char *d_noise = nullptr;               // rt_render_noise & co.: the batch state (noise_state, rt_api_post.cpp), then what the blocking calls stage
 	size_t d_noise_bytes = 0;
 	char *d_bloom = nullptr;               // rt_bloom: state, workspace, input and output, grown for larger frames
 	size_t d_bloom_bytes = 0;
@@ -236,42 +244,36 @@ template <class T> static int grow_device_buffer(T *&p, size_t &count, size_t ne
 	return RT_OK;
 }
 
-// The copies and the status of one blocking entry point on s->stream.  Optional channels (host pointer or NULL, a count of
-// 4-byte elements) are laid out one after another behind a prefix the caller owns; copies are skipped once anything has
-// failed; finish() always drains the stream.  Which error wins: a non-OK `rc` (set by the caller from the _device call, its
-// message kept), else the first HIP error in `e`, else the synchronise error.
+// a scene-owned byte buffer carved by `L` (rt_layout.h): the one way such a buffer gets its size, and L its base
+static int grow_device_buffer(char *&p, size_t &bytes, rt::Layout &L)
+{
+	if (L.overflowed)
+		return fail(RT_ERR_UNSUPPORTED, "internal: a buffer layout of more parts than rt::Layout holds");
+	const int rc = grow_device_buffer(p, bytes, (size_t)L.total());
+	L.base = p;
+	return rc;
+}
+
+// The copies and the status of one blocking entry point on s->stream.  Copies are skipped for a NULL (optional) side and once
+// anything has failed; finish() always drains the stream.  Which error wins: a non-OK `rc` (set by the caller from the _device
+// call, its message kept), else the first HIP error in `e`, else the synchronise error.  Where the device side of a copy is a
+// part of a carved buffer, put / get take it as (layout, part): the part's size is the copy's.
 struct Staging {
 	rt_scene *s;
-	size_t total = 0; // 4-byte elements laid out so far (construct with the prefix)
 	int rc = RT_OK;
 	hipError_t e = hipSuccess;
-	int n = 0;
-	const void *host[8];
-	size_t offset[8], count[8];
 
 	bool ok() const { return rc == RT_OK && e == hipSuccess; }
-	void add(const void *h, size_t elements)
-	{
-		host[n] = h;
-		offset[n] = total;
-		count[n++] = elements;
-		total += h ? elements : 0;
-	}
-	// channel c inside the allocation at `base`; NULL when the caller did not give it
-	template <class T = float> T *at(char *base, int c) const { return host[c] ? reinterpret_cast<T *>(base + 4 * offset[c]) : nullptr; }
-	void copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) // skipped for a NULL (optional) host side
+	void copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind)
 	{
 		if (dst && src && ok())
 			e = hipMemcpyAsync(dst, src, bytes, kind, s->stream);
 	}
 	void to_device(void *d, const void *h, size_t bytes) { copy(d, h, bytes, hipMemcpyHostToDevice); }
 	void download(void *h, const void *d, size_t bytes) { copy(h, d, bytes, hipMemcpyDeviceToHost); }
-	bool upload(char *base) // every channel given
-	{
-		for (int c = 0; c < n; ++c)
-			to_device(at<char>(base, c), host[c], 4 * count[c]);
-		return ok();
-	}
+	// (always inlined: the library exports no symbol of its host plumbing)
+	template <class T> __attribute__((always_inline)) void put(const rt::Layout &L, rt::Layout::Part<T> p, const void *h) { to_device(L.at(p), h, L.size_of(p)); }
+	template <class T> __attribute__((always_inline)) void get(void *h, const rt::Layout &L, rt::Layout::Part<T> p) { download(h, L.at(p), L.size_of(p)); }
 	int finish(const char *what)
 	{
 		const hipError_t e_sync = hipStreamSynchronize(s->stream);

@@ -1,7 +1,9 @@
 // rt_api_post.cpp -- the host side of the post-processing stages of librt_hip.so (include/rt_hip.h): first-hit and specular-chain
 // AOV buffers, ID mattes, ambient occlusion, the A-Trous denoiser, noise estimates, firefly-robust frames, temporal accumulation, the depth-of-field, bloom and display stages and AOV-guided upscaling.  Each stage has its kernels in a file of
 // its own (rt_aov.hip, rt_aov_chain.hip, rt_matte.hip, rt_ao.hip, rt_denoise.hip, rt_noise.hip, rt_robust.hip, rt_temporal.hip, rt_dof.hip, rt_bloom.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
-// and the blocking wrappers that stage host buffers through scene-owned device memory (Staging, rt_api_internal.h).
+// and the blocking wrappers that stage host buffers through scene-owned device memory: each buffer is carved by a Layout (rt_layout.h),
+// so its size and every pointer into it come from one description; Staging (rt_api_internal.h) carries the copies and the status.
+// The steps the one-call composites share: enqueue_guides, enqueue_denoise, render_denoised_guided.
 // Every check function ends with the device (need_device), so that a host-only scene reports bad arguments as such.
 #include <hip/hip_runtime.h>
 
@@ -109,30 +111,38 @@ int rt_render_aov_device(rt_scene *s, const rt_camera *camera, const rt_render_o
 	return RT_OK;
 }
 
-int rt_render_aov(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *out)
+// Both blocking AOV entry points once their arguments are checked (`c` NULL: the first-hit pass): one device allocation per call
+// for the requested channels, in rt_aov_chain_buffers order; 4-byte elements throughout
+static int render_aov_staged(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_chain_opts *c,
+                             const rt_aov_buffers &a, float *bounces, const char *what)
 {
-	uint32_t mask = 0;
-	int rc = aov_check(s, camera, o, out, &mask);
-	if (rc != RT_OK)
-		return rc;
 	HIP_TRY(hipSetDevice(s->device));
-	// one device allocation per call for the requested channels, in rt_aov_buffers order; 4-byte elements throughout
-	const size_t n_px = (size_t)(o->width * o->height);
-	Staging st{s};
-	void *host[6] = {out->albedo, out->normal, out->depth, out->coverage, out->primitive, out->material};
-	for (int c = 0; c < 6; ++c)
-		st.add(host[c], (c < 2 ? 3 : 1) * n_px);
+	const uint64_t n_px = o->width * o->height;
+	void *host[7] = {a.albedo, a.normal, a.depth, a.coverage, a.primitive, a.material, bounces};
+	Layout L;
+	Layout::Part<float> ch[7];
+	for (int k = 0; k < 7; ++k)
+		ch[k] = L.optional<float>(host[k], (k < 2 ? 3 : 1) * n_px);
 	char *d = nullptr;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), st.total * 4));
-	const rt_aov_buffers dev_out = {st.at(d, 0), st.at(d, 1), st.at(d, 2), st.at(d, 3), st.at<uint32_t>(d, 4), st.at<uint32_t>(d, 5)};
-	st.rc = rt_render_aov_device(s, camera, o, &dev_out, s->stream);
-	for (int c = 0; c < 6; ++c)
-		st.download(host[c], st.at(d, c), 4 * st.count[c]);
-	rc = st.finish("render_aov");
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), L.total()));
+	L.base = d;
+	auto ids = [&](int k) { return reinterpret_cast<uint32_t *>(L.at(ch[k])); };
+	const rt_aov_chain_buffers dev_out = {{L.at(ch[0]), L.at(ch[1]), L.at(ch[2]), L.at(ch[3]), ids(4), ids(5)}, L.at(ch[6])};
+	Staging st{s};
+	st.rc = c ? rt_render_aov_chain_device(s, camera, o, c, &dev_out, s->stream) : rt_render_aov_device(s, camera, o, &dev_out.aov, s->stream);
+	for (int k = 0; k < 7; ++k)
+		st.get(host[k], L, ch[k]);
+	const int rc = st.finish(what);
 	(void)hipFree(d);
 	return rc;
 }
 
+int rt_render_aov(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *out)
+{
+	uint32_t mask = 0;
+	const int rc = aov_check(s, camera, o, out, &mask);
+	return rc == RT_OK ? render_aov_staged(s, camera, o, nullptr, *out, nullptr, "render_aov") : rc;
+}
 
 // ---- specular-chain AOV buffers (rt_aov_chain.hip) ----
 int rt_aov_chain_opts_default(rt_aov_chain_opts *out)
@@ -194,25 +204,8 @@ int rt_render_aov_chain(rt_scene *s, const rt_camera *camera, const rt_render_op
                         const rt_aov_chain_buffers *out)
 {
 	uint32_t mask = 0;
-	int rc = aov_chain_check(s, camera, o, c, out, &mask);
-	if (rc != RT_OK)
-		return rc;
-	HIP_TRY(hipSetDevice(s->device));
-	// one device allocation per call for the requested channels, in rt_aov_chain_buffers order; 4-byte elements throughout
-	const size_t n_px = (size_t)(o->width * o->height);
-	Staging st{s};
-	void *host[7] = {out->aov.albedo, out->aov.normal, out->aov.depth, out->aov.coverage, out->aov.primitive, out->aov.material, out->bounces};
-	for (int ch = 0; ch < 7; ++ch)
-		st.add(host[ch], (ch < 2 ? 3 : 1) * n_px);
-	char *d = nullptr;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), st.total * 4));
-	const rt_aov_chain_buffers dev_out = {{st.at(d, 0), st.at(d, 1), st.at(d, 2), st.at(d, 3), st.at<uint32_t>(d, 4), st.at<uint32_t>(d, 5)}, st.at(d, 6)};
-	st.rc = rt_render_aov_chain_device(s, camera, o, c, &dev_out, s->stream);
-	for (int ch = 0; ch < 7; ++ch)
-		st.download(host[ch], st.at(d, ch), 4 * st.count[ch]);
-	rc = st.finish("render_aov_chain");
-	(void)hipFree(d);
-	return rc;
+	const int rc = aov_chain_check(s, camera, o, c, out, &mask);
+	return rc == RT_OK ? render_aov_staged(s, camera, o, c, out->aov, out->bounces, "render_aov_chain") : rc;
 }
 
 } // extern "C"
@@ -315,20 +308,17 @@ int rt_render_matte(rt_scene *s, const rt_camera *camera, const rt_render_opts *
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
 	// ids, coverage, then the residual if asked for; 4-byte elements throughout
-	const size_t n = (size_t)(o->width * o->height);
+	const uint64_t n = o->width * o->height;
+	Layout L;
+	const auto p_ids = L.add<uint32_t>(m->layers * n);
+	const auto p_coverage = L.add<float>(m->layers * n), p_residual = L.optional<float>(out->residual, n);
+	RT_TRY(grow_device_buffer(s->d_denoise, s->d_denoise_bytes, L)); // shared with rt_denoise / rt_render_denoised
+	const rt_matte_buffers d_out = {L.at(p_ids), L.at(p_coverage), L.at(p_residual)};
 	Staging st{s};
-	st.add(out->ids, m->layers * n);
-	st.add(out->coverage, m->layers * n);
-	st.add(out->residual, n);
-	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, st.total * 4); // shared with rt_denoise / rt_render_denoised
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_denoise;
-	const rt_matte_buffers d_out = {st.at<uint32_t>(base, 0), st.at(base, 1), st.at(base, 2)};
 	st.rc = rt_render_matte_device(s, camera, o, m, &d_out, s->stream);
-	st.download(out->ids, d_out.ids, 4 * st.count[0]);
-	st.download(out->coverage, d_out.coverage, 4 * st.count[1]);
-	st.download(out->residual, d_out.residual, 4 * st.count[2]);
+	st.get(out->ids, L, p_ids);
+	st.get(out->coverage, L, p_coverage);
+	st.get(out->residual, L, p_residual);
 	return st.finish("render_matte");
 }
 
@@ -361,22 +351,21 @@ int rt_matte_extract(rt_scene *s, const rt_matte_buffers *layers_in, uint32_t wi
 	HIP_TRY(hipSetDevice(s->device));
 	std::vector<uint32_t> sorted(ids, ids + n_ids); // the caller's selection in any order, duplicates and all
 	std::sort(sorted.begin(), sorted.end());
-	const size_t n = (size_t)width * height;
+	const uint64_t n = (uint64_t)width * height;
 	// out first, then the layers and the sorted selection
-	Staging st{s, n};
-	st.add(layers_in->ids, layers * n);
-	st.add(layers_in->coverage, layers * n);
-	st.add(sorted.data(), sorted.size());
-	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, st.total * 4); // shared with rt_denoise / rt_render_denoised
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_denoise;
-	float *d_out = reinterpret_cast<float *>(base);
-	if (!st.upload(base))
+	Layout L;
+	const auto p_out = L.add<float>(n), p_coverage = L.add<float>(layers * n);
+	const auto p_ids = L.add<uint32_t>(layers * n), p_sel = L.add<uint32_t>(sorted.size());
+	RT_TRY(grow_device_buffer(s->d_denoise, s->d_denoise_bytes, L)); // shared with rt_denoise / rt_render_denoised
+	Staging st{s};
+	st.put(L, p_ids, layers_in->ids);
+	st.put(L, p_coverage, layers_in->coverage);
+	st.put(L, p_sel, sorted.data());
+	if (!st.ok())
 		return st.finish("matte_extract upload");
-	const rt_matte_buffers d_layers = {st.at<uint32_t>(base, 0), st.at(base, 1), nullptr};
-	st.rc = rt_matte_extract_device(s, &d_layers, width, height, layers, st.at<uint32_t>(base, 2), n_ids, d_out, s->stream);
-	st.download(out, d_out, 4 * n);
+	const rt_matte_buffers d_layers = {L.at(p_ids), L.at(p_coverage), nullptr};
+	st.rc = rt_matte_extract_device(s, &d_layers, width, height, layers, L.at(p_sel), n_ids, L.at(p_out), s->stream);
+	st.get(out, L, p_out);
 	return st.finish("matte_extract");
 }
 
@@ -456,18 +445,15 @@ int rt_render_ao(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, 
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
 	// the visibility, then the bent normal, each if asked for; 4-byte elements throughout
-	const size_t n = (size_t)(o->width * o->height);
+	const uint64_t n = o->width * o->height;
+	Layout L;
+	const auto p_visibility = L.optional<float>(out->visibility, n), p_bent = L.optional<float>(out->bent_normal, 3 * n);
+	RT_TRY(grow_device_buffer(s->d_denoise, s->d_denoise_bytes, L)); // shared with rt_denoise / rt_render_denoised
+	const rt_ao_buffers d_out = {L.at(p_visibility), L.at(p_bent)};
 	Staging st{s};
-	st.add(out->visibility, n);
-	st.add(out->bent_normal, 3 * n);
-	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, st.total * 4); // shared with rt_denoise / rt_render_denoised
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_denoise;
-	const rt_ao_buffers d_out = {st.at(base, 0), st.at(base, 1)};
 	st.rc = rt_render_ao_device(s, camera, o, a, &d_out, s->stream);
-	st.download(out->visibility, d_out.visibility, 4 * st.count[0]);
-	st.download(out->bent_normal, d_out.bent_normal, 4 * st.count[1]);
+	st.get(out->visibility, L, p_visibility);
+	st.get(out->bent_normal, L, p_bent);
 	return st.finish("render_ao");
 }
 
@@ -562,52 +548,107 @@ static int render_denoised_opts_check(const char *who, const rt_render_opts *o, 
 	return RT_OK;
 }
 
-// The device side of rt_render_denoised in the scene's buffer at `base`: two ray counters (16 bytes), the workspace, then the
-// frames A, B, albedo, normal, depth, noisy, clean of o's size.
-struct DenoisedFrames {
-	unsigned long long *d_rays;
-	float *d_albedo, *d_normal, *d_depth, *d_noisy, *d_clean;
-};
-static size_t denoised_frames_bytes(size_t n) { return 16 + 4 * (kDenoiseWorkspaceBytesPerPixel / 4 * n + 19 * n); }
-
-// two half renders, the AOVs of all passes, the variance and the filter on s->stream; the status goes to `st`
-static DenoisedFrames enqueue_render_denoised(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_denoise_opts *dopts,
-                                              char *base, Staging &st)
+// ---- the steps the one-call composites share, on s->stream; the status goes to `st` (nothing is enqueued once it is not ok) ----
+// the guide AOVs of all passes of the render `o` into device planes, any of them NULL
+static void enqueue_guides(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, float *d_albedo, float *d_normal, float *d_depth,
+                           Staging &st)
 {
-	const size_t n = (size_t)(o->width * o->height);
-	const size_t ws_floats = kDenoiseWorkspaceBytesPerPixel / 4 * n;
-	unsigned long long *d_rays = reinterpret_cast<unsigned long long *>(base);
-	float *ws = reinterpret_cast<float *>(base + 16);
-	float *d_a = ws + ws_floats, *d_b = d_a + 3 * n, *d_albedo = d_b + 3 * n, *d_normal = d_albedo + 3 * n,
-	      *d_depth = d_normal + 3 * n, *d_noisy = d_depth + n, *d_clean = d_noisy + 3 * n;
+	if (!st.ok())
+		return;
+	const rt_aov_buffers aov = {d_albedo, d_normal, d_depth, nullptr, nullptr, nullptr};
+	st.rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
+}
+
+// rt_denoise_device at the render's size with the caller's options
+static void enqueue_denoise(rt_scene *s, const rt_render_opts *o, const rt_denoise_opts *dopts, const rt_denoise_inputs &in, void *ws,
+                            float *d_clean, Staging &st)
+{
+	if (!st.ok())
+		return;
+	rt_denoise_opts d = *dopts;
+	d.width = (uint32_t)o->width;
+	d.height = (uint32_t)o->height;
+	st.rc = rt_denoise_device(s, &in, &d, ws, d_clean, s->stream);
+}
+
+// The device side of rt_render_denoised for a render of n pixels: two ray counters, the workspace, then the frames A, B, albedo,
+// normal, depth, noisy, clean.  rt_render_upscaled describes its destination-size frames behind them.
+struct DenoisedParts {
+	Layout::Part<unsigned long long> rays;
+	Layout::Part<char> ws;
+	Layout::Part<float> a, b, albedo, normal, depth, noisy, clean;
+};
+static DenoisedParts denoised_parts(Layout &L, uint64_t n)
+{
+	return DenoisedParts{L.add<unsigned long long>(2), L.bytes(kDenoiseWorkspaceBytesPerPixel * n), L.add<float>(3 * n), L.add<float>(3 * n),
+	                     L.add<float>(3 * n), L.add<float>(3 * n), L.add<float>(n), L.add<float>(3 * n), L.add<float>(3 * n)}; // (in this order)
+}
+
+// two half renders, the AOVs of all passes, the variance and the filter, in the parts `P` of the grown buffer
+static void enqueue_render_denoised(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_denoise_opts *dopts,
+                                    const Layout &L, const DenoisedParts &P, Staging &st)
+{
+	uint64_t *d_rays = reinterpret_cast<uint64_t *>(L.at(P.rays));
+	float *d_a = L.at(P.a), *d_b = L.at(P.b), *d_albedo = L.at(P.albedo), *d_normal = L.at(P.normal),
+	      *d_depth = L.at(P.depth), *d_noisy = L.at(P.noisy);
 	const uint64_t half = o->samples_per_pixel / 2;
 	rt_render_opts oh = *o;
 	oh.samples_per_pixel = half;
 	if (st.ok())
-		st.rc = rt_render_device(s, camera, &oh, d_a, reinterpret_cast<uint64_t *>(d_rays), s->stream);
+		st.rc = rt_render_device(s, camera, &oh, d_a, d_rays, s->stream);
 	if (st.ok()) {
 		oh.sample_begin = o->sample_begin + half;
-		st.rc = rt_render_device(s, camera, &oh, d_b, reinterpret_cast<uint64_t *>(d_rays + 1), s->stream);
+		st.rc = rt_render_device(s, camera, &oh, d_b, d_rays + 1, s->stream);
 	}
 	if (st.ok())
 		st.e = hipSetDevice(s->device);
-	if (st.ok()) {
-		rt_aov_buffers aov;
-		std::memset(&aov, 0, sizeof aov);
-		aov.albedo = d_albedo;
-		aov.normal = d_normal;
-		aov.depth = d_depth;
-		st.rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
-	}
+	enqueue_guides(s, camera, o, d_albedo, d_normal, d_depth, st);
 	if (st.ok()) {
 		const rt_denoise_inputs in = {d_noisy, d_albedo, d_normal, d_depth, nullptr};
-		DevDenoiseParams P = denoise_params(dopts, o->width, o->height, in, ws, d_clean);
-		P.half_a = d_a;
-		P.half_b = d_b;
-		P.noisy = d_noisy;
-		st.e = launch_denoise(s->stream, P);
+		DevDenoiseParams D = denoise_params(dopts, o->width, o->height, in, L.at(P.ws), L.at(P.clean));
+		D.half_a = d_a;
+		D.half_b = d_b;
+		D.noisy = d_noisy;
+		st.e = launch_denoise(s->stream, D);
 	}
-	return DenoisedFrames{d_rays, d_albedo, d_normal, d_depth, d_noisy, d_clean};
+}
+
+// What rt_render_denoised_split and rt_render_denoised_robust share once their own arguments are checked.  In the denoiser's buffer:
+// the ray counter, the workspace, albedo, normal, depth, the frame the filter reads, `extra_floats` for the middle call, clean.
+// Enqueued: the guides, middle(d_albedo, d_frame, d_extra, d_rays) -- the render into d_frame --, the filter (d_extra its variance
+// plane if extra_is_variance), the downloads and the ray count.
+template <class Middle>
+static int render_denoised_guided(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_denoise_opts *dopts, uint64_t px,
+                                  uint64_t extra_floats, bool extra_is_variance, Middle middle, const char *what, float *out_clean,
+                                  float *out_frame, float *out_extra, uint64_t *rays_shot)
+{
+	int rc = need_device(s);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	Layout L;
+	const auto p_rays = L.add<uint64_t>(1);
+	const auto p_ws = L.bytes(kDenoiseWorkspaceBytesPerPixel * px);
+	const auto p_albedo = L.add<float>(3 * px), p_normal = L.add<float>(3 * px), p_depth = L.add<float>(px), p_frame = L.add<float>(3 * px),
+	           p_extra = L.add<float>(extra_floats), p_clean = L.add<float>(3 * px);
+	RT_TRY(grow_device_buffer(s->d_denoise, s->d_denoise_bytes, L));
+	float *d_albedo = L.at(p_albedo), *d_normal = L.at(p_normal), *d_depth = L.at(p_depth), *d_frame = L.at(p_frame),
+	      *d_extra = L.at(p_extra);
+	Staging st{s};
+	enqueue_guides(s, camera, o, d_albedo, d_normal, d_depth, st);
+	if (st.ok())
+		st.rc = middle(d_albedo, d_frame, d_extra, L.at(p_rays));
+	enqueue_denoise(s, o, dopts, {d_frame, d_albedo, d_normal, d_depth, extra_is_variance ? d_extra : nullptr}, L.at(p_ws),
+	                L.at(p_clean), st);
+	uint64_t rays = 0;
+	st.get(out_clean, L, p_clean);
+	st.get(out_frame, L, p_frame);
+	st.get(out_extra, L, p_extra);
+	st.get(&rays, L, p_rays);
+	rc = st.finish(what);
+	if (rc == RT_OK && rays_shot)
+		*rays_shot = rays;
+	return rc;
 }
 
 extern "C" {
@@ -653,24 +694,25 @@ int rt_denoise(rt_scene *s, const rt_denoise_inputs *in, const rt_denoise_opts *
 	if (rc != RT_OK)
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
-	const size_t n = (size_t)o->width * o->height;
-	// workspace first (16-byte aligned), then out, then the inputs given, in rt_denoise_inputs order
-	Staging st{s, kDenoiseWorkspaceBytesPerPixel / 4 * n + 3 * n};
-	st.add(in->color, 3 * n);
-	st.add(in->albedo, 3 * n);
-	st.add(in->normal, 3 * n);
-	st.add(in->depth, n);
-	st.add(in->variance, n);
-	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, st.total * 4); // grown on first use / larger frames only
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_denoise;
-	float *d_out = reinterpret_cast<float *>(base) + kDenoiseWorkspaceBytesPerPixel / 4 * n;
-	if (!st.upload(base))
+	const uint64_t n = (uint64_t)o->width * o->height;
+	// the workspace, out, then the inputs given, in rt_denoise_inputs order
+	Layout L;
+	const auto p_ws = L.bytes(kDenoiseWorkspaceBytesPerPixel * n);
+	const auto p_out = L.add<float>(3 * n), p_color = L.add<float>(3 * n), p_albedo = L.optional<float>(in->albedo, 3 * n),
+	           p_normal = L.optional<float>(in->normal, 3 * n), p_depth = L.optional<float>(in->depth, n),
+	           p_variance = L.optional<float>(in->variance, n);
+	RT_TRY(grow_device_buffer(s->d_denoise, s->d_denoise_bytes, L)); // grown on first use / larger frames only
+	Staging st{s};
+	st.put(L, p_color, in->color);
+	st.put(L, p_albedo, in->albedo);
+	st.put(L, p_normal, in->normal);
+	st.put(L, p_depth, in->depth);
+	st.put(L, p_variance, in->variance);
+	if (!st.ok())
 		return st.finish("denoise upload");
-	const rt_denoise_inputs d_in = {st.at(base, 0), st.at(base, 1), st.at(base, 2), st.at(base, 3), st.at(base, 4)};
-	st.rc = rt_denoise_device(s, &d_in, o, base, d_out, s->stream);
-	st.download(out, d_out, 3 * n * 4);
+	const rt_denoise_inputs d_in = {L.at(p_color), L.at(p_albedo), L.at(p_normal), L.at(p_depth), L.at(p_variance)};
+	st.rc = rt_denoise_device(s, &d_in, o, L.at(p_ws), L.at(p_out), s->stream);
+	st.get(out, L, p_out);
 	return st.finish("denoise");
 }
 
@@ -682,22 +724,22 @@ int rt_render_denoised(rt_scene *s, const rt_camera *camera, const rt_render_opt
 	int rc = render_denoised_opts_check("rt_render_denoised", o, dopts, o->width, o->height);
 	if (rc != RT_OK)
 		return rc;
-	const size_t n = (size_t)(o->width * o->height);
+	const uint64_t n = o->width * o->height;
 	if (ranges_overlap(out_clean, 12 * n, out_noisy, 12 * n))
 		return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_denoised: out_clean overlaps out_noisy");
 	rc = need_device(s);
 	if (rc != RT_OK)
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
-	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, denoised_frames_bytes(n));
-	if (rc != RT_OK)
-		return rc;
+	Layout L;
+	const DenoisedParts P = denoised_parts(L, n);
+	RT_TRY(grow_device_buffer(s->d_denoise, s->d_denoise_bytes, L));
 	Staging st{s};
-	const DenoisedFrames F = enqueue_render_denoised(s, camera, o, dopts, s->d_denoise, st);
+	enqueue_render_denoised(s, camera, o, dopts, L, P, st);
 	unsigned long long rays[2] = {0, 0};
-	st.download(out_clean, F.d_clean, 3 * n * 4);
-	st.download(out_noisy, F.d_noisy, 3 * n * 4);
-	st.download(rays, F.d_rays, sizeof rays);
+	st.get(out_clean, L, P.clean);
+	st.get(out_noisy, L, P.noisy);
+	st.get(rays, L, P.rays);
 	rc = st.finish("render_denoised");
 	if (rc == RT_OK && rays_shot)
 		*rays_shot = rays[0] + rays[1];
@@ -764,8 +806,16 @@ static int noise_render_check(const rt_scene *s, const rt_render_opts *o, const 
 }
 
 static uint64_t noise_tile_count(uint64_t w, uint64_t h) { return ((w + 7) / 8) * ((h + 7) / 8); }
-// the scene's scratch: the summary of the blocking calls, then the state planes M, L, V; what a blocking call stages comes behind
-static size_t noise_state_bytes(size_t n) { return kNoiseSummaryBytes + 20 * n; }
+// the scene's scratch for n pixels: the summary of the blocking calls, then the state planes M, L, V; what a blocking call stages
+// comes behind (described after these, so that the state is where the _device call inside it finds it)
+struct NoiseState {
+	Layout::Part<rt_noise_summary> summary;
+	Layout::Part<float> m, l, v;
+};
+static NoiseState noise_state(Layout &L, uint64_t n)
+{
+	return NoiseState{L.add<rt_noise_summary>(1), L.add<float>(3 * n), L.add<float>(n), L.add<float>(n)}; // (in this order)
+}
 
 static int noise_buffers_check(const rt_scene *s, const float *albedo, const rt_noise_buffers *b, uint64_t n, uint64_t w, uint64_t h)
 {
@@ -802,18 +852,17 @@ static int enqueue_noise_tiles(hipStream_t stream, const float *d_lum, const flo
 
 // One batch on `stream`: the render of rt_render_device at `split` into d_render, the chunk kernel (state == nullptr: one batch,
 // nothing kept; else batch number `nb` of a sequence, 1 = fresh) and, if a tile output is asked for, the tile stage.
-// out->variance / lum_mean NULL with a tile output: the state's L and V planes stand in (`scratch`, noise_state_bytes).
+// out->variance / lum_mean NULL with a tile output: the state's L and V planes stand in (the parts `N` of the scene's scratch, noise_state).
 static int enqueue_noise_batch(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, uint32_t split, const rt_noise_opts *n,
-                               const float *d_albedo, float *d_render, char *scratch, bool keep_state, uint32_t nb, const rt_noise_buffers *out,
-                               uint64_t *d_rays, hipStream_t stream)
+                               const float *d_albedo, float *d_render, const Layout &L, const NoiseState &N, bool keep_state,
+                               uint32_t nb, const rt_noise_buffers *out, uint64_t *d_rays, hipStream_t stream)
 {
 	rt_render_opts os = *o;
 	os.sample_split = split;
 	int rc = rt_render_device(s, camera, &os, d_render, d_rays, stream);
 	if (rc != RT_OK)
 		return rc;
-	const size_t px = (size_t)(o->width * o->height);
-	float *const state_m = reinterpret_cast<float *>(scratch + kNoiseSummaryBytes), *const state_l = state_m + 3 * px, *const state_v = state_l + px;
+	float *const state_m = L.at(N.m), *const state_l = L.at(N.l), *const state_v = L.at(N.v);
 	const bool tiles = out->tile_error || out->summary;
 	float *d_lum = out->lum_mean, *d_var = out->variance;
 	if (tiles && !keep_state) { // (a sequence divides its state out into planes of its own)
@@ -894,10 +943,10 @@ int rt_render_noise_device(rt_scene *s, const rt_camera *camera, const rt_render
 	if (rc != RT_OK)
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
-	rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, noise_state_bytes(px)); // grows on first use only (not capturable on that call)
-	if (rc != RT_OK)
-		return rc;
-	return enqueue_noise_batch(s, camera, o, split, n, d_albedo, d_out->mean, s->d_noise, false, 1u, d_out, d_rays_shot,
+	Layout L;
+	const NoiseState N = noise_state(L, px);
+	RT_TRY(grow_device_buffer(s->d_noise, s->d_noise_bytes, L)); // grows on first use only (not capturable on that call)
+	return enqueue_noise_batch(s, camera, o, split, n, d_albedo, d_out->mean, L, N, false, 1u, d_out, d_rays_shot,
 	                           static_cast<hipStream_t>(hip_stream));
 }
 
@@ -914,27 +963,23 @@ int rt_render_noise(rt_scene *s, const rt_camera *camera, const rt_render_opts *
 	if (rc != RT_OK)
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
-	// behind the state: the mean, then the channels asked for, the summary (4 words) and the albedo if given
-	Staging st{s, noise_state_bytes(px) / 4 + 3 * px};
-	st.add(out->variance, px);
-	st.add(out->lum_mean, px);
-	st.add(out->tile_error, noise_tile_count(o->width, o->height));
-	st.add(out->summary, 4);
-	st.add(albedo, 3 * px);
-	rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, st.total * 4);
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_noise;
-	float *d_mean = reinterpret_cast<float *>(base + noise_state_bytes(px));
-	st.to_device(st.at(base, 4), albedo, 12 * px);
-	const rt_noise_buffers d_out = {d_mean, st.at(base, 0), st.at(base, 1), st.at(base, 2), st.at<rt_noise_summary>(base, 3)};
+	// behind the state: the mean, then the channels asked for, the summary and the albedo if given
+	Layout L;
+	noise_state(L, px);
+	const auto p_mean = L.add<float>(3 * px), p_variance = L.optional<float>(out->variance, px), p_lum = L.optional<float>(out->lum_mean, px),
+	           p_tiles = L.optional<float>(out->tile_error, noise_tile_count(o->width, o->height)), p_albedo = L.optional<float>(albedo, 3 * px);
+	const auto p_summary = L.optional<rt_noise_summary>(out->summary, 1);
+	RT_TRY(grow_device_buffer(s->d_noise, s->d_noise_bytes, L));
+	Staging st{s};
+	st.put(L, p_albedo, albedo);
+	const rt_noise_buffers d_out = {L.at(p_mean), L.at(p_variance), L.at(p_lum), L.at(p_tiles), L.at(p_summary)};
 	if (st.ok())
-		st.rc = rt_render_noise_device(s, camera, o, n, st.at(base, 4), &d_out, reinterpret_cast<uint64_t *>(s->d_rays), s->stream);
-	st.download(out->mean, d_mean, 12 * px);
-	st.download(out->variance, d_out.variance, 4 * st.count[0]);
-	st.download(out->lum_mean, d_out.lum_mean, 4 * st.count[1]);
-	st.download(out->tile_error, d_out.tile_error, 4 * st.count[2]);
-	st.download(out->summary, d_out.summary, kNoiseSummaryBytes);
+		st.rc = rt_render_noise_device(s, camera, o, n, L.at(p_albedo), &d_out, reinterpret_cast<uint64_t *>(s->d_rays), s->stream);
+	st.get(out->mean, L, p_mean);
+	st.get(out->variance, L, p_variance);
+	st.get(out->lum_mean, L, p_lum);
+	st.get(out->tile_error, L, p_tiles);
+	st.get(out->summary, L, p_summary);
 	st.download(rays_shot, s->d_rays, sizeof(uint64_t));
 	return st.finish("render_noise");
 }
@@ -956,22 +1001,19 @@ int rt_noise_tiles(rt_scene *s, const float *lum_mean, const float *variance, ui
 	if (rc != RT_OK)
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
-	const size_t px = (size_t)width * height;
+	const uint64_t px = (uint64_t)width * height;
+	Layout L;
+	const auto p_lum = L.add<float>(px), p_variance = L.add<float>(px), p_tiles = L.optional<float>(tile_error, noise_tile_count(width, height));
+	const auto p_summary = L.optional<rt_noise_summary>(summary, 1);
+	RT_TRY(grow_device_buffer(s->d_noise, s->d_noise_bytes, L));
 	Staging st{s};
-	st.add(lum_mean, px);
-	st.add(variance, px);
-	st.add(tile_error, noise_tile_count(width, height));
-	st.add(summary, 4);
-	rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, st.total * 4);
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_noise;
-	st.to_device(st.at(base, 0), lum_mean, 4 * px);
-	st.to_device(st.at(base, 1), variance, 4 * px);
+	st.put(L, p_lum, lum_mean);
+	st.put(L, p_variance, variance);
 	if (st.ok())
-		st.rc = rt_noise_tiles_device(s, st.at(base, 0), st.at(base, 1), width, height, n, st.at(base, 2), st.at<rt_noise_summary>(base, 3), s->stream);
-	st.download(tile_error, st.at(base, 2), 4 * st.count[2]);
-	st.download(summary, st.at(base, 3), kNoiseSummaryBytes);
+		st.rc = rt_noise_tiles_device(s, L.at(p_lum), L.at(p_variance), width, height, n, L.at(p_tiles), L.at(p_summary),
+		                              s->stream);
+	st.get(tile_error, L, p_tiles);
+	st.get(summary, L, p_summary);
 	return st.finish("noise_tiles");
 }
 
@@ -1001,24 +1043,23 @@ int rt_render_converged(rt_scene *s, const rt_camera *camera, const rt_render_op
 			return rc;
 	}
 	HIP_TRY(hipSetDevice(s->device));
-	// behind the state (its first 16 bytes are the summary): this batch's render, then mean, lum_mean, variance and the tile errors
-	const size_t floats = noise_state_bytes(px) / 4 + 3 * px + 3 * px + px + px + n_tiles;
-	rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, floats * 4);
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_noise;
-	float *d_render = reinterpret_cast<float *>(base + noise_state_bytes(px)), *d_mean = d_render + 3 * px, *d_lum = d_mean + 3 * px,
-	      *d_var = d_lum + px, *d_tile = d_var + px;
-	const rt_noise_buffers d_out = {d_mean, d_var, d_lum, d_tile, reinterpret_cast<rt_noise_summary *>(base)};
+	// behind the state (whose summary this sequence uses): this batch's render, then mean, lum_mean, variance and the tile errors
+	Layout L;
+	const NoiseState N = noise_state(L, px);
+	const auto p_render = L.add<float>(3 * px), p_mean = L.add<float>(3 * px), p_lum = L.add<float>(px), p_variance = L.add<float>(px),
+	           p_tiles = L.add<float>(n_tiles);
+	RT_TRY(grow_device_buffer(s->d_noise, s->d_noise_bytes, L));
+	const rt_noise_buffers d_out = {L.at(p_mean), L.at(p_variance), L.at(p_lum), L.at(p_tiles), L.at(N.summary)};
 	std::memset(result, 0, sizeof *result);
 	rt_render_opts ob = *o;
 	ob.samples_per_pixel = batch;
 	for (uint32_t nb = 1;; ++nb) {
 		ob.sample_begin = o->sample_begin + (uint64_t)(nb - 1u) * batch;
 		Staging st{s};
-		st.rc = enqueue_noise_batch(s, camera, &ob, split, n, nullptr, d_render, base, true, nb, &d_out, reinterpret_cast<uint64_t *>(s->d_rays), s->stream);
+		st.rc = enqueue_noise_batch(s, camera, &ob, split, n, nullptr, L.at(p_render), L, N, true, nb, &d_out,
+		                            reinterpret_cast<uint64_t *>(s->d_rays), s->stream);
 		unsigned long long rays = 0;
-		st.download(&result->summary, base, kNoiseSummaryBytes);
+		st.get(&result->summary, L, N.summary);
 		st.download(&rays, s->d_rays, sizeof rays);
 		rc = st.finish("render_converged");
 		if (rc != RT_OK)
@@ -1031,9 +1072,9 @@ int rt_render_converged(rt_scene *s, const rt_camera *camera, const rt_render_op
 			break;
 	}
 	Staging st{s};
-	st.download(out_mean, d_mean, 12 * px);
-	st.download(out_variance, d_var, 4 * px);
-	st.download(out_tile_error, d_tile, 4 * n_tiles);
+	st.get(out_mean, L, p_mean);
+	st.get(out_variance, L, p_variance);
+	st.get(out_tile_error, L, p_tiles);
 	return st.finish("render_converged");
 }
 
@@ -1052,52 +1093,17 @@ int rt_render_denoised_split(rt_scene *s, const rt_camera *camera, const rt_rend
 	rc = noise_render_check(s, o, &n, o->samples_per_pixel, &split, &px);
 	if (rc != RT_OK)
 		return rc;
-	{
-		const void *buf[3] = {out_clean, out_noisy, out_variance};
-		const uint64_t bytes[3] = {12 * px, 12 * px, 4 * px};
-		rc = check_disjoint("rt_render_denoised_split: two output buffers overlap", buf, bytes, 3, 3);
-		if (rc == RT_OK)
-			rc = need_device(s);
-		if (rc != RT_OK)
-			return rc;
-	}
-	HIP_TRY(hipSetDevice(s->device));
-	// in the denoiser's buffer: the ray counter (16 bytes), the workspace, then albedo, normal, depth, noisy, variance, clean
-	const size_t ws_floats = kDenoiseWorkspaceBytesPerPixel / 4 * px;
-	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, 16 + 4 * (ws_floats + 14 * px));
+	const void *buf[3] = {out_clean, out_noisy, out_variance};
+	const uint64_t bytes[3] = {12 * px, 12 * px, 4 * px};
+	rc = check_disjoint("rt_render_denoised_split: two output buffers overlap", buf, bytes, 3, 3);
 	if (rc != RT_OK)
 		return rc;
-	char *base = s->d_denoise;
-	float *ws = reinterpret_cast<float *>(base + 16);
-	float *d_albedo = ws + ws_floats, *d_normal = d_albedo + 3 * px, *d_depth = d_normal + 3 * px, *d_noisy = d_depth + px,
-	      *d_var = d_noisy + 3 * px, *d_clean = d_var + px;
-	Staging st{s};
-	rt_aov_buffers aov;
-	std::memset(&aov, 0, sizeof aov);
-	aov.albedo = d_albedo;
-	aov.normal = d_normal;
-	aov.depth = d_depth;
-	st.rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
-	if (st.ok()) {
+	// the middle call: the render and its variance plane, one render at the split
+	auto middle = [&](float *d_albedo, float *d_noisy, float *d_var, uint64_t *d_rays) {
 		const rt_noise_buffers d_out = {d_noisy, d_var, nullptr, nullptr, nullptr};
-		st.rc = rt_render_noise_device(s, camera, o, &n, d_albedo, &d_out, reinterpret_cast<uint64_t *>(base), s->stream);
-	}
-	if (st.ok()) {
-		rt_denoise_opts d = *dopts;
-		d.width = (uint32_t)o->width;
-		d.height = (uint32_t)o->height;
-		const rt_denoise_inputs in = {d_noisy, d_albedo, d_normal, d_depth, d_var};
-		st.rc = rt_denoise_device(s, &in, &d, ws, d_clean, s->stream);
-	}
-	unsigned long long rays = 0;
-	st.download(out_clean, d_clean, 12 * px);
-	st.download(out_noisy, d_noisy, 12 * px);
-	st.download(out_variance, d_var, 4 * px);
-	st.download(&rays, base, sizeof rays);
-	rc = st.finish("render_denoised_split");
-	if (rc == RT_OK && rays_shot)
-		*rays_shot = rays;
-	return rc;
+		return rt_render_noise_device(s, camera, o, &n, d_albedo, &d_out, d_rays, s->stream);
+	};
+	return render_denoised_guided(s, camera, o, dopts, px, px, true, middle, "render_denoised_split", out_clean, out_noisy, out_variance, rays_shot);
 }
 
 } // extern "C"
@@ -1208,10 +1214,10 @@ int rt_render_robust_device(rt_scene *s, const rt_camera *camera, const rt_rende
 	hipStream_t stream = static_cast<hipStream_t>(hip_stream);
 	float *d_render = d_out->mean;
 	if (!d_render) { // the render's frame goes to the noise stage's scratch: grows on first use only (not capturable on that call)
-		rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, 12 * px);
-		if (rc != RT_OK)
-			return rc;
-		d_render = reinterpret_cast<float *>(s->d_noise);
+		Layout L;
+		const auto p_render = L.add<float>(3 * px);
+		RT_TRY(grow_device_buffer(s->d_noise, s->d_noise_bytes, L));
+		d_render = L.at(p_render);
 	}
 	rt_render_opts os = *o;
 	os.sample_split = split;
@@ -1243,26 +1249,21 @@ int rt_render_robust(rt_scene *s, const rt_camera *camera, const rt_render_opts 
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
 	// the render's frame first (where the _device call would put its scratch), then out, the planes asked for and the albedo if given
-	Staging st{s, 3 * px};
-	st.add(out->out, 3 * px);
-	st.add(out->gini, px);
-	st.add(out->trimmed, (px + 3) / 4);
-	st.add(out->dropped, (px + 3) / 4);
-	st.add(albedo, 3 * px);
-	rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, st.total * 4);
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_noise;
-	float *d_mean = reinterpret_cast<float *>(base);
-	st.to_device(st.at(base, 4), albedo, 12 * px);
-	const rt_robust_buffers d_out = {st.at(base, 0), d_mean, st.at(base, 1), st.at<uint8_t>(base, 2), st.at<uint8_t>(base, 3)};
+	Layout L;
+	const auto p_mean = L.add<float>(3 * px), p_out = L.add<float>(3 * px), p_gini = L.optional<float>(out->gini, px),
+	           p_albedo = L.optional<float>(albedo, 3 * px);
+	const auto p_trimmed = L.optional<uint8_t>(out->trimmed, px), p_dropped = L.optional<uint8_t>(out->dropped, px);
+	RT_TRY(grow_device_buffer(s->d_noise, s->d_noise_bytes, L));
+	Staging st{s};
+	st.put(L, p_albedo, albedo);
+	const rt_robust_buffers d_out = {L.at(p_out), L.at(p_mean), L.at(p_gini), L.at(p_trimmed), L.at(p_dropped)};
 	if (st.ok())
-		st.rc = rt_render_robust_device(s, camera, o, r, st.at(base, 4), &d_out, reinterpret_cast<uint64_t *>(s->d_rays), s->stream);
-	st.download(out->out, d_out.out, 12 * px);
-	st.download(out->mean, d_mean, 12 * px);
-	st.download(out->gini, d_out.gini, 4 * px);
-	st.download(out->trimmed, d_out.trimmed, px);
-	st.download(out->dropped, d_out.dropped, px);
+		st.rc = rt_render_robust_device(s, camera, o, r, L.at(p_albedo), &d_out, reinterpret_cast<uint64_t *>(s->d_rays), s->stream);
+	st.get(out->out, L, p_out);
+	st.get(out->mean, L, p_mean);
+	st.get(out->gini, L, p_gini);
+	st.get(out->trimmed, L, p_trimmed);
+	st.get(out->dropped, L, p_dropped);
 	st.download(rays_shot, s->d_rays, sizeof(uint64_t));
 	return st.finish("render_robust");
 }
@@ -1288,28 +1289,22 @@ int rt_robust_combine(rt_scene *s, const float *sums, uint32_t split, uint64_t c
 	if (rc != RT_OK)
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
+	Layout L;
+	const auto p_sums = L.add<float>(3 * px * split), p_albedo = L.optional<float>(albedo, 3 * px), p_out = L.add<float>(3 * px),
+	           p_mean = L.optional<float>(out->mean, 3 * px), p_gini = L.optional<float>(out->gini, px);
+	const auto p_trimmed = L.optional<uint8_t>(out->trimmed, px), p_dropped = L.optional<uint8_t>(out->dropped, px);
+	RT_TRY(grow_device_buffer(s->d_noise, s->d_noise_bytes, L));
 	Staging st{s};
-	st.add(sums, 3 * px * split);
-	st.add(albedo, 3 * px);
-	st.add(out->out, 3 * px);
-	st.add(out->mean, 3 * px);
-	st.add(out->gini, px);
-	st.add(out->trimmed, (px + 3) / 4);
-	st.add(out->dropped, (px + 3) / 4);
-	rc = grow_device_buffer(s->d_noise, s->d_noise_bytes, st.total * 4);
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_noise;
-	st.to_device(st.at(base, 0), sums, 12 * px * split);
-	st.to_device(st.at(base, 1), albedo, 12 * px);
-	const rt_robust_buffers d_out = {st.at(base, 2), st.at(base, 3), st.at(base, 4), st.at<uint8_t>(base, 5), st.at<uint8_t>(base, 6)};
+	st.put(L, p_sums, sums);
+	st.put(L, p_albedo, albedo);
+	const rt_robust_buffers d_out = {L.at(p_out), L.at(p_mean), L.at(p_gini), L.at(p_trimmed), L.at(p_dropped)};
 	if (st.ok())
-		st.rc = rt_robust_combine_device(s, st.at(base, 0), split, chunk_passes, width, height, st.at(base, 1), r, &d_out, s->stream);
-	st.download(out->out, d_out.out, 12 * px);
-	st.download(out->mean, d_out.mean, 12 * px);
-	st.download(out->gini, d_out.gini, 4 * px);
-	st.download(out->trimmed, d_out.trimmed, px);
-	st.download(out->dropped, d_out.dropped, px);
+		st.rc = rt_robust_combine_device(s, L.at(p_sums), split, chunk_passes, width, height, L.at(p_albedo), r, &d_out, s->stream);
+	st.get(out->out, L, p_out);
+	st.get(out->mean, L, p_mean);
+	st.get(out->gini, L, p_gini);
+	st.get(out->trimmed, L, p_trimmed);
+	st.get(out->dropped, L, p_dropped);
 	return st.finish("robust_combine");
 }
 
@@ -1328,45 +1323,12 @@ int rt_render_denoised_robust(rt_scene *s, const rt_camera *camera, const rt_ren
 		return rc;
 	if (ranges_overlap(out_clean, 12 * px, out_robust, 12 * px))
 		return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_denoised_robust: out_clean overlaps out_robust");
-	rc = need_device(s);
-	if (rc != RT_OK)
-		return rc;
-	HIP_TRY(hipSetDevice(s->device));
-	// in the denoiser's buffer: the ray counter (16 bytes), the workspace, then albedo, normal, depth, the render, robust, clean
-	const size_t ws_floats = kDenoiseWorkspaceBytesPerPixel / 4 * px;
-	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, 16 + 4 * (ws_floats + 16 * px));
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_denoise;
-	float *ws = reinterpret_cast<float *>(base + 16);
-	float *d_albedo = ws + ws_floats, *d_normal = d_albedo + 3 * px, *d_depth = d_normal + 3 * px, *d_mean = d_depth + px,
-	      *d_robust = d_mean + 3 * px, *d_clean = d_robust + 3 * px;
-	Staging st{s};
-	rt_aov_buffers aov;
-	std::memset(&aov, 0, sizeof aov);
-	aov.albedo = d_albedo;
-	aov.normal = d_normal;
-	aov.depth = d_depth;
-	st.rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
-	if (st.ok()) {
+	// the middle call: the robust frame (the one filtered) and the plain render behind it
+	auto middle = [&](float *d_albedo, float *d_robust, float *d_mean, uint64_t *d_rays) {
 		const rt_robust_buffers d_out = {d_robust, d_mean, nullptr, nullptr, nullptr};
-		st.rc = rt_render_robust_device(s, camera, o, r, d_albedo, &d_out, reinterpret_cast<uint64_t *>(base), s->stream);
-	}
-	if (st.ok()) {
-		rt_denoise_opts d = *dopts;
-		d.width = (uint32_t)o->width;
-		d.height = (uint32_t)o->height;
-		const rt_denoise_inputs in = {d_robust, d_albedo, d_normal, d_depth, nullptr};
-		st.rc = rt_denoise_device(s, &in, &d, ws, d_clean, s->stream);
-	}
-	unsigned long long rays = 0;
-	st.download(out_clean, d_clean, 12 * px);
-	st.download(out_robust, d_robust, 12 * px);
-	st.download(&rays, base, sizeof rays);
-	rc = st.finish("render_denoised_robust");
-	if (rc == RT_OK && rays_shot)
-		*rays_shot = rays;
-	return rc;
+		return rt_render_robust_device(s, camera, o, r, d_albedo, &d_out, d_rays, s->stream);
+	};
+	return render_denoised_guided(s, camera, o, dopts, px, 3 * px, false, middle, "render_denoised_robust", out_clean, out_robust, nullptr, rays_shot);
 }
 
 } // extern "C"
@@ -1503,39 +1465,40 @@ int rt_denoise_temporal(rt_scene *s, const rt_temporal_inputs *in, const rt_came
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
 	const uint32_t w = o->denoise.width, h = o->denoise.height;
-	const size_t n = (size_t)w * h;
+	const uint64_t n = (uint64_t)w * h;
+	Layout H; // the two histories, alone in their buffer: the same description puts them at the same place in every call
+	const Layout::Part<char> p_hist[2] = {H.bytes(kTemporalHistoryBytesPerPixel * n), H.bytes(kTemporalHistoryBytesPerPixel * n)};
 	if (w != s->temporal_w || h != s->temporal_h) { // a new frame size: new histories, no history
 		s->temporal_w = s->temporal_h = 0;
 		s->temporal_cur = -1;
 		size_t held = 0; // (always replaced: the buffer is two histories of exactly w x h)
-		rc = grow_device_buffer(s->d_temporal, held, 2 * kTemporalHistoryBytesPerPixel * n);
-		if (rc != RT_OK)
-			return rc;
+		RT_TRY(grow_device_buffer(s->d_temporal, held, H));
 		s->temporal_w = w;
 		s->temporal_h = h;
 	}
-	// the workspace (16-byte aligned), out, motion, then the inputs given, in rt_temporal_inputs order
-	Staging st{s, kTemporalWorkspaceBytesPerPixel / 4 * n + 5 * n};
-	st.add(in->color, 3 * n);
-	st.add(in->albedo, 3 * n);
-	st.add(in->normal, 3 * n);
-	st.add(in->depth, n);
-	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, st.total * 4); // shared with rt_denoise / rt_render_denoised
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_denoise;
-	float *d_out = reinterpret_cast<float *>(base) + kTemporalWorkspaceBytesPerPixel / 4 * n, *d_motion = d_out + 3 * n;
-	if (!st.upload(base))
+	// the workspace, out, motion if asked for, then the inputs given, in rt_temporal_inputs order
+	Layout L;
+	const auto p_ws = L.bytes(kTemporalWorkspaceBytesPerPixel * n);
+	const auto p_out = L.add<float>(3 * n), p_motion = L.optional<float>(motion, 2 * n), p_color = L.add<float>(3 * n),
+	           p_albedo = L.optional<float>(in->albedo, 3 * n), p_normal = L.optional<float>(in->normal, 3 * n), p_depth = L.add<float>(n);
+	RT_TRY(grow_device_buffer(s->d_denoise, s->d_denoise_bytes, L)); // shared with rt_denoise / rt_render_denoised
+	Staging st{s};
+	st.put(L, p_color, in->color);
+	st.put(L, p_albedo, in->albedo);
+	st.put(L, p_normal, in->normal);
+	st.put(L, p_depth, in->depth);
+	if (!st.ok())
 		return st.finish("denoise_temporal upload");
-	const rt_temporal_inputs d_in = {st.at(base, 0), st.at(base, 1), st.at(base, 2), st.at(base, 3)};
-	char *hist[2] = {s->d_temporal, s->d_temporal + kTemporalHistoryBytesPerPixel * n};
+	const rt_temporal_inputs d_in = {L.at(p_color), L.at(p_albedo), L.at(p_normal), L.at(p_depth)};
+	H.base = s->d_temporal;
+	char *hist[2] = {H.at(p_hist[0]), H.at(p_hist[1])};
 	const int next = s->temporal_cur == 0 ? 1 : 0;
 	const void *h_in = s->temporal_cur >= 0 ? hist[s->temporal_cur] : nullptr;
 	s->temporal_cur = -1; // until this call has succeeded
-	st.rc = rt_denoise_temporal_device(s, &d_in, cam, &s->temporal_prev, h_in, hist[next], o, base, d_out, motion ? d_motion : nullptr,
-	                                   s->stream);
-	st.download(out, d_out, 3 * n * 4);
-	st.download(motion, d_motion, 2 * n * 4);
+	st.rc = rt_denoise_temporal_device(s, &d_in, cam, &s->temporal_prev, h_in, hist[next], o, L.at(p_ws), L.at(p_out),
+	                                   L.at(p_motion), s->stream);
+	st.get(out, L, p_out);
+	st.get(motion, L, p_motion);
 	rc = st.finish("denoise_temporal");
 	if (rc == RT_OK) {
 		s->temporal_cur = next;
@@ -1706,35 +1669,33 @@ int rt_display(rt_scene *s, const float *host_rgb, const rt_display_opts *o, voi
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
 	const uint64_t n = (uint64_t)o->width * o->height;
-	// state (16), histogram (1024), workspace, output, input: every part 16-byte aligned
-	auto up16 = [](uint64_t b) { return (b + 15u) / 16u * 16u; };
-	const uint64_t off_hist = 16, off_ws = off_hist + 4ull * kDisplayBins, off_out = off_ws + display_workspace_bytes(n);
-	const uint64_t off_in = off_out + up16(display_out_bytes(o)), total = off_in + 12 * n;
-	if (total > s->d_display_bytes) { // grown for larger frames only; the state is kept on the host side meanwhile
+	// the state first (so that it is found again whatever the frame size), the histogram, workspace, output, input
+	Layout L;
+	const auto p_state = L.add<rt_display_state>(1);
+	const auto p_hist = L.add<uint32_t>(kDisplayBins);
+	const auto p_ws = L.bytes(display_workspace_bytes(n)), p_out = L.bytes(display_out_bytes(o));
+	const auto p_in = L.add<float>(3 * n);
+	if (L.total() > s->d_display_bytes) { // grown for larger frames only; the state is kept on the host side meanwhile
 		rt_display_state keep{};
 		if (s->d_display && s->display_has_state)
-			HIP_TRY(hipMemcpy(&keep, s->d_display, sizeof keep, hipMemcpyDeviceToHost));
-		rc = grow_device_buffer(s->d_display, s->d_display_bytes, (size_t)total);
-		if (rc != RT_OK)
-			return rc;
+			HIP_TRY(hipMemcpy(&keep, s->d_display, sizeof keep, hipMemcpyDeviceToHost)); // (the state is the first part)
+		RT_TRY(grow_device_buffer(s->d_display, s->d_display_bytes, L));
 		HIP_TRY(hipMemcpy(s->d_display, &keep, sizeof keep, hipMemcpyHostToDevice));
 	}
-	char *base = s->d_display;
-	rt_display_state *d_state = reinterpret_cast<rt_display_state *>(base);
-	uint32_t *d_hist = reinterpret_cast<uint32_t *>(base + off_hist);
+	L.base = s->d_display;
+	rt_display_state *d_state = L.at(p_state);
 	const bool fresh = !s->display_has_state || o->width != s->display_w || o->height != s->display_h;
 	s->display_has_state = false; // until this call has succeeded
 	Staging st{s};
 	if (fresh)
 		st.e = hipMemsetAsync(d_state, 0, sizeof(rt_display_state), s->stream);
-	st.to_device(base + off_in, host_rgb, 12 * n);
+	st.put(L, p_in, host_rgb);
 	if (!st.ok())
 		return st.finish("display upload");
-	st.rc = rt_display_device(s, reinterpret_cast<const float *>(base + off_in), o, d_state, base + off_ws, base + off_out, d_hist,
-	                          s->stream);
-	st.download(host_out, base + off_out, display_out_bytes(o));
-	st.download(host_state, d_state, sizeof(rt_display_state));
-	st.download(host_histogram, d_hist, 4ull * kDisplayBins);
+	st.rc = rt_display_device(s, L.at(p_in), o, d_state, L.at(p_ws), L.at(p_out), L.at(p_hist), s->stream);
+	st.get(host_out, L, p_out);
+	st.get(host_state, L, p_state);
+	st.get(host_histogram, L, p_hist);
 	rc = st.finish("display");
 	if (rc == RT_OK) {
 		s->display_has_state = true;
@@ -1819,22 +1780,18 @@ static DevDofParams dof_params(const rt_dof_opts *o, uint64_t w, uint64_t h, con
 	return P;
 }
 
-// the scene's buffer for a frame of n pixels: workspace, output, CoC plane, frame, depth, every part 16-byte aligned
+// the scene's buffer for a frame of n pixels: workspace, output, CoC plane, frame, depth
 struct DofFrames {
 	char *ws;
 	float *out, *coc, *rgb, *depth;
 };
 static int dof_frames(rt_scene *s, uint64_t n, DofFrames *F)
 {
-	auto up16 = [](uint64_t b) { return (b + 15u) / 16u * 16u; };
-	const uint64_t off_out = dof_workspace_bytes(n), off_coc = off_out + up16(12 * n), off_rgb = off_coc + up16(4 * n),
-	               off_depth = off_rgb + up16(12 * n);
-	const int rc = grow_device_buffer(s->d_dof, s->d_dof_bytes, (size_t)(off_depth + 4 * n));
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_dof;
-	*F = DofFrames{base, reinterpret_cast<float *>(base + off_out), reinterpret_cast<float *>(base + off_coc),
-	               reinterpret_cast<float *>(base + off_rgb), reinterpret_cast<float *>(base + off_depth)};
+	Layout L;
+	const auto p_ws = L.bytes(dof_workspace_bytes(n));
+	const auto p_out = L.add<float>(3 * n), p_coc = L.add<float>(n), p_rgb = L.add<float>(3 * n), p_depth = L.add<float>(n);
+	RT_TRY(grow_device_buffer(s->d_dof, s->d_dof_bytes, L));
+	*F = DofFrames{L.at(p_ws), L.at(p_out), L.at(p_coc), L.at(p_rgb), L.at(p_depth)};
 	return RT_OK;
 }
 
@@ -1945,12 +1902,7 @@ int rt_render_dof(rt_scene *s, const rt_camera *camera, const rt_render_opts *o,
 	st.rc = rt_render_device(s, camera, o, F.rgb, nullptr, s->stream);
 	if (st.ok())
 		st.e = hipSetDevice(s->device);
-	if (st.ok()) {
-		rt_aov_buffers aov;
-		std::memset(&aov, 0, sizeof aov);
-		aov.depth = F.depth;
-		st.rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
-	}
+	enqueue_guides(s, camera, o, nullptr, nullptr, F.depth, st);
 	if (st.ok())
 		st.e = launch_dof(s->stream, dof_params(dopts, o->width, o->height, camera, F.rgb, F.depth, F.ws, F.out, nullptr));
 	st.download(out, F.out, 12 * n);
@@ -2073,22 +2025,19 @@ int rt_bloom(rt_scene *s, const float *host_rgb, const rt_bloom_opts *o, const r
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
 	const uint64_t n = (uint64_t)o->width * o->height;
-	// state (16), workspace (a multiple of 16), output, input: every part 16-byte aligned
-	auto up16 = [](uint64_t b) { return (b + 15u) / 16u * 16u; };
-	const uint64_t off_ws = 16, off_out = off_ws + bloom_levels(o->width, o->height, o->levels).bytes, off_in = off_out + up16(12 * n);
-	rc = grow_device_buffer(s->d_bloom, s->d_bloom_bytes, (size_t)(off_in + 12 * n));
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_bloom;
+	// the state if given, workspace, output, input
+	Layout L;
+	const auto p_state = L.optional<rt_display_state>(host_state, 1);
+	const auto p_ws = L.bytes(bloom_levels(o->width, o->height, o->levels).bytes);
+	const auto p_out = L.add<float>(3 * n), p_in = L.add<float>(3 * n);
+	RT_TRY(grow_device_buffer(s->d_bloom, s->d_bloom_bytes, L));
 	Staging st{s};
-	st.to_device(base, host_state, sizeof(rt_display_state));
-	st.to_device(base + off_in, host_rgb, 12 * n);
+	st.put(L, p_state, host_state);
+	st.put(L, p_in, host_rgb);
 	if (!st.ok())
 		return st.finish("bloom upload");
-	st.rc = rt_bloom_device(s, reinterpret_cast<const float *>(base + off_in), o,
-	                        host_state ? reinterpret_cast<const rt_display_state *>(base) : nullptr, base + off_ws,
-	                        reinterpret_cast<float *>(base + off_out), s->stream);
-	st.download(host_out, base + off_out, 12 * n);
+	st.rc = rt_bloom_device(s, L.at(p_in), o, L.at(p_state), L.at(p_ws), L.at(p_out), s->stream);
+	st.get(host_out, L, p_out);
 	return st.finish("bloom");
 }
 
@@ -2183,28 +2132,27 @@ int rt_upscale(rt_scene *s, const rt_upscale_inputs *in, const rt_upscale_opts *
 	if (rc != RT_OK)
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
-	const size_t n = (size_t)o->src_width * o->src_height, N = (size_t)o->dst_width * o->dst_height;
-	// out first, then the inputs given, in rt_upscale_inputs order, then the stage map (bytes)
-	Staging st{s, 3 * N};
-	st.add(in->color, 3 * n);
-	st.add(in->src_albedo, 3 * n);
-	st.add(in->src_normal, 3 * n);
-	st.add(in->src_depth, n);
-	st.add(in->dst_albedo, 3 * N);
-	st.add(in->dst_normal, 3 * N);
-	st.add(in->dst_depth, N);
-	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, st.total * 4 + N); // shared with rt_denoise / rt_render_denoised
-	if (rc != RT_OK)
-		return rc;
-	char *base = s->d_denoise;
-	float *d_out = reinterpret_cast<float *>(base);
-	uint8_t *d_stage = reinterpret_cast<uint8_t *>(base + st.total * 4);
-	if (!st.upload(base))
+	const uint64_t n = (uint64_t)o->src_width * o->src_height, N = (uint64_t)o->dst_width * o->dst_height;
+	// out first, then the inputs given, in rt_upscale_inputs order, then the stage map if asked for
+	const void *host[7] = {in->color, in->src_albedo, in->src_normal, in->src_depth, in->dst_albedo, in->dst_normal, in->dst_depth};
+	const uint64_t floats[7] = {3 * n, 3 * n, 3 * n, n, 3 * N, 3 * N, N};
+	Layout L;
+	const auto p_out = L.add<float>(3 * N);
+	Layout::Part<float> p_in[7];
+	for (int c = 0; c < 7; ++c)
+		p_in[c] = L.optional<float>(host[c], floats[c]);
+	const auto p_stage = L.optional<uint8_t>(stage, N);
+	RT_TRY(grow_device_buffer(s->d_denoise, s->d_denoise_bytes, L)); // shared with rt_denoise / rt_render_denoised
+	Staging st{s};
+	for (int c = 0; c < 7; ++c)
+		st.put(L, p_in[c], host[c]);
+	if (!st.ok())
 		return st.finish("upscale upload");
-	const rt_upscale_inputs d_in = {st.at(base, 0), st.at(base, 1), st.at(base, 2), st.at(base, 3), st.at(base, 4), st.at(base, 5), st.at(base, 6)};
-	st.rc = rt_upscale_device(s, &d_in, o, d_out, stage ? d_stage : nullptr, s->stream);
-	st.download(out, d_out, 3 * N * 4);
-	st.download(stage, d_stage, N);
+	const rt_upscale_inputs d_in = {L.at(p_in[0]), L.at(p_in[1]), L.at(p_in[2]), L.at(p_in[3]),
+	                                L.at(p_in[4]), L.at(p_in[5]), L.at(p_in[6])};
+	st.rc = rt_upscale_device(s, &d_in, o, L.at(p_out), L.at(p_stage), s->stream);
+	st.get(out, L, p_out);
+	st.get(stage, L, p_stage);
 	return st.finish("upscale");
 }
 
@@ -2219,41 +2167,33 @@ int rt_render_upscaled(rt_scene *s, const rt_camera *camera, const rt_render_opt
 		rc = upscale_opts_check(uopts, w, h, W, H);
 	if (rc != RT_OK)
 		return rc;
-	const size_t n = (size_t)(w * h), N = (size_t)(W * H);
+	const uint64_t n = w * h, N = W * H;
 	if (ranges_overlap(out, 12 * N, out_src, 12 * n))
 		return fail(RT_ERR_INVALID_ARGUMENT, "rt_render_upscaled: out overlaps out_src");
 	rc = need_device(s);
 	if (rc != RT_OK)
 		return rc;
 	HIP_TRY(hipSetDevice(s->device));
-	// rt_render_denoised's frames at the source size (16-byte aligned end), then at the destination size: albedo, normal, depth, out
-	const size_t src_bytes = (denoised_frames_bytes(n) + 15) / 16 * 16;
-	rc = grow_device_buffer(s->d_denoise, s->d_denoise_bytes, src_bytes + 4 * 10 * N);
-	if (rc != RT_OK)
-		return rc;
-	float *d_albedo = reinterpret_cast<float *>(s->d_denoise + src_bytes), *d_normal = d_albedo + 3 * N, *d_depth = d_normal + 3 * N,
-	      *d_out = d_depth + N;
+	// rt_render_denoised's frames at the source size, then at the destination size: albedo, normal, depth, out
+	Layout L;
+	const DenoisedParts P = denoised_parts(L, n);
+	const auto p_albedo = L.add<float>(3 * N), p_normal = L.add<float>(3 * N), p_depth = L.add<float>(N), p_out = L.add<float>(3 * N);
+	RT_TRY(grow_device_buffer(s->d_denoise, s->d_denoise_bytes, L));
+	float *d_albedo = L.at(p_albedo), *d_normal = L.at(p_normal), *d_depth = L.at(p_depth);
 	rt_render_opts os = *o;
 	os.width = w;
 	os.height = h;
 	Staging st{s};
-	const DenoisedFrames F = enqueue_render_denoised(s, camera, &os, dopts, s->d_denoise, st);
+	enqueue_render_denoised(s, camera, &os, dopts, L, P, st);
+	enqueue_guides(s, camera, o, d_albedo, d_normal, d_depth, st);
 	if (st.ok()) {
-		rt_aov_buffers aov;
-		std::memset(&aov, 0, sizeof aov);
-		aov.albedo = d_albedo;
-		aov.normal = d_normal;
-		aov.depth = d_depth;
-		st.rc = rt_render_aov_device(s, camera, o, &aov, s->stream);
-	}
-	if (st.ok()) {
-		const rt_upscale_inputs in = {F.d_clean, F.d_albedo, F.d_normal, F.d_depth, d_albedo, d_normal, d_depth};
-		st.e = launch_upscale(s->stream, upscale_params(uopts, w, h, W, H, in, d_out, nullptr));
+		const rt_upscale_inputs in = {L.at(P.clean), L.at(P.albedo), L.at(P.normal), L.at(P.depth), d_albedo, d_normal, d_depth};
+		st.e = launch_upscale(s->stream, upscale_params(uopts, w, h, W, H, in, L.at(p_out), nullptr));
 	}
 	unsigned long long rays[2] = {0, 0};
-	st.download(out, d_out, 3 * N * 4);
-	st.download(out_src, F.d_clean, 3 * n * 4);
-	st.download(rays, F.d_rays, sizeof rays);
+	st.get(out, L, p_out);
+	st.get(out_src, L, P.clean);
+	st.get(rays, L, P.rays);
 	rc = st.finish("render_upscaled");
 	if (rc == RT_OK && rays_shot)
 		*rays_shot = rays[0] + rays[1];
