@@ -1309,7 +1309,48 @@ int rt_selftest_division(float divisor, float *reciprocal, int *exact);
 #define RT_SELFTEST_LEAN_CLASSES 9
 int rt_selftest_lean(int device, uint64_t n_per_thread, uint64_t seed, uint64_t mismatches[RT_SELFTEST_LEAN_CLASSES]);
 
-/* ---- self-test of the two-sphere kernels' primary walk.  A render of a scene those kernels take (one inner node over two
+/* ---- enumeration of the short forms that rest on what gfx950's v_rcp_f32 / v_sqrt_f32 return (csrc/rt_lean.h).  hipcc's
+ * expansions of `1 / d` and `sqrtf` hold for ANY hardware approximation within 1 ulp; the device's is one fixed function, so
+ * which correction steps ever change a bit is a fact an enumeration ON the device settles.  With operands == NULL the call
+ * runs every form against the plain operator over
+ *   reciprocal forms: all 2^23 significands, both signs, at the binary exponents -81, -60, -24, -1, 0, 1, 24 and 41 (the ends
+ *                     of the tame range of rt_lean.h and between); against `1.0f / d`;
+ *   square-root forms: every float of {+-0} U [2^-96, +inf] U NaN U [-inf, -2^-126] (lean_sqrt's domain: v_sqrt_f32 takes a negative
+ *                     denormal for -0, so those 2^23 - 1 inputs belong to the plain operator); against `sqrtf(x)`;
+ * and reports per form how many inputs it ran, how many results differ in their bits (NaN == NaN) and the first such input in
+ * enumeration order, and for the raw v_sqrt_f32 how often it is exact, one ulp high, one ulp low or further off.  in_use has
+ * bit k set when the render kernels use form k: those forms must show zero mismatches.
+ * With operands != NULL (n_operands in [1, 2^20]) the call runs instead the CALL SITES that guard the forms -- Ray::new of the
+ * two-sphere kernels and of the general kernels -- on directions built from every operand (as each component against tame
+ * others, and as all three) against the plain operators, and counts differing rays in site_mismatches: operands outside the
+ * forms' domains (zeros, denormals, huge, inf, NaN) must take the plain operators there, so these must be zero too. ---- */
+enum {
+	RT_SHORT_FORM_RCP_REFINED = 0, /* v_rcp_f32 and one Newton step: lean_inv_gfx950 */
+	RT_SHORT_FORM_INV_ONE_PAIR = 1, /* ... and one (residual, correction) pair */
+	RT_SHORT_FORM_INV_TWO_PAIRS = 2, /* ... and two: lean_inv, hipcc's expansion minus its identity steps */
+	RT_SHORT_FORM_SQRT_RAW = 3, /* v_sqrt_f32 alone */
+	RT_SHORT_FORM_SQRT_BOTH = 4 /* ... and both one-ulp corrections: lean_sqrt */
+};
+#define RT_SHORT_FORMS 5
+enum { RT_SHORT_SITE_RAY_NEW_PAIR = 0, RT_SHORT_SITE_RAY_NEW_FULL = 1 };
+#define RT_SHORT_SITES 2
+typedef struct rt_short_form_count {
+	uint64_t tested;
+	uint64_t mismatches;
+	uint32_t first_mismatch; /* bits of the first mismatching input (when mismatches != 0) */
+	uint32_t reserved;
+} rt_short_form_count;
+typedef struct rt_short_forms_result {
+	rt_short_form_count form[RT_SHORT_FORMS];
+	uint64_t sqrt_raw_exact, sqrt_raw_high, sqrt_raw_low, sqrt_raw_other;
+	uint64_t site_tested;
+	uint64_t site_mismatches[RT_SHORT_SITES];
+	uint32_t in_use;
+	uint32_t reserved;
+} rt_short_forms_result;
+int rt_selftest_short_forms(int device, const float *operands, uint64_t n_operands, rt_short_forms_result *out);
+
+/* ---- self-test of the two-sphere kernels' primary walk. A render of a scene those kernels take (one inner node over two
  * single-sphere leaves: scenes/rtweekend1.ssml) hands them the terms of the box and sphere tests that depend on the camera's origin
  * and the scene alone -- 28 values, csrc/rt_types.h DevPairPrimary -- computed once on the host.  This call forms them for `origin`
  * as a render would, forms them again ON the scene's device with the plain operators and counts the words that differ (NaN ==

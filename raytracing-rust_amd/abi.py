@@ -515,6 +515,22 @@ class UpscaleInputs(C.Structure):  # rt_upscale_inputs
     _fields_ = [(name, C.POINTER(C.c_float)) for name in UPSCALE_INPUTS]
 
 
+# rt_selftest_short_forms (csrc/rt_lean.h: the forms that rest on what gfx950's v_rcp_f32 / v_sqrt_f32 return)
+SHORT_FORM_NAMES = ("rcp_refined", "inv_one_pair", "inv_two_pairs", "sqrt_raw", "sqrt_both")
+SHORT_SITE_NAMES = ("ray_new_pair", "ray_new_full")
+
+
+class ShortFormCount(C.Structure):  # rt_short_form_count
+    _fields_ = [("tested", C.c_uint64), ("mismatches", C.c_uint64), ("first_mismatch", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ShortFormsResult(C.Structure):  # rt_short_forms_result
+    _fields_ = [("form", ShortFormCount * len(SHORT_FORM_NAMES)),
+                ("sqrt_raw_exact", C.c_uint64), ("sqrt_raw_high", C.c_uint64), ("sqrt_raw_low", C.c_uint64), ("sqrt_raw_other", C.c_uint64),
+                ("site_tested", C.c_uint64), ("site_mismatches", C.c_uint64 * len(SHORT_SITE_NAMES)),
+                ("in_use", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 DISPLAY_OPTIONS = tuple(n for n, _ in DisplayOpts._fields_ if n not in ("width", "height", "reserved"))
 
 # rt_presentation_update: int (*)(void *data, const rt_sampler_progress *, uint64_t samples_done)
@@ -559,6 +575,8 @@ EXPECTED_SIZES = {
     "rt_dof_opts": (DofOpts, 64),
     "rt_upscale_opts": (UpscaleOpts, 56),
     "rt_upscale_inputs": (UpscaleInputs, 56),
+    "rt_short_form_count": (ShortFormCount, 24),
+    "rt_short_forms_result": (ShortFormsResult, 184),
 }
 
 # every symbol include/rt_hip.h declares
@@ -604,6 +622,7 @@ EXPORTED_SYMBOLS = [
     "rt_check_hit",
     "rt_check_hit_index",
     "rt_selftest_lean",
+    "rt_selftest_short_forms",
     "rt_selftest_pair_primary",
     "rt_selftest_sky",
     "rt_render_aov",

@@ -193,6 +193,58 @@ int rt_selftest_lean(int device, uint64_t n_per_thread, uint64_t seed, uint64_t 
 	return RT_OK;
 }
 
+int rt_selftest_short_forms(int device, const float *operands, uint64_t n_operands, rt_short_forms_result *out)
+{
+	if (!out || (operands && (n_operands == 0 || n_operands > (1ull << 20))) || (!operands && n_operands != 0))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (operands NULL with n_operands 0, or 1 to 2^20 operands)");
+	int n_dev = 0;
+	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
+		return fail(RT_ERR_NO_DEVICE, "no such HIP device");
+	HIP_TRY(hipSetDevice(device));
+	// one allocation: the counters in the order of DevShortForms, then the operands
+	constexpr size_t kWords = 2 + RT_SHORT_FORMS + RT_SHORT_FORMS + 4 + 1 + RT_SHORT_SITES;
+	unsigned long long host[kWords] = {};
+	unsigned long long *d = nullptr;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), kWords * sizeof *d + (size_t)n_operands * sizeof(float)));
+	DevShortForms D;
+	D.tested = d;
+	D.mismatches = D.tested + 2;
+	D.first_index = D.mismatches + RT_SHORT_FORMS;
+	D.sqrt_raw = D.first_index + RT_SHORT_FORMS;
+	D.site_tested = D.sqrt_raw + 4;
+	D.site_mismatches = D.site_tested + 1;
+	for (int k = 0; k < RT_SHORT_FORMS; ++k)
+		host[2 + RT_SHORT_FORMS + k] = ~0ull;
+	float *d_operands = reinterpret_cast<float *>(d + kWords);
+	hipError_t e = hipMemcpy(d, host, sizeof host, hipMemcpyHostToDevice);
+	if (e == hipSuccess && operands)
+		e = hipMemcpy(d_operands, operands, (size_t)n_operands * sizeof(float), hipMemcpyHostToDevice);
+	if (e == hipSuccess)
+		e = launch_short_forms(nullptr, D, operands ? d_operands : nullptr, n_operands);
+	if (e == hipSuccess)
+		e = hipMemcpy(host, d, sizeof host, hipMemcpyDeviceToHost);
+	(void)hipFree(d);
+	if (e != hipSuccess)
+		return hip_fail(e, "selftest_short_forms");
+	std::memset(out, 0, sizeof *out);
+	for (int k = 0; k < RT_SHORT_FORMS; ++k) {
+		out->form[k].tested = host[k <= RT_SHORT_FORM_INV_TWO_PAIRS ? 0 : 1];
+		out->form[k].mismatches = host[2 + k];
+		if (out->form[k].mismatches)
+			out->form[k].first_mismatch = short_forms_input_bits(k, host[2 + RT_SHORT_FORMS + k]);
+	}
+	const unsigned long long *raw = host + 2 + 2 * RT_SHORT_FORMS;
+	out->sqrt_raw_exact = raw[0];
+	out->sqrt_raw_high = raw[1];
+	out->sqrt_raw_low = raw[2];
+	out->sqrt_raw_other = raw[3];
+	out->site_tested = raw[4];
+	for (int k = 0; k < RT_SHORT_SITES; ++k)
+		out->site_mismatches[k] = raw[5 + k];
+	out->in_use = short_forms_in_use();
+	return RT_OK;
+}
+
 int rt_selftest_pair_primary(rt_scene *s, const float origin[3], uint32_t *valid, uint64_t *mismatches)
 {
 	if (!s || !origin || !valid || !mismatches)

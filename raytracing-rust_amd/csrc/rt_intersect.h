@@ -29,7 +29,8 @@ struct Ray {
 // [2^-60, 2^20] and the squared length lies in [2^-40, 2^40] (every ray a render produces, bar the exactly axis-parallel
 // ones) all operands below are tame in the sense of rt_lean.h -- length in [2^-20, 2^20], normalised components in
 // [2^-81, 1], numerators 1 or such components -- so the short forms return the bits of the plain operators; any other
-// direction takes the plain operators.
+// direction takes the plain operators.  The two-sphere kernels form 1 / component by the reciprocal proven for gfx950
+// (rt_lean.h lean_inv_gfx950), the others by lean_inv.
 template <class F> __device__ __forceinline__ Ray ray_new(V3 origin, V3 direction)
 {
 	Ray r;
@@ -42,7 +43,7 @@ template <class F> __device__ __forceinline__ Ray ray_new(V3 origin, V3 directio
 	if (__builtin_expect(smallest >= 0x1p-60f && m2 >= 0x1p-40f && m2 <= 0x1p40f, 1)) {
 		direction = lean_div3(direction, lean_sqrt(m2));
 		r.d = direction;
-		r.inv = v3(lean_inv(direction.x), lean_inv(direction.y), lean_inv(direction.z));
+		r.inv = v3(lean_inv_for<F::pair>(direction.x), lean_inv_for<F::pair>(direction.y), lean_inv_for<F::pair>(direction.z));
 		if (F::tri) {
 			const float ax = fabsf(direction.x), ay = fabsf(direction.y), az = fabsf(direction.z);
 			const bool swap = (ax > ay && ax > az) || (ay > az);
@@ -119,8 +120,9 @@ __device__ __forceinline__ bool aabb_does_int_from(const float dmin[3], const fl
 	return aabb_slabs([&](int axis, bool upper) { return upper ? dmax[axis] : dmin[axis]; }, inv, tmin_out);
 }
 
-// sqrtf; the short form of rt_lean.h where the argument is in its range (>= 2^-96; zero, negatives and NaN too), the plain
-// operator for the tiny positives in between
+// sqrtf of a sum of squares or of a max(., 0) (rt_shade.h prim_sample_visible_from_point): zero, positive or NaN, never one of the
+// negative denormals rt_lean.h's short form is wrong for.  The short form where the argument is in its range (>= 2^-96, zero or
+// NaN), the plain operator for the tiny positives in between
 __device__ __forceinline__ float sqrt_from_(float x)
 {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(RT_NO_LEAN)

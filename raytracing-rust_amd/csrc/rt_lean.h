@@ -106,6 +106,13 @@ RT_FN float div_by_verified(float x, float c, float rc)
 // reciprocals are the compile-time IEEE quotients
 constexpr float kRcpPi = 1.0f / RT_PI, kRcpTau = 1.0f / RT_TAU;
 
+// which form of 1 / d Ray::new takes (lean_inv_for below): the two-sphere kernels the reciprocal proven for gfx950, the others keep
+// lean_inv, instruction for instruction (they sit on guarded register budgets, tests/test_resource_table.py, and have not been
+// measured with it).  lean_inv_for selects by this and rt_selftest_short_forms reports its forms "in use" from it (rt_selftest_forms.hip
+// short_forms_in_use), so a kernel moved to another form here is a form the enumeration test then asks zero mismatches of.
+enum class LeanInvForm { two_pairs, refined };
+constexpr LeanInvForm lean_inv_form(bool pair) { return pair ? LeanInvForm::refined : LeanInvForm::two_pairs; }
+
 #if defined(__HIP_DEVICE_COMPILE__)
 // ---- device: hipcc's f32 division and square root without the identity steps (see the header comment) ----
 
@@ -141,6 +148,19 @@ __device__ __forceinline__ float lean_inv(float d)
 	const float e2 = __builtin_fmaf(-d, q1, 1.0f);
 	return __builtin_fmaf(e2, r1, q1);
 }
+// 1 / d, d tame, ON GFX950: the refined reciprocal IS the quotient.  hipcc's expansion (lean_inv) must hold for any v_rcp_f32
+// within 1 ulp and therefore corrects r1 twice; gfx950's v_rcp_f32 is one fixed function, and 1 / d is scale-invariant while
+// nothing leaves the normal range, so the 2^23 significands decide whether a correction ever changes a bit.  None does:
+// rt_selftest_short_forms (rt_selftest_forms.hip) runs r1, r1 with one correction pair and lean_inv against `1.0f / d` ON THE
+// DEVICE over every significand, both signs, at the exponents -81, -60, -24, -1, 0, 1, 24 and 41 (the ends of the tame range and
+// between) -- 134 217 728 inputs, no mismatch for any of the three (profiles/r07_short_forms_enumeration.txt);
+// tests/test_gpu_short_forms.py asserts it on every build.  Three instructions instead of seven.  A statement about gfx950 only.
+__device__ __forceinline__ float lean_inv_gfx950(float d) { return lean_rcp_refined(d); }
+// the one lean_inv_form names for the feature set
+template <bool PAIR> __device__ __forceinline__ float lean_inv_for(float d)
+{
+	return lean_inv_form(PAIR) == LeanInvForm::refined ? lean_inv_gfx950(d) : lean_inv(d);
+}
 // v / d componentwise with ONE refined reciprocal; v's components and d tame
 __device__ __forceinline__ V3 lean_div3(V3 v, float d)
 {
@@ -155,7 +175,10 @@ __device__ __forceinline__ V3 lean_div3_fix(V3 v, float d)
 	          __builtin_amdgcn_div_fixupf(lean_div_core(v.z, d, r1), d, v.z)};
 }
 
-// sqrtf(x) for x in {+-0} U [2^-96, +inf] U NaN U negatives: v_sqrt_f32 (1 ulp) and the expansion's two one-ulp corrections.
+// sqrtf(x) for x in {+-0} U [2^-96, +inf] U NaN U [-inf, -2^-126]: v_sqrt_f32 (1 ulp) and the expansion's two one-ulp corrections.
+// NOT the negative denormals: v_sqrt_f32 takes them for -0 and returns -0 where sqrtf returns NaN (all 2^23 - 1 of them differ).
+// Both corrections are needed on gfx950: over every float of this domain v_sqrt_f32 is one ulp low 283 860 640 times and one ulp
+// high 109 984 times (rt_selftest_short_forms), so neither can be dropped.
 // The 2^32 pre-scale the expansion applies below 2^-96 and its final class test (which returns x itself for +-0 and +inf)
 // are the identity there: for x = +-0 both corrections compare NaN / +-0 residuals and keep v_sqrt's +-0, for +inf they keep inf.
 __device__ __forceinline__ float lean_sqrt(float x)
@@ -191,6 +214,8 @@ RT_FN V3 lean_div3(V3 v, float d) { return v / d; }
 RT_FN V3 lean_div3_fix(V3 v, float d) { return v / d; }
 RT_FN float lean_sqrt(float x) { return sqrtf(x); }
 constexpr float kLeanSqrtMin = 0x1p-96f;
+RT_FN float lean_inv_gfx950(float d) { return 1.0f / d; }
+template <bool PAIR> RT_FN float lean_inv_for(float d) { return 1.0f / d; }
 RT_FN float lean_atan2(float y, float x) { return lean_atan2_portable(y, x); }
 RT_FN float lean_acos_dev(float x) { return lean_acos(x); }
 #endif

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "../../include/rt_hip.h"
 #include "rt_types.h"
 
 namespace rt {
@@ -24,5 +25,20 @@ struct DevSkySelftest {
 // the dynamic LDS the kernel needs with the tables staged (render_kernel's prologue layout: rows, marginal, padding to 16 bytes, guides)
 size_t sky_selftest_lds_bytes(const DevScene &S);
 hipError_t launch_sky_selftest(bool tables_in_lds, hipStream_t stream, const DevScene &S, const DevSkySelftest &P);
+
+
+// rt_selftest_short_forms (rt_selftest_forms.hip): the device-side counters, zeroed by the caller except first_index (all ones)
+constexpr uint32_t kShortFormsRcpExponentCount = 8;
+struct DevShortForms {
+	unsigned long long *tested;          // [2]: reciprocal inputs, square-root inputs
+	unsigned long long *mismatches;      // [RT_SHORT_FORMS]
+	unsigned long long *first_index;     // [RT_SHORT_FORMS]: smallest enumeration index that mismatched
+	unsigned long long *sqrt_raw;        // [4]: exact, one ulp high, one ulp low, further off
+	unsigned long long *site_tested;     // [1]
+	unsigned long long *site_mismatches; // [RT_SHORT_SITES]
+};
+uint32_t short_forms_input_bits(int form, uint64_t index); // the input the enumeration runs at `index`
+uint32_t short_forms_in_use();                             // bit k: the render kernels use form k
+hipError_t launch_short_forms(hipStream_t stream, const DevShortForms &D, const float *operands, uint64_t n_operands);
 
 } // namespace rt

@@ -7,6 +7,7 @@
 
 #include "rt_shade.h"
 #include "rt_selftest.h"
+#include "rt_selftest_dev.h"
 
 namespace rt {
 
@@ -14,26 +15,11 @@ namespace rt {
 // Operand classes: 0 lean_div, 1 lean_div_fix (numerator may be zero / inf / NaN), 2 lean_inv, 3 lean_div3 (shared reciprocal),
 // 4 lean_sqrt, 5 lean_sincos, 6 lean_acos_dev, 7 lean_atan2, 8 ray_new (fast path and fallback against the plain operators).
 // mismatches[k] counts results whose BITS differ (two NaNs count as equal). ----
-__device__ __forceinline__ bool same_f32(float a, float b) { return __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b); }
 __device__ __forceinline__ float tame_from_bits(uint32_t u, int lo_exp, int hi_exp) // random sign and mantissa, exponent in [lo_exp, hi_exp]
 {
 	const uint32_t span = (uint32_t)(hi_exp - lo_exp + 1);
 	const uint32_t e = (uint32_t)(127 + lo_exp) + ((u >> 23) & 0xFFu) % span;
 	return __uint_as_float((u & 0x807FFFFFu) | (e << 23));
-}
-__device__ __noinline__ Ray ray_new_plain(V3 origin, V3 direction) // the plain operators, kept out of line so nothing is shared with the short form
-{
-	Ray r;
-	direction = direction / mag(direction);
-	r.o = origin;
-	r.d = direction;
-	r.inv = v3(1.0f / direction.x, 1.0f / direction.y, 1.0f / direction.z);
-	const float ax = fabsf(direction.x), ay = fabsf(direction.y), az = fabsf(direction.z);
-	const bool swap = (ax > ay && ax > az) || (ay > az);
-	const float sx = swap ? direction.z : direction.x;
-	const float sz = swap ? direction.x : direction.z;
-	r.shear = v3(-sx / sz, -direction.y / sz, 1.0f / sz);
-	return r;
 }
 __global__ __launch_bounds__(256) void selftest_lean_kernel(uint64_t n_per_thread, uint64_t seed, unsigned long long *__restrict__ mismatches)
 {

@@ -1,0 +1,166 @@
+// rt_selftest_forms.hip -- rt_selftest_short_forms (include/rt_hip.h): the short forms of rt_lean.h that rest on what gfx950's
+// v_rcp_f32 / v_sqrt_f32 return, ENUMERATED against the plain operators on the device, and the call sites that guard them on
+// operands the caller chooses.  Plain grid-stride kernels, integer counters through atomicAdd / atomicMin; no array is indexed by
+// anything but a compile-time constant.  A translation unit of its own: tests/test_sky_resources.py pins the kernels of
+// rt_selftest.hip's bundle by name.
+#include <algorithm>
+
+#include "rt_shade.h"
+#include "rt_selftest.h"
+#include "rt_selftest_dev.h"
+
+namespace rt {
+
+// counts[form] += bad; first[form] = min(first[form], index of the input in enumeration order) -- deterministic whatever the schedule
+struct FormTally {
+	unsigned long long bad[RT_SHORT_FORMS] = {};
+	unsigned long long first[RT_SHORT_FORMS];
+	__device__ FormTally()
+	{
+		for (int k = 0; k < RT_SHORT_FORMS; ++k)
+			first[k] = ~0ull;
+	}
+	__device__ void note(int form, bool differs, unsigned long long index)
+	{
+		if (differs) {
+			bad[form] += 1ull;
+			first[form] = index < first[form] ? index : first[form];
+		}
+	}
+	__device__ void flush(int form, DevShortForms &D) const
+	{
+		if (bad[form]) {
+			atomicAdd(&D.mismatches[form], bad[form]);
+			atomicMin(&D.first_index[form], first[form]);
+		}
+	}
+};
+
+// input `index` of the reciprocal enumeration: exponent slot (index >> 24), sign (bit 23), significand (bits 0-22)
+__host__ __device__ inline uint32_t short_forms_rcp_input(uint64_t index)
+{
+	static_assert(kShortFormsRcpExponentCount == 8, "one case per exponent");
+	int e = 0;
+	switch ((uint32_t)(index >> 24)) { // the ends of rt_lean.h's tame range and between
+	case 0: e = -81; break;
+	case 1: e = -60; break;
+	case 2: e = -24; break;
+	case 3: e = -1; break;
+	case 4: e = 0; break;
+	case 5: e = 1; break;
+	case 6: e = 24; break;
+	default: e = 41; break;
+	}
+	return ((uint32_t)(index >> 23) & 1u) << 31 | (uint32_t)(127 + e) << 23 | ((uint32_t)index & 0x007FFFFFu);
+}
+
+__global__ __launch_bounds__(256) void short_forms_rcp_kernel(DevShortForms D)
+{
+	FormTally T;
+	unsigned long long tested = 0;
+	const uint64_t total = (uint64_t)kShortFormsRcpExponentCount << 24;
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+		const float d = __uint_as_float(short_forms_rcp_input(i));
+		const float want = 1.0f / d;
+		T.note(RT_SHORT_FORM_RCP_REFINED, !same_f32(lean_inv_gfx950(d), want), i);
+		const float r1 = lean_rcp_refined(d);
+		T.note(RT_SHORT_FORM_INV_ONE_PAIR, !same_f32(__builtin_fmaf(__builtin_fmaf(-d, r1, 1.0f), r1, r1), want), i);
+		T.note(RT_SHORT_FORM_INV_TWO_PAIRS, !same_f32(lean_inv(d), want), i);
+		++tested;
+	}
+	atomicAdd(&D.tested[0], tested);
+	T.flush(RT_SHORT_FORM_RCP_REFINED, D);
+	T.flush(RT_SHORT_FORM_INV_ONE_PAIR, D);
+	T.flush(RT_SHORT_FORM_INV_TWO_PAIRS, D);
+}
+
+// every bit pattern of lean_sqrt's stated domain: all but the positives below 2^-96 (bits 1 .. 0x0F7FFFFF) and the negative
+// denormals (0x80000001 .. 0x807FFFFF).  One ulp high means the downward correction is needed somewhere, one ulp low the upward one.
+__global__ __launch_bounds__(256) void short_forms_sqrt_kernel(DevShortForms D)
+{
+	FormTally T;
+	unsigned long long tested = 0, exact = 0, high = 0, low = 0, other = 0;
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (1ull << 32); i += (uint64_t)gridDim.x * blockDim.x) {
+		const uint32_t bits = (uint32_t)i;
+		if ((bits >= 1u && bits < 0x0F800000u) || (bits > 0x80000000u && bits < 0x80800000u))
+			continue;
+		const float x = __uint_as_float(bits);
+		const float want = sqrtf(x);
+		const float raw = __builtin_amdgcn_sqrtf(x);
+		T.note(RT_SHORT_FORM_SQRT_RAW, !same_f32(raw, want), i);
+		T.note(RT_SHORT_FORM_SQRT_BOTH, !same_f32(lean_sqrt(x), want), i);
+		const uint32_t rb = __float_as_uint(raw), wb = __float_as_uint(want);
+		const bool is_exact = same_f32(raw, want);
+		const bool is_high = !is_exact && rb == wb + 1u, is_low = !is_exact && rb + 1u == wb; // (positive finite results: bits order as values)
+		exact += is_exact;
+		high += is_high;
+		low += is_low;
+		other += !(is_exact || is_high || is_low);
+		++tested;
+	}
+	atomicAdd(&D.tested[1], tested);
+	atomicAdd(&D.sqrt_raw[0], exact);
+	atomicAdd(&D.sqrt_raw[1], high);
+	atomicAdd(&D.sqrt_raw[2], low);
+	atomicAdd(&D.sqrt_raw[3], other);
+	T.flush(RT_SHORT_FORM_SQRT_RAW, D);
+	T.flush(RT_SHORT_FORM_SQRT_BOTH, D);
+}
+
+// the call sites on the caller's operands: each operand as the x, y or z component against tame others, and as all three
+template <class F> __device__ __forceinline__ bool ray_new_differs(V3 dir)
+{
+	const Ray a = ray_new<F>(v3s(0.0f), dir), b = ray_new_plain(v3s(0.0f), dir);
+	bool same = same_f32(a.d.x, b.d.x) && same_f32(a.d.y, b.d.y) && same_f32(a.d.z, b.d.z) && same_f32(a.inv.x, b.inv.x) && same_f32(a.inv.y, b.inv.y) &&
+	            same_f32(a.inv.z, b.inv.z);
+	if (F::tri)
+		same = same && same_f32(a.shear.x, b.shear.x) && same_f32(a.shear.y, b.shear.y) && same_f32(a.shear.z, b.shear.z);
+	return !same;
+}
+__global__ __launch_bounds__(256) void short_forms_sites_kernel(DevShortForms D, const float *__restrict__ operands, uint64_t n_operands)
+{
+	unsigned long long tested = 0, bad_pair = 0, bad_full = 0;
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 4u * n_operands; i += (uint64_t)gridDim.x * blockDim.x) {
+		const float x = operands[i >> 2];
+		const uint32_t shape = (uint32_t)i & 3u;
+		const V3 dir = shape == 0u ? v3(x, 0.75f, -0.5f) : (shape == 1u ? v3(-0.5f, x, 0.75f) : (shape == 2u ? v3(0.75f, -0.5f, x) : v3(x, x, x)));
+		bad_pair += ray_new_differs<FeatPair>(dir);
+		bad_full += ray_new_differs<FeatFull>(dir);
+		++tested;
+	}
+	atomicAdd(&D.site_tested[0], tested);
+	if (bad_pair)
+		atomicAdd(&D.site_mismatches[RT_SHORT_SITE_RAY_NEW_PAIR], bad_pair);
+	if (bad_full)
+		atomicAdd(&D.site_mismatches[RT_SHORT_SITE_RAY_NEW_FULL], bad_full);
+}
+
+uint32_t short_forms_input_bits(int form, uint64_t index)
+{
+	return form <= RT_SHORT_FORM_INV_TWO_PAIRS ? short_forms_rcp_input(index) : (uint32_t)index;
+}
+// from the switch the kernels themselves select by (rt_lean.h lean_inv_form, over both values of F::pair); lean_sqrt has one form
+constexpr uint32_t short_form_bit(LeanInvForm f)
+{
+	return 1u << (f == LeanInvForm::refined ? RT_SHORT_FORM_RCP_REFINED : RT_SHORT_FORM_INV_TWO_PAIRS);
+}
+uint32_t short_forms_in_use()
+{
+	return short_form_bit(lean_inv_form(true)) | short_form_bit(lean_inv_form(false)) | 1u << RT_SHORT_FORM_SQRT_BOTH;
+}
+
+hipError_t launch_short_forms(hipStream_t stream, const DevShortForms &D, const float *operands, uint64_t n_operands)
+{
+	if (operands) {
+		const uint32_t blocks = (uint32_t)std::min<uint64_t>((4u * n_operands + 255u) / 256u, 2048u);
+		hipLaunchKernelGGL(short_forms_sites_kernel, dim3(blocks), dim3(256), 0, stream, D, operands, n_operands);
+		return hipGetLastError();
+	}
+	hipLaunchKernelGGL(short_forms_rcp_kernel, dim3(2048), dim3(256), 0, stream, D);
+	if (hipError_t e = hipGetLastError(); e != hipSuccess)
+		return e;
+	hipLaunchKernelGGL(short_forms_sqrt_kernel, dim3(2048), dim3(256), 0, stream, D);
+	return hipGetLastError();
+}
+
+} // namespace rt

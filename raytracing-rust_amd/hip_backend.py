@@ -106,6 +106,23 @@ def selftest_lean(device=0, n_per_thread=64, seed=1):
     return [int(x) for x in out]
 
 
+def selftest_short_forms(device=0, operands=None):
+    """rt_selftest_short_forms.  operands None: the enumeration of every short form of csrc/rt_lean.h that rests on gfx950's
+    v_rcp_f32 / v_sqrt_f32 against the plain operators -- {"forms": {name: (tested, mismatches, first mismatching input's bits or
+    None)}, "sqrt_raw": {"exact", "high", "low", "other"}, "in_use": names of the forms the render kernels use}.  With operands
+    (f32 values): {"sites": {name: mismatches}, "tested": n} of the guarded call sites on directions built from them."""
+    res = abi.ShortFormsResult()
+    if operands is None:
+        _check(lib().rt_selftest_short_forms(C.c_int(device), None, C.c_uint64(0), C.byref(res)))
+        forms = {name: (int(f.tested), int(f.mismatches), int(f.first_mismatch) if f.mismatches else None)
+                 for name, f in zip(abi.SHORT_FORM_NAMES, res.form)}
+        raw = {k: int(getattr(res, "sqrt_raw_" + k)) for k in ("exact", "high", "low", "other")}
+        return {"forms": forms, "sqrt_raw": raw, "in_use": [n for k, n in enumerate(abi.SHORT_FORM_NAMES) if res.in_use >> k & 1]}
+    ops = np.ascontiguousarray(operands, dtype=np.float32).ravel()
+    _check(lib().rt_selftest_short_forms(C.c_int(device), _p(ops, C.c_float), C.c_uint64(ops.size), C.byref(res)))
+    return {"sites": dict(zip(abi.SHORT_SITE_NAMES, (int(x) for x in res.site_mismatches))), "tested": int(res.site_tested)}
+
+
 def selftest_pair_primary(scene, origin):
     """rt_selftest_pair_primary: (valid, mismatches) -- whether a render from `origin` would use the host's block of
     origin-only terms (csrc/rt_types.h DevPairPrimary), and how many of its words differ from the device's own arithmetic."""
