@@ -1350,6 +1350,31 @@ typedef struct rt_short_forms_result {
 } rt_short_forms_result;
 int rt_selftest_short_forms(int device, const float *operands, uint64_t n_operands, rt_short_forms_result *out);
 
+/* ---- self-test of the two-sphere kernels' shadow walk.  Those scenes have no emissive primitive, so every shadow ray is a sky
+ * shadow ray without a limit, and its walk asks of a sphere only whether some t > 0 exists: the kernels answer from signs,
+ * without the square root and the quotient of Sphere::get_int, and send the few rays the signs cannot settle to the full test
+ * (csrc/rt_intersect.h sphere_occludes_unlimited).  This call runs that predicate, and the branch-free full test behind it, next
+ * to Sphere::get_int's `hit && t > 0` ON `device` over the caller's cases -- n_cases in [1, 2^22], each RT_PAIR_SHADOW_CASE_FLOATS
+ * floats: centre (3), radius, ray origin (3), ray direction (3, used as given: not normalised) -- and counts: cases run, cases
+ * where the predicate differs, cases where the full test's branch-free form differs, cases the signs could not settle.  Both
+ * mismatch counts must be zero. ---- */
+enum { RT_PAIR_SHADOW_TESTED = 0, RT_PAIR_SHADOW_MISMATCHES = 1, RT_PAIR_SHADOW_ASKED_MISMATCHES = 2, RT_PAIR_SHADOW_ASKED = 3 };
+#define RT_PAIR_SHADOW_COUNTS 4
+#define RT_PAIR_SHADOW_CASE_FLOATS 10
+int rt_selftest_pair_shadow(int device, const float *cases, uint64_t n_cases, uint64_t counts[RT_PAIR_SHADOW_COUNTS]);
+/* ... and of the walk around that predicate: the two-sphere kernels' whole shadow arm (both box tests, `skip`, the sign step of each
+ * candidate, the cold loop that runs the full test of whichever sphere has to be asked) next to the same arm with the full test of
+ * every candidate, ON `device`, on one two-sphere scene per case -- n_cases in [1, 2^22], each RT_PAIR_SHADOW_WALK_CASE_FLOATS floats:
+ * first sphere (centre, radius), second sphere, ray origin (3), ray direction (3, normalised as Ray::new does), skip (0 none,
+ * 1 the first sphere, 2 the second), one unused; the boxes are centre -+ |radius|.  Counts: cases run, cases where the two arms
+ * differ (must be zero), cases that entered the cold loop, of those the ones where both spheres had to be asked, and the ones
+ * that entered it with the other sphere already known to occlude. ---- */
+enum { RT_PAIR_SHADOW_WALK_TESTED = 0, RT_PAIR_SHADOW_WALK_MISMATCHES = 1, RT_PAIR_SHADOW_WALK_ASKED = 2, RT_PAIR_SHADOW_WALK_ASKED_BOTH = 3,
+       RT_PAIR_SHADOW_WALK_ASKED_WITH_OCCLUDED = 4 };
+#define RT_PAIR_SHADOW_WALK_COUNTS 5
+#define RT_PAIR_SHADOW_WALK_CASE_FLOATS 16
+int rt_selftest_pair_shadow_walk(int device, const float *cases, uint64_t n_cases, uint64_t counts[RT_PAIR_SHADOW_WALK_COUNTS]);
+
 /* ---- self-test of the two-sphere kernels' primary walk. A render of a scene those kernels take (one inner node over two
  * single-sphere leaves: scenes/rtweekend1.ssml) hands them the terms of the box and sphere tests that depend on the camera's origin
  * and the scene alone -- 28 values, csrc/rt_types.h DevPairPrimary -- computed once on the host.  This call forms them for `origin`

@@ -531,6 +531,12 @@ class ShortFormsResult(C.Structure):  # rt_short_forms_result
                 ("in_use", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# rt_selftest_pair_shadow (csrc/rt_intersect.h sphere_occludes_unlimited): floats per case, names of the counts
+PAIR_SHADOW_CASE_FLOATS = 10
+PAIR_SHADOW_COUNT_NAMES = ("tested", "mismatches", "asked_mismatches", "asked")
+PAIR_SHADOW_WALK_CASE_FLOATS = 16
+PAIR_SHADOW_WALK_COUNT_NAMES = ("tested", "mismatches", "asked", "asked_both", "asked_with_occluded")
+
 DISPLAY_OPTIONS = tuple(n for n, _ in DisplayOpts._fields_ if n not in ("width", "height", "reserved"))
 
 # rt_presentation_update: int (*)(void *data, const rt_sampler_progress *, uint64_t samples_done)
@@ -623,6 +629,8 @@ EXPORTED_SYMBOLS = [
     "rt_check_hit_index",
     "rt_selftest_lean",
     "rt_selftest_short_forms",
+    "rt_selftest_pair_shadow",
+    "rt_selftest_pair_shadow_walk",
     "rt_selftest_pair_primary",
     "rt_selftest_sky",
     "rt_render_aov",

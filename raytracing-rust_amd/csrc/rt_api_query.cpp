@@ -245,6 +245,48 @@ int rt_selftest_short_forms(int device, const float *operands, uint64_t n_operan
 	return RT_OK;
 }
 
+// rt_selftest_pair_shadow / _walk: the caller's cases up, one launch, the counters down
+static int run_pair_shadow_cases(int device, const float *cases, uint64_t n_cases, size_t case_floats, uint64_t *counts, int n_counts,
+                                 hipError_t (*launch)(hipStream_t, const float *, uint64_t, unsigned long long *), const char *what)
+{
+	if (!cases || !counts || n_cases == 0 || n_cases > (1ull << 22))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (1 to 2^22 cases)");
+	int n_dev = 0;
+	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
+		return fail(RT_ERR_NO_DEVICE, "no such HIP device");
+	HIP_TRY(hipSetDevice(device));
+	// one allocation: the counters, then the cases
+	constexpr int kMaxCounts = 8;
+	static_assert(RT_PAIR_SHADOW_COUNTS <= kMaxCounts && RT_PAIR_SHADOW_WALK_COUNTS <= kMaxCounts, "counters");
+	unsigned long long host[kMaxCounts] = {};
+	const size_t case_bytes = (size_t)n_cases * case_floats * sizeof(float);
+	unsigned long long *d = nullptr;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof host + case_bytes));
+	float *d_cases = reinterpret_cast<float *>(d + kMaxCounts);
+	hipError_t e = hipMemcpy(d, host, sizeof host, hipMemcpyHostToDevice);
+	if (e == hipSuccess)
+		e = hipMemcpy(d_cases, cases, case_bytes, hipMemcpyHostToDevice);
+	if (e == hipSuccess)
+		e = launch(nullptr, d_cases, n_cases, d);
+	if (e == hipSuccess)
+		e = hipMemcpy(host, d, sizeof host, hipMemcpyDeviceToHost);
+	(void)hipFree(d);
+	if (e != hipSuccess)
+		return hip_fail(e, what);
+	for (int k = 0; k < n_counts; ++k)
+		counts[k] = host[k];
+	return RT_OK;
+}
+int rt_selftest_pair_shadow(int device, const float *cases, uint64_t n_cases, uint64_t counts[RT_PAIR_SHADOW_COUNTS])
+{
+	return run_pair_shadow_cases(device, cases, n_cases, RT_PAIR_SHADOW_CASE_FLOATS, counts, RT_PAIR_SHADOW_COUNTS, launch_pair_shadow, "selftest_pair_shadow");
+}
+int rt_selftest_pair_shadow_walk(int device, const float *cases, uint64_t n_cases, uint64_t counts[RT_PAIR_SHADOW_WALK_COUNTS])
+{
+	return run_pair_shadow_cases(device, cases, n_cases, RT_PAIR_SHADOW_WALK_CASE_FLOATS, counts, RT_PAIR_SHADOW_WALK_COUNTS, launch_pair_shadow_walk,
+	                             "selftest_pair_shadow_walk");
+}
+
 int rt_selftest_pair_primary(rt_scene *s, const float origin[3], uint32_t *valid, uint64_t *mismatches)
 {
 	if (!s || !origin || !valid || !mismatches)

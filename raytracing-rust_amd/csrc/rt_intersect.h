@@ -136,10 +136,15 @@ __device__ __forceinline__ float sqrt_from_(float x)
 // ... with deltap = centre - origin and ddp = dot(r.d, deltap) given and c() = dot(deltap, deltap) - radius * radius asked for where
 // the quotient needs it: formed from the ray's origin (sphere_t), or taken ready-made where the origin is a launch constant
 // (sphere_t_from)
-template <class C> __device__ __forceinline__ bool sphere_t_tail(V3 deltap, float ddp, const C &c, float radius, const Ray &r, float &t)
+// (host + device, as sphere_t and sphere_occludes_unlimited below: tests/cpp/pair_shadow_check.cpp runs them on the CPU)
+RT_FN float sphere_discriminant(V3 deltap, float ddp, float radius, const Ray &r)
 {
 	const V3 remedy_term = deltap - ddp * r.d;
-	const float discriminant = radius * radius - dot(remedy_term, remedy_term);
+	return radius * radius - dot(remedy_term, remedy_term);
+}
+template <class C> RT_FN bool sphere_t_tail(V3 deltap, float ddp, const C &c, float radius, const Ray &r, float &t)
+{
+	const float discriminant = sphere_discriminant(deltap, ddp, radius, r);
 	if (!(discriminant > 0.0f))
 		return false;
 	const float sqrt_val = sqrtf(discriminant); // (the tested short form, sqrt_from_, measured no gain here: its branch costs what it saves)
@@ -156,14 +161,79 @@ template <class C> __device__ __forceinline__ bool sphere_t_tail(V3 deltap, floa
 	t = t1;
 	return true;
 }
-__device__ __forceinline__ bool sphere_t(V3 center, float radius, const Ray &r, float &t)
+RT_FN bool sphere_t(V3 center, float radius, const Ray &r, float &t)
 {
 	const V3 deltap = center - r.o;
 	const float ddp = dot(r.d, deltap);
 	const float deltapdot = dot(deltap, deltap);
 	return sphere_t_tail(deltap, ddp, [&]() { return deltapdot - radius * radius; }, radius, r, t);
 }
-__device__ __forceinline__ bool sphere_t_from(V3 deltap, float c, float radius, const Ray &r, float &t)
+
+// "does this sphere occlude a ray WITHOUT a limit": sphere_t(center, radius, r, t) && t > 0.0f, bit for bit in its answer, without the
+// square root and the quotient.  The sky shadow ray (trace_any with t_limit = NaN) asks exactly this: t itself is never read.
+// Proof, reading sphere_t_tail with discriminant > 0 established (else both return false; a NaN discriminant included), so that
+// sqrt_val = sqrtf(discriminant) lies in (0, +inf]:
+//   * ddp > 0: q = ddp + sqrt_val > 0 (+inf possible), and t0, t1 are q and c / q in some order.  c / q NaN: no swap, t0 = q > 0,
+//     returned.  Otherwise after the swap t0 is the smaller: positive -> returned; not positive -> it was c / q, t1 = q > 0 is
+//     returned.  Either way t > 0: OCCLUDED, whatever c is -- it is not even formed.
+//   * ddp NaN: q, t0, t1 are NaN, every comparison fails, t = NaN is returned and the caller's t > 0 is false: NOT occluded.  (Such
+//     a ddp makes remedy_term and the discriminant NaN, so the case never gets here; the form below still answers it rightly:
+//     NaN is not tame.)
+//   * ddp <= 0 (-0, -inf): q = ddp - sqrt_val < 0, never NaN.  t0 = q is not positive on either side of the swap; if c / q < q both are
+//     negative: false; else the answer is t1 = c / q > 0 (false for a NaN quotient).  With q < 0 that needs c < 0 (-0 gives +0, c >= 0 a
+//     quotient <= 0, NaN a NaN: all false), and for c < 0 it holds unless the quotient rounds to zero or is NaN (c = q = -inf).
+//     TAME: c <= -2^-60 (-inf included), ddp >= -2^59 and |radius| <= 2^59.  remedy_term's square is >= 0, so discriminant <=
+//     RN(radius^2) <= 2^118 and sqrt_val <= |radius| (1 + 2^-23) (or < 2^-62 where radius^2 underflows); |q| = RN(|ddp| + sqrt_val) <=
+//     2^60 (1 + 2^-22), finite.  The exact quotient is >= 2^-60 / (2^60 (1 + 2^-22)) > 2^-121: a normal number, it rounds to a positive
+//     one whether or not denormals are flushed: OCCLUDED.  Any other lane has to ASK the full test (cold: a sphere of radius
+//     above 2^59, or an origin within 2^-60 of the surface in the units of c).
+// Plain C++ over the operators of sphere_t, same spelling of deltap, ddp, c and the discriminant, no contraction.
+// tests/cpp/pair_shadow_check.cpp compares the two on the host (10^7 random cases and a grid of the edges named above),
+// rt_selftest_pair_shadow (rt_selftest_forms.hip) on the device.
+// The bounds as the kernel can afford them: RN(radius^2) <= 2^118 exactly when |radius| <= 2^59 (the next float squares past it), so
+// radius^2 2^-59 (exact, or an underflow towards zero) and -ddp share ONE comparison; neither is NaN where the discriminant is positive.
+RT_FN bool sphere_shadow_is_tame(float ddp, float c, float radius)
+{
+	return fmax_(radius * radius * 0x1p-59f, -ddp) <= 0x1p59f && c <= -0x1p-60f;
+}
+// what the signs say: occluded, or `ask` -- only the full test can tell (never both).  key stands for c, and for "negative and tame"
+// where ddp > 0 (c is not needed there: a lane ahead of a sphere of radius above 2^59 asks as well, which costs time, not
+// correctness -- the full test is right for every lane).  Selects, no branch: on the device each branch saves and restores exec
+// through scalar registers the pair kernels do not have to spare (tests/test_resource_table.py).
+struct ShadowSigns {
+	bool occluded, ask;
+};
+RT_FN ShadowSigns sphere_shadow_signs(V3 center, float radius, const Ray &r)
+{
+	const V3 deltap = center - r.o;
+	const float ddp = dot(r.d, deltap);
+	const float c = dot(deltap, deltap) - radius * radius;
+	const bool root = sphere_discriminant(deltap, ddp, radius, r) > 0.0f;
+	const float key = ddp > 0.0f ? -1.0f : c;
+	const bool sure = root && sphere_shadow_is_tame(ddp, key, radius);
+	return ShadowSigns{sure, root && key < 0.0f && !sure};
+}
+// the full test's own answer to the same question FOR EVERY INPUT, its square root and quotient without its branches (a copy of
+// sphere_t_tail per sphere in the cold path cost the pair kernels spilled SGPRs): after the swap t0 and t1 are q and c / q in some
+// order, a positive t0 is returned, else a t1 that is not <= 0 (positive or NaN), so t > 0 holds exactly when either is positive
+RT_FN bool sphere_occludes_asked(V3 center, float radius, const Ray &r)
+{
+	const V3 deltap = center - r.o;
+	const float ddp = dot(r.d, deltap);
+	const float c = dot(deltap, deltap) - radius * radius;
+	const float discriminant = sphere_discriminant(deltap, ddp, radius, r);
+	const float sqrt_val = sqrtf(discriminant);
+	const float q = ddp > 0.0f ? ddp + sqrt_val : ddp - sqrt_val;
+	return discriminant > 0.0f && (q > 0.0f || c / q > 0.0f);
+}
+RT_FN bool sphere_occludes_unlimited(V3 center, float radius, const Ray &r)
+{
+	const ShadowSigns s = sphere_shadow_signs(center, radius, r);
+	if (__builtin_expect(!s.ask, 1))
+		return s.occluded;
+	return sphere_occludes_asked(center, radius, r);
+}
+RT_FN bool sphere_t_from(V3 deltap, float c, float radius, const Ray &r, float &t)
 {
 	return sphere_t_tail(deltap, dot(r.d, deltap), [&]() { return c; }, radius, r, t);
 }
@@ -943,6 +1013,30 @@ __device__ __forceinline__ bool trace_any(const DevScene &S, const DevScene &SU,
 		float t0, t1, t;
 		const bool h0 = aabb_does_int(n.c0min, n.c0max, r, t0);
 		const bool h1 = aabb_does_int(n.c1min, n.c1max, r, t1);
+		if constexpr (F::sky_shadows_only) {
+			// t_limit is NaN in every call (rt_types.h): the sign question alone (sphere_occludes_unlimited's two steps, with ONE cold
+			// copy of the full test for the lanes either sphere sends there).  The answer is an OR of two side-effect-free tests, so
+			// the second sphere is looked at only where the first does not occlude, as before, and nothing else can show.  (The first
+			// sphere's sign step runs on every lane, its box hit or not, and forms c where ddp > 0 too: the selects that would
+			// spare them are the masks and exec saves the SGPR budget has no room for; c0 discards the answer.)
+			const bool c0 = h0 && ps.slot0 != skip, c1 = h1 && ps.slot1 != skip;
+			const ShadowSigns s0 = sphere_shadow_signs(v3(ps.sphere[0][0], ps.sphere[0][1], ps.sphere[0][2]), ps.sphere[0][3], r);
+			// (one word per lane, not five lane masks: bit 0 occluded, bit 1 / 2 the first / second sphere has to be asked)
+			uint32_t st = c0 ? (s0.occluded ? 1u : s0.ask ? 2u : 0u) : 0u;
+			if (st != 1u && c1) {
+				const ShadowSigns s1 = sphere_shadow_signs(v3(ps.sphere[1][0], ps.sphere[1][1], ps.sphere[1][2]), ps.sphere[1][3], r);
+				st |= s1.occluded ? 1u : s1.ask ? 4u : 0u;
+			}
+			if (__builtin_expect(st < 2u, 1))
+				return st != 0u;
+#pragma unroll 1
+			for (uint32_t k = 0; k < 2u; ++k) { // cold: the full test
+				const V3 center = k == 0u ? v3(ps.sphere[0][0], ps.sphere[0][1], ps.sphere[0][2]) : v3(ps.sphere[1][0], ps.sphere[1][1], ps.sphere[1][2]);
+				if ((st & (2u << k)) != 0u && sphere_occludes_asked(center, k == 0u ? ps.sphere[0][3] : ps.sphere[1][3], r))
+					st |= 1u;
+			}
+			return (st & 1u) != 0u;
+		}
 		if (h0 && ps.slot0 != skip && sphere_t(v3(ps.sphere[0][0], ps.sphere[0][1], ps.sphere[0][2]), ps.sphere[0][3], r, t) && t > 0.0f && !(t >= t_limit))
 			return true;
 		return h1 && ps.slot1 != skip && sphere_t(v3(ps.sphere[1][0], ps.sphere[1][1], ps.sphere[1][2]), ps.sphere[1][3], r, t) && t > 0.0f &&

@@ -41,4 +41,9 @@ uint32_t short_forms_input_bits(int form, uint64_t index); // the input the enum
 uint32_t short_forms_in_use();                             // bit k: the render kernels use form k
 hipError_t launch_short_forms(hipStream_t stream, const DevShortForms &D, const float *operands, uint64_t n_operands);
 
+// rt_selftest_pair_shadow (rt_selftest_forms.hip): n cases of RT_PAIR_SHADOW_CASE_FLOATS floats, counts[RT_PAIR_SHADOW_COUNTS] zeroed by the caller
+hipError_t launch_pair_shadow(hipStream_t stream, const float *cases, uint64_t n_cases, unsigned long long *counts);
+// rt_selftest_pair_shadow_walk: n cases of RT_PAIR_SHADOW_WALK_CASE_FLOATS floats, counts[RT_PAIR_SHADOW_WALK_COUNTS] zeroed by the caller
+hipError_t launch_pair_shadow_walk(hipStream_t stream, const float *cases, uint64_t n_cases, unsigned long long *counts);
+
 } // namespace rt

@@ -1,4 +1,4 @@
-// rt_selftest_forms.hip -- rt_selftest_short_forms (include/rt_hip.h): the short forms of rt_lean.h that rest on what gfx950's
+// rt_selftest_forms.hip -- rt_selftest_pair_shadow (below) and rt_selftest_short_forms (include/rt_hip.h): the short forms of rt_lean.h that rest on what gfx950's
 // v_rcp_f32 / v_sqrt_f32 return, ENUMERATED against the plain operators on the device, and the call sites that guard them on
 // operands the caller chooses.  Plain grid-stride kernels, integer counters through atomicAdd / atomicMin; no array is indexed by
 // anything but a compile-time constant.  A translation unit of its own: tests/test_sky_resources.py pins the kernels of
@@ -133,6 +133,106 @@ __global__ __launch_bounds__(256) void short_forms_sites_kernel(DevShortForms D,
 		atomicAdd(&D.site_mismatches[RT_SHORT_SITE_RAY_NEW_PAIR], bad_pair);
 	if (bad_full)
 		atomicAdd(&D.site_mismatches[RT_SHORT_SITE_RAY_NEW_FULL], bad_full);
+}
+
+// rt_selftest_pair_shadow: the two-sphere kernels' occlusion predicate for a ray without a limit (rt_intersect.h
+// sphere_occludes_unlimited) and the branch-free full test its cold path runs (sphere_occludes_asked), each against
+// sphere_t(...) && t > 0 on the caller's cases: centre, radius, origin, direction -- the direction as given, not normalised
+__global__ __launch_bounds__(256) void pair_shadow_kernel(const float *__restrict__ cases, uint64_t n_cases, unsigned long long *counts)
+{
+	unsigned long long tested = 0, bad = 0, bad_asked = 0, asked = 0;
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_cases; i += (uint64_t)gridDim.x * blockDim.x) {
+		const float *c = cases + i * RT_PAIR_SHADOW_CASE_FLOATS;
+		const V3 center = v3(c[0], c[1], c[2]);
+		const float radius = c[3];
+		Ray r;
+		r.o = v3(c[4], c[5], c[6]);
+		r.d = v3(c[7], c[8], c[9]);
+		r.inv = r.shear = v3s(0.0f); // (no sphere test reads them)
+		float t;
+		const bool want = sphere_t(center, radius, r, t) && t > 0.0f;
+		bad += sphere_occludes_unlimited(center, radius, r) != want;
+		bad_asked += sphere_occludes_asked(center, radius, r) != want;
+		asked += sphere_shadow_signs(center, radius, r).ask;
+		++tested;
+	}
+	atomicAdd(&counts[RT_PAIR_SHADOW_TESTED], tested);
+	if (bad)
+		atomicAdd(&counts[RT_PAIR_SHADOW_MISMATCHES], bad);
+	if (bad_asked)
+		atomicAdd(&counts[RT_PAIR_SHADOW_ASKED_MISMATCHES], bad_asked);
+	if (asked)
+		atomicAdd(&counts[RT_PAIR_SHADOW_ASKED], asked);
+}
+hipError_t launch_pair_shadow(hipStream_t stream, const float *cases, uint64_t n_cases, unsigned long long *counts)
+{
+	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_cases + 255u) / 256u, 2048u);
+	hipLaunchKernelGGL(pair_shadow_kernel, dim3(blocks), dim3(256), 0, stream, cases, n_cases, counts);
+	return hipGetLastError();
+}
+
+// rt_selftest_pair_shadow_walk: trace_any's two-sphere arm AS THE RENDER KERNELS INSTANTIATE IT (FeatPair: sign step, state word,
+// cold loop) next to the same arm with the sign step compiled out (the full test of each candidate, as every other limit takes
+// it), on a two-sphere scene per case: spheres, their boxes (centre -+ |radius|), ray and `skip` from the caller
+struct FeatPairFullShadow : FeatPair {
+	static constexpr bool sky_shadows_only = false;
+};
+constexpr uint32_t kWalkSlot0 = 7u, kWalkSlot1 = 3u; // (any two distinct slots)
+__global__ __launch_bounds__(256) void pair_shadow_walk_kernel(const float *__restrict__ cases, uint64_t n_cases, unsigned long long *counts)
+{
+	unsigned long long tested = 0, bad = 0, asked = 0, asked_both = 0, asked_with_occluded = 0;
+	const DevScene S = {}; // (the two-sphere arm reads neither the scene nor a stack)
+	const StackMem M = {};
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_cases; i += (uint64_t)gridDim.x * blockDim.x) {
+		const float *c = cases + i * RT_PAIR_SHADOW_WALK_CASE_FLOATS;
+		DevPairScene ps = {};
+		for (int k = 0; k < 4; ++k) {
+			ps.sphere[0][k] = c[k];
+			ps.sphere[1][k] = c[4 + k];
+		}
+		for (int k = 0; k < 3; ++k) {
+			ps.c0min[k] = c[k] - fabsf(c[3]); ps.c0max[k] = c[k] + fabsf(c[3]);
+			ps.c1min[k] = c[4 + k] - fabsf(c[7]); ps.c1max[k] = c[4 + k] + fabsf(c[7]);
+		}
+		ps.slot0 = kWalkSlot0;
+		ps.slot1 = kWalkSlot1;
+		const uint32_t skip = c[14] == 1.0f ? kWalkSlot0 : (c[14] == 2.0f ? kWalkSlot1 : kNoPrim);
+		Ray r; // Ray::new with the plain operators (spheres-only: no shear)
+		r.o = v3(c[8], c[9], c[10]);
+		r.d = v3(c[11], c[12], c[13]);
+		r.d = r.d / mag(r.d);
+		r.inv = v3(1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z);
+		r.shear = v3s(0.0f);
+		const float no_limit = __uint_as_float(0x7FC00000u);
+		const bool got = trace_any<FeatPair, false>(S, S, M, r, nullptr, no_limit, skip, ps);
+		const bool want = trace_any<FeatPairFullShadow, false>(S, S, M, r, nullptr, no_limit, skip, ps);
+		bad += got != want;
+		// which lanes the sign step sends into the cold loop, and in what state: the arm's own rule, from its own parts
+		float tb;
+		const bool c0 = aabb_does_int(ps.c0min, ps.c0max, r, tb) && ps.slot0 != skip, c1 = aabb_does_int(ps.c1min, ps.c1max, r, tb) && ps.slot1 != skip;
+		const ShadowSigns s0 = sphere_shadow_signs(v3(c[0], c[1], c[2]), c[3], r), s1 = sphere_shadow_signs(v3(c[4], c[5], c[6]), c[7], r);
+		const bool occ0 = c0 && s0.occluded, ask0 = c0 && s0.ask;
+		const bool occ1 = !occ0 && c1 && s1.occluded, ask1 = !occ0 && c1 && s1.ask;
+		asked += ask0 || ask1;
+		asked_both += ask0 && ask1;
+		asked_with_occluded += (ask0 || ask1) && (occ0 || occ1);
+		++tested;
+	}
+	atomicAdd(&counts[RT_PAIR_SHADOW_WALK_TESTED], tested);
+	if (bad)
+		atomicAdd(&counts[RT_PAIR_SHADOW_WALK_MISMATCHES], bad);
+	if (asked)
+		atomicAdd(&counts[RT_PAIR_SHADOW_WALK_ASKED], asked);
+	if (asked_both)
+		atomicAdd(&counts[RT_PAIR_SHADOW_WALK_ASKED_BOTH], asked_both);
+	if (asked_with_occluded)
+		atomicAdd(&counts[RT_PAIR_SHADOW_WALK_ASKED_WITH_OCCLUDED], asked_with_occluded);
+}
+hipError_t launch_pair_shadow_walk(hipStream_t stream, const float *cases, uint64_t n_cases, unsigned long long *counts)
+{
+	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_cases + 255u) / 256u, 2048u);
+	hipLaunchKernelGGL(pair_shadow_walk_kernel, dim3(blocks), dim3(256), 0, stream, cases, n_cases, counts);
+	return hipGetLastError();
 }
 
 uint32_t short_forms_input_bits(int form, uint64_t index)

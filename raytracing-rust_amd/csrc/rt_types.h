@@ -32,6 +32,7 @@ template <bool TRI, bool LIGHTS, bool CMAT, bool CTEX> struct Feat {
 	static constexpr bool ctex = CTEX;     // Checkered / Image / Perlin textures
 	static constexpr bool pair = false;    // (see FeatPair)
 	static constexpr bool known_materials = false; // (see FeatPair)
+	static constexpr bool sky_shadows_only = false; // (see FeatPair)
 };
 using FeatFull = Feat<true, true, true, true>;
 // The smallest set plus one fact about the TREE: one inner node over two leaves of one primitive each (scenes/rtweekend1.ssml:
@@ -42,9 +43,15 @@ using FeatFull = Feat<true, true, true, true>;
 // Emit (what the loader makes of `sky ( texture ... )`).  A material's type then follows from what a ray hit, and the
 // dependent loads that only looked it up are not compiled in (rt_shade.h, kMatRead).  A two-leaf scene with other materials
 // runs the spheres-only set, which walks such a tree the same way.
+// ... and one about its SHADOW RAYS: without an emissive primitive (lights is false: sample_lights can pick the sky alone,
+// rt_render.hip do_light) every shadow ray is a sky shadow ray, whose limit is "none" (NaN).  Its walk then asks of a sphere only
+// whether some t > 0 exists, never for t, and trace_any's pair arm answers that from signs (rt_intersect.h
+// sphere_occludes_unlimited).  True of the general spheres-only set as well, which keeps the full test for now (it sits on
+// guarded spill budgets and has not been measured with the predicate).
 struct FeatPair : Feat<false, false, false, false> {
 	static constexpr bool pair = true;
 	static constexpr bool known_materials = true;
+	static constexpr bool sky_shadows_only = true;
 };
 
 // child reference: bit 31 clear = inner node index; bit 31 set = leaf, bits 26-30 primitive count

@@ -123,6 +123,30 @@ def selftest_short_forms(device=0, operands=None):
     return {"sites": dict(zip(abi.SHORT_SITE_NAMES, (int(x) for x in res.site_mismatches))), "tested": int(res.site_tested)}
 
 
+def selftest_pair_shadow(cases, device=0):
+    """rt_selftest_pair_shadow: cases (n, 10) f32 -- centre, radius, ray origin, ray direction (as given) -- through the two-sphere
+    kernels' occlusion predicate for a ray without a limit and through Sphere::get_int's `hit && t > 0`, on the GPU:
+    {"tested", "mismatches", "asked_mismatches", "asked"}.  Both mismatch counts must be zero."""
+    cases = np.ascontiguousarray(cases, dtype=np.float32)
+    if cases.ndim != 2 or cases.shape[1] != abi.PAIR_SHADOW_CASE_FLOATS:
+        raise ValueError(f"cases must be (n, {abi.PAIR_SHADOW_CASE_FLOATS}), got {cases.shape}")
+    out = (C.c_uint64 * len(abi.PAIR_SHADOW_COUNT_NAMES))()
+    _check(lib().rt_selftest_pair_shadow(C.c_int(device), _p(cases, C.c_float), C.c_uint64(cases.shape[0]), out))
+    return dict(zip(abi.PAIR_SHADOW_COUNT_NAMES, (int(x) for x in out)))
+
+
+def selftest_pair_shadow_walk(cases, device=0):
+    """rt_selftest_pair_shadow_walk: cases (n, 16) f32 -- first sphere (centre, radius), second sphere, ray origin, ray direction,
+    skip (0 none, 1 first, 2 second), one unused -- through the two-sphere kernels' whole shadow arm and through the same arm with
+    the full test of every candidate, on the GPU: {"tested", "mismatches", "asked", "asked_both", "asked_with_occluded"}."""
+    cases = np.ascontiguousarray(cases, dtype=np.float32)
+    if cases.ndim != 2 or cases.shape[1] != abi.PAIR_SHADOW_WALK_CASE_FLOATS:
+        raise ValueError(f"cases must be (n, {abi.PAIR_SHADOW_WALK_CASE_FLOATS}), got {cases.shape}")
+    out = (C.c_uint64 * len(abi.PAIR_SHADOW_WALK_COUNT_NAMES))()
+    _check(lib().rt_selftest_pair_shadow_walk(C.c_int(device), _p(cases, C.c_float), C.c_uint64(cases.shape[0]), out))
+    return dict(zip(abi.PAIR_SHADOW_WALK_COUNT_NAMES, (int(x) for x in out)))
+
+
 def selftest_pair_primary(scene, origin):
     """rt_selftest_pair_primary: (valid, mismatches) -- whether a render from `origin` would use the host's block of
     origin-only terms (csrc/rt_types.h DevPairPrimary), and how many of its words differ from the device's own arithmetic."""
