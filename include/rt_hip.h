@@ -1350,6 +1350,54 @@ typedef struct rt_short_forms_result {
 } rt_short_forms_result;
 int rt_selftest_short_forms(int device, const float *operands, uint64_t n_operands, rt_short_forms_result *out);
 
+/* ---- enumeration of the short f32 QUOTIENT (csrc/rt_lean.h lean_div_core_gfx950): gfx950's refined reciprocal is RN(1 / d) for every
+ * tame d (above), so one (residual, correction) pair should do where hipcc's expansion spends two.  Whether it does is again a
+ * fact about one fixed function, settled ON the device.  With `slice` != NULL (operands NULL) the call runs the one-pair form, the
+ * two-pair form (lean_div_core) and `n / d` side by side over
+ *   every denominator significand of the slice -- denominators[0 .. n_denominators) when the list is given, else
+ *   first_denominator + [0 .. n_denominators) -- x all 2^23 numerator significands x every (numerator exponent, denominator
+ *   exponent) pair of `exponents` (2 * n_exponent_pairs binary exponents in [-126, 127]), positive operands (round-to-nearest is
+ *   symmetric in the signs); n_denominators * n_exponent_pairs in [1, 2^17]: at most 2^40 quotients a call;
+ * and reports per form how many quotients differ in their bits from `n / d`, and the operands of the first one in enumeration order
+ * (exponent pair, then denominator, then numerator).  in_use has bit k set when the render kernels' guarded divisions use form k
+ * (the compile-time switch lean_div_form): that form must show zero mismatches.
+ * With `operands` != NULL (slice NULL; n_operand_pairs in [1, 2^20] pairs (n, d)) the call runs instead the wrappers and the CALL
+ * SITES that guard the form, as the two-sphere kernels instantiate them, against the plain expressions -- site_mismatches:
+ *   RT_DIV_SITE_FIX, RT_DIV_SITE_DIV3_FIX   lean_div_fix_for / lean_div3_fix_for at n / d, counted only on pairs inside their
+ *                                           stated domain (d tame, n tame or zero / infinite / NaN, exponents less than 96 apart);
+ *   RT_DIV_SITE_MIS_LIGHT_TERM              the light-sampling term te * power_heuristic(l, m) * le / l with n and d in turn as
+ *                                           the pdfs and as components of te;
+ *   RT_DIV_SITE_ATAN2                       atan2(n, d) and atan2(d, n);
+ * operands outside a site's bounds must take the plain operator there, so every count must be zero whatever the operands. ---- */
+enum { RT_DIV_FORM_ONE_PAIR = 0, RT_DIV_FORM_TWO_PAIRS = 1 };
+#define RT_DIV_FORMS 2
+enum { RT_DIV_SITE_FIX = 0, RT_DIV_SITE_DIV3_FIX = 1, RT_DIV_SITE_MIS_LIGHT_TERM = 2, RT_DIV_SITE_ATAN2 = 3 };
+#define RT_DIV_SITES 4
+typedef struct rt_div_forms_slice {
+	const uint32_t *denominators; /* n_denominators significands (low 23 bits), or NULL: a range */
+	uint64_t n_denominators;
+	uint32_t first_denominator; /* the range's first significand (denominators == NULL) */
+	uint32_t reserved;
+	const int32_t *exponents; /* n_exponent_pairs x (numerator exponent, denominator exponent) */
+	uint64_t n_exponent_pairs;
+} rt_div_forms_slice;
+typedef struct rt_div_forms_result {
+	uint64_t tested; /* quotients run per form */
+	uint64_t mismatches[RT_DIV_FORMS];
+	uint32_t first_numerator[RT_DIV_FORMS]; /* bits of the first mismatching operands (when mismatches != 0) */
+	uint32_t first_denominator[RT_DIV_FORMS];
+	uint64_t site_tested;     /* operand pairs run */
+	uint64_t site_in_domain;  /* ... of which inside the wrappers' domain */
+	uint64_t site_mismatches[RT_DIV_SITES];
+	uint32_t in_use;
+	uint32_t reserved;
+} rt_div_forms_result;
+int rt_selftest_div_forms(int device, const rt_div_forms_slice *slice, const float *operands, uint64_t n_operand_pairs, rt_div_forms_result *out);
+/* ... and sky_pdf (csrc/rt_shade.h) as the two-sphere kernels instantiate it next to the default instantiation, at the caller's m
+ * directions (3 * m floats, m in [1, 2^24]) on the scene's sky tables in global memory: out_pdf_pair[j] and out_pdf_default[j].  They
+ * must be equal bit for bit.  Errors as rt_selftest_sky. */
+int rt_selftest_sky_pdf_forms(rt_scene *scene, const float *dirs, uint64_t m, float *out_pdf_pair, float *out_pdf_default);
+
 /* ---- self-test of the two-sphere kernels' shadow walk.  Those scenes have no emissive primitive, so every shadow ray is a sky
  * shadow ray without a limit, and its walk asks of a sphere only whether some t > 0 exists: the kernels answer from signs,
  * without the square root and the quotient of Sphere::get_int, and send the few rays the signs cannot settle to the full test

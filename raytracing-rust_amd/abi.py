@@ -531,6 +531,23 @@ class ShortFormsResult(C.Structure):  # rt_short_forms_result
                 ("in_use", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# rt_selftest_div_forms (csrc/rt_lean.h lean_div_core_gfx950: the quotient with one correction pair, and the sites that guard it)
+DIV_FORM_NAMES = ("one_pair", "two_pairs")
+DIV_SITE_NAMES = ("fix", "div3_fix", "mis_light_term", "atan2")
+
+
+class DivFormsSlice(C.Structure):  # rt_div_forms_slice
+    _fields_ = [("denominators", C.POINTER(C.c_uint32)), ("n_denominators", C.c_uint64), ("first_denominator", C.c_uint32),
+                ("reserved", C.c_uint32), ("exponents", C.POINTER(C.c_int32)), ("n_exponent_pairs", C.c_uint64)]
+
+
+class DivFormsResult(C.Structure):  # rt_div_forms_result
+    _fields_ = [("tested", C.c_uint64), ("mismatches", C.c_uint64 * len(DIV_FORM_NAMES)),
+                ("first_numerator", C.c_uint32 * len(DIV_FORM_NAMES)), ("first_denominator", C.c_uint32 * len(DIV_FORM_NAMES)),
+                ("site_tested", C.c_uint64), ("site_in_domain", C.c_uint64), ("site_mismatches", C.c_uint64 * len(DIV_SITE_NAMES)),
+                ("in_use", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 # rt_selftest_pair_shadow (csrc/rt_intersect.h sphere_occludes_unlimited): floats per case, names of the counts
 PAIR_SHADOW_CASE_FLOATS = 10
 PAIR_SHADOW_COUNT_NAMES = ("tested", "mismatches", "asked_mismatches", "asked")
@@ -583,6 +600,8 @@ EXPECTED_SIZES = {
     "rt_upscale_inputs": (UpscaleInputs, 56),
     "rt_short_form_count": (ShortFormCount, 24),
     "rt_short_forms_result": (ShortFormsResult, 184),
+    "rt_div_forms_slice": (DivFormsSlice, 40),
+    "rt_div_forms_result": (DivFormsResult, 96),
 }
 
 # every symbol include/rt_hip.h declares
@@ -629,6 +648,8 @@ EXPORTED_SYMBOLS = [
     "rt_check_hit_index",
     "rt_selftest_lean",
     "rt_selftest_short_forms",
+    "rt_selftest_div_forms",
+    "rt_selftest_sky_pdf_forms",
     "rt_selftest_pair_shadow",
     "rt_selftest_pair_shadow_walk",
     "rt_selftest_pair_primary",

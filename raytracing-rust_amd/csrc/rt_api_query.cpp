@@ -245,6 +245,110 @@ int rt_selftest_short_forms(int device, const float *operands, uint64_t n_operan
 	return RT_OK;
 }
 
+int rt_selftest_div_forms(int device, const rt_div_forms_slice *slice, const float *operands, uint64_t n_operand_pairs, rt_div_forms_result *out)
+{
+	if (!out || (slice != nullptr) == (operands != nullptr))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (a slice or operands, not both)");
+	if (operands && (n_operand_pairs == 0 || n_operand_pairs > (1ull << 20)))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (1 to 2^20 operand pairs)");
+	if (slice) {
+		if (!slice->exponents || slice->n_denominators == 0 || slice->n_exponent_pairs == 0 || slice->n_denominators > (1ull << 17) ||
+		    slice->n_exponent_pairs > (1ull << 17) || slice->n_denominators * slice->n_exponent_pairs > (1ull << 17))
+			return fail(RT_ERR_INVALID_ARGUMENT, "bad slice (n_denominators * n_exponent_pairs in [1, 2^17])");
+		if (!slice->denominators && (uint64_t)slice->first_denominator + slice->n_denominators > (1ull << 23))
+			return fail(RT_ERR_INVALID_ARGUMENT, "bad slice (the range leaves the 2^23 significands)");
+		for (uint64_t k = 0; k < 2 * slice->n_exponent_pairs; ++k)
+			if (slice->exponents[k] < -126 || slice->exponents[k] > 127)
+				return fail(RT_ERR_INVALID_ARGUMENT, "bad slice (binary exponents in [-126, 127])");
+	}
+	int n_dev = 0;
+	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
+		return fail(RT_ERR_NO_DEVICE, "no such HIP device");
+	HIP_TRY(hipSetDevice(device));
+	// one allocation: the counters, then the operands, or the exponents and the denominator list
+	const uint64_t n_den = slice && slice->denominators ? slice->n_denominators : 0, n_exp = slice ? 2 * slice->n_exponent_pairs : 0;
+	const size_t tail_bytes = operands ? (size_t)n_operand_pairs * 2 * sizeof(float) : (size_t)(n_exp + n_den) * sizeof(uint32_t);
+	unsigned long long host[kDivCounts] = {};
+	for (int k = 0; k < RT_DIV_FORMS; ++k)
+		host[kDivCountFirst + k] = ~0ull;
+	unsigned long long *d = nullptr;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof host + tail_bytes));
+	hipError_t e = hipMemcpy(d, host, sizeof host, hipMemcpyHostToDevice);
+	if (operands) {
+		float *d_pairs = reinterpret_cast<float *>(d + kDivCounts);
+		if (e == hipSuccess)
+			e = hipMemcpy(d_pairs, operands, tail_bytes, hipMemcpyHostToDevice);
+		if (e == hipSuccess)
+			e = launch_div_sites(nullptr, d_pairs, n_operand_pairs, d);
+	} else {
+		int32_t *d_exp = reinterpret_cast<int32_t *>(d + kDivCounts);
+		uint32_t *d_den = reinterpret_cast<uint32_t *>(d_exp + n_exp);
+		if (e == hipSuccess)
+			e = hipMemcpy(d_exp, slice->exponents, n_exp * sizeof(int32_t), hipMemcpyHostToDevice);
+		if (e == hipSuccess && n_den)
+			e = hipMemcpy(d_den, slice->denominators, n_den * sizeof(uint32_t), hipMemcpyHostToDevice);
+		DevDivForms D;
+		D.denominators = n_den ? d_den : nullptr;
+		D.n_denominators = (uint32_t)slice->n_denominators;
+		D.first_denominator = slice->first_denominator;
+		D.exponents = d_exp;
+		D.n_exponent_pairs = (uint32_t)slice->n_exponent_pairs;
+		D.counts = d;
+		if (e == hipSuccess)
+			e = launch_div_forms(nullptr, D);
+	}
+	if (e == hipSuccess)
+		e = hipMemcpy(host, d, sizeof host, hipMemcpyDeviceToHost);
+	(void)hipFree(d);
+	if (e != hipSuccess)
+		return hip_fail(e, "selftest_div_forms");
+	std::memset(out, 0, sizeof *out);
+	out->tested = host[kDivCountTested];
+	for (int k = 0; k < RT_DIV_FORMS; ++k) {
+		out->mismatches[k] = host[kDivCountBad + k];
+		if (slice && out->mismatches[k]) { // the first index back to its operands
+			const unsigned long long index = host[kDivCountFirst + k];
+			const uint64_t pair_index = index >> 23, ep = pair_index / slice->n_denominators, j = pair_index - ep * slice->n_denominators;
+			const uint32_t d_sig = (slice->denominators ? slice->denominators[j] : slice->first_denominator + (uint32_t)j) & 0x007FFFFFu;
+			out->first_numerator[k] = (uint32_t)(127 + slice->exponents[2 * ep]) << 23 | ((uint32_t)index & 0x007FFFFFu);
+			out->first_denominator[k] = (uint32_t)(127 + slice->exponents[2 * ep + 1]) << 23 | d_sig;
+		}
+	}
+	out->site_tested = host[kDivCountSiteTested];
+	out->site_in_domain = host[kDivCountSiteInDomain];
+	for (int k = 0; k < RT_DIV_SITES; ++k)
+		out->site_mismatches[k] = host[kDivCountSiteBad + k];
+	out->in_use = div_forms_in_use();
+	return RT_OK;
+}
+
+int rt_selftest_sky_pdf_forms(rt_scene *s, const float *dirs, uint64_t m, float *out_pdf_pair, float *out_pdf_default)
+{
+	if (!s || !dirs || !out_pdf_pair || !out_pdf_default || m == 0 || m > (1ull << 24))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (1 to 2^24 directions)");
+	if ((s->host.sky.sampler_res_x | s->host.sky.sampler_res_y) == 0u)
+		return fail(RT_ERR_INVALID_ARGUMENT, "the sky is not samplable (sampler_res 0 x 0)");
+	if (int rc = need_device(s); rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	float *d = nullptr; // directions, then both results
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), 5 * m * sizeof(float)));
+	hipError_t e = hipMemcpyAsync(d, dirs, 3 * m * sizeof(float), hipMemcpyHostToDevice, s->stream);
+	if (e == hipSuccess)
+		e = launch_sky_pdf_forms(s->stream, s->dev, d, m, d + 3 * m, d + 4 * m);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(out_pdf_pair, d + 3 * m, m * sizeof(float), hipMemcpyDeviceToHost, s->stream);
+	if (e == hipSuccess)
+		e = hipMemcpyAsync(out_pdf_default, d + 4 * m, m * sizeof(float), hipMemcpyDeviceToHost, s->stream);
+	const hipError_t e_sync = hipStreamSynchronize(s->stream);
+	if (e == hipSuccess)
+		e = e_sync;
+	(void)hipFree(d);
+	if (e != hipSuccess)
+		return hip_fail(e, "selftest_sky_pdf_forms");
+	return RT_OK;
+}
+
 // rt_selftest_pair_shadow / _walk: the caller's cases up, one launch, the counters down
 static int run_pair_shadow_cases(int device, const float *cases, uint64_t n_cases, size_t case_floats, uint64_t *counts, int n_counts,
                                  hipError_t (*launch)(hipStream_t, const float *, uint64_t, unsigned long long *), const char *what)

@@ -112,6 +112,14 @@ constexpr float kRcpPi = 1.0f / RT_PI, kRcpTau = 1.0f / RT_TAU;
 // short_forms_in_use), so a kernel moved to another form here is a form the enumeration test then asks zero mismatches of.
 enum class LeanInvForm { two_pairs, refined };
 constexpr LeanInvForm lean_inv_form(bool pair) { return pair ? LeanInvForm::refined : LeanInvForm::two_pairs; }
+// ... and which form of n / d the bounce path's guarded divisions take: the two-sphere kernels the quotient with ONE correction
+// pair, proven for gfx950 by rt_selftest_div_forms -- lean_div_for and lean_div3_for (no fixup: the test sends zeros to the plain
+// operator) at the light-sampling term (rt_shade.h mis_light_term_short), lean_div_fix_for in atan2's octant fold (lean_atan2_for);
+// lean_div3_fix_for completes the set and is reached by the self-test alone.  The other kernels are not asked -- their sites keep
+// the plain operator, and lean_div* keeps its two pairs wherever it is used today.
+// rt_selftest_div_forms reports the form "in use" from this switch (rt_selftest_forms.hip div_forms_in_use).
+enum class LeanDivForm { two_pairs, one_pair };
+constexpr LeanDivForm lean_div_form(bool pair) { return pair ? LeanDivForm::one_pair : LeanDivForm::two_pairs; }
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // ---- device: hipcc's f32 division and square root without the identity steps (see the header comment) ----
@@ -175,6 +183,44 @@ __device__ __forceinline__ V3 lean_div3_fix(V3 v, float d)
 	          __builtin_amdgcn_div_fixupf(lean_div_core(v.z, d, r1), d, v.z)};
 }
 
+// n / d, both tame, ON GFX950: the quotient from the refined reciprocal with ONE (residual, correction) pair.  hipcc's expansion
+// (lean_div_core) corrects twice because its r1 is only known to be close; on gfx950 r1 IS RN(1 / d) for every tame d
+// (lean_inv_gfx950 above), and with a correctly rounded reciprocal q0 = n * r1, e = fma(-d, q0, n), q = fma(e, r1, q0) is the
+// classical one-step correction.  Theory leaves denominators with an all-ones significand open, so the claim rests on enumeration:
+// rt_selftest_div_forms (rt_selftest_forms.hip) runs this form, lean_div_core and `n / d` side by side ON THE DEVICE; n / d is
+// scale-invariant while nothing leaves the normal range, so all 2^23 x 2^23 significand pairs at exponents (0, 0) decide it, and
+// the ends of the tame range are run for the denominators most likely to differ (profiles/r09_div_forms_enumeration.txt: no
+// mismatch); tests/test_gpu_div_forms.py asserts a slice of it on every build.  Six instructions instead of eight, and four
+// instead of six per further quotient by the same d.  A statement about gfx950 only.
+__device__ __forceinline__ float lean_div_core_gfx950(float n, float d, float r1)
+{
+	const float q0 = n * r1;
+	const float e = __builtin_fmaf(-d, q0, n);
+	return __builtin_fmaf(e, r1, q0);
+}
+// the core lean_div_form names for the feature set
+template <bool PAIR> __device__ __forceinline__ float lean_div_core_for(float n, float d, float r1)
+{
+	return lean_div_form(PAIR) == LeanDivForm::one_pair ? lean_div_core_gfx950(n, d, r1) : lean_div_core(n, d, r1);
+}
+// lean_div, lean_div_fix and lean_div3_fix (same domains) over that core
+template <bool PAIR> __device__ __forceinline__ float lean_div_for(float n, float d) { return lean_div_core_for<PAIR>(n, d, lean_rcp_refined(d)); }
+template <bool PAIR> __device__ __forceinline__ float lean_div_fix_for(float n, float d)
+{
+	return __builtin_amdgcn_div_fixupf(lean_div_core_for<PAIR>(n, d, lean_rcp_refined(d)), d, n);
+}
+template <bool PAIR> __device__ __forceinline__ V3 lean_div3_for(V3 v, float d)
+{
+	const float r1 = lean_rcp_refined(d);
+	return V3{lean_div_core_for<PAIR>(v.x, d, r1), lean_div_core_for<PAIR>(v.y, d, r1), lean_div_core_for<PAIR>(v.z, d, r1)};
+}
+template <bool PAIR> __device__ __forceinline__ V3 lean_div3_fix_for(V3 v, float d)
+{
+	const float r1 = lean_rcp_refined(d);
+	return V3{__builtin_amdgcn_div_fixupf(lean_div_core_for<PAIR>(v.x, d, r1), d, v.x), __builtin_amdgcn_div_fixupf(lean_div_core_for<PAIR>(v.y, d, r1), d, v.y),
+	          __builtin_amdgcn_div_fixupf(lean_div_core_for<PAIR>(v.z, d, r1), d, v.z)};
+}
+
 // sqrtf(x) for x in {+-0} U [2^-96, +inf] U NaN U [-inf, -2^-126]: v_sqrt_f32 (1 ulp) and the expansion's two one-ulp corrections.
 // NOT the negative denormals: v_sqrt_f32 takes them for -0 and returns -0 where sqrtf returns NaN (all 2^23 - 1 of them differ).
 // Both corrections are needed on gfx950: over every float of this domain v_sqrt_f32 is one ulp low 283 860 640 times and one ulp
@@ -201,6 +247,13 @@ __device__ __forceinline__ float lean_atan2(float y, float x)
 {
 	return lean_atan2_with(y, x, [](float n, float d) { return n / d; }, [](float n, float d) { return lean_div_fix(n, d); });
 }
+// ... with the octant fold through the form lean_div_form names (same operands, same domain).  The ratio min / max stays on the
+// plain operator: its operands are whatever the caller's vector holds, and the test that would admit them costs what the short
+// form saves.  PAIR = false is lean_atan2.
+template <bool PAIR> __device__ __forceinline__ float lean_atan2_for(float y, float x)
+{
+	return lean_atan2_with(y, x, [](float n, float d) { return n / d; }, [](float n, float d) { return lean_div_fix_for<PAIR>(n, d); });
+}
 // acos with the short square root: 0.5 * (1 - |x|) is zero, negative, NaN or >= 2^-25
 __device__ __forceinline__ float lean_acos_dev(float x) { return lean_acos_with(x, lean_sqrt(0.5f * (1.0f - fabsf(x)))); }
 #else
@@ -216,6 +269,13 @@ RT_FN float lean_sqrt(float x) { return sqrtf(x); }
 constexpr float kLeanSqrtMin = 0x1p-96f;
 RT_FN float lean_inv_gfx950(float d) { return 1.0f / d; }
 template <bool PAIR> RT_FN float lean_inv_for(float d) { return 1.0f / d; }
+RT_FN float lean_div_core_gfx950(float n, float d, float) { return n / d; }
+template <bool PAIR> RT_FN float lean_div_core_for(float n, float d, float) { return n / d; }
+template <bool PAIR> RT_FN float lean_div_for(float n, float d) { return n / d; }
+template <bool PAIR> RT_FN float lean_div_fix_for(float n, float d) { return n / d; }
+template <bool PAIR> RT_FN V3 lean_div3_for(V3 v, float d) { return v / d; }
+template <bool PAIR> RT_FN V3 lean_div3_fix_for(V3 v, float d) { return v / d; }
+template <bool PAIR> RT_FN float lean_atan2_for(float y, float x) { return lean_atan2_portable(y, x); }
 RT_FN float lean_atan2(float y, float x) { return lean_atan2_portable(y, x); }
 RT_FN float lean_acos_dev(float x) { return lean_acos(x); }
 #endif

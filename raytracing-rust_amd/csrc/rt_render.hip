@@ -748,7 +748,7 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 					const uint32_t n_choices = sky_samplable ? n_l + 1u : n_l;
 					float l_pdf;
 					if (prim == kNoPrim) {
-						l_pdf = div_by_count(sky_pdf(S, T, m_wi), n_choices);
+						l_pdf = div_by_count(sky_pdf<F::pair>(S, T, m_wi), n_choices);
 					} else {
 						const PrimGeom g = load_prim<F>(S, prim);
 						l_pdf = div_by_count(prim_scattering_pdf<F>(g, hit.point, m_wi, nh), n_choices);
@@ -862,7 +862,7 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 			float l_pdf = 0.0f;
 			if (L.shadow_is_sky) { // sample_sky  mis.rs:104-115
 				le = emission_of_hit<F>(S, PS, S.sky.material, true, hit, L.l_wi);
-				l_pdf = sky_pdf(S, T, L.l_wi) * L.pdf_multiplier;
+				l_pdf = sky_pdf<F::pair>(S, T, L.l_wi) * L.pdf_multiplier;
 				valid = true;
 			} else { // sample_light  mis.rs:117-133 (`ray` still is the shadow ray)
 				Hit lh;
@@ -889,8 +889,12 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 			}
 			if (valid) { // mis.rs:39-43
 				const float m_pdf = mat_scattering_pdf<F>(S, mat, hit, wo, L.l_wi, known_path);
-				const float mis_weight = power_heuristic(l_pdf, m_pdf);
-				outp = outp + thr * mat_eval<F>(S, mat, hit, wo, L.l_wi, known_path, PS) * mis_weight * le / l_pdf;
+				if constexpr (F::pair) { // weight and quotients by the guarded short forms (rt_shade.h)
+					outp = outp + mis_light_term_short(thr * mat_eval<F>(S, mat, hit, wo, L.l_wi, known_path, PS), le, l_pdf, m_pdf);
+				} else {
+					const float mis_weight = power_heuristic(l_pdf, m_pdf);
+					outp = outp + thr * mat_eval<F>(S, mat, hit, wo, L.l_wi, known_path, PS) * mis_weight * le / l_pdf;
+				}
 			}
 		}
 		RT_SECTION(10); // SCATTER: the light's contribution

@@ -41,6 +41,21 @@ uint32_t short_forms_input_bits(int form, uint64_t index); // the input the enum
 uint32_t short_forms_in_use();                             // bit k: the render kernels use form k
 hipError_t launch_short_forms(hipStream_t stream, const DevShortForms &D, const float *operands, uint64_t n_operands);
 
+// rt_selftest_div_forms (rt_selftest_forms.hip): device pointers; counts zeroed by the caller except the two first indices (all ones)
+enum { kDivCountTested = 0, kDivCountBad = 1, kDivCountFirst = 1 + RT_DIV_FORMS, kDivCountSiteTested = 1 + 2 * RT_DIV_FORMS, kDivCountSiteInDomain,
+       kDivCountSiteBad, kDivCounts = kDivCountSiteBad + RT_DIV_SITES };
+struct DevDivForms {
+	const uint32_t *denominators; // or null: first_denominator + j
+	uint32_t n_denominators, first_denominator;
+	const int32_t *exponents;
+	uint32_t n_exponent_pairs;
+	unsigned long long *counts; // [kDivCounts]; a first index is (exponent pair * n_denominators + denominator) << 23 | numerator significand
+};
+uint32_t div_forms_in_use(); // bit k: the render kernels' guarded divisions use form k
+hipError_t launch_div_forms(hipStream_t stream, const DevDivForms &D);
+hipError_t launch_div_sites(hipStream_t stream, const float *operand_pairs, uint64_t n_pairs, unsigned long long *counts);
+hipError_t launch_sky_pdf_forms(hipStream_t stream, const DevScene &S, const float *dirs, uint64_t m, float *out_pair, float *out_default);
+
 // rt_selftest_pair_shadow (rt_selftest_forms.hip): n cases of RT_PAIR_SHADOW_CASE_FLOATS floats, counts[RT_PAIR_SHADOW_COUNTS] zeroed by the caller
 hipError_t launch_pair_shadow(hipStream_t stream, const float *cases, uint64_t n_cases, unsigned long long *counts);
 // rt_selftest_pair_shadow_walk: n cases of RT_PAIR_SHADOW_WALK_CASE_FLOATS floats, counts[RT_PAIR_SHADOW_WALK_COUNTS] zeroed by the caller

@@ -235,6 +235,156 @@ hipError_t launch_pair_shadow_walk(hipStream_t stream, const float *cases, uint6
 	return hipGetLastError();
 }
 
+// rt_selftest_div_forms, the enumeration: a work item is one denominator at one exponent pair against 2^kDivChunkBits consecutive
+// numerator significands; the refined reciprocal is formed once per item, as a shared-reciprocal site forms it
+constexpr uint32_t kDivChunkBits = 10;
+__global__ __launch_bounds__(256) void div_forms_kernel(DevDivForms D)
+{
+	unsigned long long tested = 0, bad_one = 0, bad_two = 0, first_one = ~0ull, first_two = ~0ull;
+	const uint32_t chunk_shift = 23u - kDivChunkBits;
+	const uint64_t items = ((uint64_t)D.n_exponent_pairs * D.n_denominators) << chunk_shift;
+	for (uint64_t item = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; item < items; item += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t pair_index = item >> chunk_shift; // exponent pair * n_denominators + denominator
+		const uint32_t chunk = (uint32_t)item & ((1u << chunk_shift) - 1u);
+		const uint32_t e = (uint32_t)(pair_index / D.n_denominators), j = (uint32_t)(pair_index - (uint64_t)e * D.n_denominators);
+		const uint32_t d_sig = (D.denominators ? D.denominators[j] : D.first_denominator + j) & 0x007FFFFFu;
+		const uint32_t n_high = (uint32_t)(127 + D.exponents[2u * e]) << 23;
+		const float d = __uint_as_float((uint32_t)(127 + D.exponents[2u * e + 1u]) << 23 | d_sig);
+		const float r1 = lean_rcp_refined(d);
+		for (uint32_t k = 0; k < (1u << kDivChunkBits); ++k) {
+			const uint32_t n_sig = chunk << kDivChunkBits | k;
+			const float n = __uint_as_float(n_high | n_sig);
+			const float want = n / d;
+			const unsigned long long index = pair_index << 23 | n_sig;
+			if (!same_f32(lean_div_core_gfx950(n, d, r1), want)) {
+				bad_one += 1ull;
+				first_one = index < first_one ? index : first_one;
+			}
+			if (!same_f32(lean_div_core(n, d, r1), want)) {
+				bad_two += 1ull;
+				first_two = index < first_two ? index : first_two;
+			}
+		}
+		tested += 1ull << kDivChunkBits;
+	}
+	atomicAdd(&D.counts[kDivCountTested], tested);
+	if (bad_one) {
+		atomicAdd(&D.counts[kDivCountBad + RT_DIV_FORM_ONE_PAIR], bad_one);
+		atomicMin(&D.counts[kDivCountFirst + RT_DIV_FORM_ONE_PAIR], first_one);
+	}
+	if (bad_two) {
+		atomicAdd(&D.counts[kDivCountBad + RT_DIV_FORM_TWO_PAIRS], bad_two);
+		atomicMin(&D.counts[kDivCountFirst + RT_DIV_FORM_TWO_PAIRS], first_two);
+	}
+}
+hipError_t launch_div_forms(hipStream_t stream, const DevDivForms &D)
+{
+	const uint64_t items = ((uint64_t)D.n_exponent_pairs * D.n_denominators) << (23u - kDivChunkBits);
+	const uint32_t blocks = (uint32_t)std::min<uint64_t>((items + 255u) / 256u, 4096u);
+	hipLaunchKernelGGL(div_forms_kernel, dim3(blocks), dim3(256), 0, stream, D);
+	return hipGetLastError();
+}
+constexpr uint32_t div_form_bit(LeanDivForm f) { return 1u << (f == LeanDivForm::one_pair ? RT_DIV_FORM_ONE_PAIR : RT_DIV_FORM_TWO_PAIRS); }
+// from the switch the sites select by (rt_lean.h lean_div_form): only the two-sphere kernels have such sites
+uint32_t div_forms_in_use() { return div_form_bit(lean_div_form(true)); }
+
+// ... the wrappers and the guarded sites (rt_shade.h) on the caller's (n, d) pairs.  The plain expressions are kept out of line so
+// that nothing is shared with the short forms.
+__device__ __noinline__ V3 mis_light_term_plain(V3 te, V3 le, float l_pdf, float m_pdf)
+{
+	const float a_sq = l_pdf * l_pdf;
+	const float mis_weight = a_sq / (a_sq + m_pdf * m_pdf); // power_heuristic (rt_render.hip)
+	return te * mis_weight * le / l_pdf;
+}
+__device__ __noinline__ V3 div3_plain(V3 v, float d) { return v / d; }
+__device__ __forceinline__ bool same_v3(V3 a, V3 b) { return same_f32(a.x, b.x) && same_f32(a.y, b.y) && same_f32(a.z, b.z); }
+// lean_div_fix's stated domain: d tame, n tame or zero / infinite / NaN, exponents less than 96 apart
+__device__ __forceinline__ bool div_fix_domain(float n, float d)
+{
+	const float an = fabsf(n), ad = fabsf(d);
+	const bool d_tame = ad >= 0x1p-81f && ad <= 0x1p41f;
+	const bool n_tame = an >= 0x1p-81f && an <= 0x1p41f;
+	const int apart = (int)(__float_as_uint(an) >> 23) - (int)(__float_as_uint(ad) >> 23);
+	return d_tame && ((n_tame && apart < 96 && apart > -96) || an == 0.0f || an == INFINITY || n != n);
+}
+__global__ __launch_bounds__(256) void div_sites_kernel(const float *__restrict__ pairs, uint64_t n_pairs, unsigned long long *counts)
+{
+	unsigned long long tested = 0, in_domain = 0, bad_fix = 0, bad_fix3 = 0, bad_mis = 0, bad_atan2 = 0;
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pairs; i += (uint64_t)gridDim.x * blockDim.x) {
+		const float n = pairs[2u * i], d = pairs[2u * i + 1u];
+		if (div_fix_domain(n, d)) {
+			in_domain += 1ull;
+			bad_fix += !same_f32(lean_div_fix_for<true>(n, d), n / d);
+			// (a tame, a zero and an infinite neighbour share the reciprocal)
+			const V3 v = v3(n, 0.0f, -INFINITY);
+			bad_fix3 += !same_v3(lean_div3_fix_for<true>(v, d), div3_plain(v, d));
+		}
+		// the light term: (n, d) as (m_pdf, l_pdf) and the other way round, then as a component of te under tame pdfs (the weight is
+		// 0.5 there, so 2 n reaches the quotient as n), alone and as all three
+		const V3 one = v3s(1.0f), te = v3(1.0f, 0.75f, -0.5f);
+		bool ok = same_v3(mis_light_term_short(te, one, d, n), mis_light_term_plain(te, one, d, n));
+		ok = ok && same_v3(mis_light_term_short(te, one, n, d), mis_light_term_plain(te, one, n, d));
+		const V3 tx = v3(2.0f * n, 0.75f, -0.5f), tz = v3(0.75f, -0.5f, 2.0f * n), ta = v3s(2.0f * n);
+		ok = ok && same_v3(mis_light_term_short(tx, one, 1.0f, 1.0f), mis_light_term_plain(tx, one, 1.0f, 1.0f));
+		ok = ok && same_v3(mis_light_term_short(tz, one, d, d), mis_light_term_plain(tz, one, d, d));
+		ok = ok && same_v3(mis_light_term_short(ta, v3(1.0f, d, -1.0f), 1.0f, 1.0f), mis_light_term_plain(ta, v3(1.0f, d, -1.0f), 1.0f, 1.0f));
+		bad_mis += !ok;
+		bad_atan2 += !(same_f32(lean_atan2_for<true>(n, d), lean_atan2(n, d)) && same_f32(lean_atan2_for<true>(d, n), lean_atan2(d, n)) &&
+		               same_f32(lean_atan2_for<true>(-n, d), rt_atan2f(-n, d)));
+		++tested;
+	}
+	atomicAdd(&counts[kDivCountSiteTested], tested);
+	atomicAdd(&counts[kDivCountSiteInDomain], in_domain);
+	if (bad_fix)
+		atomicAdd(&counts[kDivCountSiteBad + RT_DIV_SITE_FIX], bad_fix);
+	if (bad_fix3)
+		atomicAdd(&counts[kDivCountSiteBad + RT_DIV_SITE_DIV3_FIX], bad_fix3);
+	if (bad_mis)
+		atomicAdd(&counts[kDivCountSiteBad + RT_DIV_SITE_MIS_LIGHT_TERM], bad_mis);
+	if (bad_atan2)
+		atomicAdd(&counts[kDivCountSiteBad + RT_DIV_SITE_ATAN2], bad_atan2);
+}
+hipError_t launch_div_sites(hipStream_t stream, const float *operand_pairs, uint64_t n_pairs, unsigned long long *counts)
+{
+	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_pairs + 255u) / 256u, 2048u);
+	hipLaunchKernelGGL(div_sites_kernel, dim3(blocks), dim3(256), 0, stream, operand_pairs, n_pairs, counts);
+	return hipGetLastError();
+}
+
+// rt_selftest_sky_pdf_forms: sky_pdf as the two-sphere kernels instantiate it and as every other kernel does, tables in global memory
+struct SkyPdfFormsArgs {
+	DevScene S;
+	const float *dirs;
+	uint64_t m;
+	float *out_pair, *out_default;
+};
+__global__ __launch_bounds__(256) void sky_pdf_forms_kernel(const SkyPdfFormsArgs A)
+{
+	SkyTables T;
+	T.row_cdf = A.S.sky.row_cdf;
+	T.marginal_cdf = A.S.sky.marginal_cdf;
+	T.guide = A.S.sky.guide;
+	T.guide_k = A.S.sky.guide_k;
+	T.inv_res = nullptr; // (sky_pdf reads none of the verified reciprocals)
+	for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < A.m; j += (uint64_t)gridDim.x * blockDim.x) {
+		const V3 wi = v3(A.dirs[3 * j], A.dirs[3 * j + 1], A.dirs[3 * j + 2]);
+		A.out_pair[j] = sky_pdf<true>(A.S, T, wi);
+		A.out_default[j] = sky_pdf(A.S, T, wi);
+	}
+}
+hipError_t launch_sky_pdf_forms(hipStream_t stream, const DevScene &S, const float *dirs, uint64_t m, float *out_pair, float *out_default)
+{
+	SkyPdfFormsArgs A;
+	A.S = S;
+	A.dirs = dirs;
+	A.m = m;
+	A.out_pair = out_pair;
+	A.out_default = out_default;
+	const uint32_t blocks = (uint32_t)std::min<uint64_t>((m + 255u) / 256u, 2048u);
+	hipLaunchKernelGGL(sky_pdf_forms_kernel, dim3(blocks), dim3(256), 0, stream, A);
+	return hipGetLastError();
+}
+
 uint32_t short_forms_input_bits(int form, uint64_t index)
 {
 	return form <= RT_SHORT_FORM_INV_TWO_PAIRS ? short_forms_rcp_input(index) : (uint32_t)index;

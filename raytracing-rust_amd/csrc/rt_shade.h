@@ -31,6 +31,42 @@ __device__ __forceinline__ float div_tame_fix_(float n, float d)
 #endif
 }
 
+// ---- the bounce path's divisions as the two-sphere kernels take them (rt_lean.h lean_div_form): each tests its operands and
+// keeps the plain operator on the lanes that fail, so every function returns the bits of the expression it is named after for
+// EVERY input.  rt_selftest_div_forms runs each next to that expression on operands on both sides of every bound. ----
+constexpr float kSitePdfMin = 0x1p-27f, kSitePdfMax = 0x1p20f;  // pdfs: squares in [2^-54, 2^40], their sum at most 2^41
+constexpr float kSiteNumMin = 0x1p-75f, kSiteNumMax = 0x1p41f;  // numerators over a divisor in [2^-27, 2^41]
+// `te * power_heuristic(l_pdf, m_pdf) * le / l_pdf` (mis.rs:39-43; te = throughput x eval).  Two regions in a row, not nested:
+// the weight, then the three quotients by ONE reciprocal.
+//   weight: both pdfs' magnitudes in [2^-27, 2^20] make a_sq in [2^-54, 2^40] and the sum in [a_sq, 2^41]: tame, exponents at most
+//     95 apart.  A zero, NaN or infinite pdf fails a compare and takes the plain operator (which returns the NaN of 0 / 0).
+//   quotients: |l_pdf| in [2^-27, 2^20] by the same test; the numerators' magnitudes in [2^-75, 2^41] (min3 / max3 and two compares)
+//     keep the exponents at most 95 apart.  A zero or infinite component sends the lane to the plain operator, so none needs
+//     v_div_fixup; a NaN component is the one thing min / max do not see, and it comes out NaN from either form.
+__device__ __forceinline__ V3 mis_light_term_short(V3 te, V3 le, float l_pdf, float m_pdf)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(RT_NO_LEAN)
+	const float a_sq = l_pdf * l_pdf;
+	const float sum = a_sq + m_pdf * m_pdf;
+	const float al = fabsf(l_pdf), am = fabsf(m_pdf);
+	const bool pdfs_tame = al >= kSitePdfMin && al <= kSitePdfMax && am >= kSitePdfMin && am <= kSitePdfMax;
+	float w;
+	if (__builtin_expect(pdfs_tame, 1))
+		w = lean_div_for<true>(a_sq, sum);
+	else
+		w = a_sq / sum;
+	const V3 num = te * w * le;
+	const float smallest = fminf(fminf(fabsf(num.x), fabsf(num.y)), fabsf(num.z));
+	const float largest = fmaxf(fmaxf(fabsf(num.x), fabsf(num.y)), fabsf(num.z));
+	if (__builtin_expect(pdfs_tame && smallest >= kSiteNumMin && largest <= kSiteNumMax, 1))
+		return lean_div3_for<true>(num, l_pdf);
+	return num / l_pdf;
+#else
+	const float a_sq = l_pdf * l_pdf;
+	return te * (a_sq / (a_sq + m_pdf * m_pdf)) * le / l_pdf;
+#endif
+}
+
 // ---- utility/mod.rs ----
 __device__ __forceinline__ float next_float(float f) // :51-65
 {
@@ -331,14 +367,17 @@ struct SkyTables {
 __device__ __forceinline__ bool sky_can_sample(const DevScene &S) { return (S.sky.res_x | S.sky.res_y) != 0u; } // sky.rs:61-63
 
 // Sky::pdf  sky.rs:43-60 with Distribution2D::pdf distributions.rs:105-110
-__device__ __forceinline__ float sky_pdf(const DevScene &S, const SkyTables &T, V3 wi)
+// (SHORT: the two-sphere kernels' instantiation -- atan2's octant fold through the one-pair quotient, rt_lean.h lean_atan2_for.  The
+// final division stays plain there too: its numerator is a product of table differences, zero for a zero-pdf cell and without a
+// lower bound otherwise, and the two compares that would admit it cost what the short form saves)
+template <bool SHORT = false> __device__ __forceinline__ float sky_pdf(const DevScene &S, const SkyTables &T, V3 wi)
 {
 	// 1 - z * z is zero, negative, NaN or >= 2^-24: inside the range of the short square root (rt_lean.h)
 	const float sin_theta = sqrt_unit_(1.0f - wi.z * wi.z);
 	if (sin_theta <= 0.0f)
 		return 0.0f;
 	const float theta = lean_acos_dev(wi.z);
-	float phi = lean_atan2(wi.y, wi.x);
+	float phi = SHORT ? lean_atan2_for<true>(wi.y, wi.x) : lean_atan2(wi.y, wi.x);
 	if (phi < 0.0f)
 		phi += 2.0f * kPi;
 	// u = phi / (2 pi) and v = theta / pi only pick a table cell below, and the divisions are by constants: the verified

@@ -123,6 +123,45 @@ def selftest_short_forms(device=0, operands=None):
     return {"sites": dict(zip(abi.SHORT_SITE_NAMES, (int(x) for x in res.site_mismatches))), "tested": int(res.site_tested)}
 
 
+def selftest_div_forms(denominators=None, exponents=((0, 0),), first_denominator=0, n_denominators=None, operands=None, device=0):
+    """rt_selftest_div_forms.  Without operands, the enumeration of the quotient forms of csrc/rt_lean.h against `n / d`: every
+    denominator significand of the list `denominators` (or of the range first_denominator + [0, n_denominators)) x all 2^23
+    numerator significands x every (numerator exponent, denominator exponent) of `exponents` -- {"tested", "forms": {name:
+    (mismatches, (numerator bits, denominator bits) of the first one or None)}, "in_use": names of the forms the render kernels'
+    guarded divisions use}.  With operands ((n, 2) f32 pairs (n, d)): {"tested", "in_domain", "sites": {name: mismatches}} of the
+    wrappers and the guarded call sites on them."""
+    res = abi.DivFormsResult()
+    if operands is not None:
+        ops = np.ascontiguousarray(operands, dtype=np.float32)
+        if ops.ndim != 2 or ops.shape[1] != 2:
+            raise ValueError(f"operands must be (n, 2), got {ops.shape}")
+        _check(lib().rt_selftest_div_forms(C.c_int(device), None, _p(ops, C.c_float), C.c_uint64(ops.shape[0]), C.byref(res)))
+        return {"tested": int(res.site_tested), "in_domain": int(res.site_in_domain),
+                "sites": dict(zip(abi.DIV_SITE_NAMES, (int(x) for x in res.site_mismatches)))}
+    exps = np.ascontiguousarray(exponents, dtype=np.int32).reshape(-1, 2)
+    sl = abi.DivFormsSlice()
+    sl.exponents, sl.n_exponent_pairs = _p(exps, C.c_int32), exps.shape[0]
+    if denominators is not None:
+        dens = np.ascontiguousarray(denominators, dtype=np.uint32).ravel()
+        sl.denominators, sl.n_denominators = _p(dens, C.c_uint32), dens.size
+    else:
+        sl.denominators, sl.n_denominators, sl.first_denominator = None, int(n_denominators), int(first_denominator)
+    _check(lib().rt_selftest_div_forms(C.c_int(device), C.byref(sl), None, C.c_uint64(0), C.byref(res)))
+    forms = {name: (int(res.mismatches[k]), (int(res.first_numerator[k]), int(res.first_denominator[k])) if res.mismatches[k] else None)
+             for k, name in enumerate(abi.DIV_FORM_NAMES)}
+    return {"tested": int(res.tested), "forms": forms, "in_use": [n for k, n in enumerate(abi.DIV_FORM_NAMES) if res.in_use >> k & 1]}
+
+
+def selftest_sky_pdf_forms(scene, dirs):
+    """rt_selftest_sky_pdf_forms: (pdf as the two-sphere kernels instantiate sky_pdf, pdf of the default instantiation) at dirs (m, 3)"""
+    dirs = np.ascontiguousarray(dirs, dtype=np.float32)
+    if dirs.ndim != 2 or dirs.shape[1] != 3:
+        raise ValueError(f"dirs must be (m, 3), got {dirs.shape}")
+    a, b = np.empty(dirs.shape[0], dtype=np.float32), np.empty(dirs.shape[0], dtype=np.float32)
+    _check(lib().rt_selftest_sky_pdf_forms(scene._h, _p(dirs, C.c_float), C.c_uint64(dirs.shape[0]), _p(a, C.c_float), _p(b, C.c_float)))
+    return a, b
+
+
 def selftest_pair_shadow(cases, device=0):
     """rt_selftest_pair_shadow: cases (n, 10) f32 -- centre, radius, ray origin, ray direction (as given) -- through the two-sphere
     kernels' occlusion predicate for a ray without a limit and through Sphere::get_int's `hit && t > 0`, on the GPU:
