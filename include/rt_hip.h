@@ -1398,6 +1398,22 @@ int rt_selftest_div_forms(int device, const rt_div_forms_slice *slice, const flo
  * must be equal bit for bit.  Errors as rt_selftest_sky. */
 int rt_selftest_sky_pdf_forms(rt_scene *scene, const float *dirs, uint64_t m, float *out_pdf_pair, float *out_pdf_default);
 
+/* ---- self-test of the two-sphere kernels' scatter frame and ray normalisation (csrc/rt_shade.h coord_from_z_pair, csrc/
+ * rt_intersect.h ray_new; the compile-time switches lean_frame_form and lean_ray_norm_short of csrc/rt_lean.h).  Runs ON `device`,
+ * over the caller's n_vectors in [1, 2^22] vectors of 3 floats, each vector both as a normal and as a ray direction:
+ *   the frame as the two-sphere kernels' Lambertian bounce forms it next to the plain coord_from_z (x, y and z axes, nine words);
+ *   ray_new<FeatPair>'s direction and reciprocals next to the plain operators (direction / |direction|, 1 / component).
+ * Counts: vectors run; frames that differ in a bit (any NaN equals any NaN); vectors that passed / failed the frame's guard;
+ * rays that differ; vectors that passed / failed ray_new's guard; and RT_FRAME_FORMS_IN_USE, bit RT_FRAME_FORM_FRAME_SHORT set
+ * when the kernels' frame is the guarded short form, bit RT_FRAME_FORM_RAY_NORM_ONE_PAIR when ray_new normalises by the one-pair
+ * quotient.  Vectors that fail a guard must take the plain operators there, so both mismatch counts must be zero whatever the
+ * vectors; this call is the only test of the frame's cold copy, because no scene the host accepts sends a sphere normal there. ---- */
+enum { RT_FRAME_FORMS_TESTED = 0, RT_FRAME_FORMS_FRAME_MISMATCHES = 1, RT_FRAME_FORMS_FRAME_SHORT = 2, RT_FRAME_FORMS_FRAME_PLAIN = 3,
+       RT_FRAME_FORMS_RAY_MISMATCHES = 4, RT_FRAME_FORMS_RAY_SHORT = 5, RT_FRAME_FORMS_RAY_PLAIN = 6, RT_FRAME_FORMS_IN_USE = 7 };
+#define RT_FRAME_FORMS_COUNTS 8
+enum { RT_FRAME_FORM_FRAME_SHORT = 0, RT_FRAME_FORM_RAY_NORM_ONE_PAIR = 1 };
+int rt_selftest_frame_forms(int device, const float *vectors, uint64_t n_vectors, uint64_t counts[RT_FRAME_FORMS_COUNTS]);
+
 /* ---- self-test of the two-sphere kernels' shadow walk.  Those scenes have no emissive primitive, so every shadow ray is a sky
  * shadow ray without a limit, and its walk asks of a sphere only whether some t > 0 exists: the kernels answer from signs,
  * without the square root and the quotient of Sphere::get_int, and send the few rays the signs cannot settle to the full test

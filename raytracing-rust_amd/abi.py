@@ -553,6 +553,9 @@ PAIR_SHADOW_CASE_FLOATS = 10
 PAIR_SHADOW_COUNT_NAMES = ("tested", "mismatches", "asked_mismatches", "asked")
 PAIR_SHADOW_WALK_CASE_FLOATS = 16
 PAIR_SHADOW_WALK_COUNT_NAMES = ("tested", "mismatches", "asked", "asked_both", "asked_with_occluded")
+# rt_selftest_frame_forms (csrc/rt_shade.h coord_from_z_pair, csrc/rt_intersect.h ray_new): names of the counts, and of the bits of "in_use"
+FRAME_FORMS_COUNT_NAMES = ("tested", "frame_mismatches", "frame_short", "frame_plain", "ray_mismatches", "ray_short", "ray_plain", "in_use")
+FRAME_FORM_NAMES = ("frame_guarded_short", "ray_norm_one_pair")
 
 DISPLAY_OPTIONS = tuple(n for n, _ in DisplayOpts._fields_ if n not in ("width", "height", "reserved"))
 
@@ -650,6 +653,7 @@ EXPORTED_SYMBOLS = [
     "rt_selftest_short_forms",
     "rt_selftest_div_forms",
     "rt_selftest_sky_pdf_forms",
+    "rt_selftest_frame_forms",
     "rt_selftest_pair_shadow",
     "rt_selftest_pair_shadow_walk",
     "rt_selftest_pair_primary",

@@ -361,7 +361,7 @@ static int run_pair_shadow_cases(int device, const float *cases, uint64_t n_case
 	HIP_TRY(hipSetDevice(device));
 	// one allocation: the counters, then the cases
 	constexpr int kMaxCounts = 8;
-	static_assert(RT_PAIR_SHADOW_COUNTS <= kMaxCounts && RT_PAIR_SHADOW_WALK_COUNTS <= kMaxCounts, "counters");
+	static_assert(RT_PAIR_SHADOW_COUNTS <= kMaxCounts && RT_PAIR_SHADOW_WALK_COUNTS <= kMaxCounts && RT_FRAME_FORMS_COUNTS <= kMaxCounts, "counters");
 	unsigned long long host[kMaxCounts] = {};
 	const size_t case_bytes = (size_t)n_cases * case_floats * sizeof(float);
 	unsigned long long *d = nullptr;
@@ -389,6 +389,14 @@ int rt_selftest_pair_shadow_walk(int device, const float *cases, uint64_t n_case
 {
 	return run_pair_shadow_cases(device, cases, n_cases, RT_PAIR_SHADOW_WALK_CASE_FLOATS, counts, RT_PAIR_SHADOW_WALK_COUNTS, launch_pair_shadow_walk,
 	                             "selftest_pair_shadow_walk");
+}
+// rt_selftest_frame_forms: the same plumbing, three floats a vector; the switches' report is the host's to fill
+int rt_selftest_frame_forms(int device, const float *vectors, uint64_t n_vectors, uint64_t counts[RT_FRAME_FORMS_COUNTS])
+{
+	const int rc = run_pair_shadow_cases(device, vectors, n_vectors, 3, counts, RT_FRAME_FORMS_COUNTS, launch_frame_forms, "selftest_frame_forms");
+	if (rc == RT_OK)
+		counts[RT_FRAME_FORMS_IN_USE] = frame_forms_in_use();
+	return rc;
 }
 
 int rt_selftest_pair_primary(rt_scene *s, const float origin[3], uint32_t *valid, uint64_t *mismatches)

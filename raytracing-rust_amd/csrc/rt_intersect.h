@@ -30,7 +30,8 @@ struct Ray {
 // ones) all operands below are tame in the sense of rt_lean.h -- length in [2^-20, 2^20], normalised components in
 // [2^-81, 1], numerators 1 or such components -- so the short forms return the bits of the plain operators; any other
 // direction takes the plain operators.  The two-sphere kernels form 1 / component by the reciprocal proven for gfx950
-// (rt_lean.h lean_inv_gfx950), the others by lean_inv.
+// (rt_lean.h lean_inv_gfx950) and the normalised components by the one-pair quotient (lean_div_core_gfx950), the others by
+// lean_inv and lean_div3.
 template <class F> __device__ __forceinline__ Ray ray_new(V3 origin, V3 direction)
 {
 	Ray r;
@@ -41,7 +42,11 @@ template <class F> __device__ __forceinline__ Ray ray_new(V3 origin, V3 directio
 	// (deciding for the WAVE instead -- one untame lane sends all through the plain operators, a scalar branch instead of an
 	// exec-mask region -- measured 0.3 % slower on configs 2 and 3: profiles/r04j_sums_coord_waveguard_ab.log)
 	if (__builtin_expect(smallest >= 0x1p-60f && m2 >= 0x1p-40f && m2 <= 0x1p40f, 1)) {
-		direction = lean_div3(direction, lean_sqrt(m2));
+		// (the two-sphere kernels: the quotient with one correction pair, rt_lean.h lean_ray_norm_short.  No new test of the
+		// operands: the guard above puts the length in [2^-20, 2^20] and every component's magnitude in [2^-60, length], so the
+		// quotients lie in [2^-80, 1] -- inside the domain rt_selftest_div_forms enumerated, operands in [2^-81, 2^41] with
+		// exponents less than 96 apart.  Every other kernel: lean_div3, instruction for instruction)
+		direction = lean_div3_for<lean_ray_norm_short(F::pair)>(direction, lean_sqrt(m2));
 		r.d = direction;
 		r.inv = v3(lean_inv_for<F::pair>(direction.x), lean_inv_for<F::pair>(direction.y), lean_inv_for<F::pair>(direction.z));
 		if (F::tri) {

@@ -120,6 +120,28 @@ constexpr LeanInvForm lean_inv_form(bool pair) { return pair ? LeanInvForm::refi
 // rt_selftest_div_forms reports the form "in use" from this switch (rt_selftest_forms.hip div_forms_in_use).
 enum class LeanDivForm { two_pairs, one_pair };
 constexpr LeanDivForm lean_div_form(bool pair) { return pair ? LeanDivForm::one_pair : LeanDivForm::two_pairs; }
+// ... and two more sites of the two-sphere kernels, each a switch of its own so that each can be built and measured alone
+// (-DRT_PAIR_RAY_NORM_SHORT=0 / -DRT_PAIR_FRAME_SHORT=0 put a site back on its previous form; these kernels sit on a scheduling
+// knife edge, DESIGN section 4, so a site ships only on its own measured gain):
+//   lean_ray_norm_short   Ray::new's normalisation direction / |direction| (rt_intersect.h ray_new, inside the guard it already
+//                         has) through lean_div3_for<true>: the one-pair quotient instead of lean_div3's two pairs;
+//   lean_frame_form       the scatter frame of a Lambertian bounce (rt_shade.h coord_from_z_pair): the arm chosen once by selects
+//                         on the operands, one guard, the short square root, one refined reciprocal and two one-pair quotients;
+//                         lanes that fail the guard run the plain expression.
+// rt_selftest_frame_forms reports both from these switches (rt_selftest_forms.hip frame_forms_in_use).
+// Measured, six interleaved runs each on rtweekend1 (profiles/r10_frame_forms_ab.log; the gate: every run below every parent run and
+// a mean gain of three parent spreads): the frame alone -0.819 ms = 6.0 spreads: ON.  The normalisation alone -0.369 ms = 2.7
+// spreads, and -0.447 ms on top of the frame = 2.8 of that build's spreads: every run below, but short of the gate both times: OFF,
+// ray_new keeps lean_div3 (HISTORY.md).
+#ifndef RT_PAIR_RAY_NORM_SHORT
+#define RT_PAIR_RAY_NORM_SHORT 0
+#endif
+#ifndef RT_PAIR_FRAME_SHORT
+#define RT_PAIR_FRAME_SHORT 1
+#endif
+constexpr bool lean_ray_norm_short(bool pair) { return pair && RT_PAIR_RAY_NORM_SHORT != 0; }
+enum class LeanFrameForm { plain, guarded_short };
+constexpr LeanFrameForm lean_frame_form(bool pair) { return pair && RT_PAIR_FRAME_SHORT != 0 ? LeanFrameForm::guarded_short : LeanFrameForm::plain; }
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // ---- device: hipcc's f32 division and square root without the identity steps (see the header comment) ----

@@ -56,6 +56,11 @@ hipError_t launch_div_forms(hipStream_t stream, const DevDivForms &D);
 hipError_t launch_div_sites(hipStream_t stream, const float *operand_pairs, uint64_t n_pairs, unsigned long long *counts);
 hipError_t launch_sky_pdf_forms(hipStream_t stream, const DevScene &S, const float *dirs, uint64_t m, float *out_pair, float *out_default);
 
+// rt_selftest_frame_forms (rt_selftest_forms.hip): n vectors of 3 floats, counts[RT_FRAME_FORMS_COUNTS] zeroed by the caller (the
+// kernel leaves RT_FRAME_FORMS_IN_USE alone: the caller fills it from frame_forms_in_use)
+uint32_t frame_forms_in_use(); // bit RT_FRAME_FORM_*: what the two-sphere kernels' switches select (rt_lean.h)
+hipError_t launch_frame_forms(hipStream_t stream, const float *vectors, uint64_t n_vectors, unsigned long long *counts);
+
 // rt_selftest_pair_shadow (rt_selftest_forms.hip): n cases of RT_PAIR_SHADOW_CASE_FLOATS floats, counts[RT_PAIR_SHADOW_COUNTS] zeroed by the caller
 hipError_t launch_pair_shadow(hipStream_t stream, const float *cases, uint64_t n_cases, unsigned long long *counts);
 // rt_selftest_pair_shadow_walk: n cases of RT_PAIR_SHADOW_WALK_CASE_FLOATS floats, counts[RT_PAIR_SHADOW_WALK_COUNTS] zeroed by the caller

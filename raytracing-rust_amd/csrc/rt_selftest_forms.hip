@@ -385,6 +385,51 @@ hipError_t launch_sky_pdf_forms(hipStream_t stream, const DevScene &S, const flo
 	return hipGetLastError();
 }
 
+// rt_selftest_frame_forms: the scatter frame and Ray::new's normalisation as the two-sphere kernels' switches select them
+// (rt_lean.h lean_frame_form, lean_ray_norm_short) next to the plain expressions, each vector as a normal and as a direction.
+// The plain frame is kept out of line so that nothing is shared with the short form.
+__device__ __noinline__ Coord coord_from_z_plain(V3 z) { return coord_from_z(z); }
+__device__ __forceinline__ Coord pair_kernels_frame(V3 z)
+{
+	return lean_frame_form(true) == LeanFrameForm::guarded_short ? coord_from_z_pair(z) : coord_from_z(z);
+}
+__global__ __launch_bounds__(256) void frame_forms_kernel(const float *__restrict__ vectors, uint64_t n_vectors, unsigned long long *counts)
+{
+	unsigned long long tested = 0, bad_frame = 0, frame_short = 0, bad_ray = 0, ray_short = 0;
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vectors; i += (uint64_t)gridDim.x * blockDim.x) {
+		const V3 v = v3(vectors[3u * i], vectors[3u * i + 1u], vectors[3u * i + 2u]);
+		const Coord got = pair_kernels_frame(v), want = coord_from_z_plain(v);
+		bad_frame += !(same_v3(got.x, want.x) && same_v3(got.y, want.y) && same_v3(got.z, want.z));
+		const float a = fabsf(v.x) > fabsf(v.y) ? v.x : v.y; // the frame's guard, from its own parts (rt_shade.h)
+		frame_short += frame_guard_(a, v.z, a * a + v.z * v.z);
+		const Ray r = ray_new<FeatPair>(v3s(0.0f), v), p = ray_new_plain(v3s(0.0f), v);
+		bad_ray += !(same_v3(r.d, p.d) && same_v3(r.inv, p.inv));
+		const float m2 = dot(v, v); // ray_new's guard (rt_intersect.h)
+		ray_short += fminf(fminf(fabsf(v.x), fabsf(v.y)), fabsf(v.z)) >= 0x1p-60f && m2 >= 0x1p-40f && m2 <= 0x1p40f;
+		++tested;
+	}
+	atomicAdd(&counts[RT_FRAME_FORMS_TESTED], tested);
+	atomicAdd(&counts[RT_FRAME_FORMS_FRAME_SHORT], frame_short);
+	atomicAdd(&counts[RT_FRAME_FORMS_FRAME_PLAIN], tested - frame_short);
+	atomicAdd(&counts[RT_FRAME_FORMS_RAY_SHORT], ray_short);
+	atomicAdd(&counts[RT_FRAME_FORMS_RAY_PLAIN], tested - ray_short);
+	if (bad_frame)
+		atomicAdd(&counts[RT_FRAME_FORMS_FRAME_MISMATCHES], bad_frame);
+	if (bad_ray)
+		atomicAdd(&counts[RT_FRAME_FORMS_RAY_MISMATCHES], bad_ray);
+}
+hipError_t launch_frame_forms(hipStream_t stream, const float *vectors, uint64_t n_vectors, unsigned long long *counts)
+{
+	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_vectors + 255u) / 256u, 2048u);
+	hipLaunchKernelGGL(frame_forms_kernel, dim3(blocks), dim3(256), 0, stream, vectors, n_vectors, counts);
+	return hipGetLastError();
+}
+uint32_t frame_forms_in_use()
+{
+	return (lean_frame_form(true) == LeanFrameForm::guarded_short ? 1u << RT_FRAME_FORM_FRAME_SHORT : 0u) |
+	       (lean_ray_norm_short(true) ? 1u << RT_FRAME_FORM_RAY_NORM_ONE_PAIR : 0u);
+}
+
 uint32_t short_forms_input_bits(int form, uint64_t index)
 {
 	return form <= RT_SHORT_FORM_INV_TWO_PAIRS ? short_forms_rcp_input(index) : (uint32_t)index;

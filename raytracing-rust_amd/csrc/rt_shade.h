@@ -113,13 +113,53 @@ __device__ __forceinline__ V3 random_unit_vector(rt_rng &rng) // :15-25
 struct Coord {
 	V3 x, y, z;
 };
-__device__ __forceinline__ Coord coord_from_z(V3 z)
+RT_FN Coord coord_from_z(V3 z) // (host too: tests/cpp/frame_forms_check.cpp runs it next to coord_from_z_pair)
 {
 	Coord c;
 	if (fabsf(z.x) > fabsf(z.y))
 		c.x = v3(-z.z, 0.0f, z.x) / sqrtf(z.x * z.x + z.z * z.z);
 	else
 		c.x = v3(0.0f, z.z, -z.y) / sqrtf(z.y * z.y + z.z * z.z);
+	c.y = cross(c.x, z);
+	c.z = z;
+	return c;
+}
+// The same frame as the two-sphere kernels form it (rt_lean.h lean_frame_form): the bits of coord_from_z for EVERY z.
+// The arm is chosen once, as the reference's branch decides it (a NaN compare falls to the y-arm), by selects on the operands:
+// a = the component the arm squares, n0 / n1 = the two numerators that are not the literal zero, with the signs the reference
+// gives them (the operand is negated, not the quotient).  One guard, one region:
+//   s2 = a * a + z.z * z.z in [2^-40, 2^40] and min(|a|, |z.z|) >= 2^-60
+// make s = sqrtf(s2) lie in [2^-20, 2^20] (s2 far above lean_sqrt's 2^-96) and both numerators' magnitudes in [2^-60, s]
+// (RN(sqrt(RN(a * a))) = |a|, and both roundings are monotonic), so the quotients lie in [2^-80, 1]: operands in [2^-81, 2^41],
+// exponents less than 96 apart, the domain rt_selftest_div_forms enumerated for the one-pair quotient; no operand is zero,
+// infinite or NaN, so no v_div_fixup.  The zero component is the literal +0: 0 / s with s finite and positive is +0.
+// Lanes that fail -- a zero, tiny, huge, infinite or NaN component, an exact-equator normal among them -- run the plain
+// expression in one cold copy.  rt_selftest_frame_forms runs this next to coord_from_z ON the device on both sides of every
+// bound; on the host the short forms are the plain operators, and tests/cpp/frame_forms_check.cpp checks the algebra.
+constexpr float kFrameS2Min = 0x1p-40f, kFrameS2Max = 0x1p40f, kFrameNumMin = 0x1p-60f;
+RT_FN bool frame_guard_(float a, float zz, float s2) { return s2 >= kFrameS2Min && s2 <= kFrameS2Max && fminf(fabsf(a), fabsf(zz)) >= kFrameNumMin; }
+RT_FN Coord coord_from_z_pair(V3 z)
+{
+	const bool x_arm = fabsf(z.x) > fabsf(z.y);
+	const float a = x_arm ? z.x : z.y;
+	const float s2 = a * a + z.z * z.z;
+	const float n0 = x_arm ? -z.z : z.z; // x-arm (-z.z, 0, z.x) / s, y-arm (0, z.z, -z.y) / s
+	const float n1 = x_arm ? z.x : -z.y;
+	float q0, q1, zero;
+	if (__builtin_expect(frame_guard_(a, z.z, s2), 1)) {
+		const float s = lean_sqrt(s2);
+		const float r1 = lean_rcp_refined(s);
+		q0 = lean_div_core_for<true>(n0, s, r1);
+		q1 = lean_div_core_for<true>(n1, s, r1);
+		zero = 0.0f;
+	} else {
+		const float s = sqrtf(s2);
+		q0 = n0 / s;
+		q1 = n1 / s;
+		zero = 0.0f / s;
+	}
+	Coord c;
+	c.x = v3(x_arm ? q0 : zero, x_arm ? zero : q0, q1);
 	c.y = cross(c.x, z);
 	c.z = z;
 	return c;
@@ -444,8 +484,8 @@ __device__ __forceinline__ V3 lambertian_sample(V3 normal, rt_rng &rng) // lambe
 	const Coord c = coord_from_z(normal);
 	return to_coord(c, local);
 }
-// (the kernels with triangles: see coord_from_z_zsel)
-template <bool ZSEL = false> __device__ __forceinline__ V3 lambertian_sample_(V3 normal, rt_rng &rng) // lambertian.rs:5-18
+// (the kernels with triangles: see coord_from_z_zsel; the two-sphere kernels, PAIR_FRAME: see coord_from_z_pair)
+template <bool ZSEL = false, bool PAIR_FRAME = false> __device__ __forceinline__ V3 lambertian_sample_(V3 normal, rt_rng &rng) // lambertian.rs:5-18
 {
 	// 1 - r with r in [0, 1 - 2^-24] is >= 2^-24; 1 - c * c with c in [2^-12, 1] is zero or >= 2^-24 (rt_lean.h)
 	const float cos_theta = sqrt_unit_(1.0f - rt_rng_f32(&rng));
@@ -454,7 +494,7 @@ template <bool ZSEL = false> __device__ __forceinline__ V3 lambertian_sample_(V3
 	float sin_phi, cos_phi;
 	lean_sincos(phi, sin_phi, cos_phi);
 	const V3 local = v3(cos_phi * sin_theta, sin_phi * sin_theta, cos_theta);
-	const Coord c = ZSEL ? coord_from_z_zsel(normal) : coord_from_z(normal);
+	const Coord c = PAIR_FRAME ? coord_from_z_pair(normal) : (ZSEL ? coord_from_z_zsel(normal) : coord_from_z(normal));
 	return to_coord(c, local);
 }
 __device__ __forceinline__ float tr_d(float alpha, float cos_theta) // trowbridge_reitz.rs:14-21
@@ -577,7 +617,9 @@ template <class F> __device__ __forceinline__ bool mat_scatter_ray(const DevScen
 	const DevMaterial &m = mat_record(S, mat);
 	const int type = mat_type_<F>(mat, known);
 	if (type == 1) { // Lambertian  lambertian.rs:30-41
-		const V3 direction = F::tri ? lambertian_sample_<true>(hit.normal, rng) : lambertian_sample(hit.normal, rng);
+		constexpr bool pair_frame = lean_frame_form(F::pair) == LeanFrameForm::guarded_short;
+		const V3 direction = F::tri ? lambertian_sample_<true>(hit.normal, rng)
+		                            : (pair_frame ? lambertian_sample_<false, true>(hit.normal, rng) : lambertian_sample(hit.normal, rng));
 		const V3 point = offset_ray(hit.point, hit.normal, hit.err_dot, true);
 		ray = ray_new<F>(point, direction);
 		return false;

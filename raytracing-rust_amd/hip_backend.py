@@ -162,6 +162,22 @@ def selftest_sky_pdf_forms(scene, dirs):
     return a, b
 
 
+def selftest_frame_forms(vectors, device=0):
+    """rt_selftest_frame_forms: vectors (n, 3) f32, each both as a normal -- the scatter frame as the two-sphere kernels form it next
+    to the plain coord_from_z -- and as a ray direction -- ray_new<FeatPair>'s direction and reciprocals next to the plain operators --
+    on the GPU: {"tested", "frame_mismatches", "frame_short", "frame_plain", "ray_mismatches", "ray_short", "ray_plain"} (short / plain:
+    vectors that passed / failed the site's guard) and "in_use": names of the short forms the kernels' switches select.  Both
+    mismatch counts must be zero."""
+    vectors = np.ascontiguousarray(vectors, dtype=np.float32)
+    if vectors.ndim != 2 or vectors.shape[1] != 3:
+        raise ValueError(f"vectors must be (n, 3), got {vectors.shape}")
+    out = (C.c_uint64 * len(abi.FRAME_FORMS_COUNT_NAMES))()
+    _check(lib().rt_selftest_frame_forms(C.c_int(device), _p(vectors, C.c_float), C.c_uint64(vectors.shape[0]), out))
+    res = dict(zip(abi.FRAME_FORMS_COUNT_NAMES, (int(x) for x in out)))
+    res["in_use"] = [n for k, n in enumerate(abi.FRAME_FORM_NAMES) if res["in_use"] >> k & 1]
+    return res
+
+
 def selftest_pair_shadow(cases, device=0):
     """rt_selftest_pair_shadow: cases (n, 10) f32 -- centre, radius, ray origin, ray direction (as given) -- through the two-sphere
     kernels' occlusion predicate for a ray without a limit and through Sphere::get_int's `hit && t > 0`, on the GPU:
