@@ -381,9 +381,12 @@ int rt_scene_set_traversal(rt_scene *scene, int mode);
  *                         launch has per wave resident on the device (none below 2.5: sharded and small frames keep
  *                         every tile in chunk items; at most half the tiles, at most 3 whole tiles per resident wave).  Applies to the kernels of rt_launch_info.feature_set = 3
  *                         on 64-pixel tiles of power-of-two width with a power-of-two sample_split in 2..64 (other launches
- *                         ignore it: rt_launch_info.whole_claims = 0); 0 hands every tile out chunk by chunk */
+ *                         ignore it: rt_launch_info.whole_claims = 0); 0 hands every tile out chunk by chunk
+ *   RT_TUNE_RADIANCE_GROUPS  0 automatic (default); n in 1..65536: rt_radiance launches at most n workgroups (of 256 lanes), so
+ *                         that a small batch already makes every lane work through several rays (tests of the refill);
+ *                         other entry points ignore it */
 typedef enum rt_tuning_key { RT_TUNE_TRAVERSAL = 0, RT_TUNE_FEATURE_SET = 1, RT_TUNE_SCENE_IN_LDS = 2, RT_TUNE_SCHEDULE = 3, RT_TUNE_WALK = 4,
-                             RT_TUNE_STACK_CAP = 5, RT_TUNE_EXCHANGE = 6, RT_TUNE_WHOLE_PIXEL_SHARE = 7 } rt_tuning_key;
+                             RT_TUNE_STACK_CAP = 5, RT_TUNE_EXCHANGE = 6, RT_TUNE_WHOLE_PIXEL_SHARE = 7, RT_TUNE_RADIANCE_GROUPS = 8 } rt_tuning_key;
 int rt_scene_set_tuning(rt_scene *scene, int key, int value);
 /* The work items of a render under `opts` at an explicit split with `share` sixteenths of the shard's tiles handed out as whole
  * pixels (RT_TUNE_WHOLE_PIXEL_SHARE): what rt_launch_info.whole_claims and .n_items report after such a render by a kernel that
@@ -486,6 +489,42 @@ int rt_render_rgb8(rt_scene *scene, const rt_camera *camera, const rt_render_opt
 int rt_check_hit(rt_scene *scene, const rt_ray_desc *rays, uint64_t n_rays, rt_hit_record *out);
 int rt_check_hit_index(rt_scene *scene, const rt_ray_desc *rays, const uint64_t *object_index, uint64_t n_rays,
                        rt_hit_record *out);
+
+/* ---- radiance queries: the integrator on rays the CALLER supplies (cameras the reference does not have, light probes, baking,
+ * one pixel of a frame), run on the GPU.  For ray i of n_rays and sample k of K = samples_per_ray the value c[i][k] is
+ *   NaiveIntegrator::get_colour (integrators/mod.rs:22-78) or MisIntegrator::get_colour (integrators/mis.rs:7-92), by
+ *   render_method, on Ray::new(origin_i, direction_i) -- the clone-scatter draw of the MIS prologue, the emission evaluated
+ *   against the OLD hit, the NaN / non-finite filter where the reference applies it (not on the MIS prologue's early return),
+ *   max_depth and rr_threshold included --
+ *   on the random stream (seed, stream_i, sample_begin + k) of rt_detmath.h's rt_rng_seed, stream_i = streams ? streams[i] : i.
+ * NO draw is consumed before the integrator starts: a query has no pixel jitter and no camera `time` draw (there is no camera;
+ * this is the convention of the CPU checker's fixed-ray integrator).  rt_render spends the first draws of (seed, pixel, pass) on
+ * the jitter, so a query of a camera's rays does NOT reproduce a frame's bytes, whatever streams it is given.
+ * Output: out_rgb[3 i + j] = (c[i][0] + c[i][1] + ... in sample order, f32, from +0) / (float)K, the division once -- the chunk-sum
+ * rule of sample_split; with K = 1 the output is c[i][0].  Which lane computes which ray, and when, is not part of this
+ * definition and changes no bit (RT_TUNE_RADIANCE_GROUPS, rt_scene_set_traversal, RT_TUNE_WALK: same bytes).
+ * Every primitive, material and texture type is served by the same kernels.  n_rays = 0: RT_OK, nothing written.  n_rays >= 2^31:
+ * RT_ERR_UNSUPPORTED.  samples_per_ray = 0, a NULL rays / out_rgb / opts, an unknown render_method or a non-zero `reserved`:
+ * RT_ERR_INVALID_ARGUMENT; a host-only scene: RT_ERR_NO_DEVICE (after the argument checks); a multi-device scene runs on
+ * devices[0].  No side effects on rt_render or any other entry point.
+ * rt_radiance: HOST buffers, blocking; its device copies live on the scene (shared with rt_denoise; grown for larger batches only).
+ * rt_radiance_device: DEVICE buffers on the scene's GPU (4-byte aligned rays and output, 8-byte aligned streams), asynchronous on
+ * hip_stream: it allocates nothing, keeps no state on the scene, does not synchronise, may be captured into a graph from the
+ * scene's first call and may be in flight on several streams at once. ---- */
+typedef struct rt_radiance_opts {
+	uint64_t seed, sample_begin;
+	uint32_t samples_per_ray;   /* K >= 1 */
+	int32_t  render_method;     /* rt_render_method */
+	uint32_t max_depth;         /* 50 */
+	uint32_t rr_threshold;      /* 3 */
+	uint32_t reserved[2];
+} rt_radiance_opts;
+/* seed 0, sample_begin 0, one sample, MIS, max_depth 50, rr_threshold 3 (the defaults of rt_render_opts_default) */
+int rt_radiance_opts_default(rt_radiance_opts *out);
+int rt_radiance(rt_scene *scene, const rt_ray_desc *rays, const uint64_t *streams /* may be NULL */, uint64_t n_rays,
+                const rt_radiance_opts *opts, float *out_rgb);
+int rt_radiance_device(rt_scene *scene, const rt_ray_desc *d_rays, const uint64_t *d_streams /* may be NULL */, uint64_t n_rays,
+                       const rt_radiance_opts *opts, float *d_out_rgb, void *hip_stream);
 
 /* ---- first-hit auxiliary buffers ("AOVs": what a denoiser, compositing or picking needs besides the noisy mean) over the SAME
  * camera rays rt_render traces for passes [sample_begin, sample_begin + samples_per_pixel): pass p of pixel (x, y) uses the first

@@ -415,6 +415,35 @@ inline std::vector<float> matte_extract(const Bvh &bvh, const MatteLayers &layer
 	return out;
 }
 
+// Radiance queries (semantics: rt_hip.h rt_radiance_opts): the mean of `samples_per_ray` samples of the integrator along each of
+// the caller's rays, 3 floats a ray.  Sample k of ray i runs on the stream (seed, streams[i] or i, sample_begin + k) with no draw
+// ahead of the integrator: a query of a camera's rays does not reproduce a frame's bytes.  Blocking.
+struct RadianceOptions {
+	uint64_t seed = 0, sample_begin = 0;
+	uint32_t samples_per_ray = 1;
+	rt_render_method render_method = RT_METHOD_MIS;
+	uint32_t max_depth = 50, rr_threshold = 3;
+};
+inline std::vector<float> radiance(const Bvh &bvh, const std::vector<rt_ray_desc> &rays, const RadianceOptions &r = RadianceOptions(),
+                                   const std::vector<uint64_t> *streams = nullptr)
+{
+	rt_radiance_opts opts;
+	check(rt_radiance_opts_default(&opts));
+	opts.seed = r.seed;
+	opts.sample_begin = r.sample_begin;
+	opts.samples_per_ray = r.samples_per_ray;
+	opts.render_method = r.render_method;
+	opts.max_depth = r.max_depth;
+	opts.rr_threshold = r.rr_threshold;
+	if (streams && streams->size() != rays.size())
+		throw std::invalid_argument("radiance: one stream per ray");
+	std::vector<float> out(3 * rays.size());
+	// (an empty batch: the library writes nothing; the vectors' data() may be null, which it would refuse)
+	if (!rays.empty())
+		check(rt_radiance(bvh.raw(), rays.data(), streams ? streams->data() : nullptr, rays.size(), &opts, out.data()));
+	return out;
+}
+
 // Ambient occlusion (semantics: rt_hip.h rt_ao_opts): per pixel the share of `rays_per_pass` cosine-weighted rays per pass from the
 // first hit that reach nothing within `radius` (0: no limit), and the mean direction of those rays (length = openness).
 struct AoOptions {

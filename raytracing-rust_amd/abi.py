@@ -27,6 +27,7 @@ RT_SPLIT_SAH, RT_SPLIT_MIDDLE, RT_SPLIT_EQUAL_COUNTS = range(3)
 RT_METHOD_NAIVE, RT_METHOD_MIS = range(2)
 RT_LAYOUT_FRAME, RT_LAYOUT_SHARD = range(2)
 RT_TUNE_TRAVERSAL, RT_TUNE_FEATURE_SET, RT_TUNE_SCENE_IN_LDS, RT_TUNE_SCHEDULE, RT_TUNE_WALK, RT_TUNE_STACK_CAP, RT_TUNE_EXCHANGE, RT_TUNE_WHOLE_PIXEL_SHARE = range(8)
+RT_TUNE_RADIANCE_GROUPS = 8  # rt_radiance: at most that many workgroups (0: automatic)
 
 NO_INDEX = 0xFFFFFFFFFFFFFFFF  # usize::MAX
 RT_DEVICE_NONE = -1  # rt_scene_create: Bvh::new on the host only (no GPU touched, nothing can be rendered)
@@ -292,6 +293,22 @@ class AoBuffers(C.Structure):  # rt_ao_buffers
 
 
 AO_CHANNELS = ("visibility", "bent_normal")
+
+
+# radiance queries (rt_radiance)
+class RadianceOpts(C.Structure):  # rt_radiance_opts
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("sample_begin", C.c_uint64),
+        ("samples_per_ray", C.c_uint32),
+        ("render_method", C.c_int32),
+        ("max_depth", C.c_uint32),
+        ("rr_threshold", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+RADIANCE_OPTIONS = tuple(n for n, _ in RadianceOpts._fields_ if n != "reserved")
 
 
 # noise estimates (rt_render_noise, rt_noise_tiles, rt_render_converged)
@@ -585,6 +602,7 @@ EXPECTED_SIZES = {
     "rt_matte_buffers": (MatteBuffers, 24),
     "rt_ao_opts": (AoOpts, 32),
     "rt_ao_buffers": (AoBuffers, 16),
+    "rt_radiance_opts": (RadianceOpts, 40),
     "rt_noise_opts": (NoiseOpts, 32),
     "rt_noise_summary": (NoiseSummary, 16),
     "rt_noise_buffers": (NoiseBuffers, 40),
@@ -649,6 +667,9 @@ EXPORTED_SYMBOLS = [
     "rt_render_rgb8",
     "rt_check_hit",
     "rt_check_hit_index",
+    "rt_radiance_opts_default",
+    "rt_radiance",
+    "rt_radiance_device",
     "rt_selftest_lean",
     "rt_selftest_short_forms",
     "rt_selftest_div_forms",

@@ -725,6 +725,11 @@ static int set_tuning_one(rt_scene *s, int key, int value)
 			return fail(RT_ERR_INVALID_ARGUMENT, "walk must be 0 (automatic) or 1 (two-child walk for every ray)");
 		s->dev.narrow_only = (uint32_t)value;
 		return RT_OK;
+	case RT_TUNE_RADIANCE_GROUPS:
+		if (value < 0 || value > 65536)
+			return fail(RT_ERR_INVALID_ARGUMENT, "radiance groups must be 0 (automatic) or 1..65536 workgroups");
+		s->radiance_groups = (uint32_t)value;
+		return RT_OK;
 	default:
 		return fail(RT_ERR_INVALID_ARGUMENT, "unknown tuning key");
 	}

@@ -1,7 +1,7 @@
 // rt_api_query.cpp -- the entry points of librt_hip.so that ask a scene or the device a question without rendering: the batch
-// hit queries (rt_check_hit / rt_check_hit_index), the self-tests (rt_selftest_*) and, in the diagnostic build,
-// rt_debug_trace_queue.  Their kernels are rt_query.hip and rt_selftest.hip; the scene handle, the error convention and the
-// traversal policy are rt_api_internal.h.
+// hit queries (rt_check_hit / rt_check_hit_index), the radiance queries (rt_radiance), the self-tests (rt_selftest_*) and, in the
+// diagnostic build, rt_debug_trace_queue.  Their kernels are rt_query.hip, rt_radiance.hip and rt_selftest.hip; the scene handle,
+// the error convention and the traversal policy are rt_api_internal.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,6 +11,7 @@
 #include "../../include/rt_hip.h"
 #include "rt_api_internal.h"
 #include "rt_query.h"
+#include "rt_radiance.h"
 #include "rt_selftest.h"
 
 using namespace rt;
@@ -114,6 +115,101 @@ int rt_check_hit_index(rt_scene *s, const rt_ray_desc *rays, const uint64_t *obj
 	if (!object_index)
 		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
 	return check_common(s, rays, object_index, n_rays, out);
+}
+
+// ---- radiance queries (rt_radiance.hip) ----
+int rt_radiance_opts_default(rt_radiance_opts *out)
+{
+	if (!out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	std::memset(out, 0, sizeof *out);
+	out->samples_per_ray = 1;
+	out->render_method = RT_METHOD_MIS;
+	out->max_depth = 50;
+	out->rr_threshold = 3;
+	return RT_OK;
+}
+
+// argument checks of both entry points, the device last (so that a host-only scene reports bad arguments as such)
+static int radiance_check(const rt_scene *s, const rt_ray_desc *rays, uint64_t n, const rt_radiance_opts *o, const float *out)
+{
+	if (!s || !rays || !o || !out)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (o->samples_per_ray == 0)
+		return fail(RT_ERR_INVALID_ARGUMENT, "radiance: samples_per_ray must be >= 1");
+	if (o->render_method != RT_METHOD_NAIVE && o->render_method != RT_METHOD_MIS)
+		return fail(RT_ERR_INVALID_ARGUMENT, "radiance: unknown render_method");
+	for (uint32_t r : o->reserved)
+		if (r != 0u)
+			return fail(RT_ERR_INVALID_ARGUMENT, "radiance: reserved must be zero");
+	if (n >= (1ull << 31))
+		return fail(RT_ERR_UNSUPPORTED, "radiance: 2^31 rays or more in one call");
+	return need_device(s);
+}
+
+// The workgroups of a launch: one lane per ray up to what the device holds at once -- kRadianceWaves workgroups a CU by registers,
+// fewer where the stacks' LDS allows fewer (160 KB a CU) -- beyond that the lanes refill; RT_TUNE_RADIANCE_GROUPS caps it.
+static uint32_t radiance_groups(const rt_scene *s, const DevScene &dev, uint64_t n)
+{
+	const uint64_t by_lds = std::max<uint64_t>(1, (160u * 1024u) / std::max<size_t>(1, four_wave_stack_lds_bytes(dev)));
+	const uint64_t resident = (uint64_t)std::max(1, s->n_cus) * std::min<uint64_t>(kRadianceWaves, by_lds);
+	uint64_t groups = std::min<uint64_t>((n + 255) / 256, resident);
+	if (s->radiance_groups != 0u)
+		groups = std::min<uint64_t>(groups, s->radiance_groups);
+	return (uint32_t)groups;
+}
+
+int rt_radiance_device(rt_scene *s, const rt_ray_desc *d_rays, const uint64_t *d_streams, uint64_t n_rays, const rt_radiance_opts *o,
+                       float *d_out_rgb, void *hip_stream)
+{
+	if (int rc = radiance_check(s, d_rays, n_rays, o, d_out_rgb); rc != RT_OK)
+		return rc;
+	if (n_rays == 0)
+		return RT_OK;
+	// a multi-device head is an ordinary scene on devices[0]: the query runs there alone
+	HIP_TRY(hipSetDevice(s->device));
+	bool prune = false;
+	DevScene dev;
+	if (int rc = four_wave_traversal(s, &prune, &dev); rc != RT_OK) // (rt_api_internal.h)
+		return rc;
+	DevRadianceParams P;
+	std::memset(&P, 0, sizeof P);
+	P.rays = reinterpret_cast<const float *>(d_rays);
+	P.streams = d_streams;
+	P.out = d_out_rgb;
+	P.n_rays = (uint32_t)n_rays;
+	P.samples = o->samples_per_ray;
+	P.seed_lo = (uint32_t)o->seed;
+	P.seed_hi = (uint32_t)(o->seed >> 32);
+	P.sample_begin_lo = (uint32_t)o->sample_begin;
+	P.sample_begin_hi = (uint32_t)(o->sample_begin >> 32);
+	P.max_depth = o->max_depth;
+	P.rr_threshold = o->rr_threshold;
+	HIP_TRY(launch_radiance(o->render_method == RT_METHOD_NAIVE ? 0 : 1, prune, static_cast<hipStream_t>(hip_stream), dev, P,
+	                        radiance_groups(s, dev, n_rays)));
+	return RT_OK;
+}
+
+int rt_radiance(rt_scene *s, const rt_ray_desc *rays, const uint64_t *streams, uint64_t n_rays, const rt_radiance_opts *o, float *out_rgb)
+{
+	if (int rc = radiance_check(s, rays, n_rays, o, out_rgb); rc != RT_OK)
+		return rc;
+	if (n_rays == 0)
+		return RT_OK;
+	HIP_TRY(hipSetDevice(s->device));
+	// the rays, the streams if given, the output
+	Layout L;
+	const auto p_rays = L.add<rt_ray_desc>(n_rays);
+	const auto p_streams = L.optional<uint64_t>(streams, n_rays);
+	const auto p_out = L.add<float>(3 * n_rays);
+	RT_TRY(grow_device_buffer(s->d_denoise, s->d_denoise_bytes, L)); // shared with rt_denoise / rt_render_ao
+	Staging st{s};
+	st.put(L, p_rays, rays);
+	st.put(L, p_streams, streams);
+	if (st.ok())
+		st.rc = rt_radiance_device(s, L.at(p_rays), L.at(p_streams), n_rays, o, L.at(p_out), s->stream);
+	st.get(out_rgb, L, p_out);
+	return st.finish("radiance");
 }
 
 int rt_selftest_division(float divisor, float *reciprocal, int *exact)

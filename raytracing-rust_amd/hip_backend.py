@@ -969,6 +969,36 @@ class HipScene:
                                         C.c_uint64(rays.shape[0]), out.ctypes.data_as(C.POINTER(abi.HitRecord))))
         return out
 
+    # ---- radiance queries (rt_radiance): the integrator on caller-supplied rays ----
+    def radiance(self, origins, directions, *, streams=None, method=abi.RT_METHOD_MIS, samples=1, seed=0, sample_begin=0,
+                 max_depth=50, rr_threshold=3):
+        """The mean of `samples` samples of Naive / MisIntegrator::get_colour along each ray, as an (n, 3) f32 array.  Sample k of
+        ray i runs on the stream (seed, streams[i] or i, sample_begin + k) with no draw ahead of the integrator (no jitter: a query
+        of a camera's rays does not reproduce a frame's bytes).  Semantics: include/rt_hip.h rt_radiance_opts."""
+        rays = _pack_rays(origins, directions)
+        n = rays.shape[0]
+        out = np.zeros((n, 3), dtype=np.float32)
+        st = None
+        if streams is not None:
+            st = np.ascontiguousarray(streams, dtype=np.uint64)
+            if st.shape != (n,):
+                raise ValueError(f"streams must be one per ray: {st.shape} for {n} rays")
+        o = radiance_opts(render_method=method, samples_per_ray=samples, seed=seed, sample_begin=sample_begin, max_depth=max_depth,
+                          rr_threshold=rr_threshold)
+        _check(lib().rt_radiance(self._h, rays.ctypes.data_as(C.POINTER(abi.RayDesc)), _p(st, C.c_uint64) if st is not None else None,
+                                 C.c_uint64(n), C.byref(o), _p(out, C.c_float)))
+        return out
+
+    def radiance_device(self, d_rays, d_streams, n_rays, d_out, *, method=abi.RT_METHOD_MIS, samples=1, seed=0, sample_begin=0,
+                        max_depth=50, rr_threshold=3, stream=0):
+        """rt_radiance_device: asynchronous, DEVICE pointers on the scene's GPU -- d_rays n x rt_ray_desc, d_streams n x u64 or
+        0 / None (stream i = i), d_out 3 n f32.  Allocates nothing and keeps no state: capturable from the first call, and safe
+        on several streams at once."""
+        o = radiance_opts(render_method=method, samples_per_ray=samples, seed=seed, sample_begin=sample_begin, max_depth=max_depth,
+                          rr_threshold=rr_threshold)
+        _check(lib().rt_radiance_device(self._h, C.c_void_p(d_rays), C.c_void_p(d_streams or None), C.c_uint64(n_rays), C.byref(o),
+                                        _dp(d_out, C.c_float), C.c_void_p(stream)))
+
 
 def output_floats(opts):
     n = C.c_uint64()
@@ -1102,6 +1132,17 @@ def ao_opts(**kw):
     for k, v in kw.items():
         if k not in ("rays_per_pass", "radius"):
             raise ValueError(f"unknown AO option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def radiance_opts(**kw):
+    """rt_radiance_opts_default with any of seed, sample_begin, samples_per_ray, render_method, max_depth, rr_threshold set."""
+    o = abi.RadianceOpts()
+    _check(lib().rt_radiance_opts_default(C.byref(o)))
+    for k, v in kw.items():
+        if k not in abi.RADIANCE_OPTIONS:
+            raise ValueError(f"unknown radiance option {k!r}")
         setattr(o, k, v)
     return o
 
