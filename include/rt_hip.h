@@ -497,6 +497,8 @@ int rt_check_hit_index(rt_scene *scene, const rt_ray_desc *rays, const uint64_t 
  *   against the OLD hit, the NaN / non-finite filter where the reference applies it (not on the MIS prologue's early return),
  *   max_depth and rr_threshold included --
  *   on the random stream (seed, stream_i, sample_begin + k) of rt_detmath.h's rt_rng_seed, stream_i = streams ? streams[i] : i.
+ *   seed, stream_i and sample_begin are full 64-bit values; sample_begin + k is a uint64_t addition and WRAPS: from
+ *   sample_begin = 2^64 - 2 the samples are 2^64 - 2, 2^64 - 1, 0, 1, ...
  * NO draw is consumed before the integrator starts: a query has no pixel jitter and no camera `time` draw (there is no camera;
  * this is the convention of the CPU checker's fixed-ray integrator).  rt_render spends the first draws of (seed, pixel, pass) on
  * the jitter, so a query of a camera's rays does NOT reproduce a frame's bytes, whatever streams it is given.

@@ -691,7 +691,7 @@ typedef struct integ_job {
 	rt_ray_desc ray;
 	int32_t method;
 	uint32_t max_depth, rr_threshold;
-	uint64_t seed, begin, end;
+	uint64_t seed, stream, sample_begin, begin, end;
 	double sum[3];
 } integ_job;
 
@@ -702,7 +702,7 @@ static void *integ_worker(void *p)
 	ora_ctx_init(&ctx);
 	j->sum[0] = j->sum[1] = j->sum[2] = 0.0;
 	for (uint64_t k = j->begin; k < j->end; ++k) {
-		rt_rng_seed(&ctx.rng, j->seed, 0, k);
+		rt_rng_seed(&ctx.rng, j->seed, j->stream, j->sample_begin + k); /* u64: wraps */
 		ora_ray ray = ora_ray_new(v3_from(j->ray.origin), v3_from(j->ray.direction), 0.0f);
 		uint64_t rc;
 		const vec3 c = j->method == RT_METHOD_NAIVE
@@ -716,8 +716,9 @@ static void *integ_worker(void *p)
 	return NULL;
 }
 
-int ora_integrate_ray(const ora_scene *scene, const rt_ray_desc *ray, int32_t method, uint32_t max_depth,
-                      uint32_t rr_threshold, uint64_t seed, uint64_t n_samples, uint32_t n_threads, double out_mean[3])
+int ora_integrate_ray_stream(const ora_scene *scene, const rt_ray_desc *ray, int32_t method, uint32_t max_depth,
+                             uint32_t rr_threshold, uint64_t seed, uint64_t n_samples, uint32_t n_threads, double out_mean[3],
+                             uint64_t stream, uint64_t sample_begin)
 {
 	if (!scene || !ray || !out_mean || n_samples == 0)
 		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments");
@@ -732,6 +733,8 @@ int ora_integrate_ray(const ora_scene *scene, const rt_ray_desc *ray, int32_t me
 		jobs[t].max_depth = max_depth;
 		jobs[t].rr_threshold = rr_threshold;
 		jobs[t].seed = seed;
+		jobs[t].stream = stream;
+		jobs[t].sample_begin = sample_begin;
 		jobs[t].begin = n_samples * t / n_threads;
 		jobs[t].end = n_samples * (t + 1) / n_threads;
 		pthread_create(&threads[t], NULL, integ_worker, &jobs[t]);
@@ -747,6 +750,12 @@ int ora_integrate_ray(const ora_scene *scene, const rt_ray_desc *ray, int32_t me
 	free(jobs);
 	free(threads);
 	return RT_OK;
+}
+
+int ora_integrate_ray(const ora_scene *scene, const rt_ray_desc *ray, int32_t method, uint32_t max_depth,
+                      uint32_t rr_threshold, uint64_t seed, uint64_t n_samples, uint32_t n_threads, double out_mean[3])
+{
+	return ora_integrate_ray_stream(scene, ray, method, max_depth, rr_threshold, seed, n_samples, n_threads, out_mean, 0, 0);
 }
 
 /* ---------------- hooks for the restated statistical / unit tests ---------------- */

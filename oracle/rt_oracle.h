@@ -57,6 +57,12 @@ int ora_check_hit_index(const ora_scene *scene, const rt_ray_desc *rays, const u
  * reference's furnace / MIS-vs-naive tests (crates/implementations/tests/sampling.rs:239-297). */
 int ora_integrate_ray(const ora_scene *scene, const rt_ray_desc *ray, int32_t render_method, uint32_t max_depth,
                       uint32_t rr_threshold, uint64_t seed, uint64_t n_samples, uint32_t n_threads, double out_mean[3]);
+/* the same on the streams (seed, stream, sample_begin + k), k = 0 .. n_samples - 1, the sum sample_begin + k in uint64_t (it
+ * wraps past 2^64 - 1): the counterpart of rt_radiance's (seed, stream_i, sample_begin + k).  ora_integrate_ray is this entry
+ * with stream = 0, sample_begin = 0. */
+int ora_integrate_ray_stream(const ora_scene *scene, const rt_ray_desc *ray, int32_t render_method, uint32_t max_depth,
+                             uint32_t rr_threshold, uint64_t seed, uint64_t n_samples, uint32_t n_threads, double out_mean[3],
+                             uint64_t stream, uint64_t sample_begin);
 
 /* ---- hooks for the restated statistical tests ---- */
 /* elementwise rt_detmath functions: which = 0 sin, 1 cos, 2 acos, 3 atan2(a,b), 4 tan, 5 pow5 */

@@ -94,6 +94,21 @@ def assert_render_unaffected(gpu, cam, between):
     assert gpu.last_kernel_ms()[1] == n_a and gpu.last_launch_info() == info_a
 
 
+def radiance_device_run(torch, gpu, o, d, streams, off, **kw):
+    """rt_radiance_device on guarded buffers `off` floats past a 16-byte boundary, `streams` (u64 per ray, or None) in a device
+    array: returns (GuardedBuffers with "rays" and "out", enqueue(stream handle), the streams tensor to keep alive)"""
+    n = len(o)
+    bufs = GuardedBuffers(torch, {"rays": ((n, 6), np.float32), "out": ((n, 3), np.float32)}, off=off)
+    packed = np.ascontiguousarray(np.concatenate([o, d], axis=1), dtype=np.float32).view(np.int32).reshape(-1)
+    lo = 4 + off
+    bufs.buf["rays"][lo:lo + 6 * n] = torch.from_numpy(packed.copy()).to(bufs.buf["rays"].device)
+    d_streams = None if streams is None else torch.from_numpy(streams.astype(np.uint64).view(np.int64).copy()).to("cuda:0")
+
+    def enqueue(s):
+        gpu.radiance_device(bufs.ptr("rays"), 0 if d_streams is None else d_streams.data_ptr(), n, bufs.ptr("out"), stream=s, **kw)
+    return bufs, enqueue, d_streams
+
+
 def ssml_scene(name):
     ls = scenes.load_ssml(name)
     return ls.scene, ls.camera_params

@@ -11,7 +11,7 @@ import aov_checker as K
 import hard_tree_cases as HT
 import radiance_checker as R
 import scenes
-from gpu_support import GuardedBuffers, assert_render_unaffected, assert_same_bits, capture, ssml_scene
+from gpu_support import assert_render_unaffected, assert_same_bits, capture, radiance_device_run, ssml_scene
 
 pytestmark = pytest.mark.gpu
 abi = scenes.abi
@@ -104,15 +104,12 @@ def _gpu(hb, name, **kw):
 
 def _samples(gpu, o, d, method, k, seed, **kw):
     """[n, k, 3] f32: sample j of every ray on stream 0, one query a sample"""
-    zeros = np.zeros(len(o), dtype=np.uint64)
-    return np.stack([gpu.radiance(o, d, streams=zeros, method=method, samples=1, seed=seed, sample_begin=j, **kw) for j in range(k)], axis=1)
+    return R.samples(gpu, o, d, method, k, seed, **kw)
 
 
 def _assert_matches_oracle(gpu, name, which, n, method, k, seed, what, **kw):
     o, d = _ray_set(name, which, n)
-    got = _samples(gpu, o, d, method, k, seed, **kw)
-    R.assert_same_f64(R.fold_prefix(got), _oracle(name, which, n, method, k, seed, **kw), what)
-    return got
+    return R.assert_matches(gpu, o, d, _oracle(name, which, n, method, k, seed, **kw), method, seed, what, **kw)
 
 
 # ---- per-sample parity ----
@@ -246,17 +243,7 @@ def test_hard_trees(hb, case):
 
 # ---- entry points ----
 def _device_run(torch, gpu, o, d, streams, off, stream=0, **kw):
-    """the device entry on guarded buffers `off` floats past a 16-byte boundary; returns (GuardedBuffers, enqueue)"""
-    n = len(o)
-    bufs = GuardedBuffers(torch, {"rays": ((n, 6), np.float32), "out": ((n, 3), np.float32)}, off=off)
-    packed = np.ascontiguousarray(np.concatenate([o, d], axis=1), dtype=np.float32).view(np.int32).reshape(-1)
-    lo = 4 + off
-    bufs.buf["rays"][lo:lo + 6 * n] = torch.from_numpy(packed.copy()).to(bufs.buf["rays"].device)
-    d_streams = None if streams is None else torch.from_numpy(streams.astype(np.int64)).to("cuda:0")
-
-    def enqueue(s):
-        gpu.radiance_device(bufs.ptr("rays"), 0 if d_streams is None else d_streams.data_ptr(), n, bufs.ptr("out"), stream=s, **kw)
-    return bufs, enqueue, d_streams
+    return radiance_device_run(torch, gpu, o, d, streams, off, **kw)
 
 
 def test_host_entry_device_entry_alignment_streams_and_a_multi_device_head(hb):
