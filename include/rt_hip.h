@@ -384,7 +384,8 @@ int rt_scene_set_traversal(rt_scene *scene, int mode);
  *                         ignore it: rt_launch_info.whole_claims = 0); 0 hands every tile out chunk by chunk
  *   RT_TUNE_RADIANCE_GROUPS  0 automatic (default); n in 1..65536: rt_radiance launches at most n workgroups (of 256 lanes), so
  *                         that a small batch already makes every lane work through several rays (tests of the refill);
- *                         other entry points ignore it */
+ *                         rt_render_tiles, whose kernel has the same shape, obeys it too (a short tile list then makes
+ *                         every lane refill); other entry points ignore it */
 typedef enum rt_tuning_key { RT_TUNE_TRAVERSAL = 0, RT_TUNE_FEATURE_SET = 1, RT_TUNE_SCENE_IN_LDS = 2, RT_TUNE_SCHEDULE = 3, RT_TUNE_WALK = 4,
                              RT_TUNE_STACK_CAP = 5, RT_TUNE_EXCHANGE = 6, RT_TUNE_WHOLE_PIXEL_SHARE = 7, RT_TUNE_RADIANCE_GROUPS = 8 } rt_tuning_key;
 int rt_scene_set_tuning(rt_scene *scene, int key, int value);
@@ -880,6 +881,87 @@ int rt_render_converged(rt_scene *scene, const rt_camera *camera, const rt_rende
                         float *out_tile_error, rt_noise_result *result);
 int rt_render_denoised_split(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_denoise_opts *dopts,
                              float *out_clean, float *out_noisy, float *out_variance, uint64_t *rays_shot);
+
+/* ---- The render on a LIST of tiles, and the list of the noisy ones (csrc/rt_adaptive.hip).  What per-tile refinement and a region
+ * render (re-render a crop of a frame) need of the device: rt_render's own pixels, for the tiles named, nothing else touched.
+ *
+ * Tiles.  Tile t covers x in [8 tx, 8 tx + 8), y in [8 ty, 8 ty + 8) with t = ty * ceil(W / 8) + tx: the grid of rt_noise_tiles,
+ *   whatever opts->tile_width / tile_height say (they shape rt_render's schedule and no byte of its frame).
+ * rt_render_tiles[_device].  For every opts rt_render_device accepts with RT_LAYOUT_FRAME and shard_count 1, every pixel of a listed
+ *   tile receives THE BYTES rt_render_device writes for it under the same opts: sample_split 1 the running mean
+ *   `mean += (pass - mean) / i`; S > 1 the chunk sums in pass order from +0, added in chunk order, divided by spp once; S = 0
+ *   resolved as rt_render resolves it for the whole frame (rt_scene_auto_sample_split).  Every other pixel of the frame is left
+ *   untouched.  The pixel's passes are the streams (seed, pixel, sample_begin + pass) of rt_render_opts, so a pixel does not depend
+ *   on which other tiles are listed.
+ *   chunk_sums (may be NULL; read only when the resolved S > 1): receives the S sums of every listed pixel as
+ *   [chunk][64 * slot + 8 * (y & 7) + (x & 7)][3], slot the tile's position in the list: 3 * S * 64 * n_tiles floats.  The padding
+ *   lanes of an edge tile hold +0.  With the buffer the launch spreads (tile, chunk) pairs over the device -- a short list at S = 16
+ *   is sixteen times the lanes -- and a second small kernel combines them; without it one lane folds all S chunks of its pixel:
+ *   the same bytes, no memory besides the frame.
+ *   rays_shot (may be NULL) is WRITTEN, not added to: the integrators' ray counters over the listed pixels and passes, counted as
+ *   rt_render's rays_shot (SamplerProgress.rays_shot), so that the counters of a list and of its complement add up to rt_render's.
+ *   n_tiles = 0: RT_OK, nothing written but rays_shot = 0.
+ *   rt_render_tiles (HOST buffers, blocking): the indices must be distinct and below the tile count, so n_tiles is at most the tile
+ *   count (RT_ERR_INVALID_ARGUMENT; the device entry checks neither);
+ *   out_rgb is the caller's whole frame, which travels to the device and back.
+ *   rt_render_tiles_device (DEVICE buffers on the scene's GPU, asynchronous on `hip_stream`) cannot check the list: an index at or
+ *   past the tile count is skipped (nothing is ever written out of bounds; its slot of chunk_sums is left as it was), a duplicate
+ *   computes the same bytes twice.  It allocates nothing, keeps no state on the scene, does not synchronise and can be captured
+ *   into a HIP graph from a scene's first call; launches on two streams may be in flight at once (into one frame if their lists
+ *   are disjoint).
+ *   Performance: the (tile, chunk) spread over the device is reached only WITH chunk_sums; a short list without the buffer is 64
+ *   lanes a tile whatever S is.  rt_render_adaptive always passes one.
+ *   Errors: NULL scene / camera / opts / out, a NULL list with n_tiles > 0, whatever rt_render_device refuses in opts, a chunk
+ *   buffer overlapping the frame: RT_ERR_INVALID_ARGUMENT; then RT_ERR_UNSUPPORTED for RT_LAYOUT_SHARD, shard_count != 1, a
+ *   multi-device scene, 2^31 pixels or more, or 64 * n_tiles * S at or above 2^31; then RT_ERR_NO_DEVICE for a host-only scene.
+ *   Which lane renders which pixel, the traversal mode, the walk and RT_TUNE_RADIANCE_GROUPS change no bit.
+ * rt_noise_select_tiles[_device].  From a tile_error plane (ceil(W/8) * ceil(H/8) floats, as rt_noise_tiles writes it) and a
+ *   threshold: tiles[0 .. *count) = the indices t with tile_error[t] > threshold (strictly: the rule of
+ *   rt_noise_summary.tiles_above; a NaN error is not above), in ASCENDING order, so that the list is a pure function of the plane;
+ *   the rest of `tiles` (capacity: the tile count) is left as it was.  A NaN threshold, a NULL argument, width or height 0:
+ *   RT_ERR_INVALID_ARGUMENT; more than 2^31 pixels: RT_ERR_UNSUPPORTED; a host-only scene: RT_ERR_NO_DEVICE.  The list is what
+ *   rt_render_tiles_device takes next on the same stream (the count is read by the host: the launch is sized by it). ---- */
+/* ---- Adaptive sampling: rt_render_converged that stops refining a tile once it is quiet (blocking, HOST buffers).
+ * Definition, per pixel p: state M (3 channels), L, V from +0 and a batch count nb_p = 0.  Batch b = 0, 1, ... renders the window
+ *   [sample_begin + b * batch, + batch) at the split the rule of the noise estimates gives for `batch` passes (sample_split in 2..64
+ *   dividing batch, 0 automatic), for every pixel of the tiles ACTIVE at that batch.  Every tile is active at batch 0 and as long as
+ *   b < min_batches; after that a tile is active iff its tile_error after the previous batch is > nopts->threshold (strictly: an
+ *   error equal to the threshold is not).  For each rendered pixel (mean_b, lbar_b, var_b) are exactly the "one render" quantities
+ *   of the noise estimates (with the optional albedo); M += mean_b, L += lbar_b, V += var_b, nb_p += 1.  Outputs: mean = M /
+ *   (float)nb_p, lum_mean = L / (float)nb_p, variance = V / ((float)nb_p * (float)nb_p); after every batch the tile_error of EVERY
+ *   tile is the butterfly of rt_noise_tiles over these planes.  The planes of a tile that was not rendered do not change, so
+ *   neither does its error: a tile that has stopped never restarts.
+ *   The loop stops after batch b when b + 1 >= min_batches and no tile is active (converged = 1), or when another batch would
+ *   exceed max_passes (converged = 0).  out_passes[p] (may be NULL) = nb_p * batch.  result->pixel_passes = the sum of out_passes:
+ *   the work done, to set against W * H * batches * batch; rays_shot is summed over the batches; summary is the last batch's.
+ *   rt_render_converged never drops a tile: a run whose batches all render every tile (threshold 0 on a noisy frame, or a threshold
+ *   above every error, which stops at min_batches) returns rt_render_converged's bytes in mean, variance and tile_error.
+ * TWO WARNINGS.  The mean of a stopped tile is a mean of FEWER batches than its neighbour's: at loose thresholds the borders of
+ *   the 8 x 8 tiles can show in the image (nothing here dilates the active set or blends across borders).  And the thresholds are
+ *   the untuned defaults of rt_noise_opts: starting values, not recommendations.
+ * Launches: whole-frame batches are rt_render_device's own launch (as rt_render_noise_device); the others rt_render_tiles_device
+ *   with its chunk buffer and one fold kernel.  Scratch lives on the scene and grows on first use (the chunk buffer is sized for
+ *   the whole tile grid: 12 * S * 64 bytes a tile).  Checks and their order are rt_render_converged's; in addition 2^24 batches or
+ *   more (max_passes / batch) and 64 * tiles * S at or above 2^31 are RT_ERR_UNSUPPORTED, and out_passes must not overlap the
+ *   other outputs. ---- */
+typedef struct rt_adaptive_result {
+	uint64_t pixel_passes; /* sum over the pixels of the passes rendered for them */
+	uint64_t rays_shot;    /* summed over the batches */
+	uint32_t batches;
+	uint32_t converged;    /* 1: no tile active any more; 0: stopped by max_passes */
+	rt_noise_summary summary; /* after the last batch */
+} rt_adaptive_result;
+int rt_render_adaptive(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const rt_noise_opts *nopts,
+                       const float *albedo_or_null, uint64_t batch, uint32_t min_batches, uint64_t max_passes, float *out_mean,
+                       float *out_variance, float *out_tile_error, uint32_t *out_passes, rt_adaptive_result *result);
+int rt_render_tiles(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const uint32_t *tiles, uint32_t n_tiles,
+                    float *out_rgb, float *chunk_sums_or_null, uint64_t *rays_shot_or_null);
+int rt_render_tiles_device(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, const uint32_t *d_tiles, uint32_t n_tiles,
+                           float *d_out_rgb, float *d_chunk_sums_or_null, uint64_t *d_rays_shot_or_null, void *hip_stream);
+int rt_noise_select_tiles(rt_scene *scene, const float *tile_error, uint32_t width, uint32_t height, float threshold, uint32_t *tiles,
+                          uint32_t *count);
+int rt_noise_select_tiles_device(rt_scene *scene, const float *d_tile_error, uint32_t width, uint32_t height, float threshold,
+                                 uint32_t *d_tiles, uint32_t *d_count, void *hip_stream);
 
 /* ---- Firefly-robust frames (csrc/rt_robust.hip): a rank-trimmed mean of the chunk sums.  The integrator keeps the reference's
  * quirks, so one wild sample -- or one inf / NaN -- ends up in a pixel's mean, where no later stage can undo it.  The S

@@ -549,6 +549,51 @@ inline ConvergedFrame render_converged(const RenderOptions &o, const SimpleCamer
 	return r;
 }
 
+// render_converged that, after min_batches whole-frame windows, renders only the tiles whose error is still above the threshold.
+// The mean of a stopped tile is a mean of fewer batches than its neighbour's (tile borders can show at loose thresholds); the
+// thresholds are untuned defaults.  passes[p] = the passes rendered for pixel p.
+struct AdaptiveFrame {
+	std::vector<float> mean, variance, tile_error;
+	std::vector<uint32_t> passes;
+	rt_adaptive_result result{};
+};
+inline AdaptiveFrame render_adaptive(const RenderOptions &o, const SimpleCamera &camera, const Bvh &bvh, uint32_t sample_split, uint64_t batch,
+                                     uint32_t min_batches, uint64_t max_passes, const NoiseOptions &n = NoiseOptions(), uint64_t seed = 1)
+{
+	const rt_render_opts opts = detail::noise_render_opts(o, sample_split, seed, 0);
+	const rt_noise_opts nopts = detail::noise_opts(n);
+	const size_t px = (size_t)o.width * o.height;
+	AdaptiveFrame r;
+	r.mean.resize(3 * px);
+	r.variance.resize(px);
+	r.passes.resize(px);
+	r.tile_error.resize(((size_t)o.width + 7) / 8 * (((size_t)o.height + 7) / 8));
+	check(rt_render_adaptive(bvh.raw(), &camera.raw(), &opts, &nopts, nullptr, batch, min_batches, max_passes, r.mean.data(), r.variance.data(),
+	                         r.tile_error.data(), r.passes.data(), &r.result));
+	return r;
+}
+// The pixels of the listed 8 x 8 tiles (distinct indices into the grid of the tile errors) of `frame` (3 * width * height floats)
+// receive the bytes render gives them under the same options; every other pixel keeps its value.  Returns the rays shot.
+inline uint64_t render_tiles(const RenderOptions &o, const SimpleCamera &camera, const Bvh &bvh, uint32_t sample_split, const std::vector<uint32_t> &tiles,
+                             std::vector<float> &frame, uint64_t seed = 1)
+{
+	const rt_render_opts opts = detail::noise_render_opts(o, sample_split, seed, 0);
+	if (frame.size() != 3 * (size_t)o.width * o.height)
+		throw std::invalid_argument("render_tiles: frame must hold 3 * width * height floats");
+	uint64_t rays = 0;
+	check(rt_render_tiles(bvh.raw(), &camera.raw(), &opts, tiles.data(), (uint32_t)tiles.size(), frame.data(), nullptr, &rays));
+	return rays;
+}
+// The indices, ascending, of the tiles whose error is above `threshold` (strictly; NaN is not): what render_tiles takes next.
+inline std::vector<uint32_t> select_tiles(const Bvh &bvh, const std::vector<float> &tile_error, uint32_t width, uint32_t height, float threshold)
+{
+	std::vector<uint32_t> tiles(tile_error.size());
+	uint32_t count = 0;
+	check(rt_noise_select_tiles(bvh.raw(), tile_error.data(), width, height, threshold, tiles.data(), &count));
+	tiles.resize(count);
+	return tiles;
+}
+
 // Firefly-robust frames (semantics: rt_hip.h rt_robust_opts): from ONE render at `sample_split` (2..64 dividing the passes, 0 =
 // automatic) the rank-trimmed mean of its chunk sums next to the plain mean rt_render gives at that split.  Symmetric trimming
 // darkens; the defaults are untuned starting values.

@@ -27,7 +27,7 @@ RT_SPLIT_SAH, RT_SPLIT_MIDDLE, RT_SPLIT_EQUAL_COUNTS = range(3)
 RT_METHOD_NAIVE, RT_METHOD_MIS = range(2)
 RT_LAYOUT_FRAME, RT_LAYOUT_SHARD = range(2)
 RT_TUNE_TRAVERSAL, RT_TUNE_FEATURE_SET, RT_TUNE_SCENE_IN_LDS, RT_TUNE_SCHEDULE, RT_TUNE_WALK, RT_TUNE_STACK_CAP, RT_TUNE_EXCHANGE, RT_TUNE_WHOLE_PIXEL_SHARE = range(8)
-RT_TUNE_RADIANCE_GROUPS = 8  # rt_radiance: at most that many workgroups (0: automatic)
+RT_TUNE_RADIANCE_GROUPS = 8  # rt_radiance, rt_render_tiles: at most that many workgroups (0: automatic)
 
 NO_INDEX = 0xFFFFFFFFFFFFFFFF  # usize::MAX
 RT_DEVICE_NONE = -1  # rt_scene_create: Bvh::new on the host only (no GPU touched, nothing can be rendered)
@@ -354,6 +354,16 @@ class NoiseResult(C.Structure):  # rt_noise_result
     ]
 
 
+class AdaptiveResult(C.Structure):  # rt_adaptive_result
+    _fields_ = [
+        ("pixel_passes", C.c_uint64),
+        ("rays_shot", C.c_uint64),
+        ("batches", C.c_uint32),
+        ("converged", C.c_uint32),
+        ("summary", NoiseSummary),
+    ]
+
+
 NOISE_CHANNELS = ("mean", "variance", "lum_mean", "tile_error", "summary")
 
 
@@ -607,6 +617,7 @@ EXPECTED_SIZES = {
     "rt_noise_summary": (NoiseSummary, 16),
     "rt_noise_buffers": (NoiseBuffers, 40),
     "rt_noise_result": (NoiseResult, 40),
+    "rt_adaptive_result": (AdaptiveResult, 40),
     "rt_robust_opts": (RobustOpts, 32),
     "rt_robust_buffers": (RobustBuffers, 40),
     "rt_denoise_opts": (DenoiseOpts, 48),
@@ -704,6 +715,11 @@ EXPORTED_SYMBOLS = [
     "rt_noise_tiles_device",
     "rt_render_converged",
     "rt_render_denoised_split",
+    "rt_render_adaptive",
+    "rt_render_tiles",
+    "rt_render_tiles_device",
+    "rt_noise_select_tiles",
+    "rt_noise_select_tiles_device",
     "rt_robust_opts_default",
     "rt_render_robust",
     "rt_render_robust_device",

@@ -82,7 +82,7 @@ struct rt_scene {
 	uint32_t stack_cap_override = 0; // RT_TUNE_STACK_CAP
 	int exchange_mode = 0;           // RT_TUNE_EXCHANGE
 	int whole_share = kWholeShareDefault; // RT_TUNE_WHOLE_PIXEL_SHARE
-	uint32_t radiance_groups = 0;    // RT_TUNE_RADIANCE_GROUPS
+	uint32_t radiance_groups = 0;    // RT_TUNE_RADIANCE_GROUPS (rt_radiance and rt_render_tiles)
 	uint32_t stack_depth_narrow = 2; // HostScene::stack_depth_narrow (members of a multi-device scene have no host scene of their own)
 	uint32_t *d_stack_ovf = nullptr; // traversal-stack overflow area (deep trees under the fine schedule), grown on demand
 	size_t stack_ovf_words = 0;

@@ -19,6 +19,7 @@
 #include "rt_ao.h"
 #include "rt_denoise.h"
 #include "rt_noise.h"
+#include "rt_adaptive.h"
 #include "rt_render.h"
 #include "rt_robust.h"
 #include "rt_temporal.h"
@@ -1076,6 +1077,343 @@ int rt_render_converged(rt_scene *s, const rt_camera *camera, const rt_render_op
 	st.get(out_variance, L, p_variance);
 	st.get(out_tile_error, L, p_tiles);
 	return st.finish("render_converged");
+}
+
+} // extern "C"
+
+// ---- the render on a list of tiles and the active list (rt_adaptive.hip) ----
+// argument checks of both rt_render_tiles entry points in the order rt_hip.h states, the device last; *split is S resolved
+static int tiles_check(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const uint32_t *tiles, uint32_t n_tiles,
+                       const float *out, const float *chunk_sums, uint32_t *split, uint64_t *px)
+{
+	if (!s || !camera || !o || !out || (!tiles && n_tiles != 0u))
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	int rc = frame_sides("", o->width, o->height, 2);
+	if (rc != RT_OK)
+		return rc;
+	if (o->shard_count == 0 || o->shard_index >= o->shard_count)
+		return fail(RT_ERR_INVALID_ARGUMENT, "shard_index must be < shard_count and shard_count >= 1");
+	if (o->render_method != RT_METHOD_NAIVE && o->render_method != RT_METHOD_MIS)
+		return fail(RT_ERR_INVALID_ARGUMENT, "unknown render method");
+	if (o->samples_per_pixel == 0 || o->samples_per_pixel >= (1ull << 32))
+		return fail(RT_ERR_INVALID_ARGUMENT, "samples_per_pixel must be in [1, 2^32)");
+	if (o->output_layout != RT_LAYOUT_FRAME && o->output_layout != RT_LAYOUT_SHARD)
+		return fail(RT_ERR_INVALID_ARGUMENT, "unknown output layout");
+	if (o->width > (1ull << 31) || o->height > (1ull << 31) || o->width * o->height >= (1ull << 31))
+		return fail(RT_ERR_UNSUPPORTED, "render_tiles: 2^31 pixels or more");
+	*px = o->width * o->height;
+	uint32_t S = o->sample_split;
+	if (S == 0u) // as rt_render resolves it for the whole frame (a host-only scene: for 256 CUs)
+		S = auto_sample_split(s->n_cus, *px, o->samples_per_pixel, 1u);
+	if (S > o->samples_per_pixel)
+		return fail(RT_ERR_INVALID_ARGUMENT, "sample_split larger than samples_per_pixel");
+	*split = S;
+	if (S > 1u && ranges_overlap(out, 12 * *px, chunk_sums, 12ull * S * 64u * n_tiles))
+		return fail(RT_ERR_INVALID_ARGUMENT, "render_tiles: chunk_sums overlaps the frame");
+	if (o->output_layout != RT_LAYOUT_FRAME)
+		return fail(RT_ERR_UNSUPPORTED, "render_tiles: RT_LAYOUT_FRAME only");
+	if (o->shard_count != 1)
+		return fail(RT_ERR_UNSUPPORTED, "render_tiles: the whole frame only (shard_count 1)");
+	if (!s->peers.empty())
+		return fail(RT_ERR_UNSUPPORTED, "render_tiles: a multi-device scene renders its own shards");
+	if (64ull * n_tiles * S >= (1ull << 31))
+		return fail(RT_ERR_UNSUPPORTED, "render_tiles: 64 x tiles x sample_split exceeds 2^31 lane items");
+	return need_device(s);
+}
+
+// The workgroups of a launch over `items` work items (one wave each at a time): what the device holds at once -- kTilesWaves
+// workgroups a CU by registers, fewer where the LDS of the stacks and the fold records allows fewer (160 KB a CU) -- and never more
+// than the items need, so that a short list launches no idle workgroup; beyond that the waves take further items.
+static uint32_t tiles_groups(const rt_scene *s, size_t lds_bytes, uint64_t items)
+{
+	const uint64_t by_lds = std::max<uint64_t>(1, (160u * 1024u) / std::max<size_t>(1, lds_bytes));
+	const uint64_t resident = (uint64_t)std::max(1, s->n_cus) * std::min<uint64_t>(kTilesWaves, by_lds);
+	uint64_t groups = std::min<uint64_t>((items + kFourWaves - 1u) / kFourWaves, resident);
+	if (s->radiance_groups != 0u) // RT_TUNE_RADIANCE_GROUPS
+		groups = std::min<uint64_t>(groups, s->radiance_groups);
+	return (uint32_t)std::max<uint64_t>(groups, 1);
+}
+
+static int select_check(const rt_scene *s, const float *tile_error, uint32_t w, uint32_t h, float threshold, const uint32_t *tiles,
+                        const uint32_t *count)
+{
+	if (!s || !tile_error || !tiles || !count)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (threshold != threshold)
+		return fail(RT_ERR_INVALID_ARGUMENT, "select_tiles: the threshold is NaN");
+	uint64_t px = 0;
+	int rc = frame_pixels("select_tiles: ", w, h, 1, &px);
+	if (rc != RT_OK)
+		return rc;
+	const uint64_t n = noise_tile_count(w, h);
+	const void *buf[3] = {tiles, count, tile_error};
+	const uint64_t bytes[3] = {4 * n, 4, 4 * n};
+	rc = check_disjoint("select_tiles: an output buffer overlaps another buffer", buf, bytes, 2, 3);
+	return rc == RT_OK ? need_device(s) : rc;
+}
+
+extern "C" {
+
+int rt_render_tiles_device(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const uint32_t *d_tiles, uint32_t n_tiles,
+                           float *d_out_rgb, float *d_chunk_sums, uint64_t *d_rays_shot, void *hip_stream)
+{
+	uint32_t split = 0;
+	uint64_t px = 0;
+	int rc = tiles_check(s, camera, o, d_tiles, n_tiles, d_out_rgb, d_chunk_sums, &split, &px);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	bool prune = false;
+	DevScene dev;
+	rc = four_wave_traversal(s, &prune, &dev); // (rt_api_internal.h)
+	if (rc != RT_OK)
+		return rc;
+	const size_t lds_bytes = four_wave_stack_lds_bytes(dev) + kTilesRecordLdsBytes;
+	if (lds_bytes > s->max_lds)
+		return fail(RT_ERR_UNSUPPORTED, "traversal stacks exceed the LDS of one CU");
+	DevTilesParams P;
+	std::memset(&P, 0, sizeof P);
+	std::memcpy(P.cam.origin, camera->origin, 12);
+	std::memcpy(P.cam.lower_left, camera->lower_left, 12);
+	std::memcpy(P.cam.horizontal, camera->horizontal, 12);
+	std::memcpy(P.cam.vertical, camera->vertical, 12);
+	P.tiles = d_tiles;
+	P.out = d_out_rgb;
+	P.chunk_sums = split > 1u ? d_chunk_sums : nullptr;
+	P.rays_shot = reinterpret_cast<unsigned long long *>(d_rays_shot);
+	P.n_tiles = n_tiles;
+	P.width = (uint32_t)o->width;
+	P.height = (uint32_t)o->height;
+	P.tiles_x = (P.width + 7u) / 8u;
+	P.tile_count = P.tiles_x * ((P.height + 7u) / 8u);
+	P.spp = (uint32_t)o->samples_per_pixel;
+	P.split = split;
+	P.item_chunks = P.chunk_sums ? 1u : split;
+	const uint64_t items = (uint64_t)n_tiles * (split / P.item_chunks);
+	P.n_lanes = (uint32_t)(64u * items);
+	P.seed_lo = (uint32_t)o->seed;
+	P.seed_hi = (uint32_t)(o->seed >> 32);
+	P.sample_begin_lo = (uint32_t)o->sample_begin;
+	P.sample_begin_hi = (uint32_t)(o->sample_begin >> 32);
+	P.max_depth = o->max_depth;
+	P.rr_threshold = o->rr_threshold;
+	HIP_TRY(launch_tiles(o->render_method == RT_METHOD_NAIVE ? 0 : 1, prune, static_cast<hipStream_t>(hip_stream), dev, P,
+	                     tiles_groups(s, lds_bytes, items)));
+	return RT_OK;
+}
+
+int rt_render_tiles(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const uint32_t *tiles, uint32_t n_tiles, float *out_rgb,
+                    float *chunk_sums, uint64_t *rays_shot)
+{
+	uint32_t split = 0;
+	uint64_t px = 0;
+	int rc = tiles_check(s, camera, o, tiles, n_tiles, out_rgb, chunk_sums, &split, &px);
+	if (rc != RT_OK && rc != RT_ERR_NO_DEVICE)
+		return rc;
+	{ // the list itself, ahead of the device: distinct indices below the tile count
+		const uint64_t tile_count = noise_tile_count(o->width, o->height);
+		if (n_tiles > tile_count) // (a longer list repeats a tile or names none)
+			return fail(RT_ERR_INVALID_ARGUMENT, "render_tiles: more tiles listed than the frame has");
+		std::vector<bool> seen(tile_count, false);
+		for (uint32_t i = 0; i < n_tiles; ++i) {
+			if (tiles[i] >= tile_count)
+				return fail(RT_ERR_INVALID_ARGUMENT, "render_tiles: a tile index is not below the tile count");
+			if (seen[tiles[i]])
+				return fail(RT_ERR_INVALID_ARGUMENT, "render_tiles: a tile is listed twice");
+			seen[tiles[i]] = true;
+		}
+	}
+	if (rc != RT_OK)
+		return need_device(s);
+	HIP_TRY(hipSetDevice(s->device));
+	if (split == 1u)
+		chunk_sums = nullptr;
+	// the frame, the list, the chunk sums if asked for
+	Layout L;
+	const auto p_frame = L.add<float>(3 * px), p_sums = L.optional<float>(chunk_sums, 3ull * split * 64u * n_tiles);
+	const auto p_tiles = L.add<uint32_t>(n_tiles);
+	RT_TRY(grow_device_buffer(s->d_noise, s->d_noise_bytes, L));
+	Staging st{s};
+	st.put(L, p_frame, out_rgb);
+	if (n_tiles != 0u)
+		st.put(L, p_tiles, tiles);
+	if (st.ok())
+		st.rc = rt_render_tiles_device(s, camera, o, L.at(p_tiles), n_tiles, L.at(p_frame), L.at(p_sums), reinterpret_cast<uint64_t *>(s->d_rays),
+		                               s->stream);
+	if (n_tiles != 0u) {
+		st.get(out_rgb, L, p_frame);
+		st.get(chunk_sums, L, p_sums);
+	}
+	st.download(rays_shot, s->d_rays, sizeof(uint64_t));
+	return st.finish("render_tiles");
+}
+
+// Adaptive sampling (rt_hip.h): whole-frame batches are rt_render_converged's own (enqueue_noise_batch: the specialised render
+// kernels, the same state arithmetic, so a run that never drops a tile returns its bytes); a batch whose active list is shorter
+// than the tile grid goes through rt_render_tiles_device with its chunk buffer and adaptive_fold_kernel.  After either, the tile
+// stage recomputes every tile's error from the planes (a stopped tile's planes have not changed, so neither has its error) and the
+// selection makes the next list; the host reads the count, the summary and the ray counter.
+int rt_render_adaptive(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_noise_opts *n, const float *albedo,
+                       uint64_t batch, uint32_t min_batches, uint64_t max_passes, float *out_mean, float *out_variance, float *out_tile_error,
+                       uint32_t *out_passes, rt_adaptive_result *result)
+{
+	if (!s || !camera || !o || !n || !out_mean || !result)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (batch == 0 || max_passes < batch)
+		return fail(RT_ERR_INVALID_ARGUMENT, "render_adaptive: batch must be >= 1 and max_passes >= batch");
+	uint32_t split = 0;
+	uint64_t px = 0;
+	int rc = noise_render_check(s, o, n, batch, &split, &px);
+	if (rc != RT_OK)
+		return rc;
+	if (max_passes / batch >= (1ull << 24)) // (nb is divided by as a float)
+		return fail(RT_ERR_UNSUPPORTED, "render_adaptive: 2^24 batches or more");
+	const uint64_t n_tiles = noise_tile_count(o->width, o->height);
+	if (64ull * n_tiles * split >= (1ull << 31))
+		return fail(RT_ERR_UNSUPPORTED, "render_adaptive: 64 x tiles x sample_split exceeds 2^31 lane items");
+	{
+		const void *buf[5] = {out_mean, out_variance, out_tile_error, out_passes, albedo};
+		const uint64_t bytes[5] = {12 * px, 4 * px, 4 * n_tiles, 4 * px, 12 * px};
+		rc = check_disjoint("render_adaptive: an output buffer overlaps another buffer", buf, bytes, 4, 5);
+		if (rc == RT_OK)
+			rc = need_device(s);
+		if (rc != RT_OK)
+			return rc;
+	}
+	HIP_TRY(hipSetDevice(s->device));
+	// behind the state: this batch's render, the three planes and the tile errors (as rt_render_converged), then the per-pixel batch
+	// counts, the active list and its length, the albedo if given, and the chunk sums of a masked batch (sized for the whole grid)
+	Layout L;
+	const NoiseState N = noise_state(L, px);
+	const auto p_render = L.add<float>(3 * px), p_mean = L.add<float>(3 * px), p_lum = L.add<float>(px), p_variance = L.add<float>(px),
+	           p_tiles = L.add<float>(n_tiles), p_albedo = L.optional<float>(albedo, 3 * px), p_sums = L.add<float>(3ull * split * 64u * n_tiles);
+	const auto p_nb = L.add<uint32_t>(px), p_list = L.add<uint32_t>(n_tiles), p_count = L.add<uint32_t>(1);
+	RT_TRY(grow_device_buffer(s->d_noise, s->d_noise_bytes, L));
+	const rt_noise_buffers d_out = {L.at(p_mean), L.at(p_variance), L.at(p_lum), L.at(p_tiles), L.at(N.summary)};
+	uint64_t *const d_rays = reinterpret_cast<uint64_t *>(s->d_rays);
+	std::memset(result, 0, sizeof *result);
+	rt_render_opts ob = *o;
+	ob.samples_per_pixel = batch;
+	ob.sample_split = split;
+	uint32_t active = (uint32_t)n_tiles; // before any batch every tile is active
+	bool masked = false;
+	for (uint32_t nb = 1;; ++nb) {
+		ob.sample_begin = o->sample_begin + (uint64_t)(nb - 1u) * batch;
+		Staging st{s};
+		if (nb == 1u)
+			st.put(L, p_albedo, albedo);
+		if (st.ok()) {
+			// whole-frame batches come first: until one batch has been masked every pixel has nb - 1 batches behind it
+			if (!masked && (nb - 1u < min_batches || active == n_tiles)) {
+				st.rc = enqueue_noise_batch(s, camera, &ob, split, n, L.at(p_albedo), L.at(p_render), L, N, true, nb, &d_out, d_rays, s->stream);
+				if (st.rc == RT_OK)
+					st.e = launch_fill_u32(s->stream, L.at(p_nb), px, nb);
+			} else {
+				masked = true;
+				st.rc = rt_render_tiles_device(s, camera, &ob, L.at(p_list), active, L.at(p_render), L.at(p_sums), d_rays, s->stream);
+				if (st.rc == RT_OK) {
+					DevFoldParams F;
+					std::memset(&F, 0, sizeof F);
+					F.tiles = L.at(p_list);
+					F.n_tiles = active;
+					F.width = (uint32_t)o->width;
+					F.height = (uint32_t)o->height;
+					F.tiles_x = (F.width + 7u) / 8u;
+					F.tile_count = (uint32_t)n_tiles;
+					F.split = split;
+					F.chunk_passes = (uint32_t)(batch / split);
+					F.sums = L.at(p_sums);
+					F.albedo = L.at(p_albedo);
+					F.mean_in = L.at(p_render);
+					F.state_m = L.at(N.m);
+					F.state_l = L.at(N.l);
+					F.state_v = L.at(N.v);
+					F.nb = L.at(p_nb);
+					F.out_mean = L.at(p_mean);
+					F.out_lum = L.at(p_lum);
+					F.out_var = L.at(p_variance);
+					st.e = launch_adaptive_fold(s->stream, F);
+				}
+				if (st.ok())
+					st.rc = enqueue_noise_tiles(s->stream, L.at(p_lum), L.at(p_variance), o->width, o->height, n, L.at(p_tiles), L.at(N.summary));
+			}
+		}
+		if (st.ok())
+			st.rc = rt_noise_select_tiles_device(s, L.at(p_tiles), (uint32_t)o->width, (uint32_t)o->height, n->threshold, L.at(p_list),
+			                                     L.at(p_count), s->stream);
+		unsigned long long rays = 0;
+		st.get(&result->summary, L, N.summary);
+		st.get(&active, L, p_count);
+		st.download(&rays, s->d_rays, sizeof rays);
+		rc = st.finish("render_adaptive");
+		if (rc != RT_OK)
+			return rc;
+		result->batches = nb;
+		result->rays_shot += rays;
+		result->converged = nb >= min_batches && active == 0u ? 1u : 0u;
+		if (result->converged || (uint64_t)(nb + 1u) * batch > max_passes)
+			break;
+	}
+	std::vector<uint32_t> counts(px);
+	Staging st{s};
+	st.get(out_mean, L, p_mean);
+	st.get(out_variance, L, p_variance);
+	st.get(out_tile_error, L, p_tiles);
+	st.get(counts.data(), L, p_nb);
+	rc = st.finish("render_adaptive");
+	if (rc != RT_OK)
+		return rc;
+	for (uint64_t p = 0; p < px; ++p) {
+		result->pixel_passes += (uint64_t)counts[p] * batch;
+		if (out_passes)
+			out_passes[p] = (uint32_t)((uint64_t)counts[p] * batch);
+	}
+	return RT_OK;
+}
+
+int rt_noise_select_tiles_device(rt_scene *s, const float *d_tile_error, uint32_t width, uint32_t height, float threshold, uint32_t *d_tiles,
+                                 uint32_t *d_count, void *hip_stream)
+{
+	int rc = select_check(s, d_tile_error, width, height, threshold, d_tiles, d_count);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	DevSelectParams P;
+	std::memset(&P, 0, sizeof P);
+	P.tile_error = d_tile_error;
+	P.tiles = d_tiles;
+	P.count = d_count;
+	P.n_tiles = (uint32_t)noise_tile_count(width, height);
+	P.threshold = threshold;
+	HIP_TRY(launch_select_tiles(static_cast<hipStream_t>(hip_stream), P));
+	return RT_OK;
+}
+
+int rt_noise_select_tiles(rt_scene *s, const float *tile_error, uint32_t width, uint32_t height, float threshold, uint32_t *tiles,
+                          uint32_t *count)
+{
+	int rc = select_check(s, tile_error, width, height, threshold, tiles, count);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	const uint64_t n = noise_tile_count(width, height);
+	Layout L;
+	const auto p_err = L.add<float>(n);
+	const auto p_tiles = L.add<uint32_t>(n), p_count = L.add<uint32_t>(1);
+	RT_TRY(grow_device_buffer(s->d_noise, s->d_noise_bytes, L));
+	Staging st{s};
+	st.put(L, p_err, tile_error);
+	if (st.ok())
+		st.rc = rt_noise_select_tiles_device(s, L.at(p_err), width, height, threshold, L.at(p_tiles), L.at(p_count), s->stream);
+	uint32_t found = 0;
+	st.get(&found, L, p_count);
+	rc = st.finish("select_tiles");
+	if (rc != RT_OK)
+		return rc;
+	*count = found;
+	Staging st2{s};
+	st2.download(tiles, L.at(p_tiles), 4ull * found); // (the rest of `tiles` stays as it was)
+	return st2.finish("select_tiles");
 }
 
 int rt_render_denoised_split(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_denoise_opts *dopts, float *out_clean,

@@ -691,6 +691,73 @@ class HipScene:
                                               _p(noisy, C.c_float), _p(variance, C.c_float), C.byref(rays)))
         return clean, noisy, variance, rays.value
 
+    # ---- the render on a list of tiles, and the list of the noisy ones (rt_render_tiles, rt_noise_select_tiles) ----
+    def render_tiles(self, camera, opts, tiles, frame, chunk_sums=False):
+        """rt_render_tiles: the pixels of the listed 8 x 8 tiles (indices into the grid of noise_tiles, distinct) of `frame`
+        ((H, W, 3) f32, contiguous, changed in place) receive the bytes render() gives them under the same opts; every other
+        pixel keeps its value.  Returns (rays_shot, sums): sums is None, or with chunk_sums=True and a resolved split S > 1 the
+        (S, len(tiles), 8, 8, 3) chunk sums, padding lanes of edge tiles +0."""
+        h, w = int(opts.height), int(opts.width)
+        if not (isinstance(frame, np.ndarray) and frame.dtype == np.float32 and frame.shape == (h, w, 3) and frame.flags.c_contiguous):
+            raise ValueError(f"frame must be a contiguous float32 array of shape {(h, w, 3)}")
+        tiles = np.ascontiguousarray(tiles, dtype=np.uint32).reshape(-1)
+        sums = None
+        if chunk_sums:
+            split = int(opts.sample_split) or self.auto_sample_split(opts)
+            if split > 1:
+                sums = np.zeros((split, len(tiles), 8, 8, 3), dtype=np.float32)
+        rays = C.c_uint64()
+        _check(lib().rt_render_tiles(self._h, C.byref(camera), C.byref(opts), _p(tiles, C.c_uint32) if len(tiles) else None,
+                                     C.c_uint32(len(tiles)), _p(frame, C.c_float), _p(sums, C.c_float) if sums is not None else None,
+                                     C.byref(rays)))
+        return rays.value, sums
+
+    def render_adaptive(self, camera, opts, batch, min_batches=1, max_passes=None, albedo=None, **nopts):
+        """rt_render_adaptive: render_converged that renders, after min_batches whole-frame windows, only the tiles whose error is
+        still above the threshold.  Returns {"mean", "variance", "tile_error", "passes" ((H, W) uint32: passes rendered per pixel),
+        "batches", "converged", "pixel_passes", "rays_shot", "summary"}.  The mean of a stopped tile is a mean of fewer batches
+        than its neighbour's: tile borders can show at loose thresholds."""
+        n = noise_opts(**nopts)
+        h, w = int(opts.height), int(opts.width)
+        out, _, _ = _noise_outputs(w, h, ("mean", "variance", "tile_error"))
+        passes = np.zeros((h, w), dtype=np.uint32)
+        if albedo is not None:
+            albedo = np.ascontiguousarray(albedo, dtype=np.float32)
+            if albedo.shape != (h, w, 3):
+                raise ValueError(f"albedo must be {(h, w, 3)}, got {albedo.shape}")
+        res = abi.AdaptiveResult()
+        _check(lib().rt_render_adaptive(self._h, C.byref(camera), C.byref(opts), C.byref(n), _p(albedo, C.c_float) if albedo is not None else None,
+                                        C.c_uint64(batch), C.c_uint32(min_batches), C.c_uint64(64 * batch if max_passes is None else max_passes),
+                                        _p(out["mean"], C.c_float), _p(out["variance"], C.c_float), _p(out["tile_error"], C.c_float),
+                                        _p(passes, C.c_uint32), C.byref(res)))
+        out.update(passes=passes, batches=res.batches, converged=bool(res.converged), pixel_passes=res.pixel_passes,
+                   rays_shot=res.rays_shot, summary=_summary_dict(res.summary))
+        return out
+
+    def render_tiles_device(self, camera, opts, d_tiles, n_tiles, d_frame, d_chunk_sums=None, d_rays_ptr=None, stream=0):
+        """rt_render_tiles_device: asynchronous, DEVICE buffers of the scene's GPU; allocates nothing, keeps no state."""
+        _check(lib().rt_render_tiles_device(self._h, C.byref(camera), C.byref(opts), _dp(d_tiles, C.c_uint32), C.c_uint32(n_tiles),
+                                            _dp(d_frame), _dp(d_chunk_sums), C.c_void_p(d_rays_ptr) if d_rays_ptr else None,
+                                            C.c_void_p(stream)))
+
+    def noise_select_tiles(self, tile_error, threshold):
+        """rt_noise_select_tiles: the indices (uint32, ascending) of the tiles of a (ceil(H/8), ceil(W/8)) f32 error map whose
+        error is > threshold (NaN is not)."""
+        tile_error = np.ascontiguousarray(tile_error, dtype=np.float32)
+        if tile_error.ndim != 2:
+            raise ValueError(f"tile_error must be (tiles_y, tiles_x), got {tile_error.shape}")
+        ty, tx = tile_error.shape
+        tiles = np.zeros(ty * tx, dtype=np.uint32)
+        count = C.c_uint32()
+        _check(lib().rt_noise_select_tiles(self._h, _p(tile_error, C.c_float), C.c_uint32(8 * tx), C.c_uint32(8 * ty), C.c_float(threshold),
+                                           _p(tiles, C.c_uint32), C.byref(count)))
+        return tiles[:count.value].copy()
+
+    def noise_select_tiles_device(self, d_tile_error, width, height, threshold, d_tiles, d_count, stream=0):
+        """rt_noise_select_tiles_device: asynchronous, DEVICE buffers (d_tiles: capacity the tile count; d_count: one u32)."""
+        _check(lib().rt_noise_select_tiles_device(self._h, _dp(d_tile_error), C.c_uint32(width), C.c_uint32(height), C.c_float(threshold),
+                                                  _dp(d_tiles, C.c_uint32), _dp(d_count, C.c_uint32), C.c_void_p(stream)))
+
     # ---- firefly-robust frames (rt_render_robust, rt_robust_combine, rt_render_denoised_robust) ----
     def render_robust(self, camera, opts, albedo=None, channels=abi.ROBUST_CHANNELS, **ropts):
         """rt_render_robust: ONE render at opts.sample_split (2..64 dividing the passes; 0 = automatic) and the rank-trimmed mean
