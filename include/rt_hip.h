@@ -175,7 +175,11 @@ typedef struct rt_render_opts {
 	uint64_t width;
 	uint64_t height;
 	uint64_t samples_per_pixel; /* passes rendered by THIS call */
-	uint64_t sample_begin;      /* index of the first pass (0 for a fresh render) */
+	/* index of the first pass (0 for a fresh render).  A full 64-bit value, as the seed is: pass k of the call runs on the streams
+	 * (seed, pixel, sample_begin + k), and sample_begin + k is a uint64_t addition that WRAPS, as it does for rt_radiance: from
+	 * sample_begin = 2^64 - 2 the passes are samples 2^64 - 2, 2^64 - 1, 0, 1, ...  rt_render, rt_render_tiles and the CPU checker
+	 * (oracle/) all add this way. */
+	uint64_t sample_begin;
 	uint64_t seed;
 	int32_t render_method;  /* rt_render_method; reference default MIS (src/parameters.rs:37-38) */
 	uint32_t max_depth;     /* reference value 50 */

@@ -24,19 +24,26 @@ def passes(cpu_scene, cpu_camera, opts, n_passes, sample_begin=None):
     o.samples_per_pixel, o.sample_split = 1, 1
     out = np.zeros((n_passes, opts.height, opts.width, 3), F32)
     for s in range(n_passes):
-        o.sample_begin = begin + s
+        o.sample_begin = (begin + s) & ((1 << 64) - 1)  # a uint64_t addition: it wraps (rt_render_opts.sample_begin)
         out[s] = cpu_scene.render(cpu_camera, o, n_threads=1)[0]
     return out
 
 
-def chunk_sums(pass_images, split):
-    """(S, H, W, 3): chunk c = passes [c*n, (c+1)*n) summed in pass order from +0"""
+def chunk_bounds(spp, split):
+    """[b_0 .. b_S]: chunk c holds passes [b_c, b_c+1) = [floor(c*spp/S), floor((c+1)*spp/S)), the rule of
+    rt_render_opts.sample_split.  Where S divides spp these are the equal chunks [c*n, (c+1)*n), n = spp / S."""
+    assert 1 <= split <= spp, (spp, split)
+    return [(c * spp) // split for c in range(split + 1)]
+
+
+def chunk_sums(pass_images, split, bounds=None):
+    """(S, H, W, 3): chunk c = passes [b_c, b_c+1) summed in pass order from +0; the bounds are chunk_bounds' unless given"""
     spp = len(pass_images)
-    assert split >= 1 and spp % split == 0, (spp, split)
-    n = spp // split
+    b = chunk_bounds(spp, split) if bounds is None else list(bounds)
+    assert len(b) == split + 1 and b[0] == 0 and b[-1] == spp and all(lo <= hi for lo, hi in zip(b, b[1:])), (spp, split, b)
     sums = np.zeros((split,) + pass_images.shape[1:], F32)
     for c in range(split):
-        for s in range(c * n, (c + 1) * n):
+        for s in range(b[c], b[c + 1]):
             sums[c] = sums[c] + pass_images[s]
     return sums
 

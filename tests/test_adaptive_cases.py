@@ -10,7 +10,7 @@ import pytest
 import adaptive_checker as A
 import noise_checker as N
 import scenes
-from test_gpu_ao import _built
+from tiles_cases import built as _built  # test_gpu_ao.SCENES by name, radiance_cases' scenes by key
 
 abi = scenes.abi
 F32 = np.float32
@@ -23,6 +23,8 @@ CASES = {
     "materials_naive_mid": ("all_materials", abi.RT_METHOD_NAIVE, 4, 4, 2, 12, 0.5, True),
     "weekend_mis_low": ("rtweekend1", abi.RT_METHOD_MIS, 2, 2, 1, 4, 0.1, False),
     "shadowed_mis_mid": ("overshadowed", abi.RT_METHOD_MIS, 4, 2, 1, 10, 0.5, False),
+    # emissive primitives AND a samplable sky (radiance_cases.SHAPES): the one arm of sample_lights the loop had never run
+    "lit_sky_mis_mid": ("shape/primitives_and_sky", abi.RT_METHOD_MIS, 4, 2, 1, 10, 0.5, False),
 }
 
 

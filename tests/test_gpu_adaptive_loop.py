@@ -6,7 +6,7 @@ import pytest
 import scenes
 import test_adaptive_cases as T
 from gpu_support import assert_same_bits
-from test_gpu_ao import _built
+from tiles_cases import built as _built
 
 pytestmark = pytest.mark.gpu
 abi = scenes.abi
