@@ -56,8 +56,8 @@ constexpr uint32_t kTilesWaves = 4;
 constexpr uint32_t kTilesRecordWords = 11;
 constexpr size_t kTilesRecordLdsBytes = kTilesRecordWords * 256u * sizeof(uint32_t);
 
-// the counter zeroed by a kernel, `groups` 256-thread workgroups of tiles_kernel (the host sizes them: rt_api_post.cpp
-// tiles_groups) and, when the sums went to chunk_sums, the combine of the listed pixels
+// the counter zeroed by a kernel, `groups` 256-thread workgroups of tiles_kernel (the host sizes them: rt_api_internal.h
+// path_lane_groups) and, when the sums went to chunk_sums, the combine of the listed pixels
 hipError_t launch_tiles(int method, bool prune, hipStream_t stream, const DevScene &S, const DevTilesParams &P, uint32_t groups);
 hipError_t launch_select_tiles(hipStream_t stream, const DevSelectParams &P);
 

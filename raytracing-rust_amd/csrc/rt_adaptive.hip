@@ -1,10 +1,8 @@
 // rt_adaptive.hip -- the render on a LIST of 8 x 8 tiles (rt_render_tiles, include/rt_hip.h) and the selection of the tiles
 // whose error is above a threshold (rt_noise_select_tiles): what per-tile refinement and a region render need of the device.
 //
-// tiles_kernel is radiance_kernel (rt_radiance.hip) with another START and another FINISH: every lane is
-// the state machine FINISH / CLAIM / START / CLOSEST / SHADOW over the device functions of rt_shade.h / rt_intersect.h, the wave
-// decides by ballot which of the two walks an iteration runs, and the integrator arms are restated here once more -- shared
-// through a header they would have to be proven not to move radiance_kernel's register rows, which nothing here needs.
+// tiles_kernel is radiance_kernel (rt_radiance.hip) with another START and another FINISH around the same
+// per-lane integrator, rt_path_lane.h (its header describes the phases, the quorum and the hand-out).  This file holds:
 //   START   the render's own camera ray (rt_render.hip do_gen, rt_aov_common.h aov_camera_ray): the first two draws of the stream
 //           (seed, pixel, sample_begin + pass) jitter the pixel, SimpleCamera::get_ray draws its unused time, and the path goes on
 //           ON THAT STREAM
@@ -14,8 +12,7 @@
 // Work items: item i is tile slot i / (split / item_chunks) of the list and `item_chunks` chunks of it from chunk
 // (i % (split / item_chunks)) * item_chunks on; its 64 lane slots are the 64 pixels of the tile, row-major.  With a chunk buffer an
 // item is ONE chunk, so that ten tiles at split 16 are 10 240 lanes of work and not 640; without one it is the whole pixel and the
-// launch needs no memory besides the frame.  Hand-out as radiance_kernel's: wave w of W takes items w, w + W, ... and its lanes
-// refill in place from the wave's current item -- a cursor in registers, no counter in memory, nothing two launches share.  A lane
+// launch needs no memory besides the frame.  The hand-out's blocks of 64 slots are the items (WaveBlocks, rt_path_lane.h).  A lane
 // whose slot is padding of an edge tile writes +0 sums and claims again; a tile index past the grid is skipped whole.
 //
 // Ray counters: SamplerProgress.rays_shot as rt_render.hip counts it -- naive: one per walk of a path ray (do_shade), MIS: one per
@@ -25,7 +22,7 @@
 // above the threshold in ascending order, so the list is a pure function of the plane.
 #include <algorithm>
 
-#include "rt_aov_common.h"
+#include "rt_path_lane.h"
 #include "rt_adaptive.h"
 
 namespace rt {
@@ -35,8 +32,6 @@ struct TilesArgs {
 	DevTilesParams P;
 };
 
-namespace {
-
 // lanes of the wave that must wait for a closest-hit walk before it runs while shadow rays are pending elsewhere (as
 // kRadianceQuorum)
 #ifndef RT_TILES_QUORUM
@@ -44,57 +39,13 @@ namespace {
 #endif
 constexpr uint32_t kTilesQuorum = RT_TILES_QUORUM;
 
-enum : int { PH_CLAIM = 0, PH_START = 1, PH_CLOSEST = 2, PH_SHADOW = 3, PH_DONE = 4, PH_FINISH = 5, PH_FINISH_UNFILTERED = 6 };
-
-__device__ __forceinline__ float power_heuristic(float pdf_a, float pdf_b) // rt_core/src/lib.rs:36-40
-{
-	const float a_sq = pdf_a * pdf_a;
-	return a_sq / (a_sq + pdf_b * pdf_b);
-}
-
-// the sky's tables where they lie (global memory)
-__device__ __forceinline__ SkyTables sky_tables(const DevScene &S, KWords inv_res)
-{
-	SkyTables T;
-	T.row_cdf = S.sky.row_cdf;
-	T.marginal_cdf = S.sky.marginal_cdf;
-	T.guide = S.sky.guide;
-	T.guide_k = S.sky.guide_k;
-	T.inv_res = inv_res;
-	return T;
-}
-
-// bvh.get_samplable().contains(&index) (acceleration/mod.rs:84-88): the material of the primitive that was hit answers it
-__device__ __forceinline__ bool prim_in_light_list(const DevScene &S, uint32_t prim, uint32_t prim_mat)
-{
-	return prim != kNoPrim && mat_is_light(S, prim_mat);
-}
-
-// how many things sample_lights chooses among (mis.rs:135-157)
-__device__ __forceinline__ uint32_t light_choices(const DevScene &S) { return sky_can_sample(S) ? S.n_lights + 1u : S.n_lights; }
-
-// Bvh::get_pdf_from_index  acceleration/mod.rs:299-318
-template <class F>
-__device__ __forceinline__ float pdf_from_index(const DevScene &S, const SkyTables &T, const Hit &last, const Hit &now, V3 wi, uint32_t prim)
-{
-	if (prim == kNoPrim)
-		return div_by_count(sky_pdf(S, T, wi), light_choices(S));
-	const PrimGeom g = load_prim<F>(S, prim);
-	return div_by_count(prim_scattering_pdf<F>(g, last.point, wi, now), light_choices(S));
-}
-
-} // namespace
-
 template <int METHOD, bool PRUNE>
 __global__ __launch_bounds__(256, kTilesWaves) void tiles_kernel(const TilesArgs args_by_value)
 {
 	using F = FeatFull; // every primitive, material and texture type compiled in (as radiance_kernel)
 	extern __shared__ __align__(16) uint32_t lds[];
 	const DevScene &S = args_by_value.S;
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	uint32_t *stk = lds + wave * (S.stack_depth * kStackStride) + lane;
-	// the whole worst case in LDS: the overflow branch is never taken (its base only has to be some global pointer, rt_query.hip)
-	const StackMem SM = {S.stack_depth, 0u, const_cast<uint32_t *>(S.prim_rank), lds};
+	const WaveStack W = wave_stack(S, lds);
 	// Behind the stacks: the lane's FOLD RECORD, kTilesRecordWords words (word w of thread t at rec[256 w]).  What a pixel's fold
 	// carries from pass to pass is needed in FINISH, CLAIM and START only, so it waits in LDS while the walks and the shading have
 	// the registers: kept there, the MIS kernels spilled 14 to 19 VGPRs to scratch.
@@ -109,38 +60,15 @@ __global__ __launch_bounds__(256, kTilesWaves) void tiles_kernel(const TilesArgs
 		R_RAYS = 10u * 256u,     // the lane's ray counter (flushed in FINISH long before it could wrap)
 	};
 	rec[R_RAYS] = 0u;
-
-	// the wave's hand-out: lane slots [wq_next, wq_end) of its current item; `block` the next item it takes
-	const uint32_t n_waves = gridDim.x * kFourWaves;
-	uint32_t wq_next = 0u, wq_end = 0u, block = blockIdx.x * kFourWaves + wave;
-
-	// ---- per-lane state in registers: the path ----
-	int ph = PH_CLAIM;
-	rt_rng rng = {0u, 0u, 0u, 0u};
-	Ray ray; // the path ray (CLOSEST) or the shadow ray (SHADOW)
-	ray.o = ray.d = ray.inv = ray.shear = v3s(0.0f);
-	V3 thr = v3s(1.0f), outp = v3s(0.0f), wo = v3s(0.0f);
-	Hit hit; // MIS: the vertex the path stands on
-	hit.t = 0.0f;
-	hit.point = hit.error = hit.normal = v3s(0.0f);
-	hit.err_dot = 0.0f;
-	hit.uvx = hit.uvy = 0.0f;
-	hit.has_uv = hit.out = false;
-	uint32_t mat = 0u, depth = 0u;
-	bool primary = true;
-	// the light sample in flight (MIS): its direction as sampled, the shadow ray's limit (NaN: the sky, no limit) and the light's slot
-	V3 l_wi = v3s(0.0f);
-	float t_limit = 0.0f;
-	uint32_t skip = kNoPrim;
-	bool have_shadow = false; // false: sample_lights produced no shadow ray (the SHADOW step only scatters)
+	const auto count_ray = [rec] { rec[R_RAYS] += 1u; };
+	WaveBlocks blocks; // of 64 lane slots: a work item each
+	PathLane L;        // the path, in registers
 
 #pragma unroll 1
 	for (;;) {
-		// ---- FINISH: integrators/mod.rs:74-76, mis.rs:88-90, then the fold of rt_render_opts.sample_split ----
-		if (ph >= PH_FINISH) {
-			V3 v = outp;
-			if (ph == PH_FINISH && (contains_nan(v) || !is_finite_any(v)))
-				v = v3s(0.0f);
+		// ---- FINISH: the sample's value, then the fold of rt_render_opts.sample_split ----
+		if (L.ph >= PH_FINISH) {
+			const V3 v = L.sample_value();
 			const KArgPtr<TilesArgs> ka = aov_kargs(args_by_value);
 			const uint32_t split = ka->P.split;
 			const uint32_t k = rec[R_PASS] + 1u; // passes of the pixel folded once this one is
@@ -166,7 +94,7 @@ __global__ __launch_bounds__(256, kTilesWaves) void tiles_kernel(const TilesArgs
 				rec[R_RAYS] = lane_rays;
 			}
 			rec[R_PASS] = k;
-			ph = PH_START;
+			L.ph = PH_START;
 			if (k == rec[R_CHUNK_END]) {
 				const uint32_t spp = ka->P.spp;
 				float *const sums = ka->P.chunk_sums;
@@ -175,7 +103,7 @@ __global__ __launch_bounds__(256, kTilesWaves) void tiles_kernel(const TilesArgs
 					o[0] = sum.x;
 					o[1] = sum.y;
 					o[2] = sum.z;
-					ph = PH_CLAIM;
+					L.ph = PH_CLAIM;
 				} else if (sums != nullptr) { // the item was this chunk: [chunk][64 * slot + place][3]
 					const uint32_t id = rec[R_ID];
 					const uint32_t item = id >> 6, slot = item / split, c = item - slot * split;
@@ -183,7 +111,7 @@ __global__ __launch_bounds__(256, kTilesWaves) void tiles_kernel(const TilesArgs
 					o[0] = sum.x;
 					o[1] = sum.y;
 					o[2] = sum.z;
-					ph = PH_CLAIM;
+					L.ph = PH_CLAIM;
 				} else {
 					// the item is the pixel: its chunk sums added in chunk order from +0, divided by spp once.
 					// j = the chunk that starts at pass k: floor(j * spp / split) == k
@@ -199,7 +127,7 @@ __global__ __launch_bounds__(256, kTilesWaves) void tiles_kernel(const TilesArgs
 						o[0] = t.x / (float)spp;
 						o[1] = t.y / (float)spp;
 						o[2] = t.z / (float)spp;
-						ph = PH_CLAIM;
+						L.ph = PH_CLAIM;
 					} else {
 						rec[R_TOTAL] = __float_as_uint(t.x);
 						rec[R_TOTAL + 256u] = __float_as_uint(t.y);
@@ -213,18 +141,15 @@ __global__ __launch_bounds__(256, kTilesWaves) void tiles_kernel(const TilesArgs
 			rec[R_SUM + 256u] = __float_as_uint(sum.y);
 			rec[R_SUM + 512u] = __float_as_uint(sum.z);
 		}
-		// ---- CLAIM: refill in place from the wave's item (as radiance_kernel), then the lane slot -> tile, chunk and pixel ----
-		const uint64_t need = __ballot(ph == PH_CLAIM);
+		// ---- CLAIM: the next lane slot of the wave's item -> tile, chunk and pixel ----
+		const uint64_t need = __ballot(L.ph == PH_CLAIM);
 		if (need != 0ull) { // (wave-uniform)
 			const KArgPtr<TilesArgs> ka = aov_kargs(args_by_value);
 			const uint32_t n = ka->P.n_lanes;
-			const uint32_t cnt = (uint32_t)__popcll(need), avail = wq_end - wq_next;
-			const uint32_t base = block * 64u;
-			if (ph == PH_CLAIM) {
-				const uint32_t r = (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
-				const uint32_t id = r < avail ? wq_next + r : base + (r - avail);
+			if (L.ph == PH_CLAIM) {
+				const uint32_t id = blocks.claimed(need);
 				if (id >= n) {
-					ph = PH_DONE;
+					L.ph = PH_DONE;
 				} else {
 					const uint32_t split = ka->P.split, item_chunks = ka->P.item_chunks, spp = ka->P.spp;
 					const uint32_t per_tile = item_chunks == 1u ? split : 1u; // items a tile is
@@ -248,21 +173,14 @@ __global__ __launch_bounds__(256, kTilesWaves) void tiles_kernel(const TilesArgs
 						rec[R_PASS] = (uint32_t)(((uint64_t)c0 * spp) / split);
 						rec[R_CHUNK_END] = (uint32_t)(((uint64_t)(c0 + 1u) * spp) / split);
 						rec[R_SUM] = rec[R_SUM + 256u] = rec[R_SUM + 512u] = 0u; // +0
-						ph = PH_START;
+						L.ph = PH_START;
 					}
 				}
 			}
-			if (avail < cnt) {
-				wq_next = base + (cnt - avail);
-				wq_end = base + 64u;
-				if (base < n) // (past the list every claim ends its lane: the cursor stays, so it cannot wrap)
-					block += n_waves;
-			} else {
-				wq_next += cnt;
-			}
+			blocks.advance(need, n);
 		}
 		// ---- START: the next pass of the pixel.  random_sampler.rs:50-61 as rt_render.hip do_gen ----
-		if (ph == PH_START) {
+		if (L.ph == PH_START) {
 			const KArgPtr<TilesArgs> ka = aov_kargs(args_by_value);
 			const uint64_t seed = ((uint64_t)ka->P.seed_hi << 32) | ka->P.seed_lo;
 			const uint64_t sample_begin = ((uint64_t)ka->P.sample_begin_hi << 32) | ka->P.sample_begin_lo;
@@ -273,220 +191,21 @@ __global__ __launch_bounds__(256, kTilesWaves) void tiles_kernel(const TilesArgs
 			const uint32_t width = ka->P.width, height = ka->P.height;
 			const uint32_t pixel = rec[R_PIXEL], k = rec[R_PASS];
 			const uint32_t py = pixel / width, px = pixel - py * width;
-			rt_rng_seed(&rng, seed, (uint64_t)pixel, sample_begin + k);
-			const float jx = rt_rng_range_f32(&rng, 0.0f, 1.0f) + (float)px, jy = rt_rng_range_f32(&rng, 0.0f, 1.0f) + (float)py;
+			rt_rng_seed(&L.rng, seed, (uint64_t)pixel, sample_begin + k);
+			const float jx = rt_rng_range_f32(&L.rng, 0.0f, 1.0f) + (float)px, jy = rt_rng_range_f32(&L.rng, 0.0f, 1.0f) + (float)py;
 			const float u = jx / (float)(width - 1u);
 			const float v = 1.0f - jy / (float)(height - 1u);
-			ray = ray_new<F>(cam_o, cam_ll + cam_h * u + cam_v * v - cam_o); // SimpleCamera::get_ray  camera.rs:57-63
-			(void)rt_rng_f32(&rng);                                         // (its unused `time`)
-			thr = v3s(1.0f);
-			outp = v3s(0.0f);
-			depth = 0u;
-			primary = true;
-			ph = PH_CLOSEST;
+			L.ray = ray_new<F>(cam_o, cam_ll + cam_h * u + cam_v * v - cam_o); // SimpleCamera::get_ray  camera.rs:57-63
+			(void)rt_rng_f32(&L.rng);                                         // (its unused `time`)
+			L.start();
 		}
 
-		const uint64_t m_closest = __ballot(ph == PH_CLOSEST), m_shadow = __ballot(ph == PH_SHADOW);
+		const uint64_t m_closest = __ballot(L.ph == PH_CLOSEST), m_shadow = __ballot(L.ph == PH_SHADOW);
 		// no walk is waiting: every lane is DONE, or some claim again (their slot was padding or no tile)
-		if ((m_closest | m_shadow) == 0ull && __ballot(ph == PH_CLAIM) == 0ull)
+		if ((m_closest | m_shadow) == 0ull && __ballot(L.ph == PH_CLAIM) == 0ull)
 			break;
-
-		if (METHOD == 0 || m_shadow == 0ull || (uint32_t)__popcll(m_closest) >= kTilesQuorum) { // (wave-uniform)
-			// ---- CLOSEST: the walk of a path ray and the shading of what it reached ----
-			if (ph == PH_CLOSEST) {
-				float best_t;
-				uint32_t prim;
-				trace_closest<F, PRUNE>(S, S, SM, ray, stk, best_t, prim);
-				Hit nh;
-				uint32_t nmat;
-				if (prim != kNoPrim)
-					make_hit<F>(S, prim, ray, best_t, nh, nmat);
-				else
-					make_sky_hit(S, nh, nmat);
-				bool finish = false, filter = true;
-				if (METHOD == 0) {
-					// ---- NaiveIntegrator::get_colour loop body  integrators/mod.rs:31-72 ----
-					rec[R_RAYS] += 1u;
-					const V3 wo_n = ray.d;
-					const V3 emission = mat_get_emission<F>(S, nmat, nh, wo_n);
-					const bool exit = mat_scatter_ray<F>(S, nmat, ray, nh, rng);
-					if (depth == 0u) {
-						outp = outp + emission;
-						if (exit)
-							finish = true;
-					}
-					if (!finish && exit) {
-						outp = outp + thr * emission;
-						finish = true;
-					}
-					if (!finish) {
-						if (!mat_is_delta<F>(S, nmat))
-							thr = thr * mat_eval_over_pdf<F>(S, nmat, nh, wo_n, ray.d);
-						else
-							thr = thr * mat_eval<F>(S, nmat, nh, wo_n, ray.d);
-						const KArgPtr<TilesArgs> ka = aov_kargs(args_by_value);
-						if (depth > ka->P.rr_threshold) {
-							const float p = component_max(thr);
-							if (rt_rng_f32(&rng) > p)
-								finish = true;
-							else
-								thr = thr / p;
-						}
-						if (!finish) {
-							depth += 1u;
-							if (!(depth < ka->P.max_depth))
-								finish = true;
-						}
-					}
-					// (the path continues: `ray` already is the scattered ray, ph stays CLOSEST)
-				} else if (primary) {
-					// ---- MisIntegrator::get_colour prologue  mis.rs:17-33 ----
-					wo = ray.d;
-					hit = nh;
-					mat = nmat;
-					const V3 emission = mat_get_emission<F>(S, mat, hit, wo);
-					Ray clone = ray; // scatter on a clone: the draws are consumed, the ray is discarded (mis.rs:25)
-					const bool exit = mat_scatter_ray<F>(S, mat, clone, hit, rng);
-					outp = outp + emission;
-					if (exit) {
-						finish = true;
-						filter = false; // mis.rs:29-31 returns before the filter
-					} else {
-						depth = 1u;
-						primary = false;
-						if (!(depth < aov_kargs(args_by_value)->P.max_depth))
-							finish = true;
-					}
-				} else {
-					// ---- material-sampling half of the MIS loop  mis.rs:50-86 ----
-					const V3 m_wi = ray.d;
-					const float m_pdf = mat_scattering_pdf<F>(S, mat, hit, wo, m_wi);
-					const V3 le = mat_get_emission<F>(S, nmat, hit /* the OLD hit, mis.rs:55 */, m_wi);
-					thr = thr * mat_eval_over_pdf<F>(S, mat, hit, wo, m_wi);
-					if (!is_zero(le)) {
-						if ((prim_in_light_list(S, prim, nmat) && !mat_is_delta<F>(S, mat)) || (prim == kNoPrim && sky_can_sample(S))) {
-							const KArgPtr<TilesArgs> ka = aov_kargs(args_by_value);
-							const SkyTables T = sky_tables(S, reinterpret_cast<KWords>(&ka->S.sky.inv_res_ok));
-							const float l_pdf = pdf_from_index<F>(S, T, hit, nh, m_wi, prim);
-							const float mis_weight = power_heuristic(m_pdf, l_pdf);
-							outp = outp + thr * le * mis_weight;
-						} else {
-							outp = outp + thr * le;
-						}
-					}
-					if (mat_is_light(S, nmat)) {
-						finish = true;
-					} else {
-						const KArgPtr<TilesArgs> ka = aov_kargs(args_by_value);
-						if (depth > ka->P.rr_threshold) {
-							const float p = component_max(thr);
-							if (rt_rng_f32(&rng) > p)
-								finish = true;
-							else
-								thr = thr / p;
-						}
-						if (!finish) {
-							wo = m_wi;
-							hit = nh;
-							mat = nmat;
-							depth += 1u;
-							if (!(depth < ka->P.max_depth))
-								finish = true;
-						}
-					}
-				}
-				if (finish) {
-					ph = filter ? PH_FINISH : PH_FINISH_UNFILTERED;
-				} else if (METHOD == 1) {
-					// ---- sample_lights up to the shadow ray  mis.rs:95-157 ----
-					rec[R_RAYS] += 1u; // mis.rs:38
-					have_shadow = false;
-					skip = kNoPrim;
-					const uint32_t samplable_len = S.n_lights;
-					const bool sky_samplable = sky_can_sample(S);
-					bool pick_sky = false, pick_light = false;
-					uint32_t light_slot = 0u;
-					if (samplable_len == 0u) {
-						pick_sky = sky_samplable; // (0, true) => sample_sky(1.0); (0, false) => None
-					} else if (!sky_samplable) {
-						light_slot = rt_rng_below(&rng, samplable_len); // gen_range(0..len)
-						pick_light = true;
-					} else {
-						light_slot = rt_rng_below(&rng, samplable_len + 1u); // gen_range(0..=len)
-						if (light_slot == samplable_len)
-							pick_sky = true;
-						else
-							pick_light = true;
-					}
-					PrimGeom g;
-					g.type = g.material = 0u;
-					g.p0 = g.p1 = g.p2 = v3s(0.0f);
-					if (pick_sky) {
-						const KArgPtr<TilesArgs> ka = aov_kargs(args_by_value);
-						const SkyTables T = sky_tables(S, reinterpret_cast<KWords>(&ka->S.sky.inv_res_ok));
-						l_wi = sky_sample(S, T, rng);
-						t_limit = __uint_as_float(0x7FC00000u); // NaN: any t > 0 occludes
-						have_shadow = true;
-					} else if (pick_light) {
-						skip = S.lights[light_slot];
-						g = load_prim<F>(S, skip);
-						l_wi = prim_sample_visible_from_point<F>(g, hit.point, rng);
-					}
-					if (pick_sky || pick_light)
-						ray = ray_new<F>(hit.point + 0.0001f * hit.normal, l_wi);
-					if (pick_light) {
-						float lt;
-						if (prim_t<F>(g, ray, lt) && lt > 0.0f) { // Bvh::check_hit_index  mod.rs:231-242
-							t_limit = lt;
-							have_shadow = true;
-						}
-					}
-					ph = PH_SHADOW;
-				}
-			}
-		} else if (METHOD == 1) {
-			// ---- SHADOW: the shadow walk, the light's contribution (mis.rs:39-43) and material sampling (mis.rs:46-49) ----
-			if (ph == PH_SHADOW) {
-				if (have_shadow && !trace_any<F, PRUNE>(S, S, SM, ray, stk, t_limit, skip)) {
-					const bool is_sky = t_limit != t_limit;
-					const uint32_t n_l = S.n_lights;
-					// sample_lights' pdf_multiplier: 1 when the sky is all there is to choose
-					const float pdf_multiplier = n_l == 0u ? 1.0f : 1.0f / (float)light_choices(S);
-					bool valid = false;
-					V3 le = v3s(0.0f);
-					float l_pdf = 0.0f;
-					if (is_sky) { // sample_sky  mis.rs:104-115
-						const KArgPtr<TilesArgs> ka = aov_kargs(args_by_value);
-						const SkyTables T = sky_tables(S, reinterpret_cast<KWords>(&ka->S.sky.inv_res_ok));
-						le = mat_get_emission<F>(S, S.sky.material, hit, l_wi);
-						l_pdf = sky_pdf(S, T, l_wi) * pdf_multiplier;
-						valid = true;
-					} else { // sample_light  mis.rs:117-133 (`ray` still is the shadow ray)
-						Hit lh;
-						uint32_t lm;
-						make_hit<F>(S, skip, ray, t_limit, lh, lm);
-						const PrimGeom g = load_prim<F>(S, skip);
-						const float p = prim_scattering_pdf<F>(g, hit.point, l_wi, lh);
-						if (p > 0.0f) {
-							le = mat_get_emission<F>(S, lm, lh, l_wi);
-							l_pdf = p * pdf_multiplier;
-							valid = true;
-						}
-					}
-					if (valid) { // mis.rs:39-43
-						const float m_pdf = mat_scattering_pdf<F>(S, mat, hit, wo, l_wi);
-						const float mis_weight = power_heuristic(l_pdf, m_pdf);
-						outp = outp + thr * mat_eval<F>(S, mat, hit, wo, l_wi) * mis_weight * le / l_pdf;
-					}
-				}
-				// scatter_ray reads only the incoming direction of the ray that produced `hit`, which is `wo` (mis.rs:21,82)
-				ray.d = wo;
-				if (mat_scatter_ray<F>(S, mat, ray, hit, rng))
-					ph = PH_FINISH;
-				else
-					ph = PH_CLOSEST;
-			}
-		}
+		// (the walk falls through when only claims wait: a `continue` would be the loop's second back edge)
+		path_lane_walk<METHOD, PRUNE, kTilesQuorum, F>(L, args_by_value, W, m_closest, m_shadow, count_ray);
 	}
 
 	// ---- SamplerProgress.rays_shot: wave reduction, one atomic per wave (as rt_render.hip) ----
@@ -495,7 +214,7 @@ __global__ __launch_bounds__(256, kTilesWaves) void tiles_kernel(const TilesArgs
 		unsigned long long total = rec[R_RAYS];
 		for (int off = 32; off > 0; off >>= 1)
 			total += __shfl_down(total, off);
-		if (lane == 0u)
+		if ((threadIdx.x & 63u) == 0u)
 			atomicAdd(rays_shot, total);
 	}
 }
@@ -575,13 +294,7 @@ hipError_t launch_tiles(int method, bool prune, hipStream_t stream, const DevSce
 	A.P = P;
 	void (*const fn)(const TilesArgs) = method == 0 ? (prune ? tiles_kernel<0, true> : tiles_kernel<0, false>)
 	                                                : (prune ? tiles_kernel<1, true> : tiles_kernel<1, false>);
-	const size_t lds_bytes = four_wave_stack_lds_bytes(S) + kTilesRecordLdsBytes;
-	// deep trees: more than the default 64 KB of dynamic LDS per workgroup
-	hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-	if (e != hipSuccess)
-		return e;
-	hipLaunchKernelGGL(fn, dim3(groups), dim3(256), lds_bytes, stream, A);
-	e = hipGetLastError();
+	const hipError_t e = launch_path_lanes(fn, groups, four_wave_stack_lds_bytes(S) + kTilesRecordLdsBytes, stream, A);
 	if (e != hipSuccess || P.split == 1u || P.item_chunks != 1u)
 		return e;
 	hipLaunchKernelGGL(tiles_combine_kernel, dim3((64u * P.n_tiles + 255u) / 256u), dim3(256), 0, stream, P);

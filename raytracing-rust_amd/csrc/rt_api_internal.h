@@ -170,6 +170,20 @@ inline int four_wave_traversal(const rt_scene *s, bool *prune, rt::DevScene *dev
 	return RT_OK;
 }
 
+// The workgroups of a launch of the per-lane path kernels (rt_radiance, rt_render_tiles): what the device holds at once -- `waves`
+// workgroups a CU by registers, fewer where their `lds_bytes` of dynamic LDS allow fewer (160 KB a CU) -- never more than the
+// `wanted` the work fills (so that a short batch launches no idle workgroup; beyond that lanes refill) and never none;
+// RT_TUNE_RADIANCE_GROUPS caps it.
+inline uint32_t path_lane_groups(const rt_scene *s, size_t lds_bytes, uint32_t waves, uint64_t wanted)
+{
+	const uint64_t by_lds = std::max<uint64_t>(1, (160u * 1024u) / std::max<size_t>(1, lds_bytes));
+	const uint64_t resident = (uint64_t)std::max(1, s->n_cus) * std::min<uint64_t>(waves, by_lds);
+	uint64_t groups = std::min<uint64_t>(wanted, resident);
+	if (s->radiance_groups != 0u)
+		groups = std::min<uint64_t>(groups, s->radiance_groups);
+	return (uint32_t)std::max<uint64_t>(groups, 1);
+}
+
 template <class T> static int upload(rt_scene *s, const T *src, size_t count, const T **dst)
 {
 	void *p = nullptr;

@@ -1121,19 +1121,6 @@ static int tiles_check(const rt_scene *s, const rt_camera *camera, const rt_rend
 	return need_device(s);
 }
 
-// The workgroups of a launch over `items` work items (one wave each at a time): what the device holds at once -- kTilesWaves
-// workgroups a CU by registers, fewer where the LDS of the stacks and the fold records allows fewer (160 KB a CU) -- and never more
-// than the items need, so that a short list launches no idle workgroup; beyond that the waves take further items.
-static uint32_t tiles_groups(const rt_scene *s, size_t lds_bytes, uint64_t items)
-{
-	const uint64_t by_lds = std::max<uint64_t>(1, (160u * 1024u) / std::max<size_t>(1, lds_bytes));
-	const uint64_t resident = (uint64_t)std::max(1, s->n_cus) * std::min<uint64_t>(kTilesWaves, by_lds);
-	uint64_t groups = std::min<uint64_t>((items + kFourWaves - 1u) / kFourWaves, resident);
-	if (s->radiance_groups != 0u) // RT_TUNE_RADIANCE_GROUPS
-		groups = std::min<uint64_t>(groups, s->radiance_groups);
-	return (uint32_t)std::max<uint64_t>(groups, 1);
-}
-
 static int select_check(const rt_scene *s, const float *tile_error, uint32_t w, uint32_t h, float threshold, const uint32_t *tiles,
                         const uint32_t *count)
 {
@@ -1197,8 +1184,9 @@ int rt_render_tiles_device(rt_scene *s, const rt_camera *camera, const rt_render
 	P.sample_begin_hi = (uint32_t)(o->sample_begin >> 32);
 	P.max_depth = o->max_depth;
 	P.rr_threshold = o->rr_threshold;
+	// one wave per work item at a time (an empty list still plans one workgroup; launch_tiles then launches none)
 	HIP_TRY(launch_tiles(o->render_method == RT_METHOD_NAIVE ? 0 : 1, prune, static_cast<hipStream_t>(hip_stream), dev, P,
-	                     tiles_groups(s, lds_bytes, items)));
+	                     path_lane_groups(s, lds_bytes, kTilesWaves, (items + kFourWaves - 1u) / kFourWaves)));
 	return RT_OK;
 }
 

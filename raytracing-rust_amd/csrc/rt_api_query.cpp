@@ -147,18 +147,6 @@ static int radiance_check(const rt_scene *s, const rt_ray_desc *rays, uint64_t n
 	return need_device(s);
 }
 
-// The workgroups of a launch: one lane per ray up to what the device holds at once -- kRadianceWaves workgroups a CU by registers,
-// fewer where the stacks' LDS allows fewer (160 KB a CU) -- beyond that the lanes refill; RT_TUNE_RADIANCE_GROUPS caps it.
-static uint32_t radiance_groups(const rt_scene *s, const DevScene &dev, uint64_t n)
-{
-	const uint64_t by_lds = std::max<uint64_t>(1, (160u * 1024u) / std::max<size_t>(1, four_wave_stack_lds_bytes(dev)));
-	const uint64_t resident = (uint64_t)std::max(1, s->n_cus) * std::min<uint64_t>(kRadianceWaves, by_lds);
-	uint64_t groups = std::min<uint64_t>((n + 255) / 256, resident);
-	if (s->radiance_groups != 0u)
-		groups = std::min<uint64_t>(groups, s->radiance_groups);
-	return (uint32_t)groups;
-}
-
 int rt_radiance_device(rt_scene *s, const rt_ray_desc *d_rays, const uint64_t *d_streams, uint64_t n_rays, const rt_radiance_opts *o,
                        float *d_out_rgb, void *hip_stream)
 {
@@ -185,8 +173,9 @@ int rt_radiance_device(rt_scene *s, const rt_ray_desc *d_rays, const uint64_t *d
 	P.sample_begin_hi = (uint32_t)(o->sample_begin >> 32);
 	P.max_depth = o->max_depth;
 	P.rr_threshold = o->rr_threshold;
+	// one lane per ray (n_rays >= 1 here, so the planner's floor of one workgroup changes nothing)
 	HIP_TRY(launch_radiance(o->render_method == RT_METHOD_NAIVE ? 0 : 1, prune, static_cast<hipStream_t>(hip_stream), dev, P,
-	                        radiance_groups(s, dev, n_rays)));
+	                        path_lane_groups(s, four_wave_stack_lds_bytes(dev), kRadianceWaves, (n_rays + 255) / 256)));
 	return RT_OK;
 }
 

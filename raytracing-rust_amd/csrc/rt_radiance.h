@@ -18,7 +18,7 @@ struct DevRadianceParams {
 // waves per SIMD the kernels are compiled for (their __launch_bounds__): with the LDS of the stacks, what a CU holds of them
 constexpr uint32_t kRadianceWaves = 4;
 
-// `groups` 256-thread workgroups (the host sizes them: rt_api_query.cpp radiance_groups); every wave works through the 64-ray
+// `groups` 256-thread workgroups (the host sizes them: rt_api_internal.h path_lane_groups); every wave works through the 64-ray
 // blocks wave, wave + waves, ... of the batch.  (the whole worst-case traversal stack of a workgroup in LDS: four_wave_stack_lds_bytes)
 hipError_t launch_radiance(int method, bool prune, hipStream_t stream, const DevScene &S, const DevRadianceParams &P, uint32_t groups);
 

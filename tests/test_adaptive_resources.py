@@ -3,7 +3,8 @@ its own in librt_hip.so, outside the bundles profiles/resource_table.json descri
 the parent's code object; the radiance bundle still holds exactly its four kernels (tests/test_radiance_resources.py asserts
 their rows, unchanged).
 
-tiles_kernel is radiance_kernel's integrator with a camera ray in front and the render's fold behind.  What a pixel's fold
+tiles_kernel is radiance_kernel's integrator (csrc/rt_path_lane.h, one copy for both: DESIGN.md section 22 has the rows before and
+after the move) with a camera ray in front and the render's fold behind.  What a pixel's fold
 carries between passes (sums, pass counters, the ray counter: eleven words a lane) waits in LDS behind the stacks, not in
 registers: kept in registers the MIS kernels spilled 14 to 19 VGPRs.  As built: no scratch, no spilled vector register, four
 waves per SIMD -- radiance_kernel's occupancy.  What is built is what is asserted."""

@@ -97,7 +97,7 @@ def test_the_chain_needs_more_than_64_kb_of_dynamic_lds(hb):
     nodes, _, depth, _ = _host(hb, sc).wide_tree()  # rt_scene_wide_info's stack depth
     assert len(nodes) > 0
     assert RC.four_wave_lds_bytes(depth) == 87040 > 65536, depth
-    assert (160 * 1024) // RC.four_wave_lds_bytes(depth) == 1  # radiance_groups: one workgroup a CU
+    assert (160 * 1024) // RC.four_wave_lds_bytes(depth) == 1  # path_lane_groups: one workgroup a CU
 
 
 # ---- sky regimes ----
