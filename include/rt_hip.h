@@ -368,7 +368,10 @@ int rt_scene_set_traversal(rt_scene *scene, int mode);
  *                         set here, 0 included, turns that off (same pixels: a test renders both)
  *   RT_TUNE_SCENE_IN_LDS  1 (default): tiny scenes are staged whole into LDS; 0: read from HBM/L2
  *   RT_TUNE_SCHEDULE      -1 automatic, 0 coarse (two voted super-phases), 1 fine (every step of the
- *                         per-lane state machine is voted; implies the pruned walk)
+ *                         per-lane state machine is voted; implies the pruned walk).  The fine kernels walk the wide
+ *                         tree only: a scene that has none (its root is a leaf; bounds that are non-finite or beyond
+ *                         2^60) keeps the coarse schedule when 1 is asked for (rt_launch_info.fine = 0), and a fine
+ *                         launch never stages the scene in LDS, whatever RT_TUNE_SCENE_IN_LDS says
  *   RT_TUNE_WALK          0 automatic: pruned walks use the wide (four-child, 128-byte-node) regrouping of the
  *                         reference tree for regular rays and the two-child tree for the rest; 1: the two-child
  *                         tree for every ray
