@@ -214,6 +214,9 @@ class SkyInfo(C.Structure):  # rt_sky_info
     ]
 
 
+# Channel tables: one beside each struct of pointers, {channel: the shape of its array} -- "hw" (h, w), "hw3" (h, w, 3), "lhw"
+# (layers, h, w), "tiles" (the NOISE_TILE grid: (ceil(h/8), ceil(w/8))) or "summary" (one struct, not an array).  The element type
+# is the field's own (see channels()); a nested table stands under the name of the nested struct's field.
 class AovBuffers(C.Structure):  # rt_aov_buffers
     _fields_ = [
         ("albedo", C.POINTER(C.c_float)),
@@ -225,7 +228,8 @@ class AovBuffers(C.Structure):  # rt_aov_buffers
     ]
 
 
-AOV_CHANNELS = ("albedo", "normal", "depth", "coverage", "primitive", "material")
+AOV_SHAPES = {"albedo": "hw3", "normal": "hw3", "depth": "hw", "coverage": "hw", "primitive": "hw", "material": "hw"}
+AOV_CHANNELS = tuple(AOV_SHAPES)
 
 
 class AovChainOpts(C.Structure):  # rt_aov_chain_opts
@@ -243,6 +247,7 @@ class AovChainBuffers(C.Structure):  # rt_aov_chain_buffers
     ]
 
 
+AOV_CHAIN_SHAPES = {"aov": AOV_SHAPES, "bounces": "hw"}
 AOV_CHAIN_CHANNELS = AOV_CHANNELS + ("bounces",)
 AOV_CHAIN_MAX_CHAIN = 64
 
@@ -270,7 +275,8 @@ class MatteBuffers(C.Structure):  # rt_matte_buffers
     ]
 
 
-MATTE_BUFFERS = ("ids", "coverage", "residual")
+MATTE_SHAPES = {"ids": "lhw", "coverage": "lhw", "residual": "hw"}
+MATTE_BUFFERS = tuple(MATTE_SHAPES)
 
 
 # ambient occlusion (rt_render_ao)
@@ -292,7 +298,8 @@ class AoBuffers(C.Structure):  # rt_ao_buffers
     ]
 
 
-AO_CHANNELS = ("visibility", "bent_normal")
+AO_SHAPES = {"visibility": "hw", "bent_normal": "hw3"}
+AO_CHANNELS = tuple(AO_SHAPES)
 
 
 # radiance queries (rt_radiance)
@@ -364,7 +371,8 @@ class AdaptiveResult(C.Structure):  # rt_adaptive_result
     ]
 
 
-NOISE_CHANNELS = ("mean", "variance", "lum_mean", "tile_error", "summary")
+NOISE_SHAPES = {"mean": "hw3", "variance": "hw", "lum_mean": "hw", "tile_error": "tiles", "summary": "summary"}
+NOISE_CHANNELS = tuple(NOISE_SHAPES)
 
 
 # firefly-robust frames (rt_render_robust, rt_robust_combine, rt_render_denoised_robust)
@@ -392,7 +400,8 @@ class RobustBuffers(C.Structure):  # rt_robust_buffers
     ]
 
 
-ROBUST_CHANNELS = ("out", "mean", "gini", "trimmed", "dropped")
+ROBUST_SHAPES = {"out": "hw3", "mean": "hw3", "gini": "hw", "trimmed": "hw", "dropped": "hw"}
+ROBUST_CHANNELS = tuple(ROBUST_SHAPES)
 
 
 class DenoiseOpts(C.Structure):  # rt_denoise_opts
@@ -407,11 +416,14 @@ class DenoiseOpts(C.Structure):  # rt_denoise_opts
     ]
 
 
+DENOISE_SHAPES = {"color": "hw3", "albedo": "hw3", "normal": "hw3", "depth": "hw", "variance": "hw"}
+DENOISE_INPUTS = tuple(DENOISE_SHAPES)
+
+
 class DenoiseInputs(C.Structure):  # rt_denoise_inputs
-    _fields_ = [(name, C.POINTER(C.c_float)) for name in ("color", "albedo", "normal", "depth", "variance")]
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in DENOISE_INPUTS]
 
 
-DENOISE_INPUTS = ("color", "albedo", "normal", "depth", "variance")
 DENOISE_WORKSPACE_BYTES_PER_PIXEL = 48  # three float4 planes
 
 
@@ -427,11 +439,14 @@ class TemporalOpts(C.Structure):  # rt_temporal_opts
     ]
 
 
+TEMPORAL_SHAPES = {"color": "hw3", "albedo": "hw3", "normal": "hw3", "depth": "hw"}
+TEMPORAL_INPUTS = tuple(TEMPORAL_SHAPES)
+
+
 class TemporalInputs(C.Structure):  # rt_temporal_inputs
-    _fields_ = [(name, C.POINTER(C.c_float)) for name in ("color", "albedo", "normal", "depth")]
+    _fields_ = [(name, C.POINTER(C.c_float)) for name in TEMPORAL_INPUTS]
 
 
-TEMPORAL_INPUTS = ("color", "albedo", "normal", "depth")
 TEMPORAL_OPTIONS = ("alpha_color", "alpha_moments", "depth_tolerance", "normal_tolerance", "max_history")
 TEMPORAL_HISTORY_BYTES_PER_PIXEL = 48  # H0 = (e_1, n), H1 = (n^, z), H2 = (m1, m2, 0, 0): three float4 planes
 TEMPORAL_WORKSPACE_BYTES_PER_PIXEL = 32  # the denoiser's two (e, Var) planes
@@ -533,7 +548,9 @@ class UpscaleOpts(C.Structure):  # rt_upscale_opts
     ]
 
 
-UPSCALE_INPUTS = ("color", "src_albedo", "src_normal", "src_depth", "dst_albedo", "dst_normal", "dst_depth")
+UPSCALE_SHAPES = {"color": "hw3", "src_albedo": "hw3", "src_normal": "hw3", "src_depth": "hw",  # color and src_* at the source size,
+                  "dst_albedo": "hw3", "dst_normal": "hw3", "dst_depth": "hw"}  # dst_* at the destination size
+UPSCALE_INPUTS = tuple(UPSCALE_SHAPES)
 UPSCALE_GUIDES = ("albedo", "normal", "depth")
 UPSCALE_OPTIONS = ("sigma_normal", "depth_tolerance")
 
@@ -753,6 +770,18 @@ EXPORTED_SYMBOLS = [
     "rt_upscale",
     "rt_render_upscaled",
 ]
+
+
+def channels(table, struct):
+    """{channel: (the struct that holds its pointer, the element ctype, the shape name)} of a channel table and an instance of
+    its struct, a nested table flattened in place"""
+    out = {}
+    for name, shape in table.items():
+        if isinstance(shape, dict):
+            out.update(channels(shape, getattr(struct, name)))
+        else:
+            out[name] = (struct, dict(struct._fields_)[name]._type_, shape)
+    return out
 
 
 def default_aov_chain_opts(max_chain=8, fuzz_limit=0.0):

@@ -54,33 +54,109 @@ def _check(rc):
 
 
 def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
+    """a numpy array (None = not given) as a typed ctypes pointer"""
+    return None if a is None else a.ctypes.data_as(C.POINTER(t))
+
+
+def _ref(s):
+    """byref of a ctypes struct (None = not given)"""
+    return None if s is None else C.byref(s)
+
+
+def _vp(ptr):
+    """a device address (an int, 0 / None = not given) as a void pointer"""
+    return C.c_void_p(int(ptr)) if ptr else None
 
 
 def _dp(ptr, ctype=C.c_float):
     """a device address (an int, 0 / None = not given) as a typed ctypes pointer"""
-    return C.cast(C.c_void_p(int(ptr)), C.POINTER(ctype)) if ptr else None
+    return C.cast(_vp(ptr), C.POINTER(ctype)) if ptr else None
 
 
-def _set_f32_inputs(ins, color, optional, keep):
-    """the inputs of denoise / denoise_temporal: color (H, W, 3) and the optional (name, array or None, channels) guides as
-    contiguous f32 of the frame's size; sets the pointers of `ins`, appends the arrays to `keep`; returns (h, w)"""
-    color = np.ascontiguousarray(color, dtype=np.float32)
-    if color.ndim != 3 or color.shape[2] != 3:
-        raise ValueError(f"color must be (H, W, 3), got {color.shape}")
-    h, w = color.shape[:2]
-    keep.append(color)
-    ins.color = _p(color, C.c_float)
-    for name, a, channels in optional:
-        if a is None:
+def _known(key, allowed, what):
+    if key not in allowed:
+        raise ValueError(f"unknown {what} {key!r}: one of {sorted(allowed)}")
+
+
+def _f32(a, shape, name):
+    """`a` (None = not given) as a contiguous f32 array, which must have exactly `shape`"""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.shape != shape:
+        raise ValueError(f"{name} must be {shape}, got {a.shape}")
+    return a
+
+
+def _image(image, name="image"):
+    """(the frame as a contiguous f32 array, h, w) of an (H, W, 3) frame"""
+    a = np.ascontiguousarray(image, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"{name} must be (H, W, 3), got {a.shape}")
+    return a, a.shape[0], a.shape[1]
+
+
+def _guides(color, albedo, **named):
+    """(color, {guide: array or None}) of denoise / denoise_temporal, whose guides may come by name or as the dict render_aov
+    returns, either in place of `albedo` or, with the image under "color", in place of `color`"""
+    guides = {}
+    if isinstance(color, dict):  # denoise({"color": ..., **scene.render_aov(...)})
+        guides, color = color, color["color"]
+    elif isinstance(albedo, dict):  # denoise(color, scene.render_aov(...))
+        guides, albedo = albedo, None
+    return color, {k: guides.get(k, v) for k, v in dict(albedo=albedo, **named).items()}
+
+
+def _shape(kind, h, w, layers=0):
+    """the array shape an abi channel table names, for an h x w frame"""
+    return {"hw": (h, w), "hw3": (h, w, 3), "lhw": (layers, h, w), "tiles": ((h + 7) // 8, (w + 7) // 8)}[kind]
+
+
+def _host_buffers(table, bufs, channels, h, w, layers=0):
+    """{channel: zeroed array} for the `channels` (repeats count once) of an abi channel table at h x w, with the pointers of
+    the struct `bufs` set to them; a "summary" channel is its struct, for _summary_dict once the library has filled it"""
+    known = abi.channels(table, bufs)
+    out = {}
+    for name in channels:
+        _known(name, known, "channel")
+        holder, ctype, kind = known[name]
+        if name in out:
             continue
-        shape = (h, w, channels) if channels > 1 else (h, w)
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.shape != shape:
-            raise ValueError(f"{name} must be {shape}, got {a.shape}")
-        keep.append(a)
-        setattr(ins, name, _p(a, C.c_float))
-    return h, w
+        if kind == "summary":
+            out[name] = ctype()
+            setattr(holder, name, C.pointer(out[name]))
+        else:
+            out[name] = np.zeros(_shape(kind, h, w, layers), dtype=np.dtype(ctype))
+            setattr(holder, name, _p(out[name], ctype))
+    return out
+
+
+def _host_inputs(table, ins, arrays, h, w):
+    """the pointers of the struct `ins` set to `arrays` ({input: array or None}) as contiguous f32 of the shapes the abi channel
+    table gives them at h x w; `ins` keeps the arrays alive"""
+    known = abi.channels(table, ins)
+    ins._arrays = getattr(ins, "_arrays", [])
+    for name, a in arrays.items():
+        holder, ctype, kind = known[name]
+        ins._arrays.append(_f32(a, _shape(kind, h, w), name))
+        setattr(holder, name, _p(ins._arrays[-1], ctype))
+
+
+def _device_buffers(table, bufs, d_ptrs):
+    """`bufs` with the pointers of d_ptrs ({channel: device address}) set, each typed as the struct's field"""
+    known = abi.channels(table, bufs)
+    for name, ptr in d_ptrs.items():
+        _known(name, known, "channel")
+        holder, ctype, _ = known[name]
+        setattr(holder, name, _dp(ptr, ctype))
+    return bufs
+
+
+def _u64(symbol, opts):
+    """the uint64 a query `symbol(const opts *, uint64_t *)` of the library answers"""
+    n = C.c_uint64()
+    _check(getattr(lib(), symbol)(C.byref(opts), C.byref(n)))
+    return n.value
 
 
 def _f3(v):
@@ -333,7 +409,7 @@ class HipScene:
         marg = np.zeros(si["res_y"] + 1, dtype=np.float32)
         guide = np.zeros((si["res_y"] + 1, si["guide_k"]), dtype=np.uint8) if si["guide_k"] else None
         _check(lib().rt_scene_get_sky_tables(self._h, _p(rows, C.c_float), C.c_uint64(rows.size), _p(marg, C.c_float), C.c_uint64(marg.size),
-                                             _p(guide, C.c_uint8) if guide is not None else None, C.c_uint64(0 if guide is None else guide.size)))
+                                             _p(guide, C.c_uint8), C.c_uint64(0 if guide is None else guide.size)))
         return rows, marg, guide
 
     def selftest_sky(self, tables_in_lds, n, seed=1, dirs=None):
@@ -358,9 +434,7 @@ class HipScene:
 
     # ---- Sampler::sample_image: mean over opts.samples_per_pixel passes ----
     def render(self, camera, opts):
-        n = C.c_uint64()
-        _check(lib().rt_render_output_floats(C.byref(opts), C.byref(n)))
-        out = np.zeros(n.value, dtype=np.float32)
+        out = np.zeros(output_floats(opts), dtype=np.float32)
         rays = C.c_uint64()
         _check(lib().rt_render(self._h, C.byref(camera), C.byref(opts), _p(out, C.c_float), C.byref(rays)))
         if opts.output_layout == abi.RT_LAYOUT_FRAME:
@@ -371,9 +445,7 @@ class HipScene:
 
     def render_rgb8(self, camera, opts, gamma=2.2):
         """rt_render + the output stage on the device: the 8-bit image save_data_to_image would write (lib.rs:89-97)."""
-        n = C.c_uint64()
-        _check(lib().rt_render_output_floats(C.byref(opts), C.byref(n)))
-        out = np.zeros(n.value, dtype=np.uint8)
+        out = np.zeros(output_floats(opts), dtype=np.uint8)
         rays = C.c_uint64()
         _check(lib().rt_render_rgb8(self._h, C.byref(camera), C.byref(opts), C.c_float(gamma), _p(out, C.c_uint8), C.byref(rays)))
         return (out.reshape(opts.height, opts.width, 3) if opts.output_layout == abi.RT_LAYOUT_FRAME else out.reshape(-1, 3)), rays.value
@@ -384,8 +456,7 @@ class HipScene:
 
     def render_device(self, camera, opts, d_out_ptr, d_rays_ptr=None, stream=0):
         """Asynchronous render into device memory (raw pointers, e.g. torch.Tensor.data_ptr())."""
-        _check(lib().rt_render_device(self._h, C.byref(camera), C.byref(opts), C.c_void_p(d_out_ptr),
-                                      C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream)))
+        _check(lib().rt_render_device(self._h, C.byref(camera), C.byref(opts), C.c_void_p(d_out_ptr), _vp(d_rays_ptr), C.c_void_p(stream)))
 
     def gather_info(self):
         """(rt_gather_mode, why): how a multi-device scene moves its members' shards into devices[0] (rt_scene_gather_info)"""
@@ -417,29 +488,15 @@ class HipScene:
         """The auxiliary buffers of the primary hits of passes [sample_begin, sample_begin + samples_per_pixel) -- the camera rays
         rt_render traces -- as {channel: numpy array}: albedo / normal (H, W, 3) f32, depth / coverage (H, W) f32, primitive /
         material (H, W) u32 (abi.AOV_NO_ID where pass sample_begin missed).  Semantics: include/rt_hip.h rt_aov_buffers."""
-        channels = tuple(channels)
-        unknown = set(channels) - set(abi.AOV_CHANNELS)
-        if unknown:
-            raise ValueError(f"unknown AOV channels {sorted(unknown)}")
-        h, w = int(opts.height), int(opts.width)
-        out, bufs = {}, abi.AovBuffers()
-        for name in channels:
-            dtype, ctype = (np.uint32, C.c_uint32) if name in ("primitive", "material") else (np.float32, C.c_float)
-            shape = (h, w, 3) if name in ("albedo", "normal") else (h, w)
-            out[name] = np.zeros(shape, dtype=dtype)
-            setattr(bufs, name, _p(out[name], ctype))
+        bufs = abi.AovBuffers()
+        out = _host_buffers(abi.AOV_SHAPES, bufs, channels, int(opts.height), int(opts.width))
         _check(lib().rt_render_aov(self._h, C.byref(camera), C.byref(opts), C.byref(bufs)))
         return out
 
     def render_aov_device(self, camera, opts, d_ptrs, stream=0):
         """rt_render_aov_device: asynchronous, into DEVICE buffers of the scene's GPU.  d_ptrs = {channel: device pointer}
         (e.g. torch.Tensor.data_ptr()); channels left out are not produced."""
-        bufs = abi.AovBuffers()
-        for name, ptr in d_ptrs.items():
-            if name not in abi.AOV_CHANNELS:
-                raise ValueError(f"unknown AOV channel {name!r}")
-            ctype = C.c_uint32 if name in ("primitive", "material") else C.c_float
-            setattr(bufs, name, _dp(ptr, ctype))
+        bufs = _device_buffers(abi.AOV_SHAPES, abi.AovBuffers(), d_ptrs)
         _check(lib().rt_render_aov_device(self._h, C.byref(camera), C.byref(opts), C.byref(bufs), C.c_void_p(stream)))
 
     # ---- specular-chain AOV buffers (rt_render_aov_chain): the same channels seen through perfect mirrors and glass ----
@@ -448,17 +505,8 @@ class HipScene:
         surface, plus "bounces" (H, W) f32, the mean number of surfaces followed; as {channel: numpy array}.  albedo / normal /
         depth are drop-in guides for denoise and upscale (not for denoise_temporal: the depth is a path length).  Semantics:
         include/rt_hip.h rt_aov_chain_opts."""
-        channels = tuple(channels)
-        unknown = set(channels) - set(abi.AOV_CHAIN_CHANNELS)
-        if unknown:
-            raise ValueError(f"unknown AOV channels {sorted(unknown)}")
-        h, w = int(opts.height), int(opts.width)
-        out, bufs = {}, abi.AovChainBuffers()
-        for name in channels:
-            dtype, ctype = (np.uint32, C.c_uint32) if name in ("primitive", "material") else (np.float32, C.c_float)
-            shape = (h, w, 3) if name in ("albedo", "normal") else (h, w)
-            out[name] = np.zeros(shape, dtype=dtype)
-            setattr(bufs if name == "bounces" else bufs.aov, name, _p(out[name], ctype))
+        bufs = abi.AovChainBuffers()
+        out = _host_buffers(abi.AOV_CHAIN_SHAPES, bufs, channels, int(opts.height), int(opts.width))
         copts = abi.default_aov_chain_opts(max_chain, fuzz_limit)
         _check(lib().rt_render_aov_chain(self._h, C.byref(camera), C.byref(opts), C.byref(copts), C.byref(bufs)))
         return out
@@ -466,12 +514,7 @@ class HipScene:
     def render_aov_chain_device(self, camera, opts, d_ptrs, stream=0, max_chain=8, fuzz_limit=0.0):
         """rt_render_aov_chain_device: asynchronous, into DEVICE buffers of the scene's GPU.  d_ptrs = {channel: device pointer}
         over abi.AOV_CHAIN_CHANNELS; channels left out are not produced.  Allocates nothing: capturable from the first call."""
-        bufs = abi.AovChainBuffers()
-        for name, ptr in d_ptrs.items():
-            if name not in abi.AOV_CHAIN_CHANNELS:
-                raise ValueError(f"unknown AOV channel {name!r}")
-            ctype = C.c_uint32 if name in ("primitive", "material") else C.c_float
-            setattr(bufs if name == "bounces" else bufs.aov, name, _dp(ptr, ctype))
+        bufs = _device_buffers(abi.AOV_CHAIN_SHAPES, abi.AovChainBuffers(), d_ptrs)
         copts = abi.default_aov_chain_opts(max_chain, fuzz_limit)
         _check(lib().rt_render_aov_chain_device(self._h, C.byref(camera), C.byref(opts), C.byref(copts), C.byref(bufs),
                                                 C.c_void_p(stream)))
@@ -484,24 +527,16 @@ class HipScene:
         an empty layer the same ID and coverage 0.  id_kind: "material" / "primitive" or abi.RT_MATTE_ID_*.  Semantics:
         include/rt_hip.h rt_matte_opts."""
         m = matte_opts(id_kind=id_kind, layers=layers)
-        h, w, k = int(opts.height), int(opts.width), max(0, min(int(layers), abi.RT_MATTE_SLOTS))
-        out = {"ids": np.zeros((k, h, w), dtype=np.uint32), "coverage": np.zeros((k, h, w), dtype=np.float32)}
-        if residual:
-            out["residual"] = np.zeros((h, w), dtype=np.float32)
         bufs = abi.MatteBuffers()
-        for name, a in out.items():
-            setattr(bufs, name, _p(a, C.c_uint32 if name == "ids" else C.c_float))
+        k = max(0, min(int(layers), abi.RT_MATTE_SLOTS))  # enough to allocate; a layer count out of range is the library's to refuse
+        out = _host_buffers(abi.MATTE_SHAPES, bufs, abi.MATTE_BUFFERS if residual else ("ids", "coverage"), int(opts.height), int(opts.width), k)
         _check(lib().rt_render_matte(self._h, C.byref(camera), C.byref(opts), C.byref(m), C.byref(bufs)))
         return out
 
     def render_matte_device(self, camera, opts, d_ptrs, id_kind="material", layers=4, stream=0):
         """rt_render_matte_device: asynchronous, into DEVICE buffers of the scene's GPU.  d_ptrs = {"ids": ..., "coverage": ...,
         "residual": ...} device pointers (the residual may be left out).  Allocates nothing: capturable from the first call."""
-        bufs = abi.MatteBuffers()
-        for name, ptr in d_ptrs.items():
-            if name not in abi.MATTE_BUFFERS:
-                raise ValueError(f"unknown matte buffer {name!r}")
-            setattr(bufs, name, _dp(ptr, C.c_uint32 if name == "ids" else C.c_float))
+        bufs = _device_buffers(abi.MATTE_SHAPES, abi.MatteBuffers(), d_ptrs)
         m = matte_opts(id_kind=id_kind, layers=layers)
         _check(lib().rt_render_matte_device(self._h, C.byref(camera), C.byref(opts), C.byref(m), C.byref(bufs), C.c_void_p(stream)))
 
@@ -527,8 +562,7 @@ class HipScene:
     def matte_extract_device(self, d_ids, d_coverage, width, height, layers, d_sorted_ids, n_ids, d_out, stream=0):
         """rt_matte_extract_device: asynchronous, DEVICE buffers of the scene's GPU, no state.  d_sorted_ids: n_ids u32 in ASCENDING
         order (not verified; 0 / None with n_ids = 0)."""
-        bufs = abi.MatteBuffers()
-        bufs.ids, bufs.coverage = _dp(d_ids, C.c_uint32), _dp(d_coverage, C.c_float)
+        bufs = _device_buffers(abi.MATTE_SHAPES, abi.MatteBuffers(), {"ids": d_ids, "coverage": d_coverage})
         _check(lib().rt_matte_extract_device(self._h, C.byref(bufs), C.c_uint32(width), C.c_uint32(height), C.c_uint32(layers),
                                              _dp(d_sorted_ids, C.c_uint32), C.c_uint64(n_ids), _dp(d_out), C.c_void_p(stream)))
 
@@ -539,25 +573,15 @@ class HipScene:
         {"visibility": (H, W) f32, "bent_normal": (H, W, 3) f32}; only `channels` are produced.  A pixel no pass hit has visibility
         1 and bent normal 0.  Semantics: include/rt_hip.h rt_ao_opts."""
         a = ao_opts(rays_per_pass=rays_per_pass, radius=radius)
-        h, w = int(opts.height), int(opts.width)
-        out = {}
         bufs = abi.AoBuffers()
-        for name in channels:
-            if name not in abi.AO_CHANNELS:
-                raise ValueError(f"unknown AO channel {name!r}")
-            out[name] = np.zeros((h, w, 3) if name == "bent_normal" else (h, w), dtype=np.float32)
-            setattr(bufs, name, _p(out[name], C.c_float))
+        out = _host_buffers(abi.AO_SHAPES, bufs, channels, int(opts.height), int(opts.width))
         _check(lib().rt_render_ao(self._h, C.byref(camera), C.byref(opts), C.byref(a), C.byref(bufs)))
         return out
 
     def render_ao_device(self, camera, opts, d_ptrs, rays_per_pass=4, radius=0.0, stream=0):
         """rt_render_ao_device: asynchronous, into DEVICE buffers of the scene's GPU.  d_ptrs = {"visibility": ..., "bent_normal":
         ...} device pointers (either may be left out).  Allocates nothing: capturable from the first call."""
-        bufs = abi.AoBuffers()
-        for name, ptr in d_ptrs.items():
-            if name not in abi.AO_CHANNELS:
-                raise ValueError(f"unknown AO channel {name!r}")
-            setattr(bufs, name, _dp(ptr, C.c_float))
+        bufs = _device_buffers(abi.AO_SHAPES, abi.AoBuffers(), d_ptrs)
         a = ao_opts(rays_per_pass=rays_per_pass, radius=radius)
         _check(lib().rt_render_ao_device(self._h, C.byref(camera), C.byref(opts), C.byref(a), C.byref(bufs), C.c_void_p(stream)))
 
@@ -567,16 +591,10 @@ class HipScene:
         (H, W); returns (H, W, 3) f32.  The guides may also come as the dict render_aov returns, in place of `albedo` (its
         other channels are ignored), or with the image under "color" in place of `color`.  Keyword options: iterations,
         sigma_luminance, sigma_normal, sigma_depth.  Semantics: include/rt_hip.h rt_denoise_opts."""
-        guides = {}
-        if isinstance(color, dict):  # denoise({"color": ..., **scene.render_aov(...)})
-            guides, color = color, color["color"]
-        elif isinstance(albedo, dict):  # denoise(color, scene.render_aov(...))
-            guides, albedo = albedo, None
-        albedo, normal = guides.get("albedo", albedo), guides.get("normal", normal)
-        depth, variance = guides.get("depth", depth), guides.get("variance", variance)
-        ins, keep = abi.DenoiseInputs(), []
-        h, w = _set_f32_inputs(ins, color, (("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1),
-                                            ("variance", variance, 1)), keep)
+        color, guides = _guides(color, albedo, normal=normal, depth=depth, variance=variance)
+        color, h, w = _image(color, "color")
+        ins = abi.DenoiseInputs()
+        _host_inputs(abi.DENOISE_SHAPES, ins, {"color": color, **guides}, h, w)
         o = denoise_opts(w, h, **opts)
         out = np.zeros((h, w, 3), dtype=np.float32)
         _check(lib().rt_denoise(self._h, C.byref(ins), C.byref(o), _p(out, C.c_float)))
@@ -586,11 +604,7 @@ class HipScene:
         """rt_denoise_device: asynchronous, DEVICE buffers of the scene's GPU.  d_ptrs = {input: device pointer} over
         abi.DENOISE_INPUTS ("color" required); d_workspace: denoise_workspace_bytes(opts) bytes, 16-byte aligned;
         opts: abi.DenoiseOpts with the frame size set."""
-        ins = abi.DenoiseInputs()
-        for name, ptr in d_ptrs.items():
-            if name not in abi.DENOISE_INPUTS:
-                raise ValueError(f"unknown denoise input {name!r}")
-            setattr(ins, name, _dp(ptr))
+        ins = _device_buffers(abi.DENOISE_SHAPES, abi.DenoiseInputs(), d_ptrs)
         _check(lib().rt_denoise_device(self._h, C.byref(ins), C.byref(opts), C.c_void_p(int(d_workspace)),
                                        _dp(d_out), C.c_void_p(stream)))
 
@@ -601,12 +615,14 @@ class HipScene:
         h, w = int(opts.height), int(opts.width)
         if dopts is None:
             dopts = denoise_opts(w, h)
-        clean = np.zeros((h, w, 3), dtype=np.float32)
-        noisy = np.zeros((h, w, 3), dtype=np.float32)
+        return self._frames_and_rays("rt_render_denoised", (C.byref(camera), C.byref(opts), C.byref(dopts)), (h, w, 3), (h, w, 3))
+
+    def _frames_and_rays(self, symbol, args, *shapes):
+        """a composite call symbol(scene, args..., one zeroed f32 frame per shape..., rays_shot *): (the frames..., rays_shot)"""
+        frames = [np.zeros(shape, dtype=np.float32) for shape in shapes]
         rays = C.c_uint64()
-        _check(lib().rt_render_denoised(self._h, C.byref(camera), C.byref(opts), C.byref(dopts), _p(clean, C.c_float),
-                                        _p(noisy, C.c_float), C.byref(rays)))
-        return clean, noisy, rays.value
+        _check(getattr(lib(), symbol)(self._h, *args, *(_p(a, C.c_float) for a in frames), C.byref(rays)))
+        return (*frames, rays.value)
 
     # ---- noise estimates (rt_render_noise, rt_noise_tiles, rt_render_converged, rt_render_denoised_split) ----
     def render_noise(self, camera, opts, albedo=None, channels=abi.NOISE_CHANNELS, **nopts):
@@ -616,30 +632,23 @@ class HipScene:
         Keyword options: luminance_floor, threshold.  Semantics: include/rt_hip.h rt_noise_opts."""
         n = noise_opts(**nopts)
         h, w = int(opts.height), int(opts.width)
-        out, bufs, summary = _noise_outputs(w, h, channels)
-        if albedo is not None:
-            albedo = np.ascontiguousarray(albedo, dtype=np.float32)
-            if albedo.shape != (h, w, 3):
-                raise ValueError(f"albedo must be {(h, w, 3)}, got {albedo.shape}")
+        bufs = abi.NoiseBuffers()
+        out = _host_buffers(abi.NOISE_SHAPES, bufs, ("mean", *channels), h, w)
+        albedo = _f32(albedo, (h, w, 3), "albedo")
         rays = C.c_uint64()
-        _check(lib().rt_render_noise(self._h, C.byref(camera), C.byref(opts), C.byref(n), _p(albedo, C.c_float) if albedo is not None else None,
-                                     C.byref(bufs), C.byref(rays)))
-        if summary is not None:
-            out["summary"] = _summary_dict(summary)
+        _check(lib().rt_render_noise(self._h, C.byref(camera), C.byref(opts), C.byref(n), _p(albedo, C.c_float), C.byref(bufs), C.byref(rays)))
+        if "summary" in out:
+            out["summary"] = _summary_dict(out["summary"])
         out["rays_shot"] = rays.value
         return out
 
     def render_noise_device(self, camera, opts, d_ptrs, d_albedo=None, d_rays_ptr=None, stream=0, **nopts):
         """rt_render_noise_device: asynchronous, DEVICE buffers of the scene's GPU.  d_ptrs = {channel: device pointer} over
         abi.NOISE_CHANNELS ("mean" required; "summary": 16 bytes)."""
-        bufs = abi.NoiseBuffers()
-        for name, ptr in d_ptrs.items():
-            if name not in abi.NOISE_CHANNELS:
-                raise ValueError(f"unknown noise channel {name!r}")
-            setattr(bufs, name, _dp(ptr, abi.NoiseSummary if name == "summary" else C.c_float))
+        bufs = _device_buffers(abi.NOISE_SHAPES, abi.NoiseBuffers(), d_ptrs)
         n = noise_opts(**nopts)
         _check(lib().rt_render_noise_device(self._h, C.byref(camera), C.byref(opts), C.byref(n), _dp(d_albedo), C.byref(bufs),
-                                            C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream)))
+                                            _vp(d_rays_ptr), C.c_void_p(stream)))
 
     def noise_tiles(self, lum_mean, variance, **nopts):
         """rt_noise_tiles: the tile stage alone on (H, W) f32 planes; returns (tile_error (ceil(H/8), ceil(W/8)), summary dict)."""
@@ -649,7 +658,7 @@ class HipScene:
             raise ValueError(f"lum_mean and variance must be (H, W) alike, got {lum_mean.shape} and {variance.shape}")
         h, w = lum_mean.shape
         n = noise_opts(**nopts)
-        tiles = np.zeros(((h + 7) // 8, (w + 7) // 8), dtype=np.float32)
+        tiles = np.zeros(_shape("tiles", h, w), dtype=np.float32)
         summary = abi.NoiseSummary()
         _check(lib().rt_noise_tiles(self._h, _p(lum_mean, C.c_float), _p(variance, C.c_float), C.c_uint32(w), C.c_uint32(h), C.byref(n),
                                     _p(tiles, C.c_float), C.byref(summary)))
@@ -668,11 +677,12 @@ class HipScene:
         means, not the bytes of one render of all the passes."""
         n = noise_opts(**nopts)
         h, w = int(opts.height), int(opts.width)
-        out, _, _ = _noise_outputs(w, h, ("mean", "variance", "tile_error"))
+        bufs = abi.NoiseBuffers()
+        out = _host_buffers(abi.NOISE_SHAPES, bufs, ("mean", "variance", "tile_error"), h, w)
         res = abi.NoiseResult()
         _check(lib().rt_render_converged(self._h, C.byref(camera), C.byref(opts), C.byref(n), C.c_uint64(batch), C.c_uint32(min_batches),
-                                         C.c_uint64(64 * batch if max_passes is None else max_passes), _p(out["mean"], C.c_float),
-                                         _p(out["variance"], C.c_float), _p(out["tile_error"], C.c_float), C.byref(res)))
+                                         C.c_uint64(64 * batch if max_passes is None else max_passes), bufs.mean, bufs.variance,
+                                         bufs.tile_error, C.byref(res)))
         out.update(passes=res.passes, batches=res.batches, converged=bool(res.converged), rays_shot=res.rays_shot,
                    summary=_summary_dict(res.summary))
         return out
@@ -683,13 +693,7 @@ class HipScene:
         h, w = int(opts.height), int(opts.width)
         if dopts is None:
             dopts = denoise_opts(w, h)
-        clean = np.zeros((h, w, 3), dtype=np.float32)
-        noisy = np.zeros((h, w, 3), dtype=np.float32)
-        variance = np.zeros((h, w), dtype=np.float32)
-        rays = C.c_uint64()
-        _check(lib().rt_render_denoised_split(self._h, C.byref(camera), C.byref(opts), C.byref(dopts), _p(clean, C.c_float),
-                                              _p(noisy, C.c_float), _p(variance, C.c_float), C.byref(rays)))
-        return clean, noisy, variance, rays.value
+        return self._frames_and_rays("rt_render_denoised_split", (C.byref(camera), C.byref(opts), C.byref(dopts)), (h, w, 3), (h, w, 3), (h, w))
 
     # ---- the render on a list of tiles, and the list of the noisy ones (rt_render_tiles, rt_noise_select_tiles) ----
     def render_tiles(self, camera, opts, tiles, frame, chunk_sums=False):
@@ -708,8 +712,7 @@ class HipScene:
                 sums = np.zeros((split, len(tiles), 8, 8, 3), dtype=np.float32)
         rays = C.c_uint64()
         _check(lib().rt_render_tiles(self._h, C.byref(camera), C.byref(opts), _p(tiles, C.c_uint32) if len(tiles) else None,
-                                     C.c_uint32(len(tiles)), _p(frame, C.c_float), _p(sums, C.c_float) if sums is not None else None,
-                                     C.byref(rays)))
+                                     C.c_uint32(len(tiles)), _p(frame, C.c_float), _p(sums, C.c_float), C.byref(rays)))
         return rays.value, sums
 
     def render_adaptive(self, camera, opts, batch, min_batches=1, max_passes=None, albedo=None, **nopts):
@@ -719,17 +722,14 @@ class HipScene:
         than its neighbour's: tile borders can show at loose thresholds."""
         n = noise_opts(**nopts)
         h, w = int(opts.height), int(opts.width)
-        out, _, _ = _noise_outputs(w, h, ("mean", "variance", "tile_error"))
+        bufs = abi.NoiseBuffers()
+        out = _host_buffers(abi.NOISE_SHAPES, bufs, ("mean", "variance", "tile_error"), h, w)
         passes = np.zeros((h, w), dtype=np.uint32)
-        if albedo is not None:
-            albedo = np.ascontiguousarray(albedo, dtype=np.float32)
-            if albedo.shape != (h, w, 3):
-                raise ValueError(f"albedo must be {(h, w, 3)}, got {albedo.shape}")
+        albedo = _f32(albedo, (h, w, 3), "albedo")
         res = abi.AdaptiveResult()
-        _check(lib().rt_render_adaptive(self._h, C.byref(camera), C.byref(opts), C.byref(n), _p(albedo, C.c_float) if albedo is not None else None,
-                                        C.c_uint64(batch), C.c_uint32(min_batches), C.c_uint64(64 * batch if max_passes is None else max_passes),
-                                        _p(out["mean"], C.c_float), _p(out["variance"], C.c_float), _p(out["tile_error"], C.c_float),
-                                        _p(passes, C.c_uint32), C.byref(res)))
+        _check(lib().rt_render_adaptive(self._h, C.byref(camera), C.byref(opts), C.byref(n), _p(albedo, C.c_float), C.c_uint64(batch),
+                                        C.c_uint32(min_batches), C.c_uint64(64 * batch if max_passes is None else max_passes),
+                                        bufs.mean, bufs.variance, bufs.tile_error, _p(passes, C.c_uint32), C.byref(res)))
         out.update(passes=passes, batches=res.batches, converged=bool(res.converged), pixel_passes=res.pixel_passes,
                    rays_shot=res.rays_shot, summary=_summary_dict(res.summary))
         return out
@@ -737,8 +737,7 @@ class HipScene:
     def render_tiles_device(self, camera, opts, d_tiles, n_tiles, d_frame, d_chunk_sums=None, d_rays_ptr=None, stream=0):
         """rt_render_tiles_device: asynchronous, DEVICE buffers of the scene's GPU; allocates nothing, keeps no state."""
         _check(lib().rt_render_tiles_device(self._h, C.byref(camera), C.byref(opts), _dp(d_tiles, C.c_uint32), C.c_uint32(n_tiles),
-                                            _dp(d_frame), _dp(d_chunk_sums), C.c_void_p(d_rays_ptr) if d_rays_ptr else None,
-                                            C.c_void_p(stream)))
+                                            _dp(d_frame), _dp(d_chunk_sums), _vp(d_rays_ptr), C.c_void_p(stream)))
 
     def noise_select_tiles(self, tile_error, threshold):
         """rt_noise_select_tiles: the indices (uint32, ascending) of the tiles of a (ceil(H/8), ceil(W/8)) f32 error map whose
@@ -767,11 +766,11 @@ class HipScene:
         "gini"), trim, gini_gain.  Semantics: include/rt_hip.h rt_robust_opts."""
         r = robust_opts(**ropts)
         h, w = int(opts.height), int(opts.width)
-        out, bufs = _robust_outputs(w, h, channels)
-        albedo = _robust_albedo(albedo, w, h)
+        bufs = abi.RobustBuffers()
+        out = _host_buffers(abi.ROBUST_SHAPES, bufs, ("out", *channels), h, w)
+        albedo = _f32(albedo, (h, w, 3), "albedo")
         rays = C.c_uint64()
-        _check(lib().rt_render_robust(self._h, C.byref(camera), C.byref(opts), C.byref(r), _p(albedo, C.c_float) if albedo is not None else None,
-                                      C.byref(bufs), C.byref(rays)))
+        _check(lib().rt_render_robust(self._h, C.byref(camera), C.byref(opts), C.byref(r), _p(albedo, C.c_float), C.byref(bufs), C.byref(rays)))
         out["rays_shot"] = rays.value
         return out
 
@@ -779,8 +778,9 @@ class HipScene:
         """rt_render_robust_device: asynchronous, DEVICE buffers of the scene's GPU.  d_ptrs = {channel: device pointer} over
         abi.ROBUST_CHANNELS ("out" required)."""
         r = robust_opts(**ropts)
-        _check(lib().rt_render_robust_device(self._h, C.byref(camera), C.byref(opts), C.byref(r), _dp(d_albedo), C.byref(_robust_device_buffers(d_ptrs)),
-                                             C.c_void_p(d_rays_ptr) if d_rays_ptr else None, C.c_void_p(stream)))
+        bufs = _device_buffers(abi.ROBUST_SHAPES, abi.RobustBuffers(), d_ptrs)
+        _check(lib().rt_render_robust_device(self._h, C.byref(camera), C.byref(opts), C.byref(r), _dp(d_albedo), C.byref(bufs),
+                                             _vp(d_rays_ptr), C.c_void_p(stream)))
 
     def robust_combine(self, chunk_sums, chunk_passes, albedo=None, channels=abi.ROBUST_CHANNELS, **ropts):
         """rt_robust_combine: the rank-trimmed mean of the caller's chunk sums (S, H, W, 3) f32, each the sum of chunk_passes
@@ -790,18 +790,19 @@ class HipScene:
             raise ValueError(f"chunk_sums must be (S, H, W, 3), got {sums.shape}")
         split, h, w = sums.shape[:3]
         r = robust_opts(**ropts)
-        out, bufs = _robust_outputs(w, h, channels)
-        albedo = _robust_albedo(albedo, w, h)
+        bufs = abi.RobustBuffers()
+        out = _host_buffers(abi.ROBUST_SHAPES, bufs, ("out", *channels), h, w)
+        albedo = _f32(albedo, (h, w, 3), "albedo")
         _check(lib().rt_robust_combine(self._h, _p(sums, C.c_float), C.c_uint32(split), C.c_uint64(chunk_passes), C.c_uint32(w), C.c_uint32(h),
-                                       _p(albedo, C.c_float) if albedo is not None else None, C.byref(r), C.byref(bufs)))
+                                       _p(albedo, C.c_float), C.byref(r), C.byref(bufs)))
         return out
 
     def robust_combine_device(self, d_chunk_sums, split, chunk_passes, width, height, d_ptrs, d_albedo=None, stream=0, **ropts):
         """rt_robust_combine_device: asynchronous, DEVICE planes [S][h][w][3]; allocates nothing."""
         r = robust_opts(**ropts)
+        bufs = _device_buffers(abi.ROBUST_SHAPES, abi.RobustBuffers(), d_ptrs)
         _check(lib().rt_robust_combine_device(self._h, _dp(d_chunk_sums), C.c_uint32(split), C.c_uint64(chunk_passes), C.c_uint32(width),
-                                              C.c_uint32(height), _dp(d_albedo), C.byref(r), C.byref(_robust_device_buffers(d_ptrs)),
-                                              C.c_void_p(stream)))
+                                              C.c_uint32(height), _dp(d_albedo), C.byref(r), C.byref(bufs), C.c_void_p(stream)))
 
     def render_denoised_robust(self, camera, opts, dopts=None, **ropts):
         """rt_render_denoised_robust: the AOVs, render_robust with their albedo and the filter on the robust frame (no variance
@@ -810,12 +811,8 @@ class HipScene:
         if dopts is None:
             dopts = denoise_opts(w, h)
         r = robust_opts(**ropts)
-        clean = np.zeros((h, w, 3), dtype=np.float32)
-        robust = np.zeros((h, w, 3), dtype=np.float32)
-        rays = C.c_uint64()
-        _check(lib().rt_render_denoised_robust(self._h, C.byref(camera), C.byref(opts), C.byref(r), C.byref(dopts), _p(clean, C.c_float),
-                                               _p(robust, C.c_float), C.byref(rays)))
-        return clean, robust, rays.value
+        return self._frames_and_rays("rt_render_denoised_robust", (C.byref(camera), C.byref(opts), C.byref(r), C.byref(dopts)),
+                                     (h, w, 3), (h, w, 3))
 
     # ---- temporal accumulation with camera reprojection (rt_denoise_temporal) ----
     def denoise_temporal(self, color, camera, albedo=None, normal=None, depth=None, motion=False, **opts):
@@ -824,21 +821,16 @@ class HipScene:
         abi.Camera.  The scene keeps the history between calls (temporal_reset forgets it; a new frame size starts over).
         Returns out (H, W, 3) f32, or (out, motion (H, W, 2) f32) with motion=True.  Keyword options: those of denoise_opts and
         of abi.TEMPORAL_OPTIONS.  Semantics: include/rt_hip.h rt_temporal_opts."""
-        guides = {}
-        if isinstance(color, dict):
-            guides, color = color, color["color"]
-        elif isinstance(albedo, dict):
-            guides, albedo = albedo, None
-        albedo, normal, depth = guides.get("albedo", albedo), guides.get("normal", normal), guides.get("depth", depth)
-        if depth is None:
+        color, guides = _guides(color, albedo, normal=normal, depth=depth)
+        if guides["depth"] is None:
             raise ValueError("denoise_temporal needs depth")
-        ins, keep = abi.TemporalInputs(), []
-        h, w = _set_f32_inputs(ins, color, (("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1)), keep)
+        color, h, w = _image(color, "color")
+        ins = abi.TemporalInputs()
+        _host_inputs(abi.TEMPORAL_SHAPES, ins, {"color": color, **guides}, h, w)
         o = temporal_opts(w, h, **opts)
         out = np.zeros((h, w, 3), dtype=np.float32)
         mv = np.zeros((h, w, 2), dtype=np.float32) if motion else None
-        _check(lib().rt_denoise_temporal(self._h, C.byref(ins), C.byref(camera), C.byref(o), _p(out, C.c_float),
-                                         _p(mv, C.c_float) if motion else None))
+        _check(lib().rt_denoise_temporal(self._h, C.byref(ins), C.byref(camera), C.byref(o), _p(out, C.c_float), _p(mv, C.c_float)))
         return (out, mv) if motion else out
 
     def temporal_reset(self):
@@ -851,15 +843,9 @@ class HipScene:
         pointer} over abi.TEMPORAL_INPUTS ("color" and "depth" required); d_history_in 0 = no history (prev_camera may then be
         None); the histories temporal_history_bytes(opts) and the workspace temporal_workspace_bytes(opts) bytes, 16-byte
         aligned; d_motion 0 = not written; opts: abi.TemporalOpts with the frame size set."""
-        ins = abi.TemporalInputs()
-        for name, ptr in d_ptrs.items():
-            if name not in abi.TEMPORAL_INPUTS:
-                raise ValueError(f"unknown temporal input {name!r}")
-            setattr(ins, name, _dp(ptr))
-        _check(lib().rt_denoise_temporal_device(
-            self._h, C.byref(ins), C.byref(camera), C.byref(prev_camera) if prev_camera is not None else None,
-            C.c_void_p(int(d_history_in) or None), C.c_void_p(int(d_history_out) or None), C.byref(opts),
-            C.c_void_p(int(d_workspace) or None), _dp(d_out), _dp(d_motion), C.c_void_p(stream)))
+        ins = _device_buffers(abi.TEMPORAL_SHAPES, abi.TemporalInputs(), d_ptrs)
+        _check(lib().rt_denoise_temporal_device(self._h, C.byref(ins), C.byref(camera), _ref(prev_camera), _vp(d_history_in), _vp(d_history_out),
+                                                C.byref(opts), _vp(d_workspace), _dp(d_out), _dp(d_motion), C.c_void_p(stream)))
 
     # ---- display stage: auto-exposure, tone curve, transfer, 8-bit output (rt_display) ----
     def display(self, image, histogram=False, **opts):
@@ -867,10 +853,7 @@ class HipScene:
         state between calls (display_reset forgets it; a new frame size starts over); display_state() is the state after the last
         call.  histogram=True returns (pixels, the 256 uint32 counts).  Keyword options: display_opts'.  Semantics: include/rt_hip.h
         rt_display_opts."""
-        a = np.ascontiguousarray(image, dtype=np.float32)
-        if a.ndim != 3 or a.shape[2] != 3:
-            raise ValueError(f"image must be (H, W, 3), got {a.shape}")
-        h, w = a.shape[:2]
+        a, h, w = _image(image)
         o = display_opts(w, h, **opts)
         out = np.zeros((h, w, 3 if o.pixel_format == abi.RT_PIXEL_RGB8 else 4), dtype=np.uint8)
         hist = np.zeros(abi.DISPLAY_HISTOGRAM_BINS, dtype=np.uint32)
@@ -896,60 +879,45 @@ class HipScene:
         """rt_display_device: asynchronous, DEVICE buffers of the scene's GPU, no state of its own.  d_rgb: W*H*3 f32; d_state: an
         rt_display_state (16 bytes, read and written on the device; 0 = none); d_workspace: display_workspace_bytes(opts) bytes,
         16-byte aligned; d_out: display_output_bytes(opts) bytes; d_histogram: 256 uint32 or 0; opts: abi.DisplayOpts."""
-        def vp(ptr):
-            return C.c_void_p(int(ptr) or None)
-
-        _check(lib().rt_display_device(self._h, C.cast(vp(d_rgb), C.POINTER(C.c_float)), C.byref(opts), vp(d_state),
-                                       vp(d_workspace), vp(d_out), C.cast(vp(d_histogram), C.POINTER(C.c_uint32)),
-                                       C.c_void_p(stream)))
+        _check(lib().rt_display_device(self._h, _dp(d_rgb), C.byref(opts), _vp(d_state), _vp(d_workspace), _vp(d_out),
+                                       _dp(d_histogram, C.c_uint32), C.c_void_p(stream)))
 
     # ---- bloom stage: glare around over-range pixels, ahead of the display stage (rt_bloom) ----
     def bloom(self, image, state=None, **opts):
         """rt_bloom: an (H, W, 3) f32 frame to an (H, W, 3) f32 frame, the input plus `intensity` times a wide blur of its
         over-threshold part.  state: an abi.DisplayState (display_state()) whose ev is added to exposure_ev, or None.  Keyword
         options: bloom_opts'.  Semantics: include/rt_hip.h rt_bloom_opts."""
-        a = np.ascontiguousarray(image, dtype=np.float32)
-        if a.ndim != 3 or a.shape[2] != 3:
-            raise ValueError(f"image must be (H, W, 3), got {a.shape}")
-        h, w = a.shape[:2]
+        a, h, w = _image(image)
         o = bloom_opts(w, h, **opts)
         out = np.zeros((h, w, 3), dtype=np.float32)
-        _check(lib().rt_bloom(self._h, _p(a, C.c_float), C.byref(o), C.byref(state) if state is not None else None,
-                              _p(out, C.c_float)))
+        _check(lib().rt_bloom(self._h, _p(a, C.c_float), C.byref(o), _ref(state), _p(out, C.c_float)))
         return out
 
     def bloom_device(self, d_rgb, opts, d_state, d_workspace, d_out, stream=0):
         """rt_bloom_device: asynchronous, DEVICE buffers of the scene's GPU, no state.  d_rgb, d_out: W*H*3 f32 (d_out may be
         d_rgb); d_state: an rt_display_state read on the device, or 0; d_workspace: bloom_workspace_bytes(opts) bytes, 16-byte
         aligned; opts: abi.BloomOpts."""
-        _check(lib().rt_bloom_device(self._h, _dp(d_rgb), C.byref(opts), C.c_void_p(int(d_state) or None),
-                                     C.c_void_p(int(d_workspace) or None), _dp(d_out), C.c_void_p(stream)))
+        _check(lib().rt_bloom_device(self._h, _dp(d_rgb), C.byref(opts), _vp(d_state), _vp(d_workspace), _dp(d_out), C.c_void_p(stream)))
 
     # ---- depth-of-field stage: depth-driven disc blur, ahead of the bloom stage (rt_dof) ----
     def dof(self, image, depth, camera=None, coc=False, **opts):
         """rt_dof: an (H, W, 3) f32 frame and its (H, W) depth plane (render_aov's "depth") to the defocused (H, W, 3) frame.
         camera: the abi.Camera the depth was rendered with, or None (then planar_depth must be 0).  coc=True returns (out, the
         (H, W) signed circle-of-confusion radii).  Keyword options: dof_opts'.  Semantics: include/rt_hip.h rt_dof_opts."""
-        a = np.ascontiguousarray(image, dtype=np.float32)
-        if a.ndim != 3 or a.shape[2] != 3:
-            raise ValueError(f"image must be (H, W, 3), got {a.shape}")
-        h, w = a.shape[:2]
-        z = np.ascontiguousarray(depth, dtype=np.float32)
-        if z.shape != (h, w):
-            raise ValueError(f"depth must be {(h, w)}, got {z.shape}")
+        a, h, w = _image(image)
+        z = _f32(depth, (h, w), "depth")
         o = dof_opts(w, h, **opts)
         out = np.zeros((h, w, 3), dtype=np.float32)
         radii = np.zeros((h, w), dtype=np.float32) if coc else None
-        _check(lib().rt_dof(self._h, _p(a, C.c_float), _p(z, C.c_float), C.byref(camera) if camera is not None else None,
-                            C.byref(o), _p(out, C.c_float), _p(radii, C.c_float) if coc else None))
+        _check(lib().rt_dof(self._h, _p(a, C.c_float), _p(z, C.c_float), _ref(camera), C.byref(o), _p(out, C.c_float), _p(radii, C.c_float)))
         return (out, radii) if coc else out
 
     def dof_device(self, d_rgb, d_depth, camera, opts, d_workspace, d_out, d_coc=0, stream=0):
         """rt_dof_device: asynchronous, DEVICE buffers of the scene's GPU, no state.  d_rgb, d_out: W*H*3 f32 (disjoint); d_depth:
         W*H f32; d_coc: W*H f32 or 0; d_workspace: dof_workspace_bytes(opts) bytes, 16-byte aligned; camera: abi.Camera or None;
         opts: abi.DofOpts."""
-        _check(lib().rt_dof_device(self._h, _dp(d_rgb), _dp(d_depth), C.byref(camera) if camera is not None else None,
-                                   C.byref(opts), C.c_void_p(int(d_workspace) or None), _dp(d_out), _dp(d_coc), C.c_void_p(stream)))
+        _check(lib().rt_dof_device(self._h, _dp(d_rgb), _dp(d_depth), _ref(camera), C.byref(opts), _vp(d_workspace), _dp(d_out), _dp(d_coc),
+                                   C.c_void_p(stream)))
 
     def render_dof(self, camera, opts, dopts):
         """rt_render_dof: rt_render, the depth of the same passes and rt_dof in one call; dopts: abi.DofOpts (its sizes are
@@ -975,33 +943,21 @@ class HipScene:
             (H, W), dst = dst, {}
         else:
             raise ValueError("upscale needs dst: the destination guides, or the destination size (H, W)")
-        ins, keep = abi.UpscaleInputs(), []
-        h, w = _set_f32_inputs(ins, color, [("src_" + k, src.get(k), 3 if k != "depth" else 1) for k in abi.UPSCALE_GUIDES], keep)
-        for k in abi.UPSCALE_GUIDES:
-            a = dst.get(k)
-            if a is None:
-                continue
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            shape = (H, W, 3) if k != "depth" else (H, W)
-            if a.shape != shape:
-                raise ValueError(f"dst {k} must be {shape}, got {a.shape}")
-            keep.append(a)
-            setattr(ins, "dst_" + k, _p(a, C.c_float))
+        color, h, w = _image(color, "color")
+        ins = abi.UpscaleInputs()
+        _host_inputs(abi.UPSCALE_SHAPES, ins, {"color": color, **{"src_" + k: src.get(k) for k in abi.UPSCALE_GUIDES}}, h, w)
+        _host_inputs(abi.UPSCALE_SHAPES, ins, {"dst_" + k: dst.get(k) for k in abi.UPSCALE_GUIDES}, H, W)
         o = upscale_opts(w, h, W, H, **opts)
         out = np.zeros((H, W, 3), dtype=np.float32)
         smap = np.zeros((H, W), dtype=np.uint8) if stage else None
-        _check(lib().rt_upscale(self._h, C.byref(ins), C.byref(o), _p(out, C.c_float), _p(smap, C.c_uint8) if stage else None))
+        _check(lib().rt_upscale(self._h, C.byref(ins), C.byref(o), _p(out, C.c_float), _p(smap, C.c_uint8)))
         return (out, smap) if stage else out
 
     def upscale_device(self, d_ptrs, d_out, opts, d_stage=0, stream=0):
         """rt_upscale_device: asynchronous, DEVICE buffers of the scene's GPU, no state, no workspace.  d_ptrs = {input: device
         pointer} over abi.UPSCALE_INPUTS ("color" required; each guide at both sizes or not at all); d_out: W*H*3 f32; d_stage:
         W*H bytes or 0; opts: abi.UpscaleOpts with both frame sizes set."""
-        ins = abi.UpscaleInputs()
-        for name, ptr in d_ptrs.items():
-            if name not in abi.UPSCALE_INPUTS:
-                raise ValueError(f"unknown upscale input {name!r}")
-            setattr(ins, name, _dp(ptr))
+        ins = _device_buffers(abi.UPSCALE_SHAPES, abi.UpscaleInputs(), d_ptrs)
         _check(lib().rt_upscale_device(self._h, C.byref(ins), C.byref(opts), _dp(d_out), _dp(d_stage, C.c_uint8), C.c_void_p(stream)))
 
     def render_upscaled(self, camera, opts, src_width, src_height, dopts=None, uopts=None):
@@ -1013,12 +969,8 @@ class HipScene:
             dopts = denoise_opts(w, h)
         if uopts is None:
             uopts = upscale_opts(w, h, W, H)
-        out = np.zeros((H, W, 3), dtype=np.float32)
-        out_src = np.zeros((h, w, 3), dtype=np.float32)
-        rays = C.c_uint64()
-        _check(lib().rt_render_upscaled(self._h, C.byref(camera), C.byref(opts), C.c_uint32(w), C.c_uint32(h), C.byref(dopts),
-                                        C.byref(uopts), _p(out, C.c_float), _p(out_src, C.c_float), C.byref(rays)))
-        return out, out_src, rays.value
+        return self._frames_and_rays("rt_render_upscaled", (C.byref(camera), C.byref(opts), C.c_uint32(w), C.c_uint32(h), C.byref(dopts),
+                                                            C.byref(uopts)), (H, W, 3), (h, w, 3))
 
     # ---- AccelerationStructure::check_hit / check_hit_index for batches ----
     def check_hit(self, origins, directions):
@@ -1052,8 +1004,8 @@ class HipScene:
                 raise ValueError(f"streams must be one per ray: {st.shape} for {n} rays")
         o = radiance_opts(render_method=method, samples_per_ray=samples, seed=seed, sample_begin=sample_begin, max_depth=max_depth,
                           rr_threshold=rr_threshold)
-        _check(lib().rt_radiance(self._h, rays.ctypes.data_as(C.POINTER(abi.RayDesc)), _p(st, C.c_uint64) if st is not None else None,
-                                 C.c_uint64(n), C.byref(o), _p(out, C.c_float)))
+        _check(lib().rt_radiance(self._h, rays.ctypes.data_as(C.POINTER(abi.RayDesc)), _p(st, C.c_uint64), C.c_uint64(n), C.byref(o),
+                                 _p(out, C.c_float)))
         return out
 
     def radiance_device(self, d_rays, d_streams, n_rays, d_out, *, method=abi.RT_METHOD_MIS, samples=1, seed=0, sample_begin=0,
@@ -1063,14 +1015,12 @@ class HipScene:
         on several streams at once."""
         o = radiance_opts(render_method=method, samples_per_ray=samples, seed=seed, sample_begin=sample_begin, max_depth=max_depth,
                           rr_threshold=rr_threshold)
-        _check(lib().rt_radiance_device(self._h, C.c_void_p(d_rays), C.c_void_p(d_streams or None), C.c_uint64(n_rays), C.byref(o),
+        _check(lib().rt_radiance_device(self._h, C.c_void_p(d_rays), _vp(d_streams), C.c_uint64(n_rays), C.byref(o),
                                         _dp(d_out, C.c_float), C.c_void_p(stream)))
 
 
 def output_floats(opts):
-    n = C.c_uint64()
-    _check(lib().rt_render_output_floats(C.byref(opts), C.byref(n)))
-    return n.value
+    return _u64("rt_render_output_floats", opts)
 
 
 def plan_work_items(opts, split, share, resident_waves=0):
@@ -1165,128 +1115,59 @@ def save_image(filename, image, gamma=2.2):
     _check(lib().rt_output_save(filename.encode(), _p(a, C.c_float), C.c_uint32(w), C.c_uint32(h), C.c_float(gamma)))
 
 
+def _set_opts(o, what, kw, allowed, enums=None, nested=None):
+    """the keywords of every *_opts builder set on the struct `o`: a key must be in `allowed`, or in `nested` ({key: the struct
+    inside `o` that holds it}).  With `enums` ({key: {name: value}}) a string stands for the value of that name, in either case."""
+    for k, v in kw.items():
+        _known(k, (*allowed, *(nested or ())), f"{what} option")
+        if enums and isinstance(v, str):
+            names = enums.get(k, {})
+            _known(v.lower(), names, k)
+            v = names[v.lower()]
+        setattr((nested or {}).get(k, o), k, v)
+    return o
+
+
+def _opts(struct, what, kw, allowed, enums=None, **size):
+    """rt_<what>_opts_default's `struct` with the frame-size fields `size`, then the keywords `kw` (see _set_opts), set"""
+    o = struct()
+    _check(getattr(lib(), f"rt_{what}_opts_default")(C.byref(o)))
+    for k, v in size.items():
+        setattr(o, k, int(v))
+    return _set_opts(o, what, kw, allowed, enums)
+
+
+_DENOISE_OPTIONS = ("iterations", "sigma_luminance", "sigma_normal", "sigma_depth")
+
+
 def denoise_opts(width, height, **kw):
     """rt_denoise_opts_default with the frame size and any of iterations / sigma_luminance / sigma_normal / sigma_depth set."""
-    o = abi.DenoiseOpts()
-    _check(lib().rt_denoise_opts_default(C.byref(o)))
-    o.width, o.height = int(width), int(height)
-    for k, v in kw.items():
-        if k not in ("iterations", "sigma_luminance", "sigma_normal", "sigma_depth"):
-            raise ValueError(f"unknown denoise option {k!r}")
-        setattr(o, k, v)
-    return o
+    return _opts(abi.DenoiseOpts, "denoise", kw, _DENOISE_OPTIONS, width=width, height=height)
 
 
 def matte_opts(**kw):
     """rt_matte_opts_default with id_kind (abi.RT_MATTE_ID_* or its name, "primitive" / "material") and / or layers set."""
-    o = abi.MatteOpts()
-    _check(lib().rt_matte_opts_default(C.byref(o)))
-    for k, v in kw.items():
-        if k not in ("id_kind", "layers"):
-            raise ValueError(f"unknown matte option {k!r}")
-        if isinstance(v, str):
-            if v.lower() not in abi.MATTE_ID_KINDS:
-                raise ValueError(f"unknown {k} {v!r}: one of {sorted(abi.MATTE_ID_KINDS)}")
-            v = abi.MATTE_ID_KINDS[v.lower()]
-        setattr(o, k, v)
-    return o
+    return _opts(abi.MatteOpts, "matte", kw, ("id_kind", "layers"), {"id_kind": abi.MATTE_ID_KINDS})
 
 
 def ao_opts(**kw):
     """rt_ao_opts_default with rays_per_pass and / or radius set."""
-    o = abi.AoOpts()
-    _check(lib().rt_ao_opts_default(C.byref(o)))
-    for k, v in kw.items():
-        if k not in ("rays_per_pass", "radius"):
-            raise ValueError(f"unknown AO option {k!r}")
-        setattr(o, k, v)
-    return o
+    return _opts(abi.AoOpts, "ao", kw, ("rays_per_pass", "radius"))
 
 
 def radiance_opts(**kw):
     """rt_radiance_opts_default with any of seed, sample_begin, samples_per_ray, render_method, max_depth, rr_threshold set."""
-    o = abi.RadianceOpts()
-    _check(lib().rt_radiance_opts_default(C.byref(o)))
-    for k, v in kw.items():
-        if k not in abi.RADIANCE_OPTIONS:
-            raise ValueError(f"unknown radiance option {k!r}")
-        setattr(o, k, v)
-    return o
+    return _opts(abi.RadianceOpts, "radiance", kw, abi.RADIANCE_OPTIONS)
 
 
 def noise_opts(**kw):
     """rt_noise_opts_default with luminance_floor and / or threshold set."""
-    o = abi.NoiseOpts()
-    _check(lib().rt_noise_opts_default(C.byref(o)))
-    for k, v in kw.items():
-        if k not in ("luminance_floor", "threshold"):
-            raise ValueError(f"unknown noise option {k!r}")
-        setattr(o, k, v)
-    return o
+    return _opts(abi.NoiseOpts, "noise", kw, ("luminance_floor", "threshold"))
 
 
 def robust_opts(**kw):
     """rt_robust_opts_default with mode (abi.RT_ROBUST_* or its name, "trim" / "median" / "gini"), trim and / or gini_gain set."""
-    o = abi.RobustOpts()
-    _check(lib().rt_robust_opts_default(C.byref(o)))
-    for k, v in kw.items():
-        if k not in ("mode", "trim", "gini_gain"):
-            raise ValueError(f"unknown robust option {k!r}")
-        if isinstance(v, str):
-            if v.lower() not in abi.ROBUST_MODES:
-                raise ValueError(f"unknown {k} {v!r}: one of {sorted(abi.ROBUST_MODES)}")
-            v = abi.ROBUST_MODES[v.lower()]
-        setattr(o, k, v)
-    return o
-
-
-def _robust_outputs(w, h, channels):
-    """(arrays by channel, rt_robust_buffers pointing at them) of a w x h frame"""
-    shapes = {"out": ((h, w, 3), np.float32), "mean": ((h, w, 3), np.float32), "gini": ((h, w), np.float32),
-              "trimmed": ((h, w), np.uint8), "dropped": ((h, w), np.uint8)}
-    out, bufs = {}, abi.RobustBuffers()
-    for name in ("out", *channels):
-        if name not in abi.ROBUST_CHANNELS:
-            raise ValueError(f"unknown robust channel {name!r}")
-        if name not in out:
-            shape, dtype = shapes[name]
-            out[name] = np.zeros(shape, dtype=dtype)
-            setattr(bufs, name, _p(out[name], C.c_float if dtype is np.float32 else C.c_uint8))
-    return out, bufs
-
-
-def _robust_albedo(albedo, w, h):
-    if albedo is None:
-        return None
-    albedo = np.ascontiguousarray(albedo, dtype=np.float32)
-    if albedo.shape != (h, w, 3):
-        raise ValueError(f"albedo must be {(h, w, 3)}, got {albedo.shape}")
-    return albedo
-
-
-def _robust_device_buffers(d_ptrs):
-    bufs = abi.RobustBuffers()
-    for name, ptr in d_ptrs.items():
-        if name not in abi.ROBUST_CHANNELS:
-            raise ValueError(f"unknown robust channel {name!r}")
-        setattr(bufs, name, _dp(ptr, C.c_uint8 if name in ("trimmed", "dropped") else C.c_float))
-    return bufs
-
-
-def _noise_outputs(w, h, channels):
-    """(arrays by channel, rt_noise_buffers pointing at them, the summary struct or None) of a w x h frame"""
-    shapes = {"mean": (h, w, 3), "variance": (h, w), "lum_mean": (h, w), "tile_error": ((h + 7) // 8, (w + 7) // 8)}
-    out, bufs, summary = {}, abi.NoiseBuffers(), None
-    for name in ("mean", *channels):
-        if name not in abi.NOISE_CHANNELS:
-            raise ValueError(f"unknown noise channel {name!r}")
-        if name == "summary":
-            summary = abi.NoiseSummary()
-            bufs.summary = C.pointer(summary)
-        elif name not in out:
-            out[name] = np.zeros(shapes[name], dtype=np.float32)
-            setattr(bufs, name, _p(out[name], C.c_float))
-    return out, bufs, summary
+    return _opts(abi.RobustOpts, "robust", kw, ("mode", "trim", "gini_gain"), {"mode": abi.ROBUST_MODES})
 
 
 def _summary_dict(s):
@@ -1295,102 +1176,56 @@ def _summary_dict(s):
 
 def denoise_workspace_bytes(opts):
     """rt_denoise_workspace_bytes: the workspace rt_denoise_device needs for opts' frame size."""
-    n = C.c_uint64()
-    _check(lib().rt_denoise_workspace_bytes(C.byref(opts), C.byref(n)))
-    return n.value
+    return _u64("rt_denoise_workspace_bytes", opts)
 
 
 def temporal_opts(width, height, **kw):
     """rt_temporal_opts_default with the frame size and any of the denoise_opts keywords (iterations, sigma_*) or
     abi.TEMPORAL_OPTIONS set."""
-    o = abi.TemporalOpts()
-    _check(lib().rt_temporal_opts_default(C.byref(o)))
+    o = _opts(abi.TemporalOpts, "temporal", {}, ())
     o.denoise.width, o.denoise.height = int(width), int(height)
-    for k, v in kw.items():
-        if k in ("iterations", "sigma_luminance", "sigma_normal", "sigma_depth"):
-            setattr(o.denoise, k, v)
-        elif k in abi.TEMPORAL_OPTIONS:
-            setattr(o, k, v)
-        else:
-            raise ValueError(f"unknown temporal option {k!r}")
-    return o
+    return _set_opts(o, "temporal", kw, abi.TEMPORAL_OPTIONS, nested=dict.fromkeys(_DENOISE_OPTIONS, o.denoise))
 
 
 def temporal_history_bytes(opts):
     """rt_temporal_history_bytes: the size of one history buffer for opts' frame size."""
-    n = C.c_uint64()
-    _check(lib().rt_temporal_history_bytes(C.byref(opts), C.byref(n)))
-    return n.value
+    return _u64("rt_temporal_history_bytes", opts)
 
 
 def temporal_workspace_bytes(opts):
     """rt_temporal_workspace_bytes: the workspace rt_denoise_temporal_device needs for opts' frame size."""
-    n = C.c_uint64()
-    _check(lib().rt_temporal_workspace_bytes(C.byref(opts), C.byref(n)))
-    return n.value
+    return _u64("rt_temporal_workspace_bytes", opts)
 
 
 def display_opts(width, height, **kw):
     """rt_display_opts_default with the frame size and any of abi.DISPLAY_OPTIONS set; the enum options also take their names
     (tonemap="hable", pixel_format="rgb8", ...)."""
-    o = abi.DisplayOpts()
-    _check(lib().rt_display_opts_default(C.byref(o)))
-    o.width, o.height = int(width), int(height)
-    for k, v in kw.items():
-        if k not in abi.DISPLAY_OPTIONS:
-            raise ValueError(f"unknown display option {k!r}")
-        if isinstance(v, str):
-            names = abi.DISPLAY_ENUMS.get(k, {})
-            if v.lower() not in names:
-                raise ValueError(f"unknown {k} {v!r}: one of {sorted(names)}")
-            v = names[v.lower()]
-        setattr(o, k, v)
-    return o
+    return _opts(abi.DisplayOpts, "display", kw, abi.DISPLAY_OPTIONS, abi.DISPLAY_ENUMS, width=width, height=height)
 
 
 def display_workspace_bytes(opts):
     """rt_display_workspace_bytes: the workspace rt_display_device needs for opts' frame size."""
-    n = C.c_uint64()
-    _check(lib().rt_display_workspace_bytes(C.byref(opts), C.byref(n)))
-    return n.value
+    return _u64("rt_display_workspace_bytes", opts)
 
 
 def display_output_bytes(opts):
     """rt_display_output_bytes: W*H*4 (RGBA8, BGRA8) or W*H*3 (RGB8)."""
-    n = C.c_uint64()
-    _check(lib().rt_display_output_bytes(C.byref(opts), C.byref(n)))
-    return n.value
+    return _u64("rt_display_output_bytes", opts)
 
 
 def bloom_opts(width, height, **kw):
     """rt_bloom_opts_default with the frame size and any of abi.BLOOM_OPTIONS set."""
-    o = abi.BloomOpts()
-    _check(lib().rt_bloom_opts_default(C.byref(o)))
-    o.width, o.height = int(width), int(height)
-    for k, v in kw.items():
-        if k not in abi.BLOOM_OPTIONS:
-            raise ValueError(f"unknown bloom option {k!r}")
-        setattr(o, k, v)
-    return o
+    return _opts(abi.BloomOpts, "bloom", kw, abi.BLOOM_OPTIONS, width=width, height=height)
 
 
 def bloom_workspace_bytes(opts):
     """rt_bloom_workspace_bytes: the workspace rt_bloom_device needs for opts' frame size and levels."""
-    n = C.c_uint64()
-    _check(lib().rt_bloom_workspace_bytes(C.byref(opts), C.byref(n)))
-    return n.value
+    return _u64("rt_bloom_workspace_bytes", opts)
 
 
 def dof_opts(width, height, **kw):
     """rt_dof_opts_default with the frame size and any of abi.DOF_OPTIONS set."""
-    o = abi.DofOpts()
-    _check(lib().rt_dof_opts_default(C.byref(o)))
-    o.width, o.height = int(width), int(height)
-    for k, v in kw.items():
-        if k not in abi.DOF_OPTIONS:
-            raise ValueError(f"unknown dof option {k!r}")
-        setattr(o, k, v)
-    return o
+    return _opts(abi.DofOpts, "dof", kw, abi.DOF_OPTIONS, width=width, height=height)
 
 
 def dof_opts_from_camera(camera, aperture, focus_dist, width, height, **kw):
@@ -1399,30 +1234,18 @@ def dof_opts_from_camera(camera, aperture, focus_dist, width, height, **kw):
     o = abi.DofOpts()
     _check(lib().rt_dof_opts_from_camera(C.byref(o), C.byref(camera), C.c_float(aperture), C.c_float(focus_dist),
                                          C.c_uint32(int(width)), C.c_uint32(int(height))))
-    for k, v in kw.items():
-        if k not in abi.DOF_OPTIONS:
-            raise ValueError(f"unknown dof option {k!r}")
-        setattr(o, k, v)
-    return o
+    return _set_opts(o, "dof", kw, abi.DOF_OPTIONS)
 
 
 def dof_workspace_bytes(opts):
     """rt_dof_workspace_bytes: the workspace rt_dof_device needs for opts' frame size."""
-    n = C.c_uint64()
-    _check(lib().rt_dof_workspace_bytes(C.byref(opts), C.byref(n)))
-    return n.value
+    return _u64("rt_dof_workspace_bytes", opts)
 
 
 def upscale_opts(src_width, src_height, dst_width, dst_height, **kw):
     """rt_upscale_opts_default with the two frame sizes and any of abi.UPSCALE_OPTIONS set."""
-    o = abi.UpscaleOpts()
-    _check(lib().rt_upscale_opts_default(C.byref(o)))
-    o.src_width, o.src_height, o.dst_width, o.dst_height = int(src_width), int(src_height), int(dst_width), int(dst_height)
-    for k, v in kw.items():
-        if k not in abi.UPSCALE_OPTIONS:
-            raise ValueError(f"unknown upscale option {k!r}")
-        setattr(o, k, v)
-    return o
+    return _opts(abi.UpscaleOpts, "upscale", kw, abi.UPSCALE_OPTIONS, src_width=src_width, src_height=src_height, dst_width=dst_width,
+                 dst_height=dst_height)
 
 
 def save_aov(prefix, aovs):
