@@ -30,8 +30,9 @@ struct DevSelectParams {
 };
 
 // One masked batch of rt_render_adaptive folded into the per-pixel state: one wave a listed tile, one lane a pixel.  The chunk sums
-// are rt_render_tiles' ([chunk][64 * slot + place][3]); (mean_b, lbar_b, var_b) are noise_chunk_kernel's (rt_noise.hip), operation for
-// operation; M += mean_b, L += lbar_b, V += var_b, nb += 1, and the planes are the state divided out by the pixel's own nb.
+// are rt_render_tiles' ([chunk][64 * slot + place][3]); (lbar_b, var_b) are chunk_stats' and the step M += mean_b, L += lbar_b,
+// V += var_b with the planes divided out is chunk_state_step's (rt_chunk_stats.h: the routines noise_chunk_kernel calls), here with
+// the pixel's own nb, which it counts up.
 struct DevFoldParams {
 	const uint32_t *tiles;
 	uint32_t n_tiles;      // list length

@@ -24,6 +24,7 @@
 
 #include "rt_path_lane.h"
 #include "rt_adaptive.h"
+#include "rt_chunk_stats.h"
 
 namespace rt {
 
@@ -156,12 +157,12 @@ __global__ __launch_bounds__(256, kTilesWaves) void tiles_kernel(const TilesArgs
 					const uint32_t item = id >> 6, place = id & 63u;
 					const uint32_t slot = item / per_tile, c0 = (item - slot * per_tile) * item_chunks;
 					const uint32_t tile = ka->P.tiles[slot]; // (slot < n_tiles: id < n_lanes)
-					const uint32_t tiles_x = ka->P.tiles_x, width = ka->P.width;
-					const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-					const uint32_t x = 8u * tx + (place & 7u), y = 8u * ty + (place >> 3);
+					const uint32_t width = ka->P.width;
+					uint32_t x, y;
+					const bool inside = grid8_pixel(tile, place, ka->P.tiles_x, width, ka->P.height, x, y);
 					if (tile >= ka->P.tile_count) {
 						// not a tile of this frame: skipped whole (ph stays CLAIM: the lane takes another slot next iteration)
-					} else if (x >= width || y >= ka->P.height) { // padding of an edge tile
+					} else if (!inside) { // padding of an edge tile
 						float *const sums = ka->P.chunk_sums;
 						if (split > 1u && sums != nullptr) {
 							float *const o = sums + 3u * ((size_t)c0 * 64u * ka->P.n_tiles + (64u * slot + place));
@@ -231,9 +232,8 @@ __global__ __launch_bounds__(256) void tiles_combine_kernel(const DevTilesParams
 	const uint32_t tile = P.tiles[i >> 6], place = i & 63u;
 	if (tile >= P.tile_count)
 		return;
-	const uint32_t ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
-	const uint32_t x = 8u * tx + (place & 7u), y = 8u * ty + (place >> 3);
-	if (x >= P.width || y >= P.height)
+	uint32_t x, y;
+	if (!grid8_pixel(tile, place, P.tiles_x, P.width, P.height, x, y))
 		return;
 	const size_t stride = 3u * (size_t)64u * P.n_tiles;
 	const float *m = P.chunk_sums + 3u * (size_t)i;
@@ -301,9 +301,7 @@ hipError_t launch_tiles(int method, bool prune, hipStream_t stream, const DevSce
 	return hipGetLastError();
 }
 
-// the denoiser's lum, left to right (rt_post_common.h lum; restated: this file does not include the post-processing header)
-__device__ __forceinline__ float fold_lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-
+// (mean_b, lbar_b, var_b) of a listed pixel's chunk sums into its state, by the routines of the whole-frame batch (rt_chunk_stats.h)
 __global__ __launch_bounds__(256) void adaptive_fold_kernel(const DevFoldParams P)
 {
 	const uint32_t lane = threadIdx.x & 63u, slot = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -312,48 +310,15 @@ __global__ __launch_bounds__(256) void adaptive_fold_kernel(const DevFoldParams 
 	const uint32_t tile = P.tiles[slot];
 	if (tile >= P.tile_count)
 		return;
-	const uint32_t ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
-	const uint32_t x = 8u * tx + (lane & 7u), y = 8u * ty + (lane >> 3);
-	if (x >= P.width || y >= P.height)
+	uint32_t x, y;
+	if (!grid8_pixel(tile, lane, P.tiles_x, P.width, P.height, x, y))
 		return;
-	const size_t p = (size_t)y * P.width + x, p3 = 3u * p;
-	float d0 = 1.0f, d1 = 1.0f, d2 = 1.0f;
-	if (P.albedo) {
-		d0 = fmaxf(P.albedo[p3], 1e-3f);
-		d1 = fmaxf(P.albedo[p3 + 1u], 1e-3f);
-		d2 = fmaxf(P.albedo[p3 + 2u], 1e-3f);
-	}
-	const float n = (float)P.chunk_passes, s = (float)P.split;
-	const float *const first = P.sums + 3u * ((size_t)64u * slot + lane);
-	const size_t stride = 3u * (size_t)64u * P.n_tiles;
-	float lsum = 0.0f;
-	for (uint32_t c = 0; c < P.split; ++c) { // (the sums are read twice: no array, nothing indexed by the loop)
-		const float *m = first + c * stride;
-		lsum = lsum + fold_lum(m[0] / n / d0, m[1] / n / d1, m[2] / n / d2);
-	}
-	const float lbar = lsum / s;
-	float sq = 0.0f;
-	for (uint32_t c = 0; c < P.split; ++c) {
-		const float *m = first + c * stride;
-		const float dl = fold_lum(m[0] / n / d0, m[1] / n / d1, m[2] / n / d2) - lbar;
-		sq = sq + dl * dl;
-	}
-	const float var = sq / (float)(P.split * (P.split - 1u));
-	const float m0 = P.state_m[p3] + P.mean_in[p3], m1 = P.state_m[p3 + 1u] + P.mean_in[p3 + 1u], m2 = P.state_m[p3 + 2u] + P.mean_in[p3 + 2u];
-	const float l = P.state_l[p] + lbar, v = P.state_v[p] + var;
-	const uint32_t count = P.nb[p] + 1u;
-	P.state_m[p3] = m0;
-	P.state_m[p3 + 1u] = m1;
-	P.state_m[p3 + 2u] = m2;
-	P.state_l[p] = l;
-	P.state_v[p] = v;
+	const size_t p = (size_t)y * P.width + x;
+	const Demod d = demod_divisors(P.albedo, 3u * p);
+	const ChunkStats b = chunk_stats(P.sums + 3u * ((size_t)64u * slot + lane), 3u * (size_t)64u * P.n_tiles, P.split, (float)P.chunk_passes, d);
+	const uint32_t count = P.nb[p] + 1u; // the pixel's own batch count
+	chunk_state_step<false>(p, P.mean_in, b, P.state_m, P.state_l, P.state_v, false, (float)count, P.out_mean, P.out_lum, P.out_var);
 	P.nb[p] = count;
-	const float nb = (float)count;
-	P.out_mean[p3] = m0 / nb;
-	P.out_mean[p3 + 1u] = m1 / nb;
-	P.out_mean[p3 + 2u] = m2 / nb;
-	P.out_lum[p] = l / nb;
-	P.out_var[p] = v / (nb * nb);
 }
 
 __global__ __launch_bounds__(256) void adaptive_fill_kernel(uint32_t *p, uint64_t n, uint32_t value)

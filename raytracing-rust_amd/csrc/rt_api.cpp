@@ -865,10 +865,11 @@ int shard_geometry(const rt_render_opts *o, ShardGeometry &g)
 		return fail(RT_ERR_UNSUPPORTED, "image larger than 2^31 pixels");
 	if (o->shard_count == 0 || o->shard_index >= o->shard_count)
 		return fail(RT_ERR_INVALID_ARGUMENT, "shard_index must be < shard_count and shard_count >= 1");
-	g.tile_w = o->tile_width ? o->tile_width : 8;
-	g.tile_h = o->tile_height ? o->tile_height : 8;
-	g.tiles_x = (uint32_t)((o->width + g.tile_w - 1) / g.tile_w);
-	g.tiles_y = (uint32_t)((o->height + g.tile_h - 1) / g.tile_h);
+	const FrameTiling t = frame_tiling(o);
+	g.tile_w = t.tile_w;
+	g.tile_h = t.tile_h;
+	g.tiles_x = t.tiles_x;
+	g.tiles_y = t.tiles_y;
 	const uint64_t n_tiles = (uint64_t)g.tiles_x * g.tiles_y;
 	g.n_tiles_owned = n_tiles > o->shard_index ? (n_tiles - o->shard_index + o->shard_count - 1) / o->shard_count : 0;
 	g.n_work = g.n_tiles_owned * g.tile_w * g.tile_h;
@@ -1509,11 +1510,7 @@ int rt_render_device(rt_scene *s, const rt_camera *camera, const rt_render_opts 
 		HIP_TRY(launch_reset(stream, s->d_work_counter, reinterpret_cast<unsigned long long *>(d_rays_shot), d_out_rgb, zero_floats));
 	}
 	fill_launch_info(plan, o, s->n_cus, &s->last_launch);
-	DevCamera cam;
-	std::memcpy(cam.origin, camera->origin, 12);
-	std::memcpy(cam.lower_left, camera->lower_left, 12);
-	std::memcpy(cam.horizontal, camera->horizontal, 12);
-	std::memcpy(cam.vertical, camera->vertical, 12);
+	const DevCamera cam = dev_camera(camera);
 	// FeatPair: the origin-only terms of the primary walks (rt_types.h DevPairPrimary).  The camera belongs to the render, not to
 	// the scene, so they are formed here, per launch: some forty operations
 	DevPairPrimary primary{};

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -182,6 +183,40 @@ inline uint32_t path_lane_groups(const rt_scene *s, size_t lds_bytes, uint32_t w
 	if (s->radiance_groups != 0u)
 		groups = std::min<uint64_t>(groups, s->radiance_groups);
 	return (uint32_t)std::max<uint64_t>(groups, 1);
+}
+
+// ---- the geometry of a frame and the camera, as every launch takes them ----
+
+// the 8 x 8 tile grid of a w x h frame (rt_noise_tiles' grid: AOV passes, tile errors, tile lists): tiles across, and how many
+struct TileGrid { uint32_t tiles_x; uint64_t count; };
+inline TileGrid tile_grid(uint64_t w, uint64_t h)
+{
+	const uint64_t across = (w + 7) / 8, down = (h + 7) / 8;
+	return TileGrid{(uint32_t)across, across * down};
+}
+
+// the tiling of a whole-frame render under `o` (tile_width / tile_height 0: 8): what the render kernel hands out as work items, and
+// what the readers of its chunk sums find pixels by.  n_work counts the padding of edge tiles.
+struct FrameTiling { uint32_t tile_w, tile_h, tiles_x, tiles_y; uint64_t n_work; };
+inline FrameTiling frame_tiling(const rt_render_opts *o)
+{
+	FrameTiling t;
+	t.tile_w = o->tile_width ? o->tile_width : 8;
+	t.tile_h = o->tile_height ? o->tile_height : 8;
+	t.tiles_x = (uint32_t)((o->width + t.tile_w - 1) / t.tile_w);
+	t.tiles_y = (uint32_t)((o->height + t.tile_h - 1) / t.tile_h);
+	t.n_work = (uint64_t)t.tiles_x * t.tiles_y * t.tile_w * t.tile_h;
+	return t;
+}
+
+inline rt::DevCamera dev_camera(const rt_camera *camera)
+{
+	rt::DevCamera cam;
+	std::memcpy(cam.origin, camera->origin, 12);
+	std::memcpy(cam.lower_left, camera->lower_left, 12);
+	std::memcpy(cam.horizontal, camera->horizontal, 12);
+	std::memcpy(cam.vertical, camera->vertical, 12);
+	return cam;
 }
 
 template <class T> static int upload(rt_scene *s, const T *src, size_t count, const T **dst)

@@ -66,14 +66,11 @@ static DevAovParams aov_params(const rt_scene *s, const rt_camera *camera, const
 {
 	DevAovParams P;
 	std::memset(&P, 0, sizeof P);
-	std::memcpy(P.cam.origin, camera->origin, 12);
-	std::memcpy(P.cam.lower_left, camera->lower_left, 12);
-	std::memcpy(P.cam.horizontal, camera->horizontal, 12);
-	std::memcpy(P.cam.vertical, camera->vertical, 12);
+	P.cam = dev_camera(camera);
 	P.width = (uint32_t)o->width;
 	P.height = (uint32_t)o->height;
-	P.tiles_x = (P.width + 7u) / 8u;
-	P.n_tiles = P.tiles_x * ((P.height + 7u) / 8u);
+	P.tiles_x = tile_grid(o->width, o->height).tiles_x;
+	P.n_tiles = (uint32_t)tile_grid(o->width, o->height).count;
 	P.spp = (uint32_t)o->samples_per_pixel;
 	P.mask = mask;
 	P.seed_lo = (uint32_t)o->seed;
@@ -806,7 +803,13 @@ static int noise_render_check(const rt_scene *s, const rt_render_opts *o, const 
 	return frame_pixels("noise: ", o->width, o->height, 2, px);
 }
 
-static uint64_t noise_tile_count(uint64_t w, uint64_t h) { return ((w + 7) / 8) * ((h + 7) / 8); }
+static uint64_t noise_tile_count(uint64_t w, uint64_t h) { return tile_grid(w, h).count; }
+// the render's whole-frame tiling into the parameters of a kernel that reads its chunk sums in work-item order
+template <class P> static void fill_frame_tiling(P &p, const rt_render_opts *o)
+{
+	const FrameTiling t = frame_tiling(o);
+	p.tile_w = t.tile_w, p.tile_h = t.tile_h, p.tiles_x = t.tiles_x, p.n_work = (uint32_t)t.n_work;
+}
 // the scene's scratch for n pixels: the summary of the blocking calls, then the state planes M, L, V; what a blocking call stages
 // comes behind (described after these, so that the state is where the _device call inside it finds it)
 struct NoiseState {
@@ -837,8 +840,8 @@ static int enqueue_noise_tiles(hipStream_t stream, const float *d_lum, const flo
 	std::memset(&T, 0, sizeof T);
 	T.width = (uint32_t)w;
 	T.height = (uint32_t)h;
-	T.tiles_x = (uint32_t)((w + 7) / 8);
-	T.n_tiles = (uint32_t)noise_tile_count(w, h);
+	T.tiles_x = tile_grid(w, h).tiles_x;
+	T.n_tiles = (uint32_t)tile_grid(w, h).count;
 	T.luminance_floor = n->luminance_floor;
 	T.threshold = n->threshold;
 	T.lum_mean = d_lum;
@@ -874,10 +877,7 @@ static int enqueue_noise_batch(rt_scene *s, const rt_camera *camera, const rt_re
 	std::memset(&C, 0, sizeof C);
 	C.width = (uint32_t)o->width;
 	C.height = (uint32_t)o->height;
-	C.tile_w = o->tile_width ? o->tile_width : 8u; // (shard_geometry, rt_api.cpp)
-	C.tile_h = o->tile_height ? o->tile_height : 8u;
-	C.tiles_x = (C.width + C.tile_w - 1u) / C.tile_w;
-	C.n_work = C.tiles_x * ((C.height + C.tile_h - 1u) / C.tile_h) * C.tile_w * C.tile_h;
+	fill_frame_tiling(C, o);
 	C.split = split;
 	C.chunk_passes = (uint32_t)(os.samples_per_pixel / split);
 	C.fresh = nb == 1u ? 1u : 0u;
@@ -918,6 +918,77 @@ static int noise_tiles_check(const rt_scene *s, const float *lum_mean, const flo
 	rc = check_disjoint("noise_tiles: an output buffer overlaps another buffer", buf, bytes, 2, 4);
 	return rc == RT_OK ? need_device(s) : rc;
 }
+
+// A sequence of batches over one state: what rt_render_converged and rt_render_adaptive share.  Batch nb = 1, 2, ... is a render of
+// `batch` passes from sample_begin + (nb - 1) * batch at the resolved split, its (mean, lbar, var) go into the state, and the planes,
+// the tile errors and the summary are the state's divided out.  A stage describes its own parts on L between check() and
+// allocate(), and keeps its own stop rule and result.
+namespace {
+
+struct BatchSequence {
+	rt_scene *s;
+	const rt_camera *camera;
+	const rt_render_opts *o;
+	const rt_noise_opts *n;
+	uint64_t batch;
+	const char *stage; // starts the messages
+	uint32_t split = 0;
+	uint64_t px = 0, n_tiles = 0;
+	Layout L;
+	NoiseState N{};
+	Layout::Part<float> p_render{}, p_mean{}, p_lum{}, p_variance{}, p_tiles{};
+	rt_noise_buffers d_out{};
+
+	// The checks both stages start with, in their order (the stage checks its buffers next and the device last), then the shared
+	// parts: behind the state, whose summary the sequence uses, a batch's render, then mean, lum_mean, variance and the tile errors.
+	int check(uint64_t max_passes, const float *out_mean, const void *result)
+	{
+		if (!s || !camera || !o || !n || !out_mean || !result)
+			return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+		if (batch == 0 || max_passes < batch)
+			return fail(RT_ERR_INVALID_ARGUMENT, std::string(stage) + ": batch must be >= 1 and max_passes >= batch");
+		RT_TRY(noise_render_check(s, o, n, batch, &split, &px));
+		if (max_passes / batch >= (1ull << 24)) // (nb is divided by as a float)
+			return fail(RT_ERR_UNSUPPORTED, std::string(stage) + ": 2^24 batches or more");
+		n_tiles = noise_tile_count(o->width, o->height);
+		N = noise_state(L, px);
+		p_render = L.add<float>(3 * px), p_mean = L.add<float>(3 * px), p_lum = L.add<float>(px), p_variance = L.add<float>(px);
+		p_tiles = L.add<float>(n_tiles);
+		return RT_OK;
+	}
+	int allocate()
+	{
+		HIP_TRY(hipSetDevice(s->device));
+		RT_TRY(grow_device_buffer(s->d_noise, s->d_noise_bytes, L));
+		d_out = rt_noise_buffers{L.at(p_mean), L.at(p_variance), L.at(p_lum), L.at(p_tiles), L.at(N.summary)};
+		return RT_OK;
+	}
+	rt_render_opts batch_opts(uint32_t nb) const
+	{
+		rt_render_opts ob = *o;
+		ob.samples_per_pixel = batch, ob.sample_split = split, ob.sample_begin = o->sample_begin + (uint64_t)(nb - 1u) * batch;
+		return ob;
+	}
+	// batch nb over the whole frame on s->stream: the render, the chunk kernel on the state, the tile stage
+	int whole_frame(uint32_t nb, const float *d_albedo)
+	{
+		const rt_render_opts ob = batch_opts(nb);
+		return enqueue_noise_batch(s, camera, &ob, split, n, d_albedo, L.at(p_render), L, N, true, nb, &d_out, reinterpret_cast<uint64_t *>(s->d_rays),
+		                           s->stream);
+	}
+	// what the host reads after every batch, and the batch's status: the summary, and the ray counter added to *rays_shot
+	int read_back(Staging &st, rt_noise_summary *summary, uint64_t *rays_shot)
+	{
+		unsigned long long rays = 0;
+		st.get(summary, L, N.summary);
+		st.download(&rays, s->d_rays, sizeof rays);
+		RT_TRY(st.finish(stage));
+		*rays_shot += rays;
+		return RT_OK;
+	}
+};
+
+} // namespace
 
 extern "C" {
 
@@ -1022,60 +1093,30 @@ int rt_render_converged(rt_scene *s, const rt_camera *camera, const rt_render_op
                         uint32_t min_batches, uint64_t max_passes, float *out_mean, float *out_variance, float *out_tile_error,
                         rt_noise_result *result)
 {
-	if (!s || !camera || !o || !n || !out_mean || !result)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (batch == 0 || max_passes < batch)
-		return fail(RT_ERR_INVALID_ARGUMENT, "render_converged: batch must be >= 1 and max_passes >= batch");
-	uint32_t split = 0;
-	uint64_t px = 0;
-	int rc = noise_render_check(s, o, n, batch, &split, &px);
-	if (rc != RT_OK)
-		return rc;
-	if (max_passes / batch >= (1ull << 24)) // (nb is divided by as a float)
-		return fail(RT_ERR_UNSUPPORTED, "render_converged: more than 2^24 batches");
-	const uint64_t n_tiles = noise_tile_count(o->width, o->height);
+	BatchSequence q{s, camera, o, n, batch, "render_converged"};
+	RT_TRY(q.check(max_passes, out_mean, result));
 	{
 		const void *buf[3] = {out_mean, out_variance, out_tile_error};
-		const uint64_t bytes[3] = {12 * px, 4 * px, 4 * n_tiles};
-		rc = check_disjoint("render_converged: two output buffers overlap", buf, bytes, 3, 3);
-		if (rc == RT_OK)
-			rc = need_device(s);
-		if (rc != RT_OK)
-			return rc;
+		const uint64_t bytes[3] = {12 * q.px, 4 * q.px, 4 * q.n_tiles};
+		RT_TRY(check_disjoint("render_converged: two output buffers overlap", buf, bytes, 3, 3));
+		RT_TRY(need_device(s));
 	}
-	HIP_TRY(hipSetDevice(s->device));
-	// behind the state (whose summary this sequence uses): this batch's render, then mean, lum_mean, variance and the tile errors
-	Layout L;
-	const NoiseState N = noise_state(L, px);
-	const auto p_render = L.add<float>(3 * px), p_mean = L.add<float>(3 * px), p_lum = L.add<float>(px), p_variance = L.add<float>(px),
-	           p_tiles = L.add<float>(n_tiles);
-	RT_TRY(grow_device_buffer(s->d_noise, s->d_noise_bytes, L));
-	const rt_noise_buffers d_out = {L.at(p_mean), L.at(p_variance), L.at(p_lum), L.at(p_tiles), L.at(N.summary)};
+	RT_TRY(q.allocate());
 	std::memset(result, 0, sizeof *result);
-	rt_render_opts ob = *o;
-	ob.samples_per_pixel = batch;
 	for (uint32_t nb = 1;; ++nb) {
-		ob.sample_begin = o->sample_begin + (uint64_t)(nb - 1u) * batch;
 		Staging st{s};
-		st.rc = enqueue_noise_batch(s, camera, &ob, split, n, nullptr, L.at(p_render), L, N, true, nb, &d_out,
-		                            reinterpret_cast<uint64_t *>(s->d_rays), s->stream);
-		unsigned long long rays = 0;
-		st.get(&result->summary, L, N.summary);
-		st.download(&rays, s->d_rays, sizeof rays);
-		rc = st.finish("render_converged");
-		if (rc != RT_OK)
-			return rc;
+		st.rc = q.whole_frame(nb, nullptr);
+		RT_TRY(q.read_back(st, &result->summary, &result->rays_shot));
 		result->batches = nb;
 		result->passes = (uint64_t)nb * batch;
-		result->rays_shot += rays;
 		result->converged = nb >= min_batches && result->summary.max_tile_error <= n->threshold ? 1u : 0u;
 		if (result->converged || result->passes + batch > max_passes)
 			break;
 	}
 	Staging st{s};
-	st.get(out_mean, L, p_mean);
-	st.get(out_variance, L, p_variance);
-	st.get(out_tile_error, L, p_tiles);
+	st.get(out_mean, q.L, q.p_mean);
+	st.get(out_variance, q.L, q.p_variance);
+	st.get(out_tile_error, q.L, q.p_tiles);
 	return st.finish("render_converged");
 }
 
@@ -1160,10 +1201,7 @@ int rt_render_tiles_device(rt_scene *s, const rt_camera *camera, const rt_render
 		return fail(RT_ERR_UNSUPPORTED, "traversal stacks exceed the LDS of one CU");
 	DevTilesParams P;
 	std::memset(&P, 0, sizeof P);
-	std::memcpy(P.cam.origin, camera->origin, 12);
-	std::memcpy(P.cam.lower_left, camera->lower_left, 12);
-	std::memcpy(P.cam.horizontal, camera->horizontal, 12);
-	std::memcpy(P.cam.vertical, camera->vertical, 12);
+	P.cam = dev_camera(camera);
 	P.tiles = d_tiles;
 	P.out = d_out_rgb;
 	P.chunk_sums = split > 1u ? d_chunk_sums : nullptr;
@@ -1171,8 +1209,8 @@ int rt_render_tiles_device(rt_scene *s, const rt_camera *camera, const rt_render
 	P.n_tiles = n_tiles;
 	P.width = (uint32_t)o->width;
 	P.height = (uint32_t)o->height;
-	P.tiles_x = (P.width + 7u) / 8u;
-	P.tile_count = P.tiles_x * ((P.height + 7u) / 8u);
+	P.tiles_x = tile_grid(o->width, o->height).tiles_x;
+	P.tile_count = (uint32_t)tile_grid(o->width, o->height).count;
 	P.spp = (uint32_t)o->samples_per_pixel;
 	P.split = split;
 	P.item_chunks = P.chunk_sums ? 1u : split;
@@ -1245,112 +1283,76 @@ int rt_render_adaptive(rt_scene *s, const rt_camera *camera, const rt_render_opt
                        uint64_t batch, uint32_t min_batches, uint64_t max_passes, float *out_mean, float *out_variance, float *out_tile_error,
                        uint32_t *out_passes, rt_adaptive_result *result)
 {
-	if (!s || !camera || !o || !n || !out_mean || !result)
-		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (batch == 0 || max_passes < batch)
-		return fail(RT_ERR_INVALID_ARGUMENT, "render_adaptive: batch must be >= 1 and max_passes >= batch");
-	uint32_t split = 0;
-	uint64_t px = 0;
-	int rc = noise_render_check(s, o, n, batch, &split, &px);
-	if (rc != RT_OK)
-		return rc;
-	if (max_passes / batch >= (1ull << 24)) // (nb is divided by as a float)
-		return fail(RT_ERR_UNSUPPORTED, "render_adaptive: 2^24 batches or more");
-	const uint64_t n_tiles = noise_tile_count(o->width, o->height);
+	BatchSequence q{s, camera, o, n, batch, "render_adaptive"};
+	RT_TRY(q.check(max_passes, out_mean, result));
+	const uint64_t px = q.px, n_tiles = q.n_tiles;
+	const uint32_t split = q.split;
 	if (64ull * n_tiles * split >= (1ull << 31))
 		return fail(RT_ERR_UNSUPPORTED, "render_adaptive: 64 x tiles x sample_split exceeds 2^31 lane items");
 	{
 		const void *buf[5] = {out_mean, out_variance, out_tile_error, out_passes, albedo};
 		const uint64_t bytes[5] = {12 * px, 4 * px, 4 * n_tiles, 4 * px, 12 * px};
-		rc = check_disjoint("render_adaptive: an output buffer overlaps another buffer", buf, bytes, 4, 5);
-		if (rc == RT_OK)
-			rc = need_device(s);
-		if (rc != RT_OK)
-			return rc;
+		RT_TRY(check_disjoint("render_adaptive: an output buffer overlaps another buffer", buf, bytes, 4, 5));
+		RT_TRY(need_device(s));
 	}
-	HIP_TRY(hipSetDevice(s->device));
-	// behind the state: this batch's render, the three planes and the tile errors (as rt_render_converged), then the per-pixel batch
-	// counts, the active list and its length, the albedo if given, and the chunk sums of a masked batch (sized for the whole grid)
-	Layout L;
-	const NoiseState N = noise_state(L, px);
-	const auto p_render = L.add<float>(3 * px), p_mean = L.add<float>(3 * px), p_lum = L.add<float>(px), p_variance = L.add<float>(px),
-	           p_tiles = L.add<float>(n_tiles), p_albedo = L.optional<float>(albedo, 3 * px), p_sums = L.add<float>(3ull * split * 64u * n_tiles);
+	// behind the sequence's parts: the albedo if given, the chunk sums of a masked batch (sized for the whole grid), the per-pixel
+	// batch counts, the active list and its length
+	Layout &L = q.L;
+	const auto p_albedo = L.optional<float>(albedo, 3 * px), p_sums = L.add<float>(3ull * split * 64u * n_tiles);
 	const auto p_nb = L.add<uint32_t>(px), p_list = L.add<uint32_t>(n_tiles), p_count = L.add<uint32_t>(1);
-	RT_TRY(grow_device_buffer(s->d_noise, s->d_noise_bytes, L));
-	const rt_noise_buffers d_out = {L.at(p_mean), L.at(p_variance), L.at(p_lum), L.at(p_tiles), L.at(N.summary)};
-	uint64_t *const d_rays = reinterpret_cast<uint64_t *>(s->d_rays);
+	RT_TRY(q.allocate());
 	std::memset(result, 0, sizeof *result);
-	rt_render_opts ob = *o;
-	ob.samples_per_pixel = batch;
-	ob.sample_split = split;
 	uint32_t active = (uint32_t)n_tiles; // before any batch every tile is active
 	bool masked = false;
 	for (uint32_t nb = 1;; ++nb) {
-		ob.sample_begin = o->sample_begin + (uint64_t)(nb - 1u) * batch;
 		Staging st{s};
 		if (nb == 1u)
 			st.put(L, p_albedo, albedo);
 		if (st.ok()) {
 			// whole-frame batches come first: until one batch has been masked every pixel has nb - 1 batches behind it
 			if (!masked && (nb - 1u < min_batches || active == n_tiles)) {
-				st.rc = enqueue_noise_batch(s, camera, &ob, split, n, L.at(p_albedo), L.at(p_render), L, N, true, nb, &d_out, d_rays, s->stream);
+				st.rc = q.whole_frame(nb, L.at(p_albedo));
 				if (st.rc == RT_OK)
 					st.e = launch_fill_u32(s->stream, L.at(p_nb), px, nb);
 			} else {
 				masked = true;
-				st.rc = rt_render_tiles_device(s, camera, &ob, L.at(p_list), active, L.at(p_render), L.at(p_sums), d_rays, s->stream);
+				const rt_render_opts ob = q.batch_opts(nb);
+				st.rc = rt_render_tiles_device(s, camera, &ob, L.at(p_list), active, L.at(q.p_render), L.at(p_sums), reinterpret_cast<uint64_t *>(s->d_rays),
+				                               s->stream);
 				if (st.rc == RT_OK) {
 					DevFoldParams F;
 					std::memset(&F, 0, sizeof F);
 					F.tiles = L.at(p_list);
 					F.n_tiles = active;
-					F.width = (uint32_t)o->width;
-					F.height = (uint32_t)o->height;
-					F.tiles_x = (F.width + 7u) / 8u;
-					F.tile_count = (uint32_t)n_tiles;
-					F.split = split;
-					F.chunk_passes = (uint32_t)(batch / split);
-					F.sums = L.at(p_sums);
-					F.albedo = L.at(p_albedo);
-					F.mean_in = L.at(p_render);
-					F.state_m = L.at(N.m);
-					F.state_l = L.at(N.l);
-					F.state_v = L.at(N.v);
-					F.nb = L.at(p_nb);
-					F.out_mean = L.at(p_mean);
-					F.out_lum = L.at(p_lum);
-					F.out_var = L.at(p_variance);
+					F.width = (uint32_t)o->width, F.height = (uint32_t)o->height;
+					F.tiles_x = tile_grid(o->width, o->height).tiles_x, F.tile_count = (uint32_t)n_tiles;
+					F.split = split, F.chunk_passes = (uint32_t)(batch / split);
+					F.sums = L.at(p_sums), F.albedo = L.at(p_albedo), F.mean_in = L.at(q.p_render);
+					F.state_m = L.at(q.N.m), F.state_l = L.at(q.N.l), F.state_v = L.at(q.N.v), F.nb = L.at(p_nb);
+					F.out_mean = q.d_out.mean, F.out_lum = q.d_out.lum_mean, F.out_var = q.d_out.variance;
 					st.e = launch_adaptive_fold(s->stream, F);
 				}
 				if (st.ok())
-					st.rc = enqueue_noise_tiles(s->stream, L.at(p_lum), L.at(p_variance), o->width, o->height, n, L.at(p_tiles), L.at(N.summary));
+					st.rc = enqueue_noise_tiles(s->stream, q.d_out.lum_mean, q.d_out.variance, o->width, o->height, n, q.d_out.tile_error, q.d_out.summary);
 			}
 		}
 		if (st.ok())
-			st.rc = rt_noise_select_tiles_device(s, L.at(p_tiles), (uint32_t)o->width, (uint32_t)o->height, n->threshold, L.at(p_list),
+			st.rc = rt_noise_select_tiles_device(s, q.d_out.tile_error, (uint32_t)o->width, (uint32_t)o->height, n->threshold, L.at(p_list),
 			                                     L.at(p_count), s->stream);
-		unsigned long long rays = 0;
-		st.get(&result->summary, L, N.summary);
 		st.get(&active, L, p_count);
-		st.download(&rays, s->d_rays, sizeof rays);
-		rc = st.finish("render_adaptive");
-		if (rc != RT_OK)
-			return rc;
+		RT_TRY(q.read_back(st, &result->summary, &result->rays_shot));
 		result->batches = nb;
-		result->rays_shot += rays;
 		result->converged = nb >= min_batches && active == 0u ? 1u : 0u;
 		if (result->converged || (uint64_t)(nb + 1u) * batch > max_passes)
 			break;
 	}
 	std::vector<uint32_t> counts(px);
 	Staging st{s};
-	st.get(out_mean, L, p_mean);
-	st.get(out_variance, L, p_variance);
-	st.get(out_tile_error, L, p_tiles);
+	st.get(out_mean, L, q.p_mean);
+	st.get(out_variance, L, q.p_variance);
+	st.get(out_tile_error, L, q.p_tiles);
 	st.get(counts.data(), L, p_nb);
-	rc = st.finish("render_adaptive");
-	if (rc != RT_OK)
-		return rc;
+	RT_TRY(st.finish("render_adaptive"));
 	for (uint64_t p = 0; p < px; ++p) {
 		result->pixel_passes += (uint64_t)counts[p] * batch;
 		if (out_passes)
@@ -1553,10 +1555,7 @@ int rt_render_robust_device(rt_scene *s, const rt_camera *camera, const rt_rende
 	rt_robust_buffers kernel_out = *d_out;
 	kernel_out.mean = nullptr; // combine_chunks_kernel has written it
 	DevRobustParams P = robust_params(r, o->width, o->height, split, (uint32_t)(o->samples_per_pixel / split), s->d_partial, d_albedo, &kernel_out);
-	P.tile_w = o->tile_width ? o->tile_width : 8u; // (shard_geometry, rt_api.cpp)
-	P.tile_h = o->tile_height ? o->tile_height : 8u;
-	P.tiles_x = (P.width + P.tile_w - 1u) / P.tile_w;
-	P.n_work = P.tiles_x * ((P.height + P.tile_h - 1u) / P.tile_h) * P.tile_w * P.tile_h;
+	fill_frame_tiling(P, o);
 	HIP_TRY(launch_robust_chunks(stream, P));
 	return RT_OK;
 }

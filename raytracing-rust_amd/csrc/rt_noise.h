@@ -13,7 +13,7 @@ constexpr uint32_t kNoiseSummaryBytes = 16u;      // rt_noise_summary
 
 // Stage one: the chunk sums of ONE render at sample_split = split (the scene's partial buffer, [chunk][work item][3]) -> lbar and
 // var of that render, added to the state of a batch sequence and divided out.  The work item -> pixel map is the render kernel's
-// (work_to_pixel, rt_render.hip) for RT_LAYOUT_FRAME and shard_count 1: tile k = w / (tile_w * tile_h), row-major inside the tile.
+// for RT_LAYOUT_FRAME and shard_count 1 (frame_work_pixel, rt_chunk_stats.h; the host fills it from frame_tiling, rt_api_internal.h).
 struct DevNoiseChunkParams {
 	uint32_t width, height, tile_w, tile_h, tiles_x;
 	uint32_t n_work;       // work items per chunk, edge-tile padding included

@@ -1,18 +1,19 @@
 // rt_noise.hip -- per-pixel noise estimates from the chunk sums of one render (rt_render_noise, include/rt_hip.h): the S
 // independent estimates of a pixel that a render at sample_split = S leaves in the scene's partial buffer give a variance of the
-// mean at no extra ray.  The definition is in the header; tests/noise_checker.py restates it in numpy f32, bit for bit.
+// mean at no extra ray.  The definition is in the header; tests/noise_checker.py restates it in numpy f32, bit for bit.  The
+// arithmetic of a pixel and both maps to a pixel are rt_chunk_stats.h's, shared with the other readers of chunk sums.
 //
 // Kernels (stable names for rocprofv3):
-//   noise_chunk_kernel   one lane per work item of a chunk (= per pixel, in the render's tile order): reads the S chunk sums
-//                        twice -- once for lbar, once for the squared deviations; no array is kept, so nothing is indexed
-//                        dynamically -- adds (mean, lbar, var) to the batch state and writes the state divided out.  A wave reads
-//                        64 consecutive work items of one chunk: 768 contiguous bytes per load instruction triple.
+//   noise_chunk_kernel   one lane per work item of a chunk (= per pixel, in the render's tile order): (lbar, var) of its S chunk
+//                        sums (chunk_stats), then (mean, lbar, var) added to the batch state and the state divided out
+//                        (chunk_state_step).  A wave reads 64 consecutive work items of one chunk: 768 contiguous bytes per load
+//                        instruction triple.
 //   noise_tile_kernel    one wave per 8 x 8 tile, one lane per pixel: the relative error of the pixel, a butterfly sum over the
 //                        64 lanes by __shfl_xor (every lane adds the same two values in either order, so all 64 hold the same
 //                        bits and the result is the tree the header states), lane 0 writes the tile and does the two atomics.
 //                        -DRT_NOISE_TILE_LDS builds the same tree through LDS instead (a measurement variant).
 #include "rt_noise.h"
-#include "rt_post_common.h"
+#include "rt_chunk_stats.h"
 
 namespace rt {
 
@@ -21,62 +22,12 @@ __global__ __launch_bounds__(256) void noise_chunk_kernel(const DevNoiseChunkPar
 	const uint32_t wp = blockIdx.x * 256u + threadIdx.x;
 	if (wp >= P.n_work)
 		return;
-	// work item -> pixel, as the render kernel's work_to_pixel for the whole frame (shard 0 of 1)
-	const uint32_t tile_pixels = P.tile_w * P.tile_h;
-	const uint32_t tile = wp / tile_pixels, in = wp - tile * tile_pixels;
-	const uint32_t ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
-	const uint32_t x = tx * P.tile_w + in % P.tile_w, y = ty * P.tile_h + in / P.tile_w;
-	if (x >= P.width || y >= P.height)
+	size_t p;
+	if (!frame_work_pixel(wp, P.tile_w, P.tile_h, P.tiles_x, P.width, P.height, p))
 		return; // edge-tile padding
-	const size_t p = (size_t)y * P.width + x, p3 = 3u * p;
-	float d0 = 1.0f, d1 = 1.0f, d2 = 1.0f;
-	if (P.albedo) {
-		d0 = fmaxf(P.albedo[p3], 1e-3f);
-		d1 = fmaxf(P.albedo[p3 + 1u], 1e-3f);
-		d2 = fmaxf(P.albedo[p3 + 2u], 1e-3f);
-	}
-	const float n = (float)P.chunk_passes, s = (float)P.split;
-	const float *const first = P.partial + 3u * (size_t)wp;
-	const size_t stride = 3u * (size_t)P.n_work;
-	float lsum = 0.0f;
-	for (uint32_t c = 0; c < P.split; ++c) {
-		const float *m = first + c * stride;
-		lsum = lsum + lum(m[0] / n / d0, m[1] / n / d1, m[2] / n / d2);
-	}
-	const float lbar = lsum / s;
-	float sq = 0.0f;
-	for (uint32_t c = 0; c < P.split; ++c) {
-		const float *m = first + c * stride;
-		const float dl = lum(m[0] / n / d0, m[1] / n / d1, m[2] / n / d2) - lbar;
-		sq = sq + dl * dl;
-	}
-	const float var = sq / (float)(P.split * (P.split - 1u));
-
-	float m0 = P.mean_in[p3], m1 = P.mean_in[p3 + 1u], m2 = P.mean_in[p3 + 2u], l = lbar, v = var;
-	if (P.state_m) {
-		if (!P.fresh) {
-			m0 = P.state_m[p3] + m0;
-			m1 = P.state_m[p3 + 1u] + m1;
-			m2 = P.state_m[p3 + 2u] + m2;
-			l = P.state_l[p] + l;
-			v = P.state_v[p] + v;
-		}
-		P.state_m[p3] = m0;
-		P.state_m[p3 + 1u] = m1;
-		P.state_m[p3 + 2u] = m2;
-		P.state_l[p] = l;
-		P.state_v[p] = v;
-	}
-	const float nb = P.batches;
-	if (P.out_mean) {
-		P.out_mean[p3] = m0 / nb;
-		P.out_mean[p3 + 1u] = m1 / nb;
-		P.out_mean[p3 + 2u] = m2 / nb;
-	}
-	if (P.out_lum)
-		P.out_lum[p] = l / nb;
-	if (P.out_var)
-		P.out_var[p] = v / (nb * nb);
+	const Demod d = demod_divisors(P.albedo, 3u * p);
+	const ChunkStats b = chunk_stats(P.partial + 3u * (size_t)wp, 3u * (size_t)P.n_work, P.split, (float)P.chunk_passes, d);
+	chunk_state_step<true>(p, P.mean_in, b, P.state_m, P.state_l, P.state_v, P.fresh != 0u, P.batches, P.out_mean, P.out_lum, P.out_var);
 }
 
 __global__ __launch_bounds__(256) void noise_tile_kernel(const DevNoiseTileParams P)
@@ -87,10 +38,9 @@ __global__ __launch_bounds__(256) void noise_tile_kernel(const DevNoiseTileParam
 #endif
 	// (a wave's trip count is its own: nothing below synchronises the workgroup)
 	for (uint32_t tile = blockIdx.x * 4u + wave; tile < P.n_tiles; tile += gridDim.x * 4u) {
-		const uint32_t ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
-		const uint32_t x = 8u * tx + (lane & 7u), y = 8u * ty + (lane >> 3);
+		uint32_t x, y;
 		float v = 0.0f; // a slot outside the frame
-		if (x < P.width && y < P.height) {
+		if (grid8_pixel(tile, lane, P.tiles_x, P.width, P.height, x, y)) {
 			const size_t p = (size_t)y * P.width + x;
 			v = sqrtf(P.variance[p]) / (fabsf(P.lum_mean[p]) + P.luminance_floor);
 			if (!__builtin_isfinite(v))
@@ -109,6 +59,7 @@ __global__ __launch_bounds__(256) void noise_tile_kernel(const DevNoiseTileParam
 			v = v + __shfl_xor(v, 1 << k);
 #endif
 		if (lane == 0u) {
+			const uint32_t ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
 			const uint32_t w_in = P.width - 8u * tx < 8u ? P.width - 8u * tx : 8u, h_in = P.height - 8u * ty < 8u ? P.height - 8u * ty : 8u;
 			const float e = v / (float)(w_in * h_in);
 			if (P.tile_error)

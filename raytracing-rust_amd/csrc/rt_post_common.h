@@ -11,8 +11,8 @@ namespace {
 
 constexpr uint32_t kMaxBlocks = 65536; // grid-stride beyond this (tall one-column frames)
 
-// Rec. 709 luminance, as written: (0.2126 r + 0.7152 g) + 0.0722 b, no fma
-__device__ inline float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+// Rec. 709 luminance, as written: (0.2126 r + 0.7152 g) + 0.0722 b, no fma (host too: rt_chunk_stats.h is checked there)
+__host__ __device__ inline float lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
 
 __device__ inline bool finite3(float a, float b, float c) { return __builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(c); }
 

@@ -11,8 +11,8 @@ constexpr uint32_t kRobustMaxSplit = 64u;     // the most chunks a pixel is rank
 constexpr uint32_t kRobustBlockThreads = 128u; // two waves: 40 KB of LDS at 64 chunks, below the 64 KB a launch gets unasked
 
 // The S chunk sums of a frame -> the rank-trimmed mean of include/rt_hip.h (rt_robust_opts).  Two addressing modes:
-//   tile_w != 0  the scene's partial buffer, [chunk][work item][3] in the render kernel's tile work order (work_to_pixel,
-//                rt_render.hip, for RT_LAYOUT_FRAME and shard_count 1, as noise_chunk_kernel restates it)
+//   tile_w != 0  the scene's partial buffer, [chunk][work item][3] in the render kernel's tile work order for RT_LAYOUT_FRAME and
+//                shard_count 1 (frame_work_pixel, rt_chunk_stats.h)
 //   tile_w == 0  the caller's planes, [chunk][h][w][3] in frame raster: work item = pixel, n_work = width * height
 struct DevRobustParams {
 	uint32_t width, height, tile_w, tile_h, tiles_x;

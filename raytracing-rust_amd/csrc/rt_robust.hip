@@ -15,7 +15,7 @@
 //     pass 2   (only lanes that drop or trim something) reads the S sums again and adds those whose rank is kept, in chunk order.
 //   Nothing synchronises: a lane touches its own column only.  S is padded to a multiple of eight with keys that rank last.
 #include "rt_robust.h"
-#include "rt_post_common.h"
+#include "rt_chunk_stats.h"
 
 #include "../../include/rt_hip.h"
 
@@ -34,24 +34,13 @@ __global__ __launch_bounds__(kRobustBlockThreads) void robust_chunk_kernel(const
 	const uint32_t wp = blockIdx.x * T + threadIdx.x;
 	if (wp >= P.n_work)
 		return;
-	size_t p = wp;
+	size_t p = wp; // (the caller's planes: frame raster)
 	if (P.tile_w != 0u) {
-		// work item -> pixel, as the render kernel's work_to_pixel for the whole frame (shard 0 of 1)
-		const uint32_t tile_pixels = P.tile_w * P.tile_h;
-		const uint32_t tile = wp / tile_pixels, in = wp - tile * tile_pixels;
-		const uint32_t ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
-		const uint32_t x = tx * P.tile_w + in % P.tile_w, y = ty * P.tile_h + in / P.tile_w;
-		if (x >= P.width || y >= P.height)
+		if (!frame_work_pixel(wp, P.tile_w, P.tile_h, P.tiles_x, P.width, P.height, p))
 			return; // edge-tile padding
-		p = (size_t)y * P.width + x;
 	}
 	const size_t p3 = 3u * p;
-	float d0 = 1.0f, d1 = 1.0f, d2 = 1.0f;
-	if (P.albedo) {
-		d0 = fmaxf(P.albedo[p3], 1e-3f);
-		d1 = fmaxf(P.albedo[p3 + 1u], 1e-3f);
-		d2 = fmaxf(P.albedo[p3 + 2u], 1e-3f);
-	}
+	const Demod d = demod_divisors(P.albedo, p3);
 	const uint32_t S = P.split, Sp = (S + 7u) & ~7u;
 	const float n = (float)P.chunk_passes;
 	const float *const first = P.sums + 3u * (size_t)wp;
@@ -68,7 +57,7 @@ __global__ __launch_bounds__(kRobustBlockThreads) void robust_chunk_kernel(const
 		t0 = t0 + m0;
 		t1 = t1 + m1;
 		t2 = t2 + m2;
-		const float l = lum(m0 / n / d0, m1 / n / d1, m2 / n / d2);
+		const float l = chunk_lum(m, n, d);
 		const uint32_t b = __float_as_uint(l);
 		uint32_t k = kNotFinite;
 		if (__builtin_isfinite(l)) {
