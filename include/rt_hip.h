@@ -1544,6 +1544,25 @@ enum { RT_FRAME_FORMS_TESTED = 0, RT_FRAME_FORMS_FRAME_MISMATCHES = 1, RT_FRAME_
 enum { RT_FRAME_FORM_FRAME_SHORT = 0, RT_FRAME_FORM_RAY_NORM_ONE_PAIR = 1 };
 int rt_selftest_frame_forms(int device, const float *vectors, uint64_t n_vectors, uint64_t counts[RT_FRAME_FORMS_COUNTS]);
 
+/* ---- self-test of the stream seed of GEN as the coarse two-sphere kernels form it (csrc/rt_gen_keys.h; the compile-time switches
+ * lean_gen_keys and lean_gen_item_product of csrc/rt_lean.h): the Philox round keys of `seed` taken from a table the host forms
+ * once (rt_philox_round_keys below) and read by the kernel from its arguments as the render kernels read theirs, without and with
+ * the first round's pixel product formed ahead of the seeding.  Runs ON `device` over the caller's n_cases in [1, 2^22] cases of
+ * RT_GEN_KEYS_CASE_WORDS words -- pixel index, sample index, sample_begin (low word, high word): the stream is that of sample
+ * sample_begin + sample index (64-bit, wrapping) of the pixel, as GEN forms it -- next to include/rt_detmath.h's rt_rng_seed on the
+ * same inputs, and counts: cases run; cases where one of the four state words differs / where one of the first eight draws
+ * (rt_rng_u32) differs, of the keyed form and of the keyed form with the product carried; cases whose Philox block was all zero
+ * (the guard that keeps xoshiro off the zero state ran); and RT_GEN_KEYS_IN_USE, bit RT_GEN_KEYS_FORM_TABLE set when the render
+ * kernels read the table, bit RT_GEN_KEYS_FORM_ITEM_PRODUCT when they carry the product.  The four mismatch counts must be zero. ---- */
+enum { RT_GEN_KEYS_TESTED = 0, RT_GEN_KEYS_STATE_MISMATCHES = 1, RT_GEN_KEYS_DRAW_MISMATCHES = 2, RT_GEN_KEYS_ITEM_STATE_MISMATCHES = 3,
+       RT_GEN_KEYS_ITEM_DRAW_MISMATCHES = 4, RT_GEN_KEYS_ZERO_BLOCKS = 5, RT_GEN_KEYS_IN_USE = 6 };
+#define RT_GEN_KEYS_COUNTS 7
+#define RT_GEN_KEYS_CASE_WORDS 4
+enum { RT_GEN_KEYS_FORM_TABLE = 0, RT_GEN_KEYS_FORM_ITEM_PRODUCT = 1 };
+int rt_selftest_gen_keys(int device, uint64_t seed, const uint32_t *cases, uint64_t n_cases, uint64_t counts[RT_GEN_KEYS_COUNTS]);
+/* the table itself: keys[2 * r], keys[2 * r + 1] = the key words round r (0 = the first) of rt_philox4x32_10 xors in for `seed` */
+void rt_philox_round_keys(uint64_t seed, uint32_t keys[20]);
+
 /* ---- self-test of the two-sphere kernels' shadow walk.  Those scenes have no emissive primitive, so every shadow ray is a sky
  * shadow ray without a limit, and its walk asks of a sphere only whether some t > 0 exists: the kernels answer from signs,
  * without the square root and the quotient of Sphere::get_int, and send the few rays the signs cannot settle to the full test

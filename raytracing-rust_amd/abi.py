@@ -600,6 +600,10 @@ PAIR_SHADOW_WALK_COUNT_NAMES = ("tested", "mismatches", "asked", "asked_both", "
 # rt_selftest_frame_forms (csrc/rt_shade.h coord_from_z_pair, csrc/rt_intersect.h ray_new): names of the counts, and of the bits of "in_use"
 FRAME_FORMS_COUNT_NAMES = ("tested", "frame_mismatches", "frame_short", "frame_plain", "ray_mismatches", "ray_short", "ray_plain", "in_use")
 FRAME_FORM_NAMES = ("frame_guarded_short", "ray_norm_one_pair")
+# rt_selftest_gen_keys (csrc/rt_gen_keys.h): words per case, names of the counts, and of the bits of "in_use"
+GEN_KEYS_CASE_WORDS = 4
+GEN_KEYS_COUNT_NAMES = ("tested", "state_mismatches", "draw_mismatches", "item_state_mismatches", "item_draw_mismatches", "zero_blocks", "in_use")
+GEN_KEYS_FORM_NAMES = ("key_table", "item_product")
 
 DISPLAY_OPTIONS = tuple(n for n, _ in DisplayOpts._fields_ if n not in ("width", "height", "reserved"))
 
@@ -703,6 +707,8 @@ EXPORTED_SYMBOLS = [
     "rt_selftest_div_forms",
     "rt_selftest_sky_pdf_forms",
     "rt_selftest_frame_forms",
+    "rt_selftest_gen_keys",
+    "rt_philox_round_keys",
     "rt_selftest_pair_shadow",
     "rt_selftest_pair_shadow_walk",
     "rt_selftest_pair_primary",

@@ -13,6 +13,7 @@
 #include "rt_query.h"
 #include "rt_radiance.h"
 #include "rt_selftest.h"
+#include "rt_gen_keys.h"
 
 using namespace rt;
 
@@ -482,6 +483,49 @@ int rt_selftest_frame_forms(int device, const float *vectors, uint64_t n_vectors
 	if (rc == RT_OK)
 		counts[RT_FRAME_FORMS_IN_USE] = frame_forms_in_use();
 	return rc;
+}
+
+// rt_selftest_gen_keys: the cases up, one launch on the key table of `seed`, the counters down
+int rt_selftest_gen_keys(int device, uint64_t seed, const uint32_t *cases, uint64_t n_cases, uint64_t counts[RT_GEN_KEYS_COUNTS])
+{
+	if (!cases || !counts || n_cases == 0 || n_cases > (1ull << 22))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (1 to 2^22 cases)");
+	int n_dev = 0;
+	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
+		return fail(RT_ERR_NO_DEVICE, "no such HIP device");
+	HIP_TRY(hipSetDevice(device));
+	// one allocation: the counters, then the cases
+	unsigned long long host[RT_GEN_KEYS_COUNTS] = {};
+	const size_t case_bytes = (size_t)n_cases * RT_GEN_KEYS_CASE_WORDS * sizeof(uint32_t);
+	unsigned long long *d = nullptr;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof host + case_bytes));
+	uint32_t *d_cases = reinterpret_cast<uint32_t *>(d + RT_GEN_KEYS_COUNTS);
+	hipError_t e = hipMemcpy(d, host, sizeof host, hipMemcpyHostToDevice);
+	if (e == hipSuccess)
+		e = hipMemcpy(d_cases, cases, case_bytes, hipMemcpyHostToDevice);
+	if (e == hipSuccess)
+		e = launch_gen_keys(nullptr, seed, d_cases, n_cases, d);
+	if (e == hipSuccess)
+		e = hipMemcpy(host, d, sizeof host, hipMemcpyDeviceToHost);
+	(void)hipFree(d);
+	if (e != hipSuccess)
+		return hip_fail(e, "selftest_gen_keys");
+	for (int k = 0; k < RT_GEN_KEYS_COUNTS; ++k)
+		counts[k] = host[k];
+	counts[RT_GEN_KEYS_IN_USE] = gen_keys_in_use();
+	return RT_OK;
+}
+
+void rt_philox_round_keys(uint64_t seed, uint32_t keys[20])
+{
+	if (!keys)
+		return;
+	DevGenKeys K;
+	philox_round_keys(seed, K);
+	for (int r = 0; r < 10; ++r) {
+		keys[2 * r] = K.key[r][0];
+		keys[2 * r + 1] = K.key[r][1];
+	}
 }
 
 int rt_selftest_pair_primary(rt_scene *s, const float origin[3], uint32_t *valid, uint64_t *mismatches)

@@ -133,8 +133,10 @@ constexpr LeanDivForm lean_div_form(bool pair) { return pair ? LeanDivForm::one_
 // a mean gain of three parent spreads): the frame alone -0.819 ms = 6.0 spreads: ON.  The normalisation alone -0.369 ms = 2.7
 // spreads, and -0.447 ms on top of the frame = 2.8 of that build's spreads: every run below, but short of the gate both times: OFF,
 // ray_new keeps lean_div3 (HISTORY.md).
+// Round 25 measured the normalisation again once the parent's spread had tightened (profiles/r25_gen_keys_ab.log, the same gate):
+// every run below every run of the build without it and a mean gain of more than three of that build's spreads: ON.
 #ifndef RT_PAIR_RAY_NORM_SHORT
-#define RT_PAIR_RAY_NORM_SHORT 0
+#define RT_PAIR_RAY_NORM_SHORT 1
 #endif
 #ifndef RT_PAIR_FRAME_SHORT
 #define RT_PAIR_FRAME_SHORT 1
@@ -142,6 +144,27 @@ constexpr LeanDivForm lean_div_form(bool pair) { return pair ? LeanDivForm::one_
 constexpr bool lean_ray_norm_short(bool pair) { return pair && RT_PAIR_RAY_NORM_SHORT != 0; }
 enum class LeanFrameForm { plain, guarded_short };
 constexpr LeanFrameForm lean_frame_form(bool pair) { return pair && RT_PAIR_FRAME_SHORT != 0 ? LeanFrameForm::guarded_short : LeanFrameForm::plain; }
+// ... and two switches for the integer work of GEN's stream seed in the coarse two-sphere kernels (rt_gen_keys.h; the same bits as
+// rt_rng_seed for every input, rt_selftest_gen_keys):
+//   lean_gen_keys           the Philox round keys read from the kernel arguments (rt_types.h DevGenKeys, formed by the host once per
+//                           render) instead of eighteen scalar adds per sample.  RT_PAIR_GEN_KEYS: 0 = off (rt_rng_seed); 1 = one
+//                           round of loads where the compiler puts them; 2 / 3 / 4 = three groups, the later ones issued 1 / 2 / 3
+//                           rounds ahead of their use;
+//   lean_gen_item_product   the first round's product 0xD2511F53 * pixel formed when the lane is handed its item and carried in two
+//                           registers of lane state (which replace the pixel's index there); needs lean_gen_keys.
+// Measured, six interleaved runs each on rtweekend1 against the parent (51.363 - 51.465 ms kernel time, spread 0.102;
+// profiles/r25_gen_keys_ab.log): the table in one round of loads +0.027 ms, in three groups two rounds ahead -0.031 ms -- the
+// eighteen s_add_i32 are gone from the assembly and the time does not move: both OFF, GEN seeds through rt_rng_seed.  The table
+// with the product carried -0.084 ms (0.16 %, 77 VGPRs instead of 76), runs on both sides of the parent's: OFF.
+#ifndef RT_PAIR_GEN_KEYS
+#define RT_PAIR_GEN_KEYS 0
+#endif
+#ifndef RT_PAIR_GEN_ITEM_PRODUCT
+#define RT_PAIR_GEN_ITEM_PRODUCT 0
+#endif
+constexpr bool lean_gen_keys(bool pair) { return pair && RT_PAIR_GEN_KEYS != 0; }
+constexpr int lean_gen_keys_lead(bool pair) { return lean_gen_keys(pair) ? RT_PAIR_GEN_KEYS - 1 : 0; }
+constexpr bool lean_gen_item_product(bool pair) { return lean_gen_keys(pair) && RT_PAIR_GEN_ITEM_PRODUCT != 0; }
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // ---- device: hipcc's f32 division and square root without the identity steps (see the header comment) ----

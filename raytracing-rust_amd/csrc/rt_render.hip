@@ -36,6 +36,7 @@
 // staged once per workgroup into LDS next to the per-lane traversal stacks.  HBM write traffic is
 // 12 bytes per pixel for the whole render.  No MFMA: nothing here is a dense contraction.
 #include "rt_shade.h"
+#include "rt_gen_keys.h"
 #include "rt_render.h"
 
 namespace rt {
@@ -238,6 +239,7 @@ struct RenderArgs {
 	uint32_t *stack_ovf;
 	DevPairScene pair; // FeatPair only (rt_types.h): the whole scene, read where it is used
 	DevPairPrimary primary; // FeatPair only: the origin-only terms of this render's primary walks
+	DevGenKeys gen_keys; // FeatPair only: the Philox round keys of this render's seed (rt_gen_keys.h)
 };
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const __attribute__((address_space(4))) RenderArgs *KArgs; // the kernarg segment is constant memory: s_load
@@ -414,6 +416,10 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 	constexpr bool kWholeItems = F::pair && !FINE;
 	static_assert(!(kWholeItems && XCHG), "the exchange's records carry chunk_begin and chunk_end, not chunk_c: no whole-pixel items there");
 	constexpr int known_path = F::known_materials ? kMatLambertian : kMatRead; // the material a path continues from (see do_shade)
+	// GEN's stream seed from the host's key table, and with the pixel's product carried from the hand-out (rt_gen_keys.h, the
+	// switches of rt_lean.h): the coarse two-sphere kernels only
+	constexpr bool kKeyedGen = kWholeItems && lean_gen_keys(F::pair);
+	constexpr bool kItemProduct = kWholeItems && lean_gen_item_product(F::pair);
 
 	// ---- per-lane state (registers) ----
 	int ph = PH_NEED_PIXEL;
@@ -444,6 +450,9 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 	uint32_t ray_count = 0;
 	unsigned long long rays_total = 0;
 	bool primary = true;
+	// kItemProduct: (hi, lo) of the first Philox round's product for this lane's pixel, formed where the item is handed out; a
+	// whole-pixel item's later chunks (finalize) are chunks of the same pixel and keep it
+	uint32_t gen_hi0 = 0, gen_lo0 = 0;
 	// the light sample in flight (LIGHT -> shadow walk -> SCATTER).  With the fine schedule it
 	// survives loop iterations (PL below, and the shadow ray lives in `ray`); with the coarse schedule
 	// LIGHT, the shadow walk and SCATTER run back to back in one iteration, so the context and the
@@ -561,7 +570,14 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 		// (the image size in the same round of scalar loads as the rest: left to the compiler it is fetched after the Philox rounds,
 		// a round trip of its own)
 		const uint32_t w1 = here_(k->P.width - 1u), h1 = here_(k->P.height - 1u);
-		rt_rng_seed(&rng, seed, (uint64_t)pixel_index, sample_begin + chunk_begin + sample_i);
+		if constexpr (kKeyedGen) {
+			uint32_t hi0 = gen_hi0, lo0 = gen_lo0;
+			if constexpr (!kItemProduct)
+				philox_pixel_product(pixel_index, hi0, lo0);
+			rng_seed_keyed<lean_gen_keys_lead(F::pair)>(&rng, &k->gen_keys, hi0, lo0, sample_begin + chunk_begin + sample_i);
+		} else {
+			rt_rng_seed(&rng, seed, (uint64_t)pixel_index, sample_begin + chunk_begin + sample_i);
+		}
 		RT_SECTION(15); // GEN: loads + stream seed
 		// (jitter + pixel) / (W - 1): the numerator is zero or in [2^-23, 2^31), the denominator in [1, 2^31]: tame (rt_lean.h) --
 		// and when the host has verified the two divisors (DevRenderParams::w1h1_ok), two fma steps on its reciprocals
@@ -1393,6 +1409,8 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 					out_index = k->P.shard_layout ? w : pixel_index;
 				}
 			}
+			if constexpr (kItemProduct)
+				philox_pixel_product(pixel_index, gen_hi0, gen_lo0);
 			if (w >= k->P.n_items) {
 				ph = PH_DONE;
 			} else if (inside) {
@@ -2080,6 +2098,7 @@ hipError_t launch_render(int method, bool prune, bool fine, bool sky_lds, int fe
 	A.stack_ovf = stack_ovf;
 	A.pair = pair ? *pair : DevPairScene{};
 	A.primary = primary ? *primary : DevPairPrimary{};
+	philox_round_keys(((uint64_t)P.seed_hi << 32) | P.seed_lo, A.gen_keys);
 	hipLaunchKernelGGL(fn, dim3(n_blocks), dim3(block_threads ? block_threads : render_block_threads(feature_set, fine, xchg)), lds_bytes, stream, A);
 	return hipGetLastError();
 }

@@ -61,6 +61,11 @@ hipError_t launch_sky_pdf_forms(hipStream_t stream, const DevScene &S, const flo
 uint32_t frame_forms_in_use(); // bit RT_FRAME_FORM_*: what the two-sphere kernels' switches select (rt_lean.h)
 hipError_t launch_frame_forms(hipStream_t stream, const float *vectors, uint64_t n_vectors, unsigned long long *counts);
 
+// rt_selftest_gen_keys (rt_selftest_forms.hip): n cases of RT_GEN_KEYS_CASE_WORDS words on the key table of `seed`, counts[RT_GEN_KEYS_COUNTS]
+// zeroed by the caller (the kernel leaves RT_GEN_KEYS_IN_USE alone: the caller fills it from gen_keys_in_use)
+uint32_t gen_keys_in_use(); // bit RT_GEN_KEYS_FORM_*: what the two-sphere kernels' switches select (rt_lean.h)
+hipError_t launch_gen_keys(hipStream_t stream, uint64_t seed, const uint32_t *cases, uint64_t n_cases, unsigned long long *counts);
+
 // rt_selftest_pair_shadow (rt_selftest_forms.hip): n cases of RT_PAIR_SHADOW_CASE_FLOATS floats, counts[RT_PAIR_SHADOW_COUNTS] zeroed by the caller
 hipError_t launch_pair_shadow(hipStream_t stream, const float *cases, uint64_t n_cases, unsigned long long *counts);
 // rt_selftest_pair_shadow_walk: n cases of RT_PAIR_SHADOW_WALK_CASE_FLOATS floats, counts[RT_PAIR_SHADOW_WALK_COUNTS] zeroed by the caller

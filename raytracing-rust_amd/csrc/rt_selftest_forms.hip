@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "rt_shade.h"
+#include "rt_gen_keys.h"
 #include "rt_selftest.h"
 #include "rt_selftest_dev.h"
 
@@ -428,6 +429,90 @@ uint32_t frame_forms_in_use()
 {
 	return (lean_frame_form(true) == LeanFrameForm::guarded_short ? 1u << RT_FRAME_FORM_FRAME_SHORT : 0u) |
 	       (lean_ray_norm_short(true) ? 1u << RT_FRAME_FORM_RAY_NORM_ONE_PAIR : 0u);
+}
+
+// rt_selftest_gen_keys: GEN's stream seed from the host's key table (rt_gen_keys.h), in the grouping the render kernels' switch
+// selects, without and with the pixel's product formed ahead, next to rt_rng_seed.  The table travels as a kernel argument and is
+// read through the kernarg pointer with scalar loads, as render_kernel reads RenderArgs::gen_keys.
+struct GenKeysSelftestArgs {
+	DevGenKeys keys;
+	uint64_t seed;
+	const uint32_t *cases;
+	uint64_t n_cases;
+	unsigned long long *counts;
+};
+__device__ __forceinline__ bool same_stream(rt_rng a, rt_rng b, bool &draws_differ)
+{
+	const bool same = a.s0 == b.s0 && a.s1 == b.s1 && a.s2 == b.s2 && a.s3 == b.s3;
+	draws_differ = false;
+	for (int d = 0; d < 8; ++d)
+		draws_differ |= rt_rng_u32(&a) != rt_rng_u32(&b);
+	return same;
+}
+__global__ __launch_bounds__(256) void gen_keys_kernel(const GenKeysSelftestArgs args_by_value)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	const auto *A = (const __attribute__((address_space(4))) GenKeysSelftestArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+	(void)args_by_value;
+#else
+	const GenKeysSelftestArgs *A = &args_by_value;
+#endif
+	constexpr int lead = lean_gen_keys_lead(true);
+	const uint64_t seed = A->seed, n_cases = A->n_cases;
+	const uint32_t *const cases = A->cases;
+	unsigned long long tested = 0, bad_state = 0, bad_draw = 0, bad_item_state = 0, bad_item_draw = 0, zero_blocks = 0;
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_cases; i += (uint64_t)gridDim.x * blockDim.x) {
+		const uint32_t pixel = cases[4u * i], sample_i = cases[4u * i + 1u];
+		const uint64_t sample_begin = ((uint64_t)cases[4u * i + 3u] << 32) | cases[4u * i + 2u];
+		const uint64_t sample = sample_begin + sample_i; // (wraps, as GEN's sum does)
+		rt_rng want, keyed, item;
+		rt_rng_seed(&want, seed, (uint64_t)pixel, sample);
+		uint32_t hi0, lo0;
+		philox_pixel_product(pixel, hi0, lo0);
+		rng_seed_keyed<lead>(&keyed, &A->keys, hi0, lo0, sample);
+		// ... and with the product formed ahead of the seeding, behind a barrier the optimiser cannot merge the two across
+		uint32_t hi0_item, lo0_item;
+		philox_pixel_product(pixel, hi0_item, lo0_item);
+#if defined(__HIP_DEVICE_COMPILE__)
+		asm volatile("" : "+v"(hi0_item), "+v"(lo0_item));
+#endif
+		rng_seed_keyed<lead>(&item, &A->keys, hi0_item, lo0_item, sample);
+		bool draws;
+		bad_state += !same_stream(keyed, want, draws);
+		bad_draw += draws;
+		bad_item_state += !same_stream(item, want, draws);
+		bad_item_draw += draws;
+		zero_blocks += want.s0 == 1u && (want.s1 | want.s2 | want.s3) == 0u; // (the guard's state; a block (1, 0, 0, 0) itself counts too)
+		++tested;
+	}
+	unsigned long long *const counts = A->counts;
+	atomicAdd(&counts[RT_GEN_KEYS_TESTED], tested);
+	if (bad_state)
+		atomicAdd(&counts[RT_GEN_KEYS_STATE_MISMATCHES], bad_state);
+	if (bad_draw)
+		atomicAdd(&counts[RT_GEN_KEYS_DRAW_MISMATCHES], bad_draw);
+	if (bad_item_state)
+		atomicAdd(&counts[RT_GEN_KEYS_ITEM_STATE_MISMATCHES], bad_item_state);
+	if (bad_item_draw)
+		atomicAdd(&counts[RT_GEN_KEYS_ITEM_DRAW_MISMATCHES], bad_item_draw);
+	if (zero_blocks)
+		atomicAdd(&counts[RT_GEN_KEYS_ZERO_BLOCKS], zero_blocks);
+}
+hipError_t launch_gen_keys(hipStream_t stream, uint64_t seed, const uint32_t *cases, uint64_t n_cases, unsigned long long *counts)
+{
+	GenKeysSelftestArgs A;
+	philox_round_keys(seed, A.keys);
+	A.seed = seed;
+	A.cases = cases;
+	A.n_cases = n_cases;
+	A.counts = counts;
+	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_cases + 255u) / 256u, 2048u);
+	hipLaunchKernelGGL(gen_keys_kernel, dim3(blocks), dim3(256), 0, stream, A);
+	return hipGetLastError();
+}
+uint32_t gen_keys_in_use()
+{
+	return (lean_gen_keys(true) ? 1u << RT_GEN_KEYS_FORM_TABLE : 0u) | (lean_gen_item_product(true) ? 1u << RT_GEN_KEYS_FORM_ITEM_PRODUCT : 0u);
 }
 
 uint32_t short_forms_input_bits(int form, uint64_t index)

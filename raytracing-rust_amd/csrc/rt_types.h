@@ -287,6 +287,17 @@ RT_FN void pair_primary_terms(const DevPairScene &q, const float root_min[3], co
 	pp.pad[0] = pp.pad[1] = pp.pad[2] = 0u;
 }
 
+// FeatPair, GEN: the key of a sample's Philox block is the render's seed, so the ten round keys (k0, k1) of rt_philox4x32_10
+// (include/rt_detmath.h: the seed's two words, then `k0 += 0x9E3779B9; k1 += 0xBB67AE85` after every round, wrapping) are the
+// same for every sample of a launch.  The host forms them once per render (rt_gen_keys.h philox_round_keys) and GEN reads them
+// with scalar loads next to the seed it already read there, instead of eighteen scalar adds per sample.  key[r] is what round r
+// (0 = the first) xors in; rounds 0 - 7 fill the first 64-byte line, 8 and 9 start the second.
+struct alignas(64) DevGenKeys {
+	uint32_t key[10][2];
+	uint32_t pad[12];
+};
+static_assert(sizeof(DevGenKeys) == 128, "DevGenKeys: two 64-byte lines");
+
 struct DevCamera {
 	float origin[3], lower_left[3], horizontal[3], vertical[3];
 };

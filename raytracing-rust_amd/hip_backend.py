@@ -254,6 +254,29 @@ def selftest_frame_forms(vectors, device=0):
     return res
 
 
+def philox_round_keys(seed):
+    """rt_philox_round_keys: (10, 2) uint32, row r = the key words round r of rt_philox4x32_10 xors in for `seed` (host only)"""
+    keys = np.zeros((10, 2), dtype=np.uint32)
+    lib().rt_philox_round_keys.restype = None
+    lib().rt_philox_round_keys(C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), _p(keys, C.c_uint32))
+    return keys
+
+
+def selftest_gen_keys(seed, cases, device=0):
+    """rt_selftest_gen_keys: cases (n, 4) uint32 -- pixel index, sample index, sample_begin low word, high word -- seeded on the GPU
+    from the host's key table of `seed`, without and with the pixel's product formed ahead, next to rt_rng_seed: {"tested",
+    "state_mismatches", "draw_mismatches", "item_state_mismatches", "item_draw_mismatches", "zero_blocks"} and "in_use": names of
+    the forms the render kernels' switches select.  The four mismatch counts must be zero."""
+    cases = np.ascontiguousarray(cases, dtype=np.uint32)
+    if cases.ndim != 2 or cases.shape[1] != abi.GEN_KEYS_CASE_WORDS:
+        raise ValueError(f"cases must be (n, {abi.GEN_KEYS_CASE_WORDS}), got {cases.shape}")
+    out = (C.c_uint64 * len(abi.GEN_KEYS_COUNT_NAMES))()
+    _check(lib().rt_selftest_gen_keys(C.c_int(device), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), _p(cases, C.c_uint32), C.c_uint64(cases.shape[0]), out))
+    res = dict(zip(abi.GEN_KEYS_COUNT_NAMES, (int(x) for x in out)))
+    res["in_use"] = [n for k, n in enumerate(abi.GEN_KEYS_FORM_NAMES) if res["in_use"] >> k & 1]
+    return res
+
+
 def selftest_pair_shadow(cases, device=0):
     """rt_selftest_pair_shadow: cases (n, 10) f32 -- centre, radius, ray origin, ray direction (as given) -- through the two-sphere
     kernels' occlusion predicate for a ray without a limit and through Sphere::get_int's `hit && t > 0`, on the GPU:
