@@ -604,6 +604,14 @@ FRAME_FORM_NAMES = ("frame_guarded_short", "ray_norm_one_pair")
 GEN_KEYS_CASE_WORDS = 4
 GEN_KEYS_COUNT_NAMES = ("tested", "state_mismatches", "draw_mismatches", "item_state_mismatches", "item_draw_mismatches", "zero_blocks", "in_use")
 GEN_KEYS_FORM_NAMES = ("key_table", "item_product")
+# the self-tests that take (n, width) cases and answer named counts: name -> (symbol, element type, width, what the binding calls the
+# cases, names of the counts, names of the bits of "in_use" where the counts have one)
+SELFTEST_CASE_TABLES = {
+    "pair_shadow": ("rt_selftest_pair_shadow", C.c_float, PAIR_SHADOW_CASE_FLOATS, "cases", PAIR_SHADOW_COUNT_NAMES, None),
+    "pair_shadow_walk": ("rt_selftest_pair_shadow_walk", C.c_float, PAIR_SHADOW_WALK_CASE_FLOATS, "cases", PAIR_SHADOW_WALK_COUNT_NAMES, None),
+    "frame_forms": ("rt_selftest_frame_forms", C.c_float, 3, "vectors", FRAME_FORMS_COUNT_NAMES, FRAME_FORM_NAMES),
+    "gen_keys": ("rt_selftest_gen_keys", C.c_uint32, GEN_KEYS_CASE_WORDS, "cases", GEN_KEYS_COUNT_NAMES, GEN_KEYS_FORM_NAMES),
+}
 
 DISPLAY_OPTIONS = tuple(n for n, _ in DisplayOpts._fields_ if n not in ("width", "height", "reserved"))
 

@@ -63,6 +63,61 @@ extern "C" int rt_debug_trace_queue(rt_scene *s, const rt_ray_desc *rays, uint64
 }
 #endif
 
+// ---- what the self-tests share: cases up, one launch, counters down ----
+// On `device`: ONE allocation of the n_words counters -- they start as `counts` holds them: zeros, all ones in a first-index slot --
+// with the case_bytes of `cases` behind them (none: nothing goes up); launch(d_counts, d_cases) on the null stream; the counters
+// back into `counts`.  The caller has checked its arguments: the device is looked at here, last.
+template <class Launch>
+static int run_cases(int device, const void *cases, size_t case_bytes, unsigned long long *counts, size_t n_words, const char *what, Launch launch)
+{
+	int n_dev = 0;
+	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
+		return fail(RT_ERR_NO_DEVICE, "no such HIP device");
+	HIP_TRY(hipSetDevice(device));
+	unsigned long long *d = nullptr;
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), n_words * sizeof *d + case_bytes));
+	void *d_cases = d + n_words;
+	hipError_t e = hipMemcpy(d, counts, n_words * sizeof *d, hipMemcpyHostToDevice);
+	if (e == hipSuccess && case_bytes)
+		e = hipMemcpy(d_cases, cases, case_bytes, hipMemcpyHostToDevice);
+	if (e == hipSuccess)
+		e = launch(d, d_cases);
+	if (e == hipSuccess)
+		e = hipMemcpy(counts, d, n_words * sizeof *d, hipMemcpyDeviceToHost);
+	(void)hipFree(d);
+	if (e != hipSuccess)
+		return hip_fail(e, what);
+	return RT_OK;
+}
+
+// the self-tests that take a table of 1 to 2^22 cases of `case_size` bytes and answer N counters, all from zero
+template <int N, class Case, class Launch>
+static int run_case_table(int device, const Case *cases, uint64_t n_cases, size_t case_size, uint64_t *counts, const char *what, Launch launch)
+{
+	if (!cases || !counts || n_cases == 0 || n_cases > (1ull << 22))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (1 to 2^22 cases)");
+	unsigned long long host[N] = {};
+	RT_TRY(run_cases(device, cases, (size_t)n_cases * case_size, host, N, what, [&](unsigned long long *d_counts, void *d_cases) {
+		return launch(nullptr, static_cast<const Case *>(d_cases), n_cases, d_counts);
+	}));
+	std::copy(host, host + N, counts);
+	return RT_OK;
+}
+
+// the two self-tests on a scene's stream: a device buffer of their own carved by `L` (freed by sky_finish), copies through Staging
+static int sky_buffer(rt_scene *s, Layout &L)
+{
+	HIP_TRY(hipSetDevice(s->device));
+	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&L.base), L.total()));
+	return RT_OK;
+}
+static int sky_finish(Staging &st, Layout &L, const char *what)
+{
+	const int rc = st.finish(what);
+	(void)hipFree(L.base);
+	return rc;
+}
+
 extern "C" {
 
 // ---- batch hit queries ----
@@ -225,57 +280,36 @@ int rt_selftest_sky(rt_scene *s, int tables_in_lds, uint64_t seed, uint64_t n, f
 		return fail(RT_ERR_UNSUPPORTED, "the sky tables exceed what a launch stages into LDS");
 	if (n + m == 0)
 		return RT_OK;
-	HIP_TRY(hipSetDevice(s->device));
-	// one allocation: directions and pdfs of the samples, then the caller's directions and their pdfs
-	float *d = nullptr;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), (4 * n + 4 * m) * sizeof(float)));
+	// directions and pdfs of the samples, then the caller's directions and their pdfs (a part of no elements is absent: NULL)
+	Layout L;
+	const auto p_out_dirs = L.add<float>(3 * n), p_out_pdf_s = L.add<float>(n), p_dirs = L.add<float>(3 * m), p_out_pdf = L.add<float>(m);
+	RT_TRY(sky_buffer(s, L));
 	DevSkySelftest P;
 	P.seed = seed;
 	P.n = n;
 	P.m = m;
-	P.out_dirs = d;
-	P.out_pdf_s = d + 3 * n;
-	float *d_dirs = d + 4 * n;
-	P.dirs = d_dirs;
-	P.out_pdf = d_dirs + 3 * m;
-	hipError_t e = hipSuccess;
-	if (m)
-		e = hipMemcpyAsync(d_dirs, dirs, 3 * m * sizeof(float), hipMemcpyHostToDevice, s->stream);
-	if (e == hipSuccess)
-		e = launch_sky_selftest(tables_in_lds != 0, s->stream, s->dev, P);
-	if (e == hipSuccess && n)
-		e = hipMemcpyAsync(out_dirs, P.out_dirs, 3 * n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-	if (e == hipSuccess && n)
-		e = hipMemcpyAsync(out_pdf_of_sample, P.out_pdf_s, n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-	if (e == hipSuccess && m)
-		e = hipMemcpyAsync(out_pdf, P.out_pdf, m * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-	const hipError_t e_sync = hipStreamSynchronize(s->stream);
-	if (e == hipSuccess)
-		e = e_sync;
-	(void)hipFree(d);
-	if (e != hipSuccess)
-		return hip_fail(e, "selftest_sky");
-	return RT_OK;
+	P.out_dirs = L.at(p_out_dirs);
+	P.out_pdf_s = L.at(p_out_pdf_s);
+	P.dirs = L.at(p_dirs);
+	P.out_pdf = L.at(p_out_pdf);
+	Staging st{s};
+	st.put(L, p_dirs, dirs);
+	if (st.ok())
+		st.e = launch_sky_selftest(tables_in_lds != 0, s->stream, s->dev, P);
+	st.get(out_dirs, L, p_out_dirs);
+	st.get(out_pdf_of_sample, L, p_out_pdf_s);
+	st.get(out_pdf, L, p_out_pdf);
+	return sky_finish(st, L, "selftest_sky");
 }
 
 int rt_selftest_lean(int device, uint64_t n_per_thread, uint64_t seed, uint64_t mismatches[RT_SELFTEST_LEAN_CLASSES])
 {
 	if (!mismatches || n_per_thread == 0 || n_per_thread > (1ull << 20))
 		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (n_per_thread in [1, 2^20])");
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
-		return fail(RT_ERR_NO_DEVICE, "no such HIP device");
-	HIP_TRY(hipSetDevice(device));
-	unsigned long long *d = nullptr;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), RT_SELFTEST_LEAN_CLASSES * sizeof(unsigned long long)));
-	hipError_t e = hipMemset(d, 0, RT_SELFTEST_LEAN_CLASSES * sizeof(unsigned long long));
-	if (e == hipSuccess)
-		e = launch_selftest_lean(nullptr, 1024u, n_per_thread, seed, d);
-	if (e == hipSuccess)
-		e = hipMemcpy(mismatches, d, RT_SELFTEST_LEAN_CLASSES * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-	(void)hipFree(d);
-	if (e != hipSuccess)
-		return hip_fail(e, "selftest");
+	unsigned long long host[RT_SELFTEST_LEAN_CLASSES] = {};
+	RT_TRY(run_cases(device, nullptr, 0, host, RT_SELFTEST_LEAN_CLASSES, "selftest",
+	                 [&](unsigned long long *d, void *) { return launch_selftest_lean(nullptr, 1024u, n_per_thread, seed, d); }));
+	std::copy(host, host + RT_SELFTEST_LEAN_CLASSES, mismatches);
 	return RT_OK;
 }
 
@@ -283,35 +317,21 @@ int rt_selftest_short_forms(int device, const float *operands, uint64_t n_operan
 {
 	if (!out || (operands && (n_operands == 0 || n_operands > (1ull << 20))) || (!operands && n_operands != 0))
 		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (operands NULL with n_operands 0, or 1 to 2^20 operands)");
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
-		return fail(RT_ERR_NO_DEVICE, "no such HIP device");
-	HIP_TRY(hipSetDevice(device));
-	// one allocation: the counters in the order of DevShortForms, then the operands
+	// the counters in the order of DevShortForms, the first indices all ones
 	constexpr size_t kWords = 2 + RT_SHORT_FORMS + RT_SHORT_FORMS + 4 + 1 + RT_SHORT_SITES;
 	unsigned long long host[kWords] = {};
-	unsigned long long *d = nullptr;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), kWords * sizeof *d + (size_t)n_operands * sizeof(float)));
-	DevShortForms D;
-	D.tested = d;
-	D.mismatches = D.tested + 2;
-	D.first_index = D.mismatches + RT_SHORT_FORMS;
-	D.sqrt_raw = D.first_index + RT_SHORT_FORMS;
-	D.site_tested = D.sqrt_raw + 4;
-	D.site_mismatches = D.site_tested + 1;
 	for (int k = 0; k < RT_SHORT_FORMS; ++k)
 		host[2 + RT_SHORT_FORMS + k] = ~0ull;
-	float *d_operands = reinterpret_cast<float *>(d + kWords);
-	hipError_t e = hipMemcpy(d, host, sizeof host, hipMemcpyHostToDevice);
-	if (e == hipSuccess && operands)
-		e = hipMemcpy(d_operands, operands, (size_t)n_operands * sizeof(float), hipMemcpyHostToDevice);
-	if (e == hipSuccess)
-		e = launch_short_forms(nullptr, D, operands ? d_operands : nullptr, n_operands);
-	if (e == hipSuccess)
-		e = hipMemcpy(host, d, sizeof host, hipMemcpyDeviceToHost);
-	(void)hipFree(d);
-	if (e != hipSuccess)
-		return hip_fail(e, "selftest_short_forms");
+	RT_TRY(run_cases(device, operands, (size_t)n_operands * sizeof(float), host, kWords, "selftest_short_forms", [&](unsigned long long *d, void *d_operands) {
+		DevShortForms D;
+		D.tested = d;
+		D.mismatches = D.tested + 2;
+		D.first_index = D.mismatches + RT_SHORT_FORMS;
+		D.sqrt_raw = D.first_index + RT_SHORT_FORMS;
+		D.site_tested = D.sqrt_raw + 4;
+		D.site_mismatches = D.site_tested + 1;
+		return launch_short_forms(nullptr, D, operands ? static_cast<const float *>(d_operands) : nullptr, n_operands);
+	}));
 	std::memset(out, 0, sizeof *out);
 	for (int k = 0; k < RT_SHORT_FORMS; ++k) {
 		out->form[k].tested = host[k <= RT_SHORT_FORM_INV_TWO_PAIRS ? 0 : 1];
@@ -347,47 +367,30 @@ int rt_selftest_div_forms(int device, const rt_div_forms_slice *slice, const flo
 			if (slice->exponents[k] < -126 || slice->exponents[k] > 127)
 				return fail(RT_ERR_INVALID_ARGUMENT, "bad slice (binary exponents in [-126, 127])");
 	}
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
-		return fail(RT_ERR_NO_DEVICE, "no such HIP device");
-	HIP_TRY(hipSetDevice(device));
-	// one allocation: the counters, then the operands, or the exponents and the denominator list
-	const uint64_t n_den = slice && slice->denominators ? slice->n_denominators : 0, n_exp = slice ? 2 * slice->n_exponent_pairs : 0;
-	const size_t tail_bytes = operands ? (size_t)n_operand_pairs * 2 * sizeof(float) : (size_t)(n_exp + n_den) * sizeof(uint32_t);
 	unsigned long long host[kDivCounts] = {};
 	for (int k = 0; k < RT_DIV_FORMS; ++k)
 		host[kDivCountFirst + k] = ~0ull;
-	unsigned long long *d = nullptr;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof host + tail_bytes));
-	hipError_t e = hipMemcpy(d, host, sizeof host, hipMemcpyHostToDevice);
 	if (operands) {
-		float *d_pairs = reinterpret_cast<float *>(d + kDivCounts);
-		if (e == hipSuccess)
-			e = hipMemcpy(d_pairs, operands, tail_bytes, hipMemcpyHostToDevice);
-		if (e == hipSuccess)
-			e = launch_div_sites(nullptr, d_pairs, n_operand_pairs, d);
+		RT_TRY(run_cases(device, operands, (size_t)n_operand_pairs * 2 * sizeof(float), host, kDivCounts, "selftest_div_forms",
+		                 [&](unsigned long long *d, void *d_pairs) { return launch_div_sites(nullptr, static_cast<const float *>(d_pairs), n_operand_pairs, d); }));
 	} else {
-		int32_t *d_exp = reinterpret_cast<int32_t *>(d + kDivCounts);
-		uint32_t *d_den = reinterpret_cast<uint32_t *>(d_exp + n_exp);
-		if (e == hipSuccess)
-			e = hipMemcpy(d_exp, slice->exponents, n_exp * sizeof(int32_t), hipMemcpyHostToDevice);
-		if (e == hipSuccess && n_den)
-			e = hipMemcpy(d_den, slice->denominators, n_den * sizeof(uint32_t), hipMemcpyHostToDevice);
-		DevDivForms D;
-		D.denominators = n_den ? d_den : nullptr;
-		D.n_denominators = (uint32_t)slice->n_denominators;
-		D.first_denominator = slice->first_denominator;
-		D.exponents = d_exp;
-		D.n_exponent_pairs = (uint32_t)slice->n_exponent_pairs;
-		D.counts = d;
-		if (e == hipSuccess)
-			e = launch_div_forms(nullptr, D);
+		// behind the counters: the exponents, then the denominator list if there is one
+		const uint64_t n_den = slice->denominators ? slice->n_denominators : 0, n_exp = 2 * slice->n_exponent_pairs;
+		std::vector<uint32_t> tail(n_exp + n_den);
+		std::memcpy(tail.data(), slice->exponents, n_exp * sizeof(int32_t));
+		if (n_den)
+			std::memcpy(tail.data() + n_exp, slice->denominators, n_den * sizeof(uint32_t));
+		RT_TRY(run_cases(device, tail.data(), tail.size() * sizeof(uint32_t), host, kDivCounts, "selftest_div_forms", [&](unsigned long long *d, void *d_tail) {
+			DevDivForms D;
+			D.exponents = static_cast<const int32_t *>(d_tail);
+			D.n_exponent_pairs = (uint32_t)slice->n_exponent_pairs;
+			D.denominators = n_den ? static_cast<const uint32_t *>(d_tail) + n_exp : nullptr;
+			D.n_denominators = (uint32_t)slice->n_denominators;
+			D.first_denominator = slice->first_denominator;
+			D.counts = d;
+			return launch_div_forms(nullptr, D);
+		}));
 	}
-	if (e == hipSuccess)
-		e = hipMemcpy(host, d, sizeof host, hipMemcpyDeviceToHost);
-	(void)hipFree(d);
-	if (e != hipSuccess)
-		return hip_fail(e, "selftest_div_forms");
 	std::memset(out, 0, sizeof *out);
 	out->tested = host[kDivCountTested];
 	for (int k = 0; k < RT_DIV_FORMS; ++k) {
@@ -416,102 +419,42 @@ int rt_selftest_sky_pdf_forms(rt_scene *s, const float *dirs, uint64_t m, float 
 		return fail(RT_ERR_INVALID_ARGUMENT, "the sky is not samplable (sampler_res 0 x 0)");
 	if (int rc = need_device(s); rc != RT_OK)
 		return rc;
-	HIP_TRY(hipSetDevice(s->device));
-	float *d = nullptr; // directions, then both results
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), 5 * m * sizeof(float)));
-	hipError_t e = hipMemcpyAsync(d, dirs, 3 * m * sizeof(float), hipMemcpyHostToDevice, s->stream);
-	if (e == hipSuccess)
-		e = launch_sky_pdf_forms(s->stream, s->dev, d, m, d + 3 * m, d + 4 * m);
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(out_pdf_pair, d + 3 * m, m * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-	if (e == hipSuccess)
-		e = hipMemcpyAsync(out_pdf_default, d + 4 * m, m * sizeof(float), hipMemcpyDeviceToHost, s->stream);
-	const hipError_t e_sync = hipStreamSynchronize(s->stream);
-	if (e == hipSuccess)
-		e = e_sync;
-	(void)hipFree(d);
-	if (e != hipSuccess)
-		return hip_fail(e, "selftest_sky_pdf_forms");
-	return RT_OK;
+	Layout L; // directions, then both results
+	const auto p_dirs = L.add<float>(3 * m), p_pair = L.add<float>(m), p_default = L.add<float>(m);
+	RT_TRY(sky_buffer(s, L));
+	Staging st{s};
+	st.put(L, p_dirs, dirs);
+	if (st.ok())
+		st.e = launch_sky_pdf_forms(s->stream, s->dev, L.at(p_dirs), m, L.at(p_pair), L.at(p_default));
+	st.get(out_pdf_pair, L, p_pair);
+	st.get(out_pdf_default, L, p_default);
+	return sky_finish(st, L, "selftest_sky_pdf_forms");
 }
 
-// rt_selftest_pair_shadow / _walk: the caller's cases up, one launch, the counters down
-static int run_pair_shadow_cases(int device, const float *cases, uint64_t n_cases, size_t case_floats, uint64_t *counts, int n_counts,
-                                 hipError_t (*launch)(hipStream_t, const float *, uint64_t, unsigned long long *), const char *what)
-{
-	if (!cases || !counts || n_cases == 0 || n_cases > (1ull << 22))
-		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (1 to 2^22 cases)");
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
-		return fail(RT_ERR_NO_DEVICE, "no such HIP device");
-	HIP_TRY(hipSetDevice(device));
-	// one allocation: the counters, then the cases
-	constexpr int kMaxCounts = 8;
-	static_assert(RT_PAIR_SHADOW_COUNTS <= kMaxCounts && RT_PAIR_SHADOW_WALK_COUNTS <= kMaxCounts && RT_FRAME_FORMS_COUNTS <= kMaxCounts, "counters");
-	unsigned long long host[kMaxCounts] = {};
-	const size_t case_bytes = (size_t)n_cases * case_floats * sizeof(float);
-	unsigned long long *d = nullptr;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof host + case_bytes));
-	float *d_cases = reinterpret_cast<float *>(d + kMaxCounts);
-	hipError_t e = hipMemcpy(d, host, sizeof host, hipMemcpyHostToDevice);
-	if (e == hipSuccess)
-		e = hipMemcpy(d_cases, cases, case_bytes, hipMemcpyHostToDevice);
-	if (e == hipSuccess)
-		e = launch(nullptr, d_cases, n_cases, d);
-	if (e == hipSuccess)
-		e = hipMemcpy(host, d, sizeof host, hipMemcpyDeviceToHost);
-	(void)hipFree(d);
-	if (e != hipSuccess)
-		return hip_fail(e, what);
-	for (int k = 0; k < n_counts; ++k)
-		counts[k] = host[k];
-	return RT_OK;
-}
 int rt_selftest_pair_shadow(int device, const float *cases, uint64_t n_cases, uint64_t counts[RT_PAIR_SHADOW_COUNTS])
 {
-	return run_pair_shadow_cases(device, cases, n_cases, RT_PAIR_SHADOW_CASE_FLOATS, counts, RT_PAIR_SHADOW_COUNTS, launch_pair_shadow, "selftest_pair_shadow");
+	return run_case_table<RT_PAIR_SHADOW_COUNTS>(device, cases, n_cases, RT_PAIR_SHADOW_CASE_FLOATS * sizeof(float), counts, "selftest_pair_shadow",
+	                                             launch_pair_shadow);
 }
 int rt_selftest_pair_shadow_walk(int device, const float *cases, uint64_t n_cases, uint64_t counts[RT_PAIR_SHADOW_WALK_COUNTS])
 {
-	return run_pair_shadow_cases(device, cases, n_cases, RT_PAIR_SHADOW_WALK_CASE_FLOATS, counts, RT_PAIR_SHADOW_WALK_COUNTS, launch_pair_shadow_walk,
-	                             "selftest_pair_shadow_walk");
+	return run_case_table<RT_PAIR_SHADOW_WALK_COUNTS>(device, cases, n_cases, RT_PAIR_SHADOW_WALK_CASE_FLOATS * sizeof(float), counts,
+	                                                  "selftest_pair_shadow_walk", launch_pair_shadow_walk);
 }
-// rt_selftest_frame_forms: the same plumbing, three floats a vector; the switches' report is the host's to fill
+// ... three floats a vector; what the switches select is the host's to fill in, here and below
 int rt_selftest_frame_forms(int device, const float *vectors, uint64_t n_vectors, uint64_t counts[RT_FRAME_FORMS_COUNTS])
 {
-	const int rc = run_pair_shadow_cases(device, vectors, n_vectors, 3, counts, RT_FRAME_FORMS_COUNTS, launch_frame_forms, "selftest_frame_forms");
-	if (rc == RT_OK)
-		counts[RT_FRAME_FORMS_IN_USE] = frame_forms_in_use();
-	return rc;
+	RT_TRY(run_case_table<RT_FRAME_FORMS_COUNTS>(device, vectors, n_vectors, 3 * sizeof(float), counts, "selftest_frame_forms", launch_frame_forms));
+	counts[RT_FRAME_FORMS_IN_USE] = frame_forms_in_use();
+	return RT_OK;
 }
-
-// rt_selftest_gen_keys: the cases up, one launch on the key table of `seed`, the counters down
+// ... one launch on the key table of `seed`
 int rt_selftest_gen_keys(int device, uint64_t seed, const uint32_t *cases, uint64_t n_cases, uint64_t counts[RT_GEN_KEYS_COUNTS])
 {
-	if (!cases || !counts || n_cases == 0 || n_cases > (1ull << 22))
-		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (1 to 2^22 cases)");
-	int n_dev = 0;
-	if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev)
-		return fail(RT_ERR_NO_DEVICE, "no such HIP device");
-	HIP_TRY(hipSetDevice(device));
-	// one allocation: the counters, then the cases
-	unsigned long long host[RT_GEN_KEYS_COUNTS] = {};
-	const size_t case_bytes = (size_t)n_cases * RT_GEN_KEYS_CASE_WORDS * sizeof(uint32_t);
-	unsigned long long *d = nullptr;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof host + case_bytes));
-	uint32_t *d_cases = reinterpret_cast<uint32_t *>(d + RT_GEN_KEYS_COUNTS);
-	hipError_t e = hipMemcpy(d, host, sizeof host, hipMemcpyHostToDevice);
-	if (e == hipSuccess)
-		e = hipMemcpy(d_cases, cases, case_bytes, hipMemcpyHostToDevice);
-	if (e == hipSuccess)
-		e = launch_gen_keys(nullptr, seed, d_cases, n_cases, d);
-	if (e == hipSuccess)
-		e = hipMemcpy(host, d, sizeof host, hipMemcpyDeviceToHost);
-	(void)hipFree(d);
-	if (e != hipSuccess)
-		return hip_fail(e, "selftest_gen_keys");
-	for (int k = 0; k < RT_GEN_KEYS_COUNTS; ++k)
-		counts[k] = host[k];
+	RT_TRY(run_case_table<RT_GEN_KEYS_COUNTS>(device, cases, n_cases, RT_GEN_KEYS_CASE_WORDS * sizeof(uint32_t), counts, "selftest_gen_keys",
+	                                          [seed](hipStream_t stream, const uint32_t *d_cases, uint64_t n, unsigned long long *d_counts) {
+		                                          return launch_gen_keys(stream, seed, d_cases, n, d_counts);
+	                                          }));
 	counts[RT_GEN_KEYS_IN_USE] = gen_keys_in_use();
 	return RT_OK;
 }
@@ -536,17 +479,12 @@ int rt_selftest_pair_primary(rt_scene *s, const float origin[3], uint32_t *valid
 		return rc;
 	if (!s->pair_tree)
 		return fail(RT_ERR_UNSUPPORTED, "not a scene the two-sphere kernels take");
-	HIP_TRY(hipSetDevice(s->device));
 	DevPairPrimary host{};
 	pair_primary_terms(s->pair, s->dev.root_min, s->dev.root_max, v3(origin[0], origin[1], origin[2]), host);
-	unsigned long long *d = nullptr, bad = 0;
-	HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d), sizeof *d));
-	hipError_t e = launch_selftest_pair_primary(nullptr, s->pair, s->dev.root_min, s->dev.root_max, origin, host, d);
-	if (e == hipSuccess)
-		e = hipMemcpy(&bad, d, sizeof bad, hipMemcpyDeviceToHost);
-	(void)hipFree(d);
-	if (e != hipSuccess)
-		return hip_fail(e, "selftest_pair_primary");
+	unsigned long long bad = 0; // (the kernel's one word; the scene's device, no cases)
+	RT_TRY(run_cases(s->device, nullptr, 0, &bad, 1, "selftest_pair_primary", [&](unsigned long long *d, void *) {
+		return launch_selftest_pair_primary(nullptr, s->pair, s->dev.root_min, s->dev.root_max, origin, host, d);
+	}));
 	*valid = host.valid;
 	*mismatches = bad;
 	return RT_OK;

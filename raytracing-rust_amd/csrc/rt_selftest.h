@@ -27,7 +27,10 @@ size_t sky_selftest_lds_bytes(const DevScene &S);
 hipError_t launch_sky_selftest(bool tables_in_lds, hipStream_t stream, const DevScene &S, const DevSkySelftest &P);
 
 
-// rt_selftest_short_forms (rt_selftest_forms.hip): the device-side counters, zeroed by the caller except first_index (all ones)
+// ---- rt_selftest_forms.hip.  Every launch below adds to counters the caller has set (zeros; all ones in a first-index slot) and runs
+// its cases grid-stride (rt_selftest_dev.h); the "in use" reports are the host's to fill in, the kernels leave those words alone. ----
+
+// rt_selftest_short_forms: the device-side counters
 constexpr uint32_t kShortFormsRcpExponentCount = 8;
 struct DevShortForms {
 	unsigned long long *tested;          // [2]: reciprocal inputs, square-root inputs

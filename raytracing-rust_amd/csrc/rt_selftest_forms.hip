@@ -1,41 +1,14 @@
 // rt_selftest_forms.hip -- rt_selftest_pair_shadow (below) and rt_selftest_short_forms (include/rt_hip.h): the short forms of rt_lean.h that rest on what gfx950's
 // v_rcp_f32 / v_sqrt_f32 return, ENUMERATED against the plain operators on the device, and the call sites that guard them on
-// operands the caller chooses.  Plain grid-stride kernels, integer counters through atomicAdd / atomicMin; no array is indexed by
-// anything but a compile-time constant.  A translation unit of its own: tests/test_sky_resources.py pins the kernels of
-// rt_selftest.hip's bundle by name.
-#include <algorithm>
-
+// operands the caller chooses.  Every kernel is a comparison inside for_each_case with its counters in a Tally, launched by
+// launch_cases (rt_selftest_dev.h): integer counters through atomicAdd / atomicMin; no array is indexed by anything but a
+// compile-time constant.  A translation unit of its own: tests/test_sky_resources.py pins the kernels of rt_selftest.hip's bundle by name.
 #include "rt_shade.h"
 #include "rt_gen_keys.h"
 #include "rt_selftest.h"
 #include "rt_selftest_dev.h"
 
 namespace rt {
-
-// counts[form] += bad; first[form] = min(first[form], index of the input in enumeration order) -- deterministic whatever the schedule
-struct FormTally {
-	unsigned long long bad[RT_SHORT_FORMS] = {};
-	unsigned long long first[RT_SHORT_FORMS];
-	__device__ FormTally()
-	{
-		for (int k = 0; k < RT_SHORT_FORMS; ++k)
-			first[k] = ~0ull;
-	}
-	__device__ void note(int form, bool differs, unsigned long long index)
-	{
-		if (differs) {
-			bad[form] += 1ull;
-			first[form] = index < first[form] ? index : first[form];
-		}
-	}
-	__device__ void flush(int form, DevShortForms &D) const
-	{
-		if (bad[form]) {
-			atomicAdd(&D.mismatches[form], bad[form]);
-			atomicMin(&D.first_index[form], first[form]);
-		}
-	}
-};
 
 // input `index` of the reciprocal enumeration: exponent slot (index >> 24), sign (bit 23), significand (bits 0-22)
 __host__ __device__ inline uint32_t short_forms_rcp_input(uint64_t index)
@@ -55,24 +28,25 @@ __host__ __device__ inline uint32_t short_forms_rcp_input(uint64_t index)
 	return ((uint32_t)(index >> 23) & 1u) << 31 | (uint32_t)(127 + e) << 23 | ((uint32_t)index & 0x007FFFFFu);
 }
 
+// (the forms' mismatch counts and first indices, by RT_SHORT_FORM_*; the inputs tested: reciprocals in slot 0, square roots in 1)
+using FormTally = Tally<RT_SHORT_FORMS>;
+constexpr uint64_t kShortFormsRcpInputs = (uint64_t)kShortFormsRcpExponentCount << 24, kShortFormsSqrtInputs = 1ull << 32;
+
 __global__ __launch_bounds__(256) void short_forms_rcp_kernel(DevShortForms D)
 {
 	FormTally T;
-	unsigned long long tested = 0;
-	const uint64_t total = (uint64_t)kShortFormsRcpExponentCount << 24;
-	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+	Tally<2> tested;
+	for_each_case(kShortFormsRcpInputs, [&](uint64_t i) {
 		const float d = __uint_as_float(short_forms_rcp_input(i));
 		const float want = 1.0f / d;
 		T.note(RT_SHORT_FORM_RCP_REFINED, !same_f32(lean_inv_gfx950(d), want), i);
 		const float r1 = lean_rcp_refined(d);
 		T.note(RT_SHORT_FORM_INV_ONE_PAIR, !same_f32(__builtin_fmaf(__builtin_fmaf(-d, r1, 1.0f), r1, r1), want), i);
 		T.note(RT_SHORT_FORM_INV_TWO_PAIRS, !same_f32(lean_inv(d), want), i);
-		++tested;
-	}
-	atomicAdd(&D.tested[0], tested);
-	T.flush(RT_SHORT_FORM_RCP_REFINED, D);
-	T.flush(RT_SHORT_FORM_INV_ONE_PAIR, D);
-	T.flush(RT_SHORT_FORM_INV_TWO_PAIRS, D);
+		tested.add(0);
+	});
+	tested.flush(D.tested);
+	T.flush(D.mismatches, D.first_index);
 }
 
 // every bit pattern of lean_sqrt's stated domain: all but the positives below 2^-96 (bits 1 .. 0x0F7FFFFF) and the negative
@@ -80,11 +54,12 @@ __global__ __launch_bounds__(256) void short_forms_rcp_kernel(DevShortForms D)
 __global__ __launch_bounds__(256) void short_forms_sqrt_kernel(DevShortForms D)
 {
 	FormTally T;
-	unsigned long long tested = 0, exact = 0, high = 0, low = 0, other = 0;
-	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (1ull << 32); i += (uint64_t)gridDim.x * blockDim.x) {
+	Tally<2> tested;
+	Tally<4> raw_is; // exact, high, low, other
+	for_each_case(kShortFormsSqrtInputs, [&](uint64_t i) {
 		const uint32_t bits = (uint32_t)i;
 		if ((bits >= 1u && bits < 0x0F800000u) || (bits > 0x80000000u && bits < 0x80800000u))
-			continue;
+			return;
 		const float x = __uint_as_float(bits);
 		const float want = sqrtf(x);
 		const float raw = __builtin_amdgcn_sqrtf(x);
@@ -93,19 +68,15 @@ __global__ __launch_bounds__(256) void short_forms_sqrt_kernel(DevShortForms D)
 		const uint32_t rb = __float_as_uint(raw), wb = __float_as_uint(want);
 		const bool is_exact = same_f32(raw, want);
 		const bool is_high = !is_exact && rb == wb + 1u, is_low = !is_exact && rb + 1u == wb; // (positive finite results: bits order as values)
-		exact += is_exact;
-		high += is_high;
-		low += is_low;
-		other += !(is_exact || is_high || is_low);
-		++tested;
-	}
-	atomicAdd(&D.tested[1], tested);
-	atomicAdd(&D.sqrt_raw[0], exact);
-	atomicAdd(&D.sqrt_raw[1], high);
-	atomicAdd(&D.sqrt_raw[2], low);
-	atomicAdd(&D.sqrt_raw[3], other);
-	T.flush(RT_SHORT_FORM_SQRT_RAW, D);
-	T.flush(RT_SHORT_FORM_SQRT_BOTH, D);
+		raw_is.add(0, is_exact);
+		raw_is.add(1, is_high);
+		raw_is.add(2, is_low);
+		raw_is.add(3, !(is_exact || is_high || is_low));
+		tested.add(1);
+	});
+	tested.flush(D.tested);
+	raw_is.flush(D.sqrt_raw);
+	T.flush(D.mismatches, D.first_index);
 }
 
 // the call sites on the caller's operands: each operand as the x, y or z component against tame others, and as all three
@@ -120,20 +91,18 @@ template <class F> __device__ __forceinline__ bool ray_new_differs(V3 dir)
 }
 __global__ __launch_bounds__(256) void short_forms_sites_kernel(DevShortForms D, const float *__restrict__ operands, uint64_t n_operands)
 {
-	unsigned long long tested = 0, bad_pair = 0, bad_full = 0;
-	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 4u * n_operands; i += (uint64_t)gridDim.x * blockDim.x) {
+	Tally<RT_SHORT_SITES> T;
+	Tally<1> tested;
+	for_each_case(4u * n_operands, [&](uint64_t i) {
 		const float x = operands[i >> 2];
 		const uint32_t shape = (uint32_t)i & 3u;
 		const V3 dir = shape == 0u ? v3(x, 0.75f, -0.5f) : (shape == 1u ? v3(-0.5f, x, 0.75f) : (shape == 2u ? v3(0.75f, -0.5f, x) : v3(x, x, x)));
-		bad_pair += ray_new_differs<FeatPair>(dir);
-		bad_full += ray_new_differs<FeatFull>(dir);
-		++tested;
-	}
-	atomicAdd(&D.site_tested[0], tested);
-	if (bad_pair)
-		atomicAdd(&D.site_mismatches[RT_SHORT_SITE_RAY_NEW_PAIR], bad_pair);
-	if (bad_full)
-		atomicAdd(&D.site_mismatches[RT_SHORT_SITE_RAY_NEW_FULL], bad_full);
+		T.add(RT_SHORT_SITE_RAY_NEW_PAIR, ray_new_differs<FeatPair>(dir));
+		T.add(RT_SHORT_SITE_RAY_NEW_FULL, ray_new_differs<FeatFull>(dir));
+		tested.add(0);
+	});
+	tested.flush(D.site_tested);
+	T.flush(D.site_mismatches);
 }
 
 // rt_selftest_pair_shadow: the two-sphere kernels' occlusion predicate for a ray without a limit (rt_intersect.h
@@ -141,8 +110,8 @@ __global__ __launch_bounds__(256) void short_forms_sites_kernel(DevShortForms D,
 // sphere_t(...) && t > 0 on the caller's cases: centre, radius, origin, direction -- the direction as given, not normalised
 __global__ __launch_bounds__(256) void pair_shadow_kernel(const float *__restrict__ cases, uint64_t n_cases, unsigned long long *counts)
 {
-	unsigned long long tested = 0, bad = 0, bad_asked = 0, asked = 0;
-	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_cases; i += (uint64_t)gridDim.x * blockDim.x) {
+	Tally<RT_PAIR_SHADOW_COUNTS> T;
+	for_each_case(n_cases, [&](uint64_t i) {
 		const float *c = cases + i * RT_PAIR_SHADOW_CASE_FLOATS;
 		const V3 center = v3(c[0], c[1], c[2]);
 		const float radius = c[3];
@@ -152,24 +121,16 @@ __global__ __launch_bounds__(256) void pair_shadow_kernel(const float *__restric
 		r.inv = r.shear = v3s(0.0f); // (no sphere test reads them)
 		float t;
 		const bool want = sphere_t(center, radius, r, t) && t > 0.0f;
-		bad += sphere_occludes_unlimited(center, radius, r) != want;
-		bad_asked += sphere_occludes_asked(center, radius, r) != want;
-		asked += sphere_shadow_signs(center, radius, r).ask;
-		++tested;
-	}
-	atomicAdd(&counts[RT_PAIR_SHADOW_TESTED], tested);
-	if (bad)
-		atomicAdd(&counts[RT_PAIR_SHADOW_MISMATCHES], bad);
-	if (bad_asked)
-		atomicAdd(&counts[RT_PAIR_SHADOW_ASKED_MISMATCHES], bad_asked);
-	if (asked)
-		atomicAdd(&counts[RT_PAIR_SHADOW_ASKED], asked);
+		T.add(RT_PAIR_SHADOW_MISMATCHES, sphere_occludes_unlimited(center, radius, r) != want);
+		T.add(RT_PAIR_SHADOW_ASKED_MISMATCHES, sphere_occludes_asked(center, radius, r) != want);
+		T.add(RT_PAIR_SHADOW_ASKED, sphere_shadow_signs(center, radius, r).ask);
+		T.add(RT_PAIR_SHADOW_TESTED);
+	});
+	T.flush(counts);
 }
 hipError_t launch_pair_shadow(hipStream_t stream, const float *cases, uint64_t n_cases, unsigned long long *counts)
 {
-	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_cases + 255u) / 256u, 2048u);
-	hipLaunchKernelGGL(pair_shadow_kernel, dim3(blocks), dim3(256), 0, stream, cases, n_cases, counts);
-	return hipGetLastError();
+	return launch_cases(pair_shadow_kernel, stream, n_cases, 2048u, cases, n_cases, counts);
 }
 
 // rt_selftest_pair_shadow_walk: trace_any's two-sphere arm AS THE RENDER KERNELS INSTANTIATE IT (FeatPair: sign step, state word,
@@ -181,10 +142,10 @@ struct FeatPairFullShadow : FeatPair {
 constexpr uint32_t kWalkSlot0 = 7u, kWalkSlot1 = 3u; // (any two distinct slots)
 __global__ __launch_bounds__(256) void pair_shadow_walk_kernel(const float *__restrict__ cases, uint64_t n_cases, unsigned long long *counts)
 {
-	unsigned long long tested = 0, bad = 0, asked = 0, asked_both = 0, asked_with_occluded = 0;
+	Tally<RT_PAIR_SHADOW_WALK_COUNTS> T;
 	const DevScene S = {}; // (the two-sphere arm reads neither the scene nor a stack)
 	const StackMem M = {};
-	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_cases; i += (uint64_t)gridDim.x * blockDim.x) {
+	for_each_case(n_cases, [&](uint64_t i) {
 		const float *c = cases + i * RT_PAIR_SHADOW_WALK_CASE_FLOATS;
 		DevPairScene ps = {};
 		for (int k = 0; k < 4; ++k) {
@@ -207,44 +168,35 @@ __global__ __launch_bounds__(256) void pair_shadow_walk_kernel(const float *__re
 		const float no_limit = __uint_as_float(0x7FC00000u);
 		const bool got = trace_any<FeatPair, false>(S, S, M, r, nullptr, no_limit, skip, ps);
 		const bool want = trace_any<FeatPairFullShadow, false>(S, S, M, r, nullptr, no_limit, skip, ps);
-		bad += got != want;
+		T.add(RT_PAIR_SHADOW_WALK_MISMATCHES, got != want);
 		// which lanes the sign step sends into the cold loop, and in what state: the arm's own rule, from its own parts
 		float tb;
 		const bool c0 = aabb_does_int(ps.c0min, ps.c0max, r, tb) && ps.slot0 != skip, c1 = aabb_does_int(ps.c1min, ps.c1max, r, tb) && ps.slot1 != skip;
 		const ShadowSigns s0 = sphere_shadow_signs(v3(c[0], c[1], c[2]), c[3], r), s1 = sphere_shadow_signs(v3(c[4], c[5], c[6]), c[7], r);
 		const bool occ0 = c0 && s0.occluded, ask0 = c0 && s0.ask;
 		const bool occ1 = !occ0 && c1 && s1.occluded, ask1 = !occ0 && c1 && s1.ask;
-		asked += ask0 || ask1;
-		asked_both += ask0 && ask1;
-		asked_with_occluded += (ask0 || ask1) && (occ0 || occ1);
-		++tested;
-	}
-	atomicAdd(&counts[RT_PAIR_SHADOW_WALK_TESTED], tested);
-	if (bad)
-		atomicAdd(&counts[RT_PAIR_SHADOW_WALK_MISMATCHES], bad);
-	if (asked)
-		atomicAdd(&counts[RT_PAIR_SHADOW_WALK_ASKED], asked);
-	if (asked_both)
-		atomicAdd(&counts[RT_PAIR_SHADOW_WALK_ASKED_BOTH], asked_both);
-	if (asked_with_occluded)
-		atomicAdd(&counts[RT_PAIR_SHADOW_WALK_ASKED_WITH_OCCLUDED], asked_with_occluded);
+		T.add(RT_PAIR_SHADOW_WALK_ASKED, ask0 || ask1);
+		T.add(RT_PAIR_SHADOW_WALK_ASKED_BOTH, ask0 && ask1);
+		T.add(RT_PAIR_SHADOW_WALK_ASKED_WITH_OCCLUDED, (ask0 || ask1) && (occ0 || occ1));
+		T.add(RT_PAIR_SHADOW_WALK_TESTED);
+	});
+	T.flush(counts);
 }
 hipError_t launch_pair_shadow_walk(hipStream_t stream, const float *cases, uint64_t n_cases, unsigned long long *counts)
 {
-	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_cases + 255u) / 256u, 2048u);
-	hipLaunchKernelGGL(pair_shadow_walk_kernel, dim3(blocks), dim3(256), 0, stream, cases, n_cases, counts);
-	return hipGetLastError();
+	return launch_cases(pair_shadow_walk_kernel, stream, n_cases, 2048u, cases, n_cases, counts);
 }
 
 // rt_selftest_div_forms, the enumeration: a work item is one denominator at one exponent pair against 2^kDivChunkBits consecutive
 // numerator significands; the refined reciprocal is formed once per item, as a shared-reciprocal site forms it
-constexpr uint32_t kDivChunkBits = 10;
+constexpr uint32_t kDivChunkBits = 10, kDivChunkShift = 23u - kDivChunkBits;
+__host__ __device__ inline uint64_t div_forms_items(const DevDivForms &D) { return ((uint64_t)D.n_exponent_pairs * D.n_denominators) << kDivChunkShift; }
 __global__ __launch_bounds__(256) void div_forms_kernel(DevDivForms D)
 {
-	unsigned long long tested = 0, bad_one = 0, bad_two = 0, first_one = ~0ull, first_two = ~0ull;
-	const uint32_t chunk_shift = 23u - kDivChunkBits;
-	const uint64_t items = ((uint64_t)D.n_exponent_pairs * D.n_denominators) << chunk_shift;
-	for (uint64_t item = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; item < items; item += (uint64_t)gridDim.x * blockDim.x) {
+	Tally<RT_DIV_FORMS> T;
+	Tally<1> tested;
+	const uint32_t chunk_shift = kDivChunkShift;
+	for_each_case(div_forms_items(D), [&](uint64_t item) {
 		const uint64_t pair_index = item >> chunk_shift; // exponent pair * n_denominators + denominator
 		const uint32_t chunk = (uint32_t)item & ((1u << chunk_shift) - 1u);
 		const uint32_t e = (uint32_t)(pair_index / D.n_denominators), j = (uint32_t)(pair_index - (uint64_t)e * D.n_denominators);
@@ -257,34 +209,15 @@ __global__ __launch_bounds__(256) void div_forms_kernel(DevDivForms D)
 			const float n = __uint_as_float(n_high | n_sig);
 			const float want = n / d;
 			const unsigned long long index = pair_index << 23 | n_sig;
-			if (!same_f32(lean_div_core_gfx950(n, d, r1), want)) {
-				bad_one += 1ull;
-				first_one = index < first_one ? index : first_one;
-			}
-			if (!same_f32(lean_div_core(n, d, r1), want)) {
-				bad_two += 1ull;
-				first_two = index < first_two ? index : first_two;
-			}
+			T.note(RT_DIV_FORM_ONE_PAIR, !same_f32(lean_div_core_gfx950(n, d, r1), want), index);
+			T.note(RT_DIV_FORM_TWO_PAIRS, !same_f32(lean_div_core(n, d, r1), want), index);
 		}
-		tested += 1ull << kDivChunkBits;
-	}
-	atomicAdd(&D.counts[kDivCountTested], tested);
-	if (bad_one) {
-		atomicAdd(&D.counts[kDivCountBad + RT_DIV_FORM_ONE_PAIR], bad_one);
-		atomicMin(&D.counts[kDivCountFirst + RT_DIV_FORM_ONE_PAIR], first_one);
-	}
-	if (bad_two) {
-		atomicAdd(&D.counts[kDivCountBad + RT_DIV_FORM_TWO_PAIRS], bad_two);
-		atomicMin(&D.counts[kDivCountFirst + RT_DIV_FORM_TWO_PAIRS], first_two);
-	}
+		tested.add(0, 1ull << kDivChunkBits);
+	});
+	tested.flush(D.counts + kDivCountTested);
+	T.flush(D.counts + kDivCountBad, D.counts + kDivCountFirst);
 }
-hipError_t launch_div_forms(hipStream_t stream, const DevDivForms &D)
-{
-	const uint64_t items = ((uint64_t)D.n_exponent_pairs * D.n_denominators) << (23u - kDivChunkBits);
-	const uint32_t blocks = (uint32_t)std::min<uint64_t>((items + 255u) / 256u, 4096u);
-	hipLaunchKernelGGL(div_forms_kernel, dim3(blocks), dim3(256), 0, stream, D);
-	return hipGetLastError();
-}
+hipError_t launch_div_forms(hipStream_t stream, const DevDivForms &D) { return launch_cases(div_forms_kernel, stream, div_forms_items(D), 4096u, D); }
 constexpr uint32_t div_form_bit(LeanDivForm f) { return 1u << (f == LeanDivForm::one_pair ? RT_DIV_FORM_ONE_PAIR : RT_DIV_FORM_TWO_PAIRS); }
 // from the switch the sites select by (rt_lean.h lean_div_form): only the two-sphere kernels have such sites
 uint32_t div_forms_in_use() { return div_form_bit(lean_div_form(true)); }
@@ -310,15 +243,15 @@ __device__ __forceinline__ bool div_fix_domain(float n, float d)
 }
 __global__ __launch_bounds__(256) void div_sites_kernel(const float *__restrict__ pairs, uint64_t n_pairs, unsigned long long *counts)
 {
-	unsigned long long tested = 0, in_domain = 0, bad_fix = 0, bad_fix3 = 0, bad_mis = 0, bad_atan2 = 0;
-	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_pairs; i += (uint64_t)gridDim.x * blockDim.x) {
+	Tally<kDivCounts> T; // (the site counters of it)
+	for_each_case(n_pairs, [&](uint64_t i) {
 		const float n = pairs[2u * i], d = pairs[2u * i + 1u];
 		if (div_fix_domain(n, d)) {
-			in_domain += 1ull;
-			bad_fix += !same_f32(lean_div_fix_for<true>(n, d), n / d);
+			T.add(kDivCountSiteInDomain);
+			T.add(kDivCountSiteBad + RT_DIV_SITE_FIX, !same_f32(lean_div_fix_for<true>(n, d), n / d));
 			// (a tame, a zero and an infinite neighbour share the reciprocal)
 			const V3 v = v3(n, 0.0f, -INFINITY);
-			bad_fix3 += !same_v3(lean_div3_fix_for<true>(v, d), div3_plain(v, d));
+			T.add(kDivCountSiteBad + RT_DIV_SITE_DIV3_FIX, !same_v3(lean_div3_fix_for<true>(v, d), div3_plain(v, d)));
 		}
 		// the light term: (n, d) as (m_pdf, l_pdf) and the other way round, then as a component of te under tame pdfs (the weight is
 		// 0.5 there, so 2 n reaches the quotient as n), alone and as all three
@@ -329,27 +262,17 @@ __global__ __launch_bounds__(256) void div_sites_kernel(const float *__restrict_
 		ok = ok && same_v3(mis_light_term_short(tx, one, 1.0f, 1.0f), mis_light_term_plain(tx, one, 1.0f, 1.0f));
 		ok = ok && same_v3(mis_light_term_short(tz, one, d, d), mis_light_term_plain(tz, one, d, d));
 		ok = ok && same_v3(mis_light_term_short(ta, v3(1.0f, d, -1.0f), 1.0f, 1.0f), mis_light_term_plain(ta, v3(1.0f, d, -1.0f), 1.0f, 1.0f));
-		bad_mis += !ok;
-		bad_atan2 += !(same_f32(lean_atan2_for<true>(n, d), lean_atan2(n, d)) && same_f32(lean_atan2_for<true>(d, n), lean_atan2(d, n)) &&
-		               same_f32(lean_atan2_for<true>(-n, d), rt_atan2f(-n, d)));
-		++tested;
-	}
-	atomicAdd(&counts[kDivCountSiteTested], tested);
-	atomicAdd(&counts[kDivCountSiteInDomain], in_domain);
-	if (bad_fix)
-		atomicAdd(&counts[kDivCountSiteBad + RT_DIV_SITE_FIX], bad_fix);
-	if (bad_fix3)
-		atomicAdd(&counts[kDivCountSiteBad + RT_DIV_SITE_DIV3_FIX], bad_fix3);
-	if (bad_mis)
-		atomicAdd(&counts[kDivCountSiteBad + RT_DIV_SITE_MIS_LIGHT_TERM], bad_mis);
-	if (bad_atan2)
-		atomicAdd(&counts[kDivCountSiteBad + RT_DIV_SITE_ATAN2], bad_atan2);
+		T.add(kDivCountSiteBad + RT_DIV_SITE_MIS_LIGHT_TERM, !ok);
+		T.add(kDivCountSiteBad + RT_DIV_SITE_ATAN2,
+		      !(same_f32(lean_atan2_for<true>(n, d), lean_atan2(n, d)) && same_f32(lean_atan2_for<true>(d, n), lean_atan2(d, n)) &&
+		        same_f32(lean_atan2_for<true>(-n, d), rt_atan2f(-n, d))));
+		T.add(kDivCountSiteTested);
+	});
+	T.flush(counts);
 }
 hipError_t launch_div_sites(hipStream_t stream, const float *operand_pairs, uint64_t n_pairs, unsigned long long *counts)
 {
-	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_pairs + 255u) / 256u, 2048u);
-	hipLaunchKernelGGL(div_sites_kernel, dim3(blocks), dim3(256), 0, stream, operand_pairs, n_pairs, counts);
-	return hipGetLastError();
+	return launch_cases(div_sites_kernel, stream, n_pairs, 2048u, operand_pairs, n_pairs, counts);
 }
 
 // rt_selftest_sky_pdf_forms: sky_pdf as the two-sphere kernels instantiate it and as every other kernel does, tables in global memory
@@ -367,11 +290,11 @@ __global__ __launch_bounds__(256) void sky_pdf_forms_kernel(const SkyPdfFormsArg
 	T.guide = A.S.sky.guide;
 	T.guide_k = A.S.sky.guide_k;
 	T.inv_res = nullptr; // (sky_pdf reads none of the verified reciprocals)
-	for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < A.m; j += (uint64_t)gridDim.x * blockDim.x) {
+	for_each_case(A.m, [&](uint64_t j) {
 		const V3 wi = v3(A.dirs[3 * j], A.dirs[3 * j + 1], A.dirs[3 * j + 2]);
 		A.out_pair[j] = sky_pdf<true>(A.S, T, wi);
 		A.out_default[j] = sky_pdf(A.S, T, wi);
-	}
+	});
 }
 hipError_t launch_sky_pdf_forms(hipStream_t stream, const DevScene &S, const float *dirs, uint64_t m, float *out_pair, float *out_default)
 {
@@ -381,9 +304,7 @@ hipError_t launch_sky_pdf_forms(hipStream_t stream, const DevScene &S, const flo
 	A.m = m;
 	A.out_pair = out_pair;
 	A.out_default = out_default;
-	const uint32_t blocks = (uint32_t)std::min<uint64_t>((m + 255u) / 256u, 2048u);
-	hipLaunchKernelGGL(sky_pdf_forms_kernel, dim3(blocks), dim3(256), 0, stream, A);
-	return hipGetLastError();
+	return launch_cases(sky_pdf_forms_kernel, stream, m, 2048u, A);
 }
 
 // rt_selftest_frame_forms: the scatter frame and Ray::new's normalisation as the two-sphere kernels' switches select them
@@ -396,34 +317,26 @@ __device__ __forceinline__ Coord pair_kernels_frame(V3 z)
 }
 __global__ __launch_bounds__(256) void frame_forms_kernel(const float *__restrict__ vectors, uint64_t n_vectors, unsigned long long *counts)
 {
-	unsigned long long tested = 0, bad_frame = 0, frame_short = 0, bad_ray = 0, ray_short = 0;
-	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vectors; i += (uint64_t)gridDim.x * blockDim.x) {
+	Tally<RT_FRAME_FORMS_COUNTS> T; // (RT_FRAME_FORMS_IN_USE stays zero: the host's to fill)
+	for_each_case(n_vectors, [&](uint64_t i) {
 		const V3 v = v3(vectors[3u * i], vectors[3u * i + 1u], vectors[3u * i + 2u]);
 		const Coord got = pair_kernels_frame(v), want = coord_from_z_plain(v);
-		bad_frame += !(same_v3(got.x, want.x) && same_v3(got.y, want.y) && same_v3(got.z, want.z));
+		T.add(RT_FRAME_FORMS_FRAME_MISMATCHES, !(same_v3(got.x, want.x) && same_v3(got.y, want.y) && same_v3(got.z, want.z)));
 		const float a = fabsf(v.x) > fabsf(v.y) ? v.x : v.y; // the frame's guard, from its own parts (rt_shade.h)
-		frame_short += frame_guard_(a, v.z, a * a + v.z * v.z);
+		T.add(RT_FRAME_FORMS_FRAME_SHORT, frame_guard_(a, v.z, a * a + v.z * v.z));
 		const Ray r = ray_new<FeatPair>(v3s(0.0f), v), p = ray_new_plain(v3s(0.0f), v);
-		bad_ray += !(same_v3(r.d, p.d) && same_v3(r.inv, p.inv));
+		T.add(RT_FRAME_FORMS_RAY_MISMATCHES, !(same_v3(r.d, p.d) && same_v3(r.inv, p.inv)));
 		const float m2 = dot(v, v); // ray_new's guard (rt_intersect.h)
-		ray_short += fminf(fminf(fabsf(v.x), fabsf(v.y)), fabsf(v.z)) >= 0x1p-60f && m2 >= 0x1p-40f && m2 <= 0x1p40f;
-		++tested;
-	}
-	atomicAdd(&counts[RT_FRAME_FORMS_TESTED], tested);
-	atomicAdd(&counts[RT_FRAME_FORMS_FRAME_SHORT], frame_short);
-	atomicAdd(&counts[RT_FRAME_FORMS_FRAME_PLAIN], tested - frame_short);
-	atomicAdd(&counts[RT_FRAME_FORMS_RAY_SHORT], ray_short);
-	atomicAdd(&counts[RT_FRAME_FORMS_RAY_PLAIN], tested - ray_short);
-	if (bad_frame)
-		atomicAdd(&counts[RT_FRAME_FORMS_FRAME_MISMATCHES], bad_frame);
-	if (bad_ray)
-		atomicAdd(&counts[RT_FRAME_FORMS_RAY_MISMATCHES], bad_ray);
+		T.add(RT_FRAME_FORMS_RAY_SHORT, fminf(fminf(fabsf(v.x), fabsf(v.y)), fabsf(v.z)) >= 0x1p-60f && m2 >= 0x1p-40f && m2 <= 0x1p40f);
+		T.add(RT_FRAME_FORMS_TESTED);
+	});
+	T.add(RT_FRAME_FORMS_FRAME_PLAIN, T.n[RT_FRAME_FORMS_TESTED] - T.n[RT_FRAME_FORMS_FRAME_SHORT]);
+	T.add(RT_FRAME_FORMS_RAY_PLAIN, T.n[RT_FRAME_FORMS_TESTED] - T.n[RT_FRAME_FORMS_RAY_SHORT]);
+	T.flush(counts);
 }
 hipError_t launch_frame_forms(hipStream_t stream, const float *vectors, uint64_t n_vectors, unsigned long long *counts)
 {
-	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_vectors + 255u) / 256u, 2048u);
-	hipLaunchKernelGGL(frame_forms_kernel, dim3(blocks), dim3(256), 0, stream, vectors, n_vectors, counts);
-	return hipGetLastError();
+	return launch_cases(frame_forms_kernel, stream, n_vectors, 2048u, vectors, n_vectors, counts);
 }
 uint32_t frame_forms_in_use()
 {
@@ -460,8 +373,8 @@ __global__ __launch_bounds__(256) void gen_keys_kernel(const GenKeysSelftestArgs
 	constexpr int lead = lean_gen_keys_lead(true);
 	const uint64_t seed = A->seed, n_cases = A->n_cases;
 	const uint32_t *const cases = A->cases;
-	unsigned long long tested = 0, bad_state = 0, bad_draw = 0, bad_item_state = 0, bad_item_draw = 0, zero_blocks = 0;
-	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_cases; i += (uint64_t)gridDim.x * blockDim.x) {
+	Tally<RT_GEN_KEYS_COUNTS> T; // (RT_GEN_KEYS_IN_USE stays zero: the host's to fill)
+	for_each_case(n_cases, [&](uint64_t i) {
 		const uint32_t pixel = cases[4u * i], sample_i = cases[4u * i + 1u];
 		const uint64_t sample_begin = ((uint64_t)cases[4u * i + 3u] << 32) | cases[4u * i + 2u];
 		const uint64_t sample = sample_begin + sample_i; // (wraps, as GEN's sum does)
@@ -478,25 +391,14 @@ __global__ __launch_bounds__(256) void gen_keys_kernel(const GenKeysSelftestArgs
 #endif
 		rng_seed_keyed<lead>(&item, &A->keys, hi0_item, lo0_item, sample);
 		bool draws;
-		bad_state += !same_stream(keyed, want, draws);
-		bad_draw += draws;
-		bad_item_state += !same_stream(item, want, draws);
-		bad_item_draw += draws;
-		zero_blocks += want.s0 == 1u && (want.s1 | want.s2 | want.s3) == 0u; // (the guard's state; a block (1, 0, 0, 0) itself counts too)
-		++tested;
-	}
-	unsigned long long *const counts = A->counts;
-	atomicAdd(&counts[RT_GEN_KEYS_TESTED], tested);
-	if (bad_state)
-		atomicAdd(&counts[RT_GEN_KEYS_STATE_MISMATCHES], bad_state);
-	if (bad_draw)
-		atomicAdd(&counts[RT_GEN_KEYS_DRAW_MISMATCHES], bad_draw);
-	if (bad_item_state)
-		atomicAdd(&counts[RT_GEN_KEYS_ITEM_STATE_MISMATCHES], bad_item_state);
-	if (bad_item_draw)
-		atomicAdd(&counts[RT_GEN_KEYS_ITEM_DRAW_MISMATCHES], bad_item_draw);
-	if (zero_blocks)
-		atomicAdd(&counts[RT_GEN_KEYS_ZERO_BLOCKS], zero_blocks);
+		T.add(RT_GEN_KEYS_STATE_MISMATCHES, !same_stream(keyed, want, draws));
+		T.add(RT_GEN_KEYS_DRAW_MISMATCHES, draws);
+		T.add(RT_GEN_KEYS_ITEM_STATE_MISMATCHES, !same_stream(item, want, draws));
+		T.add(RT_GEN_KEYS_ITEM_DRAW_MISMATCHES, draws);
+		T.add(RT_GEN_KEYS_ZERO_BLOCKS, want.s0 == 1u && (want.s1 | want.s2 | want.s3) == 0u); // (the guard's state; a block (1, 0, 0, 0) itself counts too)
+		T.add(RT_GEN_KEYS_TESTED);
+	});
+	T.flush(A->counts);
 }
 hipError_t launch_gen_keys(hipStream_t stream, uint64_t seed, const uint32_t *cases, uint64_t n_cases, unsigned long long *counts)
 {
@@ -506,9 +408,7 @@ hipError_t launch_gen_keys(hipStream_t stream, uint64_t seed, const uint32_t *ca
 	A.cases = cases;
 	A.n_cases = n_cases;
 	A.counts = counts;
-	const uint32_t blocks = (uint32_t)std::min<uint64_t>((n_cases + 255u) / 256u, 2048u);
-	hipLaunchKernelGGL(gen_keys_kernel, dim3(blocks), dim3(256), 0, stream, A);
-	return hipGetLastError();
+	return launch_cases(gen_keys_kernel, stream, n_cases, 2048u, A);
 }
 uint32_t gen_keys_in_use()
 {
@@ -531,16 +431,11 @@ uint32_t short_forms_in_use()
 
 hipError_t launch_short_forms(hipStream_t stream, const DevShortForms &D, const float *operands, uint64_t n_operands)
 {
-	if (operands) {
-		const uint32_t blocks = (uint32_t)std::min<uint64_t>((4u * n_operands + 255u) / 256u, 2048u);
-		hipLaunchKernelGGL(short_forms_sites_kernel, dim3(blocks), dim3(256), 0, stream, D, operands, n_operands);
-		return hipGetLastError();
-	}
-	hipLaunchKernelGGL(short_forms_rcp_kernel, dim3(2048), dim3(256), 0, stream, D);
-	if (hipError_t e = hipGetLastError(); e != hipSuccess)
+	if (operands)
+		return launch_cases(short_forms_sites_kernel, stream, 4u * n_operands, 2048u, D, operands, n_operands);
+	if (hipError_t e = launch_cases(short_forms_rcp_kernel, stream, kShortFormsRcpInputs, 2048u, D); e != hipSuccess)
 		return e;
-	hipLaunchKernelGGL(short_forms_sqrt_kernel, dim3(2048), dim3(256), 0, stream, D);
-	return hipGetLastError();
+	return launch_cases(short_forms_sqrt_kernel, stream, kShortFormsSqrtInputs, 2048u, D);
 }
 
 } // namespace rt

@@ -163,6 +163,26 @@ def _f3(v):
     return (C.c_float * 3)(*[float(np.float32(x)) for x in v])
 
 
+def _in_use(names, mask):
+    """the names (an abi *_FORM_NAMES table) whose bit a self-test's `in_use` word has set"""
+    return [n for k, n in enumerate(names) if mask >> k & 1]
+
+
+def _selftest_cases(test, cases, device, *lead):
+    """{count name: value} of the self-test `test` of abi.SELFTEST_CASE_TABLES on `cases` (n, width); `lead`: what the entry point
+    takes between the device and the cases; "in_use" comes back as the names of its bits"""
+    symbol, ctype, width, what, names, forms = abi.SELFTEST_CASE_TABLES[test]
+    cases = np.ascontiguousarray(cases, dtype=np.dtype(ctype))
+    if cases.ndim != 2 or cases.shape[1] != width:
+        raise ValueError(f"{what} must be (n, {width}), got {cases.shape}")
+    out = (C.c_uint64 * len(names))()
+    _check(getattr(lib(), symbol)(C.c_int(device), *lead, _p(cases, ctype), C.c_uint64(cases.shape[0]), out))
+    res = dict(zip(names, (int(x) for x in out)))
+    if forms is not None:
+        res["in_use"] = _in_use(forms, res["in_use"])
+    return res
+
+
 def rccl_probe():
     """(usable, note): which RCCL a multi-device scene would bind (rt_rccl_probe; touches no GPU)"""
     usable, note = C.c_int(), C.create_string_buffer(512)
@@ -193,7 +213,7 @@ def selftest_short_forms(device=0, operands=None):
         forms = {name: (int(f.tested), int(f.mismatches), int(f.first_mismatch) if f.mismatches else None)
                  for name, f in zip(abi.SHORT_FORM_NAMES, res.form)}
         raw = {k: int(getattr(res, "sqrt_raw_" + k)) for k in ("exact", "high", "low", "other")}
-        return {"forms": forms, "sqrt_raw": raw, "in_use": [n for k, n in enumerate(abi.SHORT_FORM_NAMES) if res.in_use >> k & 1]}
+        return {"forms": forms, "sqrt_raw": raw, "in_use": _in_use(abi.SHORT_FORM_NAMES, res.in_use)}
     ops = np.ascontiguousarray(operands, dtype=np.float32).ravel()
     _check(lib().rt_selftest_short_forms(C.c_int(device), _p(ops, C.c_float), C.c_uint64(ops.size), C.byref(res)))
     return {"sites": dict(zip(abi.SHORT_SITE_NAMES, (int(x) for x in res.site_mismatches))), "tested": int(res.site_tested)}
@@ -225,7 +245,7 @@ def selftest_div_forms(denominators=None, exponents=((0, 0),), first_denominator
     _check(lib().rt_selftest_div_forms(C.c_int(device), C.byref(sl), None, C.c_uint64(0), C.byref(res)))
     forms = {name: (int(res.mismatches[k]), (int(res.first_numerator[k]), int(res.first_denominator[k])) if res.mismatches[k] else None)
              for k, name in enumerate(abi.DIV_FORM_NAMES)}
-    return {"tested": int(res.tested), "forms": forms, "in_use": [n for k, n in enumerate(abi.DIV_FORM_NAMES) if res.in_use >> k & 1]}
+    return {"tested": int(res.tested), "forms": forms, "in_use": _in_use(abi.DIV_FORM_NAMES, res.in_use)}
 
 
 def selftest_sky_pdf_forms(scene, dirs):
@@ -244,14 +264,7 @@ def selftest_frame_forms(vectors, device=0):
     on the GPU: {"tested", "frame_mismatches", "frame_short", "frame_plain", "ray_mismatches", "ray_short", "ray_plain"} (short / plain:
     vectors that passed / failed the site's guard) and "in_use": names of the short forms the kernels' switches select.  Both
     mismatch counts must be zero."""
-    vectors = np.ascontiguousarray(vectors, dtype=np.float32)
-    if vectors.ndim != 2 or vectors.shape[1] != 3:
-        raise ValueError(f"vectors must be (n, 3), got {vectors.shape}")
-    out = (C.c_uint64 * len(abi.FRAME_FORMS_COUNT_NAMES))()
-    _check(lib().rt_selftest_frame_forms(C.c_int(device), _p(vectors, C.c_float), C.c_uint64(vectors.shape[0]), out))
-    res = dict(zip(abi.FRAME_FORMS_COUNT_NAMES, (int(x) for x in out)))
-    res["in_use"] = [n for k, n in enumerate(abi.FRAME_FORM_NAMES) if res["in_use"] >> k & 1]
-    return res
+    return _selftest_cases("frame_forms", vectors, device)
 
 
 def philox_round_keys(seed):
@@ -267,38 +280,21 @@ def selftest_gen_keys(seed, cases, device=0):
     from the host's key table of `seed`, without and with the pixel's product formed ahead, next to rt_rng_seed: {"tested",
     "state_mismatches", "draw_mismatches", "item_state_mismatches", "item_draw_mismatches", "zero_blocks"} and "in_use": names of
     the forms the render kernels' switches select.  The four mismatch counts must be zero."""
-    cases = np.ascontiguousarray(cases, dtype=np.uint32)
-    if cases.ndim != 2 or cases.shape[1] != abi.GEN_KEYS_CASE_WORDS:
-        raise ValueError(f"cases must be (n, {abi.GEN_KEYS_CASE_WORDS}), got {cases.shape}")
-    out = (C.c_uint64 * len(abi.GEN_KEYS_COUNT_NAMES))()
-    _check(lib().rt_selftest_gen_keys(C.c_int(device), C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), _p(cases, C.c_uint32), C.c_uint64(cases.shape[0]), out))
-    res = dict(zip(abi.GEN_KEYS_COUNT_NAMES, (int(x) for x in out)))
-    res["in_use"] = [n for k, n in enumerate(abi.GEN_KEYS_FORM_NAMES) if res["in_use"] >> k & 1]
-    return res
+    return _selftest_cases("gen_keys", cases, device, C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF))
 
 
 def selftest_pair_shadow(cases, device=0):
     """rt_selftest_pair_shadow: cases (n, 10) f32 -- centre, radius, ray origin, ray direction (as given) -- through the two-sphere
     kernels' occlusion predicate for a ray without a limit and through Sphere::get_int's `hit && t > 0`, on the GPU:
     {"tested", "mismatches", "asked_mismatches", "asked"}.  Both mismatch counts must be zero."""
-    cases = np.ascontiguousarray(cases, dtype=np.float32)
-    if cases.ndim != 2 or cases.shape[1] != abi.PAIR_SHADOW_CASE_FLOATS:
-        raise ValueError(f"cases must be (n, {abi.PAIR_SHADOW_CASE_FLOATS}), got {cases.shape}")
-    out = (C.c_uint64 * len(abi.PAIR_SHADOW_COUNT_NAMES))()
-    _check(lib().rt_selftest_pair_shadow(C.c_int(device), _p(cases, C.c_float), C.c_uint64(cases.shape[0]), out))
-    return dict(zip(abi.PAIR_SHADOW_COUNT_NAMES, (int(x) for x in out)))
+    return _selftest_cases("pair_shadow", cases, device)
 
 
 def selftest_pair_shadow_walk(cases, device=0):
     """rt_selftest_pair_shadow_walk: cases (n, 16) f32 -- first sphere (centre, radius), second sphere, ray origin, ray direction,
     skip (0 none, 1 first, 2 second), one unused -- through the two-sphere kernels' whole shadow arm and through the same arm with
     the full test of every candidate, on the GPU: {"tested", "mismatches", "asked", "asked_both", "asked_with_occluded"}."""
-    cases = np.ascontiguousarray(cases, dtype=np.float32)
-    if cases.ndim != 2 or cases.shape[1] != abi.PAIR_SHADOW_WALK_CASE_FLOATS:
-        raise ValueError(f"cases must be (n, {abi.PAIR_SHADOW_WALK_CASE_FLOATS}), got {cases.shape}")
-    out = (C.c_uint64 * len(abi.PAIR_SHADOW_WALK_COUNT_NAMES))()
-    _check(lib().rt_selftest_pair_shadow_walk(C.c_int(device), _p(cases, C.c_float), C.c_uint64(cases.shape[0]), out))
-    return dict(zip(abi.PAIR_SHADOW_WALK_COUNT_NAMES, (int(x) for x in out)))
+    return _selftest_cases("pair_shadow_walk", cases, device)
 
 
 def selftest_pair_primary(scene, origin):

@@ -7,23 +7,9 @@
 // `hipcc --cuda-host-only -ffp-contract=off -fsanitize=address,undefined`; the device's instructions are compared by the GPU test.
 // Prints one line per operand set: "<name> <quotients> <mismatches of the one-pair sequence> <mismatches of q0 alone>".
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
-#include <vector>
+#include <cstdlib>
+#include "check_common.h"
 
-static float from_bits(uint32_t b)
-{
-	float f;
-	std::memcpy(&f, &b, sizeof f);
-	return f;
-}
-static uint32_t bits_of(float f)
-{
-	uint32_t b;
-	std::memcpy(&b, &f, sizeof b);
-	return b;
-}
 static float one_pair(float n, float d, float r)
 {
 	const float q0 = n * r;
@@ -41,16 +27,6 @@ struct Tally {
 	}
 	void print(const char *name) const { std::printf("%s %llu %llu %llu\n", name, n, bad, bad_q0); }
 };
-// one 64-bit LCG step and a mix, seeded; enough for operands
-static uint64_t next_u64(uint64_t &s)
-{
-	s = s * 6364136223846793005ull + 1442695040888963407ull;
-	uint64_t z = s;
-	z ^= z >> 33;
-	z *= 0xff51afd7ed558ccdull;
-	z ^= z >> 33;
-	return z;
-}
 
 int main(int argc, char **argv)
 {
@@ -60,16 +36,16 @@ int main(int argc, char **argv)
 		dens.push_back((uint32_t)std::strtoul(argv[k], nullptr, 16) & 0x007FFFFFu);
 	Tally listed;
 	for (uint32_t d_sig : dens) {
-		const float den = from_bits(127u << 23 | d_sig);
+		const float den = f_of(127u << 23 | d_sig);
 		for (uint32_t n_sig = 0; n_sig < (1u << 23); ++n_sig)
-			listed.run(from_bits(127u << 23 | n_sig), den);
+			listed.run(f_of(127u << 23 | n_sig), den);
 	}
 	listed.print("listed");
 	Tally random;
 	uint64_t s = 20240607ull;
 	for (int k = 0; k < 10000000; ++k) {
 		const uint64_t z = next_u64(s);
-		random.run(from_bits(127u << 23 | ((uint32_t)z & 0x007FFFFFu)), from_bits(127u << 23 | ((uint32_t)(z >> 32) & 0x007FFFFFu)));
+		random.run(f_of(127u << 23 | ((uint32_t)z & 0x007FFFFFu)), f_of(127u << 23 | ((uint32_t)(z >> 32) & 0x007FFFFFu)));
 	}
 	random.print("random");
 	return 0;

@@ -8,30 +8,12 @@
 // self-test to run the same operands.
 // Prints one line per operand set: "<name> <vectors> <frames that differ> <vectors that pass the guard> <vectors that fail it>".
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstring>
 #include <limits>
-#include <vector>
 #include "../../raytracing-rust_amd/csrc/rt_shade.h"
+#include "check_common.h"
 
 using rt::Coord;
 using rt::V3;
-
-static uint32_t bits_of(float f)
-{
-	uint32_t b;
-	std::memcpy(&b, &f, sizeof b);
-	return b;
-}
-static float f_of(uint32_t u)
-{
-	float f;
-	std::memcpy(&f, &u, sizeof f);
-	return f;
-}
-static bool same_f32(float a, float b) { return bits_of(a) == bits_of(b) || (a != a && b != b); } // any NaN equals any NaN
-static bool same_v3(V3 a, V3 b) { return same_f32(a.x, b.x) && same_f32(a.y, b.y) && same_f32(a.z, b.z); }
 
 struct Tally {
 	unsigned long long n = 0, bad = 0, pass = 0;
@@ -51,19 +33,6 @@ struct Tally {
 	}
 	void print(const char *name) const { std::printf("%s %llu %llu %llu %llu\n", name, n, bad, pass, n - pass); }
 };
-
-// one 64-bit LCG step and a mix, seeded; enough for operands
-static uint64_t g_state = 0x9E3779B97F4A7C15ull;
-static inline uint32_t next_u32()
-{
-	g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-	uint64_t x = g_state;
-	x ^= x >> 33;
-	x *= 0xFF51AFD7ED558CCDull;
-	x ^= x >> 33;
-	return (uint32_t)(x >> 16);
-}
-static inline float signed_unit() { return 2.0f * ((float)(next_u32() >> 8) * 0x1p-24f) - 1.0f; } // [-1, 1)
 
 int main(int argc, char **argv)
 {
@@ -98,12 +67,5 @@ int main(int argc, char **argv)
 			for (float z : values)
 				grid.run(rt::v3(x, y, z));
 	grid.print("grid");
-	if (grid_only) {
-		std::FILE *f = std::fopen(argv[1], "wb");
-		if (!f || std::fwrite(kept.data(), sizeof(float), kept.size(), f) != kept.size() || std::fclose(f) != 0) {
-			std::fprintf(stderr, "cannot write %s\n", argv[1]);
-			return 1;
-		}
-	}
-	return 0;
+	return grid_only ? write_cases(argv[1], kept) : 0;
 }

@@ -4,24 +4,13 @@
 // instructions are compared by tests/test_gpu_gen_keys.py.  Built by tests/test_gen_keys_host.py with
 // `hipcc --cuda-host-only -fsanitize=address,undefined`.
 // Prints one line per check: "<name> <cases> <mismatches>", and "zero_block <cases> <mismatches> <guard states seen>".
-#include <cstdint>
-#include <cstdio>
-#include <vector>
 #include "../../raytracing-rust_amd/csrc/rt_gen_keys.h"
+#include "check_common.h"
 
 // what rt_philox4x32_10 xors in at round r, restated without its loop: the seed's word plus r times the Weyl constant, mod 2^32
 static uint32_t walked_key(uint32_t word, uint32_t weyl, int r) { return (uint32_t)(((uint64_t)word + (uint64_t)r * weyl) & 0xFFFFFFFFull); }
 
-static uint64_t g_state = 0x9E3779B97F4A7C15ull;
-static uint64_t next_u64()
-{
-	g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-	uint64_t x = g_state;
-	x ^= x >> 33;
-	x *= 0xFF51AFD7ED558CCDull;
-	x ^= x >> 33;
-	return x;
-}
+static uint64_t next_u64() { return next_u64(g_state); }
 
 static bool same(const rt_rng &a, const rt_rng &b) { return a.s0 == b.s0 && a.s1 == b.s1 && a.s2 == b.s2 && a.s3 == b.s3; }
 static bool same_draws(rt_rng a, rt_rng b)

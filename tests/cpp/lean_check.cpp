@@ -9,10 +9,8 @@
 #include <vector>
 #include <atomic>
 #include "../../raytracing-rust_amd/csrc/rt_lean.h"
+#include "check_common.h"
 
-static inline float f_of(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
-static inline uint32_t u_of(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
-static inline bool same(float a, float b) { return u_of(a) == u_of(b) || (a != a && b != b); }
 
 template <class Fn> static uint64_t par_range(uint32_t lo, uint32_t hi_inclusive, uint32_t stride, Fn fn)
 {
@@ -36,14 +34,14 @@ int main(int argc, char **argv)
 	const uint32_t stride = argc > 1 ? (uint32_t)atoi(argv[1]) : 1u; // 1 = exhaustive
 	// sin + cos: every float in [0, 2^22] and its negative
 	{
-		const uint32_t hi = u_of(4194304.0f);
+		const uint32_t hi = bits_of(4194304.0f);
 		const uint64_t bad = par_range(0u, hi, stride, [](uint32_t u) {
 			bool ok = true;
 			for (int sgn = 0; sgn < 2; ++sgn) {
 				const float x = f_of(u | (sgn ? 0x80000000u : 0u));
 				float s, c;
 				rt::lean_sincos(x, s, c);
-				ok = ok && same(s, rt_sinf(x)) && same(c, rt_cosf(x));
+				ok = ok && same_f32(s, rt_sinf(x)) && same_f32(c, rt_cosf(x));
 			}
 			return ok;
 		});
@@ -53,7 +51,7 @@ int main(int argc, char **argv)
 	{
 		const uint64_t bad = par_range(0u, 0xFFFFFFFFu, stride, [](uint32_t u) {
 			const float x = f_of(u);
-			return same(rt::lean_acos(x), rt_acosf(x));
+			return same_f32(rt::lean_acos(x), rt_acosf(x));
 		});
 		std::printf("acos %llu %llu\n", (unsigned long long)(0x100000000ull / stride), (unsigned long long)bad);
 	}
@@ -72,22 +70,22 @@ int main(int argc, char **argv)
 			bool ok = true;
 			for (int s = 0; s < 4; ++s) {
 				const float y = (s & 1) ? -a : a, x = (s & 2) ? -b : b;
-				ok = ok && same(rt::lean_atan2_portable(y, x), rt_atan2f(y, x));
+				ok = ok && same_f32(rt::lean_atan2_portable(y, x), rt_atan2f(y, x));
 			}
 			return ok;
 		});
 		std::printf("atan2_grid %llu %llu\n", (unsigned long long)(4ull * n * n), (unsigned long long)bad);
 		// ... and ratios swept finely through the octant boundary and the whole of [0, 1]: y = t * x for every float t in [2^-30, 1]
-		const uint64_t bad2 = par_range(u_of(0x1p-30f), u_of(1.0f), stride * 7u, [](uint32_t u) {
+		const uint64_t bad2 = par_range(bits_of(0x1p-30f), bits_of(1.0f), stride * 7u, [](uint32_t u) {
 			const float t = f_of(u);
 			bool ok = true;
 			for (float x : {1.0f, 3.0f, 0.37f, 1.0e10f}) {
 				const float y = t * x;
-				ok = ok && same(rt::lean_atan2_portable(y, x), rt_atan2f(y, x)) && same(rt::lean_atan2_portable(x, -y), rt_atan2f(x, -y));
+				ok = ok && same_f32(rt::lean_atan2_portable(y, x), rt_atan2f(y, x)) && same_f32(rt::lean_atan2_portable(x, -y), rt_atan2f(x, -y));
 			}
 			return ok;
 		});
-		std::printf("atan2_ratio %llu %llu\n", (unsigned long long)(8ull * ((u_of(1.0f) - u_of(0x1p-30f)) / (stride * 7u) + 1)), (unsigned long long)bad2);
+		std::printf("atan2_ratio %llu %llu\n", (unsigned long long)(8ull * ((bits_of(1.0f) - bits_of(0x1p-30f)) / (stride * 7u) + 1)), (unsigned long long)bad2);
 	}
 	return 0;
 }

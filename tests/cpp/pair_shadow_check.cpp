@@ -6,12 +6,9 @@
 // origin, direction), for the device self-test to run the same operands (tests/test_gpu_pair_shadow.py).
 // Prints one line per operand set: "<name> <cases> <mismatches> <mismatches of the full test's form> <cases the signs could not settle>".
 #include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <cstdint>
 #include <limits>
-#include <vector>
 #include "../../raytracing-rust_amd/csrc/rt_intersect.h"
+#include "check_common.h"
 
 using rt::Ray;
 using rt::V3;
@@ -36,21 +33,6 @@ struct Tally {
 	}
 	void print(const char *name) const { std::printf("%s %llu %llu %llu %llu\n", name, n, bad, bad_asked, asked); }
 };
-
-// xoshiro-free: one 64-bit LCG step and a mix, seeded; enough for operands
-static uint64_t g_state = 0x9E3779B97F4A7C15ull;
-static inline uint32_t next_u32()
-{
-	g_state = g_state * 6364136223846793005ull + 1442695040888963407ull;
-	uint64_t x = g_state;
-	x ^= x >> 33;
-	x *= 0xFF51AFD7ED558CCDull;
-	x ^= x >> 33;
-	return (uint32_t)(x >> 16);
-}
-static inline float unit() { return (float)(next_u32() >> 8) * 0x1p-24f; }       // [0, 1)
-static inline float signed_unit() { return 2.0f * unit() - 1.0f; }               // [-1, 1)
-static inline float f_of(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
 
 int main(int argc, char **argv)
 {
@@ -126,12 +108,5 @@ int main(int argc, char **argv)
 				grid.run(rt::v3s(0.0f), rad, rt::v3(o, back, 0.0f), -yhat);
 			}
 	grid.print("grid");
-	if (grid_only) {
-		std::FILE *f = std::fopen(argv[1], "wb");
-		if (!f || std::fwrite(cases.data(), sizeof(float), cases.size(), f) != cases.size() || std::fclose(f) != 0) {
-			std::fprintf(stderr, "cannot write %s\n", argv[1]);
-			return 1;
-		}
-	}
-	return 0;
+	return grid_only ? write_cases(argv[1], cases) : 0;
 }

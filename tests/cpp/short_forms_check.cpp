@@ -8,10 +8,8 @@
 #include <cstring>
 #include <cstdint>
 #include "../../raytracing-rust_amd/csrc/rt_lean.h"
+#include "check_common.h"
 
-static inline float f_of(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
-static inline uint32_t u_of(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
-static inline bool same(float a, float b) { return u_of(a) == u_of(b) || (a != a && b != b); }
 
 int main()
 {
@@ -19,9 +17,9 @@ int main()
 	unsigned long long n = 0, bad_inv = 0, bad_inv_short = 0, bad_sqrt = 0;
 	for (uint64_t u = 0; u < (1ull << 32); u += stride) {
 		const float x = f_of((uint32_t)u);
-		bad_inv += !same(rt::lean_inv(x), 1.0f / x);
-		bad_inv_short += !same(rt::lean_inv_gfx950(x), 1.0f / x);
-		bad_sqrt += !same(rt::lean_sqrt(x), std::sqrt(x));
+		bad_inv += !same_f32(rt::lean_inv(x), 1.0f / x);
+		bad_inv_short += !same_f32(rt::lean_inv_gfx950(x), 1.0f / x);
+		bad_sqrt += !same_f32(rt::lean_sqrt(x), std::sqrt(x));
 		++n;
 	}
 	std::printf("lean_inv %llu %llu\n", n, bad_inv);

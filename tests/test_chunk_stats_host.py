@@ -5,29 +5,20 @@ accumulate and with the accumulation inside adaptive_checker.adaptive by bit pat
 operators are the plain IEEE ones, so this holds the arithmetic AS WRITTEN to the Python; what gfx950 computes with it the GPU suites
 compare (test_gpu_noise.py, test_gpu_adaptive.py, test_gpu_adaptive_loop.py, test_gpu_robust.py).  A stand-alone program, its host
 code built with AddressSanitizer and UBSan."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import adaptive_checker as A
+import host_check
 import noise_checker as N
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 F32 = np.float32
 H, W = 12, 25  # 300 pixels
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    assert os.path.exists(HIPCC), "hipcc is what builds this project: no build, no test"
-    path = str(tmp_path_factory.mktemp("chunk_stats") / "chunk_stats_check")
-    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "-O2", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-o", path, os.path.join(ROOT, "tests", "cpp", "chunk_stats_check.cpp")], check=True)
-    return path
+    return host_check.build("chunk_stats_check", tmp_path_factory.mktemp("chunk_stats"), sanitize=True)
 
 
 def same_bits(got, want):
@@ -47,7 +38,7 @@ def run_stats(exe, tmp_path, batch_sums, spp, albedo, masks=None, keep_state=Tru
             f.write(np.ascontiguousarray(sums, F32).tobytes())
             f.write(N.combine(sums, spp).astype(F32).tobytes())  # this render's mean, as the combine wrote it
             f.write((np.ones((h, w), np.uint32) if masks is None else masks[b].astype(np.uint32)).tobytes())
-    subprocess.run([exe, "stats", str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], check=True, timeout=120)
+    host_check.run(exe, "stats", tmp_path / "in.bin", tmp_path / "out.bin", timeout=120)
     out = np.fromfile(tmp_path / "out.bin", F32).reshape(len(batch_sums), 7, h, w)
     return [(o[0], o[1], o[2:5].reshape(h, w, 3), o[5], o[6]) for o in out]  # (out_mean is [pixel][3]: 3 * h * w floats in a row)
 
@@ -124,7 +115,7 @@ def test_per_pixel_batch_counts_are_the_adaptive_checkers_bits(exe, tmp_path):
 
 def test_both_maps_to_a_pixel(exe, tmp_path):
     w, h, tile_w, tile_h = 13, 11, 4, 16
-    subprocess.run([exe, "maps", str(w), str(h), str(tile_w), str(tile_h), str(tmp_path / "maps.bin")], check=True, timeout=120)
+    host_check.run(exe, "maps", w, h, tile_w, tile_h, tmp_path / "maps.bin", timeout=120)
     v = np.fromfile(tmp_path / "maps.bin", np.int32)
     tx, ty = (w + 7) // 8, (h + 7) // 8
     grid, work = v[:tx * ty * 64 * 3].reshape(tx * ty, 64, 3), v[tx * ty * 64 * 3:]

@@ -3,24 +3,15 @@ with r = RN(1 / d), q0 = n * r, e = fma(-d, q0, n), q = fma(e, r, q0) against `n
 test enumerates x all 2^23 numerator significands, and over 10^7 seeded random significand pairs (tests/cpp/div_forms_check.cpp).
 A stand-alone program, built with AddressSanitizer and UBSan.  That gfx950's refined reciprocal IS RN(1 / d), and that the device's
 instructions return the same, is what tests/test_gpu_div_forms.py enumerates on the GPU."""
-import os
-import subprocess
-
 import div_forms_cases
+import host_check
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 DENOMINATORS = [int(x) for x in div_forms_cases.DENOMINATORS]  # the list the GPU test enumerates
 
 
 def test_the_one_pair_sequence_is_the_quotient_on_the_host(tmp_path):
-    assert os.path.exists(HIPCC), "hipcc is what builds this project: no build, no test"
-    exe = str(tmp_path / "div_forms_check")
-    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "-O2", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-o", exe, os.path.join(ROOT, "tests", "cpp", "div_forms_check.cpp")], check=True)
-    out = subprocess.run([exe] + [f"{d:x}" for d in DENOMINATORS], check=True, capture_output=True, text=True, timeout=600).stdout
-    res = {name: tuple(int(x) for x in rest) for name, *rest in (line.split() for line in out.splitlines())}
+    exe = host_check.build("div_forms_check", tmp_path, sanitize=True, extra=())
+    res = host_check.run(exe, *(f"{d:x}" for d in DENOMINATORS), timeout=600)
     print(res)
     assert set(res) == {"listed", "random"}
     n, bad, bad_q0 = res["listed"]

@@ -3,21 +3,11 @@ selects on the operands, one guard, a literal zero component -- against the two-
 equals any NaN): 10^6 seeded random unit normals and a grid of the edges (tests/cpp/frame_forms_check.cpp).  On the host the short
 forms are the plain operators, so this proves the algebra of the rewrite; the device's instructions are compared by
 tests/test_gpu_frame_forms.py.  A stand-alone program, its host code built with AddressSanitizer and UBSan."""
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import host_check
 
 
 def test_the_select_first_frame_is_the_two_arm_frame_on_the_host(tmp_path):
-    assert os.path.exists(HIPCC), "hipcc is what builds this project: no build, no test"
-    exe = str(tmp_path / "frame_forms_check")
-    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "-O2", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-o", exe, os.path.join(ROOT, "tests", "cpp", "frame_forms_check.cpp")], check=True)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=600).stdout
-    res = {name: tuple(int(x) for x in rest) for name, *rest in (line.split() for line in out.splitlines())}
+    res = host_check.run(host_check.build("frame_forms_check", tmp_path, sanitize=True), timeout=600)
     print(res)
     assert set(res) == {"random", "grid"}
     n, bad, passed, failed = res["random"]

@@ -5,24 +5,15 @@ pixel's product formed ahead -- against rt_rng_seed: state words and the first e
 2^32 - 1, sample indices 0 and 1, sample windows that cross 2^32 and 2^64, random cases, and the one counter whose Philox block is
 all zero (tests/cpp/gen_keys_check.cpp).  A stand-alone program, its host code built with AddressSanitizer and UBSan.  The device's
 instructions are compared by tests/test_gpu_gen_keys.py; rt_philox_round_keys, the library's own table, is checked here too."""
-import os
-import subprocess
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import host_check
+
 SEEDS = (0, 1, 0xFFFFFFFFFFFFFFFF, 0x61C8864700000000, 0x0000000061C88647, 0x4498517B00000000, 0x12345678F0000000, 0x806AB30FD9C60ABE)
 
 
 def test_the_key_table_and_the_keyed_seed_are_rt_rng_seed_on_the_host(tmp_path):
-    assert os.path.exists(HIPCC), "hipcc is what builds this project: no build, no test"
-    exe = str(tmp_path / "gen_keys_check")
-    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "-O2", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-o", exe, os.path.join(ROOT, "tests", "cpp", "gen_keys_check.cpp")], check=True)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=600).stdout
-    res = {name: tuple(int(x) for x in rest) for name, *rest in (line.split() for line in out.splitlines())}
+    res = host_check.run(host_check.build("gen_keys_check", tmp_path, sanitize=True), timeout=600)
     print(res)
     assert set(res) == {"table", "rounds", "keyed", "item", "zero_block"}
     assert res["table"] == (len(SEEDS) * 20 + 3, 0), res

@@ -5,20 +5,16 @@ reach both sides of each guard, and over 2^20 seeded random inputs per site; thi
 no scene the host accepts sends a sphere normal there.  (b) frames and ray counts of rtweekend1, bit for bit against the general
 spheres-only kernel and against the oracle as tests/test_gpu_parity.py compares frames.  tests/test_frame_forms_host.py runs the
 frame's algebra on the CPU."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_check
 import scenes
 from gpu_support import abi, assert_same_bits
 from test_gpu_parity import assert_images_match  # the parity tests' own comparison and tolerance
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 N_RANDOM = 1 << 20
 
 
@@ -26,13 +22,7 @@ N_RANDOM = 1 << 20
 def edge_grid(tmp_path_factory):
     """(n, 3) f32: the edge grid of tests/cpp/frame_forms_check.cpp, written out by that program itself (host code only, built
     here without the sanitizers), so that host and device run the very same operands"""
-    assert os.path.exists(HIPCC), "hipcc is what builds this project: no build, no test"
-    d = tmp_path_factory.mktemp("frame_forms")
-    exe, out = str(d / "frame_forms_check"), str(d / "grid.bin")
-    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
-                    "-o", exe, os.path.join(ROOT, "tests", "cpp", "frame_forms_check.cpp")], check=True)
-    subprocess.run([exe, out], check=True, capture_output=True, timeout=120)
-    return np.fromfile(out, dtype=np.float32).reshape(-1, 3)
+    return host_check.edge_grid("frame_forms_check", 3, tmp_path_factory)
 
 
 def _jittered_unit_normals(n):

@@ -5,33 +5,23 @@ sphere_occludes_unlimited).  (a) the predicate next to `hit && t > 0` ON the dev
 seeded random cases, and trace_any's whole two-sphere arm next to the arm with the full test, on scenes that send lanes into its cold
 loop; (b) frames and ray counts, bit for bit against the oracle and against the general spheres-only kernel, on scenes
 that stress it.  tests/test_pair_shadow_host.py runs the same predicate on the CPU."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_check
 import scenes
 from gpu_support import CAMERA_16_9, abi, assert_same_bits
 
 pytestmark = pytest.mark.gpu
 
 W, H, SPP = 64, 48, 16
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 @pytest.fixture(scope="module")
 def edge_grid(tmp_path_factory):
     """(n, 10) f32: centre, radius, origin, direction -- the edge grid of tests/cpp/pair_shadow_check.cpp, written out by that
     program itself (host code only, built here without the sanitizers), so that host and device run the very same operands"""
-    assert os.path.exists(HIPCC), "hipcc is what builds this project: no build, no test"
-    d = tmp_path_factory.mktemp("pair_shadow")
-    exe, out = str(d / "pair_shadow_check"), str(d / "grid.bin")
-    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
-                    "-o", exe, os.path.join(ROOT, "tests", "cpp", "pair_shadow_check.cpp")], check=True)
-    subprocess.run([exe, out], check=True, capture_output=True, timeout=120)
-    return np.fromfile(out, dtype=np.float32).reshape(-1, 10)
+    return host_check.edge_grid("pair_shadow_check", 10, tmp_path_factory)
 
 
 def _random_cases(n):

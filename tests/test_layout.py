@@ -2,28 +2,21 @@
 (a stand-alone host program, no HIP) built with the address and undefined-behaviour sanitizers and run: alignment, order,
 disjointness, absent parts, the total at 2^31 pixels against 128-bit arithmetic, and a description beyond the fixed capacity."""
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import host_check
 
 
 @pytest.fixture(scope="module")
 def layout_check(tmp_path_factory):
-    if not os.path.exists(HIPCC):
+    if not os.path.exists(host_check.HIPCC):
         pytest.skip("hipcc not available")
-    exe = str(tmp_path_factory.mktemp("layout") / "layout_check")
     # host code only: the sanitizers go to the host side of the hipcc line (-Xarch_host), nothing is built for a GPU
-    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-Wall", "-Werror",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-                    "-o", exe, os.path.join(ROOT, "tests", "cpp", "layout_check.cpp")], check=True)
-    return exe
+    return host_check.build("layout_check", tmp_path_factory.mktemp("layout"), extra=("-O1", "-g", "-Wall", "-Werror"),
+                            sanitize=("-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"))
 
 
 def test_layouts_are_aligned_ordered_disjoint_and_do_not_wrap(layout_check):
-    run = subprocess.run([layout_check], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0, run.stdout + run.stderr
-    word, checks = run.stdout.split()
-    assert word == "ok" and int(checks) > 500
+    res = host_check.run(layout_check, timeout=120)  # (a non-zero exit fails there, with the program's output)
+    assert set(res) == {"ok"} and len(res["ok"]) == 1 and res["ok"][0] > 500, res

@@ -5,39 +5,24 @@ The division / square-root short forms of the same header exist only on the devi
 v_sqrt_f32); tests/test_gpu_parity.py::test_lean_arithmetic_matches_the_ieee_operators runs those against the plain
 operators on the GPU."""
 import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import host_check
 
 
 @pytest.fixture(scope="module")
 def lean_check(tmp_path_factory):
-    if not os.path.exists(HIPCC):
+    if not os.path.exists(host_check.HIPCC):
         pytest.skip("hipcc not available")
-    exe = str(tmp_path_factory.mktemp("lean") / "lean_check")
-    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mfma",
-                    "-Wno-unused-function", "-o", exe, os.path.join(ROOT, "tests", "cpp", "lean_check.cpp"), "-lpthread"], check=True)
-    return exe
-
-
-def _run(exe, stride):
-    out = subprocess.run([exe, str(stride)], check=True, capture_output=True, text=True, timeout=900).stdout
-    res = {}
-    for line in out.splitlines():
-        name, n, bad = line.split()
-        res[name] = (int(n), int(bad))
-    return res
+    return host_check.build("lean_check", tmp_path_factory.mktemp("lean"), sanitize=False, extra=("-mfma", "-Wno-unused-function", "-lpthread"))
 
 
 def test_lean_elementary_functions_equal_detmath(lean_check):
     # stride 13: every 13th float of [0, 2^22] (both signs) for sin + cos, every 13th of ALL bit patterns for acos,
     # the atan2 grids: ~0.6 G evaluations, about 20 s on 8 cores.  RT_LEAN_EXHAUSTIVE=1 runs stride 1 (every float).
     stride = 1 if os.environ.get("RT_LEAN_EXHAUSTIVE") == "1" else 13
-    res = _run(lean_check, stride)
+    res = host_check.run(lean_check, stride, timeout=900)
     assert set(res) == {"sincos", "acos", "atan2_grid", "atan2_ratio"}
     for name, (n, bad) in res.items():
         assert n > 1000 and bad == 0, (name, n, bad)

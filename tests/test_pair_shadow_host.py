@@ -3,21 +3,11 @@ without a limit, answered from signs -- against Sphere::get_int's `hit && t > 0`
 contract's operators: 10^7 seeded random rays and spheres and a grid of the edges the proof names (tests/cpp/pair_shadow_check.cpp).
 A stand-alone program, its host code built with AddressSanitizer and UBSan.  The device's instructions are compared by
 tests/test_gpu_pair_shadow.py."""
-import os
-import subprocess
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import host_check
 
 
 def test_the_sign_predicate_is_the_full_test_on_the_host(tmp_path):
-    assert os.path.exists(HIPCC), "hipcc is what builds this project: no build, no test"
-    exe = str(tmp_path / "pair_shadow_check")
-    subprocess.run([HIPCC, "-x", "hip", "--cuda-host-only", "-O2", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-o", exe, os.path.join(ROOT, "tests", "cpp", "pair_shadow_check.cpp")], check=True)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=600).stdout
-    res = {name: tuple(int(x) for x in rest) for name, *rest in (line.split() for line in out.splitlines())}
+    res = host_check.run(host_check.build("pair_shadow_check", tmp_path, sanitize=True), timeout=600)
     print(res)
     assert set(res) == {"random", "grid"}
     n, bad, bad_asked, asked = res["random"]
