@@ -392,9 +392,16 @@ int rt_scene_set_traversal(rt_scene *scene, int mode);
  *   RT_TUNE_RADIANCE_GROUPS  0 automatic (default); n in 1..65536: rt_radiance launches at most n workgroups (of 256 lanes), so
  *                         that a small batch already makes every lane work through several rays (tests of the refill);
  *                         rt_render_tiles, whose kernel has the same shape, obeys it too (a short tile list then makes
- *                         every lane refill); other entry points ignore it */
+ *                         every lane refill); other entry points ignore it
+ *   RT_TUNE_SKY_RUN       -1 automatic (default: on), 0 off, 1 on: the kernels of rt_launch_info.feature_set = 3 prove per 8 x 8
+ *                         tile, from the camera of the launch, that no primary ray of the tile can hit a sphere, and fold the
+ *                         samples of such tiles without a walk (rt_launch_info.sky_run; other kernels and other tilings ignore
+ *                         it, and a shard of 2^30 pixels or more, padding included, runs the general spheres-only kernels).  A
+ *                         tile is flagged only when its eight neighbours pass too.  Same pixels, same ray counts.  (Key 9 is
+ *                         not assigned.) */
 typedef enum rt_tuning_key { RT_TUNE_TRAVERSAL = 0, RT_TUNE_FEATURE_SET = 1, RT_TUNE_SCENE_IN_LDS = 2, RT_TUNE_SCHEDULE = 3, RT_TUNE_WALK = 4,
-                             RT_TUNE_STACK_CAP = 5, RT_TUNE_EXCHANGE = 6, RT_TUNE_WHOLE_PIXEL_SHARE = 7, RT_TUNE_RADIANCE_GROUPS = 8 } rt_tuning_key;
+                             RT_TUNE_STACK_CAP = 5, RT_TUNE_EXCHANGE = 6, RT_TUNE_WHOLE_PIXEL_SHARE = 7, RT_TUNE_RADIANCE_GROUPS = 8,
+                             RT_TUNE_SKY_RUN = 10 } rt_tuning_key;
 int rt_scene_set_tuning(rt_scene *scene, int key, int value);
 /* The work items of a render under `opts` at an explicit split with `share` sixteenths of the shard's tiles handed out as whole
  * pixels (RT_TUNE_WHOLE_PIXEL_SHARE): what rt_launch_info.whole_claims and .n_items report after such a render by a kernel that
@@ -469,7 +476,9 @@ typedef struct rt_launch_info {
 	uint32_t whole_claims;  /* claims of 64 items that are whole tiles, one pixel per lane (RT_TUNE_WHOLE_PIXEL_SHARE) */
 	uint64_t n_items;       /* work items of the launch: 64 x (whole_claims + (tiles - whole_claims) x sample_split) in the tiled
 	                           order, else pixels x sample_split; incl. edge-tile padding */
-	char kernel[160];
+	uint32_t sky_run;       /* 1: claims of tiles that can only see sky are flagged and run without a walk (RT_TUNE_SKY_RUN) */
+	uint32_t reserved;
+	char kernel[152];
 } rt_launch_info;
 int rt_last_launch_info(const rt_scene *scene, rt_launch_info *out);
 
@@ -1595,6 +1604,15 @@ int rt_selftest_pair_shadow_walk(int device, const float *cases, uint64_t n_case
  * NaN; the validity flag included): *mismatches must be zero.  *valid = 0: the origin or a term is not finite and a render would not use
  * the block.  RT_ERR_UNSUPPORTED for any other kind of scene, RT_ERR_NO_DEVICE on a host-only scene.  Blocking. ---- */
 int rt_selftest_pair_primary(rt_scene *scene, const float origin[3], uint32_t *valid, uint64_t *mismatches);
+
+/* ---- self-test of the two-sphere kernels' per-tile sky proof (csrc/rt_sky_tiles.h; RT_TUNE_SKY_RUN).  A render of such a scene flags
+ * the 8 x 8 tiles none of whose primary rays can hit a sphere and folds their samples without a walk.  This call forms the launch
+ * constants of the proof for `camera` and the frame `opts` describes as a render would, and runs the kernels' own inline test ON the
+ * scene's device for every tile of the frame (all shards): out_flags[ty * tiles_x + tx] = 1 where the tile would be flagged, n_tiles
+ * = ceil(width / tile_width) * ceil(height / tile_height) bytes.  All zeros for any other kind of scene and for tiles that are not 64
+ * pixels of power-of-two width.  tests/cpp/sky_tiles_check.cpp evaluates the same code on the CPU.  RT_ERR_NO_DEVICE on a
+ * host-only scene.  Blocking. ---- */
+int rt_selftest_sky_tiles(rt_scene *scene, const rt_camera *camera, const rt_render_opts *opts, uint8_t *out_flags, uint64_t n_tiles);
 
 /* ---- self-test of the kernels' sky sampling: sky_sample and sky_pdf of csrc/rt_shade.h as the render kernels inline them, run
  * directly on the scene's device.  Blocking; host buffers.  Sample i < n seeds its stream as pixel 0, sample i of `seed`, draws a

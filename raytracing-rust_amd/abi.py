@@ -28,6 +28,7 @@ RT_METHOD_NAIVE, RT_METHOD_MIS = range(2)
 RT_LAYOUT_FRAME, RT_LAYOUT_SHARD = range(2)
 RT_TUNE_TRAVERSAL, RT_TUNE_FEATURE_SET, RT_TUNE_SCENE_IN_LDS, RT_TUNE_SCHEDULE, RT_TUNE_WALK, RT_TUNE_STACK_CAP, RT_TUNE_EXCHANGE, RT_TUNE_WHOLE_PIXEL_SHARE = range(8)
 RT_TUNE_RADIANCE_GROUPS = 8  # rt_radiance, rt_render_tiles: at most that many workgroups (0: automatic)
+RT_TUNE_SKY_RUN = 10  # two-sphere kernels: tiles that can only see sky run without a walk (-1 automatic = on, 0 off, 1 on); 9 is unassigned
 
 NO_INDEX = 0xFFFFFFFFFFFFFFFF  # usize::MAX
 RT_DEVICE_NONE = -1  # rt_scene_create: Bvh::new on the host only (no GPU touched, nothing can be rendered)
@@ -198,7 +199,9 @@ class LaunchInfo(C.Structure):  # rt_launch_info
         ("sample_split", C.c_uint32),
         ("whole_claims", C.c_uint32),
         ("n_items", C.c_uint64),
-        ("kernel", C.c_char * 160),
+        ("sky_run", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("kernel", C.c_char * 152),
     ]
 
 
@@ -720,6 +723,7 @@ EXPORTED_SYMBOLS = [
     "rt_selftest_pair_shadow",
     "rt_selftest_pair_shadow_walk",
     "rt_selftest_pair_primary",
+    "rt_selftest_sky_tiles",
     "rt_selftest_sky",
     "rt_render_aov",
     "rt_render_aov_device",

@@ -730,6 +730,11 @@ static int set_tuning_one(rt_scene *s, int key, int value)
 			return fail(RT_ERR_INVALID_ARGUMENT, "radiance groups must be 0 (automatic) or 1..65536 workgroups");
 		s->radiance_groups = (uint32_t)value;
 		return RT_OK;
+	case RT_TUNE_SKY_RUN:
+		if (value < -1 || value > 1)
+			return fail(RT_ERR_INVALID_ARGUMENT, "sky run must be -1 (automatic), 0 (off) or 1 (on where the kernel has it)");
+		s->sky_run = value;
+		return RT_OK;
 	default:
 		return fail(RT_ERR_INVALID_ARGUMENT, "unknown tuning key");
 	}
@@ -1066,8 +1071,10 @@ static int plan_render_launch(const rt_scene *s, const rt_render_opts *o, const 
 	// RT_TUNE_EXCHANGE (rt_render.hip, XCHG).  Fine schedule: 512-thread workgroups whose waves trade whole lane states
 	// through two record pools behind the stacks; coarse MIS kernels: decided below, once the occupancy is known
 	// (feature set of THIS launch: 3 = FeatPair, built for the exhaustive coarse kernels without the exchange only)
+	// ... and for shards below kPairMaxWork pixels, padding included: those kernels decode bit 30 of a wave's pixel base as the sky
+	// flag (rt_render.hip kSkyClaim), switch on or off, so a larger shard takes the general spheres-only kernels -- same pixels
 	const int feature_set =
-	    (s->feature_set == 0 && s->pair_tree && !s->feature_set_forced && !prune && !fine && s->exchange_mode != 1) ? 3 : s->feature_set;
+	    (s->feature_set == 0 && s->pair_tree && !s->feature_set_forced && !prune && !fine && s->exchange_mode != 1 && g.n_work < kPairMaxWork) ? 3 : s->feature_set;
 	bool xchg = s->exchange_mode == 1 && render_exchange_available(o->render_method, prune, fine, feature_set);
 	const bool xchg_fine = xchg && fine;
 	uint32_t block_threads = render_block_threads(feature_set, fine, xchg_fine);
@@ -1510,16 +1517,21 @@ int rt_render_device(rt_scene *s, const rt_camera *camera, const rt_render_opts 
 		HIP_TRY(launch_reset(stream, s->d_work_counter, reinterpret_cast<unsigned long long *>(d_rays_shot), d_out_rgb, zero_floats));
 	}
 	fill_launch_info(plan, o, s->n_cus, &s->last_launch);
+	const bool sky_run = sky_run_applies(s, plan.feature_set, g.n_work, P.tile_log2_w != 0xFFFFFFFFu);
+	s->last_launch.sky_run = sky_run ? 1u : 0u;
 	const DevCamera cam = dev_camera(camera);
 	// FeatPair: the origin-only terms of the primary walks (rt_types.h DevPairPrimary).  The camera belongs to the render, not to
 	// the scene, so they are formed here, per launch: some forty operations
 	DevPairPrimary primary{};
 	if (plan.feature_set == 3)
 		pair_primary_terms(s->pair, plan.dev.root_min, plan.dev.root_max, v3(cam.origin[0], cam.origin[1], cam.origin[2]), primary);
+	// ... and what the per-tile sky proof reads (rt_sky_tiles.h): per launch too, from the camera the caller passed -- a few
+	// hundred double operations, nothing kept from call to call
+	const DevSkyTiles sky_tiles = sky_tiles_block(s, primary, cam, (uint32_t)o->width, (uint32_t)o->height, sky_run);
 	HIP_TRY(hipEventRecord(s->ev_start, stream));
 	HIP_TRY(launch_render(o->render_method, plan.prune, plan.fine, plan.sky_lds, plan.feature_set, plan.n_blocks, plan.lds_bytes, stream, plan.dev, cam, P,
 	                      render_target, reinterpret_cast<unsigned long long *>(d_rays_shot), s->d_work_counter, s->d_stack_ovf, plan.xchg,
-	                      plan.feature_set == 3 ? &s->pair : nullptr, plan.feature_set == 3 ? &primary : nullptr, plan.block_threads));
+	                      plan.feature_set == 3 ? &s->pair : nullptr, plan.feature_set == 3 ? &primary : nullptr, plan.block_threads, sky_tiles));
 	HIP_TRY(hipEventRecord(s->ev_stop, stream));
 	if (plan.split > 1u)
 		HIP_TRY(launch_combine(stream, P, s->d_partial, d_out_rgb));

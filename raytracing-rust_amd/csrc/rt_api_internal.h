@@ -13,6 +13,7 @@
 #include "rt_build.h"
 #include "rt_layout.h"
 #include "rt_types.h"
+#include "rt_sky_tiles.h"
 
 // the text behind rt_last_error(): ONE per thread for the whole library (defined in rt_api.cpp)
 extern thread_local std::string g_error;
@@ -84,6 +85,7 @@ struct rt_scene {
 	int exchange_mode = 0;           // RT_TUNE_EXCHANGE
 	int whole_share = kWholeShareDefault; // RT_TUNE_WHOLE_PIXEL_SHARE
 	uint32_t radiance_groups = 0;    // RT_TUNE_RADIANCE_GROUPS (rt_radiance and rt_render_tiles)
+	int sky_run = -1;                // RT_TUNE_SKY_RUN: -1 automatic (on where the kernel has it), 0 off, 1 on
 	uint32_t stack_depth_narrow = 2; // HostScene::stack_depth_narrow (members of a multi-device scene have no host scene of their own)
 	uint32_t *d_stack_ovf = nullptr; // traversal-stack overflow area (deep trees under the fine schedule), grown on demand
 	size_t stack_ovf_words = 0;
@@ -206,6 +208,23 @@ inline FrameTiling frame_tiling(const rt_render_opts *o)
 	t.tiles_x = (uint32_t)((o->width + t.tile_w - 1) / t.tile_w);
 	t.tiles_y = (uint32_t)((o->height + t.tile_h - 1) / t.tile_h);
 	t.n_work = (uint64_t)t.tiles_x * t.tiles_y * t.tile_w * t.tile_h;
+	return t;
+}
+
+// RT_TUNE_SKY_RUN resolved for a launch of `feature_set` over a shard of n_work pixels (padding included) in the tiled order or not:
+// the two-sphere kernels alone have the run (rt_render.hip kSkyRun), the flag needs bit 30 of the wave's pixel base, and only the
+// tiled order flags claims.  Automatic equals on.
+constexpr uint64_t kPairMaxWork = 1ull << 30; // pixels of a shard, padding included, the two-sphere kernels are launched for (rt_api.cpp)
+inline bool sky_run_applies(const rt_scene *s, int feature_set, uint64_t n_work, bool tiled)
+{
+	return s->sky_run != 0 && feature_set == 3 && tiled && n_work < kPairMaxWork;
+}
+// the block the per-tile proof reads (rt_sky_tiles.h), for this scene, camera and image size; enabled = 0 unless the run applies
+inline rt::DevSkyTiles sky_tiles_block(const rt_scene *s, const rt::DevPairPrimary &primary, const rt::DevCamera &cam, uint32_t width, uint32_t height, bool applies)
+{
+	rt::DevSkyTiles t{};
+	if (applies && s->pair_tree)
+		rt::sky_tiles_terms(s->pair, primary, cam, width, height, t);
 	return t;
 }
 

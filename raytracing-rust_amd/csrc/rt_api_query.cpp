@@ -490,4 +490,37 @@ int rt_selftest_pair_primary(rt_scene *s, const float origin[3], uint32_t *valid
 	return RT_OK;
 }
 
+int rt_selftest_sky_tiles(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, uint8_t *out_flags, uint64_t n_tiles)
+{
+	if (!s || !camera || !o || !out_flags)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	if (int rc = need_device(s); rc != RT_OK)
+		return rc;
+	if (o->width < 2 || o->height < 2 || o->width >= 65536 || o->height >= 65536)
+		return fail(RT_ERR_INVALID_ARGUMENT, "width and height must be in [2, 65536)");
+	const FrameTiling t = frame_tiling(o);
+	if (n_tiles != (uint64_t)t.tiles_x * t.tiles_y)
+		return fail(RT_ERR_INVALID_ARGUMENT, "n_tiles must be the tiles of the frame the options describe");
+	std::memset(out_flags, 0, (size_t)n_tiles);
+	uint32_t log2_w = 0;
+	while (log2_w < 7u && (1u << log2_w) != t.tile_w)
+		++log2_w;
+	if (!s->pair_tree || t.tile_w * t.tile_h != 64u || log2_w >= 7u)
+		return RT_OK; // not a scene, or not a tiling, whose claims are ever flagged: all zeros
+	// the block as a render of this camera and size forms it (rt_api.cpp)
+	const DevCamera cam = dev_camera(camera);
+	DevPairPrimary primary{};
+	pair_primary_terms(s->pair, s->dev.root_min, s->dev.root_max, v3(cam.origin[0], cam.origin[1], cam.origin[2]), primary);
+	const DevSkyTiles block = sky_tiles_block(s, primary, cam, (uint32_t)o->width, (uint32_t)o->height, true);
+	// The case runner moves 64-bit words: zeros up, the kernel's results down.  The flags are bytes, so they travel as ceil(n / 8)
+	// zeroed words that the kernel fills through a byte pointer (every tile's byte is written; the padding stays zero) and that
+	// are copied out as bytes below -- no byte order is involved, both sides address the same buffer by bytes.
+	std::vector<unsigned long long> words((size_t)((n_tiles + 7u) / 8u), 0ull);
+	RT_TRY(run_cases(s->device, nullptr, 0, words.data(), words.size(), "selftest_sky_tiles", [&](unsigned long long *d, void *) {
+		return launch_sky_tiles(nullptr, block, (uint32_t)o->width, (uint32_t)o->height, log2_w, t.tiles_x, n_tiles, reinterpret_cast<uint8_t *>(d));
+	}));
+	std::memcpy(out_flags, words.data(), (size_t)n_tiles);
+	return RT_OK;
+}
+
 } // extern "C"

@@ -32,6 +32,22 @@ struct Ray {
 // direction takes the plain operators.  The two-sphere kernels form 1 / component by the reciprocal proven for gfx950
 // (rt_lean.h lean_inv_gfx950) and the normalised components by the one-pair quotient (lean_div_core_gfx950), the others by
 // lean_inv and lean_div3.
+// ... its two parts, for a caller that wants the direction alone (rt_render.hip's sky run: a ray that is never walked needs neither
+// the reciprocals nor the shear): the guard, and the normalisation behind it.  ray_new is written with them, so both get the same bits.
+RT_FN bool ray_dir_is_tame(V3 direction, float m2)
+{
+	const float smallest = fmin_(fmin_(fabsf(direction.x), fabsf(direction.y)), fabsf(direction.z));
+	return smallest >= 0x1p-60f && m2 >= 0x1p-40f && m2 <= 0x1p40f;
+}
+template <class F> RT_FN V3 ray_new_dir(V3 direction)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(RT_NO_LEAN)
+	const float m2 = dot(direction, direction);
+	if (__builtin_expect(ray_dir_is_tame(direction, m2), 1))
+		return lean_div3_for<lean_ray_norm_short(F::pair)>(direction, lean_sqrt(m2));
+#endif
+	return direction / mag(direction);
+}
 template <class F> __device__ __forceinline__ Ray ray_new(V3 origin, V3 direction)
 {
 	Ray r;

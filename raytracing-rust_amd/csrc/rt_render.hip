@@ -37,6 +37,7 @@
 // 12 bytes per pixel for the whole render.  No MFMA: nothing here is a dense contraction.
 #include "rt_shade.h"
 #include "rt_gen_keys.h"
+#include "rt_sky_tiles.h"
 #include "rt_render.h"
 
 namespace rt {
@@ -77,6 +78,20 @@ constexpr uint32_t kStarveLimit = RT_STARVE_LIMIT;
 constexpr uint32_t kClaim = 64; // work items a wave claims per atomic
 constexpr uint32_t kWholePixel = 64u;      // lane state chunk_c: the item is a whole pixel (the bits below hold the chunk's number, < 64)
 constexpr uint32_t kWholeClaim = 1u << 31; // wave state wq_pbase: the claim is one of whole pixels (a pixel's index in a shard is below 2^31)
+// The sky run (FeatPair, coarse schedule; rt_sky_tiles.h has the proof): a claim whose tile can only see sky is flagged when it is
+// made, and a wave whose lanes all sit between samples of flagged items folds their samples in a loop of its own -- seed, two jitter
+// draws, the direction normalised, the sky's emission, finalize -- without a walk, a hit record or a trip round the voted loop.
+// The flag rides in bit 30 of wq_pbase for the wave and in bit 7 of chunk_c for the lane's item (a chunk's number is below 64, bit 6
+// is kWholePixel).  THE BOUND that makes room in wq_pbase: a kernel built with the run decodes bit 30 as the flag whatever the
+// switch says, so it must never see a pixel index of 2^30 or more -- the host launches the two-sphere kernels only for shards below
+// 2^30 pixels, padding included (rt_api.cpp plan_render_launch, kPairMaxWork); larger shards run the general spheres-only kernels.
+// -DRT_PAIR_SKY_RUN=0 compiles the run out (A/B libraries): bit 30 is then a bit of the pixel index again, as it was.
+#ifndef RT_PAIR_SKY_RUN
+#define RT_PAIR_SKY_RUN 1
+#endif
+constexpr uint32_t kSkyClaim = 1u << 30;
+constexpr uint32_t kSkyItem = 128u;
+static_assert(kSkyItem > kWholePixel && kSkyClaim < kWholeClaim, "the flags sit above the chunk number and below the whole-claim bit");
 #ifndef RT_ACQUIRE_BATCH
 #define RT_ACQUIRE_BATCH 1
 #endif
@@ -240,6 +255,7 @@ struct RenderArgs {
 	DevPairScene pair; // FeatPair only (rt_types.h): the whole scene, read where it is used
 	DevPairPrimary primary; // FeatPair only: the origin-only terms of this render's primary walks
 	DevGenKeys gen_keys; // FeatPair only: the Philox round keys of this render's seed (rt_gen_keys.h)
+	DevSkyTiles sky_tiles; // FeatPair only: what the per-tile sky proof reads (rt_sky_tiles.h); enabled = 0: no claim is flagged
 };
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const __attribute__((address_space(4))) RenderArgs *KArgs; // the kernarg segment is constant memory: s_load
@@ -420,6 +436,8 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 	// switches of rt_lean.h): the coarse two-sphere kernels only
 	constexpr bool kKeyedGen = kWholeItems && lean_gen_keys(F::pair);
 	constexpr bool kItemProduct = kWholeItems && lean_gen_item_product(F::pair);
+	// the sky run (kSkyClaim above): where the lane state has chunk_c to carry the flag
+	constexpr bool kSkyRun = kWholeItems && RT_PAIR_SKY_RUN != 0;
 
 	// ---- per-lane state (registers) ----
 	int ph = PH_NEED_PIXEL;
@@ -545,7 +563,7 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 				// at the next chunk's first pass.
 				const uint32_t log2_s = k->P.tile_log2_w >> 8; // (whole-pixel items exist under the tiled order only)
 				const uint32_t c1 = (chunk_c & (kWholePixel - 1u)) + 1u;
-				if (chunk_c >= kWholePixel && (c1 >> log2_s) == 0u) {
+				if ((chunk_c & kWholePixel) != 0u && (c1 >> log2_s) == 0u) { // (a flagged item stays flagged: kSkyItem rides along)
 					chunk_c += 1u;
 					chunk_end = (uint32_t)(((uint64_t)(c1 + 1u) * k->P.spp) >> log2_s);
 					out_index += k->P.n_work;
@@ -602,8 +620,60 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 	
 	};
 
+	// GEN up to the camera ray's direction (not normalised), for the sky run: a COPY of do_gen's lines, which must stay its lines.
+	// Shared (do_gen calling this lambda) the text is one, but the kernels that never run the sky run paid for it in registers: the fine
+	// MIS kernel of the triangle scenes went from 2 to 7 spilled VGPRs (12 -> 24 bytes of scratch), the pruned full-feature MIS kernel
+	// 40 -> 38, two more fine kernels 11 -> 6 and 13 -> 10 -- allocations nobody has measured; with the copy every kernel outside the
+	// pair set keeps its registers, spills and scratch (profiles/resource_table.json).  tests/test_gpu_sky_run.py compares frames with
+	// the switch off and on, which is the comparison of the two copies.
+	auto gen_direction = [&]() -> V3 {
+		const KArgs k = kargs(); // seed, sample window, image size and camera: scalar loads here, once per sample
+		const uint64_t seed = ((uint64_t)k->P.seed_hi << 32) | k->P.seed_lo;
+		const uint64_t sample_begin = ((uint64_t)k->P.sample_begin_hi << 32) | k->P.sample_begin_lo;
+		const V3 cam_o = v3(k->cam.origin[0], k->cam.origin[1], k->cam.origin[2]);
+		const V3 cam_ll = v3(k->cam.lower_left[0], k->cam.lower_left[1], k->cam.lower_left[2]);
+		const V3 cam_h = v3(k->cam.horizontal[0], k->cam.horizontal[1], k->cam.horizontal[2]);
+		const V3 cam_v = v3(k->cam.vertical[0], k->cam.vertical[1], k->cam.vertical[2]);
+		// (the image size in the same round of scalar loads as the rest: left to the compiler it is fetched after the Philox rounds,
+		// a round trip of its own)
+		const uint32_t w1 = here_(k->P.width - 1u), h1 = here_(k->P.height - 1u);
+		if constexpr (kKeyedGen) {
+			uint32_t hi0 = gen_hi0, lo0 = gen_lo0;
+			if constexpr (!kItemProduct)
+				philox_pixel_product(pixel_index, hi0, lo0);
+			rng_seed_keyed<lean_gen_keys_lead(F::pair)>(&rng, &k->gen_keys, hi0, lo0, sample_begin + chunk_begin + sample_i);
+		} else {
+			rt_rng_seed(&rng, seed, (uint64_t)pixel_index, sample_begin + chunk_begin + sample_i);
+		}
+		RT_SECTION(15); // GEN: loads + stream seed
+		// (jitter + pixel) / (W - 1): the numerator is zero or in [2^-23, 2^31), the denominator in [1, 2^31]: tame (rt_lean.h) --
+		// and when the host has verified the two divisors (DevRenderParams::w1h1_ok), two fma steps on its reciprocals
+		const float jx = rt_rng_range_f32(&rng, 0.0f, 1.0f) + (float)px, jy = rt_rng_range_f32(&rng, 0.0f, 1.0f) + (float)py;
+		float u, v;
+		if (here_(k->P.w1h1_ok) != 0u) { // (wave-uniform)
+			u = div_by_verified(jx, (float)w1, k->P.inv_w1);
+			v = 1.0f - div_by_verified(jy, (float)h1, k->P.inv_h1);
+		} else {
+			u = div_tame_fix_(jx, (float)w1);
+			v = 1.0f - div_tame_fix_(jy, (float)h1);
+		}
+		return cam_ll + cam_h * u + cam_v * v - cam_o;
+	};
+	// One sample of a pixel that can only see sky (kSkyItem): GEN's stream and direction, then what SHADE's sky arm adds and how it
+	// ends the sample -- naive: one ray counted, the filter on; MIS's prologue: no ray counted, out before the filter (mis.rs:29-31).
+	// The draws GEN and the Emit's scatter_ray make after the jitter feed nothing: the next sample seeds its own stream.
+	auto do_sky_sample = [&]() {
+		const V3 d = ray_new_dir<F>(gen_direction());
+		Hit nh;
+		uint32_t nmat;
+		make_sky_hit_lean<F>(S, nh, nmat);
+		outp = v3s(0.0f) + emission_of_hit<F>(S, PS, nmat, true, nh, d);
+		ray_count = METHOD == 0 ? 1u : 0u;
+		finalize(METHOD == 0);
+	};
+
 #ifdef RT_STATS
-	unsigned long long st_lane_nodes = 0, st_lane_prims = 0, st_lane_maxsp = 0;
+	unsigned long long st_lane_nodes = 0, st_lane_prims = 0, st_lane_maxsp = 0, st_sky_samples = 0, st_sky_runs = 0, st_sky_clock = 0, st_allsky_clock = 0, st_allsky_iters = 0, st_iter_t0 = 0;
 #endif
 	// NODE -- one inner-node step: Bvh::get_intersection_candidates' loop body (mod.rs:203-221)
 	auto do_node = [&]() {
@@ -1339,6 +1409,21 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 					const uint32_t tx = tile - ty * k->P.tiles_x;
 					wq_xy = (tx << log2_w) | ((ty * k->P.tile_h) << 16);
 					wq_pbase = ((kt << 6) + (sub << (6u - log2_s))) | (is_whole ? kWholeClaim : 0u);
+					if constexpr (kSkyRun) {
+						// once per claim: lane i tests pixel i of the claim's tile and of the eight tiles around it (rt_sky_tiles.h)
+						if (k->sky_tiles.enabled != 0u) {
+							DevSkyTiles ST;
+#pragma unroll
+							for (int i = 0; i < 3; ++i) {
+								ST.base[i] = k->sky_tiles.base[i]; ST.step_x[i] = k->sky_tiles.step_x[i]; ST.step_y[i] = k->sky_tiles.step_y[i];
+								ST.n[0][i] = k->sky_tiles.n[0][i]; ST.n[1][i] = k->sky_tiles.n[1][i];
+							}
+							ST.k[0] = k->sky_tiles.k[0]; ST.k[1] = k->sky_tiles.k[1];
+							const bool sees_sky = sky_lane_passes(ST, tx << log2_w, ty * k->P.tile_h, log2_w, lane, k->P.width, k->P.height);
+							if (__ballot(!sees_sky) == 0ull)
+								wq_pbase |= kSkyClaim;
+						}
+					}
 				}
 				// the leftovers go first, the rest comes from the new claim
 				wq_next = base + (n - avail);
@@ -1361,7 +1446,7 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 				const uint32_t pbase = from_old ? old_pbase : wq_pbase;
 				const bool whole = kWholeItems && pbase >= kWholeClaim;
 				const uint32_t ls = whole ? 0u : log2_s; // a whole-pixel claim: 64 pixels, each from its chunk 0
-				const uint32_t wp = (kWholeItems ? pbase & (kWholeClaim - 1u) : pbase) + (in >> ls); // the pixel, in this shard's order
+				const uint32_t wp = (kWholeItems ? pbase & ((kSkyRun ? kSkyClaim : kWholeClaim) - 1u) : pbase) + (in >> ls); // the pixel, in this shard's order
 				const uint32_t c = in & ((1u << ls) - 1u);                      // ... and which of its chunks
 				const uint32_t in_tile = wp & 63u;
 				px = (xy & 0xFFFFu) + (in_tile & ((1u << log2_w) - 1u));
@@ -1373,7 +1458,7 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 				if constexpr (kWholeItems) {
 					sample_i = first;
 					chunk_end = end;
-					chunk_c = c | (whole ? kWholePixel : 0u);
+					chunk_c = c | (whole ? kWholePixel : 0u) | ((kSkyRun && (pbase & kSkyClaim) != 0u) ? kSkyItem : 0u);
 				} else {
 					chunk_begin = first;
 					chunk_end = end - first;
@@ -1599,9 +1684,45 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 		// lane-iterations that paths have spent waiting for BOUNCE since it last ran (wave-uniform; see kStarveLimit)
 		uint32_t waited = 0;
 		while (alive) {
+#ifdef RT_STATS
+			st_iter_t0 = wall_clock64();
+#endif
 			if (XCHG && METHOD == 1)
 				exchange();
 			acquire();
+			if constexpr (kSkyRun) {
+				// every lane that holds work sits between samples of a flagged item (none waits for BOUNCE, none holds a walk): the sky
+				// run.  It goes on while no lane's finalize has left PH_GEN -- the pixel's next chunk keeps it there, and the flag --
+				// then the voted loop below takes over as if the samples had been its own.
+				const unsigned long long m_gen = __ballot(ph == PH_GEN);
+				if (m_gen != 0ull && __ballot(ph < PH_NEED_PIXEL && !(ph == PH_GEN && (chunk_c & kSkyItem) != 0u)) == 0ull) {
+					const KArgs k = kargs();
+#pragma unroll
+					for (int i = 0; i < 3; ++i) {
+						PS.sky_c1[i] = k->pair.sky_c1[i]; PS.sky_c2[i] = k->pair.sky_c2[i];
+					}
+					PS.sky_param = k->pair.sky_param;
+					PS.sky_tex_type = k->pair.sky_tex_type;
+#ifdef RT_STATS
+					st_sky_runs += 1;
+					RT_SECTION(0);
+#endif
+					do {
+#ifdef RT_STATS
+						st_sky_samples += (unsigned long long)__popcll(__ballot(ph == PH_GEN));
+#endif
+						if (ph == PH_GEN)
+							do_sky_sample();
+					} while (__ballot(ph == PH_GEN) == m_gen);
+#ifdef RT_STATS
+					{ // the run's wave time, apart from the sections of the voted loop
+						const unsigned long long now_ = wall_clock64();
+						st_sky_clock += now_ - st_mark;
+						st_mark = now_;
+					}
+#endif
+				}
+			}
 			// ---- tiny trees (a walk is a handful of steps): two super-phases.
 			//   TRACE = GEN + closest walk + SHADE     LIGHT = LIGHT + shadow walk + SCATTER
 			// About half of all SHADE outcomes end the sample; those lanes regenerate and stay in
@@ -1664,6 +1785,14 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 							do_shade(std::integral_constant<int, 1>{});
 						}
 						RT_SECTION(3);
+#ifdef RT_STATS
+						// a PRIMARY iteration in which no lane waited for BOUNCE and every participating lane ended in the sky arm: its
+						// wave time from the loop's top (vote and hand-out included) -- what the sky run replaces, measured with the run off
+						if (n_light == 0u && n_trace != 0u && __ballot(ph == PH_LIGHT) == 0ull) {
+							st_allsky_clock += wall_clock64() - st_iter_t0;
+							st_allsky_iters += 1;
+						}
+#endif
 						// enough paths wait for BOUNCE now?  Then run it in this iteration: the same sequence of phases the vote at the
 						// top of the next iteration would choose, without the trip round the loop in between
 						const uint32_t n_light_now = (uint32_t)__popcll(__ballot(ph == PH_LIGHT));
@@ -1770,6 +1899,11 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 		atomicAdd(&g_stats[0], st_iters[0]); atomicAdd(&g_stats[1], st_active[0]);
 		atomicAdd(&g_stats[2], st_iters[1]); atomicAdd(&g_stats[3], st_active[1]);
 		atomicAdd(&g_stats[4], st_gen);
+		atomicAdd(&g_stats[58], st_sky_samples); // samples folded inside the sky run, and the runs
+		atomicAdd(&g_stats[59], st_sky_runs);
+		atomicAdd(&g_stats[60], st_sky_clock); // ... and their wave wall-clock cycles (the sections [40..55] do not hold them)
+		atomicAdd(&g_stats[61], st_allsky_clock); // all-sky PRIMARY iterations of the voted loop: wave cycles, and how many
+		atomicAdd(&g_stats[62], st_allsky_iters);
 		for (int k = 0; k < PH_COUNT; ++k) {
 			atomicAdd(&g_stats[5 + k], st_fine_iters[k]);
 			atomicAdd(&g_stats[5 + PH_COUNT + k], st_fine_active[k]);
@@ -2083,7 +2217,7 @@ hipError_t render_occupancy(int method, bool prune, bool fine, bool sky_lds, int
 hipError_t launch_render(int method, bool prune, bool fine, bool sky_lds, int feature_set, uint32_t n_blocks, size_t lds_bytes, hipStream_t stream,
                          const DevScene &S, const DevCamera &cam, const DevRenderParams &P, float *out,
                          unsigned long long *rays_shot, uint32_t *work_counter, uint32_t *stack_ovf, bool xchg, const DevPairScene *pair,
-                         const DevPairPrimary *primary, uint32_t block_threads)
+                         const DevPairPrimary *primary, uint32_t block_threads, const DevSkyTiles &sky_tiles)
 {
 	render_fn fn = pick_render(method, prune, fine, sky_lds, feature_set, xchg);
 	if (!fn)
@@ -2098,6 +2232,7 @@ hipError_t launch_render(int method, bool prune, bool fine, bool sky_lds, int fe
 	A.stack_ovf = stack_ovf;
 	A.pair = pair ? *pair : DevPairScene{};
 	A.primary = primary ? *primary : DevPairPrimary{};
+	A.sky_tiles = sky_tiles; // (enabled = 0 for every launch but a two-sphere one with the run on: rt_api_internal.h sky_tiles_block)
 	philox_round_keys(((uint64_t)P.seed_hi << 32) | P.seed_lo, A.gen_keys);
 	hipLaunchKernelGGL(fn, dim3(n_blocks), dim3(block_threads ? block_threads : render_block_threads(feature_set, fine, xchg)), lds_bytes, stream, A);
 	return hipGetLastError();

@@ -5,6 +5,7 @@
 
 #include "../../include/rt_hip.h"
 #include "rt_types.h"
+#include "rt_sky_tiles.h"
 
 namespace rt {
 
@@ -73,5 +74,8 @@ hipError_t launch_gen_keys(hipStream_t stream, uint64_t seed, const uint32_t *ca
 hipError_t launch_pair_shadow(hipStream_t stream, const float *cases, uint64_t n_cases, unsigned long long *counts);
 // rt_selftest_pair_shadow_walk: n cases of RT_PAIR_SHADOW_WALK_CASE_FLOATS floats, counts[RT_PAIR_SHADOW_WALK_COUNTS] zeroed by the caller
 hipError_t launch_pair_shadow_walk(hipStream_t stream, const float *cases, uint64_t n_cases, unsigned long long *counts);
+
+// rt_selftest_sky_tiles (rt_selftest_forms.hip): one byte per tile of the frame, zeroed by the caller
+hipError_t launch_sky_tiles(hipStream_t stream, const DevSkyTiles &T, uint32_t width, uint32_t height, uint32_t log2_w, uint32_t tiles_x, uint64_t n_tiles, uint8_t *out);
 
 } // namespace rt

@@ -187,6 +187,25 @@ hipError_t launch_pair_shadow_walk(hipStream_t stream, const float *cases, uint6
 	return launch_cases(pair_shadow_walk_kernel, stream, n_cases, 2048u, cases, n_cases, counts);
 }
 
+// rt_selftest_sky_tiles: the per-tile sky proof (rt_sky_tiles.h) as acquire_coarse asks it -- a wave per tile, lane i testing pixel
+// i of the tile and of its eight neighbours, pixels outside the image passing, one ballot -- for every tile of a frame: one byte per tile behind `out`
+__global__ __launch_bounds__(256) void sky_tile_flags_kernel(const DevSkyTiles T, uint32_t width, uint32_t height, uint32_t log2_w, uint32_t tiles_x, uint64_t n_tiles,
+                                                        uint8_t *__restrict__ out)
+{
+	const uint32_t lane = threadIdx.x & 63u;
+	for (uint64_t tile = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6); tile < n_tiles; tile += (uint64_t)gridDim.x * 4u) { // (wave-uniform)
+		const uint32_t ty = (uint32_t)(tile / tiles_x), tx = (uint32_t)(tile - (uint64_t)ty * tiles_x);
+		const bool sees_sky = sky_lane_passes(T, tx << log2_w, ty * (64u >> log2_w), log2_w, lane, width, height);
+		const unsigned long long bad = __ballot(!sees_sky);
+		if (lane == 0u)
+			out[tile] = (T.enabled != 0u && bad == 0ull) ? 1u : 0u;
+	}
+}
+hipError_t launch_sky_tiles(hipStream_t stream, const DevSkyTiles &T, uint32_t width, uint32_t height, uint32_t log2_w, uint32_t tiles_x, uint64_t n_tiles, uint8_t *out)
+{
+	return launch_cases(sky_tile_flags_kernel, stream, n_tiles * 64u, 2048u, T, width, height, log2_w, tiles_x, n_tiles, out);
+}
+
 // rt_selftest_div_forms, the enumeration: a work item is one denominator at one exponent pair against 2^kDivChunkBits consecutive
 // numerator significands; the refined reciprocal is formed once per item, as a shared-reciprocal site forms it
 constexpr uint32_t kDivChunkBits = 10, kDivChunkShift = 23u - kDivChunkBits;

@@ -305,6 +305,16 @@ def selftest_pair_primary(scene, origin):
     return bool(valid.value), int(bad.value)
 
 
+def selftest_sky_tiles(scene, camera, opts):
+    """rt_selftest_sky_tiles: (tiles_y, tiles_x) uint8 -- 1 where a render of `camera` under `opts` would flag the tile as seeing
+    only sky (csrc/rt_sky_tiles.h), by the kernels' own test on the GPU; zeros for scenes the two-sphere kernels do not take."""
+    tw, th = int(opts.tile_width) or 8, int(opts.tile_height) or 8
+    tiles_x, tiles_y = (int(opts.width) + tw - 1) // tw, (int(opts.height) + th - 1) // th
+    out = np.zeros(tiles_x * tiles_y, dtype=np.uint8)
+    _check(lib().rt_selftest_sky_tiles(scene._h, C.byref(camera), C.byref(opts), _p(out, C.c_uint8), C.c_uint64(out.size)))
+    return out.reshape(tiles_y, tiles_x)
+
+
 def camera_new(origin, lookat, vup, fov, aspect_ratio, aperture, focus_dist):
     """SimpleCamera::new (camera.rs:20-54)."""
     cam = abi.Camera()
