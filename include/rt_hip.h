@@ -979,6 +979,81 @@ int rt_noise_select_tiles(rt_scene *scene, const float *tile_error, uint32_t wid
 int rt_noise_select_tiles_device(rt_scene *scene, const float *d_tile_error, uint32_t width, uint32_t height, float threshold,
                                  uint32_t *d_tiles, uint32_t *d_count, void *hip_stream);
 
+/* ---- Lens cameras (csrc/rt_lens.hip): whole frames through a camera MODEL -- the thin lens SimpleCamera stores (u, v, lens_radius,
+ * camera.rs:13-16,51) and get_ray never reads, and three projections the reference does not have.  The ray of every sample is made
+ * on the device, so a frame needs no ray upload (rt_radiance takes one rt_ray_desc per ray).  No render kernel is involved: the
+ * integrator is the one rt_radiance and rt_render_tiles run.
+ *
+ * rt_lens_camera_new: `pinhole` is what rt_camera_new writes for the same arguments, byte for byte; right, up, forward are
+ *   SimpleCamera::new's u, v and -w (camera.rs:32-34) -- forward is w with every component negated; lens_radius = aperture / 2
+ *   (camera.rs:51); fisheye_half_angle = rt_to_radians of fov_degrees, / 2; reserved0 = 0.  The projection is stored, not checked: the
+ *   render entry points check the whole struct, which a caller may also fill or change by hand.
+ *
+ * rt_render_lens[_device]: W x H, RT_LAYOUT_FRAME, every pixel written.  SAMPLE k OF PIXEL p = y * W + x is pass n = sample_begin + k
+ *   (the uint64_t sum of rt_render_opts, which wraps):
+ *   The camera stream is rt_rng_seed of (seed, 2^63 + p, n): pixels are below 2^31, so no pixel's path stream is ever a camera stream.
+ *     On it, in this order: jx = rt_rng_range_f32 of (0, 1), + (float)x, then jy = the same + (float)y (the render's own
+ *     expressions); s = jx / (float)(W - 1), t = 1 - jy / (float)(H - 1); and for RT_PROJ_PERSPECTIVE with lens_radius != 0 ONLY two
+ *     more draws xi1, xi2 = rt_rng_f32.
+ *   The ray: f32 throughout, every operation in the written order (sums of three terms left to right), no contraction; sin and cos
+ *     are rt_sinf / rt_cosf of rt_detmath.h, sqrtf and `/` the IEEE ones; pi = RT_PI, 2 pi = RT_TAU, pi / 2 = RT_FRAC_PI_2.
+ *     PERSPECTIVE   d0 = lower_left + horizontal * s + vertical * t - origin (get_ray's expression, camera.rs:57-63).  lens_radius 0:
+ *                   the ray (origin, d0), no lens draw, no lens arithmetic.  Else r = lens_radius * sqrtf(xi1), phi = RT_TAU * xi2,
+ *                   off = right * (r * cos phi) + up * (r * sin phi), the ray (origin + off, d0 - off): the thin lens focused on the
+ *                   plane the reference's focus_dist already scales the viewport to.
+ *     ORTHOGRAPHIC  origin lower_left + horizontal * s + vertical * t, direction forward.
+ *     FISHEYE       (equidistant) a = 2 s - 1, b = (2 t - 1) * ((float)(H - 1) / (float)(W - 1)), rho = sqrtf(a * a + b * b).
+ *                   rho > 1 or NaN: THE SAMPLE IS +0 IN ALL CHANNELS -- no path, no integrator draw, no ray counted.  rho == 0:
+ *                   direction forward.  Else theta = rho * fisheye_half_angle, direction right * (sin theta * (a / rho)) +
+ *                   up * (sin theta * (b / rho)) + forward * cos theta.  Origin `origin`.
+ *     EQUIRECT      lon = (2 s - 1) * RT_PI, lat = (2 t - 1) * RT_FRAC_PI_2, direction right * (cos lat * sin lon) + up * sin lat +
+ *                   forward * (cos lat * cos lon), origin `origin`.
+ *   The path: Naive / MisIntegrator::get_colour on Ray::new(origin, direction) on the stream (seed, p, n) FROM ITS FIRST DRAW (no
+ *     jitter and no camera time drawn on it): exactly sample n of rt_radiance with streams[i] = p.  That is why the camera has a stream
+ *     of its own.  A PERSPECTIVE FRAME AT lens_radius = 0 IS THEREFORE NOT rt_render's BYTES: the same rays in distribution, other
+ *     draws (rt_render jitters on the path's stream and draws the camera's unused time there).
+ *   The fold is rt_render_opts' own, as rt_render_tiles states it: the integrators' NaN filter, then sample_split 1 the running mean
+ *     `mean += (pass - mean) / i`; S > 1 the sums of the chunks [floor(c * spp / S), floor((c + 1) * spp / S)) in pass order from
+ *     +0, added in chunk order, divided by spp once; S = 0 resolved by rt_scene_auto_sample_split.  A black fisheye sample is folded
+ *     like any other.
+ *   chunk_sums (may be NULL; read only when the resolved S > 1): rt_render_tiles' layout for the list "all tiles ascending",
+ *     [chunk][64 * tile + 8 * (y & 7) + (x & 7)][3], 3 * S * 64 * ceil(W / 8) * ceil(H / 8) floats, padding lanes +0.  With the
+ *     buffer the launch hands out (tile, chunk) pairs and a second small kernel combines them; without it one lane folds all S
+ *     chunks of its pixel: the same bytes.
+ *   rays_shot (may be NULL) is WRITTEN, not added to: SamplerProgress.rays_shot as rt_render_tiles counts it.
+ *   rt_render_lens: HOST buffers, blocking; staged through scene-owned device memory.  rt_render_lens_device: DEVICE buffers on the
+ *     scene's GPU, asynchronous on `hip_stream`; allocates nothing, keeps no state on the scene, does not synchronise, can be
+ *     captured into a HIP graph from a scene's first call; launches on two streams may be in flight at once.
+ *   Errors, in rt_render_tiles' order: NULL scene / camera / opts / out, whatever rt_render_device refuses in opts, a chunk buffer
+ *     overlapping the frame, an unknown projection, a lens_radius that is not finite or is negative, a fisheye_half_angle that is
+ *     not finite and positive (the last two whatever the projection): RT_ERR_INVALID_ARGUMENT; then RT_ERR_UNSUPPORTED for
+ *     RT_LAYOUT_SHARD, shard_count != 1, a multi-device scene, 64 * tiles * S at or above 2^31 (2^31 pixels or more are refused
+ *     with the same code where rt_render_tiles refuses them: ahead of the resolution of sample_split); then RT_ERR_NO_DEVICE for a
+ *     host-only scene.
+ *   Which lane renders which pixel, the traversal mode, the walk and RT_TUNE_RADIANCE_GROUPS change no bit. ---- */
+typedef enum rt_projection {
+	RT_PROJ_PERSPECTIVE = 0,
+	RT_PROJ_ORTHOGRAPHIC = 1,
+	RT_PROJ_FISHEYE = 2,
+	RT_PROJ_EQUIRECT = 3
+} rt_projection;
+typedef struct rt_lens_camera {
+	rt_camera pinhole;        /* the four fields rt_camera_new writes, byte for byte */
+	float right[3];           /* SimpleCamera::new's u  (camera.rs:33) */
+	float up[3];              /* its v                  (camera.rs:34) */
+	float forward[3];         /* -w                     (camera.rs:32) */
+	float lens_radius;        /* aperture / 2 (camera.rs:51); used by PERSPECTIVE only */
+	float fisheye_half_angle; /* radians, the angle at the image circle's rim; FISHEYE only */
+	int32_t projection;       /* rt_projection */
+	uint32_t reserved0;       /* 0 */
+} rt_lens_camera;
+int rt_lens_camera_new(rt_lens_camera *out, const float origin[3], const float lookat[3], const float vup[3], float fov_degrees,
+                       float aspect_ratio, float aperture, float focus_dist, int32_t projection);
+int rt_render_lens(rt_scene *scene, const rt_lens_camera *camera, const rt_render_opts *opts, float *out_rgb,
+                   float *chunk_sums_or_null, uint64_t *rays_shot_or_null);
+int rt_render_lens_device(rt_scene *scene, const rt_lens_camera *camera, const rt_render_opts *opts, float *d_out_rgb,
+                          float *d_chunk_sums_or_null, uint64_t *d_rays_shot_or_null, void *hip_stream);
+
 /* ---- Firefly-robust frames (csrc/rt_robust.hip): a rank-trimmed mean of the chunk sums.  The integrator keeps the reference's
  * quirks, so one wild sample -- or one inf / NaN -- ends up in a pixel's mean, where no later stage can undo it.  The S
  * independent sums per pixel that a render at sample_split = S > 1 leaves in the scene's partial buffer (see the noise estimates

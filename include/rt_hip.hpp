@@ -78,6 +78,22 @@ class SimpleCamera { // camera.rs:6-54
 	rt_camera cam_{};
 };
 
+// SimpleCamera with the fields get_ray never reads in use (the thin lens: aperture > 0), or another projection (rt_hip.h
+// rt_lens_camera): what render_lens below takes
+class LensCamera {
+  public:
+	LensCamera(Vec3 origin, Vec3 lookat, Vec3 vup, float fov, float aspect_ratio, float aperture, float focus_dist,
+	           rt_projection projection = RT_PROJ_PERSPECTIVE)
+	{
+		const float o[3] = {origin.x, origin.y, origin.z}, l[3] = {lookat.x, lookat.y, lookat.z}, u[3] = {vup.x, vup.y, vup.z};
+		check(rt_lens_camera_new(&cam_, o, l, u, fov, aspect_ratio, aperture, focus_dist, (int32_t)projection));
+	}
+	const rt_lens_camera &raw() const { return cam_; }
+
+  private:
+	rt_lens_camera cam_{};
+};
+
 // Everything Bvh::new consumes.  Handles returned by the add-functions are indices, the way the
 // loader resolves names to RegionRes handles (loader/src/lib.rs:28-84).
 class SceneBuilder {
@@ -583,6 +599,16 @@ inline uint64_t render_tiles(const RenderOptions &o, const SimpleCamera &camera,
 	uint64_t rays = 0;
 	check(rt_render_tiles(bvh.raw(), &camera.raw(), &opts, tiles.data(), (uint32_t)tiles.size(), frame.data(), nullptr, &rays));
 	return rays;
+}
+// A whole frame (3 * width * height floats) through a lens camera: a thin lens, an orthographic, fisheye or equirectangular
+// projection (semantics: rt_hip.h rt_render_lens).  Not render's bytes even for a pinhole: the camera draws on a stream of its own.
+inline std::vector<float> render_lens(const RenderOptions &o, const LensCamera &camera, const Bvh &bvh, uint32_t sample_split = 1, uint64_t seed = 1,
+                                      uint64_t *rays_shot = nullptr)
+{
+	const rt_render_opts opts = detail::noise_render_opts(o, sample_split, seed, 0);
+	std::vector<float> frame(3 * (size_t)o.width * o.height);
+	check(rt_render_lens(bvh.raw(), &camera.raw(), &opts, frame.data(), nullptr, rays_shot));
+	return frame;
 }
 // The indices, ascending, of the tiles whose error is above `threshold` (strictly; NaN is not): what render_tiles takes next.
 inline std::vector<uint32_t> select_tiles(const Bvh &bvh, const std::vector<float> &tile_error, uint32_t width, uint32_t height, float threshold)

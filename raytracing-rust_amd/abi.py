@@ -374,6 +374,25 @@ class AdaptiveResult(C.Structure):  # rt_adaptive_result
     ]
 
 
+# lens cameras (rt_lens_camera_new, rt_render_lens)
+RT_PROJ_PERSPECTIVE, RT_PROJ_ORTHOGRAPHIC, RT_PROJ_FISHEYE, RT_PROJ_EQUIRECT = range(4)  # rt_projection
+PROJECTIONS = {"perspective": RT_PROJ_PERSPECTIVE, "orthographic": RT_PROJ_ORTHOGRAPHIC, "fisheye": RT_PROJ_FISHEYE,
+               "equirect": RT_PROJ_EQUIRECT}
+
+
+class LensCamera(C.Structure):  # rt_lens_camera
+    _fields_ = [
+        ("pinhole", Camera),
+        ("right", f32x3),
+        ("up", f32x3),
+        ("forward", f32x3),
+        ("lens_radius", C.c_float),
+        ("fisheye_half_angle", C.c_float),
+        ("projection", C.c_int32),
+        ("reserved0", C.c_uint32),
+    ]
+
+
 NOISE_SHAPES = {"mean": "hw3", "variance": "hw", "lum_mean": "hw", "tile_error": "tiles", "summary": "summary"}
 NOISE_CHANNELS = tuple(NOISE_SHAPES)
 
@@ -650,6 +669,7 @@ EXPECTED_SIZES = {
     "rt_noise_buffers": (NoiseBuffers, 40),
     "rt_noise_result": (NoiseResult, 40),
     "rt_adaptive_result": (AdaptiveResult, 40),
+    "rt_lens_camera": (LensCamera, 100),
     "rt_robust_opts": (RobustOpts, 32),
     "rt_robust_buffers": (RobustBuffers, 40),
     "rt_denoise_opts": (DenoiseOpts, 48),
@@ -755,6 +775,9 @@ EXPORTED_SYMBOLS = [
     "rt_render_tiles_device",
     "rt_noise_select_tiles",
     "rt_noise_select_tiles_device",
+    "rt_lens_camera_new",
+    "rt_render_lens",
+    "rt_render_lens_device",
     "rt_robust_opts_default",
     "rt_render_robust",
     "rt_render_robust_device",

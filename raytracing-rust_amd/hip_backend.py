@@ -323,6 +323,18 @@ def camera_new(origin, lookat, vup, fov, aspect_ratio, aperture, focus_dist):
     return cam
 
 
+def lens_camera_new(origin, lookat, vup, fov, aspect_ratio, aperture, focus_dist, projection="perspective"):
+    """rt_lens_camera_new: SimpleCamera::new with the fields get_ray never reads (u, v, lens_radius) kept, -w, the fisheye's
+    half angle (fov / 2, radians) and a projection: a name of abi.PROJECTIONS or an rt_projection value."""
+    if isinstance(projection, str):
+        _known(projection, abi.PROJECTIONS, "projection")
+        projection = abi.PROJECTIONS[projection]
+    cam = abi.LensCamera()
+    _check(lib().rt_lens_camera_new(C.byref(cam), _f3(origin), _f3(lookat), _f3(vup), C.c_float(fov), C.c_float(aspect_ratio),
+                                    C.c_float(aperture), C.c_float(focus_dist), C.c_int32(projection)))
+    return cam
+
+
 HIT_DTYPE = np.dtype([("t", "<f4"), ("point", "<f4", 3), ("error", "<f4", 3), ("normal", "<f4", 3), ("uv", "<f4", 2),
                       ("has_uv", "<i4"), ("out", "<i4"), ("material", "<u4"), ("found", "<u4"), ("index", "<u8")])
 NODE_DTYPE = np.dtype([("min", "<f4", 3), ("max", "<f4", 3), ("children", "<i8", 2), ("primitive_offset", "<u8"),
@@ -767,6 +779,28 @@ class HipScene:
         """rt_render_tiles_device: asynchronous, DEVICE buffers of the scene's GPU; allocates nothing, keeps no state."""
         _check(lib().rt_render_tiles_device(self._h, C.byref(camera), C.byref(opts), _dp(d_tiles, C.c_uint32), C.c_uint32(n_tiles),
                                             _dp(d_frame), _dp(d_chunk_sums), _vp(d_rays_ptr), C.c_void_p(stream)))
+
+    # ---- lens cameras (rt_render_lens): whole frames through a thin lens, a fisheye, a panorama or an orthographic camera ----
+    def render_lens(self, camera, opts, chunk_sums=False):
+        """rt_render_lens: the frame of an abi.LensCamera (lens_camera_new) under `opts`.  Returns (frame (H, W, 3) f32, rays_shot,
+        sums): sums is None, or with chunk_sums=True and a resolved split S > 1 the (S, ceil(H/8) * ceil(W/8), 8, 8, 3) chunk
+        sums, padding lanes of edge tiles +0.  A perspective frame at aperture 0 is NOT render()'s bytes: the camera draws on a
+        stream of its own."""
+        h, w = int(opts.height), int(opts.width)
+        frame = np.zeros((h, w, 3), dtype=np.float32)
+        sums = None
+        if chunk_sums:
+            split = int(opts.sample_split) or self.auto_sample_split(opts)
+            if split > 1:
+                sums = np.zeros((split, ((h + 7) // 8) * ((w + 7) // 8), 8, 8, 3), dtype=np.float32)
+        rays = C.c_uint64()
+        _check(lib().rt_render_lens(self._h, C.byref(camera), C.byref(opts), _p(frame, C.c_float), _p(sums, C.c_float), C.byref(rays)))
+        return frame, rays.value, sums
+
+    def render_lens_device(self, camera, opts, d_frame, d_chunk_sums=None, d_rays_ptr=None, stream=0):
+        """rt_render_lens_device: asynchronous, DEVICE buffers of the scene's GPU; allocates nothing, keeps no state."""
+        _check(lib().rt_render_lens_device(self._h, C.byref(camera), C.byref(opts), _dp(d_frame), _dp(d_chunk_sums), _vp(d_rays_ptr),
+                                           C.c_void_p(stream)))
 
     def noise_select_tiles(self, tile_error, threshold):
         """rt_noise_select_tiles: the indices (uint32, ascending) of the tiles of a (ceil(H/8), ceil(W/8)) f32 error map whose
