@@ -398,10 +398,14 @@ int rt_scene_set_traversal(rt_scene *scene, int mode);
  *                         samples of such tiles without a walk (rt_launch_info.sky_run; other kernels and other tilings ignore
  *                         it, and a shard of 2^30 pixels or more, padding included, runs the general spheres-only kernels).  A
  *                         tile is flagged only when its eight neighbours pass too.  Same pixels, same ray counts.  (Key 9 is
- *                         not assigned.) */
+ *                         not assigned.)
+ *   RT_TUNE_SKY_CELL      -1 automatic (default: on where the host could prove the guard for the scene's sky table), 0 off, 1 as
+ *                         -1: the kernels of rt_launch_info.feature_set = 3 carry the table cell of a sky direction they sampled
+ *                         from light sampling to its pdf and skip the acos / atan2 round trip for lanes inside the guard
+ *                         (rt_selftest_sky_cell reports the guard).  Same pixels, same ray counts. */
 typedef enum rt_tuning_key { RT_TUNE_TRAVERSAL = 0, RT_TUNE_FEATURE_SET = 1, RT_TUNE_SCENE_IN_LDS = 2, RT_TUNE_SCHEDULE = 3, RT_TUNE_WALK = 4,
                              RT_TUNE_STACK_CAP = 5, RT_TUNE_EXCHANGE = 6, RT_TUNE_WHOLE_PIXEL_SHARE = 7, RT_TUNE_RADIANCE_GROUPS = 8,
-                             RT_TUNE_SKY_RUN = 10 } rt_tuning_key;
+                             RT_TUNE_SKY_RUN = 10, RT_TUNE_SKY_CELL = 11 } rt_tuning_key;
 int rt_scene_set_tuning(rt_scene *scene, int key, int value);
 /* The work items of a render under `opts` at an explicit split with `share` sixteenths of the shard's tiles handed out as whole
  * pixels (RT_TUNE_WHOLE_PIXEL_SHARE): what rt_launch_info.whole_claims and .n_items report after such a render by a kernel that
@@ -1611,6 +1615,29 @@ int rt_selftest_div_forms(int device, const rt_div_forms_slice *slice, const flo
  * directions (3 * m floats, m in [1, 2^24]) on the scene's sky tables in global memory: out_pdf_pair[j] and out_pdf_default[j].  They
  * must be equal bit for bit.  Errors as rt_selftest_sky. */
 int rt_selftest_sky_pdf_forms(rt_scene *scene, const float *dirs, uint64_t m, float *out_pdf_pair, float *out_pdf_default);
+/* ... and the carried sky cell of the two-sphere kernels (csrc/rt_shade.h sky_sample_cell / sky_pdf_carried; RT_TUNE_SKY_CELL): for a
+ * direction light sampling drew from cell (su, sv) of the scene's sky table with jitters (r_u, r_v), the pdf as do_light -> do_scatter
+ * compute it -- the cell carried in one word, lanes outside the host-proven guard finding theirs by sky_pdf's round trip -- next to
+ * sky_pdf of the default sampling's direction.  Consecutive cases are consecutive lanes of a 64-lane wave.
+ *   cases != NULL: n in [1, 2^20] cases of four words (su, sv, bits of r_u, bits of r_v; su < res_x, sv < res_y, jitters in [0, 1));
+ *     out receives RT_SKY_CELL_OUT_WORDS words per case: bits of the carried pdf, bits of the default pdf, the cell the carried pdf was
+ *     read at (ui | vi << 16 | guard bit << 31) and the cell of the default (ui | vi << 16).  The pdf words must be equal, and the
+ *     cells too.
+ *   cases == NULL: the enumeration -- all 2^24 jitters of `axis` (0: u, 1: v) at cell (su, sv), the other jitter 0.5; out is not used.
+ * counts (RT_SKY_CELL_COUNTS): guarded lanes whose round-trip cell is not (su, sv) -- must be 0 --, unguarded lanes, unguarded lanes
+ * whose cells agree (the margin the guard leaves), pdf words that differ -- must be 0 --, lanes run.
+ * guard (RT_SKY_CELL_GUARD_WORDS): whether the host proved the guard for this table, whether the kernels are told so now
+ * (RT_TUNE_SKY_CELL), bits of delta_u and delta_v (f32), row_lo, row_hi, whether the library's kernels carry the cell at all.
+ * guard is filled first and for every scene -- a sky without sampler included, for which everything else fails as rt_selftest_sky
+ * does -- and with counts == NULL (and no cases) the call answers the guard alone, without a launch.  Errors as rt_selftest_sky. */
+enum { RT_SKY_CELL_GUARDED_DISAGREE = 0, RT_SKY_CELL_UNGUARDED = 1, RT_SKY_CELL_UNGUARDED_AGREE = 2, RT_SKY_CELL_PDF_MISMATCHES = 3, RT_SKY_CELL_TESTED = 4,
+       RT_SKY_CELL_COUNTS = 5 };
+enum { RT_SKY_CELL_OUT_WORDS = 4 };
+#define RT_SKY_CELL_NO_CELL 0x7FFFFFFFu /* both cell words (under the guard bit) where sin(theta) <= 0: the pdf is 0 and no cell is read */
+enum { RT_SKY_CELL_GUARD_PROVEN = 0, RT_SKY_CELL_GUARD_ENABLED = 1, RT_SKY_CELL_GUARD_DELTA_U = 2, RT_SKY_CELL_GUARD_DELTA_V = 3, RT_SKY_CELL_GUARD_ROW_LO = 4,
+       RT_SKY_CELL_GUARD_ROW_HI = 5, RT_SKY_CELL_GUARD_IN_USE = 6, RT_SKY_CELL_GUARD_WORDS = 8 };
+int rt_selftest_sky_cell(rt_scene *scene, const uint32_t *cases, uint64_t n, uint32_t axis, uint32_t su, uint32_t sv, uint32_t *out,
+                         uint64_t counts[RT_SKY_CELL_COUNTS], uint32_t guard[RT_SKY_CELL_GUARD_WORDS]);
 
 /* ---- self-test of the two-sphere kernels' scatter frame and ray normalisation (csrc/rt_shade.h coord_from_z_pair, csrc/
  * rt_intersect.h ray_new; the compile-time switches lean_frame_form and lean_ray_norm_short of csrc/rt_lean.h).  Runs ON `device`,

@@ -28,6 +28,7 @@ RT_METHOD_NAIVE, RT_METHOD_MIS = range(2)
 RT_LAYOUT_FRAME, RT_LAYOUT_SHARD = range(2)
 RT_TUNE_TRAVERSAL, RT_TUNE_FEATURE_SET, RT_TUNE_SCENE_IN_LDS, RT_TUNE_SCHEDULE, RT_TUNE_WALK, RT_TUNE_STACK_CAP, RT_TUNE_EXCHANGE, RT_TUNE_WHOLE_PIXEL_SHARE = range(8)
 RT_TUNE_RADIANCE_GROUPS = 8  # rt_radiance, rt_render_tiles: at most that many workgroups (0: automatic)
+RT_TUNE_SKY_CELL = 11  # two-sphere kernels: the sampled sky cell carried to its pdf (-1 automatic = on where proven, 0 off, 1 as -1)
 RT_TUNE_SKY_RUN = 10  # two-sphere kernels: tiles that can only see sky run without a walk (-1 automatic = on, 0 off, 1 on); 9 is unassigned
 
 NO_INDEX = 0xFFFFFFFFFFFFFFFF  # usize::MAX
@@ -737,6 +738,7 @@ EXPORTED_SYMBOLS = [
     "rt_selftest_short_forms",
     "rt_selftest_div_forms",
     "rt_selftest_sky_pdf_forms",
+    "rt_selftest_sky_cell",
     "rt_selftest_frame_forms",
     "rt_selftest_gen_keys",
     "rt_philox_round_keys",

@@ -358,6 +358,11 @@ static int upload_scene(rt_scene *s, const HostScene &h)
 		if (!verified_reciprocal(RT_PI, &rc_pi) || !verified_reciprocal(RT_TAU, &rc_tau) || rc_pi != 1.0f / RT_PI || rc_tau != 1.0f / RT_TAU)
 			return bail(fail(RT_ERR_UNSUPPORTED, "self-check failed: division by pi / 2 pi through their reciprocals is not exact on this host (the kernels assume it)"));
 		sky_reciprocals(h.sky, &D.sky.inv_res_ok, &D.sky.inv_res_x, &D.sky.inv_res_y);
+		{ // the carried sky cell's guard, proven for this table or off (rt_sky_cell.h; rt_shade.h sky_sample_cell)
+			const SkyCellGuard g = sky_cell_guard(h.sky.sampler_res_x, h.sky.sampler_res_y, D.sky.inv_res_ok != 0u);
+			s->sky_cell_proven = g.ok;
+			s->sky_cell = DevSkyCell{g.ok, g.half_u, g.half_v, g.row_lo, g.row_span, {0u, 0u, 0u}};
+		}
 		// Lambertian numerators (rt_shade.h cosine_is_tame_): SolidColour textures, |colour x albedo| components zero or in
 		// [2^-30, 2^30], vertex normals finite and below 2^20
 		bool tame = true;
@@ -734,6 +739,11 @@ static int set_tuning_one(rt_scene *s, int key, int value)
 		if (value < -1 || value > 1)
 			return fail(RT_ERR_INVALID_ARGUMENT, "sky run must be -1 (automatic), 0 (off) or 1 (on where the kernel has it)");
 		s->sky_run = value;
+		return RT_OK;
+	case RT_TUNE_SKY_CELL:
+		if (value < -1 || value > 1)
+			return fail(RT_ERR_INVALID_ARGUMENT, "sky cell must be -1 (automatic), 0 (off) or 1 (on where the guard is proven)");
+		s->sky_cell.ok = value != 0 ? s->sky_cell_proven : 0u;
 		return RT_OK;
 	default:
 		return fail(RT_ERR_INVALID_ARGUMENT, "unknown tuning key");
@@ -1531,7 +1541,7 @@ int rt_render_device(rt_scene *s, const rt_camera *camera, const rt_render_opts 
 	HIP_TRY(hipEventRecord(s->ev_start, stream));
 	HIP_TRY(launch_render(o->render_method, plan.prune, plan.fine, plan.sky_lds, plan.feature_set, plan.n_blocks, plan.lds_bytes, stream, plan.dev, cam, P,
 	                      render_target, reinterpret_cast<unsigned long long *>(d_rays_shot), s->d_work_counter, s->d_stack_ovf, plan.xchg,
-	                      plan.feature_set == 3 ? &s->pair : nullptr, plan.feature_set == 3 ? &primary : nullptr, plan.block_threads, sky_tiles));
+	                      plan.feature_set == 3 ? &s->pair : nullptr, plan.feature_set == 3 ? &primary : nullptr, plan.block_threads, sky_tiles, s->sky_cell));
 	HIP_TRY(hipEventRecord(s->ev_stop, stream));
 	if (plan.split > 1u)
 		HIP_TRY(launch_combine(stream, P, s->d_partial, d_out_rgb));

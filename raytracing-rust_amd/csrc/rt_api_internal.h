@@ -14,6 +14,7 @@
 #include "rt_layout.h"
 #include "rt_types.h"
 #include "rt_sky_tiles.h"
+#include "rt_sky_cell.h"
 
 // the text behind rt_last_error(): ONE per thread for the whole library (defined in rt_api.cpp)
 extern thread_local std::string g_error;
@@ -86,6 +87,8 @@ struct rt_scene {
 	int whole_share = kWholeShareDefault; // RT_TUNE_WHOLE_PIXEL_SHARE
 	uint32_t radiance_groups = 0;    // RT_TUNE_RADIANCE_GROUPS (rt_radiance and rt_render_tiles)
 	int sky_run = -1;                // RT_TUNE_SKY_RUN: -1 automatic (on where the kernel has it), 0 off, 1 on
+	rt::DevSkyCell sky_cell = {};    // the carried sky cell's guard for this scene's sky (rt_sky_cell.h), as the two-sphere kernels are told it
+	uint32_t sky_cell_proven = 0;    // sky_cell_guard(...).ok: what RT_TUNE_SKY_CELL != 0 puts in sky_cell.ok
 	uint32_t stack_depth_narrow = 2; // HostScene::stack_depth_narrow (members of a multi-device scene have no host scene of their own)
 	uint32_t *d_stack_ovf = nullptr; // traversal-stack overflow area (deep trees under the fine schedule), grown on demand
 	size_t stack_ovf_words = 0;

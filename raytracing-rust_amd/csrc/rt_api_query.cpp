@@ -431,6 +431,62 @@ int rt_selftest_sky_pdf_forms(rt_scene *s, const float *dirs, uint64_t m, float 
 	return sky_finish(st, L, "selftest_sky_pdf_forms");
 }
 
+int rt_selftest_sky_cell(rt_scene *s, const uint32_t *cases, uint64_t n, uint32_t axis, uint32_t su, uint32_t sv, uint32_t *out, uint64_t counts[RT_SKY_CELL_COUNTS],
+                         uint32_t guard[RT_SKY_CELL_GUARD_WORDS])
+{
+	if (!s || !guard || (cases && (!out || n == 0 || n > (1ull << 20))))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (1 to 2^20 cases with their output, or no cases)");
+	const uint32_t rx = s->host.sky.sampler_res_x, ry = s->host.sky.sampler_res_y;
+	{ // the guard first: it is answered for every scene, a sky without sampler included, and alone when counts is null
+		const SkyCellGuard g = sky_cell_guard(rx, ry, s->dev.sky.inv_res_ok != 0u);
+		const float du = (float)g.delta_u, dv = (float)g.delta_v;
+		std::memset(guard, 0, RT_SKY_CELL_GUARD_WORDS * sizeof(uint32_t));
+		guard[RT_SKY_CELL_GUARD_PROVEN] = g.ok;
+		guard[RT_SKY_CELL_GUARD_ENABLED] = s->sky_cell.ok;
+		std::memcpy(&guard[RT_SKY_CELL_GUARD_DELTA_U], &du, 4);
+		std::memcpy(&guard[RT_SKY_CELL_GUARD_DELTA_V], &dv, 4);
+		guard[RT_SKY_CELL_GUARD_ROW_LO] = g.row_lo;
+		guard[RT_SKY_CELL_GUARD_ROW_HI] = g.row_lo + g.row_span;
+		guard[RT_SKY_CELL_GUARD_IN_USE] = sky_cell_in_use() ? 1u : 0u;
+	}
+	if (!counts)
+		return cases ? fail(RT_ERR_INVALID_ARGUMENT, "bad arguments (cases need counts)") : RT_OK;
+	if ((rx | ry) == 0u)
+		return fail(RT_ERR_INVALID_ARGUMENT, "the sky is not samplable (sampler_res 0 x 0)");
+	if (!cases && (axis > 1u || su >= rx || sv >= ry))
+		return fail(RT_ERR_INVALID_ARGUMENT, "bad enumeration (axis 0 or 1, a cell of the table)");
+	if (rx >= kSkyCellMaxRes || ry >= kSkyCellMaxRes)
+		return fail(RT_ERR_UNSUPPORTED, "the cell word holds resolutions below 2^15");
+	for (uint64_t i = 0; cases && i < n; ++i) {
+		float r[2];
+		std::memcpy(r, cases + 4 * i + 2, sizeof r);
+		if (cases[4 * i] >= rx || cases[4 * i + 1] >= ry || !(r[0] >= 0.0f && r[0] < 1.0f && r[1] >= 0.0f && r[1] < 1.0f))
+			return fail(RT_ERR_INVALID_ARGUMENT, "bad case (a cell of the table, jitters in [0, 1))");
+	}
+	if (int rc = need_device(s); rc != RT_OK)
+		return rc;
+	const uint64_t n_run = cases ? n : 1ull << 24;
+	Layout L; // counters, then the cases and their results
+	const auto p_counts = L.add<unsigned long long>(RT_SKY_CELL_COUNTS);
+	const auto p_cases = L.add<uint32_t>(cases ? 4 * n : 4), p_out = L.add<uint32_t>(cases ? RT_SKY_CELL_OUT_WORDS * n : 4);
+	RT_TRY(sky_buffer(s, L));
+	Staging st{s};
+	const unsigned long long zero[RT_SKY_CELL_COUNTS] = {};
+	unsigned long long host[RT_SKY_CELL_COUNTS] = {};
+	st.put(L, p_counts, zero);
+	if (cases)
+		st.put(L, p_cases, cases);
+	if (st.ok())
+		st.e = launch_sky_cell(s->stream, s->dev, s->sky_cell, cases ? L.at(p_cases) : nullptr, n_run, L.at(p_out), L.at(p_counts), axis, su, sv);
+	st.get(host, L, p_counts);
+	if (cases)
+		st.get(out, L, p_out);
+	const int rc = sky_finish(st, L, "selftest_sky_cell");
+	for (int k = 0; k < RT_SKY_CELL_COUNTS; ++k)
+		counts[k] = host[k];
+	return rc;
+}
+
 int rt_selftest_pair_shadow(int device, const float *cases, uint64_t n_cases, uint64_t counts[RT_PAIR_SHADOW_COUNTS])
 {
 	return run_case_table<RT_PAIR_SHADOW_COUNTS>(device, cases, n_cases, RT_PAIR_SHADOW_CASE_FLOATS * sizeof(float), counts, "selftest_pair_shadow",

@@ -165,6 +165,14 @@ constexpr LeanFrameForm lean_frame_form(bool pair) { return pair && RT_PAIR_FRAM
 constexpr bool lean_gen_keys(bool pair) { return pair && RT_PAIR_GEN_KEYS != 0; }
 constexpr int lean_gen_keys_lead(bool pair) { return lean_gen_keys(pair) ? RT_PAIR_GEN_KEYS - 1 : 0; }
 constexpr bool lean_gen_item_product(bool pair) { return lean_gen_keys(pair) && RT_PAIR_GEN_ITEM_PRODUCT != 0; }
+// ... and one for the sky pdf of the direction LIGHT sampled itself (rt_shade.h sky_sample_cell / sky_pdf_carried): the table cell
+// travels from do_light to do_scatter in one word, and lanes a host-proven guard puts safely inside their cell skip the
+// acos / atan2 round trip that would only find it again.  -DRT_PAIR_SKY_CELL=0 compiles it out: do_light and do_scatter are then
+// sky_sample and sky_pdf<true>, as before.  Measured: profiles/r27_sky_cell_ab.log, HISTORY.md.
+#ifndef RT_PAIR_SKY_CELL
+#define RT_PAIR_SKY_CELL 1
+#endif
+constexpr bool lean_sky_cell(bool pair) { return pair && RT_PAIR_SKY_CELL != 0; }
 
 #if defined(__HIP_DEVICE_COMPILE__)
 // ---- device: hipcc's f32 division and square root without the identity steps (see the header comment) ----

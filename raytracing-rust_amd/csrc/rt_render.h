@@ -23,7 +23,7 @@ hipError_t launch_reset(hipStream_t stream, uint32_t *work_counter, unsigned lon
 hipError_t launch_render(int method, bool prune, bool fine, bool sky_lds, int feature_set, uint32_t n_blocks, size_t lds_bytes, hipStream_t stream,
                          const DevScene &S, const DevCamera &cam, const DevRenderParams &P, float *out,
                          unsigned long long *rays_shot, uint32_t *work_counter, uint32_t *stack_ovf, bool xchg, const DevPairScene *pair,
-                         const DevPairPrimary *primary, uint32_t block_threads, const DevSkyTiles &sky_tiles);
+                         const DevPairPrimary *primary, uint32_t block_threads, const DevSkyTiles &sky_tiles, const DevSkyCell &sky_cell);
 hipError_t launch_combine(hipStream_t stream, const DevRenderParams &P, const float *partial, float *out);
 // ---- multi-device scenes, output ----
 hipError_t launch_scatter_shard(hipStream_t stream, const DevRenderParams &P, const float *shard, float *frame);

@@ -256,6 +256,7 @@ struct RenderArgs {
 	DevPairPrimary primary; // FeatPair only: the origin-only terms of this render's primary walks
 	DevGenKeys gen_keys; // FeatPair only: the Philox round keys of this render's seed (rt_gen_keys.h)
 	DevSkyTiles sky_tiles; // FeatPair only: what the per-tile sky proof reads (rt_sky_tiles.h); enabled = 0: no claim is flagged
+	DevSkyCell sky_cell; // FeatPair only: the guard of the carried sky cell (rt_shade.h sky_sample_cell); ok = 0: no lane is guarded
 };
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const __attribute__((address_space(4))) RenderArgs *KArgs; // the kernarg segment is constant memory: s_load
@@ -487,6 +488,15 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 	PL.pdf_multiplier = 1.0f;
 	PL.t_limit = 0.0f;
 	PL.skip = kNoPrim;
+	// kSkyCell (the two-sphere kernels, coarse schedule only): the table cell a sky direction was drawn from and its guard bit, from
+	// do_light to do_scatter of the same iteration (rt_shade.h sky_sample_cell).  A word of its own, not a member of the context: every
+	// other kernel's context, and with it every other kernel, stays what it was.
+	constexpr bool kSkyCell = lean_sky_cell(F::pair);
+	// (the fine schedule keeps a light sample across iterations in PL and the exchange parks PL in its records: neither carries this word)
+	static_assert(!kSkyCell || (!FINE && !XCHG), "the carried sky cell lives from do_light to do_scatter of ONE coarse iteration");
+	uint32_t light_sky_cell = 0u;
+	// where DevSkyCell lies behind DevSky::inv_res_ok in the kernel arguments, in words
+	constexpr uint32_t kCellFromInv = (uint32_t)((offsetof(RenderArgs, sky_cell) - offsetof(RenderArgs, S) - offsetof(DevScene, sky) - offsetof(DevSky, inv_res_ok)) / 4u);
 	PL.have_shadow = PL.shadow_is_sky = false;
 
 	// start a walk of `ray`: the root test of Bvh::get_intersection_candidates (mod.rs:203-210)
@@ -674,6 +684,7 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 
 #ifdef RT_STATS
 	unsigned long long st_lane_nodes = 0, st_lane_prims = 0, st_lane_maxsp = 0, st_sky_samples = 0, st_sky_runs = 0, st_sky_clock = 0, st_allsky_clock = 0, st_allsky_iters = 0, st_iter_t0 = 0;
+	unsigned long long st_cell[4] = {}; // kSkyCell, do_scatter's sky pdf (per lane: the first evaluating lane of an iteration counts it)
 #endif
 	// NODE -- one inner-node step: Bvh::get_intersection_candidates' loop body (mod.rs:203-221)
 	auto do_node = [&]() {
@@ -906,7 +917,10 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 		g.type = g.material = 0u;
 		g.p0 = g.p1 = g.p2 = v3s(0.0f);
 		if (pick_sky) {
-			L.l_wi = sky_sample(S, T, rng);
+			if constexpr (kSkyCell)
+				L.l_wi = sky_sample_cell(S, T, rng, light_sky_cell, kCellFromInv);
+			else
+				L.l_wi = sky_sample(S, T, rng);
 			RT_SECTION(9); // LIGHT: sky_sample
 			L.t_limit = __uint_as_float(0x7FC00000u); // NaN: any t > 0 occludes
 			L.have_shadow = true;
@@ -948,7 +962,22 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 			float l_pdf = 0.0f;
 			if (L.shadow_is_sky) { // sample_sky  mis.rs:104-115
 				le = emission_of_hit<F>(S, PS, S.sky.material, true, hit, L.l_wi);
-				l_pdf = sky_pdf<F::pair>(S, T, L.l_wi) * L.pdf_multiplier;
+				if constexpr (kSkyCell) {
+#ifdef RT_STATS
+					{ // how often the wave skips the round trip: evaluating iterations, lanes, guarded lanes, all-guarded iterations
+						const unsigned long long m_eval = __ballot(true), m_ok = __ballot((light_sky_cell >> 31) != 0u);
+						if (lane == (uint32_t)__builtin_ctzll(m_eval)) {
+							st_cell[0] += 1;
+							st_cell[1] += (unsigned long long)__popcll(m_eval);
+							st_cell[2] += (unsigned long long)__popcll(m_ok);
+							st_cell[3] += m_ok == m_eval ? 1ull : 0ull;
+						}
+					}
+#endif
+					l_pdf = sky_pdf_carried(S, T, L.l_wi, light_sky_cell) * L.pdf_multiplier;
+				} else {
+					l_pdf = sky_pdf<F::pair>(S, T, L.l_wi) * L.pdf_multiplier;
+				}
 				valid = true;
 			} else { // sample_light  mis.rs:117-133 (`ray` still is the shadow ray)
 				Hit lh;
@@ -1822,6 +1851,8 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 					L.pdf_multiplier = 1.0f;
 					L.t_limit = 0.0f;
 					L.skip = kNoPrim;
+					if constexpr (kSkyCell)
+						light_sky_cell = 0u; // (written before it is read in every iteration: not loop-carried)
 					L.have_shadow = L.shadow_is_sky = false;
 					Ray sray;
 					sray.o = sray.d = sray.inv = sray.shear = v3s(0.0f);
@@ -1886,6 +1917,8 @@ __global__ __launch_bounds__((KernelShape<F, FINE, XCHG>::max_block), (KernelSha
 	atomicAdd(&g_stats[20], st_lane_nodes); // lane-level node steps and primitive tests of the fine schedule
 	atomicAdd(&g_stats[21], st_lane_prims);
 	atomicMax(&g_stats[22], st_lane_maxsp);
+	for (int k = 0; k < 4; ++k) // [32..35]: iterations that evaluate do_scatter's sky pdf, their lanes, the guarded ones, all-guarded iterations
+		atomicAdd(&g_stats[32 + k], st_cell[k]);
 	if (lane == 0u) {
 		for (int k = 0; k < 9; ++k)
 			atomicAdd(&g_stats[40 + k], st_sect[k]);
@@ -2217,7 +2250,7 @@ hipError_t render_occupancy(int method, bool prune, bool fine, bool sky_lds, int
 hipError_t launch_render(int method, bool prune, bool fine, bool sky_lds, int feature_set, uint32_t n_blocks, size_t lds_bytes, hipStream_t stream,
                          const DevScene &S, const DevCamera &cam, const DevRenderParams &P, float *out,
                          unsigned long long *rays_shot, uint32_t *work_counter, uint32_t *stack_ovf, bool xchg, const DevPairScene *pair,
-                         const DevPairPrimary *primary, uint32_t block_threads, const DevSkyTiles &sky_tiles)
+                         const DevPairPrimary *primary, uint32_t block_threads, const DevSkyTiles &sky_tiles, const DevSkyCell &sky_cell)
 {
 	render_fn fn = pick_render(method, prune, fine, sky_lds, feature_set, xchg);
 	if (!fn)
@@ -2232,6 +2265,7 @@ hipError_t launch_render(int method, bool prune, bool fine, bool sky_lds, int fe
 	A.stack_ovf = stack_ovf;
 	A.pair = pair ? *pair : DevPairScene{};
 	A.primary = primary ? *primary : DevPairPrimary{};
+	A.sky_cell = sky_cell;
 	A.sky_tiles = sky_tiles; // (enabled = 0 for every launch but a two-sphere one with the run on: rt_api_internal.h sky_tiles_block)
 	philox_round_keys(((uint64_t)P.seed_hi << 32) | P.seed_lo, A.gen_keys);
 	hipLaunchKernelGGL(fn, dim3(n_blocks), dim3(block_threads ? block_threads : render_block_threads(feature_set, fine, xchg)), lds_bytes, stream, A);

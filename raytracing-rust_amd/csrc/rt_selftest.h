@@ -59,6 +59,10 @@ uint32_t div_forms_in_use(); // bit k: the render kernels' guarded divisions use
 hipError_t launch_div_forms(hipStream_t stream, const DevDivForms &D);
 hipError_t launch_div_sites(hipStream_t stream, const float *operand_pairs, uint64_t n_pairs, unsigned long long *counts);
 hipError_t launch_sky_pdf_forms(hipStream_t stream, const DevScene &S, const float *dirs, uint64_t m, float *out_pair, float *out_default);
+// rt_selftest_sky_cell (rt_selftest_forms.hip): cases (su, sv, bits of r_u, bits of r_v), or cases == null: all n = 2^24 jitters of `axis` at (su, sv)
+hipError_t launch_sky_cell(hipStream_t stream, const DevScene &S, const DevSkyCell &guard, const uint32_t *cases, uint64_t n, uint32_t *out, unsigned long long *counts, uint32_t axis,
+                           uint32_t su, uint32_t sv);
+bool sky_cell_in_use(); // rt_lean.h lean_sky_cell(true)
 
 // rt_selftest_frame_forms (rt_selftest_forms.hip): n vectors of 3 floats, counts[RT_FRAME_FORMS_COUNTS] zeroed by the caller (the
 // kernel leaves RT_FRAME_FORMS_IN_USE alone: the caller fills it from frame_forms_in_use)

@@ -326,6 +326,95 @@ hipError_t launch_sky_pdf_forms(hipStream_t stream, const DevScene &S, const flo
 	return launch_cases(sky_pdf_forms_kernel, stream, m, 2048u, A);
 }
 
+// rt_selftest_sky_cell: the carried sky cell (rt_shade.h sky_direction_<true> -> sky_pdf_carried_, what do_light hands do_scatter in the
+// two-sphere kernels) next to sky_pdf<true> at sky_direction_<false>'s direction, tables in global memory, the guard's words read
+// through the kernarg pointer as render_kernel reads them.  Consecutive cases are consecutive lanes of a wave: the caller's order
+// decides which waves are all guarded, all unguarded or mixed.  cases == null: the enumeration -- case i is jitter i 2^-24 on
+// `axis` (0: u, 1: v) of cell (su, sv), the other axis at 0.5.
+struct SkyCellSelftestArgs {
+	DevScene S;
+	DevSkyCell guard;
+	const uint32_t *cases; // su, sv, bits of r_u, bits of r_v
+	uint64_t n;
+	uint32_t *out;         // RT_SKY_CELL_OUT_WORDS per case (cases only)
+	unsigned long long *counts;
+	uint32_t axis, su, sv;
+};
+constexpr uint32_t kCellFromInv =
+    (uint32_t)((offsetof(SkyCellSelftestArgs, guard) - offsetof(SkyCellSelftestArgs, S) - offsetof(DevScene, sky) - offsetof(DevSky, inv_res_ok)) / 4u);
+__global__ __launch_bounds__(256) void sky_cell_kernel(const SkyCellSelftestArgs args_by_value)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	const auto *A = (const __attribute__((address_space(4))) SkyCellSelftestArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+	(void)args_by_value;
+#else
+	const SkyCellSelftestArgs *A = &args_by_value;
+#endif
+	const DevScene S = A->S;
+	SkyTables T;
+	T.row_cdf = S.sky.row_cdf;
+	T.marginal_cdf = S.sky.marginal_cdf;
+	T.guide = S.sky.guide;
+	T.guide_k = S.sky.guide_k;
+	T.inv_res = reinterpret_cast<KWords>(&A->S.sky.inv_res_ok);
+	const uint32_t *const cases = A->cases;
+	uint32_t *const out = A->out;
+	const uint32_t axis = A->axis, su0 = A->su, sv0 = A->sv;
+	Tally<RT_SKY_CELL_COUNTS> tally;
+	for_each_case(A->n, [&](uint64_t i) {
+		uint32_t su = su0, sv = sv0;
+		float r_u = 0.5f, r_v = 0.5f;
+		if (cases) {
+			su = cases[4u * i];
+			sv = cases[4u * i + 1u];
+			r_u = __uint_as_float(cases[4u * i + 2u]);
+			r_v = __uint_as_float(cases[4u * i + 3u]);
+		} else {
+			(axis == 0u ? r_u : r_v) = (float)(uint32_t)i * 0x1p-24f;
+		}
+		uint32_t cell, unused;
+		const float nu = next_float((float)su + r_u), nv = next_float((float)sv + r_v); // (as sky_sample forms them)
+		const V3 d = sky_direction_<true>(T, S.sky.res_x, S.sky.res_y, su, sv, r_u, r_v, nu, nv, cell, kCellFromInv);
+		const V3 d_default = sky_direction_<false>(T, S.sky.res_x, S.sky.res_y, su, sv, r_u, r_v, nu, nv, unused);
+		uint32_t ui, vi, rx, ry;
+		const float got = sky_pdf_carried_(S, T, d, cell, ui, vi);
+		const float want = sky_pdf<true>(S, T, d_default);
+		const SkyCell c = sky_pdf_cell<true>(S, d_default, rx, ry);
+		const bool guarded = (cell >> 31) != 0u, agree = c.ui == su && c.vi == sv;
+		tally.add(RT_SKY_CELL_GUARDED_DISAGREE, guarded && !agree);
+		tally.add(RT_SKY_CELL_UNGUARDED, !guarded);
+		tally.add(RT_SKY_CELL_UNGUARDED_AGREE, !guarded && agree);
+		tally.add(RT_SKY_CELL_PDF_MISMATCHES, !same_f32(got, want));
+		tally.add(RT_SKY_CELL_TESTED);
+		if (cases) {
+			uint32_t *o = out + RT_SKY_CELL_OUT_WORDS * i;
+			o[0] = __float_as_uint(got);
+			o[1] = __float_as_uint(want);
+			// (sin_theta <= 0: both pdfs are 0 and neither reads a cell)
+			const bool reads = sqrt_unit_(1.0f - d_default.z * d_default.z) > 0.0f;
+			o[2] = reads ? ui | vi << 16 | (cell & 0x80000000u) : RT_SKY_CELL_NO_CELL | (cell & 0x80000000u);
+			o[3] = reads ? c.ui | c.vi << 16 : RT_SKY_CELL_NO_CELL;
+		}
+	});
+	tally.flush(A->counts);
+}
+hipError_t launch_sky_cell(hipStream_t stream, const DevScene &S, const DevSkyCell &guard, const uint32_t *cases, uint64_t n, uint32_t *out, unsigned long long *counts, uint32_t axis,
+                           uint32_t su, uint32_t sv)
+{
+	SkyCellSelftestArgs A;
+	A.S = S;
+	A.guard = guard;
+	A.cases = cases;
+	A.n = n;
+	A.out = out;
+	A.counts = counts;
+	A.axis = axis;
+	A.su = su;
+	A.sv = sv;
+	return launch_cases(sky_cell_kernel, stream, n, 2048u, A);
+}
+bool sky_cell_in_use() { return lean_sky_cell(true); }
+
 // rt_selftest_frame_forms: the scatter frame and Ray::new's normalisation as the two-sphere kernels' switches select them
 // (rt_lean.h lean_frame_form, lean_ray_norm_short) next to the plain expressions, each vector as a normal and as a direction.
 // The plain frame is kept out of line so that nothing is shared with the short form.

@@ -410,12 +410,13 @@ __device__ __forceinline__ bool sky_can_sample(const DevScene &S) { return (S.sk
 // (SHORT: the two-sphere kernels' instantiation -- atan2's octant fold through the one-pair quotient, rt_lean.h lean_atan2_for.  The
 // final division stays plain there too: its numerator is a product of table differences, zero for a zero-pdf cell and without a
 // lower bound otherwise, and the two compares that would admit it cost what the short form saves)
-template <bool SHORT = false> __device__ __forceinline__ float sky_pdf(const DevScene &S, const SkyTables &T, V3 wi)
+// The table cell Distribution2D::pdf reads at wi, clamps included: sky_pdf's lines from the angles to the clamps.  rx, ry come back
+// for the tail below.  (Callers have returned already when sin_theta <= 0.)
+struct SkyCell {
+	uint32_t ui, vi;
+};
+template <bool SHORT = false> __device__ __forceinline__ SkyCell sky_pdf_cell(const DevScene &S, V3 wi, uint32_t &rx, uint32_t &ry)
 {
-	// 1 - z * z is zero, negative, NaN or >= 2^-24: inside the range of the short square root (rt_lean.h)
-	const float sin_theta = sqrt_unit_(1.0f - wi.z * wi.z);
-	if (sin_theta <= 0.0f)
-		return 0.0f;
 	const float theta = lean_acos_dev(wi.z);
 	float phi = SHORT ? lean_atan2_for<true>(wi.y, wi.x) : lean_atan2(wi.y, wi.x);
 	if (phi < 0.0f)
@@ -427,29 +428,71 @@ template <bool SHORT = false> __device__ __forceinline__ float sky_pdf(const Dev
 	// index below is 0 both ways.  (2.0f * kPi is kTau exactly: doubling a float is exact.)
 	const float u = div_by_verified(phi, kTau, kRcpTau);
 	const float v = div_by_verified(theta, kPi, kRcpPi);
-	const uint32_t rx = here_(S.sky.res_x), ry = here_(S.sky.res_y);
-	uint32_t ui = f32_as_index((float)rx * u);
-	uint32_t vi = f32_as_index((float)ry * v);
-	ui = ui > rx - 1u ? rx - 1u : ui;
-	vi = vi > ry - 1u ? ry - 1u : vi;
+	rx = here_(S.sky.res_x);
+	ry = here_(S.sky.res_y);
+	SkyCell c;
+	c.ui = f32_as_index((float)rx * u);
+	c.vi = f32_as_index((float)ry * v);
+	c.ui = c.ui > rx - 1u ? rx - 1u : c.ui;
+	c.vi = c.vi > ry - 1u ? ry - 1u : c.vi;
+	return c;
+}
+// ... and from the cell to the pdf: the four table entries and the final quotient
+__device__ __forceinline__ float sky_pdf_from_cell(const SkyTables &T, uint32_t ui, uint32_t vi, uint32_t rx, uint32_t ry, float sin_theta)
+{
 	// pdf[i] = cdf[i+1] - cdf[i]: the subtraction Distribution1D::new performs (:32-38)
 	const float ypdf = T.marginal_cdf[vi + 1u] - T.marginal_cdf[vi];
 	const float *row = T.row_cdf + (size_t)vi * (rx + 1u);
 	const float xpdf = row[ui + 1u] - row[ui];
 	return (float)rx * (float)ry * (ypdf * xpdf) / (sin_theta * kTau * kPi);
 }
-
-// Sky::sample  sky.rs:64-78
-__device__ __forceinline__ V3 sky_sample(const DevScene &S, const SkyTables &T, rt_rng &rng)
+template <bool SHORT = false> __device__ __forceinline__ float sky_pdf(const DevScene &S, const SkyTables &T, V3 wi)
 {
-	const uint32_t rx = here_(S.sky.res_x), ry = here_(S.sky.res_y);
-	const bool guided = T.guide_k != 0u;
-	const uint32_t sv = dist1d_sample(T.marginal_cdf, ry, guided ? T.guide + (size_t)ry * T.guide_k : nullptr, T.guide_k, rng);
-	const uint32_t su = dist1d_sample(T.row_cdf + (size_t)sv * (rx + 1u), rx, guided ? T.guide + (size_t)sv * T.guide_k : nullptr, T.guide_k, rng);
-	// next_float(cell + r) is the smallest subnormal (cell = r = 0) or lies in [2^-24, 256]: the verified two-fma division applies
-	// (for the subnormal both forms return it unchanged when the table has one cell and zero otherwise: 2^-149 / n rounds to 0 for
-	// n >= 2, and x * rc underflows to 0 with a zero correction)
-	const float nu = next_float((float)su + rt_rng_f32(&rng)), nv = next_float((float)sv + rt_rng_f32(&rng));
+	// 1 - z * z is zero, negative, NaN or >= 2^-24: inside the range of the short square root (rt_lean.h)
+	const float sin_theta = sqrt_unit_(1.0f - wi.z * wi.z);
+	if (sin_theta <= 0.0f)
+		return 0.0f;
+	uint32_t rx, ry;
+	const SkyCell c = sky_pdf_cell<SHORT>(S, wi, rx, ry);
+	return sky_pdf_from_cell(T, c.ui, c.vi, rx, ry, sin_theta);
+}
+
+// Sky::sample  sky.rs:64-78.  CELL (the two-sphere kernels, rt_lean.h lean_sky_cell): `cell` also receives su | sv << 16 | ok << 31,
+// the table cell the direction was drawn from and the guard bit that lets sky_pdf_carried (below) read the pdf at that cell.
+//
+// THE GUARD AND WHY IT HOLDS.  ok is set when the scene's flag is on (DevSkyCell::ok, rt_sky_cell.h sky_cell_guard: both resolutions in
+// [1, 2^15), ry >= 3, both reciprocals verified), both jitters r satisfy |r - 0.5| <= 0.5 - delta of their axis (r and delta are
+// multiples of 2^-24 below 1, so r - 0.5 and 0.5 - delta are exact: the test is delta <= r <= 1 - delta) and row_lo <= sv <= row_hi
+// with row_lo = 1, row_hi = ry - 2.  Claim: for such a lane sky_pdf<true> at the direction returned here computes ui == su,
+// vi == sv and sin_theta > 0.  Write e = 2^-24 (every IEEE operation below is (1 + t), |t| <= e; an ulp of x is at most 2 e |x|).
+//   v axis.  a = RN(sv + r_v) and nv = next_float(a) differ from sv + r_v by at most 3 e (sv + 1).  v = nv / ry (either form: the
+//   bits of the division), theta_f = RN(v kPi): theta_f = (sv + r_v + e1) / ry * kPi * (1 + 2 e).  ct = lean_sincos's cosine: within
+//   2 ulp of cos(theta_f) (rt_detmath.h: sin, cos <= 2 ulp; the three-term reduction adds at most 2^-45), so |ct - cos theta_f| <=
+//   4 e + 2^-45 =: c.  Let s_edge = sin(pi row_lo / ry) (as a real number of kPi's units: the angles of the cell edges are
+//   k kPi / ry), the smallest sine over the guarded rows' edges.  While theta_f -+ c / s_edge stays between those edges,
+//   cos(theta_f - D) - cos(theta_f) >= D s_edge, so acos(ct) lies within D = c / s_edge of theta_f; lean_acos_dev returns
+//   rt_acosf's bits, within 2.5 ulp <= 5 e theta of it.  v' = theta' / kPi and w = RN(ry v') add (1 + 2 e).  In cell units
+//   |w - (sv + r_v)| <= ry (3 e + 9 e) + (ry / pi) (4 e + 2^-45) / s_edge =: E_v (second-order terms are below 1e-6 of it).
+//   u axis.  The same for nu, u, phi_f = RN(u * 2 kPi) (u * 2 is exact; 2 kPi = kTau).  st > 0 multiplies both x = RN(st cp) and
+//   y = RN(st sp) and cancels in atan2(y, x); sp, cp are within 4 e relative + 2^-45 of sin, cos(phi_f) and never zero (a float is
+//   at least 4e-8 from every multiple of pi / 2 but zero, which the guard excludes), the products are normal (st >= 2^-9, below),
+//   so the angle of (x, y) is within (4 e + 2^-44) + e of phi_f modulo 2 pi.  A wrong sign of a tiny sp or cp moves the angle
+//   continuously through pi / 2, pi or 3 pi / 2; only the seam at 0 = 2 pi could fold it, and there |r - 0.5| <= 0.5 - delta keeps
+//   phi_f at least delta kTau / rx away.  rt_atan2f is within 4 ulp <= 8 e pi; the fold adds kTau for 2 pi (3 e) and rounds (e kTau);
+//   u' and w add (1 + 2 e).  In cell units |w - (su + r_u)| <= rx (3 e + 4 e) + (rx / 2 pi) (40 e + 2^-44) =: E_u.
+//   The host evaluates E_u and E_v in double, rounded outward, and sets delta = 2 E rounded up to a multiple of 2^-24.  The factor 2:
+//   the ulp figures of rt_detmath.h are maxima measured against glibc (tests/test_detmath.py), not theorems, and the factor leaves
+//   room for every one of them to double; the neglected second-order terms are a millionth of E.  With delta <= r <= 1 - delta, w lies
+//   in (s, s + 1): f32_as_index truncates to s, and the clamps to rx - 1, ry - 1 do nothing.  The flag stays off when a delta would
+//   reach 1/4 or s_edge < 2^-8; with s_edge >= 2^-8, |ct| <= cos(asin s_edge) + c gives 1 - RN(ct ct) >= 2^-16 - 2^-17 - 2 e > 0:
+//   sin_theta > 0.  rt_selftest_sky_cell ENUMERATES it on the device: all 2^24 jitters of an axis at a cell, guarded lanes whose
+//   cells disagree must number zero (tests/test_gpu_sky_cell.py; profiles/r27_sky_cell_enumeration.txt).
+// (the direction of jitters r_u, r_v in cell (su, sv), given nu = next_float(su + r_u) and nv likewise: what follows sky_sample's
+// four draws, and what rt_selftest_sky_cell calls)
+template <bool CELL>
+__device__ __forceinline__ V3 sky_direction_(const SkyTables &T, uint32_t rx, uint32_t ry, uint32_t su, uint32_t sv, float r_u, float r_v, float nu, float nv,
+                                             uint32_t &cell, uint32_t cell_from_inv = 0u)
+{
 	float u, v;
 	KWords inv = T.inv_res;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -458,9 +501,19 @@ __device__ __forceinline__ V3 sky_sample(const DevScene &S, const SkyTables &T, 
 	if (inv != nullptr && inv[0] != 0u) { // (wave-uniform)
 		u = div_by_verified(nu, (float)rx, __uint_as_float(inv[1]));
 		v = div_by_verified(nv, (float)ry, __uint_as_float(inv[2]));
+		if constexpr (CELL) { // the guard: selects into the word, its constants read here (rt_types.h DevSkyCell)
+			// (cell_from_inv: where the caller's DevSkyCell lies behind DevSky::inv_res_ok in ITS kernel arguments, in words -- a constant,
+			// so the guard's loads share the reciprocals' base and no second pointer lives through the persistent loop)
+			const KWords g = inv + cell_from_inv;
+			const bool in_u = fabsf(r_u - 0.5f) <= __uint_as_float(g[1]), in_v = fabsf(r_v - 0.5f) <= __uint_as_float(g[2]);
+			const bool in_rows = sv - g[3] <= g[4];
+			cell = su | sv << 16 | (((g[0] != 0u) & in_u & in_v & in_rows) ? 0x80000000u : 0u);
+		}
 	} else {
 		u = nu / (float)rx;
 		v = nv / (float)ry;
+		if constexpr (CELL)
+			cell = su | sv << 16; // (the flag is never on without the verified reciprocals)
 	}
 	const float phi = u * 2.0f * kPi;
 	const float theta = v * kPi;
@@ -469,6 +522,64 @@ __device__ __forceinline__ V3 sky_sample(const DevScene &S, const SkyTables &T, 
 	lean_sincos(theta, st, ct);
 	lean_sincos(phi, sp, cp);
 	return v3(st * cp, st * sp, ct); // Vec3::from_spherical  vec.rs:155-163
+}
+template <bool CELL> __device__ __forceinline__ V3 sky_sample_(const DevScene &S, const SkyTables &T, rt_rng &rng, uint32_t &cell, uint32_t cell_from_inv = 0u)
+{
+	const uint32_t rx = here_(S.sky.res_x), ry = here_(S.sky.res_y);
+	const bool guided = T.guide_k != 0u;
+	const uint32_t sv = dist1d_sample(T.marginal_cdf, ry, guided ? T.guide + (size_t)ry * T.guide_k : nullptr, T.guide_k, rng);
+	const uint32_t su = dist1d_sample(T.row_cdf + (size_t)sv * (rx + 1u), rx, guided ? T.guide + (size_t)sv * T.guide_k : nullptr, T.guide_k, rng);
+	// next_float(cell + r) is the smallest subnormal (cell = r = 0) or lies in [2^-24, 256]: the verified two-fma division applies
+	// (for the subnormal both forms return it unchanged when the table has one cell and zero otherwise: 2^-149 / n rounds to 0 for
+	// n >= 2, and x * rc underflows to 0 with a zero correction)
+	// (conversion, draw, next_float, twice: the order the statement had before the jitters got names -- the kernels that never look at
+	// them keep their schedule only with it)
+	const float f_u = (float)su;
+	const float r_u = rt_rng_f32(&rng);
+	const float nu = next_float(f_u + r_u);
+	const float f_v = (float)sv;
+	const float r_v = rt_rng_f32(&rng);
+	const float nv = next_float(f_v + r_v);
+	return sky_direction_<CELL>(T, rx, ry, su, sv, r_u, r_v, nu, nv, cell, cell_from_inv);
+}
+__device__ __forceinline__ V3 sky_sample(const DevScene &S, const SkyTables &T, rt_rng &rng)
+{
+	uint32_t unused;
+	return sky_sample_<false>(S, T, rng, unused);
+}
+__device__ __forceinline__ V3 sky_sample_cell(const DevScene &S, const SkyTables &T, rt_rng &rng, uint32_t &cell, uint32_t cell_from_inv)
+{
+	return sky_sample_<true>(S, T, rng, cell, cell_from_inv);
+}
+
+// sky_pdf<true> at a direction sky_sample_cell returned with `cell`: guarded lanes take (ui, vi) from the word; if any lane
+// evaluating with this one is not guarded, ONE cold region finds those lanes' cells by sky_pdf's own lines; then one tail for all.
+// (ui, vi: the cell the pdf was read at -- for the self-test; the render kernels drop them)
+__device__ __forceinline__ float sky_pdf_carried_(const DevScene &S, const SkyTables &T, V3 wi, uint32_t cell, uint32_t &ui, uint32_t &vi)
+{
+	ui = cell & 0x7FFFu;
+	vi = (cell >> 16) & 0x7FFFu;
+	const float sin_theta = sqrt_unit_(1.0f - wi.z * wi.z);
+	if (sin_theta <= 0.0f)
+		return 0.0f;
+#if defined(__HIP_DEVICE_COMPILE__)
+	const bool guarded = (cell >> 31) != 0u;
+	if (__ballot(!guarded) != 0ull) { // (wave-uniform: the wave pays for the round trip only when a lane needs it)
+		if (!guarded) {
+			uint32_t rx_, ry_;
+			const SkyCell c = sky_pdf_cell<true>(S, wi, rx_, ry_);
+			ui = c.ui;
+			vi = c.vi;
+		}
+	}
+#endif
+	const uint32_t rx = here_(S.sky.res_x), ry = here_(S.sky.res_y);
+	return sky_pdf_from_cell(T, ui, vi, rx, ry, sin_theta);
+}
+__device__ __forceinline__ float sky_pdf_carried(const DevScene &S, const SkyTables &T, V3 wi, uint32_t cell)
+{
+	uint32_t ui, vi;
+	return sky_pdf_carried_(S, T, wi, cell, ui, vi);
 }
 
 // ---- statistics/bxdfs ----

@@ -174,6 +174,17 @@ struct DevSky {
 	uint32_t inv_res_ok;
 	float inv_res_x, inv_res_y;
 };
+// The carried sky cell of the two-sphere kernels (rt_shade.h sky_sample_cell; proven per scene by rt_sky_cell.h sky_cell_guard) as
+// KERNEL ARGUMENTS of their own (rt_render.hip RenderArgs::sky_cell, read where they are used, as the reciprocals above): ok = 0
+// sends every lane through sky_pdf's own round trip.  A lane is guarded when |jitter - 0.5| <= half_u / half_v (= 0.5 - delta of
+// that axis) and row - row_lo <= row_span.
+struct DevSkyCell {
+	uint32_t ok;
+	float half_u, half_v;
+	uint32_t row_lo, row_span;
+	uint32_t pad[3];
+};
+static_assert(sizeof(DevSkyCell) == 32, "DevSkyCell: eight words");
 
 struct DevScene {
 	const DevNode *nodes;

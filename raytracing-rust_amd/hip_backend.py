@@ -258,6 +258,42 @@ def selftest_sky_pdf_forms(scene, dirs):
     return a, b
 
 
+SKY_CELL_COUNT_NAMES = ("guarded_disagree", "unguarded", "unguarded_agree", "pdf_mismatches", "tested")
+
+
+def sky_cell_guard(scene):
+    """the guard of the carried sky cell for this scene's sky, as rt_selftest_sky_cell reports it without a launch (any scene, a sky
+    without sampler included): {"proven", "enabled", "delta_u", "delta_v", "row_lo", "row_hi", "in_use"}"""
+    guard = np.zeros(8, dtype=np.uint32)
+    _check(lib().rt_selftest_sky_cell(scene._h, None, C.c_uint64(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0), None, None, _p(guard, C.c_uint32)))
+    return _sky_cell_guard_dict(guard)
+
+
+def _sky_cell_guard_dict(guard):
+    return {"proven": bool(guard[0]), "enabled": bool(guard[1]), "delta_u": float(guard[2:3].view(np.float32)[0]), "delta_v": float(guard[3:4].view(np.float32)[0]),
+            "row_lo": int(guard[4]), "row_hi": int(guard[5]), "in_use": bool(guard[6])}
+
+
+def selftest_sky_cell(scene, cases=None, *, axis=0, su=0, sv=0):
+    """rt_selftest_sky_cell on the scene's sky table.  cases (n, 4) uint32 (su, sv, bits of r_u, bits of r_v; consecutive cases are
+    consecutive lanes of a wave): (out (n, 4) uint32 -- bits of the carried pdf, bits of the default pdf, carried cell | guard bit << 31,
+    default cell --, counts, guard).  cases None: the enumeration of all 2^24 jitters of `axis` at cell (su, sv): (None, counts, guard).
+    counts: {"guarded_disagree", "unguarded", "unguarded_agree", "pdf_mismatches", "tested"}; guard: {"proven", "enabled", "delta_u",
+    "delta_v", "row_lo", "row_hi", "in_use"}."""
+    counts, guard = (C.c_uint64 * 5)(), np.zeros(8, dtype=np.uint32)
+    out = None
+    if cases is not None:
+        cases = np.ascontiguousarray(cases, dtype=np.uint32)
+        if cases.ndim != 2 or cases.shape[1] != 4:
+            raise ValueError(f"cases must be (n, 4), got {cases.shape}")
+        out = np.zeros((cases.shape[0], 4), dtype=np.uint32)
+        _check(lib().rt_selftest_sky_cell(scene._h, _p(cases, C.c_uint32), C.c_uint64(cases.shape[0]), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0),
+                                          _p(out, C.c_uint32), counts, _p(guard, C.c_uint32)))
+    else:
+        _check(lib().rt_selftest_sky_cell(scene._h, None, C.c_uint64(0), C.c_uint32(axis), C.c_uint32(su), C.c_uint32(sv), None, counts, _p(guard, C.c_uint32)))
+    return out, dict(zip(SKY_CELL_COUNT_NAMES, (int(x) for x in counts))), _sky_cell_guard_dict(guard)
+
+
 def selftest_frame_forms(vectors, device=0):
     """rt_selftest_frame_forms: vectors (n, 3) f32, each both as a normal -- the scatter frame as the two-sphere kernels form it next
     to the plain coord_from_z -- and as a ray direction -- ray_new<FeatPair>'s direction and reciprocals next to the plain operators --
