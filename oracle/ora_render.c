@@ -693,6 +693,7 @@ typedef struct integ_job {
 	uint32_t max_depth, rr_threshold;
 	uint64_t seed, stream, sample_begin, begin, end;
 	double sum[3];
+	uint64_t rays; /* the integrator's ray_count, summed over the job's samples */
 } integ_job;
 
 static void *integ_worker(void *p)
@@ -701,13 +702,15 @@ static void *integ_worker(void *p)
 	ora_ctx ctx;
 	ora_ctx_init(&ctx);
 	j->sum[0] = j->sum[1] = j->sum[2] = 0.0;
+	j->rays = 0;
 	for (uint64_t k = j->begin; k < j->end; ++k) {
 		rt_rng_seed(&ctx.rng, j->seed, j->stream, j->sample_begin + k); /* u64: wraps */
 		ora_ray ray = ora_ray_new(v3_from(j->ray.origin), v3_from(j->ray.direction), 0.0f);
-		uint64_t rc;
+		uint64_t rc = 0;
 		const vec3 c = j->method == RT_METHOD_NAIVE
 		                   ? ora_naive_get_colour(j->scene, &ray, j->max_depth, j->rr_threshold, &rc, &ctx)
 		                   : ora_mis_get_colour(j->scene, &ray, j->max_depth, j->rr_threshold, &rc, &ctx);
+		j->rays += rc;
 		j->sum[0] += c.x;
 		j->sum[1] += c.y;
 		j->sum[2] += c.z;
@@ -716,9 +719,9 @@ static void *integ_worker(void *p)
 	return NULL;
 }
 
-int ora_integrate_ray_stream(const ora_scene *scene, const rt_ray_desc *ray, int32_t method, uint32_t max_depth,
-                             uint32_t rr_threshold, uint64_t seed, uint64_t n_samples, uint32_t n_threads, double out_mean[3],
-                             uint64_t stream, uint64_t sample_begin)
+int ora_integrate_ray_stream_counted(const ora_scene *scene, const rt_ray_desc *ray, int32_t method, uint32_t max_depth,
+                                     uint32_t rr_threshold, uint64_t seed, uint64_t n_samples, uint32_t n_threads, double out_mean[3],
+                                     uint64_t stream, uint64_t sample_begin, uint64_t *rays_shot)
 {
 	if (!scene || !ray || !out_mean || n_samples == 0)
 		return fail(RT_ERR_INVALID_ARGUMENT, "bad arguments");
@@ -740,16 +743,28 @@ int ora_integrate_ray_stream(const ora_scene *scene, const rt_ray_desc *ray, int
 		pthread_create(&threads[t], NULL, integ_worker, &jobs[t]);
 	}
 	out_mean[0] = out_mean[1] = out_mean[2] = 0.0;
+	uint64_t rays = 0;
 	for (uint32_t t = 0; t < n_threads; ++t) {
 		pthread_join(threads[t], NULL);
 		for (int k = 0; k < 3; ++k)
 			out_mean[k] += jobs[t].sum[k];
+		rays += jobs[t].rays;
 	}
 	for (int k = 0; k < 3; ++k)
 		out_mean[k] /= (double)n_samples;
+	if (rays_shot)
+		*rays_shot = rays;
 	free(jobs);
 	free(threads);
 	return RT_OK;
+}
+
+int ora_integrate_ray_stream(const ora_scene *scene, const rt_ray_desc *ray, int32_t method, uint32_t max_depth,
+                             uint32_t rr_threshold, uint64_t seed, uint64_t n_samples, uint32_t n_threads, double out_mean[3],
+                             uint64_t stream, uint64_t sample_begin)
+{
+	return ora_integrate_ray_stream_counted(scene, ray, method, max_depth, rr_threshold, seed, n_samples, n_threads, out_mean, stream,
+	                                        sample_begin, NULL);
 }
 
 int ora_integrate_ray(const ora_scene *scene, const rt_ray_desc *ray, int32_t method, uint32_t max_depth,

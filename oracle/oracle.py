@@ -136,17 +136,22 @@ class Scene:
         return out
 
     def integrate_ray(self, origin, direction, method, n_samples, seed=1, max_depth=50, rr_threshold=3,
-                      n_threads=None, *, stream=0, sample_begin=0):
-        """the f64 mean of samples k = 0 .. n_samples - 1 on the streams (seed, stream, sample_begin + k mod 2^64)"""
+                      n_threads=None, *, stream=0, sample_begin=0, return_rays=False):
+        """the f64 mean of samples k = 0 .. n_samples - 1 on the streams (seed, stream, sample_begin + k mod 2^64); with
+        return_rays also the integrator's ray count summed over those samples"""
         if n_threads is None:
             n_threads = os.cpu_count() or 1
         ray = abi.RayDesc()
         ray.origin = _f3(origin)
         ray.direction = _f3(direction)
         out = (C.c_double * 3)()
-        _check(lib().ora_integrate_ray_stream(self._h, C.byref(ray), C.c_int32(method), C.c_uint32(max_depth),
-                                              C.c_uint32(rr_threshold), C.c_uint64(seed), C.c_uint64(n_samples),
-                                              C.c_uint32(n_threads), out, C.c_uint64(stream), C.c_uint64(sample_begin)))
+        rays = C.c_uint64()
+        _check(lib().ora_integrate_ray_stream_counted(self._h, C.byref(ray), C.c_int32(method), C.c_uint32(max_depth),
+                                                      C.c_uint32(rr_threshold), C.c_uint64(seed), C.c_uint64(n_samples),
+                                                      C.c_uint32(n_threads), out, C.c_uint64(stream), C.c_uint64(sample_begin),
+                                                      C.byref(rays)))
+        if return_rays:
+            return np.array(list(out)), rays.value
         return np.array(list(out))
 
     def sample_directions(self, which, n, seed=1, incoming=(0, 0, 1), normal=(0, 0, 1), alpha=0.0, prim_index=0):

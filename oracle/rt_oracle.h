@@ -63,6 +63,12 @@ int ora_integrate_ray(const ora_scene *scene, const rt_ray_desc *ray, int32_t re
 int ora_integrate_ray_stream(const ora_scene *scene, const rt_ray_desc *ray, int32_t render_method, uint32_t max_depth,
                              uint32_t rr_threshold, uint64_t seed, uint64_t n_samples, uint32_t n_threads, double out_mean[3],
                              uint64_t stream, uint64_t sample_begin);
+/* the same, and *rays_shot (may be NULL) = the integrator's ray_count summed over the n_samples samples: what a render adds to
+ * SamplerProgress.rays_shot for them (naive: one per check_hit of the path; MIS: one per sample_lights call, none when the path
+ * ends in the prologue).  The two entries above are this one with rays_shot = NULL. */
+int ora_integrate_ray_stream_counted(const ora_scene *scene, const rt_ray_desc *ray, int32_t render_method, uint32_t max_depth,
+                                     uint32_t rr_threshold, uint64_t seed, uint64_t n_samples, uint32_t n_threads, double out_mean[3],
+                                     uint64_t stream, uint64_t sample_begin, uint64_t *rays_shot);
 
 /* ---- hooks for the restated statistical tests ---- */
 /* elementwise rt_detmath functions: which = 0 sin, 1 cos, 2 acos, 3 atan2(a,b), 4 tan, 5 pow5 */

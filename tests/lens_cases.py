@@ -52,16 +52,20 @@ def opts(method, spp, split, w=W, h=H, seed=SEED, begin=BEGIN):
 
 
 @functools.lru_cache(maxsize=None)
-def passes(name, method, projection, aperture=0.0, sky_only=False):
-    """((MAX_SPP, H, W, 3) f32, (MAX_SPP, H, W) bool): the checker's passes BEGIN .. BEGIN + MAX_SPP - 1 and their inside masks"""
+def _passes(name, method, projection, aperture, sky_only):
     import importlib
     hb = importlib.import_module("raytracing-rust_amd.hip_backend")
     cam = camera(hb, name, projection, aperture, SKY_ONLY_CAMERA if sky_only else None)
-    got = [LC.pass_image(built(name)[2], cam, W, H, method, SEED, BEGIN + k) for k in range(MAX_SPP)]
-    out = np.stack([g[0] for g in got]), np.stack([g[1] for g in got])
+    got = [LC.pass_image(built(name)[2], cam, W, H, method, SEED, BEGIN + k, return_rays=True) for k in range(MAX_SPP)]
+    out = tuple(np.stack([g[i] for g in got]) for i in range(3))
     for a in out:
         a.setflags(write=False)
     return out
+
+
+def passes(name, method, projection, aperture=0.0, sky_only=False):
+    """((MAX_SPP, H, W, 3) f32, (MAX_SPP, H, W) bool): the checker's passes BEGIN .. BEGIN + MAX_SPP - 1 and their inside masks"""
+    return _passes(name, method, projection, aperture, sky_only)[:2]
 
 
 def reference(name, method, projection, spp, split, aperture=0.0, sky_only=False):
@@ -69,3 +73,8 @@ def reference(name, method, projection, spp, split, aperture=0.0, sky_only=False
     img, inside = passes(name, method, projection, aperture, sky_only)
     frame, sums = LC.fold(img[:spp], split)
     return frame, sums, int(inside[:spp].sum())
+
+
+def rays_shot(name, method, projection, spp, aperture=0.0, sky_only=False):
+    """rt_render_lens' rays_shot for the first `spp` passes: the oracle integrator's ray count of every sample, summed"""
+    return int(_passes(name, method, projection, aperture, sky_only)[2][:spp].sum())

@@ -11,9 +11,9 @@ arithmetic of a path is restated here.  The fold is rt_render_opts' (noise_check
 
   basis(params)                          right, up, forward and the two scalars rt_lens_camera_new must write
   rays(cam, w, h, seed, n)               origins [w*h, 3], directions [w*h, 3], inside [w*h] of pass n (an absolute sample index)
-  pass_image(cpu, cam, w, h, ...)        (h, w, 3) f32: pass n, black samples +0; and the inside mask
+  pass_image(cpu, cam, w, h, ...)        (h, w, 3) f32: pass n, black samples +0; the inside mask; on request each sample's ray count
   fold(passes, split)                    the frame and, for split > 1, the chunk sums (S, h, w, 3)
-  frame(cpu, cam, opts, split)           both, and the number of inside samples
+  frame(cpu, cam, opts, split)           both, the number of inside samples and, on request, rays_shot
   tiled(sums, w, h)                      chunk sums in rt_render_lens' layout (S, tiles, 8, 8, 3), padding +0
 """
 import numpy as np
@@ -120,15 +120,19 @@ def rays(cam, w, h, seed, n):
     return o, dirs, inside
 
 
-def pass_image(cpu, cam, w, h, method, seed, n, max_depth=50, rr_threshold=3):
+def pass_image(cpu, cam, w, h, method, seed, n, max_depth=50, rr_threshold=3, return_rays=False):
     """((h, w, 3) f32, (h, w) bool): pass n of the frame -- the integrator's sample on stream (seed, pixel, n) from its first draw
-    along the pass's ray; +0 where the sample is outside the fisheye's circle"""
+    along the pass's ray; +0 where the sample is outside the fisheye's circle.  return_rays: a third value, (h, w) uint64, the
+    integrator's ray count of each sample (the oracle's counted fixed-ray entry); a black sample counts 0"""
     o, d, inside = rays(cam, w, h, seed, n)
     out = np.zeros((w * h, 3), dtype=F32)
+    shot = np.zeros(w * h, dtype=np.uint64)
     for p in np.flatnonzero(inside):
-        v = cpu.integrate_ray(o[p], d[p], method, n_samples=1, seed=seed, max_depth=max_depth, rr_threshold=rr_threshold, n_threads=1,
-                              stream=int(p), sample_begin=n & MASK64)
+        v, shot[p] = cpu.integrate_ray(o[p], d[p], method, n_samples=1, seed=seed, max_depth=max_depth, rr_threshold=rr_threshold, n_threads=1,
+                                       stream=int(p), sample_begin=n & MASK64, return_rays=True)
         out[p] = v.astype(F32)  # (the f64 mean of one f32 sample is that sample)
+    if return_rays:
+        return out.reshape(h, w, 3), inside.reshape(h, w), shot.reshape(h, w)
     return out.reshape(h, w, 3), inside.reshape(h, w)
 
 
@@ -145,15 +149,18 @@ def fold(passes, split):
         return N.combine(sums, spp).astype(F32), sums
 
 
-def frame(cpu, cam, opts, split, passes=None):
+def frame(cpu, cam, opts, split, passes=None, return_rays=False):
     """(frame, sums or None, inside samples): rt_render_lens under `opts` at the resolved split; `passes` ((spp, h, w, 3), (spp, h, w))
-    reuses pass images computed before"""
+    reuses pass images computed before.  return_rays: a fourth value, the frame's rays_shot -- the per-sample ray counts summed
+    (`passes` then carries them as its third array, (spp, h, w) uint64)"""
     w, h, spp, begin = int(opts.width), int(opts.height), int(opts.samples_per_pixel), int(opts.sample_begin)
     if passes is None:
         got = [pass_image(cpu, cam, w, h, int(opts.render_method), int(opts.seed), (begin + k) & MASK64, int(opts.max_depth),
-                          int(opts.rr_threshold)) for k in range(spp)]
-        passes = np.stack([g[0] for g in got]), np.stack([g[1] for g in got])
+                          int(opts.rr_threshold), return_rays=True) for k in range(spp)]
+        passes = tuple(np.stack([g[i] for g in got]) for i in range(3))
     img, sums = fold(passes[0], split)
+    if return_rays:
+        return img, sums, int(passes[1].sum()), int(passes[2].sum())
     return img, sums, int(passes[1].sum())
 
 

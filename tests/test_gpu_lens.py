@@ -29,13 +29,14 @@ def _gpu(hb, name):
 @pytest.mark.parametrize("method", LN.METHODS)
 @pytest.mark.parametrize("projection,aperture", CAMERAS)
 def test_frames_are_the_checkers(hb, name, method, projection, aperture):
-    """(spp, S) = (4, 1), (4, 2), (7, 3) from sample_begin 5, host entry: the frame, and with a chunk buffer the chunk sums"""
+    """(spp, S) = (4, 1), (4, 2), (7, 3) from sample_begin 5, host entry: the frame, rays_shot, and with a chunk buffer the chunk sums"""
     gpu, cam = _gpu(hb, name), LN.camera(hb, name, projection, aperture)
     for spp, split in LN.FOLDS:
         ref, ref_sums, _ = LN.reference(name, method, projection, spp, split, aperture)
         what = f"{name} method {method} {projection} aperture {aperture} spp {spp} S {split}"
-        frame, _, sums = gpu.render_lens(cam, LN.opts(method, spp, split), chunk_sums=True)
+        frame, rays, sums = gpu.render_lens(cam, LN.opts(method, spp, split), chunk_sums=True)
         assert_same_bits(frame, ref, what, nan_equal=True)
+        assert rays == LN.rays_shot(name, method, projection, spp, aperture), what  # the oracle integrator's count, sample by sample
         if split > 1:
             assert_same_bits(sums, LC.tiled(ref_sums, W, H), what + ": chunk sums", nan_equal=True)
         else:
