@@ -1058,6 +1058,57 @@ int rt_render_lens(rt_scene *scene, const rt_lens_camera *camera, const rt_rende
 int rt_render_lens_device(rt_scene *scene, const rt_lens_camera *camera, const rt_render_opts *opts, float *d_out_rgb,
                           float *d_chunk_sums_or_null, uint64_t *d_rays_shot_or_null, void *hip_stream);
 
+/* ---- Auxiliary buffers through a lens camera (csrc/rt_aov_lens.hip): the channels of rt_render_aov_chain for the frames of
+ * rt_render_lens -- guides for rt_denoise and rt_upscale that describe THE SAME IMAGE as the lens frame (a panorama's guides from the
+ * pinhole `rt_camera` describe another image; a thin-lens frame's are sharp where the frame is blurred).  A kernel of its own; no
+ * other entry point changes.  No new struct: the buffers and options are rt_render_aov_chain's.
+ *
+ * rt_render_lens_aov[_device]: W x H, RT_LAYOUT_FRAME.  chain_or_null == NULL means max_chain = 0, fuzz_limit = 0: the first hit.
+ *   Any channel of the buffers, `bounces` included, may be NULL and is then not written; all seven NULL: RT_ERR_INVALID_ARGUMENT.
+ *   CAMERA RAY OF SAMPLE k OF PIXEL p (pass n = sample_begin + k): exactly the ray rt_render_lens makes for that sample, on the same
+ *     camera stream (seed, 2^63 + p, n), the draws in the same order -- jitter x, jitter y, and for RT_PROJ_PERSPECTIVE with
+ *     lens_radius != 0 only, xi1 and xi2 -- and every expression the one stated above for each projection.  The guides therefore see
+ *     the sub-pixel positions and lens points the frame's paths start from.  No other draw is taken, on any stream.
+ *   CHAIN: from that ray as segment 0 the rules are those of rt_render_aov_chain, word for word: the followed materials, T, D, b, the
+ *     Reflect and Refract continuations, the terminal and the per-pass terms.  `depth` is the ray parameter from the ray's OWN
+ *     origin, as Hit.t is: for a thin lens that origin is the lens point, for RT_PROJ_ORTHOGRAPHIC the point on the view plane.
+ *   BLACK FISHEYE SAMPLE (rho > 1 or NaN): no walk is made and no term is added to any sum; the sample counts toward neither depth,
+ *     coverage nor bounces.  The divisors stay (float)samples_per_pixel: albedo, normal, coverage and bounces are anti-aliased at the
+ *     rim the way the frame is.  If pass sample_begin is black both IDs are UINT32_MAX.
+ *   FOLDS AND IDs: those of rt_render_aov_chain.
+ *   Consequences: max_chain = 0, or any max_chain on a scene without followed materials, gives the bytes of the NULL-opts call.  A
+ *     RT_PROJ_PERSPECTIVE camera at lens_radius = 0 does NOT give rt_render_aov's bytes: the same rays in distribution, other draws
+ *     (rt_render_aov jitters on the path's stream) -- the reason rt_render_lens gives for its frames.
+ *   Options: as for rt_render_aov, render_method, max_depth, rr_threshold and sample_split are ignored; RT_LAYOUT_FRAME and
+ *     shard_count == 1 are required; width and height >= 2.  Every traversal mode gives the same bytes.
+ *   Errors, in this order: NULL scene, camera, opts or buffers, or all channels NULL; a width or height below 2, samples_per_pixel
+ *     outside [1, 2^32) (what rt_render_aov_device calls a bad argument in opts); rt_render_lens' camera checks (an unknown
+ *     projection, a lens_radius not finite or negative, a fisheye_half_angle not finite and positive, the last two whatever the
+ *     projection); the chain option ranges of rt_render_aov_chain: RT_ERR_INVALID_ARGUMENT; then RT_ERR_UNSUPPORTED for 2^31 pixels
+ *     or more, a layout other than RT_LAYOUT_FRAME, shard_count != 1, a multi-device scene, or `primitive` asked of a scene with
+ *     2^32 - 1 or more primitives; then RT_ERR_NO_DEVICE for a host-only scene.
+ *   rt_render_lens_aov_device: DEVICE buffers on the scene's GPU, asynchronous on `hip_stream`; allocates nothing, keeps no state,
+ *     does not synchronise, so it can be captured into a HIP graph from a scene's first call; launches on two streams may be in
+ *     flight at once.  No side effect on rt_last_kernel_ms, rt_last_launch_info or a following rt_render.
+ *   rt_render_lens_aov: HOST buffers, blocking; staged as rt_render_aov_chain stages (one device allocation per call).
+ *
+ * rt_render_lens_denoised: rt_render_denoised's definition with the lens entry points in place of the pinhole ones.  With sb =
+ *   opts->sample_begin and S = opts->samples_per_pixel (even, >= 2): A = rt_render_lens_device of passes [sb, sb + S/2), B = of
+ *   [sb + S/2, sb + S), each with opts' own sample_split; albedo, normal and depth of all S passes from rt_render_lens_aov_device
+ *   with chain_or_null; noisy = (A + B) * 0.5f, variance = (lA - lB) * (lA - lB) * 0.25f with d and lum as rt_denoise defines them;
+ *   then the filter of rt_denoise_device.  out_clean (and out_noisy unless NULL) get w*h*3 floats; *rays_shot (unless NULL) = the two
+ *   halves' counts added.  Width and height come from opts.  Blocking; its buffers live on the scene (the denoiser's).  Checks: the
+ *   union of the pieces', a bad argument ahead of RT_ERR_UNSUPPORTED, that ahead of RT_ERR_NO_DEVICE.
+ * Not served here: mattes and ambient occlusion through lens cameras, rt_denoise_temporal (its reprojection is
+ * the pinhole's), rt_render_upscaled for lens frames (a caller composes it from these guides), multi-device scenes. ---- */
+int rt_render_lens_aov(rt_scene *scene, const rt_lens_camera *camera, const rt_render_opts *opts, const rt_aov_chain_opts *chain_or_null,
+                       const rt_aov_chain_buffers *host_out);
+int rt_render_lens_aov_device(rt_scene *scene, const rt_lens_camera *camera, const rt_render_opts *opts,
+                              const rt_aov_chain_opts *chain_or_null, const rt_aov_chain_buffers *device_out, void *hip_stream);
+int rt_render_lens_denoised(rt_scene *scene, const rt_lens_camera *camera, const rt_render_opts *opts,
+                            const rt_aov_chain_opts *chain_or_null, const rt_denoise_opts *dopts, float *out_clean, float *out_noisy,
+                            uint64_t *rays_shot);
+
 /* ---- Firefly-robust frames (csrc/rt_robust.hip): a rank-trimmed mean of the chunk sums.  The integrator keeps the reference's
  * quirks, so one wild sample -- or one inf / NaN -- ends up in a pixel's mean, where no later stage can undo it.  The S
  * independent sums per pixel that a render at sample_split = S > 1 leaves in the scene's partial buffer (see the noise estimates

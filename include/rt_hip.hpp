@@ -735,6 +735,60 @@ inline Denoised render_denoised(const RenderOptions &o, const SimpleCamera &came
 	return r;
 }
 
+// The channels of render_aov_chain for the frame render_lens makes: every pass starts with that pass's lens ray (semantics:
+// rt_hip.h rt_render_lens_aov).  `chain` nullptr: the first hit.  Guides for denoise and upscale of a lens frame.
+inline AovChainBuffers render_lens_aov(const RenderOptions &o, const LensCamera &camera, const Bvh &bvh, const AovChainOptions *chain = nullptr,
+                                       uint64_t seed = 1, uint64_t sample_begin = 0)
+{
+	rt_render_opts opts;
+	rt_render_opts_default(&opts);
+	opts.width = o.width;
+	opts.height = o.height;
+	opts.samples_per_pixel = o.samples_per_pixel;
+	opts.sample_begin = sample_begin;
+	opts.seed = seed;
+	rt_aov_chain_opts copts;
+	rt_aov_chain_opts_default(&copts);
+	if (chain) {
+		copts.max_chain = chain->max_chain;
+		copts.fuzz_limit = chain->fuzz_limit;
+	}
+	const size_t n = (size_t)o.width * o.height;
+	AovChainBuffers a;
+	a.albedo.resize(n * 3);
+	a.normal.resize(n * 3);
+	a.depth.resize(n);
+	a.coverage.resize(n);
+	a.primitive.resize(n);
+	a.material.resize(n);
+	a.bounces.resize(n);
+	const rt_aov_chain_buffers b = {{a.albedo.data(), a.normal.data(), a.depth.data(), a.coverage.data(), a.primitive.data(), a.material.data()},
+	                                a.bounces.data()};
+	check(rt_render_lens_aov(bvh.raw(), &camera.raw(), &opts, chain ? &copts : nullptr, &b));
+	return a;
+}
+// render_denoised for a lens camera: two half render_lens frames, the render_lens_aov guides of all passes and the filter in one
+// call (rt_render_lens_denoised; o.samples_per_pixel even, >= 2).
+inline Denoised render_lens_denoised(const RenderOptions &o, const LensCamera &camera, const Bvh &bvh, const AovChainOptions *chain = nullptr,
+                                     const DenoiseOptions &d = DenoiseOptions(), uint32_t sample_split = 1, uint64_t seed = 1,
+                                     uint64_t sample_begin = 0)
+{
+	rt_render_opts opts = detail::noise_render_opts(o, sample_split, seed, sample_begin);
+	opts.render_method = static_cast<int32_t>(o.render_method);
+	rt_aov_chain_opts copts;
+	rt_aov_chain_opts_default(&copts);
+	if (chain) {
+		copts.max_chain = chain->max_chain;
+		copts.fuzz_limit = chain->fuzz_limit;
+	}
+	const rt_denoise_opts dopts = denoise_opts(d, 0, 0); // (the frame size comes from opts)
+	Denoised r;
+	r.clean.resize((size_t)o.width * o.height * 3);
+	r.noisy.resize(r.clean.size());
+	check(rt_render_lens_denoised(bvh.raw(), &camera.raw(), &opts, chain ? &copts : nullptr, &dopts, r.clean.data(), r.noisy.data(), &r.rays_shot));
+	return r;
+}
+
 // Temporal accumulation with camera reprojection (rt_hip.h rt_temporal_opts): the options a caller sets; defaults as
 // rt_temporal_opts_default.
 struct TemporalOptions {

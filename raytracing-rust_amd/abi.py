@@ -780,6 +780,9 @@ EXPORTED_SYMBOLS = [
     "rt_lens_camera_new",
     "rt_render_lens",
     "rt_render_lens_device",
+    "rt_render_lens_aov",
+    "rt_render_lens_aov_device",
+    "rt_render_lens_denoised",
     "rt_robust_opts_default",
     "rt_render_robust",
     "rt_render_robust_device",

@@ -6,6 +6,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -15,6 +16,7 @@
 #include "rt_types.h"
 #include "rt_sky_tiles.h"
 #include "rt_sky_cell.h"
+#include "rt_aov.h"
 
 // the text behind rt_last_error(): ONE per thread for the whole library (defined in rt_api.cpp)
 extern thread_local std::string g_error;
@@ -325,6 +327,24 @@ static int grow_device_buffer(char *&p, size_t &bytes, rt::Layout &L)
 	L.base = p;
 	return rc;
 }
+
+// ---- what the lens cameras (rt_api_lens.cpp) take from the post-processing stages (rt_api_post.cpp) ----
+// the launch parameters of an AOV pass over the frame of `o` (cam: `camera`), and the option ranges of a chain
+rt::DevAovParams aov_params(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *d_out, uint32_t mask);
+int aov_chain_opts_check(const rt_aov_chain_opts *c);
+// a blocking AOV entry point once its arguments are checked: `enqueue` is its _device form on s->stream, handed the staged channels
+int render_aov_staged(rt_scene *s, const rt_render_opts *o, const rt_aov_buffers &a, float *bounces, const char *what,
+                      const std::function<int(const rt_aov_chain_buffers &)> &enqueue);
+// rt_render_denoised's steps that depend on the camera, both on s->stream: a half render into a device frame and ray counter, and
+// the albedo / normal / depth guides of all passes
+struct DenoisedSource {
+	std::function<int(const rt_render_opts *half_opts, float *d_rgb, uint64_t *d_rays)> half;
+	std::function<int(const rt_render_opts *opts, const rt_aov_buffers &d_guides)> guides;
+};
+int render_denoised_opts_check(const char *who, const rt_render_opts *o, const rt_denoise_opts *dopts, uint64_t w, uint64_t h);
+// ... once its arguments are checked and the scene has a device
+int render_denoised_staged(rt_scene *s, const DenoisedSource &src, const rt_render_opts *o, const rt_denoise_opts *dopts, const char *what,
+                           float *out_clean, float *out_noisy, uint64_t *rays_shot);
 
 // The copies and the status of one blocking entry point on s->stream.  Copies are skipped for a NULL (optional) side and once
 // anything has failed; finish() always drains the stream.  Which error wins: a non-OK `rc` (set by the caller from the _device

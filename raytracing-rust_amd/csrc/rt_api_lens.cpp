@@ -2,12 +2,16 @@
 // are rt_lens.hip.  The argument checks follow rt_render_tiles' (rt_api_post.cpp tiles_check) in order and kind, the camera's
 // own behind the buffers', the device last (so that a host-only scene reports bad arguments as such); the blocking entry stages
 // the frame and the chunk sums through the scene's d_noise buffer, as rt_render_tiles does.
+// Also here: the auxiliary buffers through a lens camera (rt_render_lens_aov[_device]; the kernel is rt_aov_lens.hip) and the denoised
+// lens frame (rt_render_lens_denoised).  Both stage and compose through the steps rt_api_post.cpp shares (rt_api_internal.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
+#include <string>
 
 #include "rt_api_internal.h"
+#include "rt_aov_lens.h"
 #include "rt_lens.h"
 
 using namespace rt;
@@ -16,6 +20,18 @@ static_assert(RT_PROJ_PERSPECTIVE == kProjPerspective && RT_PROJ_ORTHOGRAPHIC ==
                   RT_PROJ_EQUIRECT == kProjEquirect,
               "rt_projection and the kernel's constants");
 static_assert(sizeof(rt_lens_camera) == sizeof(rt_camera) + 52, "rt_lens_camera layout");
+
+// the camera's own errors (the last two whatever the projection)
+static int lens_camera_check(const rt_lens_camera *camera)
+{
+	if (camera->projection < RT_PROJ_PERSPECTIVE || camera->projection > RT_PROJ_EQUIRECT)
+		return fail(RT_ERR_INVALID_ARGUMENT, "render_lens: unknown projection");
+	if (!std::isfinite(camera->lens_radius) || camera->lens_radius < 0.0f)
+		return fail(RT_ERR_INVALID_ARGUMENT, "render_lens: lens_radius must be finite and >= 0");
+	if (!std::isfinite(camera->fisheye_half_angle) || !(camera->fisheye_half_angle > 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "render_lens: fisheye_half_angle must be finite and > 0");
+	return RT_OK;
+}
 
 // *split is S resolved, *px the pixels, *n_tiles the 8 x 8 tiles of the frame
 static int lens_check(const rt_scene *s, const rt_lens_camera *camera, const rt_render_opts *o, const float *out, const float *chunk_sums,
@@ -46,12 +62,8 @@ static int lens_check(const rt_scene *s, const rt_lens_camera *camera, const rt_
 	*split = S;
 	if (S > 1u && ranges_overlap(out, 12 * *px, chunk_sums, 12ull * S * 64u * *n_tiles))
 		return fail(RT_ERR_INVALID_ARGUMENT, "render_lens: chunk_sums overlaps the frame");
-	if (camera->projection < RT_PROJ_PERSPECTIVE || camera->projection > RT_PROJ_EQUIRECT)
-		return fail(RT_ERR_INVALID_ARGUMENT, "render_lens: unknown projection");
-	if (!std::isfinite(camera->lens_radius) || camera->lens_radius < 0.0f)
-		return fail(RT_ERR_INVALID_ARGUMENT, "render_lens: lens_radius must be finite and >= 0");
-	if (!std::isfinite(camera->fisheye_half_angle) || !(camera->fisheye_half_angle > 0.0f))
-		return fail(RT_ERR_INVALID_ARGUMENT, "render_lens: fisheye_half_angle must be finite and > 0");
+	if (const int rc = lens_camera_check(camera); rc != RT_OK)
+		return rc;
 	if (o->output_layout != RT_LAYOUT_FRAME)
 		return fail(RT_ERR_UNSUPPORTED, "render_lens: RT_LAYOUT_FRAME only");
 	if (o->shard_count != 1)
@@ -62,6 +74,57 @@ static int lens_check(const rt_scene *s, const rt_lens_camera *camera, const rt_
 		return fail(RT_ERR_UNSUPPORTED, "render_lens: 64 x tiles x sample_split exceeds 2^31 lane items");
 	return need_device(s);
 }
+
+// rt_render_lens_aov[_device], in the header's order: the arguments (the options as rt_render_aov_device reads them, the camera,
+// the chain), then what is unsupported, the device last.  `c` NULL: the first hit.  *mask: the kAov* bits of the channels given
+static int lens_aov_check(const rt_scene *s, const rt_lens_camera *camera, const rt_render_opts *o, const rt_aov_chain_opts *c,
+                          const rt_aov_chain_buffers *b, uint32_t *mask)
+{
+	if (!s || !camera || !o || !b)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	const rt_aov_buffers &a = b->aov;
+	*mask = (a.albedo ? kAovAlbedo : 0u) | (a.normal ? kAovNormal : 0u) | (a.depth ? kAovDepth : 0u) | (a.coverage ? kAovCoverage : 0u) |
+	        (a.primitive ? kAovPrimitive : 0u) | (a.material ? kAovMaterial : 0u) | (b->bounces ? kAovBounces : 0u);
+	if (*mask == 0u)
+		return fail(RT_ERR_INVALID_ARGUMENT, "rt_aov_chain_buffers: every channel is NULL");
+	int rc = frame_sides("", o->width, o->height, 2);
+	if (rc != RT_OK)
+		return rc;
+	if (o->samples_per_pixel == 0 || o->samples_per_pixel >= (1ull << 32))
+		return fail(RT_ERR_INVALID_ARGUMENT, "samples_per_pixel must be in [1, 2^32)");
+	rc = lens_camera_check(camera);
+	if (rc == RT_OK && c)
+		rc = aov_chain_opts_check(c);
+	if (rc != RT_OK)
+		return rc;
+	if (o->width > (1ull << 31) || o->height > (1ull << 31) || o->width * o->height >= (1ull << 31))
+		return fail(RT_ERR_UNSUPPORTED, "render_lens_aov: 2^31 pixels or more");
+	if (o->output_layout != RT_LAYOUT_FRAME)
+		return fail(RT_ERR_UNSUPPORTED, "render_lens_aov: RT_LAYOUT_FRAME only");
+	if (o->shard_count != 1)
+		return fail(RT_ERR_UNSUPPORTED, "render_lens_aov: the whole frame only (shard_count 1)");
+	if (!s->peers.empty())
+		return fail(RT_ERR_UNSUPPORTED, "render_lens_aov: a multi-device scene is not served");
+	if ((*mask & kAovPrimitive) && s->host.primitive_order.size() >= 0xFFFFFFFFull) // (upload_scene, rt_api.cpp, makes the table for fewer)
+		return fail(RT_ERR_UNSUPPORTED, "primitive IDs need fewer than 2^32 - 1 primitives");
+	return need_device(s);
+}
+
+// which of two statuses an entry point with several checked pieces reports: a bad argument ahead of RT_ERR_UNSUPPORTED, that ahead
+// of RT_ERR_NO_DEVICE (the message follows the status)
+struct WorstStatus {
+	int rc = RT_OK;
+	std::string message;
+	static int rank(int rc) { return rc == RT_ERR_INVALID_ARGUMENT ? 3 : rc == RT_ERR_UNSUPPORTED ? 2 : rc != RT_OK ? 1 : 0; }
+	void take(int r)
+	{
+		if (rank(r) > rank(rc)) {
+			rc = r;
+			message = g_error;
+		}
+	}
+	int result() const { return rc == RT_OK ? RT_OK : fail(rc, message); }
+};
 
 extern "C" {
 
@@ -159,6 +222,79 @@ int rt_render_lens(rt_scene *s, const rt_lens_camera *camera, const rt_render_op
 	st.get(chunk_sums, L, p_sums);
 	st.download(rays_shot, s->d_rays, sizeof(uint64_t));
 	return st.finish("render_lens");
+}
+
+// ---- the auxiliary buffers through a lens camera (rt_aov_lens.hip) ----
+int rt_render_lens_aov_device(rt_scene *s, const rt_lens_camera *camera, const rt_render_opts *o, const rt_aov_chain_opts *c,
+                              const rt_aov_chain_buffers *d_out, void *hip_stream)
+{
+	uint32_t mask = 0;
+	int rc = lens_aov_check(s, camera, o, c, d_out, &mask);
+	if (rc != RT_OK)
+		return rc;
+	HIP_TRY(hipSetDevice(s->device));
+	bool prune = false;
+	DevScene dev;
+	rc = four_wave_traversal(s, &prune, &dev); // (rt_api_internal.h)
+	if (rc != RT_OK)
+		return rc;
+	DevAovLensParams P;
+	std::memset(&P, 0, sizeof P);
+	P.C.A = aov_params(s, &camera->pinhole, o, &d_out->aov, mask);
+	P.C.max_chain = c ? c->max_chain : 0u; // NULL: the first hit
+	P.C.fuzz_limit = c ? c->fuzz_limit : 0.0f;
+	P.C.bounces = d_out->bounces;
+	std::memcpy(P.right, camera->right, 12);
+	std::memcpy(P.up, camera->up, 12);
+	std::memcpy(P.forward, camera->forward, 12);
+	P.lens_radius = camera->lens_radius;
+	P.fisheye_half_angle = camera->fisheye_half_angle;
+	P.projection = camera->projection;
+	HIP_TRY(launch_aov_lens(prune, static_cast<hipStream_t>(hip_stream), dev, P));
+	return RT_OK;
+}
+
+int rt_render_lens_aov(rt_scene *s, const rt_lens_camera *camera, const rt_render_opts *o, const rt_aov_chain_opts *c,
+                       const rt_aov_chain_buffers *out)
+{
+	uint32_t mask = 0;
+	const int rc = lens_aov_check(s, camera, o, c, out, &mask);
+	if (rc != RT_OK)
+		return rc;
+	return render_aov_staged(s, o, out->aov, out->bounces, "render_lens_aov",
+	                         [&](const rt_aov_chain_buffers &d) { return rt_render_lens_aov_device(s, camera, o, c, &d, s->stream); });
+}
+
+// ---- a denoised lens frame: rt_render_denoised's steps (rt_api_post.cpp) with the lens entry points in place of the pinhole ones ----
+int rt_render_lens_denoised(rt_scene *s, const rt_lens_camera *camera, const rt_render_opts *o, const rt_aov_chain_opts *c,
+                            const rt_denoise_opts *dopts, float *out_clean, float *out_noisy, uint64_t *rays_shot)
+{
+	if (!s || !camera || !o || !dopts || !out_clean)
+		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
+	// the union of the pieces' checks: the composite's own, a half render's (on any non-NULL frame), the guides'
+	WorstStatus st;
+	st.take(render_denoised_opts_check("rt_render_lens_denoised", o, dopts, o->width, o->height));
+	if (st.rc == RT_OK) {
+		const uint64_t n = o->width * o->height;
+		if (ranges_overlap(out_clean, 12 * n, out_noisy, 12 * n))
+			st.take(fail(RT_ERR_INVALID_ARGUMENT, "rt_render_lens_denoised: out_clean overlaps out_noisy"));
+	}
+	rt_render_opts oh = *o;
+	oh.samples_per_pixel = o->samples_per_pixel / 2;
+	uint32_t split = 0, mask = 0;
+	uint64_t px = 0, n_tiles = 0;
+	st.take(lens_check(s, camera, &oh, out_clean, nullptr, &split, &px, &n_tiles));
+	const rt_aov_chain_buffers guides = {{out_clean, out_clean, out_clean, nullptr, nullptr, nullptr}, nullptr};
+	st.take(lens_aov_check(s, camera, o, c, &guides, &mask));
+	if (st.rc != RT_OK)
+		return st.result();
+	const DenoisedSource src = {
+	    [=](const rt_render_opts *half, float *d_rgb, uint64_t *d_rays) { return rt_render_lens_device(s, camera, half, d_rgb, nullptr, d_rays, s->stream); },
+	    [=](const rt_render_opts *all, const rt_aov_buffers &d) {
+		    const rt_aov_chain_buffers b = {d, nullptr};
+		    return rt_render_lens_aov_device(s, camera, all, c, &b, s->stream);
+	    }};
+	return render_denoised_staged(s, src, o, dopts, "render_lens_denoised", out_clean, out_noisy, rays_shot);
 }
 
 } // extern "C"

@@ -3,7 +3,8 @@
 // its own (rt_aov.hip, rt_aov_chain.hip, rt_matte.hip, rt_ao.hip, rt_denoise.hip, rt_noise.hip, rt_robust.hip, rt_temporal.hip, rt_dof.hip, rt_bloom.hip, rt_display.hip, rt_upscale.hip); here are their argument checks, their _device entry points
 // and the blocking wrappers that stage host buffers through scene-owned device memory: each buffer is carved by a Layout (rt_layout.h),
 // so its size and every pointer into it come from one description; Staging (rt_api_internal.h) carries the copies and the status.
-// The steps the one-call composites share: enqueue_guides, enqueue_denoise, render_denoised_guided.
+// The steps the one-call composites share: enqueue_guides, enqueue_denoise, render_denoised_guided; render_denoised_staged and
+// render_aov_staged serve the lens cameras too (rt_api_lens.cpp; declared in rt_api_internal.h).
 // Every check function ends with the device (need_device), so that a host-only scene reports bad arguments as such.
 #include <hip/hip_runtime.h>
 
@@ -61,8 +62,8 @@ static int aov_check(const rt_scene *s, const rt_camera *camera, const rt_render
 	return need_device(s);
 }
 
-// the launch parameters both AOV kernels share
-static DevAovParams aov_params(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *d_out, uint32_t mask)
+// the launch parameters the AOV kernels share (rt_api_lens.cpp: the lens pass takes them too)
+DevAovParams aov_params(const rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *d_out, uint32_t mask)
 {
 	DevAovParams P;
 	std::memset(&P, 0, sizeof P);
@@ -109,10 +110,12 @@ int rt_render_aov_device(rt_scene *s, const rt_camera *camera, const rt_render_o
 	return RT_OK;
 }
 
-// Both blocking AOV entry points once their arguments are checked (`c` NULL: the first-hit pass): one device allocation per call
-// for the requested channels, in rt_aov_chain_buffers order; 4-byte elements throughout
-static int render_aov_staged(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_chain_opts *c,
-                             const rt_aov_buffers &a, float *bounces, const char *what)
+} // extern "C"
+
+// The blocking AOV entry points once their arguments are checked: one device allocation per call for the requested channels, in
+// rt_aov_chain_buffers order (4-byte elements throughout); `enqueue` is the entry point's _device form on s->stream
+int render_aov_staged(rt_scene *s, const rt_render_opts *o, const rt_aov_buffers &a, float *bounces, const char *what,
+                      const std::function<int(const rt_aov_chain_buffers &)> &enqueue)
 {
 	HIP_TRY(hipSetDevice(s->device));
 	const uint64_t n_px = o->width * o->height;
@@ -127,7 +130,7 @@ static int render_aov_staged(rt_scene *s, const rt_camera *camera, const rt_rend
 	auto ids = [&](int k) { return reinterpret_cast<uint32_t *>(L.at(ch[k])); };
 	const rt_aov_chain_buffers dev_out = {{L.at(ch[0]), L.at(ch[1]), L.at(ch[2]), L.at(ch[3]), ids(4), ids(5)}, L.at(ch[6])};
 	Staging st{s};
-	st.rc = c ? rt_render_aov_chain_device(s, camera, o, c, &dev_out, s->stream) : rt_render_aov_device(s, camera, o, &dev_out.aov, s->stream);
+	st.rc = enqueue(dev_out);
 	for (int k = 0; k < 7; ++k)
 		st.get(host[k], L, ch[k]);
 	const int rc = st.finish(what);
@@ -135,11 +138,26 @@ static int render_aov_staged(rt_scene *s, const rt_camera *camera, const rt_rend
 	return rc;
 }
 
+// the option ranges of a chain (rt_api_lens.cpp: the lens pass checks them too)
+int aov_chain_opts_check(const rt_aov_chain_opts *c)
+{
+	if (c->max_chain > kAovChainMaxChain)
+		return fail(RT_ERR_INVALID_ARGUMENT, "aov_chain: max_chain must be in 0..64");
+	if (!std::isfinite(c->fuzz_limit) || !(c->fuzz_limit >= 0.0f))
+		return fail(RT_ERR_INVALID_ARGUMENT, "aov_chain: fuzz_limit must be finite and >= 0");
+	return RT_OK;
+}
+
+extern "C" {
+
 int rt_render_aov(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_aov_buffers *out)
 {
 	uint32_t mask = 0;
 	const int rc = aov_check(s, camera, o, out, &mask);
-	return rc == RT_OK ? render_aov_staged(s, camera, o, nullptr, *out, nullptr, "render_aov") : rc;
+	if (rc != RT_OK)
+		return rc;
+	return render_aov_staged(s, o, *out, nullptr, "render_aov",
+	                         [&](const rt_aov_chain_buffers &d) { return rt_render_aov_device(s, camera, o, &d.aov, s->stream); });
 }
 
 // ---- specular-chain AOV buffers (rt_aov_chain.hip) ----
@@ -159,10 +177,8 @@ static int aov_chain_check(const rt_scene *s, const rt_camera *camera, const rt_
 {
 	if (!s || !camera || !o || !c || !b)
 		return fail(RT_ERR_INVALID_ARGUMENT, "null argument");
-	if (c->max_chain > kAovChainMaxChain)
-		return fail(RT_ERR_INVALID_ARGUMENT, "aov_chain: max_chain must be in 0..64");
-	if (!std::isfinite(c->fuzz_limit) || !(c->fuzz_limit >= 0.0f))
-		return fail(RT_ERR_INVALID_ARGUMENT, "aov_chain: fuzz_limit must be finite and >= 0");
+	if (int rc = aov_chain_opts_check(c); rc != RT_OK)
+		return rc;
 	// (a `bounces` pointer stands in for "some channel is given" in the first-hit check)
 	rt_aov_buffers any = b->aov;
 	if (b->bounces && !any.albedo)
@@ -203,7 +219,10 @@ int rt_render_aov_chain(rt_scene *s, const rt_camera *camera, const rt_render_op
 {
 	uint32_t mask = 0;
 	const int rc = aov_chain_check(s, camera, o, c, out, &mask);
-	return rc == RT_OK ? render_aov_staged(s, camera, o, c, out->aov, out->bounces, "render_aov_chain") : rc;
+	if (rc != RT_OK)
+		return rc;
+	return render_aov_staged(s, o, out->aov, out->bounces, "render_aov_chain",
+	                         [&](const rt_aov_chain_buffers &d) { return rt_render_aov_chain_device(s, camera, o, c, &d, s->stream); });
 }
 
 } // extern "C"
@@ -526,8 +545,8 @@ static DevDenoiseParams denoise_params(const rt_denoise_opts *o, uint64_t w, uin
 	return P;
 }
 
-// what rt_render_denoised and rt_render_upscaled ask of their render options, for a render of w x h
-static int render_denoised_opts_check(const char *who, const rt_render_opts *o, const rt_denoise_opts *dopts, uint64_t w, uint64_t h)
+// what rt_render_denoised, rt_render_upscaled and rt_render_lens_denoised (rt_api_lens.cpp) ask of their render options, for a render of w x h
+int render_denoised_opts_check(const char *who, const rt_render_opts *o, const rt_denoise_opts *dopts, uint64_t w, uint64_t h)
 {
 	int rc = denoise_opts_check(dopts, w, h);
 	if (rc != RT_OK)
@@ -582,8 +601,16 @@ static DenoisedParts denoised_parts(Layout &L, uint64_t n)
 	                     L.add<float>(3 * n), L.add<float>(3 * n), L.add<float>(n), L.add<float>(3 * n), L.add<float>(3 * n)}; // (in this order)
 }
 
+// rt_render_denoised's camera: the pinhole entry points on s->stream
+static DenoisedSource pinhole_source(rt_scene *s, const rt_camera *camera)
+{
+	return DenoisedSource{
+	    [=](const rt_render_opts *oh, float *d_rgb, uint64_t *d_rays) { return rt_render_device(s, camera, oh, d_rgb, d_rays, s->stream); },
+	    [=](const rt_render_opts *o, const rt_aov_buffers &d_guides) { return rt_render_aov_device(s, camera, o, &d_guides, s->stream); }};
+}
+
 // two half renders, the AOVs of all passes, the variance and the filter, in the parts `P` of the grown buffer
-static void enqueue_render_denoised(rt_scene *s, const rt_camera *camera, const rt_render_opts *o, const rt_denoise_opts *dopts,
+static void enqueue_render_denoised(rt_scene *s, const DenoisedSource &src, const rt_render_opts *o, const rt_denoise_opts *dopts,
                                     const Layout &L, const DenoisedParts &P, Staging &st)
 {
 	uint64_t *d_rays = reinterpret_cast<uint64_t *>(L.at(P.rays));
@@ -593,14 +620,15 @@ static void enqueue_render_denoised(rt_scene *s, const rt_camera *camera, const 
 	rt_render_opts oh = *o;
 	oh.samples_per_pixel = half;
 	if (st.ok())
-		st.rc = rt_render_device(s, camera, &oh, d_a, d_rays, s->stream);
+		st.rc = src.half(&oh, d_a, d_rays);
 	if (st.ok()) {
 		oh.sample_begin = o->sample_begin + half;
-		st.rc = rt_render_device(s, camera, &oh, d_b, d_rays + 1, s->stream);
+		st.rc = src.half(&oh, d_b, d_rays + 1);
 	}
 	if (st.ok())
 		st.e = hipSetDevice(s->device);
-	enqueue_guides(s, camera, o, d_albedo, d_normal, d_depth, st);
+	if (st.ok())
+		st.rc = src.guides(o, rt_aov_buffers{d_albedo, d_normal, d_depth, nullptr, nullptr, nullptr});
 	if (st.ok()) {
 		const rt_denoise_inputs in = {d_noisy, d_albedo, d_normal, d_depth, nullptr};
 		DevDenoiseParams D = denoise_params(dopts, o->width, o->height, in, L.at(P.ws), L.at(P.clean));
@@ -728,23 +756,31 @@ int rt_render_denoised(rt_scene *s, const rt_camera *camera, const rt_render_opt
 	rc = need_device(s);
 	if (rc != RT_OK)
 		return rc;
+	return render_denoised_staged(s, pinhole_source(s, camera), o, dopts, "render_denoised", out_clean, out_noisy, rays_shot);
+}
+
+} // extern "C"
+
+// rt_render_denoised once its arguments are checked (rt_api_lens.cpp: rt_render_lens_denoised too): the frames in the denoiser's
+// buffer on the scene, the steps enqueued, the downloads and the ray count
+int render_denoised_staged(rt_scene *s, const DenoisedSource &src, const rt_render_opts *o, const rt_denoise_opts *dopts, const char *what,
+                           float *out_clean, float *out_noisy, uint64_t *rays_shot)
+{
 	HIP_TRY(hipSetDevice(s->device));
 	Layout L;
-	const DenoisedParts P = denoised_parts(L, n);
+	const DenoisedParts P = denoised_parts(L, o->width * o->height);
 	RT_TRY(grow_device_buffer(s->d_denoise, s->d_denoise_bytes, L));
 	Staging st{s};
-	enqueue_render_denoised(s, camera, o, dopts, L, P, st);
+	enqueue_render_denoised(s, src, o, dopts, L, P, st);
 	unsigned long long rays[2] = {0, 0};
 	st.get(out_clean, L, P.clean);
 	st.get(out_noisy, L, P.noisy);
 	st.get(rays, L, P.rays);
-	rc = st.finish("render_denoised");
+	const int rc = st.finish(what);
 	if (rc == RT_OK && rays_shot)
 		*rays_shot = rays[0] + rays[1];
 	return rc;
 }
-
-} // extern "C"
 
 // ---- per-pixel noise estimates and render-until-converged (rt_noise.hip) ----
 static int noise_opts_check(const rt_noise_opts *n)
@@ -2509,7 +2545,7 @@ int rt_render_upscaled(rt_scene *s, const rt_camera *camera, const rt_render_opt
 	os.width = w;
 	os.height = h;
 	Staging st{s};
-	enqueue_render_denoised(s, camera, &os, dopts, L, P, st);
+	enqueue_render_denoised(s, pinhole_source(s, camera), &os, dopts, L, P, st);
 	enqueue_guides(s, camera, o, d_albedo, d_normal, d_depth, st);
 	if (st.ok()) {
 		const rt_upscale_inputs in = {L.at(P.clean), L.at(P.albedo), L.at(P.normal), L.at(P.depth), d_albedo, d_normal, d_depth};

@@ -838,6 +838,40 @@ class HipScene:
         _check(lib().rt_render_lens_device(self._h, C.byref(camera), C.byref(opts), _dp(d_frame), _dp(d_chunk_sums), _vp(d_rays_ptr),
                                            C.c_void_p(stream)))
 
+    # ---- guides through a lens camera (rt_render_lens_aov) and the denoised lens frame (rt_render_lens_denoised) ----
+    def render_lens_aov(self, camera, opts, channels=abi.AOV_CHAIN_CHANNELS, max_chain=None, fuzz_limit=0.0):
+        """rt_render_lens_aov: the seven channels of render_aov_chain for the frame render_lens makes of an abi.LensCamera -- every
+        pass starts with that pass's lens ray (same camera stream, same draws) -- as {channel: numpy array}.  max_chain None: no
+        chain options are passed, which is the first hit (max_chain 0).  A black fisheye sample adds to no sum; a pixel whose
+        first pass is black has the IDs abi.AOV_NO_ID.  Semantics: include/rt_hip.h rt_render_lens_aov."""
+        bufs = abi.AovChainBuffers()
+        out = _host_buffers(abi.AOV_CHAIN_SHAPES, bufs, channels, int(opts.height), int(opts.width))
+        copts = None if max_chain is None else abi.default_aov_chain_opts(max_chain, fuzz_limit)
+        _check(lib().rt_render_lens_aov(self._h, C.byref(camera), C.byref(opts), _ref(copts), C.byref(bufs)))
+        return out
+
+    def render_lens_aov_device(self, camera, opts, d_ptrs, stream=0, max_chain=None, fuzz_limit=0.0):
+        """rt_render_lens_aov_device: asynchronous, into DEVICE buffers of the scene's GPU.  d_ptrs = {channel: device pointer} over
+        abi.AOV_CHAIN_CHANNELS; channels left out are not produced.  Allocates nothing: capturable from the first call."""
+        bufs = _device_buffers(abi.AOV_CHAIN_SHAPES, abi.AovChainBuffers(), d_ptrs)
+        copts = None if max_chain is None else abi.default_aov_chain_opts(max_chain, fuzz_limit)
+        _check(lib().rt_render_lens_aov_device(self._h, C.byref(camera), C.byref(opts), _ref(copts), C.byref(bufs), C.c_void_p(stream)))
+
+    def render_lens_denoised(self, camera, opts, dopts=None, max_chain=None, fuzz_limit=0.0, noisy=True):
+        """rt_render_lens_denoised: render_denoised for an abi.LensCamera -- two half render_lens frames, the render_lens_aov guides of
+        all passes (max_chain as there) and the filter in one call.  Returns (clean, noisy, rays_shot) with clean / noisy (H, W, 3)
+        f32; noisy=False: the noisy frame is not asked for and None is returned in its place."""
+        h, w = int(opts.height), int(opts.width)
+        if dopts is None:
+            dopts = denoise_opts(w, h)
+        copts = None if max_chain is None else abi.default_aov_chain_opts(max_chain, fuzz_limit)
+        clean = np.zeros((h, w, 3), dtype=np.float32)
+        mean = np.zeros((h, w, 3), dtype=np.float32) if noisy else None
+        rays = C.c_uint64()
+        _check(lib().rt_render_lens_denoised(self._h, C.byref(camera), C.byref(opts), _ref(copts), C.byref(dopts), _p(clean, C.c_float),
+                                             _p(mean, C.c_float), C.byref(rays)))
+        return clean, mean, rays.value
+
     def noise_select_tiles(self, tile_error, threshold):
         """rt_noise_select_tiles: the indices (uint32, ascending) of the tiles of a (ceil(H/8), ceil(W/8)) f32 error map whose
         error is > threshold (NaN is not)."""
