@@ -1109,6 +1109,75 @@ int rt_render_lens_denoised(rt_scene *scene, const rt_lens_camera *camera, const
                             const rt_aov_chain_opts *chain_or_null, const rt_denoise_opts *dopts, float *out_clean, float *out_noisy,
                             uint64_t *rays_shot);
 
+/* ---- Light probes (csrc/rt_probe.hip): the radiance arriving at a POSITION from all directions, as the 9 x RGB coefficients of the
+ * real spherical harmonics of bands 0 to 2.  The directions are made on the device and every sample is projected there: a probe
+ * costs 12 bytes up and 108 bytes down, where the same samples through rt_radiance cost one rt_ray_desc up and one RGB down each.
+ * No render kernel is involved: the integrator is the one rt_radiance, rt_render_tiles and rt_render_lens run.
+ *
+ * rt_probe_sh[_device]: probe i of n_probes stands at positions[3 i .. 3 i + 2].  All arithmetic is f32, every operation in the
+ *   written order, no contraction.  SAMPLE k OF PROBE i (k < K = samples_per_probe) is pass n = sample_begin + k, a uint64_t sum
+ *   that WRAPS.
+ *   Direction: on the probe's own stream rt_rng_seed of (seed, 2^63 + i, n) two draws, xi1 then xi2, both rt_rng_f32;
+ *     z = 1 - 2 * xi1; s = sqrtf(1 - z * z); phi = RT_TAU * xi2; d = (s * cos phi, s * sin phi, z) in world axes, sin and
+ *     cos the rt_sinf / rt_cosf of rt_detmath.h, sqrtf the IEEE one.
+ *     Probes are below 2^31, so no probe's direction stream is a path stream.
+ *   Value: Naive / MisIntegrator::get_colour, by render_method, on Ray::new(position_i, d) on the stream (seed, i, n) FROM ITS FIRST
+ *     DRAW: exactly sample n of rt_radiance with streams[i] = i, the NaN / non-finite filter included where the integrator applies
+ *     one.
+ *   Basis, evaluated on d = (x, y, z) as computed, NOT renormalised, the constants f32 literals:
+ *     Y_0 = 0.282094792              Y_1 = 0.488602512 * y          Y_2 = 0.488602512 * z
+ *     Y_3 = 0.488602512 * x          Y_4 = 1.092548431 * (x * y)    Y_5 = 1.092548431 * (y * z)
+ *     Y_6 = 0.315391565 * (3 * (z * z) - 1)                         Y_7 = 1.092548431 * (x * z)
+ *     Y_8 = 0.546274215 * (x * x - y * y)
+ *   Fold: rt_render_opts' chunk rule with S = sample_split.  Chunk c is the passes [floor(c * K / S), floor((c + 1) * K / S)); within a
+ *     chunk, from +0 and in pass order, acc[j][ch] += value[ch] * Y_j (the product, then the sum); the S chunk sums are added in chunk
+ *     order from +0.  S CHANGES THE BYTES and is part of the definition: there is no automatic value.
+ *   Scale: coeff = sum * (12.5663706f / (float)K), the quotient first.  With convolve = 1 the result is then multiplied by RT_PI for
+ *     j = 0, by 2.09439510f for j = 1..3 and by 0.785398163f for j = 4..8: the cosine lobe's band factors, so that
+ *     rt_probe_sh_eval of a unit normal is the irradiance there.
+ *   Output: out_coeffs[(9 i + j) * 3 + ch], 27 n_probes floats.  rays_shot (may be NULL) is WRITTEN, not added to:
+ *     SamplerProgress.rays_shot as rt_render_lens counts it.
+ *   Which lane runs which (probe, chunk), the traversal mode, the walk and RT_TUNE_RADIANCE_GROUPS change no bit.
+ *   Errors, in rt_render_lens' order: a NULL scene, positions, opts or output (a NULL workspace in the device form), K = 0, S = 0 or
+ *     S > K, an unknown render_method, a convolve other than 0 or 1, a non-zero `reserved`: RT_ERR_INVALID_ARGUMENT; then
+ *     RT_ERR_UNSUPPORTED for n_probes * S at or above 2^31, or a multi-device scene; then RT_ERR_NO_DEVICE for a host-only scene.
+ *     n_probes = 0: RT_OK, nothing written.
+ *   rt_probe_workspace_bytes: what d_workspace must hold for n_probes under opts, 108 * n_probes * S bytes; the checks of opts and
+ *     of n_probes * S above.  The workspace is opaque, 4-byte aligned, and holds nothing between calls.
+ *   rt_probe_sh_device: DEVICE buffers on the scene's GPU (4-byte aligned; the counter 8-byte aligned), asynchronous on `hip_stream`;
+ *     allocates nothing, keeps no state on the scene, does not synchronise, can be captured into a HIP graph as a fresh scene's first
+ *     call; launches on two streams may be in flight at once with two workspaces.  rt_probe_sh: HOST buffers, blocking; staged
+ *     through scene-owned device memory, as rt_render_lens stages.
+ *
+ * rt_probe_sh_eval[_device]: out_rgb[3 i + ch] = the sum over j = 0..8, in that order from +0, of coeffs[(9 p + j) * 3 + ch] *
+ *   Y_j(normals[3 i .. 3 i + 2]), the basis above on the normal as given; p = probe_index ? probe_index[i] : i, for i < m.
+ *   p >= n_probes: the host form refuses the call with RT_ERR_INVALID_ARGUMENT and writes nothing; the device form writes the quiet
+ *   NaN 0x7FC00000 to that element's three channels.  A NULL scene, coeffs, normals or output: RT_ERR_INVALID_ARGUMENT; then
+ *   RT_ERR_UNSUPPORTED for a multi-device scene (or 2^58 probes or normals); then RT_ERR_NO_DEVICE.  m = 0: RT_OK, nothing written.  The device form is
+ *   asynchronous, allocates nothing and keeps no state; the host form stages through scene-owned memory.
+ * Not served: stratified or low-discrepancy directions, hemispheres and lightmap texels, bands above 2,
+ *   probe visibility or depth moments, multi-device scenes. ---- */
+typedef struct rt_probe_opts {
+	uint64_t seed, sample_begin;
+	uint32_t samples_per_probe;  /* K >= 1 */
+	uint32_t sample_split;       /* S, 1 <= S <= K; no automatic value */
+	int32_t  render_method;      /* rt_render_method */
+	uint32_t max_depth, rr_threshold;
+	uint32_t convolve;           /* 0: radiance coefficients; 1: irradiance (bands scaled, above) */
+	uint32_t reserved[2];        /* 0 */
+} rt_probe_opts;
+/* seed 0, sample_begin 0, K 1024, S 64, MIS, max_depth 50, rr_threshold 3, convolve 0 */
+int rt_probe_opts_default(rt_probe_opts *out);
+int rt_probe_workspace_bytes(uint64_t n_probes, const rt_probe_opts *opts, uint64_t *bytes);
+int rt_probe_sh(rt_scene *scene, const float *positions /* 3 n */, uint64_t n_probes, const rt_probe_opts *opts,
+                float *out_coeffs /* n x 9 x 3 */, uint64_t *rays_shot_or_null);
+int rt_probe_sh_device(rt_scene *scene, const float *d_positions, uint64_t n_probes, const rt_probe_opts *opts, float *d_out_coeffs,
+                       void *d_workspace, uint64_t *d_rays_shot_or_null, void *hip_stream);
+int rt_probe_sh_eval(rt_scene *scene, const float *coeffs, uint64_t n_probes, const uint32_t *probe_index_or_null,
+                     const float *normals /* 3 m */, uint64_t m, float *out_rgb /* 3 m */);
+int rt_probe_sh_eval_device(rt_scene *scene, const float *d_coeffs, uint64_t n_probes, const uint32_t *d_probe_index_or_null,
+                            const float *d_normals, uint64_t m, float *d_out_rgb, void *hip_stream);
+
 /* ---- Firefly-robust frames (csrc/rt_robust.hip): a rank-trimmed mean of the chunk sums.  The integrator keeps the reference's
  * quirks, so one wild sample -- or one inf / NaN -- ends up in a pixel's mean, where no later stage can undo it.  The S
  * independent sums per pixel that a render at sample_split = S > 1 leaves in the scene's partial buffer (see the noise estimates

@@ -394,6 +394,25 @@ class LensCamera(C.Structure):  # rt_lens_camera
     ]
 
 
+# light probes (rt_probe_sh, rt_probe_sh_eval)
+class ProbeOpts(C.Structure):  # rt_probe_opts
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("sample_begin", C.c_uint64),
+        ("samples_per_probe", C.c_uint32),
+        ("sample_split", C.c_uint32),
+        ("render_method", C.c_int32),
+        ("max_depth", C.c_uint32),
+        ("rr_threshold", C.c_uint32),
+        ("convolve", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+PROBE_OPTIONS = tuple(n for n, _ in ProbeOpts._fields_ if n != "reserved")
+PROBE_TERMS = 27  # floats a probe: 9 basis functions x RGB
+
+
 NOISE_SHAPES = {"mean": "hw3", "variance": "hw", "lum_mean": "hw", "tile_error": "tiles", "summary": "summary"}
 NOISE_CHANNELS = tuple(NOISE_SHAPES)
 
@@ -671,6 +690,7 @@ EXPECTED_SIZES = {
     "rt_noise_result": (NoiseResult, 40),
     "rt_adaptive_result": (AdaptiveResult, 40),
     "rt_lens_camera": (LensCamera, 100),
+    "rt_probe_opts": (ProbeOpts, 48),
     "rt_robust_opts": (RobustOpts, 32),
     "rt_robust_buffers": (RobustBuffers, 40),
     "rt_denoise_opts": (DenoiseOpts, 48),
@@ -783,6 +803,12 @@ EXPORTED_SYMBOLS = [
     "rt_render_lens_aov",
     "rt_render_lens_aov_device",
     "rt_render_lens_denoised",
+    "rt_probe_opts_default",
+    "rt_probe_workspace_bytes",
+    "rt_probe_sh",
+    "rt_probe_sh_device",
+    "rt_probe_sh_eval",
+    "rt_probe_sh_eval_device",
     "rt_robust_opts_default",
     "rt_render_robust",
     "rt_render_robust_device",
@@ -848,6 +874,15 @@ def default_ao_opts(rays_per_pass=4, radius=0.0):
     """rt_ao_opts_default (include/rt_hip.h)."""
     o = AoOpts()
     o.rays_per_pass, o.radius = rays_per_pass, radius
+    return o
+
+
+def default_probe_opts(samples_per_probe=1024, sample_split=64, method=RT_METHOD_MIS, convolve=0, seed=0, sample_begin=0):
+    """rt_probe_opts_default (include/rt_hip.h)."""
+    o = ProbeOpts()
+    o.seed, o.sample_begin = seed, sample_begin
+    o.samples_per_probe, o.sample_split = samples_per_probe, sample_split
+    o.render_method, o.max_depth, o.rr_threshold, o.convolve = method, 50, 3, convolve
     return o
 
 

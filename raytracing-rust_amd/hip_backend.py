@@ -838,6 +838,47 @@ class HipScene:
         _check(lib().rt_render_lens_device(self._h, C.byref(camera), C.byref(opts), _dp(d_frame), _dp(d_chunk_sums), _vp(d_rays_ptr),
                                            C.c_void_p(stream)))
 
+    # ---- light probes (rt_probe_sh): L2 spherical-harmonic radiance at positions, projected on the device ----
+    def probe_sh(self, positions, **opts):
+        """rt_probe_sh: the 9 x RGB spherical-harmonic coefficients of the radiance arriving at each of the (n, 3) `positions`, under
+        probe_opts(**opts).  Returns (coeffs (n, 9, 3) f32, rays_shot).  convolve=1: irradiance coefficients."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        n = pos.shape[0]
+        out = np.zeros((n, 9, 3), dtype=np.float32)
+        rays = C.c_uint64()
+        _check(lib().rt_probe_sh(self._h, _p(pos, C.c_float), C.c_uint64(n), C.byref(probe_opts(**opts)), _p(out, C.c_float), C.byref(rays)))
+        return out, rays.value
+
+    def probe_sh_device(self, d_positions, n_probes, d_out, d_workspace, d_rays_ptr=None, stream=0, **opts):
+        """rt_probe_sh_device: asynchronous, DEVICE buffers of the scene's GPU -- d_positions 3 n f32, d_out 27 n f32, d_workspace
+        probe_workspace_bytes(n, **opts) bytes; allocates nothing, keeps no state."""
+        _check(lib().rt_probe_sh_device(self._h, _dp(d_positions), C.c_uint64(n_probes), C.byref(probe_opts(**opts)), _dp(d_out),
+                                        _vp(d_workspace), _vp(d_rays_ptr), C.c_void_p(stream)))
+
+    @staticmethod
+    def probe_workspace_bytes(n_probes, **opts):
+        """rt_probe_workspace_bytes (the module's probe_workspace_bytes)."""
+        return probe_workspace_bytes(n_probes, **opts)
+
+    def probe_sh_eval(self, coeffs, normals, probe_index=None):
+        """rt_probe_sh_eval: the colour each of the (m, 3) `normals` sees in the (n, 9, 3) `coeffs` -- of probe probe_index[i], or of
+        probe i without an index list -- as an (m, 3) f32 array."""
+        co = np.ascontiguousarray(coeffs, dtype=np.float32).reshape(-1, 9, 3)
+        nm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        idx = None if probe_index is None else np.ascontiguousarray(probe_index, dtype=np.uint32)
+        if idx is not None and idx.shape != (nm.shape[0],):
+            raise ValueError(f"probe_index must be one per normal: {idx.shape} for {nm.shape[0]} normals")
+        out = np.zeros((nm.shape[0], 3), dtype=np.float32)
+        _check(lib().rt_probe_sh_eval(self._h, _p(co, C.c_float), C.c_uint64(co.shape[0]), _p(idx, C.c_uint32), _p(nm, C.c_float),
+                                      C.c_uint64(nm.shape[0]), _p(out, C.c_float)))
+        return out
+
+    def probe_sh_eval_device(self, d_coeffs, n_probes, d_probe_index, d_normals, m, d_out, stream=0):
+        """rt_probe_sh_eval_device: asynchronous, DEVICE buffers; d_probe_index 0 / None: element i reads probe i.  An index past
+        the probes gives a quiet NaN in that element."""
+        _check(lib().rt_probe_sh_eval_device(self._h, _dp(d_coeffs), C.c_uint64(n_probes), _dp(d_probe_index, C.c_uint32), _dp(d_normals),
+                                             C.c_uint64(m), _dp(d_out), C.c_void_p(stream)))
+
     # ---- guides through a lens camera (rt_render_lens_aov) and the denoised lens frame (rt_render_lens_denoised) ----
     def render_lens_aov(self, camera, opts, channels=abi.AOV_CHAIN_CHANNELS, max_chain=None, fuzz_limit=0.0):
         """rt_render_lens_aov: the seven channels of render_aov_chain for the frame render_lens makes of an abi.LensCamera -- every
@@ -1291,6 +1332,19 @@ def ao_opts(**kw):
 def radiance_opts(**kw):
     """rt_radiance_opts_default with any of seed, sample_begin, samples_per_ray, render_method, max_depth, rr_threshold set."""
     return _opts(abi.RadianceOpts, "radiance", kw, abi.RADIANCE_OPTIONS)
+
+
+def probe_opts(**kw):
+    """rt_probe_opts_default with any of seed, sample_begin, samples_per_probe, sample_split, render_method, max_depth,
+    rr_threshold, convolve set."""
+    return _opts(abi.ProbeOpts, "probe", kw, abi.PROBE_OPTIONS)
+
+
+def probe_workspace_bytes(n_probes, **kw):
+    """rt_probe_workspace_bytes: the bytes probe_sh_device's workspace must hold for n_probes under probe_opts(**kw)."""
+    n = C.c_uint64()
+    _check(lib().rt_probe_workspace_bytes(C.c_uint64(n_probes), C.byref(probe_opts(**kw)), C.byref(n)))
+    return n.value
 
 
 def noise_opts(**kw):
